@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """bench.py -- env-steps/sec of the dynamics-regulated rollout hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]        (N > 1: launched by torch.distributed.run, one rank per GPU)
+
+A plain run sets up, runs W untimed and then exactly K timed steps, and prints the line; --dump-outputs DIR also writes what the last timed
+step computed (observations, actions, rewards, done flags, the GRU state, qpos / qvel; the networks' parameters for train_iter) as
+DIR/<name>.npy.  Inputs are seeded, so the same arguments give the same inputs on every run.  --full adds everything else listed below.
 
 One "step" = one batched env-step of the kin_poly.yml rollout over ENVS_PER_GPU = 4096 environments
 per GPU: kinematic policy (GRU+MLP) -> step_ar -> target FK -> UHC obs (784) + ZFilter
@@ -23,9 +27,11 @@ Workloads (all BASELINE configs[2] env-steps at 4096 envs/GPU unless noted):
                  data-parallel PPO + supervised update (agent_ar.py:271-297); value = env-steps/s of the whole iteration
 
 Prints ONE JSON line on rank 0 (see the task contract) with `roofline` (dominant kernel kp_step_queue_kernel = kp_step_kernel scheduled as jobs,
-live HIP-event launch durations; `traffic` / `valu` only from a rocprofv3 --pmc pass of THIS command and workload committed under profiles/)
-and, at N = 1, `mfma` (the policy GEMMs timed in isolation), secondary workloads and `cpu_baseline` (the fp64 oracle port in 35
-single-threaded worker processes, with its counted FLOPs per env-step).
+live HIP-event launch durations; `traffic` / `valu` only from a rocprofv3 --pmc pass of THIS command and workload committed under profiles/).
+With --full the timed region is repeated (--repeats, default 5: the line reports the median block), and the line adds the parity against the
+fp64 oracle (`parity_live`, `parity`, `episode_parity`), `mujoco_pin`, at N > 1 one training iteration per rank, and at N = 1 `mfma` (the policy
+GEMMs timed in isolation), secondary workloads, 8192-env runs, object scenes, training iterations and `cpu_baseline` (the fp64 oracle port
+in 35 single-threaded worker processes, with its counted FLOPs per env-step).
 """
 import argparse
 import json
@@ -124,10 +130,12 @@ def tracking_action(env):
     return a
 
 
-def rollout_steps(sampler, k, a_track=None, wild=False, follow_clip=False):
+def rollout_steps(sampler, k, a_track=None, wild=False, follow_clip=False, keep=None):
     """k batched env-steps without keeping the experience (identical work to VectorSampler.sample's loop body).
     wild: the eval_ar_policy.py --wild loop (:196-215): mean actions, an env that terminates early is put back on the kinematic
-    roll-out (ar_fail_safe) and keeps going, an env that finishes its clip starts it again."""
+    roll-out (ar_fail_safe) and keeps going, an env that finishes its clip starts it again.
+    keep (dict, optional): filled with the device tensors the LAST step hands its caller (--dump-outputs); no copy is made, so they are valid
+    until the engine steps again."""
     env, pol = sampler.env, sampler.policy
     n_early = torch.zeros((), dtype=torch.int64, device=env.device)
     env.done_count.zero_()
@@ -155,6 +163,9 @@ def rollout_steps(sampler, k, a_track=None, wild=False, follow_clip=False):
                 done = done & ~early
                 n_early += early.sum()
             sampler.obs = env.reset(done, policy_state=sampler.hx)        # finished envs: state, target, observation and the GRU state in one pass
+            if keep is not None and t == k - 1:
+                keep.update(action=action, cc_action=info["cc_action"], reward=info["custom_reward"], reward_terms=info["custom_info"], done=done,
+                            fail=info["fail"], percent=info["percent"], body_diff=info["body_diff"], obs=sampler.obs, hx=sampler.hx)
     return n_early if wild else env.done_count.to(torch.int64)[0]       # episodes ended: counted inside kp_sim_post_step
 
 
@@ -361,8 +372,9 @@ TRAIN_KEYS = ("T_sample", "T_update", "samples_per_s_per_gpu", "samples_per_iter
               "clips_drawn_per_iter", "clips_through_init_context_per_iter", "pool_exhausted", "update_tflops", "update_mfma_frac", "update_flops_per_iter", "episode_source")
 
 
-def run_workload(workload, device_index, seed, threads, steps, warmup, barrier=None, repeats=1):
-    """Build the engine for `workload`, run `warmup` untimed + `steps` timed env-steps.  Returns (record, env, policy, sampler, std)."""
+def run_workload(workload, device_index, seed, threads, steps, warmup, barrier=None, repeats=1, keep=None):
+    """Build the engine for `workload`, run `warmup` untimed + `steps` timed env-steps.  Returns (record, env, policy, sampler, std).
+    keep: see rollout_steps (filled by the last step of the last timed block)."""
     env, policy, sampler, std = build_engine(device_index, seed, threads, workload)
     a_track = None
     if workload in ("tracked", "wild_eval"):
@@ -376,14 +388,14 @@ def run_workload(workload, device_index, seed, threads, steps, warmup, barrier=N
     # `repeats` timed blocks of exactly `steps` env-steps each, every block bracketed by barrier + synchronize on both sides (the contract's timed region,
     # repeated inside one command so that the line carries its own spread).  The caller reports the median block.
     el_blocks, kern_blocks, done_blocks, n_launch = [], [], [], 0
-    for _ in range(max(1, repeats)):
+    for b in range(max(1, repeats)):
         env.sim.timing_reset()
         if barrier is not None:
             barrier()
         else:
             torch.cuda.synchronize()
         t0 = time.perf_counter()
-        n_done = rollout_steps(sampler, steps, a_track, wild, follow)
+        n_done = rollout_steps(sampler, steps, a_track, wild, follow, keep if b == max(1, repeats) - 1 else None)
         if barrier is not None:
             barrier()
         else:
@@ -527,11 +539,12 @@ def sampler_regime(device_index, seed, horizon=TRAIN_HORIZON, calls=4, warm=2, t
     return out
 
 
-def train_iteration(device_index, seed, horizon, iters, warm, barrier=None, threads=64, objects=False, rank=0, cache_init_context=False, model_opts=None):
+def train_iteration(device_index, seed, horizon, iters, warm, barrier=None, threads=64, objects=False, rank=0, cache_init_context=False, model_opts=None, keep=None):
     """`iters` timed AgentAR.optimize_policy calls (after `warm` untimed) at ENVS_PER_GPU x horizon env-steps per rank, the way
     scripts/train_ar_policy.py runs them: every episode draws its clip from a StateARDataset (adaptive take sampling, freq_dict feedback) and goes
     through init_context (context GRU over the 100-frame clip -> init_qpos / init_qvel) -- inside the timed region, at whatever failure rate the
-    random-init networks produce.  objects=False: BASELINE configs[2] (object-free takes); True: configs[3]'s four action classes with free objects."""
+    random-init networks produce.  objects=False: BASELINE configs[2] (object-free takes); True: configs[3]'s four action classes with free objects.
+    keep (dict, optional): filled with the networks' parameters after the last iteration, flattened on the host (--dump-outputs)."""
     from kinpoly_amd.agent import AgentAR
     from kinpoly_amd import dataset as D
     from kinpoly_amd import sim as kpsim
@@ -573,9 +586,32 @@ def train_iteration(device_index, seed, horizon, iters, warm, barrier=None, thre
                                                          "adaptive take sampling + init_context per episode, pool_depth 4",
            "update_tflops": upd_flops / (tu / iters) / 1e12, "update_mfma_frac": upd_flops / (tu / iters) / 1e12 / MFMA_FP32_PEAK_TFLOPS,
            "update_flops_per_iter": upd_flops}
+    if keep is not None:
+        keep.update(policy_params=torch.cat([p.detach().reshape(-1) for p in agent.policy_net.parameters()]).cpu().numpy(),
+                    value_params=torch.cat([p.detach().reshape(-1) for p in agent.value_net.parameters()]).cpu().numpy())
     del agent, fk_sim
     torch.cuda.empty_cache()
     return rec
+
+
+DUMP_LIMIT_BYTES = 60 << 20         # --dump-outputs writes at most this much array data (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(path, arrays, seed=0):
+    """--dump-outputs: each array as <path>/<name>.npy, float64 kept, everything else (float32, bool, int) as float32.  The smallest arrays are
+    written whole first; an array larger than its share of what is left of DUMP_LIMIT_BYTES is replaced by a fixed, seeded sample of its
+    flattened elements (same indices from run to run, in ascending order), so that two builds can be compared output for output."""
+    os.makedirs(path, exist_ok=True)
+    items = sorted(((k, np.asarray(v)) for k, v in arrays.items()), key=lambda kv: kv[1].size)
+    left = DUMP_LIMIT_BYTES
+    for i, (name, a) in enumerate(items):
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        share = left // (len(items) - i) // a.itemsize
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def relaunch_under_torchrun(n_gpus):
@@ -608,10 +644,14 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads and the GEMM probe (profiling runs)")
     ap.add_argument("--workload", choices=tuple(WORKLOAD_DESC), default="tracked")
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps env-steps inside this command; value / ms_per_step = the median block (rollout workloads)")
+    ap.add_argument("--repeats", type=int, default=None, help="timed blocks of --steps env-steps inside this command; value / ms_per_step = the median block "
+                                                               "(rollout workloads; default 1, 5 with --full)")
     ap.add_argument("--policy-ckpt", default=None, help="kinematic policy checkpoint (reference layout) of --workload trained")
     ap.add_argument("--cc-ckpt", default=None, help="UHC checkpoint (reference layout: weights + ZFilter) of --workload trained")
     ap.add_argument("--no-parity-live", action="store_true", help="skip the live one-substep parity sample against the fp64 oracle (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: repeated timed blocks, secondary workloads, GEMM probe, 8192-env runs, "
+                                                        "object scenes, training iterations, parity against the fp64 oracle, MuJoCo pin, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, rank 0)")
     args = ap.parse_args()
     global POLICY_CKPT, CC_CKPT
     POLICY_CKPT, CC_CKPT = args.policy_ckpt, args.cc_ckpt
@@ -620,6 +660,8 @@ def main():
         args.steps = 3 if train else 60
     if args.warmup is None:
         args.warmup = 1 if train else 20
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a HIP device (no CPU fallback)")
@@ -671,12 +713,18 @@ def main():
         dist.all_gather_object(devices, me)
     distinct = len({(d["uuid"], d["pci_bus_id"], d["pci_device_id"]) for d in devices})
 
+    keep = {} if args.dump_outputs else None
     if train:
-        rec = train_iteration(local_rank, 4, TRAIN_HORIZON, args.steps, args.warmup, barrier, args.threads_per_env, rank=rank)
+        rec = train_iteration(local_rank, 4, TRAIN_HORIZON, args.steps, args.warmup, barrier, args.threads_per_env, rank=rank, keep=keep)
         env = policy = sampler = None
         std = np.load(os.path.join(ROOT, "tests", "golden", "standing_neutral.npz"))
     else:
-        rec, env, policy, sampler, std = run_workload(args.workload, local_rank, 4 + rank, args.threads_per_env, args.steps, args.warmup, barrier, args.repeats)
+        rec, env, policy, sampler, std = run_workload(args.workload, local_rank, 4 + rank, args.threads_per_env, args.steps, args.warmup, barrier, args.repeats, keep)
+        if keep is not None:        # the state the last timed step left, read before anything else steps the engine
+            keep.update(qpos=env.sim.get("qpos"), qvel=env.sim.get("qvel"))
+    if keep is not None and rank == 0:
+        dump_outputs(args.dump_outputs, {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else v) for k, v in keep.items()})
+        keep = None
     # per timed block: max over ranks; the line reports the MEDIAN block (its ms_per_step x steps is that block's bracketed wall time) and the spread
     blocks = list(rec.get("elapsed_blocks", [rec["elapsed"]]))
     per_rank_ms = [float(np.median(blocks)) / args.steps * 1e3]
@@ -703,12 +751,12 @@ def main():
                 "lean_max_contacts": int(env.model.get_option("lean_max_contacts")),
                 "schedule": ("5+5+5 substeps, issue priority by remaining substeps (queue_prio 3), late envs kept by their wave (queue_late)" if (env.model.get_option("lean_queue") and env.model.get_option("job_auto") and args.workload != "objects" and "KP_JOB_SCHEDULE" not in os.environ)
                              else f"substeps_per_job {spj}, job_taper {int(env.model.get_option('job_taper'))}, queue_prio {int(env.model.get_option('queue_prio'))}, queue_late {int(env.model.get_option('queue_late'))}" + (f", KP_JOB_SCHEDULE={os.environ['KP_JOB_SCHEDULE']}" if "KP_JOB_SCHEDULE" in os.environ else ""))}
-        if rank == 0 and world == 1 and not args.no_parity_live and args.workload in ("tracked", "random_init", "objects"):
+        if args.full and rank == 0 and world == 1 and not args.no_parity_live and args.workload in ("tracked", "random_init", "objects"):
             try:
                 live = parity_live(env, sampler, args.workload, getattr(env, "_a_track", None))
             except Exception as ex:
                 live = {"error": f"{type(ex).__name__}: {ex}"[:300]}
-    if world > 1 and not train and not args.no_secondary:
+    if args.full and world > 1 and not train and not args.no_secondary:
         # the Amdahl term of a training job on N GPUs: one whole optimize_policy (sampling + all-gather of advantages / returns + data-parallel update with
         # gradient all-reduces) timed on every rank, max over ranks
         del sampler, env, policy
@@ -791,15 +839,14 @@ def main():
             "hessian_factorisations_per_substep": float((diag[:, 3] >> 8).mean() / 15.0),
             "bad_envs": int(((diag[:, 2] & 255) != 0).sum()), "newton_cap_hits": int((diag[:, 2] >> 8).sum()),
             "episodes_ended_per_step_frac": rec["n_done"] / (ENVS_PER_GPU * args.steps),
-            "parity_live": live,
-            "parity": parity_summary(args.workload),
-            "mujoco_pin": mujoco_pin_report(),
             # per-env shader-clock cycles of the last launch (kp_sim_launch_cost): what the launch would take if its waves were perfectly
             # packed on the resident slots vs its longest env
             "launch_balance": {"substeps_per_job": spj, "slots": slots, "sum_env_cycles_over_slots_ms": float(cost.sum() / slots / 2.38e6),
                                "longest_env_ms": float(cost.max() / 2.38e6), "median_env_ms": float(np.median(cost) / 2.38e6)},
         }
-        if world == 1 and not args.no_secondary:
+        if args.full:
+            out.update(parity_live=live, parity=parity_summary(args.workload), mujoco_pin=mujoco_pin_report())
+        if args.full and world == 1 and not args.no_secondary:
             try:
                 out["mfma"] = policy_gemm_probe(env, policy)
             except Exception as ex:
@@ -860,12 +907,12 @@ def main():
             del sampler, env, policy
             if train_n is not None:
                 out["train_iteration"] = {f"4096x{TRAIN_HORIZON}_x{world}gpus": train_n}
-        if world == 1 and not args.no_parity_live and not args.no_secondary:
+        if args.full and world == 1 and not args.no_parity_live and not args.no_secondary:
             try:
                 out["episode_parity"] = episode_parity_live()
             except Exception as ex:
                 out["episode_parity"] = {"error": f"{type(ex).__name__}: {ex}"[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             workers = min(35, os.cpu_count() or 1)
             try:
                 out["cpu_baseline"] = cpu_baseline_workers(std, workers) if workers > 1 else cpu_baseline(std)

@@ -231,6 +231,24 @@ def test_python_model_compiler_and_hull_graph_against_qhull():
         assert len(mine) == 2 * (3 * len(v) - 6)          # a triangulated convex polyhedron: E = 3 V - 6
 
 
+def test_hull_graph_of_the_shipped_blobs_against_qhull():
+    """On the hull vertices stored in both shipped blobs: hull_graph rebuilds the stored neighbour lists exactly (order included), and their
+    edge set is qhull's ("Qt") on all 24 hulls -- the part of the test above that needs no model files outside the repository."""
+    from kinpoly_amd import model_compiler as mc
+    for path in (mc.DEFAULT_KPM, mc.STEP_KPM):
+        m = read_kpm(path)
+        adr, va, nb_ = m["vert_adr"], m["vert_nbr_adr"], m["vert_nbr"]
+        verts = m["verts"].reshape(-1, 3)
+        assert len(adr) == 25
+        for b in range(24):
+            v = verts[adr[b]:adr[b + 1]]
+            stored = [[int(j) for j in nb_[va[adr[b] + i]:va[adr[b] + i + 1]]] for i in range(len(v))]
+            assert [list(map(int, r)) for r in mc.hull_graph(v)] == stored, f"{os.path.basename(path)} hull {b}"
+            qh = mc.hull_graph_qhull(v)
+            assert {(i, j) for i in range(len(v)) for j in stored[i]} == {(i, j) for i in range(len(v)) for j in qh[i]}, f"{os.path.basename(path)} hull {b}"
+            assert sum(map(len, stored)) == 2 * (3 * len(v) - 6)          # a triangulated convex polyhedron: E = 3 V - 6
+
+
 def test_parity_tool_scene_generators_are_deterministic_and_fp32_valued():
     """tools/_scenes.py feeds the parity sweeps (substep_parity.py, obj_fuzz_trace.py): same seed -> same scenes, every number already an fp32 value
     (both sides of a sweep must get identical inputs), unit root quaternions, objects only where the scene's action class puts them."""
@@ -276,3 +294,26 @@ def test_profile_stamps_null_stale_figures(tmp_path, monkeypatch):
     assert got["substeps"] == 92160 and got["contact_set_diffs"] == 22 and got["same_entities_other_hull_vertex"] == 13 and got["max_same_set_dqpos"] == 4.3e-07
     (tmp_path / "substep_parity_bench.log").write_text(body)             # no stamp at all (a log of an earlier round): stale
     assert bench.parity_summary("tracked")["stale"] is True
+
+
+def test_bench_dump_outputs_types_cap_and_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array lands as <name>.npy in float32 (float64 kept), small arrays whole, and an array past its share of the
+    byte cap is replaced by a seeded sample of its elements that is the same on every run (two builds compare output for output)."""
+    import importlib
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    rng = np.random.default_rng(0)
+    arrays = {"done": rng.random(64) < 0.5, "qpos": rng.random((8, 4)), "obs": rng.random((100, 50)).astype(np.float32), "steps": np.arange(16, dtype=np.int32)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in arrays}
+    assert got["qpos"].dtype == np.float64 and np.array_equal(got["qpos"], arrays["qpos"])
+    assert got["done"].dtype == np.float32 and np.array_equal(got["done"], arrays["done"].astype(np.float32))
+    assert got["steps"].dtype == np.float32 and np.array_equal(got["steps"], np.arange(16))
+    assert got["obs"].dtype == np.float32 and 0 < got["obs"].size < arrays["obs"].size
+    flat = arrays["obs"].ravel()
+    assert np.array_equal(got["obs"], flat[np.isin(flat, got["obs"])])          # elements of the array, in their original order
+    assert sum(v.nbytes for v in got.values()) <= 4096
+    for k in arrays:
+        assert np.array_equal(got[k], np.load(tmp_path / "b" / (k + ".npy")))

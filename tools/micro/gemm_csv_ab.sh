@@ -1,6 +1,6 @@
 export TMPDIR=/tmp
 for r in 1 2; do for f in "" tools/micro/tunableop_candidate.csv; do
-  KP_TUNED_GEMMS=$f timeout -s KILL 300 python bench.py --no-cpu-baseline 2>/dev/null | python -c "
+  KP_TUNED_GEMMS=$f timeout -s KILL 300 python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 t=d['train_iteration']['4096x24']

@@ -20,8 +20,8 @@ python tools/micro/occupancy_premise.py > $E/occupancy_premise.log 2>&1
 python tools/micro/queue_timeline.py > $E/queue_timeline.log 2>&1
 python tools/micro/queue_policy_sim.py > $E/queue_policy_sim.log 2>&1
 python tools/micro/newton_profile.py > $E/newton_profile.log 2>&1
-python bench.py > $E/bench_default.json 2> $E/bench_default.err
-KP_BENCH_SHARED_DEVICE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29557 bench.py --gpus 2 --steps 20 --warmup 5 2> $E/bench_2rank.err | grep '^{' > $E/bench_2rank_shared_device.json     # gloo prints its own lines on stdout
+python bench.py --full > $E/bench_default.json 2> $E/bench_default.err
+KP_BENCH_SHARED_DEVICE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29557 bench.py --gpus 2 --steps 20 --warmup 5 --full 2> $E/bench_2rank.err | grep '^{' > $E/bench_2rank_shared_device.json     # gloo prints its own lines on stdout
 tools/profile_bench.sh tracked > $E/profile_tracked.log 2>&1
 cp gpurun_out/r02_prof/summary/* $E/ 2>/dev/null
 cp gpurun_out/r02_prof/tracked/stats/stats_kernel_stats.csv $E/r02_kernel_stats_tracked_full.csv 2>/dev/null

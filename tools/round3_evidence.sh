@@ -32,10 +32,10 @@ cp gpurun_out/r03_prof/summary/* $E/ 2>/dev/null
 mkdir -p profiles/r03 && cp gpurun_out/r03_prof/summary/pmc_bench_*.json profiles/r03/ 2>/dev/null      # bench.py reads the PMC summaries of ITS OWN command from there
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r03_prof/update -o stats -- python tools/update_profile.py > $E/update_profile.log 2>&1
 cp gpurun_out/r03_prof/update/stats_kernel_stats.csv $E/r03_kernel_stats_update.csv 2>/dev/null
-( time python bench.py > $E/bench_default.json 2> $E/bench_default.err ) 2> $E/bench_default.time
-python bench.py --workload objects --no-secondary --no-cpu-baseline > $E/bench_objects.json 2> $E/bench_objects.err
+( time python bench.py --full > $E/bench_default.json 2> $E/bench_default.err ) 2> $E/bench_default.time
+python bench.py --workload objects --full --no-secondary --no-cpu-baseline > $E/bench_objects.json 2> $E/bench_objects.err
 KP_BENCH_FORCE_PG=1 MASTER_PORT=29561 python bench.py --workload train_iter --steps 2 --warmup 1 > $E/bench_train_iter_1rank_nccl.json 2> $E/bench_train_iter.err
-KP_BENCH_SHARED_DEVICE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29557 bench.py --gpus 2 --steps 20 --warmup 5 2> $E/bench_2rank.err | grep '^{' > $E/bench_2rank_shared_device.json     # gloo prints its own lines on stdout
+KP_BENCH_SHARED_DEVICE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29557 bench.py --gpus 2 --steps 20 --warmup 5 --full 2> $E/bench_2rank.err | grep '^{' > $E/bench_2rank_shared_device.json     # gloo prints its own lines on stdout
 find gpurun_out/r03_prof -type f -size +2000k -delete
 for f in pytest_gpu smoke floor_fuzz obj_fuzz contact_compare obj_bench obj_profile_phases obj_profile_newton update_bench; do echo "== $f"; grep -v Warn $E/$f.log | tail -4 | cut -c1-400; done
 cut -c1-600 $E/bench_default.json

@@ -41,10 +41,10 @@ $T 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r04_pr
 cp gpurun_out/r04_prof/update/stats_kernel_stats.csv $E/r04_kernel_stats_update.csv 2>/dev/null
 $T 300 python tools/update_bench.py > $E/update_bench.log 2>&1
 # the driver's commands
-( time $T 600 python bench.py > $E/bench_default.json 2> $E/bench_default.err ) 2> $E/bench_default.time
-$T 300 python bench.py --workload objects --no-secondary --no-cpu-baseline > $E/bench_objects.json 2> $E/bench_objects.err
+( time $T 600 python bench.py --full > $E/bench_default.json 2> $E/bench_default.err ) 2> $E/bench_default.time
+$T 300 python bench.py --workload objects --full --no-secondary --no-cpu-baseline > $E/bench_objects.json 2> $E/bench_objects.err
 KP_BENCH_FORCE_PG=1 MASTER_PORT=29561 $T 300 python bench.py --workload train_iter --steps 2 --warmup 1 > $E/bench_train_iter_1rank_nccl.json 2> $E/bench_train_iter.err
-KP_BENCH_SHARED_DEVICE=1 $T 600 python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline 2> $E/bench_2rank.err | grep '^{' > $E/bench_2rank_self_launched_shared_device.json
+KP_BENCH_SHARED_DEVICE=1 $T 600 python bench.py --gpus 2 --steps 20 --warmup 5 --full --no-cpu-baseline 2> $E/bench_2rank.err | grep '^{' > $E/bench_2rank_self_launched_shared_device.json
 # the three scripts end to end
 ( $T 400 python scripts/train_ar_policy.py --num_envs 4096 --iters 3 --horizon 24; $T 400 python scripts/train_ar_policy.py --num_envs 4096 --iters 3 --horizon 24 --cache_init_context; \
   $T 400 python scripts/train_ar_policy.py --num_envs 4096 --iters 2 --horizon 99; $T 300 python scripts/train_uhc.py --iters 2; $T 300 python scripts/eval_ar_policy.py ) 2>&1 | grep -v "amdgpu.ids\|Warning\|sched_" > $E/scripts_run.log

@@ -26,7 +26,7 @@ $T 300 python tools/sampler_regime.py --profile 2>/dev/null > $E/sampler_regime_
 $T 200 python tools/obj_bench.py > $E/obj_bench.log 2>&1
 $T 200 python tools/phase_profile.py > $E/phase_cycles.log 2>&1
 # the constraint solve's starting point (model option warm_extrap): beta sweep on three workloads, 60 timed steps each
-( for we in 0 0.5 0.75 1; do for wl in objects tracked random_init wild_eval; do KP_WARM_EXTRAP=$we $T 300 python bench.py --workload $wl --steps 60 --warmup 20 --no-secondary --no-cpu-baseline --no-parity-live 2>/dev/null | python -c "
+( for we in 0 0.5 0.75 1; do for wl in objects tracked random_init wild_eval; do KP_WARM_EXTRAP=$we $T 300 python bench.py --workload $wl --steps 60 --warmup 20 --full --no-secondary --no-cpu-baseline --no-parity-live 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$wl warm_extrap=$we value %.0f launch_ms %.4f newton/substep %.3f fact/substep %.3f' % (d['value'], d['roofline']['launch_ms'], d['newton_iters_per_substep'], d['hessian_factorisations_per_substep']))"
@@ -40,10 +40,10 @@ $T 600 python tools/launches_per_step.py tracked $E/lps_tracked > $E/launches_pe
 $T 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r05_prof/update -o stats -- python tools/update_profile.py > $E/update_profile.log 2>&1
 cp gpurun_out/r05_prof/update/stats_kernel_stats.csv $E/r05_kernel_stats_update.csv 2>/dev/null
 # the driver's commands
-( time $T 900 python bench.py > $E/bench_default.json 2> $E/bench_default.err ) 2> $E/bench_default.time
-$T 300 python bench.py --workload objects --no-secondary --no-cpu-baseline > $E/bench_objects.json 2> $E/bench_objects.err
+( time $T 900 python bench.py --full > $E/bench_default.json 2> $E/bench_default.err ) 2> $E/bench_default.time
+$T 300 python bench.py --workload objects --full --no-secondary --no-cpu-baseline > $E/bench_objects.json 2> $E/bench_objects.err
 KP_BENCH_FORCE_PG=1 MASTER_PORT=29561 $T 300 python bench.py --workload train_iter --steps 2 --warmup 1 > $E/bench_train_iter_1rank_nccl.json 2> $E/bench_train_iter.err
-KP_BENCH_SHARED_DEVICE=1 $T 600 python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline 2> $E/bench_2rank.err | grep '^{' > $E/bench_2rank_self_launched_shared_device.json
+KP_BENCH_SHARED_DEVICE=1 $T 600 python bench.py --gpus 2 --steps 20 --warmup 5 --full --no-cpu-baseline 2> $E/bench_2rank.err | grep '^{' > $E/bench_2rank_self_launched_shared_device.json
 $T 60 python bench.py --gpus 4 > $E/bench_gpus4_on_one_gpu.log 2>&1; echo "exit code $?" >> $E/bench_gpus4_on_one_gpu.log
 ( $T 400 python scripts/train_ar_policy.py --num_envs 4096 --iters 3 --horizon 24; $T 400 python scripts/train_ar_policy.py --num_envs 4096 --iters 2 --horizon 24 --update_dtype fp64; \
   $T 300 python scripts/train_uhc.py --iters 2; $T 300 python scripts/eval_ar_policy.py ) 2>&1 | grep -v "amdgpu.ids\|Warning\|sched_" > $E/scripts_run.log

@@ -26,11 +26,11 @@ cp gpurun_out/r06_prof/summary/* $E/ 2>/dev/null
 cp gpurun_out/r06_prof/summary/pmc_bench_*.json profiles/r06/ 2>/dev/null      # bench.py reads the PMC summaries of ITS OWN command from there
 $T 200 python tools/phase_profile.py > $E/phase_cycles.log 2>&1
 # the driver's commands
-( time $T 900 python bench.py > $E/bench_default.json 2> $E/bench_default.err ) 2> $E/bench_default.time
-$T 300 python bench.py --workload objects --no-secondary --no-cpu-baseline > $E/bench_objects.json 2> $E/bench_objects.err
-KP_LEAN_QUEUE=0 $T 300 python bench.py --workload tracked --no-secondary --no-cpu-baseline --no-parity-live > $E/bench_tracked_full_layout.json 2> /dev/null
+( time $T 900 python bench.py --full > $E/bench_default.json 2> $E/bench_default.err ) 2> $E/bench_default.time
+$T 300 python bench.py --workload objects --full --no-secondary --no-cpu-baseline > $E/bench_objects.json 2> $E/bench_objects.err
+KP_LEAN_QUEUE=0 $T 300 python bench.py --workload tracked --full --no-secondary --no-cpu-baseline --no-parity-live > $E/bench_tracked_full_layout.json 2> /dev/null
 KP_BENCH_FORCE_PG=1 MASTER_PORT=29561 $T 300 python bench.py --workload train_iter --steps 2 --warmup 1 > $E/bench_train_iter_1rank_nccl.json 2> $E/bench_train_iter.err
-KP_BENCH_SHARED_DEVICE=1 $T 600 python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline 2> $E/bench_2rank.err | grep '^{' > $E/bench_2rank_self_launched_shared_device.json
+KP_BENCH_SHARED_DEVICE=1 $T 600 python bench.py --gpus 2 --steps 20 --warmup 5 --full --no-cpu-baseline 2> $E/bench_2rank.err | grep '^{' > $E/bench_2rank_self_launched_shared_device.json
 ( $T 400 python scripts/train_ar_policy.py --num_envs 4096 --iters 8 --horizon 24 --min_batch_size 10000; $T 400 python scripts/train_ar_policy.py --num_envs 4096 --iters 2 --horizon 24 --update_dtype fp64; \
   $T 300 python scripts/train_uhc.py --iters 2; $T 300 python scripts/eval_ar_policy.py ) 2>&1 | grep -v "amdgpu.ids\|Warning\|sched_" | cut -c1-1200 > $E/scripts_run.log
 $T 300 python tools/soak.py 120 > $E/soak.log 2>&1

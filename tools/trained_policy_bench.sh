@@ -19,7 +19,7 @@ rows=[json.loads(l) for l in open("$O/ar.log")]; it=[x for x in rows if "iter" i
 print("kinematic policy: iter 0 avg_reward %.3f fail_rate %.4f -> iter %d avg_reward %.3f fail_rate %.4f" % (it[0]["avg_reward"], it[0]["fail_rate"], it[-1]["iter"], it[-1]["avg_reward"], it[-1]["fail_rate"]))
 PY
 for wl in trained tracked; do
-  $T 300 python bench.py --workload $wl --policy-ckpt $CK/ar.p --cc-ckpt $CK/uhc.p --no-secondary --no-cpu-baseline > $O/bench_$wl.json 2> $O/bench_$wl.err
+  $T 300 python bench.py --workload $wl --policy-ckpt $CK/ar.p --cc-ckpt $CK/uhc.p --full --no-secondary --no-cpu-baseline > $O/bench_$wl.json 2> $O/bench_$wl.err
 done
 python - <<PY
 import json
