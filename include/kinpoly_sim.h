@@ -77,12 +77,14 @@ void kp_model_free(kp_model*);
  * "queue_heavy" (default 160; 0 = off): a wave whose job ran at more than that percentage of the launch's mean time per substep keeps its env and runs the
  * env's next job itself instead of queueing it -- the costliest envs are the ones a launch ends on, and with two envs per slot every trip through the
  * FIFO costs them about one job's length of waiting (objects workload 6.49 -> 5.78 ms per launch; bit-identical results);
- * "lean_queue" (0/1, default 1): floor scenes' queue launches run on the lean LDS layout (12 784 B per env: 12 envs per CU = three waves per SIMD instead of 8 = two;
- * same results bit for bit).  Its defaults, unless the caller sets the option: jobs of 5 + 5 + 5 substeps, "queue_late" (default -1 = automatic: on with the lean
- * layout): an env whose first job had to wait for a slot is never queued again, its wave runs its later jobs itself; "queue_prio" (default -1 = automatic: 3 with
- * the lean layout, else 0): a wave's issue priority (s_setprio) -- 1 envs known to be heavy, 2 by the env's remaining jobs, 3 by its remaining substeps, re-set at
- * every substep.  "lean_max_contacts" (<= 24): a lean job that finds more contacts in a substep hands the env (before it has stored anything) to a second kernel
- * on the full layout; "lean_adaptive" (0/1, default 1): when more than 1 / 64 of the envs did so, the next 64 control steps run on the full layout (kp_sim_lean_state).
+ * "lean_queue" (0/1, default 1): floor scenes' queue launches run on the lean LDS layout (12 784 B per env: 12 envs per CU = three waves per SIMD instead of
+ * 8 = two; same results bit for bit), in stale mode only: with "stale_kinematics" = 0 a substep's constraint reference sits in words the lean layout gives to the
+ * bias forces of the same substep, so those scenes run the full layout.  Its defaults, unless the caller sets the option: jobs of 5 + 5 + 5 substeps,
+ * "queue_late" (default -1 = automatic: on with the lean layout): an env whose first job had to wait for a slot is never queued again, its wave runs its later
+ * jobs itself; "queue_prio" (default -1 = automatic: 3 with the lean layout, else 0): a wave's issue priority (s_setprio) -- 1 envs known to be heavy, 2 by the
+ * env's remaining jobs, 3 by its remaining substeps, re-set at every substep.  "lean_max_contacts" (<= 24): a lean job that finds more contacts in a substep
+ * hands the env (before it has stored anything) to a second kernel on the full layout; "lean_adaptive" (0/1, default 1): when more than 1 / 64 of the envs did
+ * so, the next 64 control steps run on the full layout (kp_sim_lean_state).
  * "lds_pad" (bytes): allocate at least that much LDS per env (experiments: fewer envs per CU with the same binary);
  * "lpt_order" (1 / 0 / -1 = default: on when free objects are simulated): longest-env-first order of the workgroups (plain launch) or of the
  * envs' first jobs in the FIFO, from the previous control step's per-env cycles;
@@ -349,11 +351,12 @@ int kp_sim_diag(kp_sim*, int32_t* out_host);
  * (launch / queue order only: results do not depend on it). */
 int kp_sim_launch_cost(kp_sim*, uint32_t* out_host);
 
-/* Floor scenes' job queue: which LDS layout the control-step launches run on.  out3[0] = 1 when the next queue launch would use the lean layout (12 envs per CU,
- * 24 contact slots; model option "lean_queue"), out3[1] = how many times so far the handle has fallen back to the full layout for 64 launches because more than
- * 1 / 64 of the envs needed more contact slots than the lean layout has (their jobs are re-run by a second kernel: cheaper to run everything on the full layout
- * then; model option "lean_adaptive" = 0 keeps the lean layout regardless), out3[2] = control-step launches so far.  Host arithmetic only; no reference
- * counterpart (launch policy: results do not depend on the layout). */
+/* Floor scenes' job queue: which LDS layout the control-step launches run on.  out3[0] = 1 when the next control step, with the substep count of the last one
+ * (15 before any), would launch the job queue on the lean layout (12 envs per CU, 24 contact slots; model option "lean_queue"): 0 with one workgroup per env
+ * (no more envs than slots), in fresh mode ("stale_kinematics" = 0) and during a fallback; out3[1] = how many times so far the handle has fallen back to the
+ * full layout for 64 launches because more than 1 / 64 of the envs needed more contact slots than the lean layout has (their jobs are re-run by a second
+ * kernel: cheaper to run everything on the full layout then; model option "lean_adaptive" = 0 keeps the lean layout regardless), out3[2] = control-step
+ * launches so far.  Host arithmetic only; no reference counterpart (launch policy: results do not depend on the layout). */
 int kp_sim_lean_state(kp_sim*, int32_t* out3);
 
 /* the job sizes kp_sim_step_ctrl uses for a control step of n_substeps when it schedules through the job queue (host arithmetic, no

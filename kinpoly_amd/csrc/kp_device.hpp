@@ -102,7 +102,8 @@ struct __attribute__((aligned(16))) EnvLds {
 //   * the contact residuals jar3 live in the words of xquat, dead once collide() has run: the read-outs (xpos, xquat, xipos of the control step's last forward
 //     pass) are stored right after the last substep's collision pass instead of at the job's end;
 //   * the bias forces handed up the tree (pAa) live in the words of jv3 | lim_jv, dead during every factorisation / solve (the object kernel's Schur columns use
-//     the same gap); their zero record is re-written at the top of a solve;
+//     the same gap) in stale mode only: in fresh mode make_constraint writes aref there before the substep's aba_solve, so the lean layout serves stale mode
+//     alone (kp_sim.hip: lean_eligible); their zero record is re-written at the top of a solve;
 //   * no copy of the dof armature: the eliminations read it folded into `extra` (same sum, formed once), the two products with M read the model table;
 //   * the stable-PD position error rides in lim_jar (dead outside the Newton solve), a_{k-2} of warm_extrap in the env's HBM row (kp_sim: warm2);
 //   * sv without the two object slots.

@@ -58,7 +58,8 @@ struct kp_sim {
     unsigned ovf_last = 0;            // the most recent count that has arrived: sizes the overflow kernel's grid (an empty 2048-workgroup launch costs 34 us)      // job FIFO of kp_step_queue_kernel
     float* spd_next = nullptr;                        // [N, 80] torque hand-over between the jobs of a control step
     int jobq_cap = 0, wave_slots = 2048;
-    int q_nsub = -1, q_obj = -1;                      // what the queue's "heavy job" yardstick (jobctr[32..33] -> [48..49]) was measured on
+    int q_nsub = -1, q_layout = -1;                   // what the queue's "heavy job" yardstick (jobctr[32..33] -> [48..49]) was measured on
+    int last_nsub = 15;                               // substeps of the last control step (kp_sim_lean_state)
     unsigned long long* prof = nullptr;
     float* dbg_contacts = nullptr;
     float *obj_qpos = nullptr, *geoms = nullptr;      // [N,35], [N,8,17]
@@ -232,24 +233,99 @@ int job_schedule(int nsub, int spj, int taper, int* sizes) {
     return parts;
 }
 
+// The lean layout (EnvLdsLean) serves floor scenes in stale mode only: its pAa shares words with jv3 | lim_jv, which in fresh mode (stale_kinematics = 0)
+// hold make_constraint's aref while the substep's aba_solve writes pAa (kp_device.hpp).  P.stale: the value the kernel receives.
+bool lean_eligible(const kp_sim& s) { return !s.has_objects && s.model->lean_queue && s.model->threads == 64 && s.P.stale; }
+
+// resident envs per CU: LDS is allocated in 1 280-byte granules, 128 per CU (tools/micro/lds_granule_probe.hip); the register budgets allow 8 waves per CU
+// (full layout, <= 256 VGPRs) and 12 (lean layout, 168 VGPRs)
+int envs_per_cu(size_t lds_bytes, int reg_cap) { return std::min(reg_cap, 128 / (int)((lds_bytes + 1279) / 1280)); }
+
+// the adaptive lean / full fallback (kp_sim::ovf_host): take the overflow counts that have arrived; a failed query ends the slot's wait and fails the step
+int poll_overflow(kp_sim* s) {
+    for (int k = 0; k < 2; k++) {
+        if (!s->ovf_pending[k]) continue;
+        const hipError_t e = hipEventQuery(s->ovf_ev[k]);
+        if (e == hipErrorNotReady) continue;
+        s->ovf_pending[k] = false;
+        if (e != hipSuccess) return fail(std::string("hipEventQuery(ovf_ev): ") + hipGetErrorString(e));
+        s->ovf_last = s->ovf_host[k];
+        if ((size_t)s->ovf_host[k] * 64 > (size_t)s->n) { s->lean_off_until = s->launch_index + 64; s->lean_fallbacks++; }
+    }
+    return 0;
+}
+
+enum Layout { FULL = 0, OBJECTS = 1, LEAN = 2 };      // EnvLds, EnvLdsObj, EnvLdsLean
+// What one launch_step runs, from the handle's options and state alone (no HIP calls, no writes): launch_step launches it, kp_sim_lean_state reports it.
+struct StepPlan {
+    bool queue, lpt;      // the job queue (kp_step_queue_kernel on `slots` resident waves) instead of one workgroup per env; k_lpt_order first
+    Layout layout;        // the queue's LDS layout (one workgroup per env runs on FULL or OBJECTS)
+    int threads, slots, parts, sizes[16], queue_prio, queue_late, ovf_grid;      // ovf_grid: workgroups of kp_step_overflow_kernel
+    size_t lds;           // dynamic LDS bytes of the step kernel
+};
+
+StepPlan plan_step(const kp_sim& s, int nsub, bool capturing) {
+    const kp_model& m = *s.model;
+    StepPlan p{};
+    // floor scenes: the job queue runs on the lean layout (EnvLdsLean) with a register budget for three waves per SIMD, except during a fallback (poll_overflow);
+    // model option lean_queue = 0 keeps the full layout (two waves per SIMD; A / B measurements)
+    bool lean = lean_eligible(s);
+    if (lean && nsub > 0 && s.ovf_host && !capturing && m.lean_adaptive && s.launch_index < s.lean_off_until) lean = false;
+    p.layout = s.has_objects ? OBJECTS : lean ? LEAN : FULL;
+    p.threads = m.threads;
+    // lpt_order: 1 on, 0 off, -1 (default) on when the scene's objects are simulated: an env whose hulls press on objects stays the launch's
+    // longest for many control steps, so starting it first shortens the launch (objects workload 7.21 -> 6.62 ms); floor-only costs are not
+    // predictable from step to step (correlation 0.25 .. 0.55) and gain nothing
+    p.lpt = nsub > 0 && (m.lpt_order > 0 || (m.lpt_order < 0 && s.has_objects));
+    // lds_pad: allocate at least that many bytes per env (experiments: fewer envs per CU with the same binary)
+    const size_t lds = s.has_objects ? sizeof(kp::EnvLdsObj) : sizeof(kp::EnvLds);
+    size_t lds_q = lean ? sizeof(kp::EnvLdsLean) : lds;
+    if (m.lds_pad > 0) lds_q = std::max(lds_q, (size_t)m.lds_pad);
+    p.slots = m.queue_slots > 0 ? m.queue_slots : s.wave_slots / 8 * envs_per_cu(lds_q, lean ? 12 : 8);
+    // Schedule defaults.  Full layout (objects; floor with lean_queue = 0): 6 + 5 + 4 substeps, FIFO, no issue priorities (rounds 2 - 5).  Lean layout: 3072 slots hold
+    // three quarters of BASELINE's 4096 envs, so a quarter of the envs start one job late and the launch ends on them (sum of env cycles / slots 1.83 ms, launch
+    // 2.44 ms).  Three measures take the launch to 2.19 ms (profiles/r06/lean_schedule_knobs*.log): equal jobs 5 + 5 + 5 (the late envs start earlier), a late
+    // env is never queued again (queue_late), and every wave's issue priority follows its env's distance from the end of the control step (queue_prio = 3).
+    // Options the caller sets (substeps_per_job / job_taper, queue_prio, queue_late) are obeyed.
+    const bool lean_auto = lean && m.job_auto;
+    const int spj = lean_auto ? 5 : m.substeps_per_job, taper = lean_auto ? 0 : m.job_taper;
+    if (spj > 0 && nsub > 0) {
+        p.parts = job_schedule(nsub, spj, taper, p.sizes);
+        if (const char* e = std::getenv("KP_JOB_SCHEDULE")) {      // experiments: explicit comma-separated job sizes
+            int tmp[16], np = 0, sum = 0;
+            for (const char* c = e; *c && np < 16;) { tmp[np] = std::atoi(c); sum += tmp[np++]; while (*c && *c != ',') c++; if (*c) c++; }
+            if (sum == nsub) { p.parts = np; std::copy(tmp, tmp + np, p.sizes); }
+        }
+    }
+    // more envs than resident wave slots: schedule the control step as jobs pulled from a FIFO by one resident wave per slot instead of one workgroup per env,
+    // which ends on a long tail.  The queue pays from the env count on that one-workgroup-per-env launches (full layout) cannot hold resident at once; the lean
+    // queue then runs with every env resident up to its own slot count and in rounds beyond it.  Env ids take 24 bits of a queue entry.
+    const int resident_full = s.wave_slots / 8 * envs_per_cu(lds, 8);
+    p.queue = nsub > 0 && p.parts > 1 && m.threads == 64 && s.n > std::min(p.slots, resident_full) && s.n <= 0xFFFFFF && !s.prof;
+    p.lds = p.queue ? lds_q : lds;
+    p.queue_prio = m.queue_prio >= 0 ? m.queue_prio : (lean ? 3 : 0);
+    p.queue_late = m.queue_late >= 0 ? m.queue_late : (lean ? 1 : 0);
+    // overflow kernel: twice the overflow count last seen (the scenes that overflow keep doing so for a while), at least 128 workgroups -- an unexpected burst
+    // is slow once and sized right from the next-but-one launch on; launching full residency every time costs 34 us per control step for nothing
+    p.ovf_grid = std::min(std::min(s.n, resident_full), std::max(128, 2 * (int)std::min<unsigned>(s.ovf_last, 1u << 20)));
+    return p;
+}
+
+// one workgroup of NT threads per env: the control step, or (nsub = 0) the forward pass alone
+template <int NT, bool OBJ>
+void launch_per_env(const kp_sim* s, const kp::StepArgs& A, int nsub, size_t lds) {
+    if (nsub > 0) hipLaunchKernelGGL((kp::kp_step_kernel<NT, OBJ>), dim3(s->n), dim3(NT), lds, s->stream, A);
+    else hipLaunchKernelGGL((kp::kp_forward_kernel<NT, OBJ>), dim3(s->n), dim3(NT), lds, s->stream, A);
+}
+
 int launch_step(kp_sim* s, const float* action, int nsub, const uint8_t* mask, bool time_it) {
-    kp::StepArgs A{};
-    A.T = s->T; A.P = s->P; A.n_envs = s->n; A.n_substeps = nsub;
-    A.qpos = s->qpos; A.qvel = s->qvel; A.qpos_d = s->qpos_d; A.qvel_d = s->qvel_d; A.warm = s->warm; A.warm2 = s->warm2;
-    A.target_qpos = s->t_qpos; A.action = action; A.env_mask = mask;
-    A.xpos = s->xpos; A.xquat = s->xquat; A.xipos = s->xipos; A.diag = s->diag; A.prof = s->prof;
-    A.geoms = s->geoms; A.ngeom = s->ngeom; A.dbg_contacts = s->dbg_contacts;
-    A.obj_slot = s->obj_slot; A.obj_qpos = s->obj_qpos; A.obj_qvel = s->obj_qvel; A.obj_warm = s->obj_warm; A.obj_warm2 = s->obj_warm2;
-    A.order = nullptr; A.cost = s->cost;
     const bool obj = s->has_objects;
     if (obj && s->model->threads != 64) return fail("object contact needs threads_per_env = 64");
-    A.warm_extrap = s->model->warm_extrap < 0.f ? (obj ? 0.75f : 0.f) : s->model->warm_extrap;      // the Newton solve's starting point (kp_step_kernel.hpp)
-    size_t lds = obj ? sizeof(kp::EnvLdsObj) : sizeof(kp::EnvLds);
+    if (s->model->threads != 64 && s->model->threads != 128 && s->model->threads != 256) return fail("threads_per_env must be 64, 128 or 256");
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(s->stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+    time_it = time_it && !capturing;      // a launch that is being captured into a hipGraph carries no timing events (they could not be read back)
     hipEvent_t e0 = s->ev0, e1 = s->ev1;
-    if (time_it) {      // a launch that is being captured into a hipGraph carries no timing events (they could not be read back)
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s->stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) time_it = false;
-    }
     if (time_it && s->ring_on && s->ring_used < 4096) {
         if ((int)s->ring.size() < 2 * (s->ring_used + 1)) {
             hipEvent_t a, b;
@@ -260,80 +336,41 @@ int launch_step(kp_sim* s, const float* action, int nsub, const uint8_t* mask, b
         s->ring_used++;
     }
     if (time_it) HIP_OK(hipEventRecord(e0, s->stream));
-    // lpt_order: 1 on, 0 off, -1 (default) on when the scene's objects are simulated: an env whose hulls press on objects stays the launch's
-    // longest for many control steps, so starting it first shortens the launch (objects workload 7.21 -> 6.62 ms); floor-only costs are not
-    // predictable from step to step (correlation 0.25 .. 0.55) and gain nothing
-    if (nsub > 0 && (s->model->lpt_order > 0 || (s->model->lpt_order < 0 && s->has_objects))) {      // longest env first (inside the timed bracket): order the workgroups / the queue's first jobs by the cycles of the previous control step
+    if (nsub > 0 && s->ovf_host && !capturing && lean_eligible(*s) && poll_overflow(s)) return -1;
+    const StepPlan p = plan_step(*s, nsub, capturing);
+    if (nsub > 0) { s->launch_index++; s->last_nsub = nsub; }
+    kp::StepArgs A{};
+    A.T = s->T; A.P = s->P; A.n_envs = s->n; A.n_substeps = nsub;
+    A.qpos = s->qpos; A.qvel = s->qvel; A.qpos_d = s->qpos_d; A.qvel_d = s->qvel_d; A.warm = s->warm; A.warm2 = s->warm2;
+    A.target_qpos = s->t_qpos; A.action = action; A.env_mask = mask;
+    A.xpos = s->xpos; A.xquat = s->xquat; A.xipos = s->xipos; A.diag = s->diag; A.prof = s->prof;
+    A.geoms = s->geoms; A.ngeom = s->ngeom; A.dbg_contacts = s->dbg_contacts;
+    A.obj_slot = s->obj_slot; A.obj_qpos = s->obj_qpos; A.obj_qvel = s->obj_qvel; A.obj_warm = s->obj_warm; A.obj_warm2 = s->obj_warm2;
+    A.order = nullptr; A.cost = s->cost;
+    A.warm_extrap = s->model->warm_extrap < 0.f ? (obj ? 0.75f : 0.f) : s->model->warm_extrap;      // the Newton solve's starting point (kp_step_kernel.hpp)
+    if (p.lpt) {      // longest env first (inside the timed bracket): order the workgroups / the queue's first jobs by the cycles of the previous control step
         hipLaunchKernelGGL(kp::k_lpt_order, dim3(1), dim3(1024), 0, s->stream, s->n, s->cost, s->order);
         A.order = s->order;
     }
-#define KP_LAUNCH(NT_) do { if (nsub > 0) hipLaunchKernelGGL((kp::kp_step_kernel<NT_, false>), dim3(s->n), dim3(NT_), lds, s->stream, A); \
-                            else hipLaunchKernelGGL((kp::kp_forward_kernel<NT_, false>), dim3(s->n), dim3(NT_), lds, s->stream, A); } while (0)
-    // more envs than resident wave slots: schedule the control step as jobs of substeps_per_job substeps pulled from a FIFO by one
-    // resident wave per slot (kp_step_queue_kernel) instead of one workgroup per env, which ends on a long tail
-    // Schedule defaults.  Full layout (objects; floor with lean_queue = 0): 6 + 5 + 4 substeps, FIFO, no issue priorities (rounds 2 - 5).  Lean layout: 3072 slots hold
-    // three quarters of BASELINE's 4096 envs, so a quarter of the envs start one job late and the launch ends on them (sum of env cycles / slots 1.83 ms, launch
-    // 2.44 ms).  Three measures take the launch to 2.19 ms (profiles/r06/lean_schedule_knobs*.log): equal jobs 5 + 5 + 5 (the late envs start earlier), a late
-    // env is never queued again (queue_late), and every wave's issue priority follows its env's distance from the end of the control step (queue_prio = 3).
-    // Options the caller sets (substeps_per_job / job_taper, queue_prio, queue_late) are obeyed.
-    // resident waves: LDS is allocated in 1 280-byte granules, 128 per CU (tools/micro/lds_granule_probe.hip); the register budgets allow 8 waves per CU
-    // (full layout, <= 256 VGPRs) and 12 (lean layout, 168 VGPRs)
-    // floor scenes: the job queue runs on the lean layout (EnvLdsLean) with a register budget for three waves per SIMD; model option lean_queue = 0 keeps the
-    // full layout (two waves per SIMD; A / B measurements).  lds_pad: allocate at least that many bytes per env (experiments: fewer envs per CU with the same binary)
-    bool lean = !obj && s->model->lean_queue && s->model->threads == 64;
-    bool capturing = false;
-    { hipStreamCaptureStatus cap = hipStreamCaptureStatusNone; capturing = hipStreamIsCapturing(s->stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone; }
-    if (lean && nsub > 0 && s->ovf_host && !capturing) {
-        for (int k = 0; k < 2; k++)
-            if (s->ovf_pending[k] && hipEventQuery(s->ovf_ev[k]) == hipSuccess) {
-                s->ovf_pending[k] = false;
-                s->ovf_last = s->ovf_host[k];
-                if ((size_t)s->ovf_host[k] * 64 > (size_t)s->n) { s->lean_off_until = s->launch_index + 64; s->lean_fallbacks++; }
-            }
-        if (s->model->lean_adaptive && s->launch_index < s->lean_off_until) lean = false;
-    }
-    if (nsub > 0) s->launch_index++;
-    size_t lds_q = lean ? sizeof(kp::EnvLdsLean) : lds;
-    if (s->model->lds_pad > 0) lds_q = std::max(lds_q, (size_t)s->model->lds_pad);
-    const int per_cu = std::min(lean ? 12 : 8, 128 / (int)((lds_q + 1279) / 1280));
-    const int slots = s->model->queue_slots > 0 ? s->model->queue_slots : s->wave_slots / 8 * per_cu;
-    const bool lean_auto = lean && s->model->job_auto;
-    const int spj = lean_auto ? 5 : s->model->substeps_per_job, taper = lean_auto ? 0 : s->model->job_taper;
-    int sizes[16], parts = 0;
-    if (spj > 0 && nsub > 0) {
-        parts = job_schedule(nsub, spj, taper, sizes);
-        if (const char* e = std::getenv("KP_JOB_SCHEDULE")) {      // experiments: explicit comma-separated job sizes
-            int tmp[16], np = 0, sum = 0;
-            for (const char* c = e; *c && np < 16;) { tmp[np] = std::atoi(c); sum += tmp[np++]; while (*c && *c != ',') c++; if (*c) c++; }
-            if (sum == nsub) { parts = np; std::copy(tmp, tmp + np, sizes); }
-        }
-    }
-    // the queue pays from the env count on that one-workgroup-per-env launches (full layout) cannot hold resident at once; the lean queue then runs with
-    // every env resident up to its own slot count and in rounds beyond it
-    const int resident_full = s->wave_slots / 8 * std::min(8, 128 / (int)((lds + 1279) / 1280));
-    const bool queue = nsub > 0 && parts > 1 && s->model->threads == 64 && s->n > std::min(slots, resident_full) && s->n <= 0xFFFFFF && !s->prof;   // env ids take 24 bits of a queue entry
-    A.jobq = s->jobq; A.jobctr = s->jobctr; A.ovfq = s->ovfq; A.lean_cap = s->model->lean_cap; A.warm3 = s->warm3; A.spd_next = s->spd_next; A.n_parts = queue ? parts : 1; A.queue_fence = s->model->queue_fence; A.queue_heavy = s->model->queue_heavy; A.queue_prio = s->model->queue_prio >= 0 ? s->model->queue_prio : (lean ? 3 : 0); A.queue_late = s->model->queue_late >= 0 ? s->model->queue_late : (lean ? 1 : 0); A.order_valid = A.order != nullptr;
+    A.jobq = s->jobq; A.jobctr = s->jobctr; A.ovfq = s->ovfq; A.lean_cap = s->model->lean_cap; A.warm3 = s->warm3; A.spd_next = s->spd_next; A.n_parts = p.queue ? p.parts : 1; A.queue_fence = s->model->queue_fence; A.queue_heavy = s->model->queue_heavy; A.queue_prio = p.queue_prio; A.queue_late = p.queue_late; A.order_valid = A.order != nullptr;
     A.part_sub_lo = A.part_sub_hi = 0;
-    for (int k = 0; queue && k < parts; k++) (k < 8 ? A.part_sub_lo : A.part_sub_hi) |= (unsigned long long)(sizes[k] & 255) << (8 * (k & 7));
-    if (queue) {
+    for (int k = 0; p.queue && k < p.parts; k++) (k < 8 ? A.part_sub_lo : A.part_sub_hi) |= (unsigned long long)(p.sizes[k] & 255) << (8 * (k & 7));
+    if (p.queue) {
         // the yardstick of queue_heavy is the previous launch's mean job time per substep: it only means something for the same kernel on the same
         // schedule, so a change of the substep count or of the kernel instantiation starts it from nothing (that launch keeps no env)
-        if (nsub != s->q_nsub || (int)obj + 2 * (int)lean != s->q_obj) {
+        if (nsub != s->q_nsub || (int)p.layout != s->q_layout) {
             HIP_OK(hipMemsetAsync(s->jobctr + 32, 0, 2 * sizeof(unsigned), s->stream));
-            s->q_nsub = nsub; s->q_obj = (int)obj + 2 * (int)lean;
+            s->q_nsub = nsub; s->q_layout = (int)p.layout;
         }
-        const unsigned total = (unsigned)s->n * (unsigned)parts;
+        const unsigned total = (unsigned)s->n * (unsigned)p.parts;
         hipLaunchKernelGGL(kp::k_queue_init, dim3((total + 255) / 256), dim3(256), 0, s->stream, s->n, total, s->jobq, s->jobctr, A.order);   // inside the timed bracket
         A.order = nullptr;                                              // the queue kernel addresses envs by their queue entry
-        if (obj) hipLaunchKernelGGL((kp::kp_step_queue_kernel<true>), dim3(slots), dim3(64), lds_q, s->stream, A);
-        else if (!lean) hipLaunchKernelGGL((kp::kp_step_queue_kernel<false>), dim3(slots), dim3(64), lds_q, s->stream, A);
+        if (p.layout == OBJECTS) hipLaunchKernelGGL((kp::kp_step_queue_kernel<true>), dim3(p.slots), dim3(64), p.lds, s->stream, A);
+        else if (p.layout == FULL) hipLaunchKernelGGL((kp::kp_step_queue_kernel<false>), dim3(p.slots), dim3(64), p.lds, s->stream, A);
         else {
-            hipLaunchKernelGGL((kp::kp_step_queue_kernel<false, true>), dim3(slots), dim3(64), lds_q, s->stream, A);
+            hipLaunchKernelGGL((kp::kp_step_queue_kernel<false, true>), dim3(p.slots), dim3(64), p.lds, s->stream, A);
             // the jobs whose contacts did not fit the lean layout (normally none: every wave leaves at its first read)
-            // grid: twice the overflow count last seen (the scenes that overflow keep doing so for a while), at least 128 workgroups -- an unexpected burst is
-            // slow once and sized right from the next-but-one launch on; launching full residency every time costs 34 us per control step for nothing
-            const int ovf_grid = std::min(std::min(s->n, resident_full), std::max(128, 2 * (int)std::min<unsigned>(s->ovf_last, 1u << 20)));
-            hipLaunchKernelGGL(kp::kp_step_overflow_kernel, dim3(ovf_grid), dim3(64), lds, s->stream, A);
+            hipLaunchKernelGGL(kp::kp_step_overflow_kernel, dim3(p.ovf_grid), dim3(64), sizeof(kp::EnvLds), s->stream, A);
             if (s->ovf_host && !capturing) {
                 const int k = (int)(s->launch_index & 1);
                 if (!s->ovf_pending[k]) {
@@ -343,18 +380,10 @@ int launch_step(kp_sim* s, const float* action, int nsub, const uint8_t* mask, b
                 }
             }
         }
-    } else
-    switch (s->model->threads) {
-        case 64:
-            if (obj && nsub > 0) hipLaunchKernelGGL((kp::kp_step_kernel<64, true>), dim3(s->n), dim3(64), lds, s->stream, A);
-            else if (obj) hipLaunchKernelGGL((kp::kp_forward_kernel<64, true>), dim3(s->n), dim3(64), lds, s->stream, A);
-            else KP_LAUNCH(64);
-            break;
-        case 128: KP_LAUNCH(128); break;
-        case 256: KP_LAUNCH(256); break;
-        default: return fail("threads_per_env must be 64, 128 or 256");
-    }
-#undef KP_LAUNCH
+    } else if (obj) launch_per_env<64, true>(s, A, nsub, p.lds);
+    else if (p.threads == 64) launch_per_env<64, false>(s, A, nsub, p.lds);
+    else if (p.threads == 128) launch_per_env<128, false>(s, A, nsub, p.lds);
+    else launch_per_env<256, false>(s, A, nsub, p.lds);
     HIP_OK(hipGetLastError());
     if (time_it) {
         HIP_OK(hipEventRecord(e1, s->stream));
@@ -993,8 +1022,8 @@ int kp_job_schedule(int n_substeps, int substeps_per_job, int taper, int* sizes1
 
 int kp_sim_lean_state(kp_sim* s, int32_t* out3) {
     if (!s || !out3) return fail("kp_sim_lean_state: null argument");
-    const bool lean = !s->has_objects && s->model->lean_queue && s->model->threads == 64;
-    out3[0] = lean && !(s->model->lean_adaptive && s->launch_index < s->lean_off_until);
+    const StepPlan p = plan_step(*s, s->last_nsub, false);
+    out3[0] = p.queue && p.layout == LEAN;
     out3[1] = s->lean_fallbacks; out3[2] = (int32_t)s->launch_index;
     return 0;
 }

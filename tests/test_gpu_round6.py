@@ -59,13 +59,14 @@ def _states(n, seed, lying_every=0):
 def test_lean_queue_layout_is_the_full_layout_bit_for_bit(kp):
     """4096 floor envs, 3 control steps: kp_step_queue_kernel<false, true> (EnvLdsLean, 168 VGPRs, 10+ envs per CU) against the same queue on the full layout
     (lean_queue = 0) and against one workgroup per env -- every state, read-out and diagnostic identical; also with warm_extrap = 0.75, whose a_{k-2} the lean
-    layout keeps in an HBM row."""
+    layout keeps in an HBM row, and in fresh mode (stale_kinematics = 0), which the lean layout does not serve: its launches run on the full layout."""
     n = 4096
     qpos, qvel = _states(n, 61)
     act = np.random.default_rng(62).normal(size=(n, 75)) * 0.2
-    for extra in ({}, {"warm_extrap": 0.75}):
+    for extra in ({}, {"warm_extrap": 0.75}, {"stale_kinematics": 0}):
         lean, dl, sim = _run(kp, n, qpos, qvel, act, 3, lean_queue=1, **extra)
         assert sim.model.get_option("lds_bytes_per_env_lean") <= 12 * 1280
+        assert sim.queue_counters()["lean_layout_next_launch"] == (extra.get("stale_kinematics", 1) == 1), extra
         full, df, _ = _run(kp, n, qpos, qvel, act, 3, lean_queue=0, **extra)
         for a_, b_ in zip(lean, full):
             assert (a_ == b_).all(), extra
@@ -75,6 +76,8 @@ def test_lean_queue_layout_is_the_full_layout_bit_for_bit(kp):
             one, d1, _ = _run(kp, n, qpos, qvel, act, 3, substeps_per_job=0)
             for a_, b_ in zip(lean[:5], one[:5]):
                 assert (a_ == b_).all()
+    _, _, few = _run(kp, 256, qpos[:256], qvel[:256], act[:256], 1, lean_queue=1)      # no more envs than slots: one workgroup per env, full layout
+    assert not few.queue_counters()["lean_layout_next_launch"]
 
 
 def test_contact_overflow_goes_to_the_full_layout(kp):
