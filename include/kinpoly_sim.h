@@ -144,6 +144,14 @@ int kp_sim_set_objects(kp_sim*, const float* obj_qpos, const uint8_t* env_mask);
  * normalised), wbpos [n_rows,72], wbquat [n_rows,96], bquat [n_rows,96], body_com [n_rows,72]; outputs may be NULL. */
 int kp_sim_fk(kp_sim*, int n_rows, const float* qpos, float* qpos_out, float* wbpos, float* wbquat, float* bquat, float* body_com);
 
+/* compute_physcis_metris' sim.forward() + data.contact walk (scripts/eval_pose_all.py:205-260) on n_rows arbitrary frames:
+ * xpos [R,72] / xquat [R,96] body poses (kp_sim_fk's wbpos / wbquat of the rows' qpos), obj_qpos [R,35] or NULL (floor only);
+ * out: pen [R] = sum over hull-vs-(floor|object) contacts of max(0, -dist - pen_margin), ncon [R] (int32), hits [R, n_obj_geom] (uint32,
+ * bit b = hull b touches object geom g; reference geom id = 25 + g; n_obj_geom = the model option "n_obj_geoms").  Enqueued on the sim's
+ * stream; no contact-count limit.  n_rows == 0 does nothing. */
+int kp_sim_pose_contacts(kp_sim*, int n_rows, const float* xpos, const float* xquat, const float* obj_qpos, float pen_margin,
+                         float* pen, int32_t* ncon, uint32_t* hits);
+
 /* backward of qpos -> wbpos of the same rows (the autograd path through Humanoid.qpos_fk that TrajARNet.compute_loss_lite's
  * end-effector term takes, traj_ar_smpl_net.py:459-497, torch_smpl_humanoid.py:125-202): grad_qpos [n_rows,76] =
  * (d wbpos / d qpos)^T grad_wbpos [n_rows,72]; wbpos / wbquat are the outputs of the kp_sim_fk call on those rows. */

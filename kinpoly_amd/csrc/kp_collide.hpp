@@ -63,6 +63,49 @@ __device__ __forceinline__ double wave_max_d(double v) {
     return fmax(fmax(readlane_d(v, 0), readlane_d(v, 16)), fmax(readlane_d(v, 32), readlane_d(v, 48)));
 }
 
+// wave-wide sum without LDS traffic: xor butterflies inside each 16-lane row with DPP (quad_perm, row_half_mirror,
+// row_mirror), then the row sums travel up with row_bcast:15 (rows 1, 3 += lane 15 of the row below) and row_bcast:31 (rows 2, 3 +=
+// lane 31), so lane 63 holds (r2 + r3) + (r0 + r1) and one v_readlane hands it to every lane.
+__device__ __forceinline__ float wave_sum(float v) {
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));   // xor 1
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));   // xor 2
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));  // half mirror
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));  // row mirror
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xA, 0xF, false)); // row_bcast:15
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x143, 0xC, 0xF, false)); // row_bcast:31
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+
+// wave-wide minimum, same exchange pattern (every lane gets the result)
+__device__ __forceinline__ float wave_min(float v) {
+    v = fminf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true)));
+    v = fminf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true)));
+    v = fminf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true)));
+    v = fminf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true)));
+    const int vi = __builtin_bit_cast(int, v);
+    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(vi, 0)), r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(vi, 16));
+    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(vi, 32)), r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(vi, 48));
+    return fminf(fminf(r0, r1), fminf(r2, r3));
+}
+
+__device__ __forceinline__ float wave_max_f(float v) { return -wave_min(-v); }
+
+// signed distance of world point x to a box (type 0) / z-axis cylinder (type 1) geom record
+__device__ __forceinline__ float geom_sdf(const float* g, V3 x) {
+    const float* R = g + 7;
+    const V3 r = x - ld3(g + 4);
+    const V3 l = v3(R[0] * r.x + R[3] * r.y + R[6] * r.z, R[1] * r.x + R[4] * r.y + R[7] * r.z, R[2] * r.x + R[5] * r.y + R[8] * r.z);
+    if (g[0] == 0.f) {
+        const V3 q = v3(fabsf(l.x) - g[1], fabsf(l.y) - g[2], fabsf(l.z) - g[3]);
+        const V3 o = v3(fmaxf(q.x, 0.f), fmaxf(q.y, 0.f), fmaxf(q.z, 0.f));
+        return sqrtf(dot(o, o)) + fminf(fmaxf(q.x, fmaxf(q.y, q.z)), 0.f);
+    }
+    const float qr = sqrtf(l.x * l.x + l.y * l.y) - g[1], qz = fabsf(l.z) - g[2];
+    const float orr = fmaxf(qr, 0.f), oz = fmaxf(qz, 0.f);
+    return sqrtf(orr * orr + oz * oz) + fminf(fmaxf(qr, qz), 0.f);
+}
+__device__ __forceinline__ float geom_rbound(const float* g) { return g[0] == 0.f ? sqrtf(g[1] * g[1] + g[2] * g[2] + g[3] * g[3]) : sqrtf(g[1] * g[1] + g[2] * g[2]); }
+
 // ---- support functions (mjccd_support): farthest point along the unit world direction dir, inflated by margin along dir.
 // Both functors read their shape from LDS on every query (wave-uniform addresses: broadcast reads) instead of carrying it in registers:
 // the MPR program is wave-uniform, so everything it keeps live costs a VGPR per value on all 64 lanes, and the register file of the object

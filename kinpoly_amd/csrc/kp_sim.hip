@@ -17,6 +17,7 @@
 #include "kp_rollout_kernels.hpp"
 #include "kp_policy_kernels.hpp"
 #include "kp_step_kernel.hpp"
+#include "kp_pose_contacts.hpp"
 
 namespace {
 thread_local std::string g_err;
@@ -458,6 +459,7 @@ double kp_model_get_option(const kp_model* m, const char* name) {
     if (k == "dynamic_objects") return m->dynamic_objects;
     if (k == "planemesh_max") return m->planemesh_max;
     if (k == "planemesh_tol") return m->planemesh_tol;
+    if (k == "n_obj_geoms") return (double)(m->h.obj_geoms.size() / 18);     // columns of kp_sim_pose_contacts' hits
     if (k == "lpt_order") return m->lpt_order;
     if (k == "substeps_per_job") return m->substeps_per_job;
     if (k == "queue_slots") return m->queue_slots;
@@ -674,6 +676,24 @@ int kp_sim_fk(kp_sim* s, int n_rows, const float* qpos, float* qpos_out, float* 
     hipLaunchKernelGGL(kp::k_target_fk, dim3((n_rows + 3) / 4), dim3(256), 0, s->stream, n_rows, qpos, (const uint8_t*)nullptr, B,
                        s->T.body_pos, s->T.body_ipos, s->T.body_parent, s->T.body_depth);
     HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int kp_sim_pose_contacts(kp_sim* s, int n_rows, const float* xpos, const float* xquat, const float* obj_qpos, float pen_margin,
+                         float* pen, int32_t* ncon, uint32_t* hits) {
+    if (!s) return fail("kp_sim_pose_contacts: null sim");
+    if (n_rows < 0) return fail("kp_sim_pose_contacts: n_rows < 0");
+    if (!xpos || !xquat) return fail("kp_sim_pose_contacts: null xpos / xquat");
+    if (!pen || !ncon || !hits) return fail("kp_sim_pose_contacts: null output");
+    if (obj_qpos && !s->d_obj_geoms) return fail("kp_sim_pose_contacts: obj_qpos given but the model blob has no object geoms");
+    if (s->n_obj_geoms > kp::PC_MAXGEOM) return fail("kp_sim_pose_contacts: the model has more object geoms than the query holds (16)");
+    if (n_rows == 0) return 0;
+    HIP_OK(hipSetDevice(s->device));
+    kp::PoseContactArgs A{};
+    A.T = s->T; A.P = s->P; A.n_rows = n_rows; A.n_og = s->n_obj_geoms; A.n_obj = s->n_obj;
+    A.xpos = xpos; A.xquat = xquat; A.obj_qpos = obj_qpos; A.og = s->d_obj_geoms; A.pen_margin = pen_margin;
+    A.pen = pen; A.ncon = ncon; A.hits = hits;
+    HIP_OK(kp::launch_pose_contacts(A, s->stream));
     return 0;
 }
 

@@ -8,8 +8,17 @@
     head_dist   root_dist's measure on the head's transform against the data set's head_pose
 
 numpy, host side (an analysis step after the roll-outs, as in the reference).  Joint positions come from the forward kinematics of the poses (the
-reference reads MuJoCo's body_xpos after sim.forward: the same quantities).  NOT here: penetration, foot sliding and the object-interaction
-success rate of compute_physcis_metris (:205-292), which query MuJoCo's contact list frame by frame.
+reference reads MuJoCo's body_xpos after sim.forward: the same quantities).
+
+The physical columns of compute_physcis_metris (:205-467), on every frame of the predicted and of the ground-truth trajectory:
+
+    pen         penetration beyond 5 mm, summed over the hull - floor / hull - object contacts of a frame and over the frames, / T, x 1000
+    slide       foot sliding of the two toes (compute_foot_sliding, :294-309), mean of L_Toe and R_Toe
+    succ        the take's object interaction (compute_obj_interact, :337-467), by the action prefix of its name
+
+The contact walk is one batched device query (KpSim.pose_contacts: kp_sim_pose_contacts on kp_sim_fk's body poses); the rules applied to its
+per-frame results are restated here.  Reference geom ids: 1 + body index for the 24 hulls (1 Pelvis, 2 L_Hip, 4 L_Ankle, 5 L_Toe, 6 R_Hip,
+8 R_Ankle, 9 R_Toe, 10 Torso, 11 Spine, 14 Head), 25 + g for object geom g of the model (25-26 chair, 27 box, 28-32 table, 33 Can, 34 step).
 """
 from __future__ import annotations
 
@@ -114,3 +123,104 @@ def coverage_metrics(results: dict, gt: dict, fk, dt=1.0 / 30.0) -> dict:
         per[k] = m
     keys = sorted({kk for m in per.values() for kk in m})
     return {**{kk: float(np.mean([m[kk] for m in per.values() if kk in m])) for kk in keys}, "per_take": per}
+
+
+PEN_MARGIN = 0.005                                    # compute_physcis_metris: margin
+L_TOE, R_TOE, HEAD = 4, 8, 13                         # body indices (reference body / geom id - 1)
+_SIT_BODIES = sum(1 << b for b in (0, 1, 5, 9, 10))   # geoms 1, 2, 6, 10, 11
+_AVOID_BODIES = (1 << 12) - 1                         # geoms 1..12
+_STEP_BODIES = sum(1 << b for b in (3, 4, 7, 8))      # geoms 4, 5, 8, 9
+_CHAIR, _CAN, _STEP = (0, 1), 8, 9                    # object geoms 25-26, 33, 34
+
+
+def pen_metric(frame_pen) -> float:
+    """seq_pen (:229-285): the frames' penetration sums (frames without penetration add nothing), / T, x 1000."""
+    p = np.asarray(frame_pen, np.float64)
+    return float(np.sum(p[p > 0]) / len(p) * 1000) if np.any(p > 0) else 0.0
+
+
+def foot_sliding(toe_xyz, root_z) -> float:
+    """compute_foot_sliding (:294-309): toe positions [T, 3] (body_xpos), root heights qpos[:, 2] [T]."""
+    H, z_threshold = 0.033, 0.65
+    seq_len = len(root_z)
+    z = np.asarray(root_z, np.float64)[1:]
+    foot = np.array(toe_xyz, np.float64)
+    foot[:, -1] -= np.mean(foot[:3, -1])
+    disp = np.linalg.norm(foot[1:, :2] - foot[:-1, :2], axis=1)
+    avg = (foot[:-1, -1] + foot[1:, -1]) / 2
+    subset = np.logical_and(avg < H, z > z_threshold)
+    return float(np.sum(np.abs(disp * (2 - 2 ** (avg / H)))[subset]) / seq_len * 1000)
+
+
+def interaction_success(action, hits, root_z, obj_pose, head_pos, head_pos_gt, fail_safe=None) -> bool:
+    """compute_obj_interact (:337-467) on the per-frame hit masks hits [T, n_obj_geoms] (bit b: hull b touches object geom g).  root_z = qpos[:, 2];
+    obj_pose [T, 35]; head_pos / head_pos_gt [T, 3].  fail_safe (the predicted run only): succ &= not fail_safe.  An action the reference does not
+    know is a success here (the reference's compute_metrics raises KeyError on it)."""
+    h = np.asarray(hits, np.int64)
+    if action == "sit":
+        succ = bool(np.any((h[:, _CHAIR[0]] | h[:, _CHAIR[1]]) & _SIT_BODIES))
+    elif action == "avoid":
+        diff = np.linalg.norm(np.asarray(head_pos, np.float64)[-1] - np.asarray(head_pos_gt, np.float64)[-1])
+        succ = not (bool(np.any(h[:, _CAN] & _AVOID_BODIES)) or diff > 0.5)
+    elif action == "push":
+        box = np.asarray(obj_pose, np.float64)[:, 7:10]
+        succ = bool(np.max(np.linalg.norm(box[0] - box, axis=1)) > 0.1)
+    elif action == "step":
+        z = np.asarray(root_z, np.float64)
+        succ = bool(np.any(h[:, _STEP] & _STEP_BODIES)) and bool(np.any(z - z[0] > 0.1))
+    else:
+        succ = True
+    if fail_safe is not None:
+        succ = succ and not fail_safe
+    return succ
+
+
+def coverage_physics_metrics(results: dict, gt: dict, sim, chunk_rows: int = 65536) -> dict:
+    """compute_physcis_metris (:205-292) for the predicted and the ground-truth trajectory of every take of a `*_coverage_full.pkl` dict.  gt as in
+    coverage_metrics ({take: {'qpos', 'head_pose'}}); sim: a KpSim on the scene the run used.  Takes are cut to n = min(len(pred), len(gt qpos)) as
+    coverage_metrics does; the ground truth is played with the predicted run's obj_pose (:146-147).  All frames of all takes go to the device in one
+    query per chunk of chunk_rows rows.  Returns the means of pen_pred, pen_gt, slide_pred, slide_gt and succ, 'succ_by_action' and 'per_take'."""
+    import torch
+    takes, q_rows, o_rows = [], [], []
+    for k, r in results.items():
+        if k not in gt:
+            continue
+        pred, g = np.asarray(r["pred"], np.float64), np.asarray(gt[k]["qpos"], np.float64)
+        n = min(len(pred), len(g))
+        if n < 3:
+            continue
+        obj = np.asarray(r["obj_pose"], np.float64)[:n]
+        if obj.shape != (n, 35):
+            raise ValueError(f"{k}: obj_pose must hold the 35-float object block of every frame")
+        takes.append((k, n, r))
+        q_rows += [pred[:n], g[:n]]; o_rows += [obj, obj]
+    if not takes:
+        return {"per_take": {}, "succ_by_action": {}}
+    Q, O = np.concatenate(q_rows).astype(np.float32), np.concatenate(o_rows).astype(np.float32)
+    pen, hits, xpos = np.empty(len(Q), np.float64), None, np.empty((len(Q), 24, 3), np.float64)
+    for a in range(0, len(Q), chunk_rows):
+        out = sim.pose_contacts(torch.from_numpy(Q[a:a + chunk_rows]).to(sim.device), torch.from_numpy(O[a:a + chunk_rows]).to(sim.device))
+        pen[a:a + chunk_rows] = out["pen"].double().cpu().numpy()
+        hc = out["hits"].cpu().numpy().astype(np.int64)
+        hits = np.empty((len(Q), hc.shape[1]), np.int64) if hits is None else hits
+        hits[a:a + chunk_rows] = hc
+        xpos[a:a + chunk_rows] = out["xpos"].double().cpu().numpy().reshape(-1, 24, 3)
+    per, row = {}, 0
+    for k, n, r in takes:
+        hp_gt = np.asarray(gt[k]["head_pose"], np.float64)[:n, :3]
+        m = {}
+        for side, qp, fs in (("pred", Q[row:row + n], r.get("fail_safe")), ("gt", Q[row + n:row + 2 * n], None)):
+            sl = slice(row, row + n) if side == "pred" else slice(row + n, row + 2 * n)
+            z = qp[:, 2].astype(np.float64)
+            m["pen_" + side] = pen_metric(pen[sl])
+            m["slide_" + side] = (foot_sliding(xpos[sl, L_TOE], z) + foot_sliding(xpos[sl, R_TOE], z)) / 2
+            s = interaction_success(k.split("-")[0], hits[sl], z, O[row:row + n], xpos[sl, HEAD], hp_gt, fs)
+            m["succ" if side == "pred" else "succ_gt"] = float(s)
+        per[k] = m
+        row += 2 * n
+    keys = ("pen_pred", "pen_gt", "slide_pred", "slide_gt", "succ")
+    by_action = {}
+    for k, m in per.items():
+        by_action.setdefault(k.split("-")[0], []).append(m["succ"])
+    return {**{kk: float(np.mean([m[kk] for m in per.values()])) for kk in keys},
+            "succ_by_action": {a: float(np.mean(v)) for a, v in by_action.items()}, "per_take": per}

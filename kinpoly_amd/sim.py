@@ -37,7 +37,7 @@ ABI_SYMBOLS = [
     "kp_sim_contacts", "kp_gae_bootstrap", "kp_gru_gates_forward", "kp_gru_gates_backward", "kp_sim_phase_cycles_env",
     "kp_sim_post_step", "kp_sim_reset_rows", "kp_mcp_compose", "kp_sim_step_head", "kp_model_compile", "kp_model_load_xml",
     "kp_mcp_tail", "kp_gru_cell_step", "kp_kin_advance", "kp_pool_advance", "kp_rollout_record_pre", "kp_rollout_record_post", "kp_sim_field_device",
-    "kp_sim_lean_state",
+    "kp_sim_lean_state", "kp_sim_pose_contacts",
 ]
 
 
@@ -134,6 +134,7 @@ def load_library(path: str | None = None):
     L.kp_sim_set_obj_state.argtypes = [P, F, F, U8]; L.kp_sim_set_obj_state.restype = C.c_int
     L.kp_sim_fk.argtypes = [P, C.c_int, F, F, F, F, F, F]; L.kp_sim_fk.restype = C.c_int
     L.kp_sim_fk_backward.argtypes = [P, C.c_int, F, F, F, F, F]; L.kp_sim_fk_backward.restype = C.c_int
+    L.kp_sim_pose_contacts.argtypes = [P, C.c_int, F, F, F, C.c_float, F, F, F]; L.kp_sim_pose_contacts.restype = C.c_int
     L.kp_sim_set_stream.argtypes = [P, C.c_void_p]; L.kp_sim_set_stream.restype = C.c_int
     L.kp_sim_status_device.argtypes = [P]; L.kp_sim_status_device.restype = C.c_void_p
     L.kp_sim_mass_matrix.argtypes = [P, F, F]; L.kp_sim_mass_matrix.restype = C.c_int
@@ -349,6 +350,27 @@ class KpSim:
                 raise ValueError("fk_backward: expected contiguous float32 device tensors [R,76], [R,72], [R,96], [R,72]")
         out = torch.empty((R, NQ), dtype=torch.float32, device=self.device)
         _check(self.L.kp_sim_fk_backward(self.h, R, *[C.c_void_p(t.data_ptr()) for t in (qpos_rows, wbpos, wbquat, grad_wbpos, out)]), "kp_sim_fk_backward")
+        return out
+
+    def pose_contacts(self, qpos_rows: torch.Tensor, obj_qpos: torch.Tensor | None = None, pen_margin: float = 0.005) -> dict:
+        """compute_physcis_metris' per-frame contact walk (kp_sim_pose_contacts) on [R,76] rows (+ their [R,35] object blocks, or None: floor
+        only) -> dict of device tensors: pen [R] (sum of max(0, -dist - pen_margin) over the hull - floor / hull - object contacts), ncon [R]
+        int32, hits [R, n_obj_geoms] uint32 (bit b = hull b touches object geom g), xpos [R,72], xquat [R,96] (the rows' body poses, fk())."""
+        if qpos_rows.dim() != 2 or not qpos_rows.is_cuda or qpos_rows.dtype != torch.float32 or not qpos_rows.is_contiguous() or qpos_rows.shape[1] != NQ:
+            raise ValueError("pose_contacts: expected contiguous float32 device tensor [R,76]")
+        R = qpos_rows.shape[0]
+        op = _ptr(obj_qpos, R, 35)
+        n_og = int(self.model.get_option("n_obj_geoms"))
+        out = {"pen": torch.empty(R, dtype=torch.float32, device=self.device), "ncon": torch.empty(R, dtype=torch.int32, device=self.device),
+               "hits": torch.empty((R, n_og), dtype=torch.int32, device=self.device).view(torch.uint32)}
+        if R == 0:
+            out["xpos"] = torch.empty((0, 72), dtype=torch.float32, device=self.device)
+            out["xquat"] = torch.empty((0, 96), dtype=torch.float32, device=self.device)
+            return out
+        f = self.fk(qpos_rows)
+        out["xpos"], out["xquat"] = f["wbpos"], f["wbquat"]
+        _check(self.L.kp_sim_pose_contacts(self.h, R, C.c_void_p(out["xpos"].data_ptr()), C.c_void_p(out["xquat"].data_ptr()), op, float(pen_margin),
+                                           *[C.c_void_p(out[k].data_ptr()) for k in ("pen", "ncon", "hits")]), "kp_sim_pose_contacts")
         return out
 
     def step_begin(self):
