@@ -49,7 +49,9 @@ typedef struct kp_sim kp_sim;
 #define KP_NU 69
 #define KP_NBODY 24
 #define KP_CC_OBS_DIM 784   /* get_full_obs_v1, humanoid_im.py:144-233 */
-#define KP_AR_OBS_DIM 105   /* get_ar_obs_v1, humanoid_ar_v1.py:133-214 (kin_poly.yml flags) */
+#define KP_AR_OBS_DIM 105   /* get_ar_obs_v1, humanoid_ar_v1.py:133-214 (kin_poly.yml flags): the action one-hot is the last block, [101..104] */
+#define KP_AR_OBS_DIM_NO_ACTION 101   /* the same without the one-hot (use_action: false, kin_poly_wo_action.yml; humanoid_ar_v1.py:200-201): the
+                                         first 101 entries of the 105-d layout.  Model option "ar_obs_action" = 0 selects it (kp_model_set_option) */
 #define KP_KIN_ACTION_DIM 80
 #define KP_CC_ACTION_DIM 75
 
@@ -92,7 +94,10 @@ void kp_model_free(kp_model*);
  * MuJoCo's: the previous substep's solution a_{k-1} (mjData.qacc_warmstart).  beta != 0 starts from a_{k-1} + beta (a_{k-1} - a_{k-2}) from the second substep
  * of a kp_sim_step_ctrl call on (every call begins with the plain warm start).  Same strictly convex problem, same minimiser, same termination tests: only the
  * iteration path changes (fewer Newton iterations where accelerations change smoothly -- falls, impacts; more on quiet standing states); results do not
- * depend on how a control step is cut into jobs. */
+ * depend on how a control step is cut into jobs.
+ * "ar_obs_action" (1 / 0, default 1; anything else fails): the kinematic observation of a kp_sim created afterwards from this model -- 1: KP_AR_OBS_DIM
+ * floats with the action one-hot (use_action), 0: the first KP_AR_OBS_DIM_NO_ACTION of them (use_action: false, humanoid_ar_v1.py:200-201).
+ * kp_model_get_option also answers "ar_obs_dim" (105 or 101). */
 int kp_model_set_option(kp_model*, const char* name, double value);
 double kp_model_get_option(const kp_model*, const char* name);
 
@@ -193,8 +198,11 @@ typedef struct {
 /* records prev_bquat / prev_hpos at the top of HumanoidAREnv.step (humanoid_ar_v1.py:246-249) */
 int kp_sim_step_begin(kp_sim*);
 
-/* get_ar_obs_v1() [N,105]   (humanoid_ar_v1.py:133-214; use_head, use_action, use_obj on; use_vel/of/context off) */
+/* get_ar_obs_v1() [N,105]   (humanoid_ar_v1.py:133-214; use_head, use_action, use_obj on; use_vel/of/context off).  A handle created from a model
+ * whose option "ar_obs_action" is 0 writes [N,101] instead: no action one-hot (use_action: false, :200-201); the one-hot still selects the object
+ * of the "predicted object relative to head" block (:146-147, 466-476).  kp_sim_ar_obs_dim: the handle's width (105 or 101; -1 for NULL). */
 int kp_sim_obs_ar(kp_sim*, const kp_ctx* ctx, float* out);
+int kp_sim_ar_obs_dim(const kp_sim*);
 
 /* termination (calc_body_diff / calc_body_gt_diff, :435-458, thresholds :53-54) and the reward
  * dynamic_supervision_v1 (kin_poly/core/reward_function.py:931-995) for the state after do_simulation,
@@ -260,6 +268,9 @@ typedef struct {
 } kp_record_post;
 int kp_rollout_record_pre(const kp_record_pre*, void* hip_stream);
 int kp_rollout_record_post(const kp_record_post*, void* hip_stream);
+/* the same with the observation width of obs / states / next_states: KP_AR_OBS_DIM (what the two above use) or KP_AR_OBS_DIM_NO_ACTION */
+int kp_rollout_record_pre_w(const kp_record_pre*, int obs_dim, void* hip_stream);
+int kp_rollout_record_post_w(const kp_record_post*, int obs_dim, void* hip_stream);
 
 /* estimate_advantages before normalisation (uhc/khrylib/rl/core/common.py:5-20) on an env-major
  * [N,T] layout (each env's T rows contiguous, time increasing).  All pointers device, float32. */

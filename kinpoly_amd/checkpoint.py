@@ -113,9 +113,34 @@ def save_checkpoint(path, traj_ar_net: torch.nn.Module, value_net: torch.nn.Modu
 ALLOWED_MISSING_POLICY_KEYS = frozenset()
 
 
+class CheckpointWidthError(ValueError):
+    """A kinematic policy of one observation width loaded into a network of the other (use_action: true = 105, false = 101)."""
+
+
+def policy_obs_dim(state: dict) -> int | None:
+    """Observation width of a TrajARNet / KinPolicy state_dict (split_policy_dict form): the input width of action_rnn; None without that key."""
+    w = state.get("action_rnn.rnn_f.weight_ih")
+    return None if w is None else int(w.shape[1])
+
+
+def _width_name(d):
+    return {105: "105-d, use_action: true", 101: "101-d, use_action: false"}.get(d, f"{d}-d")
+
+
+def check_policy_obs_dim(state: dict, obs_dim: int, what="checkpoint"):
+    """Raise CheckpointWidthError, naming both widths, when the policy in `state` takes other observations than a network of `obs_dim`."""
+    got = policy_obs_dim(state)
+    if got is not None and got != obs_dim:
+        raise CheckpointWidthError(f"{what}: its kinematic policy takes {_width_name(got)} observations, the network it is loaded into {_width_name(obs_dim)} "
+                                   "(train and evaluate with the config the checkpoint was trained with)")
+
+
 def load_state_strict(module: torch.nn.Module, state: dict, allow_missing=ALLOWED_MISSING_POLICY_KEYS, what="checkpoint"):
-    """load_state_dict that names what does not fit: keys missing from `state` (beyond `allow_missing`) or not known to `module` raise."""
+    """load_state_dict that names what does not fit: keys missing from `state` (beyond `allow_missing`) or not known to `module` raise; a kinematic
+    policy of another observation width raises CheckpointWidthError."""
     state = {k: (v if torch.is_tensor(v) else torch.as_tensor(v)) for k, v in state.items()}
+    if hasattr(module, "state_dim"):
+        check_policy_obs_dim(state, module.state_dim, what)
     own = set(module.state_dict().keys())
     missing = sorted(own - set(state) - set(allow_missing))
     unexpected = sorted(set(state) - own)
@@ -135,7 +160,8 @@ def load_bench_policies(policy_ckpt: str, cc_ckpt: str | None = None, device="cu
     from .env import RunningState
     from .nets import PolicyMCP
     cp = load_checkpoint(policy_ckpt)
-    net = load_state_strict(TrajARNet(), split_policy_dict(cp["policy_dict"]), what=policy_ckpt).to(device).float()
+    sd = split_policy_dict(cp["policy_dict"])
+    net = load_state_strict(TrajARNet(use_action=policy_obs_dim(sd) != 101), sd, what=policy_ckpt).to(device).float()     # the width the checkpoint was trained at
     mcp, rs = PolicyMCP(), None
     cc_weights = cp.get("cc_dict")
     if cc_ckpt:

@@ -118,14 +118,22 @@ def gaussian_filter1d_time(x, sigma=1.0, truncate=4.0):
 class TrajARNet(KinPolicy):
     """KinPolicy (the per-step part) + the context network of TrajARNet."""
 
-    def __init__(self, state_dim=105, action_dim=80, context_dim=17, rnn_hdim=1024, mlp_hsize=(1024, 512, 256), htype="relu", log_std=-3.2):
+    def __init__(self, state_dim=None, action_dim=80, context_dim=None, rnn_hdim=1024, mlp_hsize=(1024, 512, 256), htype="relu", log_std=-3.2,
+                 use_action=True):
+        """use_action (kin_poly.yml): the action one-hot is an input of the policy (state 105) and of the context GRU (context 17 = 7 + 6 + 4); False
+        (kin_poly_wo_action.yml): state 101, context 13 (get_context_dim / get_context_feat / get_obs, traj_ar_smpl_net.py:121-167, 281-282)."""
+        state_dim = (105 if use_action else 101) if state_dim is None else state_dim
+        context_dim = (17 if use_action else 13) if context_dim is None else context_dim
         super().__init__(state_dim, action_dim, rnn_hdim, mlp_hsize, htype, log_std)
+        self.use_action = bool(use_action)
         self.context_dim, self.init_dim = context_dim, action_dim + 75
         self.context_rnn = _StepRNN(context_dim, rnn_hdim)
         self.context_mlp = MLP(rnn_hdim, mlp_hsize, htype)
         self.context_fc = nn.Linear(mlp_hsize[-1], self.init_dim)
 
     def _context_input(self, data):
+        if not self.use_action:
+            return torch.cat([data["obj_head_relative_poses"], data["head_vels"]], 2)
         one_hot = data["action_one_hot"]
         T = data["head_vels"].shape[1]
         if one_hot.dim() == 2:
@@ -133,7 +141,7 @@ class TrajARNet(KinPolicy):
         return torch.cat([data["obj_head_relative_poses"], data["head_vels"], one_hot], 2)
 
     def get_context_feat(self, data):
-        """get_context_feat (:138-167): GRU over [obj_head_relative_poses, head_vels, action_one_hot] -> [N, T, rnn_hdim]."""
+        """get_context_feat (:138-167): GRU over [obj_head_relative_poses, head_vels, action_one_hot (use_action)] -> [N, T, rnn_hdim]."""
         feat = self._context_input(data)
         hx = torch.zeros((feat.shape[0], self.rnn_hdim), device=feat.device, dtype=feat.dtype)
         outs = []
@@ -211,6 +219,9 @@ class TrajARNet(KinPolicy):
         """TrajARNet.forward (:346-383) in test mode: kinematic roll-out of the whole clip.
         Returns ar_qpos [N,T,76], ar_qvel [N,T,75] (after fix_qvel), action [N,T,80]."""
         N, T = data["qpos"].shape[:2]
+        if kin_sim.obs_ar_dim != self.state_dim:
+            raise ValueError(f"TrajARNet.rollout: the kinematic simulator writes {kin_sim.obs_ar_dim}-d observations, the policy takes {self.state_dim}-d "
+                             "(a model with ar_obs_action = 0 gives the 101-d observation of use_action: false)")
         dev = init_qpos.device
         one_hot = data["action_one_hot"] if data["action_one_hot"].dim() == 2 else data["action_one_hot"][:, 0]
         cur_t = torch.zeros(N, dtype=torch.int32, device=dev)

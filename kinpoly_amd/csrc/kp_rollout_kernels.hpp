@@ -1,5 +1,6 @@
 // kp_rollout_kernels.hpp -- per-step bookkeeping of the kinematic-policy env and the rollout driver:
-//   k_obs_ar       HumanoidAREnv.get_ar_obs_v1        kin_poly/envs/humanoid_ar_v1.py:133-214 (kin_poly.yml flags)
+//   k_obs_ar       HumanoidAREnv.get_ar_obs_v1        kin_poly/envs/humanoid_ar_v1.py:133-214 (kin_poly.yml flags; <false>: use_action off,
+//                                                      kin_poly_wo_action.yml, :200-201)
 //   k_term_reward  calc_body_diff / calc_body_gt_diff  kin_poly/envs/humanoid_ar_v1.py:435-458
 //                  dynamic_supervision_v1              kin_poly/core/reward_function.py:931-995
 //   k_snapshot     prev_bquat / prev_hpos records      kin_poly/envs/humanoid_ar_v1.py:246-249
@@ -29,12 +30,15 @@ __device__ __forceinline__ int obj_action_start(const float* one_hot) {
 
 __device__ __forceinline__ V3 tv_heading(V3 v, Q4 q) { return q_tmul_vec(q_heading(q), v); }  // transform_vec(v, q, 'heading')
 
+// ACTION: the action one-hot is the last block, o[101..104], of 105-float rows (use_action, kin_poly.yml).  Without it (use_action: false) the rows are
+// the first 101 floats of the same layout at stride 101 (humanoid_ar_v1.py:200-201); the object block o[81..87] still follows the one-hot (:146-147).
+template <bool ACTION>
 __global__ void k_obs_ar(int n, CtxDev C, const float* __restrict__ qpos, const float* __restrict__ xpos, const float* __restrict__ xquat,
                          float* __restrict__ out) {
     int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
     const float* q = qpos + (size_t)e * D_NQ;
-    float* o = out + (size_t)e * 105;
+    float* o = out + (size_t)e * (ACTION ? 105 : 101);
     int t = C.cur_t[e];
     t = t < 0 ? 0 : (t >= C.T ? C.T - 1 : t);
     const int hb = 13;
@@ -61,7 +65,7 @@ __global__ void k_obs_ar(int n, CtxDev C, const float* __restrict__ qpos, const 
     o[88] = hv[3]; o[89] = hv[4]; o[90] = hv[5];
     o[91] = hv[0]; o[92] = hv[1]; o[93] = hv[2];
     for (int k = 0; k < 7; k++) o[94 + k] = orl[k];
-    for (int k = 0; k < 4; k++) o[101 + k] = oh[k];
+    if (ACTION) for (int k = 0; k < 4; k++) o[101 + k] = oh[k];
 }
 
 __global__ void k_snapshot(int n, const float* __restrict__ qpos, const float* __restrict__ xpos, const float* __restrict__ xquat,
@@ -238,11 +242,13 @@ __device__ __forceinline__ void copy_row(float* __restrict__ dst, const float* _
     for (int i = threadIdx.x; i < dim; i += blockDim.x) dst[i] = src[i];
 }
 
+// OBS: the observation width of states / next_states / obs (105, or 101 without the action one-hot): a compile-time row stride, as every other field's
+template <int OBS>
 __global__ void k_record_pre(RecordPre R) {
     const int e = blockIdx.x;
     if (e >= R.n) return;
     const size_t at = (size_t)e * R.T + R.t;
-    if (R.states) copy_row(R.states + at * 105, R.obs + (size_t)e * 105, 105);
+    if (R.states) copy_row(R.states + at * OBS, R.obs + (size_t)e * OBS, OBS);
     if (R.curr_qpos) copy_row(R.curr_qpos + at * 76, R.qpos + (size_t)e * 76, 76);
     const int r = R.row ? R.row[e] : e;
     if (R.gt_target_qpos) {
@@ -257,12 +263,13 @@ __global__ void k_record_pre(RecordPre R) {
     }
 }
 
+template <int OBS>
 __global__ void k_record_post(RecordPost R) {
     const int e = blockIdx.x;
     if (e >= R.n) return;
     const size_t at = (size_t)e * R.T + R.t;
     if (R.actions) copy_row(R.actions + at * 80, R.action + (size_t)e * 80, 80);
-    if (R.next_states) copy_row(R.next_states + at * 105, R.obs + (size_t)e * 105, 105);
+    if (R.next_states) copy_row(R.next_states + at * OBS, R.obs + (size_t)e * OBS, OBS);
     if (R.res_qpos) copy_row(R.res_qpos + at * 76, R.qpos + (size_t)e * 76, 76);
     if (R.cc_actions) copy_row(R.cc_actions + at * 75, R.cc_action + (size_t)e * 75, 75);
     if (R.cc_states) copy_row(R.cc_states + at * 784, R.cc_state + (size_t)e * 784, 784);

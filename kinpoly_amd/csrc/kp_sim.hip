@@ -31,6 +31,7 @@ struct kp_model {
     int contact = 1, limits = 1, stale = 1, solver_iter = 100, threads = 64, dynamic_objects = 1, lpt_order = -1, substeps_per_job = 4, queue_slots = 0, job_taper = 1, queue_fence = 1, queue_heavy = 160, queue_prio = -1, queue_late = -1, job_auto = 1, lean_queue = 1, lean_adaptive = 1, lds_pad = 0, lean_cap = kp::EnvLdsLean::MAXCON;
     float warm_extrap = -1.f;      // < 0: automatic (0.75 when the scene's free objects are simulated, 0 otherwise); see kp_step_kernel.hpp
     int planemesh_max = 3; double planemesh_tol = 0.3;   // mjc_PlaneConvex's maxplanemesh / tolplanemesh (the blob's `planemesh`)
+    int ar_obs_action = 1;        // 0: kp_sim_obs_ar writes the 101-d observation without the action one-hot (use_action: false, humanoid_ar_v1.py:200-201)
     int actuation = 1;            // 0: no stable-PD torque, no residual force (ctrl = qfrc_applied = 0): torque-free flight for the energy test
     double solver_tol = 1e-8, gravity_z = -9.81, gravity_x = 0.0, gravity_y = 0.0;   // solver_iter / solver_tol: mjOption.iterations / tolerance of the reference model (kp_model_load)
 };
@@ -38,6 +39,7 @@ struct kp_model {
 struct kp_sim {
     const kp_model* model = nullptr;
     int n = 0, device = 0;
+    int ar_obs_dim = KP_AR_OBS_DIM;                   // the model's ar_obs_action when the handle was created: KP_AR_OBS_DIM or KP_AR_OBS_DIM_NO_ACTION
     hipStream_t stream = nullptr;
     std::vector<void*> allocs;
     kp::DevTables T{};
@@ -421,6 +423,7 @@ int kp_model_set_option(kp_model* m, const char* name, double v) {
     else if (k == "gravity_x") m->gravity_x = v;
     else if (k == "gravity_y") m->gravity_y = v;
     else if (k == "actuation") m->actuation = v != 0;
+    else if (k == "ar_obs_action") { if (v != 0 && v != 1) return fail("ar_obs_action must be 1 (105-d observation with the action one-hot) or 0 (101-d, use_action: false)"); m->ar_obs_action = (int)v; }
     else if (k == "stale_kinematics") m->stale = v != 0;
     else if (k == "solver_iter") m->solver_iter = (int)v;
     else if (k == "solver_tol") m->solver_tol = v;
@@ -453,6 +456,8 @@ double kp_model_get_option(const kp_model* m, const char* name) {
     if (k == "gravity_x") return m->gravity_x;
     if (k == "gravity_y") return m->gravity_y;
     if (k == "actuation") return m->actuation;
+    if (k == "ar_obs_action") return m->ar_obs_action;
+    if (k == "ar_obs_dim") return m->ar_obs_action ? KP_AR_OBS_DIM : KP_AR_OBS_DIM_NO_ACTION;
     if (k == "stale_kinematics") return m->stale;
     if (k == "solver_iter") return m->solver_iter;
     if (k == "solver_tol") return m->solver_tol;
@@ -489,6 +494,7 @@ kp_sim* kp_sim_create(const kp_model* m, int n_envs, int device_id, void* stream
     HIP_OK_NULL(hipSetDevice(device_id));
     kp_sim* s = new kp_sim();
     s->model = m; s->n = n_envs; s->device = device_id; s->stream = (hipStream_t)stream;
+    s->ar_obs_dim = m->ar_obs_action ? KP_AR_OBS_DIM : KP_AR_OBS_DIM_NO_ACTION;
     bool ok = build_tables(s);
     size_t N = n_envs;
     s->qpos = dalloc(s, N * 76, &ok); s->qvel = dalloc(s, N * 75, &ok); s->qpos_d = dalloc(s, N * 76, &ok);
@@ -841,7 +847,10 @@ int kp_sim_obs_ar(kp_sim* s, const kp_ctx* c, float* out) {
     if (!s || !c || !out || !c->head_pose || !c->head_vels || !c->obj_head_relative_poses || !c->action_one_hot || !c->cur_t || c->T < 1)
         return fail("kp_sim_obs_ar: bad arguments");
     HIP_OK(hipSetDevice(s->device));
-    hipLaunchKernelGGL(kp::k_obs_ar, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, s->n, to_dev(c), s->qpos, s->xpos, s->xquat, out);
+    if (s->ar_obs_dim == KP_AR_OBS_DIM)
+        hipLaunchKernelGGL(kp::k_obs_ar<true>, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, s->n, to_dev(c), s->qpos, s->xpos, s->xquat, out);
+    else
+        hipLaunchKernelGGL(kp::k_obs_ar<false>, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, s->n, to_dev(c), s->qpos, s->xpos, s->xquat, out);
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -916,30 +925,38 @@ int kp_pool_advance(int n, int n_slots, const uint8_t* done, int32_t* head, int3
     return 0;
 }
 
-int kp_rollout_record_pre(const kp_record_pre* r, void* stream) {
+int kp_sim_ar_obs_dim(const kp_sim* s) { return s ? s->ar_obs_dim : -1; }
+
+int kp_rollout_record_pre_w(const kp_record_pre* r, int obs_dim, void* stream) {
     if (!r || r->n <= 0 || r->T <= 0 || r->t < 0 || r->t >= r->T) return fail("kp_rollout_record_pre: bad arguments");
+    if (obs_dim != KP_AR_OBS_DIM && obs_dim != KP_AR_OBS_DIM_NO_ACTION) return fail("kp_rollout_record_pre: obs_dim must be 105 or 101, got " + std::to_string(obs_dim));
     if ((r->states && !r->obs) || (r->episode_start && !r->fresh) || (r->curr_qpos && !r->qpos) || (r->meta && !r->row_meta) ||
         (r->gt_target_qpos && (!r->ctx_qpos || !r->cur_t || !r->row_len || r->ctx_T <= 0)))
         return fail("kp_rollout_record_pre: a destination without its source");
     kp::RecordPre R{r->n, r->T, r->t, r->ctx_T, r->obs, r->fresh, r->qpos, r->ctx_qpos, r->row, r->cur_t, r->row_len, r->row_meta,
                     r->states, r->episode_start, r->curr_qpos, r->gt_target_qpos, r->meta};
-    hipLaunchKernelGGL(kp::k_record_pre, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
+    if (obs_dim == KP_AR_OBS_DIM) hipLaunchKernelGGL(kp::k_record_pre<KP_AR_OBS_DIM>, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
+    else hipLaunchKernelGGL(kp::k_record_pre<KP_AR_OBS_DIM_NO_ACTION>, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
     HIP_OK(hipGetLastError());
     return 0;
 }
+int kp_rollout_record_pre(const kp_record_pre* r, void* stream) { return kp_rollout_record_pre_w(r, KP_AR_OBS_DIM, stream); }
 
-int kp_rollout_record_post(const kp_record_post* r, void* stream) {
+int kp_rollout_record_post_w(const kp_record_post* r, int obs_dim, void* stream) {
     if (!r || r->n <= 0 || r->T <= 0 || r->t < 0 || r->t >= r->T) return fail("kp_rollout_record_post: bad arguments");
+    if (obs_dim != KP_AR_OBS_DIM && obs_dim != KP_AR_OBS_DIM_NO_ACTION) return fail("kp_rollout_record_post: obs_dim must be 105 or 101, got " + std::to_string(obs_dim));
     if ((r->actions && !r->action) || (r->rewards && !r->reward) || (r->fails && !r->fail) || (r->dones && !r->done) || (r->percents && !r->percent) ||
         (r->c_infos && !r->c_info) || (r->next_states && !r->obs) || (r->res_qpos && !r->qpos) || (r->cc_actions && !r->cc_action) ||
         (r->cc_states && !r->cc_state) || (r->v_metas && !r->meta))
         return fail("kp_rollout_record_post: a destination without its source");
     kp::RecordPost R{r->n, r->T, r->t, r->fr_num, r->action, r->reward, r->fail, r->done, r->percent, r->c_info, r->obs, r->qpos, r->cc_action, r->cc_state, r->meta,
                      r->actions, r->rewards, r->fails, r->dones, r->percents, r->c_infos, r->next_states, r->res_qpos, r->cc_actions, r->cc_states, r->v_metas};
-    hipLaunchKernelGGL(kp::k_record_post, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
+    if (obs_dim == KP_AR_OBS_DIM) hipLaunchKernelGGL(kp::k_record_post<KP_AR_OBS_DIM>, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
+    else hipLaunchKernelGGL(kp::k_record_post<KP_AR_OBS_DIM_NO_ACTION>, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
     HIP_OK(hipGetLastError());
     return 0;
 }
+int kp_rollout_record_post(const kp_record_post* r, void* stream) { return kp_rollout_record_post_w(r, KP_AR_OBS_DIM, stream); }
 
 int kp_mcp_compose(int n, int K, int A, const float* logits, const float* prim, const float* noise, int noise_stride, const float* stdv, float* out, void* stream) {
     if (n <= 0 || K <= 0 || K > 64 || A <= 0 || !logits || !prim || !out || (noise && !stdv)) return fail("kp_mcp_compose: bad arguments");

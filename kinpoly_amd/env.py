@@ -43,14 +43,17 @@ class RunningState:
 class BatchedHumanoidAREnv:
     def __init__(self, n_envs, device=0, kpm_path=None, cc_policy: PolicyMCP | None = None,
                  cc_running_state: RunningState | None = None, mode="train", wild=False, joint_controller=False,
-                 env_episode_len=100000, body_diff_thresh=10.0, body_diff_gt_thresh=12.0, model_options=None, seed=0, ar_mode=False):
+                 env_episode_len=100000, body_diff_thresh=10.0, body_diff_gt_thresh=12.0, model_options=None, seed=0, ar_mode=False, use_action=True):
+        """use_action (kin_poly.yml: true): the observation ends with the clip's action one-hot (105 floats); false (kin_poly_wo_action.yml): the first
+        101 of them (humanoid_ar_v1.py:200-201), from a model with the option ar_obs_action = 0 -- every other quantity still reads the one-hot."""
         self.n = int(n_envs)
         self.ar_mode = bool(ar_mode)
         if kpm_path is None:  # agent_ar.py:165-169: mocap training uses ..._all_step.xml, --wild uses ..._all.xml
             kpm_path = kpsim.DEFAULT_KPM if wild else kpsim.STEP_KPM
         self.model_options = dict(model_options or {})
-        self.model = kpsim.KpModel(kpm_path, **self.model_options)
+        self.model = kpsim.KpModel(kpm_path, **(self.model_options if use_action else {**self.model_options, "ar_obs_action": 0}))
         self.sim = kpsim.KpSim(self.model, self.n, device)
+        self.use_action = self.sim.obs_ar_dim == kpsim.AR_OBS_DIM
         self.device = self.sim.device
         self.mode, self.wild, self.joint_controller = mode, wild, joint_controller
         self.env_episode_len = env_episode_len
@@ -72,10 +75,10 @@ class BatchedHumanoidAREnv:
         self._row_obj_qpos = None  # [R,35] = convert_obj_qpos(action_one_hot, obj_pose[0]) of every context row
         self._ctx_struct = None
         self.end_reward = 0.0
-        self.action_dim, self.obs_dim, self.cc_action_dim = 80, kpsim.AR_OBS_DIM, kpsim.CC_ACTION_DIM
+        self.action_dim, self.obs_dim, self.cc_action_dim = 80, self.sim.obs_ar_dim, kpsim.CC_ACTION_DIM
         # persistent I/O buffers (no per-step allocation)
         f = lambda d: torch.empty((self.n, d), dtype=torch.float32, device=self.device)  # noqa: E731
-        self._next_qpos, self._cc_obs, self._obs, self._obs_next = f(76), f(784), f(105), f(105)
+        self._next_qpos, self._cc_obs, self._obs, self._obs_next = f(76), f(784), f(self.obs_dim), f(self.obs_dim)
         # what step() hands back lives in two alternating sets of buffers: a returned tensor stays valid until the next-but-one step()
         u8 = lambda: torch.empty(self.n, dtype=torch.uint8, device=self.device)  # noqa: E731
         self._outs = [dict(reward=torch.empty(self.n, device=self.device), info=f(6), diffs=f(2), fail=u8(), done=u8(), end=u8(),
@@ -451,7 +454,7 @@ class _ModelView:
 class HumanoidAREnv:
     """Single-environment facade with the reference constructor and numpy float64 I/O
     (kin_poly/envs/humanoid_ar_v1.py:28).  `cfg` / `cc_cfg` are duck-typed: only `policy_specs` thresholds,
-    `joint_controller`, `env_episode_len` are read if present; a trained UHC checkpoint can be passed as
+    `joint_controller`, `env_episode_len`, `use_action` are read if present; a trained UHC checkpoint can be passed as
     `cc_state=(policy_dict, running_state mean, std)`."""
 
     def __init__(self, cfg=None, cc_cfg=None, init_context=None, cc_iter=-1, mode="train", wild=False, ar_mode=False, cc_state=None, device=0):
@@ -464,7 +467,8 @@ class HumanoidAREnv:
         self.b = BatchedHumanoidAREnv(1, device, cc_policy=pol, cc_running_state=rs, mode=mode, wild=wild,
                                       joint_controller=bool(getattr(cfg, "joint_controller", False)),
                                       env_episode_len=int(getattr(cc_cfg, "env_episode_len", 100000)),
-                                      body_diff_thresh=ps.get("body_diff_thresh", 10), body_diff_gt_thresh=ps.get("body_diff_gt_thresh", 12), ar_mode=ar_mode)
+                                      body_diff_thresh=ps.get("body_diff_thresh", 10), body_diff_gt_thresh=ps.get("body_diff_gt_thresh", 12), ar_mode=ar_mode,
+                                      use_action=bool(getattr(cfg, "use_action", True)))
         self.kin_cfg, self.cc_cfg, self.ar_mode, self.wild, self.mode = cfg, cc_cfg, ar_mode, wild, mode
         self.cc_policy, self.cc_running_state = self.b.cc_policy, self.b.cc_running_state
         self.dt, self.end_reward = self.b.dt, 0.0
@@ -476,7 +480,7 @@ class HumanoidAREnv:
         self.num_obj, self.action_index_map, self.action_len = 5, list(ACTION_INDEX_MAP), list(ACTION_LEN)
         self.action_names = ["sit", "push", "avoid", "step"]
         self.ndof, self.vf_dim, self.cc_action_dim = 69, 6, 75
-        self.action_dim, self.obs_dim = 75, kpsim.AR_OBS_DIM      # set_spaces() (:106-112): the Box is 75-d although step() takes the 80-d kinematic action
+        self.action_dim, self.obs_dim = 75, self.b.obs_dim        # set_spaces() (:106-112): the Box is 75-d although step() takes the 80-d kinematic action
         self.action_space = Box(-np.ones(self.action_dim), np.ones(self.action_dim))
         self.observation_space = Box(-np.inf * np.ones(self.obs_dim), np.inf * np.ones(self.obs_dim))
         self.body_diff_thresh, self.body_diff_gt_thresh = ps.get("body_diff_thresh", 10), ps.get("body_diff_gt_thresh", 12)

@@ -33,7 +33,7 @@ from .nets import KinPolicy, Value
 @dataclass
 class RolloutBatch:
     """TrajBatchEgo (kin_poly/core/trajbatch_ego.py:5-14 over uhc/khrylib/rl/core/trajbatch.py:4-16), env-major [N, T, .]."""
-    states: torch.Tensor         # [N, T, 105]
+    states: torch.Tensor         # [N, T, 105] (101 without the action one-hot: env.obs_dim)
     actions: torch.Tensor        # [N, T, 80]
     rewards: torch.Tensor        # [N, T]
     masks: torch.Tensor          # [N, T]   0 where the episode ended at this row
@@ -378,12 +378,12 @@ class VectorSampler:
         if self.obs is None:
             self.start()
         f = lambda *s: torch.empty((N, T, *s), device=dev)  # noqa: E731
-        S, A, R = f(105), f(80), f()
+        S, A, R = f(env.obs_dim), f(80), f()
         E = torch.empty((N, T), dtype=torch.bool, device=dev); F = torch.empty((N, T), dtype=torch.bool, device=dev)
         Q = f(76) if self.record_qpos else None
         G = f(76) if self.record_qpos else None
         full = self.record_full
-        NS, VM, RQ, CA, CS = (f(105), f(3), f(76), f(75), f(784)) if full else (None,) * 5
+        NS, VM, RQ, CA, CS = (f(env.obs_dim), f(3), f(76), f(75), f(784)) if full else (None,) * 5
         D = torch.empty((N, T), dtype=torch.bool, device=dev); PC = f(); MT = f(2); CI = f(6)
         hx0 = self.hx.clone()
         fr_num = float(env.ctx["qpos"].shape[1])
@@ -404,14 +404,15 @@ class VectorSampler:
             # Memory.push, first half (one launch): state, episode start, the pose before the step, the GT pose of the clip's next frame, (take, fr_start)
             kpsim.record_pre(t, T, obs=self.obs, fresh=self.fresh, qpos=qview if self.record_qpos else None, ctx_qpos=env.ctx["qpos"] if self.record_qpos else None,
                              row=env.row, cur_t=env.cur_t, row_len=env.row_len, row_meta=env.row_meta,
-                             states=S, episode_start=E, curr_qpos=Q, gt_target_qpos=G, meta=MT)
+                             states=S, episode_start=E, curr_qpos=Q, gt_target_qpos=G, meta=MT, obs_dim=env.obs_dim)
             action, self.hx = pol.select_action(self.obs, self.hx, self.mean_action, env.gen, nz[:, :n_kin] if n_kin else None)
             action = action.contiguous()
             obs, _, done, info = env.step(action, need_obs=full, cc_noise=nz[:, n_kin:] if n_cc else None)
             # second half (one launch): action, reward, flags, custom_info and -- full record -- next state, pose after the step, UHC action / state, v_meta
             kpsim.record_post(t, T, fr_num, action=action, reward=info["custom_reward"], fail=info["fail"], done=done, percent=info["percent"], c_info=info["custom_info"],
                               obs=obs if full else None, qpos=qview if full else None, cc_action=info["cc_action"] if full else None, cc_state=info["cc_state"] if full else None,
-                              meta=MT, actions=A, rewards=R, fails=F, dones=D, percents=PC, c_infos=CI, next_states=NS, res_qpos=RQ, cc_actions=CA, cc_states=CS, v_metas=VM)
+                              meta=MT, actions=A, rewards=R, fails=F, dones=D, percents=PC, c_infos=CI, next_states=NS, res_qpos=RQ, cc_actions=CA, cc_states=CS, v_metas=VM,
+                              obs_dim=env.obs_dim)
             # device-side episode turnover: a finished env moves to the next clip of its ring (env.row in place), then the masked reset
             if self.source is not None:
                 kpsim.pool_advance(done, self.head, self.ahead, env.row, self.n_slots)

@@ -17,6 +17,7 @@ from . import build as _build
 
 NQ, NV, NU, NBODY = 76, 75, 69, 24
 CC_OBS_DIM, AR_OBS_DIM, KIN_ACTION_DIM, CC_ACTION_DIM = 784, 105, 80, 75
+AR_OBS_DIM_NO_ACTION = 101      # get_ar_obs_v1 without the action one-hot (use_action: false): model option ar_obs_action = 0
 DEFAULT_KPM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets", "smpl_humanoid.kpm")
 STEP_KPM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets", "smpl_humanoid_step.kpm")
 
@@ -36,7 +37,7 @@ ABI_SYMBOLS = [
     "kp_sim_launch_cost", "kp_job_schedule", "kp_sim_fk_backward", "kp_sim_set_stream", "kp_sim_status_device", "kp_sim_mass_matrix",
     "kp_sim_contacts", "kp_gae_bootstrap", "kp_gru_gates_forward", "kp_gru_gates_backward", "kp_sim_phase_cycles_env",
     "kp_sim_post_step", "kp_sim_reset_rows", "kp_mcp_compose", "kp_sim_step_head", "kp_model_compile", "kp_model_load_xml",
-    "kp_mcp_tail", "kp_gru_cell_step", "kp_kin_advance", "kp_pool_advance", "kp_rollout_record_pre", "kp_rollout_record_post", "kp_sim_field_device",
+    "kp_mcp_tail", "kp_gru_cell_step", "kp_kin_advance", "kp_pool_advance", "kp_rollout_record_pre", "kp_rollout_record_post", "kp_rollout_record_pre_w", "kp_rollout_record_post_w", "kp_sim_ar_obs_dim", "kp_sim_field_device",
     "kp_sim_lean_state", "kp_sim_pose_contacts",
 ]
 
@@ -107,6 +108,7 @@ def load_library(path: str | None = None):
     L.kp_sim_last_step_seconds.argtypes = [P]; L.kp_sim_last_step_seconds.restype = C.c_double
     L.kp_sim_step_begin.argtypes = [P]; L.kp_sim_step_begin.restype = C.c_int
     L.kp_sim_obs_ar.argtypes = [P, C.POINTER(KpCtx), F]; L.kp_sim_obs_ar.restype = C.c_int
+    L.kp_sim_ar_obs_dim.argtypes = [P]; L.kp_sim_ar_obs_dim.restype = C.c_int
     L.kp_sim_term_reward.argtypes = [P, C.POINTER(KpCtx), C.POINTER(KpRewardCfg), F, F, U8, F]; L.kp_sim_term_reward.restype = C.c_int
     L.kp_sim_post_step.argtypes = [P, C.POINTER(KpCtx), C.POINTER(KpRewardCfg), C.c_void_p, C.c_void_p, C.c_int, F, F, U8, F, U8, U8, F, C.c_void_p, F]; L.kp_sim_post_step.restype = C.c_int
     L.kp_sim_reset_rows.argtypes = [P, F, F, C.c_void_p, U8, C.c_void_p, C.c_int, F, C.c_int, F, F, F]; L.kp_sim_reset_rows.restype = C.c_int
@@ -114,6 +116,8 @@ def load_library(path: str | None = None):
     L.kp_sim_field_device.argtypes = [P, C.c_int]; L.kp_sim_field_device.restype = C.c_void_p
     L.kp_rollout_record_pre.argtypes = [C.POINTER(KpRecordPre), C.c_void_p]; L.kp_rollout_record_pre.restype = C.c_int
     L.kp_rollout_record_post.argtypes = [C.POINTER(KpRecordPost), C.c_void_p]; L.kp_rollout_record_post.restype = C.c_int
+    L.kp_rollout_record_pre_w.argtypes = [C.POINTER(KpRecordPre), C.c_int, C.c_void_p]; L.kp_rollout_record_pre_w.restype = C.c_int
+    L.kp_rollout_record_post_w.argtypes = [C.POINTER(KpRecordPost), C.c_int, C.c_void_p]; L.kp_rollout_record_post_w.restype = C.c_int
     L.kp_mcp_tail.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, F, F, F, C.c_int, F, F, F, C.c_int, F, F, C.c_void_p]; L.kp_mcp_tail.restype = C.c_int
     L.kp_kin_advance.argtypes = [C.c_int, F, F, C.c_float, F, F, C.c_void_p]; L.kp_kin_advance.restype = C.c_int
     L.kp_gru_cell_step.argtypes = [C.c_int, C.c_int, C.c_int, F, F, F, F, F, F, F, F, C.c_void_p]; L.kp_gru_cell_step.restype = C.c_int
@@ -214,6 +218,7 @@ class KpSim:
         if not self.h:
             raise KinPolyNativeError(f"kp_sim_create: {self.L.kp_last_error().decode()}")
         self._stream = stream
+        self.obs_ar_dim = int(self.L.kp_sim_ar_obs_dim(self.h))      # AR_OBS_DIM, or AR_OBS_DIM_NO_ACTION for a model with ar_obs_action = 0
 
     def use_current_stream(self):
         """Enqueue all later calls on torch's current stream of this device (the caller orders the old and the new stream)."""
@@ -393,8 +398,8 @@ class KpSim:
         return ctx
 
     def obs_ar(self, ctx: "KpCtx", out=None):
-        out = self._new(AR_OBS_DIM) if out is None else out
-        _check(self.L.kp_sim_obs_ar(self.h, C.byref(ctx), _ptr(out, self.n, AR_OBS_DIM)), "kp_sim_obs_ar")
+        out = self._new(self.obs_ar_dim) if out is None else out
+        _check(self.L.kp_sim_obs_ar(self.h, C.byref(ctx), _ptr(out, self.n, self.obs_ar_dim)), "kp_sim_obs_ar")
         return out
 
     def term_reward(self, ctx: "KpCtx", cfg: "KpRewardCfg", reward=None, info=None, fail=None, diffs=None):
@@ -490,6 +495,12 @@ def _dptr(t, dtype=None, name="tensor"):
     return t.data_ptr()
 
 
+def _obs_width(obs_dim):
+    if obs_dim not in (AR_OBS_DIM, AR_OBS_DIM_NO_ACTION):
+        raise ValueError(f"obs_dim must be {AR_OBS_DIM} or {AR_OBS_DIM_NO_ACTION} (without the action one-hot), got {obs_dim}")
+    return int(obs_dim)
+
+
 def _want(name, x, *shape):
     """the record kernels index their buffers with fixed row widths (kp_rollout_kernels.hpp): a tensor of another shape would be read / written out of bounds"""
     if x is not None and tuple(x.shape) != tuple(shape):
@@ -497,14 +508,16 @@ def _want(name, x, *shape):
 
 
 def record_pre(t: int, T: int, obs=None, fresh=None, qpos=None, ctx_qpos=None, row=None, cur_t=None, row_len=None, row_meta=None,
-               states=None, episode_start=None, curr_qpos=None, gt_target_qpos=None, meta=None):
-    """kp_rollout_record_pre: the before-the-step half of the sampler's per-step record, one launch (see include/kinpoly_sim.h)."""
+               states=None, episode_start=None, curr_qpos=None, gt_target_qpos=None, meta=None, obs_dim=AR_OBS_DIM):
+    """kp_rollout_record_pre: the before-the-step half of the sampler's per-step record, one launch (see include/kinpoly_sim.h).
+    obs_dim: the width of obs / states (the env's KpSim.obs_ar_dim)."""
     L = load_library()
+    obs_dim = _obs_width(obs_dim)
     first = next(x for x in (obs, qpos, fresh) if x is not None)
     f32, i32, u8 = torch.float32, torch.int32, torch.uint8
     n = first.shape[0]
-    _want("obs", obs, n, AR_OBS_DIM); _want("fresh", fresh, n); _want("qpos", qpos, n, 76); _want("row", row, n); _want("cur_t", cur_t, n)
-    _want("states", states, n, T, AR_OBS_DIM); _want("episode_start", episode_start, n, T); _want("curr_qpos", curr_qpos, n, T, 76)
+    _want("obs", obs, n, obs_dim); _want("fresh", fresh, n); _want("qpos", qpos, n, 76); _want("row", row, n); _want("cur_t", cur_t, n)
+    _want("states", states, n, T, obs_dim); _want("episode_start", episode_start, n, T); _want("curr_qpos", curr_qpos, n, T, 76)
     _want("gt_target_qpos", gt_target_qpos, n, T, 76); _want("meta", meta, n, T, 2)
     if ctx_qpos is not None and (ctx_qpos.dim() != 3 or ctx_qpos.shape[2] != 76):
         raise ValueError(f"ctx_qpos: expected [R, T_ctx, 76], got {tuple(ctx_qpos.shape)}")
@@ -512,27 +525,29 @@ def record_pre(t: int, T: int, obs=None, fresh=None, qpos=None, ctx_qpos=None, r
                     _dptr(obs, f32, "obs"), _dptr(fresh, u8, "fresh"), _dptr(qpos, f32, "qpos"), _dptr(ctx_qpos, f32, "ctx_qpos"), _dptr(row, i32, "row"), _dptr(cur_t, i32, "cur_t"),
                     _dptr(row_len, i32, "row_len"), _dptr(row_meta, f32, "row_meta"), _dptr(states, f32, "states"), _dptr(episode_start, u8, "episode_start"),
                     _dptr(curr_qpos, f32, "curr_qpos"), _dptr(gt_target_qpos, f32, "gt_target_qpos"), _dptr(meta, f32, "meta"))
-    _check(L.kp_rollout_record_pre(C.byref(r), C.c_void_p(torch.cuda.current_stream(first.device).cuda_stream)), "kp_rollout_record_pre")
+    _check(L.kp_rollout_record_pre_w(C.byref(r), obs_dim, C.c_void_p(torch.cuda.current_stream(first.device).cuda_stream)), "kp_rollout_record_pre")
 
 
 def record_post(t: int, T: int, fr_num=0.0, action=None, reward=None, fail=None, done=None, percent=None, c_info=None, obs=None, qpos=None, cc_action=None, cc_state=None, meta=None,
-                actions=None, rewards=None, fails=None, dones=None, percents=None, c_infos=None, next_states=None, res_qpos=None, cc_actions=None, cc_states=None, v_metas=None):
-    """kp_rollout_record_post: the after-the-step half (one launch)."""
+                actions=None, rewards=None, fails=None, dones=None, percents=None, c_infos=None, next_states=None, res_qpos=None, cc_actions=None, cc_states=None, v_metas=None,
+                obs_dim=AR_OBS_DIM):
+    """kp_rollout_record_post: the after-the-step half (one launch); obs_dim: the width of obs / next_states."""
     L = load_library()
+    obs_dim = _obs_width(obs_dim)
     first = next(x for x in (action, reward, done) if x is not None)
     f32, u8 = torch.float32, torch.uint8
     n = first.shape[0]
     _want("action", action, n, 80); _want("reward", reward, n); _want("fail", fail, n); _want("done", done, n); _want("percent", percent, n); _want("c_info", c_info, n, 6)
-    _want("obs", obs, n, AR_OBS_DIM); _want("qpos", qpos, n, 76); _want("cc_action", cc_action, n, CC_ACTION_DIM); _want("cc_state", cc_state, n, CC_OBS_DIM); _want("meta", meta, n, T, 2)
+    _want("obs", obs, n, obs_dim); _want("qpos", qpos, n, 76); _want("cc_action", cc_action, n, CC_ACTION_DIM); _want("cc_state", cc_state, n, CC_OBS_DIM); _want("meta", meta, n, T, 2)
     _want("actions", actions, n, T, 80); _want("rewards", rewards, n, T); _want("fails", fails, n, T); _want("dones", dones, n, T); _want("percents", percents, n, T)
-    _want("c_infos", c_infos, n, T, 6); _want("next_states", next_states, n, T, AR_OBS_DIM); _want("res_qpos", res_qpos, n, T, 76); _want("cc_actions", cc_actions, n, T, CC_ACTION_DIM)
+    _want("c_infos", c_infos, n, T, 6); _want("next_states", next_states, n, T, obs_dim); _want("res_qpos", res_qpos, n, T, 76); _want("cc_actions", cc_actions, n, T, CC_ACTION_DIM)
     _want("cc_states", cc_states, n, T, CC_OBS_DIM); _want("v_metas", v_metas, n, T, 3)
     r = KpRecordPost(first.shape[0], int(T), int(t), float(fr_num), _dptr(action, f32, "action"), _dptr(reward, f32, "reward"), _dptr(fail, u8, "fail"), _dptr(done, u8, "done"),
                      _dptr(percent, f32, "percent"), _dptr(c_info, f32, "c_info"), _dptr(obs, f32, "obs"), _dptr(qpos, f32, "qpos"), _dptr(cc_action, f32, "cc_action"),
                      _dptr(cc_state, f32, "cc_state"), _dptr(meta, f32, "meta"), _dptr(actions, f32, "actions"), _dptr(rewards, f32, "rewards"), _dptr(fails, u8, "fails"),
                      _dptr(dones, u8, "dones"), _dptr(percents, f32, "percents"), _dptr(c_infos, f32, "c_infos"), _dptr(next_states, f32, "next_states"), _dptr(res_qpos, f32, "res_qpos"),
                      _dptr(cc_actions, f32, "cc_actions"), _dptr(cc_states, f32, "cc_states"), _dptr(v_metas, f32, "v_metas"))
-    _check(L.kp_rollout_record_post(C.byref(r), C.c_void_p(torch.cuda.current_stream(first.device).cuda_stream)), "kp_rollout_record_post")
+    _check(L.kp_rollout_record_post_w(C.byref(r), obs_dim, C.c_void_p(torch.cuda.current_stream(first.device).cuda_stream)), "kp_rollout_record_post")
 
 
 def pool_advance(done: torch.Tensor, head: torch.Tensor, ahead: torch.Tensor, row: torch.Tensor, n_slots: int):

@@ -60,13 +60,16 @@ def main():
         args.result_dir, args.data_file, T = cfg.result_dir, cfg.data_file, int(cfg.fr_num)
         if args.iter > 0 and not args.ckpt:
             args.ckpt = cfg.checkpoint_path(args.iter)
-    env = BatchedHumanoidAREnv(n, 0, mode="test", wild=args.wild, ar_mode=args.ar_mode, seed=0)
+    use_action = cfg.use_action if cfg is not None else True          # false: kin_poly_wo_action.yml, the 101-d observation
+    env = BatchedHumanoidAREnv(n, 0, mode="test", wild=args.wild, ar_mode=args.ar_mode, seed=0, use_action=use_action)
     if cfg is not None:
         cfg.apply_reward_weights(env)
-    net = TrajARNet(log_std=cfg.policy_specs["log_std"] if cfg else -3.2).to(env.device)
+    net = TrajARNet(log_std=cfg.policy_specs["log_std"] if cfg else -3.2, use_action=use_action).to(env.device)
     if args.ckpt:
         cp = ck.load_checkpoint(args.ckpt)
-        net.load_state_dict(ck.split_policy_dict(cp["policy_dict"]), strict=False)
+        sd = ck.split_policy_dict(cp["policy_dict"])
+        ck.check_policy_obs_dim(sd, net.state_dim, args.ckpt)
+        net.load_state_dict(sd, strict=False)
     if args.data:                                   # every take of the feature file, whole, env.n at a time (run_seq over data_loader.iter_seq)
         from kinpoly_amd import dataset as D
         from kinpoly_amd.evaluate import eval_dataset
