@@ -97,7 +97,17 @@ void kp_model_free(kp_model*);
  * depend on how a control step is cut into jobs.
  * "ar_obs_action" (1 / 0, default 1; anything else fails): the kinematic observation of a kp_sim created afterwards from this model -- 1: KP_AR_OBS_DIM
  * floats with the action one-hot (use_action), 0: the first KP_AR_OBS_DIM_NO_ACTION of them (use_action: false, humanoid_ar_v1.py:200-201).
- * kp_model_get_option also answers "ar_obs_dim" (105 or 101). */
+ * kp_model_get_option also answers "ar_obs_dim" (105 or 101).
+ * The UHC config's observation (kp_sim_obs_cc_ex of a kp_sim created afterwards; humanoid_im.py:105-318), each 0 / 1 unless said otherwise, anything
+ * else fails: "cc_obs_v" (0 get_full_obs, 1 get_full_obs_v1 = default, 2 get_full_obs_v2), "cc_obs_vel_root" (obs_vel 'root': qvel[:6] instead of the
+ * 75 of 'full'), and obs_v 0's "cc_obs_heading", "cc_obs_deheading", "cc_obs_phase" (obs_heading, root_deheading, obs_phase; ignored by obs_v 1 / 2).
+ * kp_model_get_option also answers "cc_obs_dim" (784 / 715 for obs_v 1 full / root, 640 / 571 for obs_v 2, heading + 74 + (75 | 6) + 69 + phase for
+ * obs_v 0) and "cc_action_dim".
+ * The UHC controller (kp_sim_step_ctrl of a kp_sim created afterwards; humanoid_im.py:433-524): "cc_action_v" (1 default: PD base pose = the target row
+ * unwrapped to within pi of qpos; 0: the target row as it is, the caller installs cfg.a_ref), "cc_rfc" (1 default: implicit residual force from action
+ * [69:75]; 0: none), "cc_meta_pd" (0 default; 1 meta_pd: kp / kd x clip(m + 1, 0, 10) with m = action[m0 + substep] / [m0 + substep + 15], at most 15
+ * substeps per call; 2 meta_pd_joint: by joint, [m0 + j] / [m0 + 69 + j]; m0 = 69 + 6 cc_rfc).  cc_action_dim = 69 + 6 cc_rfc + (30 | 138 | 0); any
+ * other value fails.  A non-default controller runs on the full layout (no lean job-queue form). */
 int kp_model_set_option(kp_model*, const char* name, double value);
 double kp_model_get_option(const kp_model*, const char* name);
 
@@ -163,7 +173,8 @@ int kp_sim_pose_contacts(kp_sim*, int n_rows, const float* xpos, const float* xq
 int kp_sim_fk_backward(kp_sim*, int n_rows, const float* qpos, const float* wbpos, const float* wbquat, const float* grad_wbpos, float* grad_qpos);
 
 /* HumanoidEnv.do_simulation(cc_action, n_substeps)   (humanoid_im.py:506-533): per substep stable-PD
- * torque (compute_torque :433-480), clip, rfc_implicit (:497-504), sim.step() (:527).  cc_action [N,75]. */
+ * torque (compute_torque :433-480), clip, rfc_implicit (:497-504), sim.step() (:527).  cc_action [N, cc_action_dim] (75 for a default model; the
+ * width of the model's cc_rfc / cc_meta_pd when the handle was created). */
 int kp_sim_step_ctrl(kp_sim*, const float* cc_action, int n_substeps, const uint8_t* env_mask);
 
 /* HumanoidAREnv.step_ar(a)   (humanoid_ar_v1.py:216-241): kin_action [N,80] -> next_qpos [N,76] */
@@ -176,6 +187,15 @@ int kp_sim_step_head(kp_sim*, const float* kin_action);
 /* get_full_obs_v1() [N,784]   (humanoid_im.py:144-233), optional ZFilter(update=False) + clip
  * (zfilter.py:58-67): pass mean/std [784] device pointers or NULL, clip <= 0 disables clipping. */
 int kp_sim_obs_cc(kp_sim*, float* out, const float* zf_mean, const float* zf_std, float clip);
+
+/* The observation the handle's cc_obs_* options select (kp_model_set_option; fixed when the handle is created), [N, kp_sim_cc_obs_dim] with the same
+ * optional ZFilter + clip (zf_mean / zf_std of that width).  obs_v 1 / 2 read the target as kp_sim_obs_cc does (the caller installs expert frame t + 1);
+ * obs_v 0 reads only the target's joint angles, as get_expert_kin_pose(delta_t=0) (:679): the caller installs expert frame t.  phase: device float [N]
+ * = cur_t / expert len, required when the handle has cc_obs_phase (obs_v 0), and must be NULL otherwise.  A default handle writes exactly what
+ * kp_sim_obs_cc writes (the same kernel).  kp_sim_obs_cc itself always writes the 784-d uhc.yml layout. */
+int kp_sim_obs_cc_ex(kp_sim*, float* out, const float* zf_mean, const float* zf_std, float clip, const float* phase);
+/* the handle's width of kp_sim_obs_cc_ex (-1 for NULL) */
+int kp_sim_cc_obs_dim(const kp_sim*);
 
 /* per-episode context rows the env reads each step (ar_context, humanoid_ar_v1.py:84-88).
  * Arrays are [R, T, dim] device pointers (action_one_hot [R, 4]), R >= N context rows; env e reads row `row[e]` (int32 [N], or

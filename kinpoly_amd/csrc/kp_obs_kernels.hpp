@@ -2,6 +2,7 @@
 //   k_step_kin     HumanoidAREnv.step_ar                kin_poly/envs/humanoid_ar_v1.py:216-241
 //   k_target_fk    Humanoid.qpos_fk / forward_kinematics kin_poly/utils/numpy_smpl_humanoid.py:180-249
 //   k_obs_cc       HumanoidEnv.get_full_obs_v1 (+ZFilter) uhc/envs/humanoid_im.py:144-233, zfilter.py:58-67
+//   k_obs_cc_v     get_full_obs / _v1 / _v2 per the UHC config     uhc/envs/humanoid_im.py:105-318
 //   k_bquat        HumanoidEnv.get_body_quat            uhc/envs/humanoid_im.py:342-354
 // Quaternion helpers restate uhc/khrylib/utils/math.py:102-198 and transformation.py (Gohlke).
 #pragma once
@@ -272,7 +273,7 @@ __global__ void k_bquat(int n, const float* __restrict__ qpos, float* __restrict
     o[0] = r.w; o[1] = r.x; o[2] = r.y; o[3] = r.z;
 }
 
-// ---------------------------------------------------------------- get_full_obs_v1 (+ ZFilter): one wave per env, staged in LDS
+// ---------------------------------------------------------------- get_full_obs / _v1 / _v2 (+ ZFilter): one wave per env, staged in LDS
 struct ObsCcArgs {
     int n;
     const float *qpos, *qvel, *xpos, *xquat, *xipos;   // sim state (qpos/qvel fresh, x* stale)
@@ -281,66 +282,101 @@ struct ObsCcArgs {
     const float *zf_mean, *zf_std; float clip;
     float* out;
 };
-__global__ __launch_bounds__(64) void k_obs_cc(ObsCcArgs A) {
-    __shared__ float ob[784];
+// The UHC config's observation switches (uhc/envs/humanoid_im.py:105-318): V = obs_v (0: get_full_obs, 1: get_full_obs_v1, 2: get_full_obs_v2 = v1
+// without the two COM blocks); VROOT: obs_vel 'root' (qvel[:6]) instead of 'full' (75); HEAD / DEHEAD / PHASE: obs_v 0's obs_heading, root_deheading
+// and obs_phase (the other versions ignore them).  D is the row width.
+template <int V, bool VROOT, bool HEAD, bool DEHEAD, bool PHASE>
+struct ObsCcLayout {
+    static constexpr int LV = VROOT ? 6 : 75;
+    static constexpr int D = V == 0 ? (HEAD ? 1 : 0) + 74 + LV + 69 + (PHASE ? 1 : 0) : 229 + LV + (V == 1 ? 4 : 2) * 72 + 2 * 96;
+};
+template <int V, bool VROOT, bool HEAD, bool DEHEAD, bool PHASE>
+__device__ __forceinline__ void obs_cc_body(const ObsCcArgs& A, const float* __restrict__ phase) {
+    using L = ObsCcLayout<V, VROOT, HEAD, DEHEAD, PHASE>;
+    constexpr int LV = L::LV, D = L::D;
+    __shared__ float ob[D];
     const int e = blockIdx.x, tid = threadIdx.x;
     if (e >= A.n) return;
     const float* qpos = A.qpos + (size_t)e * D_NQ;
     const float* qvel = A.qvel + (size_t)e * D_NV;
     const float* tq = A.t_qpos + (size_t)e * D_NQ;
     const Q4 rq = Q4{qpos[3], qpos[4], qpos[5], qpos[6]};
-    const Q4 binv = Q4{A.br_inv[0], A.br_inv[1], A.br_inv[2], A.br_inv[3]};
-    const Q4 crq = qmul(rq, binv);                      // remove_base_rot
-    const Q4 hq = q_heading(crq);
-    const Q4 trq = qmul(Q4{tq[3], tq[4], tq[5], tq[6]}, binv);
-    const V3 root = v3(qpos[0], qpos[1], qpos[2]);
-    if (tid == 0) {
-        ob[0] = hq.w; ob[1] = hq.x; ob[2] = hq.y; ob[3] = hq.z;
-        Q4 dh = qmul(q_inverse(hq), crq);               // de_heading(curr_root_quat)
-        ob[78] = qpos[2]; ob[79] = dh.w; ob[80] = dh.x; ob[81] = dh.y; ob[82] = dh.z;
-        Q4 dq = qmul(trq, q_inverse(crq));
-        ob[152] = tq[2] - qpos[2]; ob[153] = dq.w; ob[154] = dq.x; ob[155] = dq.y; ob[156] = dq.z;
-        V3 v = q_tmul_vec(crq, q_tmul_vec(rq, v3(qvel[0], qvel[1], qvel[2])));  // transformed twice (:150, :173)
-        ob[226] = v.x; ob[227] = v.y; ob[228] = v.z;
-        float rel_h = heading_angle(trq) - heading_angle(crq);
-        if (rel_h > 3.14159265358979f) rel_h -= 6.28318530717959f;
-        if (rel_h < -3.14159265358979f) rel_h += 6.28318530717959f;
-        ob[301] = rel_h;
-        V3 rp = q_tmul_vec(crq, v3(trq.w, trq.x, trq.y) - root);  // sic: quaternion components used as a position (:187)
-        ob[302] = rp.x; ob[303] = rp.y;
-    }
-    for (int i = tid; i < 74; i += 64) ob[4 + i] = tq[2 + i];
-    for (int i = tid; i < 69; i += 64) { ob[83 + i] = qpos[7 + i]; ob[157 + i] = tq[7 + i] - qpos[7 + i]; }
-    for (int i = tid; i < 72; i += 64) ob[229 + i] = qvel[3 + i];
-    if (tid < D_NB) {
-        const int b = tid;
-        const float* xp = A.xpos + (size_t)e * 72 + 3 * b;
-        const float* xi = A.xipos + (size_t)e * 72 + 3 * b;
-        const float* xq = A.xquat + (size_t)e * 96;
-        V3 cj = ld3(xp), ci = ld3(xi);
-        V3 tj = ld3(A.t_wbpos + (size_t)e * 72 + 3 * b), tc = ld3(A.t_com + (size_t)e * 72 + 3 * b);
-        // transform_vec_batch returns a (3, 24) array that the reference ravel()s: component-major blocks
-        V3 p1 = q_tmul_vec(crq, cj - root), p2 = q_tmul_vec(crq, tj - cj), p3 = q_tmul_vec(crq, ci - root), p4 = q_tmul_vec(crq, tc - ci);
-        ob[304 + b] = p1.x; ob[328 + b] = p1.y; ob[352 + b] = p1.z;
-        ob[376 + b] = p2.x; ob[400 + b] = p2.y; ob[424 + b] = p2.z;
-        ob[448 + b] = p3.x; ob[472 + b] = p3.y; ob[496 + b] = p3.z;
-        ob[520 + b] = p4.x; ob[544 + b] = p4.y; ob[568 + b] = p4.z;
-        const float* twq = A.t_wbquat + (size_t)e * 96 + 4 * b;
-        Q4 tqt = Q4{twq[0], twq[1], twq[2], twq[3]};
-        Q4 cq = (xq[0] == 0.f) ? tqt : Q4{xq[4 * b], xq[4 * b + 1], xq[4 * b + 2], xq[4 * b + 3]};
-        Q4 r1 = qmul(q_inverse(hq), cq), r2 = qmul(q_inverse(cq), tqt);
-        float* o1 = ob + 592 + 4 * b; o1[0] = r1.w; o1[1] = r1.x; o1[2] = r1.y; o1[3] = r1.z;
-        float* o2 = ob + 688 + 4 * b; o2[0] = r2.w; o2[1] = r2.x; o2[2] = r2.y; o2[3] = r2.z;
+    if constexpr (V == 0) {
+        // get_full_obs (:112-139): the raw root quaternion throughout (no remove_base_rot); the kin pose is the target's, which the caller sets to
+        // expert frame t (get_expert_kin_pose(delta_t=0), :679)
+        constexpr int H = HEAD ? 1 : 0, K = H + 74 + LV;
+        if (tid == 0) {
+            if (HEAD) ob[0] = heading_angle(rq);
+            const Q4 r = DEHEAD ? qmul(q_inverse(q_heading(rq)), rq) : rq;
+            ob[H] = qpos[2]; ob[H + 1] = r.w; ob[H + 2] = r.x; ob[H + 3] = r.y; ob[H + 4] = r.z;
+            const V3 v = q_tmul_vec(rq, v3(qvel[0], qvel[1], qvel[2]));    // transformed once (:117)
+            ob[H + 74] = v.x; ob[H + 75] = v.y; ob[H + 76] = v.z;
+            if (PHASE) ob[K + 69] = phase[e];
+        }
+        for (int i = tid; i < 69; i += 64) { ob[H + 5 + i] = qpos[7 + i]; ob[K + i] = tq[7 + i]; }
+        for (int i = tid; i < LV - 3; i += 64) ob[H + 77 + i] = qvel[3 + i];
+    } else {
+        constexpr int P = 229 + LV, NJ = V == 1 ? 4 : 2, Q = P + 72 * NJ;    // joint / COM blocks, then the two quaternion blocks
+        const Q4 binv = Q4{A.br_inv[0], A.br_inv[1], A.br_inv[2], A.br_inv[3]};
+        const Q4 crq = qmul(rq, binv);                      // remove_base_rot
+        const Q4 hq = q_heading(crq);
+        const Q4 trq = qmul(Q4{tq[3], tq[4], tq[5], tq[6]}, binv);
+        const V3 root = v3(qpos[0], qpos[1], qpos[2]);
+        if (tid == 0) {
+            ob[0] = hq.w; ob[1] = hq.x; ob[2] = hq.y; ob[3] = hq.z;
+            Q4 dh = qmul(q_inverse(hq), crq);               // de_heading(curr_root_quat)
+            ob[78] = qpos[2]; ob[79] = dh.w; ob[80] = dh.x; ob[81] = dh.y; ob[82] = dh.z;
+            Q4 dq = qmul(trq, q_inverse(crq));
+            ob[152] = tq[2] - qpos[2]; ob[153] = dq.w; ob[154] = dq.x; ob[155] = dq.y; ob[156] = dq.z;
+            V3 v = q_tmul_vec(crq, q_tmul_vec(rq, v3(qvel[0], qvel[1], qvel[2])));  // transformed twice (:150, :173)
+            ob[226] = v.x; ob[227] = v.y; ob[228] = v.z;
+            float rel_h = heading_angle(trq) - heading_angle(crq);
+            if (rel_h > 3.14159265358979f) rel_h -= 6.28318530717959f;
+            if (rel_h < -3.14159265358979f) rel_h += 6.28318530717959f;
+            ob[P - 3] = rel_h;
+            V3 rp = q_tmul_vec(crq, v3(trq.w, trq.x, trq.y) - root);  // sic: quaternion components used as a position (:187; v2 keeps it, :265)
+            ob[P - 2] = rp.x; ob[P - 1] = rp.y;
+        }
+        for (int i = tid; i < 74; i += 64) ob[4 + i] = tq[2 + i];
+        for (int i = tid; i < 69; i += 64) { ob[83 + i] = qpos[7 + i]; ob[157 + i] = tq[7 + i] - qpos[7 + i]; }
+        for (int i = tid; i < LV - 3; i += 64) ob[229 + i] = qvel[3 + i];
+        if (tid < D_NB) {
+            const int b = tid;
+            const float* xp = A.xpos + (size_t)e * 72 + 3 * b;
+            const float* xi = A.xipos + (size_t)e * 72 + 3 * b;
+            const float* xq = A.xquat + (size_t)e * 96;
+            V3 cj = ld3(xp), ci = ld3(xi);
+            V3 tj = ld3(A.t_wbpos + (size_t)e * 72 + 3 * b), tc = ld3(A.t_com + (size_t)e * 72 + 3 * b);
+            // transform_vec_batch returns a (3, 24) array that the reference ravel()s: component-major blocks (v2 has no COM blocks: p3 / p4 are dead code there)
+            V3 p1 = q_tmul_vec(crq, cj - root), p2 = q_tmul_vec(crq, tj - cj), p3 = q_tmul_vec(crq, ci - root), p4 = q_tmul_vec(crq, tc - ci);
+            ob[P + b] = p1.x; ob[P + 24 + b] = p1.y; ob[P + 48 + b] = p1.z;
+            ob[P + 72 + b] = p2.x; ob[P + 96 + b] = p2.y; ob[P + 120 + b] = p2.z;
+            if (V == 1) {
+                ob[P + 144 + b] = p3.x; ob[P + 168 + b] = p3.y; ob[P + 192 + b] = p3.z;
+                ob[P + 216 + b] = p4.x; ob[P + 240 + b] = p4.y; ob[P + 264 + b] = p4.z;
+            }
+            const float* twq = A.t_wbquat + (size_t)e * 96 + 4 * b;
+            Q4 tqt = Q4{twq[0], twq[1], twq[2], twq[3]};
+            Q4 cq = (xq[0] == 0.f) ? tqt : Q4{xq[4 * b], xq[4 * b + 1], xq[4 * b + 2], xq[4 * b + 3]};
+            Q4 r1 = qmul(q_inverse(hq), cq), r2 = qmul(q_inverse(cq), tqt);
+            float* o1 = ob + Q + 4 * b; o1[0] = r1.w; o1[1] = r1.x; o1[2] = r1.y; o1[3] = r1.z;
+            float* o2 = ob + Q + 96 + 4 * b; o2[0] = r2.w; o2[1] = r2.x; o2[2] = r2.y; o2[3] = r2.z;
+        }
     }
     __syncthreads();
-    for (int i = tid; i < 784; i += 64) {
+    for (int i = tid; i < D; i += 64) {
         float v = ob[i];
         if (A.zf_mean) {
             v = (v - A.zf_mean[i]) / (A.zf_std[i] + 1e-8f);
             if (A.clip > 0.f) v = fminf(fmaxf(v, -A.clip), A.clip);
         }
-        A.out[(size_t)e * 784 + i] = v;
+        A.out[(size_t)e * D + i] = v;
     }
 }
+// the uhc.yml observation (get_full_obs_v1, obs_vel full: 784): kp_sim_obs_cc and every kin_poly-side caller
+__global__ __launch_bounds__(64) void k_obs_cc(ObsCcArgs A) { obs_cc_body<1, false, false, false, false>(A, nullptr); }
+// every variant (kp_sim_obs_cc_ex); phase: [n] cur_t / expert len, read only when PHASE
+template <int V, bool VROOT, bool HEAD, bool DEHEAD, bool PHASE>
+__global__ __launch_bounds__(64) void k_obs_cc_v(ObsCcArgs A, const float* __restrict__ phase) { obs_cc_body<V, VROOT, HEAD, DEHEAD, PHASE>(A, phase); }
 
 }  // namespace kp

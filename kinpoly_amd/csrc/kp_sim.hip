@@ -32,6 +32,10 @@ struct kp_model {
     float warm_extrap = -1.f;      // < 0: automatic (0.75 when the scene's free objects are simulated, 0 otherwise); see kp_step_kernel.hpp
     int planemesh_max = 3; double planemesh_tol = 0.3;   // mjc_PlaneConvex's maxplanemesh / tolplanemesh (the blob's `planemesh`)
     int ar_obs_action = 1;        // 0: kp_sim_obs_ar writes the 101-d observation without the action one-hot (use_action: false, humanoid_ar_v1.py:200-201)
+    // the UHC controller's observation (kp_sim_obs_cc_ex): obs_v 0 / 1 / 2, obs_vel 'root', and obs_v 0's obs_heading / root_deheading / obs_phase
+    int cc_obs_v = 1, cc_obs_vel_root = 0, cc_obs_heading = 0, cc_obs_deheading = 0, cc_obs_phase = 0;
+    // the UHC controller (kp_sim_step_ctrl): action_v 0 / 1, residual force off / on, meta-PD 0 none / 1 by substep / 2 by joint (humanoid_im.py:433-524)
+    int cc_action_v = 1, cc_rfc = 1, cc_meta_pd = 0;
     int actuation = 1;            // 0: no stable-PD torque, no residual force (ctrl = qfrc_applied = 0): torque-free flight for the energy test
     double solver_tol = 1e-8, gravity_z = -9.81, gravity_x = 0.0, gravity_y = 0.0;   // solver_iter / solver_tol: mjOption.iterations / tolerance of the reference model (kp_model_load)
 };
@@ -40,6 +44,9 @@ struct kp_sim {
     const kp_model* model = nullptr;
     int n = 0, device = 0;
     int ar_obs_dim = KP_AR_OBS_DIM;                   // the model's ar_obs_action when the handle was created: KP_AR_OBS_DIM or KP_AR_OBS_DIM_NO_ACTION
+    int cc_obs_v = 1, cc_obs_vel_root = 0, cc_obs_heading = 0, cc_obs_deheading = 0, cc_obs_phase = 0, cc_obs_dim = KP_CC_OBS_DIM;   // the model's cc_obs_* at creation
+    kp::XcArgs xc{KP_CC_ACTION_DIM, 0, 1, 0};        // the model's controller at creation; xc_on: not uhc.yml's (the extended-controller kernels, full layout)
+    bool xc_on = false;
     hipStream_t stream = nullptr;
     std::vector<void*> allocs;
     kp::DevTables T{};
@@ -238,7 +245,8 @@ int job_schedule(int nsub, int spj, int taper, int* sizes) {
 
 // The lean layout (EnvLdsLean) serves floor scenes in stale mode only: its pAa shares words with jv3 | lim_jv, which in fresh mode (stale_kinematics = 0)
 // hold make_constraint's aref while the substep's aba_solve writes pAa (kp_device.hpp).  P.stale: the value the kernel receives.
-bool lean_eligible(const kp_sim& s) { return !s.has_objects && s.model->lean_queue && s.model->threads == 64 && s.P.stale; }
+// (the extended controller has no lean-layout instantiation: plan_step sends it to the full layout)
+bool lean_eligible(const kp_sim& s) { return !s.has_objects && s.model->lean_queue && s.model->threads == 64 && s.P.stale && !s.xc_on; }
 
 // resident envs per CU: LDS is allocated in 1 280-byte granules, 128 per CU (tools/micro/lds_granule_probe.hip); the register budgets allow 8 waves per CU
 // (full layout, <= 256 VGPRs) and 12 (lean layout, 168 VGPRs)
@@ -317,7 +325,8 @@ StepPlan plan_step(const kp_sim& s, int nsub, bool capturing) {
 // one workgroup of NT threads per env: the control step, or (nsub = 0) the forward pass alone
 template <int NT, bool OBJ>
 void launch_per_env(const kp_sim* s, const kp::StepArgs& A, int nsub, size_t lds) {
-    if (nsub > 0) hipLaunchKernelGGL((kp::kp_step_kernel<NT, OBJ>), dim3(s->n), dim3(NT), lds, s->stream, A);
+    if (nsub > 0 && s->xc_on) hipLaunchKernelGGL((kp::kp_step_kernel_xc<NT, OBJ>), dim3(s->n), dim3(NT), lds, s->stream, A, s->xc);
+    else if (nsub > 0) hipLaunchKernelGGL((kp::kp_step_kernel<NT, OBJ>), dim3(s->n), dim3(NT), lds, s->stream, A);
     else hipLaunchKernelGGL((kp::kp_forward_kernel<NT, OBJ>), dim3(s->n), dim3(NT), lds, s->stream, A);
 }
 
@@ -368,7 +377,9 @@ int launch_step(kp_sim* s, const float* action, int nsub, const uint8_t* mask, b
         const unsigned total = (unsigned)s->n * (unsigned)p.parts;
         hipLaunchKernelGGL(kp::k_queue_init, dim3((total + 255) / 256), dim3(256), 0, s->stream, s->n, total, s->jobq, s->jobctr, A.order);   // inside the timed bracket
         A.order = nullptr;                                              // the queue kernel addresses envs by their queue entry
-        if (p.layout == OBJECTS) hipLaunchKernelGGL((kp::kp_step_queue_kernel<true>), dim3(p.slots), dim3(64), p.lds, s->stream, A);
+        if (s->xc_on && p.layout == OBJECTS) hipLaunchKernelGGL((kp::kp_step_queue_kernel_xc<true>), dim3(p.slots), dim3(64), p.lds, s->stream, A, s->xc);
+        else if (s->xc_on) hipLaunchKernelGGL((kp::kp_step_queue_kernel_xc<false>), dim3(p.slots), dim3(64), p.lds, s->stream, A, s->xc);
+        else if (p.layout == OBJECTS) hipLaunchKernelGGL((kp::kp_step_queue_kernel<true>), dim3(p.slots), dim3(64), p.lds, s->stream, A);
         else if (p.layout == FULL) hipLaunchKernelGGL((kp::kp_step_queue_kernel<false>), dim3(p.slots), dim3(64), p.lds, s->stream, A);
         else {
             hipLaunchKernelGGL((kp::kp_step_queue_kernel<false, true>), dim3(p.slots), dim3(64), p.lds, s->stream, A);
@@ -414,6 +425,15 @@ kp_model* kp_model_load(const char* path) {
 }
 void kp_model_free(kp_model* m) { delete m; }
 
+// width of the action row kp_sim_step_ctrl reads for these controller options (HumanoidEnv.set_spaces, humanoid_im.py:68-89)
+static int cc_action_width(int rfc, int meta) { return 69 + 6 * rfc + (meta == 1 ? 30 : meta == 2 ? 138 : 0); }
+
+// width of the observation kp_sim_obs_cc_ex writes for these switches (kp::ObsCcLayout)
+static int cc_obs_width(int v, int vel_root, int heading, int phase) {
+    const int lv = vel_root ? 6 : 75;
+    return v == 0 ? heading + 74 + lv + 69 + phase : 229 + lv + (v == 1 ? 4 : 2) * 72 + 2 * 96;
+}
+
 int kp_model_set_option(kp_model* m, const char* name, double v) {
     if (!m || !name) return fail("kp_model_set_option: null argument");
     std::string k(name);
@@ -424,6 +444,16 @@ int kp_model_set_option(kp_model* m, const char* name, double v) {
     else if (k == "gravity_y") m->gravity_y = v;
     else if (k == "actuation") m->actuation = v != 0;
     else if (k == "ar_obs_action") { if (v != 0 && v != 1) return fail("ar_obs_action must be 1 (105-d observation with the action one-hot) or 0 (101-d, use_action: false)"); m->ar_obs_action = (int)v; }
+    else if (k == "cc_action_v" || k == "cc_rfc") {
+        if (v != 0 && v != 1) return fail(k + " must be 0 or 1");
+        (k == "cc_action_v" ? m->cc_action_v : m->cc_rfc) = (int)v;
+    }
+    else if (k == "cc_meta_pd") { if (v != 0 && v != 1 && v != 2) return fail("cc_meta_pd must be 0 (none), 1 (meta_pd: by substep) or 2 (meta_pd_joint: by joint)"); m->cc_meta_pd = (int)v; }
+    else if (k == "cc_obs_v") { if (v != 0 && v != 1 && v != 2) return fail("cc_obs_v must be 0 (get_full_obs), 1 (get_full_obs_v1) or 2 (get_full_obs_v2)"); m->cc_obs_v = (int)v; }
+    else if (k == "cc_obs_vel_root" || k == "cc_obs_heading" || k == "cc_obs_deheading" || k == "cc_obs_phase") {
+        if (v != 0 && v != 1) return fail(k + " must be 0 or 1");
+        (k == "cc_obs_vel_root" ? m->cc_obs_vel_root : k == "cc_obs_heading" ? m->cc_obs_heading : k == "cc_obs_deheading" ? m->cc_obs_deheading : m->cc_obs_phase) = (int)v;
+    }
     else if (k == "stale_kinematics") m->stale = v != 0;
     else if (k == "solver_iter") m->solver_iter = (int)v;
     else if (k == "solver_tol") m->solver_tol = v;
@@ -458,6 +488,16 @@ double kp_model_get_option(const kp_model* m, const char* name) {
     if (k == "actuation") return m->actuation;
     if (k == "ar_obs_action") return m->ar_obs_action;
     if (k == "ar_obs_dim") return m->ar_obs_action ? KP_AR_OBS_DIM : KP_AR_OBS_DIM_NO_ACTION;
+    if (k == "cc_obs_v") return m->cc_obs_v;
+    if (k == "cc_obs_vel_root") return m->cc_obs_vel_root;
+    if (k == "cc_obs_heading") return m->cc_obs_heading;
+    if (k == "cc_obs_deheading") return m->cc_obs_deheading;
+    if (k == "cc_obs_phase") return m->cc_obs_phase;
+    if (k == "cc_obs_dim") return m->cc_obs_v == 0 ? cc_obs_width(0, m->cc_obs_vel_root, m->cc_obs_heading, m->cc_obs_phase) : cc_obs_width(m->cc_obs_v, m->cc_obs_vel_root, 0, 0);
+    if (k == "cc_action_dim") return cc_action_width(m->cc_rfc, m->cc_meta_pd);
+    if (k == "cc_action_v") return m->cc_action_v;
+    if (k == "cc_rfc") return m->cc_rfc;
+    if (k == "cc_meta_pd") return m->cc_meta_pd;
     if (k == "stale_kinematics") return m->stale;
     if (k == "solver_iter") return m->solver_iter;
     if (k == "solver_tol") return m->solver_tol;
@@ -495,6 +535,11 @@ kp_sim* kp_sim_create(const kp_model* m, int n_envs, int device_id, void* stream
     kp_sim* s = new kp_sim();
     s->model = m; s->n = n_envs; s->device = device_id; s->stream = (hipStream_t)stream;
     s->ar_obs_dim = m->ar_obs_action ? KP_AR_OBS_DIM : KP_AR_OBS_DIM_NO_ACTION;
+    s->cc_obs_v = m->cc_obs_v; s->cc_obs_vel_root = m->cc_obs_vel_root;
+    s->cc_obs_heading = m->cc_obs_v == 0 && m->cc_obs_heading; s->cc_obs_deheading = m->cc_obs_v == 0 && m->cc_obs_deheading; s->cc_obs_phase = m->cc_obs_v == 0 && m->cc_obs_phase;
+    s->cc_obs_dim = cc_obs_width(s->cc_obs_v, s->cc_obs_vel_root, s->cc_obs_heading, s->cc_obs_phase);
+    s->xc = kp::XcArgs{cc_action_width(m->cc_rfc, m->cc_meta_pd), m->cc_action_v == 0, m->cc_rfc, m->cc_meta_pd};
+    s->xc_on = m->cc_action_v != 1 || m->cc_rfc != 1 || m->cc_meta_pd != 0;
     bool ok = build_tables(s);
     size_t N = n_envs;
     s->qpos = dalloc(s, N * 76, &ok); s->qvel = dalloc(s, N * 75, &ok); s->qpos_d = dalloc(s, N * 76, &ok);
@@ -714,6 +759,8 @@ int kp_sim_fk_backward(kp_sim* s, int n_rows, const float* qpos, const float* wb
 
 int kp_sim_step_ctrl(kp_sim* s, const float* action, int nsub, const uint8_t* mask) {
     if (!s || !action || nsub <= 0) return fail("kp_sim_step_ctrl: bad arguments");
+    if (s->xc.meta == 1 && nsub > 15)       // the reference's 30-entry meta_pd block holds kp / kd scales of 15 substeps (meta_pds[i_iter + 15], humanoid_im.py:456-458)
+        return fail("kp_sim_step_ctrl: cc_meta_pd = 1 (meta_pd) scales the gains of at most 15 substeps per control step, got " + std::to_string(nsub));
     HIP_OK(hipSetDevice(s->device));
     return launch_step(s, action, nsub, mask, true);
 }
@@ -750,6 +797,49 @@ int kp_sim_obs_cc(kp_sim* s, float* out, const float* zf_mean, const float* zf_s
     HIP_OK(hipGetLastError());
     return 0;
 }
+
+extern "C++" {   // the launchers are templates
+template <int V, bool VROOT, bool HEAD, bool DEHEAD, bool PHASE>
+static void launch_obs_cc_v(kp_sim* s, const kp::ObsCcArgs& A, const float* phase) {
+    hipLaunchKernelGGL((kp::k_obs_cc_v<V, VROOT, HEAD, DEHEAD, PHASE>), dim3(s->n), dim3(64), 0, s->stream, A, phase);
+}
+template <bool VROOT>
+static void launch_obs_cc_v0(kp_sim* s, const kp::ObsCcArgs& A, const float* phase) {
+    const int sw = s->cc_obs_heading * 4 + s->cc_obs_deheading * 2 + s->cc_obs_phase;
+    switch (sw) {
+        case 0: launch_obs_cc_v<0, VROOT, false, false, false>(s, A, phase); break;
+        case 1: launch_obs_cc_v<0, VROOT, false, false, true>(s, A, phase); break;
+        case 2: launch_obs_cc_v<0, VROOT, false, true, false>(s, A, phase); break;
+        case 3: launch_obs_cc_v<0, VROOT, false, true, true>(s, A, phase); break;
+        case 4: launch_obs_cc_v<0, VROOT, true, false, false>(s, A, phase); break;
+        case 5: launch_obs_cc_v<0, VROOT, true, false, true>(s, A, phase); break;
+        case 6: launch_obs_cc_v<0, VROOT, true, true, false>(s, A, phase); break;
+        default: launch_obs_cc_v<0, VROOT, true, true, true>(s, A, phase); break;
+    }
+}
+}  // extern "C++"
+
+int kp_sim_obs_cc_ex(kp_sim* s, float* out, const float* zf_mean, const float* zf_std, float clip, const float* phase) {
+    if (!s || !out) return fail("kp_sim_obs_cc_ex: null argument");
+    if ((zf_mean == nullptr) != (zf_std == nullptr)) return fail("kp_sim_obs_cc_ex: pass both zf_mean and zf_std or neither");
+    if (s->cc_obs_phase && !phase) return fail("kp_sim_obs_cc_ex: this handle's observation ends with the phase (cc_obs_phase = 1): pass phase [N]");
+    if (!s->cc_obs_phase && phase) return fail("kp_sim_obs_cc_ex: phase given, but this handle's observation has no phase slot (cc_obs_phase = 0 or cc_obs_v != 0)");
+    HIP_OK(hipSetDevice(s->device));
+    kp::ObsCcArgs A;
+    A.n = s->n; A.qpos = s->qpos; A.qvel = s->qvel; A.xpos = s->xpos; A.xquat = s->xquat; A.xipos = s->xipos;
+    A.t_qpos = s->t_qpos; A.t_wbpos = s->t_wbpos; A.t_wbquat = s->t_wbquat; A.t_com = s->t_com;
+    for (int k = 0; k < 4; k++) A.br_inv[k] = s->P.br_inv[k];
+    A.zf_mean = zf_mean; A.zf_std = zf_std; A.clip = clip; A.out = out;
+    if (s->cc_obs_v == 1 && !s->cc_obs_vel_root) hipLaunchKernelGGL(kp::k_obs_cc, dim3(s->n), dim3(64), 0, s->stream, A);   // the uhc.yml layout: the same kernel as kp_sim_obs_cc
+    else if (s->cc_obs_v == 1) launch_obs_cc_v<1, true, false, false, false>(s, A, nullptr);
+    else if (s->cc_obs_v == 2 && s->cc_obs_vel_root) launch_obs_cc_v<2, true, false, false, false>(s, A, nullptr);
+    else if (s->cc_obs_v == 2) launch_obs_cc_v<2, false, false, false, false>(s, A, nullptr);
+    else if (s->cc_obs_vel_root) launch_obs_cc_v0<true>(s, A, phase);
+    else launch_obs_cc_v0<false>(s, A, phase);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+int kp_sim_cc_obs_dim(const kp_sim* s) { return s ? s->cc_obs_dim : -1; }
 
 int kp_field_dim(int f) {
     switch (f) {

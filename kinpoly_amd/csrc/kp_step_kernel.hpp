@@ -653,9 +653,28 @@ __device__ __forceinline__ void aba_resolve(SL& s, const Lane8& L, const float* 
 }
 
 // ---------------------------------------------------------------- stable-PD torque + residual force (reference controller)
-template <int NT, bool OBJ, class SL>
-// tq / act: this env's rows of the PD target and the action in HBM (null: zeros); read here once per substep instead of living in LDS
-__device__ __forceinline__ void spd_torque_rfc(SL& s, const DevTables& T, const Params& P, const Lane8& L8, int tid, const float* __restrict__ tq, const float* __restrict__ act) {
+// The extended controller (XC, a UHC config other than uhc.yml's; humanoid_im.py:433-480, 506-524): the action row is `stride` wide; action_v0: the PD base
+// pose is the target row as it is (cfg.a_ref, which the caller installs), without the 2 pi unwrap; rfc = 0: no residual force (applied[0:6] = 0, vf_dim 0);
+// meta = 1 (meta_pd): kp / kd of every joint x clip(m + 1, 0, 10) with m = the action's meta entries [i_iter] / [i_iter + 15]; meta = 2 (meta_pd_joint):
+// by joint, [j] / [69 + j].  The meta block starts at 69 + 6 rfc.  The scaled gains enter everywhere the SPD uses them: the K_d h armature, x and tau.
+struct XcArgs { int stride, action_v0, rfc, meta; };
+template <bool XC>
+__device__ __forceinline__ void xc_gains(const DevTables& T, const XcArgs* X, const float* __restrict__ act, int j, int i_iter, float& kp, float& kd) {
+    kp = T.kp[j]; kd = T.kd[j];
+    if constexpr (XC) {
+        if (X->meta && act) {
+            const int m0 = 69 + 6 * X->rfc;
+            const float mp = X->meta == 1 ? act[m0 + i_iter] : act[m0 + j], md = X->meta == 1 ? act[m0 + i_iter + 15] : act[m0 + 69 + j];
+            kp = kp * fminf(fmaxf(mp + 1.f, 0.f), 10.f);
+            kd = kd * fminf(fmaxf(md + 1.f, 0.f), 10.f);
+        }
+    }
+}
+template <int NT, bool OBJ, class SL, bool XC = false>
+// tq / act: this env's rows of the PD target and the action in HBM (null: zeros); read here once per substep instead of living in LDS.  i_iter: the substep's
+// index within the control step (the extended controller's meta_pd)
+__device__ __forceinline__ void spd_torque_rfc(SL& s, const DevTables& T, const Params& P, const Lane8& L8, int tid, const float* __restrict__ tq, const float* __restrict__ act,
+                                               const XcArgs* X = nullptr, int i_iter = 0) {
     float* const epv = SL::LEAN ? s.lim_jar - 6 : s.search;      // the position error of dof i >= 6 (lean layout: search is the solve's own vector, lim_jar is dead here)
     for (int i = tid; i < D_NV; i += NT) {
         float ep = 0.f, kp = 0.f, kd = 0.f;
@@ -665,10 +684,12 @@ __device__ __forceinline__ void spd_torque_rfc(SL& s, const DevTables& T, const 
             // the reference's 2 pi unwrap loops (humanoid_im.py:447-452) in closed form: no trip count that depends on the data, so a
             // non-finite or absurd target cannot spin the wavefront (it yields a non-finite state, which diag flags)
             const float dq = base - q;
-            if (dq > 3.14159265358979f) base -= 6.28318530717959f * ceilf((dq - 3.14159265358979f) * 0.159154943091895f);
-            else if (dq < -3.14159265358979f) base += 6.28318530717959f * ceilf((-dq - 3.14159265358979f) * 0.159154943091895f);
+            if (!XC || !X->action_v0) {
+                if (dq > 3.14159265358979f) base -= 6.28318530717959f * ceilf((dq - 3.14159265358979f) * 0.159154943091895f);
+                else if (dq < -3.14159265358979f) base += 6.28318530717959f * ceilf((-dq - 3.14159265358979f) * 0.159154943091895f);
+            }
             float target = base + (act ? act[j] : 0.f) * T.ascale[j];
-            kp = T.kp[j]; kd = T.kd[j];
+            xc_gains<XC>(T, X, act, j, i_iter, kp, kd);
             ep = q + s.qvel[i] * P.h - target;
         }
         float kdh = kd * P.h;                         // (M + K_d dt): K_d dt is extra joint armature
@@ -681,7 +702,9 @@ __device__ __forceinline__ void spd_torque_rfc(SL& s, const DevTables& T, const 
     aba_solve<NT, OBJ>(s, P, L8, s.x, s.x, false, tid, D_NLEV, s.fb);
     for (int j = tid; j < D_NU; j += NT) {
         int i = j + 6;
-        float tau = -T.kp[j] * epv[i] - T.kd[j] * (s.qvel[i] + s.x[i] * P.h);
+        float kp, kd;
+        xc_gains<XC>(T, X, act, j, i_iter, kp, kd);
+        float tau = -kp * epv[i] - kd * (s.qvel[i] + s.x[i] * P.h);
         float lim = T.tlim[j];
         s.ctrl[j] = fminf(fmaxf(tau, -lim), lim);
     }
@@ -691,7 +714,7 @@ __device__ __forceinline__ void spd_torque_rfc(SL& s, const DevTables& T, const 
         Q4 hq = Q4{cq.w / hn, 0.f, 0.f, cq.z / hn};
         float ar[6];
 #pragma unroll
-        for (int k = 0; k < 6; k++) ar[k] = act ? act[69 + k] : 0.f;
+        for (int k = 0; k < 6; k++) ar[k] = (act && (!XC || X->rfc)) ? act[69 + k] : 0.f;      // residual_force off: vf = 0 -> applied = 0
         V3 f = qrot(hq, v3(ar[0] * P.rfc_scale, ar[1] * P.rfc_scale, ar[2] * P.rfc_scale));
         float vf[6] = {f.x, f.y, f.z, ar[3] * P.rfc_scale, ar[4] * P.rfc_scale, ar[5] * P.rfc_scale};
 #pragma unroll
@@ -1935,8 +1958,8 @@ template <bool Q, typename V> __device__ __forceinline__ void gst(V* p, V v) {
 
 // LEAN: the floor scenes' job-queue layout (EnvLdsLean).  Returns 1 when the lean layout could not hold a substep's contacts: the job has written nothing to HBM at
 // that point and is re-run on the full layout (kp_step_overflow_kernel); 0 otherwise.
-template <int NT, bool OBJ, bool FWD, bool Q = false, bool LEAN = false>
-__device__ __forceinline__ int step_body(const StepArgs& A, const int env_in, const int part) {
+template <int NT, bool OBJ, bool FWD, bool Q = false, bool LEAN = false, bool XC = false>
+__device__ __forceinline__ int step_body(const StepArgs& A, const int env_in, const int part, const XcArgs* X = nullptr) {
     static_assert(!LEAN || (Q && !OBJ && !FWD && NT == 64), "the lean layout serves the floor scenes' job queue only");
     // this job's share of the control step; A stays the kernel's read-only argument block (a by-value copy that the job modifies is a private copy per job)
     const int n_substeps = FWD ? 0 : (part >= 0 ? (int)(((part < 8 ? A.part_sub_lo >> (8 * part) : A.part_sub_hi >> (8 * (part - 8)))) & 255ull) : A.n_substeps);
@@ -1959,7 +1982,9 @@ __device__ __forceinline__ int step_body(const StepArgs& A, const int env_in, co
 
     // ---- load: derived state first (the state the last forward pass ran on), then the real state
     const float* tq_row = A.target_qpos ? A.target_qpos + (size_t)env * D_NQ : nullptr;
-    const float* act_row = A.action ? A.action + (size_t)env * D_NV : nullptr;
+    const float* act_row = A.action ? A.action + (size_t)env * (XC ? X->stride : D_NV) : nullptr;
+    int sub_base = 0;             // the extended controller's substep index: this job's first substep within the control step
+    if constexpr (XC && Q) for (int p = 0; p < part; p++) sub_base += (int)(((p < 8 ? A.part_sub_lo >> (8 * p) : A.part_sub_hi >> (8 * (p - 8)))) & 255ull);
     // Torque hand-over between the jobs of a control step (stale mode): the stable-PD torque of substep k is a function of the kinematics of
     // substep k - 1, which sit in the LDS of the job that ran k - 1.  That job therefore also computes the torque of k (it is the same
     // solve its successor would start with) and hands over 78 floats; the successor then needs neither the derived state nor the forward
@@ -2058,7 +2083,8 @@ __device__ __forceinline__ int step_body(const StepArgs& A, const int env_in, co
         if (prof) t0 = __builtin_readcyclecounter();
         // stale mode: the controller sees M / bias of the previous forward pass (cinert, cdof, bias still in LDS)
         const bool spd_pass = torque_out && sub == n_substeps;           // the extra pass of a job that is not the control step's last: the successor's first torque
-        if ((substep || spd_pass) && P.stale && P.actuation && !(torque_in && sub == 0)) { Lane8 La; La.init(kp_launder(tid), T.sched8); spd_torque_rfc<NT, OBJ>(s, T, P, La, tid, tq_row, act_row); }
+        // (the spd pass computes the torque of the control step's substep sub_base + n_substeps, the successor job's first)
+        if ((substep || spd_pass) && P.stale && P.actuation && !(torque_in && sub == 0)) { Lane8 La; La.init(kp_launder(tid), T.sched8); spd_torque_rfc<NT, OBJ, SL, XC>(s, T, P, La, tid, tq_row, act_row, X, sub_base + sub); }
         if (spd_pass) {
             for (int i = tid; i < 78; i += NT) gst<Q>(A.spd_next + (size_t)env * 80 + (unsigned)(i), s.applied[i]);
             break;
@@ -2117,7 +2143,7 @@ __device__ __forceinline__ int step_body(const StepArgs& A, const int env_in, co
         KP_T(2)
         make_constraint<NT, OBJ>(s, T, P, tid);                 // needs sv = cvel: before any aba_solve
         KP_T(3)
-        if (!P.stale && P.actuation) { Lane8 La; La.init(kp_launder(tid), T.sched8); spd_torque_rfc<NT, OBJ>(s, T, P, La, tid, tq_row, act_row); }
+        if (!P.stale && P.actuation) { Lane8 La; La.init(kp_launder(tid), T.sched8); spd_torque_rfc<NT, OBJ, SL, XC>(s, T, P, La, tid, tq_row, act_row, X, sub_base + sub); }
         for (int i = tid; i < D_NV; i += NT) s.extra[i] = LEAN ? T.dof_armature[i] : 0.f;
         KP_SYNC();
         Lane8 L8; L8.init(kp_launder(tid), T.sched8);          // lives through the Newton solve
@@ -2302,6 +2328,11 @@ template <int NT, bool OBJ>
 __global__ __launch_bounds__(NT, (NT == 64 ? 2 : 1)) void kp_step_kernel(StepArgs A) {
     step_body<NT, OBJ, false>(A, A.order ? A.order[blockIdx.x] : (int)blockIdx.x, -1);
 }
+// the extended controller (XcArgs), one workgroup per env
+template <int NT, bool OBJ>
+__global__ __launch_bounds__(NT, (NT == 64 ? 2 : 1)) void kp_step_kernel_xc(StepArgs A, XcArgs X) {
+    step_body<NT, OBJ, false, false, false, true>(A, A.order ? A.order[blockIdx.x] : (int)blockIdx.x, -1, &X);
+}
 template <int NT, bool OBJ>
 __global__ __launch_bounds__(NT, (NT == 64 ? 2 : 1)) void kp_forward_kernel(StepArgs A) { step_body<NT, OBJ, true>(A, (int)blockIdx.x, -1); }
 
@@ -2324,8 +2355,8 @@ __global__ __launch_bounds__(NT, (NT == 64 ? 2 : 1)) void kp_forward_kernel(Step
 // the variant that is correct by construction is the default.
 // LEAN (floor scenes): the EnvLdsLean layout and a register budget for three waves per SIMD; a job whose contacts do not fit the layout is handed, with the env's
 // remaining jobs, to kp_step_overflow_kernel (launched right behind this kernel, same stream).
-template <bool OBJ, bool LEAN = false>
-__global__ __launch_bounds__(64, (LEAN ? 3 : 2)) void kp_step_queue_kernel(StepArgs A) {
+template <bool OBJ, bool LEAN, bool XC>
+__device__ __forceinline__ void step_queue_body(const StepArgs& A, const XcArgs* X) {
     // jobctr: [0] head (claimed), [1] tail (published), [2] stalled flag; on cache lines of their own, away from the head / tail every claim and publish hits:
     //         [16] jobs that were never queued because the finishing wave ran them itself; [32] time (40 ns units) and [33] substeps of the jobs finished so
     //         far in this launch; [48], [49] the same sums of the previous launch (the mean behind "heavy": constant during the launch, read once per wave)
@@ -2370,7 +2401,7 @@ __global__ __launch_bounds__(64, (LEAN ? 3 : 2)) void kp_step_queue_kernel(StepA
         if (A.queue_prio == 2) { if (part == 0) __builtin_amdgcn_s_setprio(2); else if (part + 1 < A.n_parts) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
         for (;;) {
             const unsigned long long tj = __builtin_amdgcn_s_memrealtime();          // 100 MHz ticks: only ratios of job times are used
-            const int overflow = step_body<64, OBJ, false, true, LEAN>(A, env, part);
+            const int overflow = step_body<64, OBJ, false, true, LEAN, XC>(A, env, part, X);
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // every lane's write-through state store has been acknowledged ...
             if (A.queue_fence) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");      // memory-model variant: release all of this wave's stores at agent scope
             if (LEAN && overflow) {
@@ -2411,6 +2442,12 @@ __global__ __launch_bounds__(64, (LEAN ? 3 : 2)) void kp_step_queue_kernel(StepA
         }
     }
 }
+
+template <bool OBJ, bool LEAN = false>
+__global__ __launch_bounds__(64, (LEAN ? 3 : 2)) void kp_step_queue_kernel(StepArgs A) { step_queue_body<OBJ, LEAN, false>(A, nullptr); }
+// the extended controller (XcArgs) on the full / object layout (never the lean one)
+template <bool OBJ>
+__global__ __launch_bounds__(64, 2) void kp_step_queue_kernel_xc(StepArgs A, XcArgs X) { step_queue_body<OBJ, false, true>(A, &X); }
 
 // The jobs the lean queue kernel could not hold (more than EnvLdsLean::MAXCON contacts in a substep), run on the full layout: a wave claims an entry and runs that
 // job and the env's remaining jobs itself.  Launched behind every lean queue launch; with an empty list (the rule: floor scenes hold 7 - 10 contacts) every wave

@@ -240,8 +240,18 @@ class BatchedHumanoidAREnv:
         `policy_dict` into cc_policy unless the run trains the controller jointly (`if not kin_cfg.joint_controller`, :79-81).  `path`: a pickle in
         the reference's layout ({'policy_dict', 'value_dict', 'running_state'}; scripts/train_uhc.py --save writes one)."""
         from . import checkpoint as ck
+        from .uhc_config import ConfigError
         cp = ck.load_checkpoint(path)
         arr = ck.running_state_arrays(cp.get("running_state"))
+        if arr is not None and len(arr[0]) != kpsim.CC_OBS_DIM:
+            raise ConfigError(f"{path}: running_state is {len(arr[0])}-d, a UHC of another obs_v / obs_vel; this env runs uhc.yml's controller "
+                              f"(obs_v 1, obs_vel full: {kpsim.CC_OBS_DIM})")
+        if load_policy and not any(k.startswith("composer.") for k in cp["policy_dict"]):
+            raise ConfigError(f"{path}: policy_dict is not a PolicyMCP (actor_type gauss?); this env runs uhc.yml's controller (actor_type mcp)")
+        ls = cp["policy_dict"].get("action_log_std")
+        if load_policy and ls is not None and tuple(ls.shape)[-1] != kpsim.CC_ACTION_DIM:
+            raise ConfigError(f"{path}: the policy's action is {tuple(ls.shape)[-1]}-d, a UHC with meta_pd / meta_pd_joint or residual_force off; this env runs "
+                              f"uhc.yml's controller ({kpsim.CC_ACTION_DIM})")
         if arr is not None:
             self.cc_running_state = RunningState(arr[0], arr[1], arr[2], self.device)
         if load_policy:
@@ -459,6 +469,9 @@ class HumanoidAREnv:
 
     def __init__(self, cfg=None, cc_cfg=None, init_context=None, cc_iter=-1, mode="train", wild=False, ar_mode=False, cc_state=None, device=0):
         ps = getattr(cfg, "policy_specs", {}) or {}
+        if cc_cfg is not None:
+            from .uhc_config import require_uhc_yml_controller
+            require_uhc_yml_controller(cc_cfg)
         pol = PolicyMCP()
         rs = None
         if cc_state is not None:

@@ -165,6 +165,36 @@ class PolicyMCP(nn.Module):
         return torch.addcmul(mean, torch.exp(log_std), noise)
 
 
+class PolicyGaussian(nn.Module):
+    """The UHC's plain Gaussian actor (actor_type: gauss; uhc/khrylib/rl/core/policy_gaussian.py:7-28): MLP(policy_hsize, policy_htype) and a
+    Linear mean head (weights x 0.1, bias 0), a state-independent log-std.  Same state_dict keys as the reference (net.affine_layers.*,
+    action_mean.*, action_log_std); same calling surface as PolicyMCP (forward -> (mean, log_std), select_action)."""
+
+    def __init__(self, state_dim, action_dim, policy_hsize=(300, 200), policy_htype="relu", log_std=-2.3, fix_std=True):
+        super().__init__()
+        self.type = "gaussian"
+        self.net = MLP(state_dim, tuple(policy_hsize), policy_htype)
+        self.action_mean = nn.Linear(self.net.out_dim, action_dim)
+        self.action_mean.weight.data.mul_(0.1)
+        self.action_mean.bias.data.mul_(0.0)
+        self.action_log_std = nn.Parameter(torch.ones(1, action_dim) * log_std, requires_grad=not fix_std)
+
+    def std(self):
+        return torch.exp(self.action_log_std.detach()).reshape(-1)
+
+    def forward(self, x):
+        mean = self.action_mean(self.net(x))
+        return mean, self.action_log_std.expand_as(mean)
+
+    def select_action(self, x, mean_action=False, generator=None, noise=None):
+        mean, log_std = self.forward(x)
+        if mean_action:
+            return mean
+        if noise is None:
+            noise = torch.randn(mean.shape, device=x.device, dtype=x.dtype, generator=generator)
+        return torch.addcmul(mean, torch.exp(log_std), noise)
+
+
 class _StepRNN(nn.Module):
     """RNN(cell_type='gru') in 'step' mode (uhc/khrylib/models/rnn.py:5-36) with a batched hidden state."""
 

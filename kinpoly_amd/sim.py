@@ -38,7 +38,7 @@ ABI_SYMBOLS = [
     "kp_sim_contacts", "kp_gae_bootstrap", "kp_gru_gates_forward", "kp_gru_gates_backward", "kp_sim_phase_cycles_env",
     "kp_sim_post_step", "kp_sim_reset_rows", "kp_mcp_compose", "kp_sim_step_head", "kp_model_compile", "kp_model_load_xml",
     "kp_mcp_tail", "kp_gru_cell_step", "kp_kin_advance", "kp_pool_advance", "kp_rollout_record_pre", "kp_rollout_record_post", "kp_rollout_record_pre_w", "kp_rollout_record_post_w", "kp_sim_ar_obs_dim", "kp_sim_field_device",
-    "kp_sim_lean_state", "kp_sim_pose_contacts",
+    "kp_sim_lean_state", "kp_sim_pose_contacts", "kp_sim_obs_cc_ex", "kp_sim_cc_obs_dim",
 ]
 
 
@@ -102,6 +102,8 @@ def load_library(path: str | None = None):
     L.kp_sim_step_kin.argtypes = [P, F, F]; L.kp_sim_step_kin.restype = C.c_int
     L.kp_sim_step_head.argtypes = [P, F]; L.kp_sim_step_head.restype = C.c_int
     L.kp_sim_obs_cc.argtypes = [P, F, F, F, C.c_float]; L.kp_sim_obs_cc.restype = C.c_int
+    L.kp_sim_obs_cc_ex.argtypes = [P, F, F, F, C.c_float, F]; L.kp_sim_obs_cc_ex.restype = C.c_int
+    L.kp_sim_cc_obs_dim.argtypes = [P]; L.kp_sim_cc_obs_dim.restype = C.c_int
     L.kp_field_dim.argtypes = [C.c_int]; L.kp_field_dim.restype = C.c_int
     L.kp_sim_get.argtypes = [P, C.c_int, F]; L.kp_sim_get.restype = C.c_int
     L.kp_sim_diag.argtypes = [P, C.c_void_p]; L.kp_sim_diag.restype = C.c_int
@@ -219,6 +221,9 @@ class KpSim:
             raise KinPolyNativeError(f"kp_sim_create: {self.L.kp_last_error().decode()}")
         self._stream = stream
         self.obs_ar_dim = int(self.L.kp_sim_ar_obs_dim(self.h))      # AR_OBS_DIM, or AR_OBS_DIM_NO_ACTION for a model with ar_obs_action = 0
+        self.cc_obs_dim = int(self.L.kp_sim_cc_obs_dim(self.h))      # CC_OBS_DIM, or the width of the model's cc_obs_* options (UhcConfig.obs_dim)
+        self.cc_obs_phase = bool(model.get_option("cc_obs_phase")) and int(model.get_option("cc_obs_v")) == 0
+        self.cc_action_dim = int(model.get_option("cc_action_dim"))
 
     def use_current_stream(self):
         """Enqueue all later calls on torch's current stream of this device (the caller orders the old and the new stream)."""
@@ -292,7 +297,7 @@ class KpSim:
         _check(self.L.kp_sim_set_target(self.h, _ptr(target_qpos, self.n, NQ), _mask_ptr(env_mask, self.n)), "kp_sim_set_target")
 
     def step_ctrl(self, cc_action, n_substeps=15, env_mask=None):
-        _check(self.L.kp_sim_step_ctrl(self.h, _ptr(cc_action, self.n, CC_ACTION_DIM), int(n_substeps), _mask_ptr(env_mask, self.n)), "kp_sim_step_ctrl")
+        _check(self.L.kp_sim_step_ctrl(self.h, _ptr(cc_action, self.n, self.cc_action_dim), int(n_substeps), _mask_ptr(env_mask, self.n)), "kp_sim_step_ctrl")
 
     def step_head(self, kin_action):
         """step_begin + step_kin + set_target(step_kin's result) in one launch (kp_sim_step_head)"""
@@ -303,11 +308,17 @@ class KpSim:
         _check(self.L.kp_sim_step_kin(self.h, _ptr(kin_action, self.n, KIN_ACTION_DIM), _ptr(out, self.n, NQ)), "kp_sim_step_kin")
         return out
 
-    def obs_cc(self, out=None, zf_mean=None, zf_std=None, clip=0.0):
-        out = self._new(CC_OBS_DIM) if out is None else out
+    def obs_cc(self, out=None, zf_mean=None, zf_std=None, clip=0.0, phase=None):
+        """The UHC observation of the handle's layout (kp_sim_obs_cc_ex): [N, cc_obs_dim]; 784 = get_full_obs_v1 for a default model.
+        phase: float [N] device tensor cur_t / expert len, required exactly when the layout has obs_v 0's phase slot."""
+        out = self._new(self.cc_obs_dim) if out is None else out
+        for z in (zf_mean, zf_std):
+            if z is not None and (not z.is_cuda or z.dtype != torch.float32 or not z.is_contiguous() or z.numel() != self.cc_obs_dim):
+                raise ValueError(f"ZFilter mean / std must be contiguous float32 device tensors of {self.cc_obs_dim} elements")
         zm = None if zf_mean is None else C.c_void_p(zf_mean.data_ptr())
         zs = None if zf_std is None else C.c_void_p(zf_std.data_ptr())
-        _check(self.L.kp_sim_obs_cc(self.h, _ptr(out, self.n, CC_OBS_DIM), zm, zs, float(clip)), "kp_sim_obs_cc")
+        ph = None if phase is None else _ptr(phase.view(self.n, 1), self.n, 1)
+        _check(self.L.kp_sim_obs_cc_ex(self.h, _ptr(out, self.n, self.cc_obs_dim), zm, zs, float(clip), ph), "kp_sim_obs_cc_ex")
         return out
 
     def get(self, field: str, out=None):

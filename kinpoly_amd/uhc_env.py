@@ -83,8 +83,9 @@ def get_expert_batch(sim: kpsim.KpSim, expert_qpos: torch.Tensor, body_mass: tor
     return ex
 
 
-def world_rfc_implicit_reward_t(xpos, bquat, prev_bquat, com, action, e_bquat, e_bangvel, e_ee_wpos, e_com, b_diffw, dt=1.0 / 30.0, ws=UHC_REWARD_WEIGHTS):
-    """uhc/core/reward_function.py:4-53 on [N, .] tensors -> (reward [N], info [N, 5])."""
+def world_rfc_implicit_reward_t(xpos, bquat, prev_bquat, com, action, e_bquat, e_bangvel, e_ee_wpos, e_com, b_diffw, dt=1.0 / 30.0, ws=UHC_REWARD_WEIGHTS, vf_dim=6):
+    """uhc/core/reward_function.py:4-53 on [N, .] tensors -> (reward [N], info [N, 5]).  The w_vf term reads action[-vf_dim:] (:44-46) as the reference
+    does: with meta-PD those are meta entries, and with residual_force off (vf_dim 0) action[-0:] is the whole action."""
     N = xpos.shape[0]
     cur_ee = xpos.view(N, 24, 3)[:, list(EE_BODIES)].reshape(N, 15)
     cur_bangvel = get_angvel_fd_t(prev_bquat, bquat, dt)
@@ -94,17 +95,30 @@ def world_rfc_implicit_reward_t(xpos, bquat, prev_bquat, com, action, e_bquat, e
     vel_r = torch.exp(-ws["k_v"] * ((cur_bangvel - e_bangvel) ** 2).sum(1))
     ee_r = torch.exp(-ws["k_e"] * ((cur_ee - e_ee_wpos) ** 2).sum(1))
     com_r = torch.exp(-ws["k_c"] * ((com - e_com) ** 2).sum(1))
-    vf_r = torch.exp(-ws["k_vf"] * (action[:, -6:] ** 2).sum(1)) if ws["w_vf"] > 0 else torch.zeros_like(pose_r)
+    vf = action[:, -vf_dim:] if vf_dim > 0 else action
+    vf_r = torch.exp(-ws["k_vf"] * (vf ** 2).sum(1)) if ws["w_vf"] > 0 else torch.zeros_like(pose_r)
     r = ws["w_p"] * pose_r + ws["w_v"] * vel_r + ws["w_e"] * ee_r + ws["w_c"] * com_r + ws["w_vf"] * vf_r
     return r / (ws["w_p"] + ws["w_v"] + ws["w_e"] + ws["w_c"] + ws["w_vf"]), torch.stack([pose_r, vel_r, ee_r, com_r, vf_r], 1)
 
 
 class BatchedHumanoidEnv:
-    """HumanoidEnv (UHC imitation env) x N.  `load_expert(qpos [N, T, 76])`, `reset(mask)`, `step(a [N, 75])`."""
+    """HumanoidEnv (UHC imitation env) x N.  `load_expert(qpos [N, T, 76])`, `reset(mask)`, `step(a [N, action_dim])`.
+
+    cfg (a UhcConfig) selects the controller's observation (obs_v 0 / 1 / 2, obs_vel, obs_v 0's heading / de-heading / phase), the termination body
+    and the episode / reward constants of its file; without it the env is uhc.yml's (784-d get_full_obs_v1, env_term_body 'body')."""
 
     def __init__(self, n_envs, device=0, kpm_path=None, env_episode_len=100000, env_init_noise=0.0, env_expert_trail_steps=0,
-                 body_diff_thresh=0.5, reward_weights=None, model_options=None, seed=0):
+                 body_diff_thresh=0.5, reward_weights=None, model_options=None, seed=0, cfg=None):
         self.n = int(n_envs)
+        self.cfg = cfg
+        if cfg is not None:
+            env_episode_len, env_init_noise, env_expert_trail_steps = cfg.env_episode_len, cfg.env_init_noise, cfg.env_expert_trail_steps
+            reward_weights = reward_weights or cfg.full_reward_weights()
+            model_options = {**(model_options or {}), **cfg.model_options()}
+        self.obs_v = cfg.obs_v if cfg is not None else 1
+        self.vf_dim = cfg.vf_dim if cfg is not None else 6
+        self.a_ref = None if cfg is None or cfg.action_v != 0 else cfg.a_ref
+        self.term_body = cfg.env_term_body if cfg is not None else "body"
         kpm_path = kpm_path or kpsim.DEFAULT_KPM
         self.model = kpsim.KpModel(kpm_path, **(model_options or {}))
         self.sim = kpsim.KpSim(self.model, self.n, device)
@@ -119,9 +133,11 @@ class BatchedHumanoidEnv:
         self.gen = torch.Generator(device=self.device); self.gen.manual_seed(seed)
         self.cur_t = torch.zeros(self.n, dtype=torch.long, device=self.device)
         self.expert = None
-        self._obs = torch.empty((self.n, kpsim.CC_OBS_DIM), dtype=torch.float32, device=self.device)
-        self.obs_dim, self.action_dim = kpsim.CC_OBS_DIM, kpsim.CC_ACTION_DIM
+        self.obs_dim, self.action_dim = self.sim.cc_obs_dim, self.sim.cc_action_dim
+        self._obs = torch.empty((self.n, self.obs_dim), dtype=torch.float32, device=self.device)
         self._ar = torch.arange(self.n, device=self.device)
+        if self.a_ref is not None:
+            self.a_ref = torch.tensor(self.a_ref, dtype=torch.float32, device=self.device)
 
     def load_expert(self, expert_qpos: torch.Tensor):
         self.expert = get_expert_batch(self.sim, expert_qpos, self.body_mass, self.dt)
@@ -130,8 +146,12 @@ class BatchedHumanoidEnv:
         return self.expert[key][self._ar, t.clamp(max=self.expert["len"] - 1)].contiguous()
 
     def _obs_now(self):
-        self.sim.set_target(self._e("qpos", self.cur_t + 1))            # get_full_obs_v1 looks at expert frame t + 1 (humanoid_im.py:158)
-        return self.sim.obs_cc(self._obs)
+        if self.obs_v == 0:                                             # get_full_obs: get_expert_kin_pose(delta_t=0), frame t (humanoid_im.py:132, 679)
+            self.sim.set_target(self._e("qpos", self.cur_t))
+        else:                                                           # get_full_obs_v1 / _v2 look at expert frame t + 1 (humanoid_im.py:158, 245)
+            self.sim.set_target(self._e("qpos", self.cur_t + 1))
+        phase = (self.cur_t.float() / self.expert["len"]).contiguous() if self.sim.cc_obs_phase else None      # get_phase: cur_t / expert len (:141-142)
+        return self.sim.obs_cc(self._obs, phase=phase)
 
     def reset(self, env_mask: torch.Tensor | None = None):
         m8 = None if env_mask is None else env_mask.to(self.device, torch.uint8).contiguous()
@@ -148,17 +168,23 @@ class BatchedHumanoidEnv:
     def step(self, a: torch.Tensor):
         sim = self.sim
         sim.step_begin()                                               # prev_bquat
-        sim.set_target(self._e("qpos", self.cur_t))                    # compute_torque's base pose is get_expert_kin_pose(delta_t=0) (humanoid_im.py:441, 678)
+        tq = self._e("qpos", self.cur_t)                               # compute_torque's base pose is get_expert_kin_pose(delta_t=0) (humanoid_im.py:441, 678)
+        if self.a_ref is not None:                                     # action_v 0: cfg.a_ref (:451-452); the kernel skips the unwrap for it
+            tq = tq.clone(); tq[:, 7:] = self.a_ref
+        sim.set_target(tq)
         sim.step_ctrl(a.contiguous(), self.frame_skip)
         self.cur_t += 1
         xpos, bquat = sim.get("xpos"), sim.get("bquat")
         com = (sim.get("xipos").view(self.n, 24, 3) * self.body_mass[None, :, None]).sum(1) / self.body_mass.sum()
         e_wbpos = self._e("wbpos", self.cur_t)
         body_diff = (((xpos - e_wbpos).view(self.n, 24, 3) * self.jpos_diffw[None, :, None]).norm(dim=2)).mean(1)
-        fail = body_diff > self.body_diff_thresh
+        if self.term_body == "body":
+            fail = body_diff > self.body_diff_thresh
+        else:   # 'head': the reference's chain tests 'Head', 'root' and 'body' only (humanoid_im.py:554-561), so the default never fails an episode
+            fail = torch.zeros_like(body_diff, dtype=torch.bool)
         end = (self.cur_t >= self.env_episode_len) | (self.cur_t >= self.expert["len"] + self.trail)
         reward, rinfo = world_rfc_implicit_reward_t(xpos, bquat, sim.get("prev_bquat"), com, a, self._e("bquat", self.cur_t), self._e("bangvel", self.cur_t),
-                                                    self._e("ee_wpos", self.cur_t), self._e("com", self.cur_t), self.b_diffw, self.dt, self.ws)
+                                                    self._e("ee_wpos", self.cur_t), self._e("com", self.cur_t), self.b_diffw, self.dt, self.ws, self.vf_dim)
         obs = self._obs_now()
         return obs, torch.ones(self.n, device=self.device), fail | end, {"fail": fail, "end": end, "percent": self.cur_t.float() / self.expert["len"],
                                                                         "custom_reward": reward, "custom_info": rinfo, "body_diff": body_diff}
@@ -203,9 +229,10 @@ class CopycatAgent:
         from .nets import MLP, Value
         from .rollout import _allreduce_grads, estimate_advantages, ppo_surrogate
         self.env, self.group = env, group
-        self.policy = (policy or PolicyMCP()).to(env.device).float()
-        self.value = (value or Value(MLP(kpsim.CC_OBS_DIM, (1024, 512), "relu"))).to(env.device).float()
-        self.running_state = RunningStateOnline(kpsim.CC_OBS_DIM, 5.0, env.device)
+        cfg = getattr(env, "cfg", None)
+        self.policy = (policy or (cfg.make_policy() if cfg is not None else PolicyMCP())).to(env.device).float()
+        self.value = (value or (cfg.make_value() if cfg is not None else Value(MLP(env.obs_dim, (1024, 512), "relu")))).to(env.device).float()
+        self.running_state = RunningStateOnline(env.obs_dim, 5.0, env.device)
         self.gamma, self.tau, self.clip_epsilon, self.num_optim_epoch = gamma, tau, clip_epsilon, num_optim_epoch
         self.opt_p = torch.optim.Adam([p for p in self.policy.parameters() if p.requires_grad], lr=policy_lr)
         self.opt_v = torch.optim.Adam(self.value.parameters(), lr=value_lr)

@@ -4,6 +4,10 @@ the imitation env.  The AMASS clips of the reference are not part of its reposit
 `sample_data/standing_neutral.pkl` (tests/golden/standing_neutral.npz) with small seeded joint-space sinusoids.
 
     python scripts/train_uhc.py --num_envs 4096 --iters 3
+    python scripts/train_uhc.py --cfg uhc --config_root /path/to/KinPoly       (or --cfg path/to/controller.yml)
+
+With --cfg the controller follows the file (kinpoly_amd/uhc_config.py: observation variant, actor, PPO constants, reward weights, termination);
+without it the env and agent are uhc.yml's, as before.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 scripts/train_uhc.py
 """
 import argparse
@@ -27,6 +31,8 @@ def main():
     ap.add_argument("--clip_len", type=int, default=64)
     ap.add_argument("--num_optim_epoch", type=int, default=10)
     ap.add_argument("--save", type=str, default="")
+    ap.add_argument("--cfg", type=str, default="", help="UHC config id (config/**/<id>.yml under --config_root) or a .yml path")
+    ap.add_argument("--config_root", type=str, default=None)
     args = ap.parse_args()
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local)
@@ -43,9 +49,16 @@ def main():
     tt = np.arange(T)[None, :, None] / 30.0
     clips[:, :, 7:] += amp * (np.sin(2 * np.pi * freq * tt + ph) - np.sin(ph))
     torch.manual_seed(1 + rank)
-    env = BatchedHumanoidEnv(n, local, env_init_noise=0.0, seed=1 + rank)
-    env.load_expert(torch.tensor(clips, dtype=torch.float32))
-    agent = CopycatAgent(env, num_optim_epoch=args.num_optim_epoch)
+    if args.cfg:
+        from kinpoly_amd.uhc_config import UhcConfig
+        cfg = UhcConfig(args.cfg, config_root=args.config_root)
+        env = BatchedHumanoidEnv(n, local, seed=1 + rank, cfg=cfg)
+        env.load_expert(torch.tensor(clips, dtype=torch.float32))
+        agent = CopycatAgent(env, **{**cfg.ppo_kwargs(), "num_optim_epoch": args.num_optim_epoch})
+    else:
+        env = BatchedHumanoidEnv(n, local, env_init_noise=0.0, seed=1 + rank)
+        env.load_expert(torch.tensor(clips, dtype=torch.float32))
+        agent = CopycatAgent(env, num_optim_epoch=args.num_optim_epoch)
     if world > 1:
         for p in list(agent.policy.parameters()) + list(agent.value.parameters()):
             dist.broadcast(p.data, 0)
@@ -54,7 +67,7 @@ def main():
         if rank == 0:
             print(json.dumps({"iter": it, **{k: (round(v, 5) if isinstance(v, float) else v) for k, v in stats.items()}}), flush=True)
     if args.save and rank == 0:
-        rs = ck.ZFilter((784,), clip=agent.running_state.clip); rs.rs._n = agent.running_state.count      # the clip the controller was trained under (uhc.yml: 5)
+        rs = ck.ZFilter((env.obs_dim,), clip=agent.running_state.clip); rs.rs._n = agent.running_state.count      # the clip the controller was trained under (uhc.yml: 5)
         rs.rs._M = agent.running_state._mean64.cpu().numpy(); rs.rs._S = agent.running_state._m2.cpu().numpy()
         import pickle
         with ck._RefModulePath(), open(args.save, "wb") as f:
