@@ -420,6 +420,70 @@ int kp_sim_phase_cycles(kp_sim*, double* out8_host);
 /* the same per environment: out_host [N, 8] (the tail of a launch is a few environments, not the mean). */
 int kp_sim_phase_cycles_env(kp_sim*, double* out_host);
 
+/* ---- the UHC's take library and fused tracking step (kinpoly_amd/csrc/kp_takes.hip) ----
+ *
+ * kp_takes: the expert tables of K takes of different lengths, concatenated row-wise (R rows in all; take k owns rows
+ * take_off[k] .. take_off[k + 1] - 1), resident on the device of the handle that built them and independent of its number of envs.  It is
+ * what get_expert (uhc/utils/tools.py:20-85) produces per take and DatasetAMASSSingle keeps per take (uhc/data_loaders/dataset_amass_single.py:
+ * 24-241): per row qpos [76] (as given), qpos_fk [76] (root quaternion normalised: the row kp_sim_set_target stores), wbpos [72], wbquat [96],
+ * bquat [96] (root = the raw root quaternion, get_body_quat), body_com [72], com [3], head_pose [7], ee_wpos [15], ee_pos [15], rq_rmh [4],
+ * qvel [75] (get_qvel_fd_new of rows i - 1, i over dt, clamped to +-10; the first row of every take repeats its second row's, tools.py:57-66),
+ * rlinv [3], rangv [3], rlinv_local [3], bangvel [72]; per take height_lb [1], head_height_lb [1].  A finite difference never crosses a take
+ * boundary.  Forward kinematics is kp_sim_fk's kernel; the rest is one kernel, one wavefront per row, plus one wavefront per take for the minima.
+ *
+ * kp_takes_create: qpos_rows [R,76] on the host (rows_on_device = 0) or on the handle's device; take_off_host: K + 1 increasing offsets on
+ * the host, take_off_host[0] == 0, take_off_host[K] == R, every take at least 2 rows, K >= 1; dt = env.dt (1 / 30; a finite difference is multiplied by (float)(1 / dt)).  Returns NULL and sets
+ * kp_last_error on a bad argument (nothing is launched).  The library keeps no reference to qpos_rows.  Synchronises the handle's stream once. */
+typedef struct kp_takes kp_takes;
+kp_takes* kp_takes_create(kp_sim*, const float* qpos_rows, int rows_on_device, const int32_t* take_off_host, int n_takes, double dt);
+void kp_takes_destroy(kp_takes*);
+/* device pointer, row count (R, or K for the per-take tables) and width of a table by its name above; -1 for an unknown name */
+int kp_takes_table(const kp_takes*, const char* name, const float** ptr, int* rows, int* width);
+/* K, R and (lens_host != NULL) the K take lengths */
+int kp_takes_info(const kp_takes*, int* n_takes, int* n_rows, int32_t* lens_host);
+
+/* Per-env tracking state, owned by the caller (device): which take an env imitates, where in it the episode started, and env.cur_t.
+ * base_qpos [N,76] receives compute_torque's base pose for the next control step (humanoid_im.py:441, 451-452, 678). */
+typedef struct {
+    int32_t* take_id;      /* [N] */
+    int32_t* start_ind;    /* [N] env.start_ind */
+    int32_t* cur_t;        /* [N] env.cur_t */
+    float* base_qpos;      /* [N,76] */
+} kp_uhc_state;
+
+/* world_rfc_implicit_reward's weights (uhc/core/reward_function.py:4-53; uhc.yml:37-48) and HumanoidEnv.step's episode constants */
+typedef struct {
+    float w_p, w_v, w_e, w_c, w_vf, k_p, k_v, k_e, k_c, k_vf;
+    double dt;                 /* env.dt; velocities are differences times (float)(1 / dt), as the torch path evaluates `x / dt` */
+    float body_diff_thresh;    /* 0.5 (humanoid_im.py:557) */
+    int term_body;             /* 1: env_term_body 'body' (fail = body_diff > thresh); 0: 'head' and the rest of the chain never fail (:554-561) */
+    int env_episode_len, trail;/* end = cur_t >= env_episode_len || cur_t + start_ind >= len + env_expert_trail_steps (:564) */
+    int obs_v;                 /* 0: the observation's target is expert frame t; 1 / 2: frame t + 1 (:132, 158, 245) */
+    int vf_dim;                /* the w_vf term reads action[-vf_dim:]; 0: the whole action (reward_function.py:44-46) */
+    int action_dim;
+    const float* a_ref;        /* device [69] for action_v 0 (the base pose's joint angles, :451-452), else NULL */
+    const float* b_diffw;      /* device [24]: the pose term's body weights (root 1, then cfg.b_diffw; the blob's uhc_b_diffw) */
+} kp_uhc_cfg;
+
+/* kp_sim_step_ctrl with compute_torque's base pose read from base_qpos [N,76] instead of the stored target (which then stays the observation's) */
+int kp_sim_step_ctrl_base(kp_sim*, const float* cc_action, int n_substeps, const uint8_t* env_mask, const float* base_qpos);
+
+/* The tail of HumanoidEnv.step after do_simulation (uhc/envs/humanoid_im.py:527-572) in one launch, one wavefront per env: cur_t += 1;
+ * row = take_off[take_id] + min(start_ind + cur_t, len - 1) (get_expert_index, :648-650); calc_body_diff (mean form, :719-726) -> body_diff [N];
+ * fail / end / done uint8 [N]; percent = cur_t / len (:570); world_rfc_implicit_reward -> reward [N], info [N,5] (pose, vel, ee, com, vf terms;
+ * prev_bquat is the record kp_sim_step_begin took); then the stored target <- the expert row the next observation looks at and
+ * st->base_qpos <- the next control step's base pose.  Errors (nothing launched): null argument, a library of another model or device. */
+int kp_sim_uhc_track(kp_sim*, const kp_takes*, const kp_uhc_state* st, const kp_uhc_cfg* cfg, const float* cc_action,
+                     float* reward, float* info, float* body_diff, uint8_t* fail, uint8_t* end, uint8_t* done, float* percent);
+
+/* reset_model (humanoid_im.py:574-623) / fail_safe (:235-238) for the envs of env_mask (uint8 [N] device, NULL = all): take_ids_host /
+ * start_host (host int32 [N], may be NULL: keep) are checked (0 <= take_id < K, 0 <= start < len; nothing is launched on an error) and
+ * assigned; keep_t == 0 zeroes cur_t; then qpos <- the take's raw row at min(start_ind + cur_t, len - 1) (+ noise [N,69] on the joint angles,
+ * device, may be NULL), qvel <- that row's qvel, sim.forward(), and target / base pose as kp_sim_uhc_track leaves them.  keep_t = 1 with
+ * NULL ids is fail_safe(). */
+int kp_sim_uhc_assign(kp_sim*, const kp_takes*, const kp_uhc_state* st, const kp_uhc_cfg* cfg, const uint8_t* env_mask,
+                      const int32_t* take_ids_host, const int32_t* start_host, int keep_t, const float* noise);
+
 const char* kp_last_error(void);
 const char* kp_version(void);
 

@@ -18,6 +18,7 @@
 #include "kp_policy_kernels.hpp"
 #include "kp_step_kernel.hpp"
 #include "kp_pose_contacts.hpp"
+#include "kp_takes.hpp"
 
 namespace {
 thread_local std::string g_err;
@@ -84,6 +85,16 @@ struct kp_sim {
     int ring_used = 0;
     bool ring_on = false;
     hipEvent_t last0 = nullptr, last1 = nullptr;
+    int32_t* uhc_stage = nullptr;                     // [2, N] kp_sim_uhc_assign's take ids and starts on their way to the device
+};
+
+// the take library (include/kinpoly_sim.h): tables on `device`, built with the tables of `model`
+struct kp_takes {
+    const kp_model* model = nullptr;
+    int device = 0;
+    kp::TakeTables L{};
+    std::vector<int32_t> off;
+    std::vector<void*> allocs;
 };
 
 namespace {
@@ -330,7 +341,8 @@ void launch_per_env(const kp_sim* s, const kp::StepArgs& A, int nsub, size_t lds
     else hipLaunchKernelGGL((kp::kp_forward_kernel<NT, OBJ>), dim3(s->n), dim3(NT), lds, s->stream, A);
 }
 
-int launch_step(kp_sim* s, const float* action, int nsub, const uint8_t* mask, bool time_it) {
+// base_qpos (optional): compute_torque's base pose for this launch instead of the stored target (kp_sim_step_ctrl_base)
+int launch_step(kp_sim* s, const float* action, int nsub, const uint8_t* mask, bool time_it, const float* base_qpos = nullptr) {
     const bool obj = s->has_objects;
     if (obj && s->model->threads != 64) return fail("object contact needs threads_per_env = 64");
     if (s->model->threads != 64 && s->model->threads != 128 && s->model->threads != 256) return fail("threads_per_env must be 64, 128 or 256");
@@ -354,7 +366,7 @@ int launch_step(kp_sim* s, const float* action, int nsub, const uint8_t* mask, b
     kp::StepArgs A{};
     A.T = s->T; A.P = s->P; A.n_envs = s->n; A.n_substeps = nsub;
     A.qpos = s->qpos; A.qvel = s->qvel; A.qpos_d = s->qpos_d; A.qvel_d = s->qvel_d; A.warm = s->warm; A.warm2 = s->warm2;
-    A.target_qpos = s->t_qpos; A.action = action; A.env_mask = mask;
+    A.target_qpos = base_qpos ? base_qpos : s->t_qpos; A.action = action; A.env_mask = mask;
     A.xpos = s->xpos; A.xquat = s->xquat; A.xipos = s->xipos; A.diag = s->diag; A.prof = s->prof;
     A.geoms = s->geoms; A.ngeom = s->ngeom; A.dbg_contacts = s->dbg_contacts;
     A.obj_slot = s->obj_slot; A.obj_qpos = s->obj_qpos; A.obj_qvel = s->obj_qvel; A.obj_warm = s->obj_warm; A.obj_warm2 = s->obj_warm2;
@@ -763,6 +775,146 @@ int kp_sim_step_ctrl(kp_sim* s, const float* action, int nsub, const uint8_t* ma
         return fail("kp_sim_step_ctrl: cc_meta_pd = 1 (meta_pd) scales the gains of at most 15 substeps per control step, got " + std::to_string(nsub));
     HIP_OK(hipSetDevice(s->device));
     return launch_step(s, action, nsub, mask, true);
+}
+
+int kp_sim_step_ctrl_base(kp_sim* s, const float* action, int nsub, const uint8_t* mask, const float* base_qpos) {
+    if (!base_qpos) return fail("kp_sim_step_ctrl_base: null base_qpos");
+    if (!s || !action || nsub <= 0) return fail("kp_sim_step_ctrl_base: bad arguments");
+    if (s->xc.meta == 1 && nsub > 15) return fail("kp_sim_step_ctrl_base: cc_meta_pd = 1 (meta_pd) scales the gains of at most 15 substeps per control step, got " + std::to_string(nsub));
+    HIP_OK(hipSetDevice(s->device));
+    return launch_step(s, action, nsub, mask, true, base_qpos);
+}
+
+kp_takes* kp_takes_create(kp_sim* s, const float* qpos_rows, int rows_on_device, const int32_t* take_off, int K, double dt) {
+    if (!s || !qpos_rows || !take_off) { fail("kp_takes_create: null argument"); return nullptr; }
+    if (K < 1) { fail("kp_takes_create: n_takes must be at least 1, got " + std::to_string(K)); return nullptr; }
+    if (!(dt > 0.0)) { fail("kp_takes_create: dt must be positive"); return nullptr; }
+    if (take_off[0] != 0) { fail("kp_takes_create: take_off[0] must be 0, got " + std::to_string(take_off[0])); return nullptr; }
+    for (int k = 0; k < K; k++) {
+        if (take_off[k + 1] <= take_off[k]) { fail("kp_takes_create: take_off must be increasing (take " + std::to_string(k) + ")"); return nullptr; }
+        if (take_off[k + 1] - take_off[k] < 2) { fail("kp_takes_create: take " + std::to_string(k) + " has one row; a take needs at least 2"); return nullptr; }
+    }
+    HIP_OK_NULL(hipSetDevice(s->device));
+    kp_takes* t = new kp_takes();
+    t->model = s->model; t->device = s->device; t->off.assign(take_off, take_off + K + 1);
+    const int R = take_off[K];
+    t->L.R = R; t->L.K = K;
+    bool ok = true;
+    auto alloc = [&](size_t bytes) -> void* {
+        void* d = nullptr;
+        if (hipMalloc(&d, std::max<size_t>(bytes, 16)) != hipSuccess) { ok = false; return nullptr; }
+        t->allocs.push_back(d);
+        return d;
+    };
+    for (int i = 0; i < kp::TT_COUNT; i++)
+        t->L.tab[i] = (float*)alloc(sizeof(float) * (size_t)(i < kp::TT_ROW_TABLES ? R : K) * kp::TAKE_TAB_WIDTH[i]);
+    std::vector<int32_t> row_take((size_t)R);
+    for (int k = 0; k < K; k++) for (int r = take_off[k]; r < take_off[k + 1]; r++) row_take[r] = k;
+    int32_t* d_off = (int32_t*)alloc(sizeof(int32_t) * (K + 1));
+    int32_t* d_rt = (int32_t*)alloc(sizeof(int32_t) * (size_t)R);
+    t->L.take_off = d_off; t->L.row_take = d_rt;
+    auto bail = [&](const std::string& m) -> kp_takes* { fail(m); kp_takes_destroy(t); return nullptr; };
+    if (!ok) return bail("kp_takes_create: device allocation failed");
+    if (hipMemcpy(d_off, take_off, sizeof(int32_t) * (K + 1), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_rt, row_take.data(), sizeof(int32_t) * (size_t)R, hipMemcpyHostToDevice) != hipSuccess)
+        return bail("kp_takes_create: upload of the take offsets failed");
+    if (hipMemcpyAsync(t->L.tab[kp::TT_QPOS], qpos_rows, sizeof(float) * (size_t)R * 76, rows_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream) != hipSuccess)
+        return bail("kp_takes_create: copy of qpos_rows failed");
+    kp::TargetBufs B{t->L.tab[kp::TT_QPOS_FK], t->L.tab[kp::TT_WBPOS], t->L.tab[kp::TT_WBQUAT], t->L.tab[kp::TT_BQUAT], t->L.tab[kp::TT_BODY_COM]};
+    hipLaunchKernelGGL(kp::k_target_fk, dim3((R + 3) / 4), dim3(256), 0, s->stream, R, (const float*)t->L.tab[kp::TT_QPOS], (const uint8_t*)nullptr, B,
+                       s->T.body_pos, s->T.body_ipos, s->T.body_parent, s->T.body_depth);
+    kp::TakeBuildArgs A{t->L, s->T.body_mass, (float)(1.0 / dt)};
+    if (hipGetLastError() != hipSuccess || kp::launch_take_tables(A, s->stream) != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess)
+        return bail("kp_takes_create: building the tables failed");
+    return t;
+}
+
+void kp_takes_destroy(kp_takes* t) {
+    if (!t) return;
+    hipSetDevice(t->device);
+    hipDeviceSynchronize();
+    for (void* p : t->allocs) hipFree(p);
+    delete t;
+}
+
+int kp_takes_table(const kp_takes* t, const char* name, const float** ptr, int* rows, int* width) {
+    static const char* names[kp::TT_COUNT] = {"qpos", "qpos_fk", "wbpos", "wbquat", "bquat", "body_com", "com", "head_pose", "ee_wpos", "ee_pos", "rq_rmh", "qvel",
+                                              "rlinv", "rangv", "rlinv_local", "bangvel", "height_lb", "head_height_lb"};
+    if (!t || !name) return fail("kp_takes_table: null argument");
+    for (int i = 0; i < kp::TT_COUNT; i++)
+        if (!std::strcmp(name, names[i])) {
+            if (ptr) *ptr = t->L.tab[i];
+            if (rows) *rows = i < kp::TT_ROW_TABLES ? t->L.R : t->L.K;
+            if (width) *width = kp::TAKE_TAB_WIDTH[i];
+            return 0;
+        }
+    return fail(std::string("kp_takes_table: no table named '") + name + "'");
+}
+
+int kp_takes_info(const kp_takes* t, int* n_takes, int* n_rows, int32_t* lens) {
+    if (!t) return fail("kp_takes_info: null argument");
+    if (n_takes) *n_takes = t->L.K;
+    if (n_rows) *n_rows = t->L.R;
+    for (int k = 0; lens && k < t->L.K; k++) lens[k] = t->off[k + 1] - t->off[k];
+    return 0;
+}
+
+static int uhc_check(const char* who, const kp_sim* s, const kp_takes* t, const kp_uhc_state* st, const kp_uhc_cfg* c) {
+    const std::string w(who);
+    if (!s || !t || !st || !c) return fail(w + ": null argument");
+    if (!st->take_id || !st->start_ind || !st->cur_t || !st->base_qpos) return fail(w + ": null pointer in kp_uhc_state");
+    if (t->model != s->model) return fail(w + ": the take library was built for another model");
+    if (t->device != s->device) return fail(w + ": the take library lives on device " + std::to_string(t->device) + ", the handle on " + std::to_string(s->device));
+    if (!c->b_diffw) return fail(w + ": null b_diffw in kp_uhc_cfg");
+    if (!(c->dt > 0.0)) return fail(w + ": kp_uhc_cfg.dt must be positive");
+    if (c->action_dim != s->xc.stride) return fail(w + ": kp_uhc_cfg.action_dim " + std::to_string(c->action_dim) + " is not the handle's " + std::to_string(s->xc.stride));
+    if (c->vf_dim < 0 || c->vf_dim > c->action_dim) return fail(w + ": vf_dim out of range");
+    if ((c->a_ref != nullptr) != (s->xc.action_v0 != 0)) return fail(w + ": a_ref must be given exactly for an action_v 0 controller");
+    return 0;
+}
+
+int kp_sim_uhc_track(kp_sim* s, const kp_takes* t, const kp_uhc_state* st, const kp_uhc_cfg* c, const float* action,
+                     float* reward, float* info, float* body_diff, uint8_t* failp, uint8_t* endp, uint8_t* donep, float* percent) {
+    if (uhc_check("kp_sim_uhc_track", s, t, st, c)) return -1;
+    if (!action || !reward || !info || !body_diff || !failp || !endp || !donep || !percent) return fail("kp_sim_uhc_track: null argument");
+    HIP_OK(hipSetDevice(s->device));
+    kp::UhcTrackArgs A{};
+    A.L = t->L; A.n = s->n; A.st = *st; A.cfg = *c; A.inv_dt = (float)(1.0 / c->dt);
+    A.qpos = s->qpos; A.xpos = s->xpos; A.xipos = s->xipos; A.prev_bquat = s->prev_bquat;
+    A.t_qpos = s->t_qpos; A.t_wbpos = s->t_wbpos; A.t_wbquat = s->t_wbquat; A.t_bquat = s->t_bquat; A.t_com = s->t_com;
+    A.body_mass = s->T.body_mass; A.b_diffw = c->b_diffw; A.jpos_diffw = s->diffw; A.action = action;
+    A.reward = reward; A.info = info; A.body_diff = body_diff; A.percent = percent; A.fail = failp; A.end = endp; A.done = donep;
+    HIP_OK(kp::launch_uhc_track(A, s->stream));
+    return 0;
+}
+
+int kp_sim_uhc_assign(kp_sim* s, const kp_takes* t, const kp_uhc_state* st, const kp_uhc_cfg* c, const uint8_t* mask,
+                      const int32_t* take_ids, const int32_t* start, int keep_t, const float* noise) {
+    if (uhc_check("kp_sim_uhc_assign", s, t, st, c)) return -1;
+    if (start && !take_ids) return fail("kp_sim_uhc_assign: start_host needs take_ids_host (a start is checked against its take's length)");
+    for (int e = 0; take_ids && e < s->n; e++) {
+        if (take_ids[e] < 0 || take_ids[e] >= t->L.K)
+            return fail("kp_sim_uhc_assign: take_id " + std::to_string(take_ids[e]) + " of env " + std::to_string(e) + " is out of range (the library holds " + std::to_string(t->L.K) + " takes)");
+        if (start && (start[e] < 0 || start[e] >= t->off[take_ids[e] + 1] - t->off[take_ids[e]]))
+            return fail("kp_sim_uhc_assign: start " + std::to_string(start[e]) + " of env " + std::to_string(e) + " is outside its take");
+    }
+    HIP_OK(hipSetDevice(s->device));
+    if (take_ids && !s->uhc_stage) {
+        bool ok = true;
+        s->uhc_stage = (int32_t*)dalloc(s, 2 * (size_t)s->n, &ok);
+        if (!ok) { s->uhc_stage = nullptr; return fail("kp_sim_uhc_assign: allocation failed"); }
+    }
+    kp::UhcAssignArgs A{};
+    if (take_ids) {
+        HIP_OK(hipMemcpyAsync(s->uhc_stage, take_ids, sizeof(int32_t) * s->n, hipMemcpyHostToDevice, s->stream));
+        A.take_ids = s->uhc_stage;
+        if (start) { HIP_OK(hipMemcpyAsync(s->uhc_stage + s->n, start, sizeof(int32_t) * s->n, hipMemcpyHostToDevice, s->stream)); A.start = s->uhc_stage + s->n; }
+    }
+    A.L = t->L; A.n = s->n; A.keep_t = keep_t; A.obs_v = c->obs_v; A.st = *st; A.mask = mask; A.noise = noise; A.a_ref = c->a_ref;
+    A.qpos = s->qpos; A.qpos_d = s->qpos_d; A.qvel = s->qvel; A.qvel_d = s->qvel_d; A.warm = s->warm;
+    A.t_qpos = s->t_qpos; A.t_wbpos = s->t_wbpos; A.t_wbquat = s->t_wbquat; A.t_bquat = s->t_bquat; A.t_com = s->t_com;
+    HIP_OK(kp::launch_uhc_assign(A, s->stream));
+    return launch_step(s, nullptr, 0, mask, false);      // sim.forward(): derived quantities at the new state
 }
 
 int kp_sim_step_head(kp_sim* s, const float* act) {

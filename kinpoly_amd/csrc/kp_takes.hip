@@ -1,0 +1,239 @@
+// kp_takes.hip -- the kernels declared in kp_takes.hpp (see there).  The fp32 forms of the quaternion logarithm (|xyz| and atan2 instead of
+// sqrt(1 - w^2) and acos) are those of kinpoly_amd/uhc_env.py, which the rectangular torch path uses and explains (kinpoly_amd/context.py:54-75).
+#include "kp_takes.hpp"
+#include "kp_collide.hpp"
+
+namespace kp {
+
+namespace {
+
+constexpr float TK_PI = 3.14159265358979323846f;
+__device__ const int TK_EE[5] = {4, 8, 17, 22, 13};      // L_Toe, R_Toe, L_Wrist, R_Wrist, Head (humanoid_im.py:329)
+
+__device__ __forceinline__ Q4 ldq(const float* p) { return Q4{p[0], p[1], p[2], p[3]}; }
+__device__ __forceinline__ Q4 tk_qinv(Q4 q) {            // quaternion_inverse: conj / dot
+    const float n = q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z;
+    return Q4{q.w / n, -q.x / n, -q.y / n, -q.z / n};
+}
+// get_body_quat's joint quaternion: quaternion_from_euler(a0, a1, a2) with the default 'sxyz' axes (humanoid_im.py:342-354)
+__device__ __forceinline__ Q4 tk_euler_sxyz(float ai, float aj, float ak) {
+    float si, ci, sj, cj, sk, ck;
+    sincosf(0.5f * ai, &si, &ci); sincosf(0.5f * aj, &sj, &cj); sincosf(0.5f * ak, &sk, &ck);
+    const float cc = ci * ck, cs = ci * sk, sc = si * ck, ss = si * sk;
+    return Q4{cj * cc + sj * ss, cj * sc - sj * cs, cj * ss + sj * cc, cj * cs - sj * sc};
+}
+// rotation_from_quaternion (uhc/khrylib/utils/transformation.py:348-356): axis * angle, no wrap, exactly 0 for `1 - |w| < 1e-8`
+__device__ __forceinline__ V3 tk_rotvec(Q4 q) {
+    const float n2 = q.x * q.x + q.y * q.y + q.z * q.z;
+    if (n2 < 1e-8f * (1.0f + fabsf(q.w))) return v3(0.f, 0.f, 0.f);
+    const float sn = sqrtf(n2), s = fmaxf(sn, 1e-30f), ang = 2.0f * atan2f(sn, q.w);
+    return v3(q.x / s * ang, q.y / s * ang, q.z / s * ang);
+}
+// get_angvel_fd (math.py:68-74) of one body.  The division by dt is a multiplication by (float)(1 / dt), the reciprocal taken in fp64, here and in k_take_tables: that is how the
+// torch path's `tensor / dt` is evaluated, and an expert velocity that differs from it in the last bit would start the physics from another state.
+__device__ __forceinline__ V3 tk_angvel(Q4 prev, Q4 cur, float inv_dt) {
+    const V3 r = tk_rotvec(qmul(cur, tk_qinv(prev)));
+    return v3(r.x * inv_dt, r.y * inv_dt, r.z * inv_dt);
+}
+// transform_vec(v, q, 'root'): R(q / |q|)^T v
+__device__ __forceinline__ V3 tk_rotate_t(Q4 q, V3 v) {
+    const float n = sqrtf(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z);
+    const V3 u = v3(-q.x / n, -q.y / n, -q.z / n);
+    const V3 t = 2.0f * cross(u, v);
+    return v + (q.w / n) * t + cross(u, t);
+}
+__device__ __forceinline__ float tk_clamp10(float v) { return fminf(fmaxf(v, -10.0f), 10.0f); }
+
+// the expert row `ro` becomes the stored target (what kp_sim_set_target computes from the same qpos row: the tables ARE k_target_fk's outputs, the
+// target's bquat has the normalised root) and row `rb` the next control step's base pose (joint angles a_ref for action_v 0)
+__device__ __forceinline__ void tk_write_targets(const TakeTables& L, size_t e, size_t ro, size_t rb, float* t_qpos, float* t_wbpos, float* t_wbquat,
+                                                 float* t_bquat, float* t_com, float* base, const float* a_ref, int lane) {
+    const float* qf = L.tab[TT_QPOS_FK] + ro * 76;
+    for (int i = lane; i < 76; i += 64) t_qpos[e * 76 + i] = qf[i];
+    for (int i = lane; i < 72; i += 64) { t_wbpos[e * 72 + i] = L.tab[TT_WBPOS][ro * 72 + i]; t_com[e * 72 + i] = L.tab[TT_BODY_COM][ro * 72 + i]; }
+    for (int i = lane; i < 96; i += 64) {
+        t_wbquat[e * 96 + i] = L.tab[TT_WBQUAT][ro * 96 + i];
+        t_bquat[e * 96 + i] = i < 4 ? qf[3 + i] : L.tab[TT_BQUAT][ro * 96 + i];
+    }
+    const float* qb = L.tab[TT_QPOS_FK] + rb * 76;
+    for (int i = lane; i < 76; i += 64) base[e * 76 + i] = (a_ref && i >= 7) ? a_ref[i - 7] : qb[i];
+}
+
+}  // namespace
+
+// grid = R workgroups of one wavefront.  Row r of take k = row_take[r] differences against the row before it; the take's first row against its
+// second (tools.py:57-66: frame 0 repeats frame 1's velocities), so no difference reaches across take_off[k].
+__global__ __launch_bounds__(64) void k_take_tables(TakeBuildArgs A) {
+    const TakeTables& L = A.L;
+    const int r = blockIdx.x, lane = threadIdx.x;
+    if (r >= L.R) return;
+    const int o0 = L.take_off[L.row_take[r]];
+    const size_t cur = r == o0 ? (size_t)o0 : (size_t)r - 1, nxt = cur + 1, row = (size_t)r;      // the pair the finite difference is taken over
+    const float* q = L.tab[TT_QPOS] + row * 76;
+    const float *qc = L.tab[TT_QPOS] + cur * 76, *qn = L.tab[TT_QPOS] + nxt * 76;
+    const bool body = lane < D_NB;
+    const int b = body ? lane : 0;
+    const float inv_dt = A.inv_dt;
+    // com (data.subtree_com[0]): mass-weighted mean of the body COMs
+    const float m = body ? A.body_mass[b] : 0.f;
+    const V3 bc = ld3(L.tab[TT_BODY_COM] + row * 72 + 3 * b);
+    const float msum = wave_sum(m);
+    const float cx = wave_sum(m * bc.x) / msum, cy = wave_sum(m * bc.y) / msum, cz = wave_sum(m * bc.z) / msum;
+    if (lane == 0) st3(L.tab[TT_COM] + row * 3, v3(cx, cy, cz));
+    // bquat: get_body_quat() starts from the raw root quaternion (the FK's is normalised)
+    if (lane < 4) L.tab[TT_BQUAT][row * 96 + lane] = q[3 + lane];
+    if (lane < 7) L.tab[TT_HEAD_POSE][row * 7 + lane] = lane < 3 ? L.tab[TT_WBPOS][row * 72 + 39 + lane] : L.tab[TT_WBQUAT][row * 96 + 52 + lane - 3];
+    const Q4 rq = ldq(q + 3);
+    if (lane < 5) {
+        const V3 ee = ld3(L.tab[TT_WBPOS] + row * 72 + 3 * TK_EE[lane]);
+        st3(L.tab[TT_EE_WPOS] + row * 15 + 3 * lane, ee);
+        st3(L.tab[TT_EE_POS] + row * 15 + 3 * lane, tk_rotate_t(rq, ee - ld3(q)));
+    }
+    if (lane == 5) {                                          // rq_rmh = de_heading(q) = inverse(heading q) (x) q
+        const float hn = sqrtf(rq.w * rq.w + rq.z * rq.z);
+        const Q4 o = qmul(tk_qinv(Q4{rq.w / hn, 0.f, 0.f, rq.z / hn}), rq);
+        float* d = L.tab[TT_RQ_RMH] + row * 4;
+        d[0] = o.w; d[1] = o.x; d[2] = o.y; d[3] = o.z;
+    }
+    // qvel = get_qvel_fd_new(cur, next, dt) (math.py:45-65), clamped to +-10
+    float* qv = L.tab[TT_QVEL] + row * 75;
+    if (lane == 6) {
+        const V3 v = v3(tk_clamp10((qn[0] - qc[0]) * inv_dt), tk_clamp10((qn[1] - qc[1]) * inv_dt), tk_clamp10((qn[2] - qc[2]) * inv_dt));
+        const Q4 cq = ldq(qc + 3), qrel = qmul(ldq(qn + 3), tk_qinv(cq));
+        const float n2 = qrel.x * qrel.x + qrel.y * qrel.y + qrel.z * qrel.z;
+        V3 axis = v3(1.f, 0.f, 0.f);
+        float angle = 0.f;
+        if (!(n2 < 1e-8f * (1.0f + fabsf(qrel.w)))) {
+            const float sn = sqrtf(n2), s = fmaxf(sn, 1e-30f);
+            axis = v3(qrel.x / s, qrel.y / s, qrel.z / s); angle = 2.0f * atan2f(sn, qrel.w);
+        }
+        if (angle > TK_PI) angle -= 2.0f * TK_PI;
+        V3 w = tk_rotate_t(cq, v3(axis.x * angle * inv_dt, axis.y * angle * inv_dt, axis.z * angle * inv_dt));
+        w = v3(tk_clamp10(w.x), tk_clamp10(w.y), tk_clamp10(w.z));
+        st3(qv, v); st3(qv + 3, w);
+        st3(L.tab[TT_RLINV] + row * 3, v); st3(L.tab[TT_RANGV] + row * 3, w);
+        st3(L.tab[TT_RLINV_LOCAL] + row * 3, tk_rotate_t(ldq(qn + 3), v));       // in the frame of the row the difference ends on (tools.py:62)
+    }
+    for (int j = lane; j < D_NU; j += 64) {
+        float d = qn[7 + j] - qc[7 + j];
+        d -= 2.0f * TK_PI * ceilf((d - TK_PI) / (2.0f * TK_PI));                   // the two while-loops: into (-pi, pi]
+        qv[6 + j] = tk_clamp10(d * inv_dt);
+    }
+    // bangvel = get_angvel_fd(bquat[cur], bquat[next], dt); the joint quaternions are the FK kernel's, the root is the raw one
+    if (body) {
+        const Q4 p = b == 0 ? ldq(qc + 3) : ldq(L.tab[TT_BQUAT] + cur * 96 + 4 * b);
+        const Q4 c = b == 0 ? ldq(qn + 3) : ldq(L.tab[TT_BQUAT] + nxt * 96 + 4 * b);
+        st3(L.tab[TT_BANGVEL] + row * 72 + 3 * b, tk_angvel(p, c, inv_dt));
+    }
+}
+
+// grid = K workgroups of one wavefront: the lowest root and head heights of a take
+__global__ __launch_bounds__(64) void k_take_minima(TakeTables L) {
+    const int k = blockIdx.x, lane = threadIdx.x;
+    if (k >= L.K) return;
+    float h = 3.0e38f, hh = 3.0e38f;
+    for (int r = L.take_off[k] + lane; r < L.take_off[k + 1]; r += 64) {
+        h = fminf(h, L.tab[TT_QPOS][(size_t)r * 76 + 2]);
+        hh = fminf(hh, L.tab[TT_HEAD_POSE][(size_t)r * 7 + 2]);
+    }
+    h = wave_min(h); hh = wave_min(hh);
+    if (lane == 0) { L.tab[TT_HEIGHT_LB][k] = h; L.tab[TT_HEAD_HEIGHT_LB][k] = hh; }
+}
+
+// grid = n workgroups of one wavefront, lane = body
+__global__ __launch_bounds__(64) void k_uhc_track(UhcTrackArgs A) {
+    const TakeTables& L = A.L;
+    const int lane = threadIdx.x;
+    const size_t e = blockIdx.x;
+    if ((int)e >= A.n) return;
+    const kp_uhc_cfg& C = A.cfg;
+    const int k = A.st.take_id[e];
+    const int o0 = L.take_off[k], len = L.take_off[k + 1] - o0, start = A.st.start_ind[e];
+    const int t = A.st.cur_t[e] + 1;
+    const size_t row = (size_t)o0 + (size_t)min(start + t, len - 1);          // get_expert_index (humanoid_im.py:648-650)
+    const bool body = lane < D_NB;
+    const int b = body ? lane : 0;
+    // calc_body_diff (mean form, :719-726)
+    const V3 xp = ld3(A.xpos + e * 72 + 3 * b);
+    const V3 dw = A.jpos_diffw[b] * (xp - ld3(L.tab[TT_WBPOS] + row * 72 + 3 * b));
+    const float body_diff = wave_sum(body ? sqrtf(dot(dw, dw)) : 0.f) / 24.0f;
+    // the whole-body COM from xipos
+    const float m = body ? A.body_mass[b] : 0.f;
+    const V3 xi = ld3(A.xipos + e * 72 + 3 * b);
+    const float msum = wave_sum(m);
+    const V3 com = v3(wave_sum(m * xi.x) / msum, wave_sum(m * xi.y) / msum, wave_sum(m * xi.z) / msum);
+    // world_rfc_implicit_reward (reward_function.py:4-53)
+    const float* q = A.qpos + e * 76;
+    const Q4 bq = b == 0 ? ldq(q + 3) : tk_euler_sxyz(q[7 + 3 * (b - 1)], q[8 + 3 * (b - 1)], q[9 + 3 * (b - 1)]);
+    const Q4 ebq = ldq(L.tab[TT_BQUAT] + row * 96 + 4 * b);
+    const Q4 qd = qmul(bq, tk_qinv(ebq));
+    const float pd = atan2f(sqrtf(qd.x * qd.x + qd.y * qd.y + qd.z * qd.z), fabsf(qd.w)) * A.b_diffw[b];       // acos(|w|)
+    const float pose_s = wave_sum(body ? pd * pd : 0.f);
+    const V3 dv = tk_angvel(ldq(A.prev_bquat + e * 96 + 4 * b), bq, A.inv_dt) - ld3(L.tab[TT_BANGVEL] + row * 72 + 3 * b);
+    const float vel_s = wave_sum(body ? dot(dv, dv) : 0.f);
+    const int eb = TK_EE[lane < 5 ? lane : 0];
+    const V3 de = ld3(A.xpos + e * 72 + 3 * eb) - ld3(L.tab[TT_EE_WPOS] + row * 15 + 3 * (lane < 5 ? lane : 0));
+    const float ee_s = wave_sum(lane < 5 ? dot(de, de) : 0.f);
+    const V3 dc = com - ld3(L.tab[TT_COM] + row * 3);
+    const int nvf = C.vf_dim > 0 ? C.vf_dim : C.action_dim;                     // action[-vf_dim:]; [-0:] is the whole action
+    float vf = 0.f;
+    for (int i = lane; i < nvf; i += 64) { const float a = A.action[e * C.action_dim + (C.action_dim - nvf) + i]; vf += a * a; }
+    vf = wave_sum(vf);
+    if (lane == 0) {
+        const float pose_r = expf(-C.k_p * pose_s), vel_r = expf(-C.k_v * vel_s), ee_r = expf(-C.k_e * ee_s), com_r = expf(-C.k_c * dot(dc, dc));
+        const float vf_r = C.w_vf > 0.f ? expf(-C.k_vf * vf) : 0.f;
+        const float r = C.w_p * pose_r + C.w_v * vel_r + C.w_e * ee_r + C.w_c * com_r + C.w_vf * vf_r;
+        A.reward[e] = r / (C.w_p + C.w_v + C.w_e + C.w_c + C.w_vf);
+        float* io = A.info + e * 5;
+        io[0] = pose_r; io[1] = vel_r; io[2] = ee_r; io[3] = com_r; io[4] = vf_r;
+        const bool fail = C.term_body && body_diff > C.body_diff_thresh;
+        const bool end = t >= C.env_episode_len || start + t >= len + C.trail;        // cur_t + start_ind >= len + trail (humanoid_im.py:564)
+        A.body_diff[e] = body_diff; A.fail[e] = fail; A.end[e] = end; A.done[e] = fail || end;
+        A.percent[e] = (float)t / (float)len;
+        A.st.cur_t[e] = t;
+    }
+    const size_t ro = (size_t)o0 + (size_t)min(start + (C.obs_v == 0 ? t : t + 1), len - 1);
+    tk_write_targets(L, e, ro, row, A.t_qpos, A.t_wbpos, A.t_wbquat, A.t_bquat, A.t_com, A.st.base_qpos, C.a_ref, lane);
+}
+
+// grid = n workgroups of one wavefront; the caller runs sim.forward() on the same mask afterwards
+__global__ __launch_bounds__(64) void k_uhc_assign(UhcAssignArgs A) {
+    const TakeTables& L = A.L;
+    const int lane = threadIdx.x;
+    const size_t e = blockIdx.x;
+    if ((int)e >= A.n || (A.mask && !A.mask[e])) return;
+    const int k = A.take_ids ? A.take_ids[e] : A.st.take_id[e];
+    const int start = A.start ? A.start[e] : (A.take_ids ? 0 : A.st.start_ind[e]);
+    const int t = A.keep_t ? A.st.cur_t[e] : 0;
+    const int o0 = L.take_off[k], len = L.take_off[k + 1] - o0;
+    const size_t row = (size_t)o0 + (size_t)min(start + t, len - 1);
+    if (lane == 0) { A.st.take_id[e] = k; A.st.start_ind[e] = start; A.st.cur_t[e] = t; }
+    for (int i = lane; i < 76; i += 64) {
+        const float v = L.tab[TT_QPOS][row * 76 + i] + ((A.noise && i >= 7) ? A.noise[e * 69 + i - 7] : 0.f);
+        A.qpos[e * 76 + i] = v; A.qpos_d[e * 76 + i] = v;
+    }
+    for (int i = lane; i < 75; i += 64) {
+        const float v = L.tab[TT_QVEL][row * 75 + i];
+        A.qvel[e * 75 + i] = v; A.qvel_d[e * 75 + i] = v; A.warm[e * 75 + i] = 0.f;
+    }
+    const size_t ro = (size_t)o0 + (size_t)min(start + (A.obs_v == 0 ? t : t + 1), len - 1);
+    tk_write_targets(L, e, ro, row, A.t_qpos, A.t_wbpos, A.t_wbquat, A.t_bquat, A.t_com, A.st.base_qpos, A.a_ref, lane);
+}
+
+hipError_t launch_take_tables(const TakeBuildArgs& A, hipStream_t stream) {
+    hipLaunchKernelGGL(k_take_tables, dim3(A.L.R), dim3(64), 0, stream, A);
+    hipLaunchKernelGGL(k_take_minima, dim3(A.L.K), dim3(64), 0, stream, A.L);
+    return hipGetLastError();
+}
+
+hipError_t launch_uhc_track(const UhcTrackArgs& A, hipStream_t stream) {
+    hipLaunchKernelGGL(k_uhc_track, dim3(A.n), dim3(64), 0, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_uhc_assign(const UhcAssignArgs& A, hipStream_t stream) {
+    hipLaunchKernelGGL(k_uhc_assign, dim3(A.n), dim3(64), 0, stream, A);
+    return hipGetLastError();
+}
+
+}  // namespace kp

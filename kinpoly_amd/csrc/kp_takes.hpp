@@ -1,0 +1,69 @@
+// kp_takes.hpp -- the UHC's take library and the fused tracking step (include/kinpoly_sim.h: kp_takes_*, kp_sim_uhc_track, kp_sim_uhc_assign).
+//
+//   k_take_tables   get_expert's derived features (uhc/utils/tools.py:20-85) for R concatenated rows, segmented by take
+//   k_take_minima   height_lb / head_height_lb per take (tools.py:82-83)
+//   k_uhc_track     the tail of HumanoidEnv.step after do_simulation (uhc/envs/humanoid_im.py:527-572): cur_t, calc_body_diff, termination,
+//                   world_rfc_implicit_reward (uhc/core/reward_function.py:4-53), and the expert rows of the next observation / control step
+//   k_uhc_assign    reset_model / fail_safe (humanoid_im.py:574-623, 235-238): take, start and state of the masked envs
+//
+// One wavefront per row / take / env, lane = body; reductions are kp_collide.hpp's DPP butterflies, so there is no LDS, no atomic and every
+// store is a plain vector store.  The kernels live in their own translation unit (kp_takes.hip) for the reason kp_pose_contacts.hpp gives: the step
+// kernels' code generation must not move.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/kinpoly_sim.h"
+#include "kp_device.hpp"
+
+namespace kp {
+
+// the tables, in the order of TakeTables::tab; the last two have one row per take
+enum TakeTab { TT_QPOS, TT_QPOS_FK, TT_WBPOS, TT_WBQUAT, TT_BQUAT, TT_BODY_COM, TT_COM, TT_HEAD_POSE, TT_EE_WPOS, TT_EE_POS, TT_RQ_RMH, TT_QVEL,
+               TT_RLINV, TT_RANGV, TT_RLINV_LOCAL, TT_BANGVEL, TT_HEIGHT_LB, TT_HEAD_HEIGHT_LB, TT_COUNT };
+constexpr int TT_ROW_TABLES = TT_HEIGHT_LB;
+constexpr int TAKE_TAB_WIDTH[TT_COUNT] = {76, 76, 72, 96, 96, 72, 3, 7, 15, 15, 4, 75, 3, 3, 3, 72, 1, 1};
+
+struct TakeTables {
+    float* tab[TT_COUNT];             // [R, width] ([K, 1] for the last two)
+    const int32_t* take_off;          // [K + 1]
+    const int32_t* row_take;          // [R] the take a row belongs to
+    int R, K;
+};
+
+struct TakeBuildArgs {
+    TakeTables L;
+    const float* body_mass;           // [24]
+    float inv_dt;                     // (float)(1 / dt) in fp64: the factor the torch path's `x / dt` multiplies by
+};
+
+struct UhcTrackArgs {
+    TakeTables L;
+    int n;
+    kp_uhc_state st;
+    kp_uhc_cfg cfg;
+    float inv_dt;
+    const float *qpos, *xpos, *xipos, *prev_bquat;             // sim state after the control step
+    float *t_qpos, *t_wbpos, *t_wbquat, *t_bquat, *t_com;      // the stored target (kp_sim_set_target's buffers)
+    const float *body_mass, *b_diffw, *jpos_diffw;             // [24] each
+    const float* action;
+    float *reward, *info, *body_diff, *percent;
+    uint8_t *fail, *end, *done;
+};
+
+struct UhcAssignArgs {
+    TakeTables L;
+    int n, keep_t, obs_v;
+    kp_uhc_state st;
+    const uint8_t* mask;
+    const int32_t *take_ids, *start;  // device [N] or null
+    const float* noise;               // [N, 69] or null
+    const float* a_ref;
+    float *qpos, *qpos_d, *qvel, *qvel_d, *warm;
+    float *t_qpos, *t_wbpos, *t_wbquat, *t_bquat, *t_com;
+};
+
+hipError_t launch_take_tables(const TakeBuildArgs& A, hipStream_t stream);
+hipError_t launch_uhc_track(const UhcTrackArgs& A, hipStream_t stream);
+hipError_t launch_uhc_assign(const UhcAssignArgs& A, hipStream_t stream);
+
+}  // namespace kp

@@ -247,3 +247,78 @@ def synthetic_takes(sim, std_qpos, n_per_action=2, T_range=(110, 160), body_mass
             else:
                 takes[f"none-synthetic-{a}-{j:02d}"] = build_take_features(sim, q, None, None, body_mass)
     return takes
+
+
+def _ewma(x, alpha=0.05):
+    """uhc/utils/math_utils.py:8-12, the recursion as written"""
+    avg = x[0]
+    for i in x[1:]:
+        avg = alpha * i + (1 - alpha) * avg
+    return avg
+
+
+class AmassSingleDataset:
+    """DatasetAMASSSingle (uhc/data_loaders/dataset_amass_single.py:24-241): the UHC's library of whole takes.
+
+    Reads the reference's take pickle `{take: {pose_aa, pose_6d, trans, qpos, obj_pose}}` from data_specs['file_path'] (data_mode 'train') or
+    ['test_file_path'] ('test'), keeps the takes of at least t_min (default 90) frames in the file's order -- or, with mode 'singles', those of
+    data_specs['key_subsets'] -- and hands them to the device as one KpTakes library.  Takes that carry objects (`obj_pose` of another shape than
+    `qpos`: has_obj, :223) are refused by name: object placement for the UHC env is not part of this engine."""
+
+    SAMPLING_TEMP, SAMPLING_FREQ = 0.2, 0.75          # sample_seq's constants (:162-163)
+
+    def __init__(self, data_specs: dict, data_mode: str = "train", takes: dict | None = None):
+        if data_mode not in ("train", "test"):
+            raise ValueError(f"data_mode must be 'train' or 'test', got {data_mode!r}")
+        self.data_specs, self.data_mode = dict(data_specs), data_mode
+        self.t_min, self.t_max, self.mode = data_specs.get("t_min", 90), data_specs.get("t_max", -1), data_specs.get("mode", "all")
+        if takes is None:
+            self.data_root = data_specs["file_path" if data_mode == "train" else "test_file_path"]
+            import joblib
+            takes = joblib.load(self.data_root)
+        if self.mode == "all":
+            keys = list(takes.keys())
+        elif self.mode == "singles":
+            keys = list(data_specs["key_subsets"])
+        else:
+            raise ValueError(f"data_specs['mode'] must be 'all' or 'singles', got {self.mode!r}")
+        self.data_keys, self.qpos = [], {}
+        for k in keys:
+            v = takes[k]
+            if v["pose_aa"].shape[0] < self.t_min:             # :94-97
+                continue
+            qpos = np.asarray(v["qpos"], np.float64)
+            # :103-107 as written: `(not v["obj_pose"] is None) in v` looks the BOOLEAN up among the take's keys, so obj_pose is the take's own only
+            # for a take that has such a key; every other take gets its qpos, and has_obj (:223) is False
+            obj = v["obj_pose"] if ("obj_pose" in v) and ((v["obj_pose"] is not None) in v) else v["qpos"]
+            if np.shape(obj) != qpos.shape:
+                raise NotImplementedError(f"take '{k}' carries objects (obj_pose {np.shape(obj)} against qpos {qpos.shape}): objects in UHC takes are not supported")
+            if qpos.ndim != 2 or qpos.shape[1] != 76 or qpos.shape[0] < 2:
+                raise ValueError(f"take '{k}': qpos must be [T >= 2, 76], got {qpos.shape}")
+            self.data_keys.append(k); self.qpos[k] = qpos
+        if not self.data_keys:
+            raise ValueError(f"no take of at least t_min = {self.t_min} frames")
+        self.lens = np.array([self.qpos[k].shape[0] for k in self.data_keys], np.int64)
+
+    def get_len(self):
+        return len(self.data_keys)
+
+    def new_freq_dict(self):
+        return {k: [] for k in self.data_keys}
+
+    def sample_probs(self, freq_dict: dict) -> np.ndarray:
+        """sample_seq's init_probs (:164-175): exp(-ewma(success history) / 0.2) normalised over data_keys, a take without history counting as ewma 0; fp64"""
+        e = np.array([_ewma(np.array(freq_dict[k])[:, 0] == 1) if len(freq_dict[k]) > 0 else 0 for k in self.data_keys], np.float64)
+        p = np.exp(-e / self.SAMPLING_TEMP)
+        return p / p.sum()
+
+    def draw_probs(self, freq_dict: dict) -> np.ndarray:
+        """the distribution one sample_seq draw follows (:177-181): sample_probs three times out of four, uniform otherwise"""
+        return self.SAMPLING_FREQ * self.sample_probs(freq_dict) + (1 - self.SAMPLING_FREQ) / len(self.data_keys)
+
+    def to_library(self, sim, dt=None):
+        """all kept takes as one device-resident KpTakes (take k = data_keys[k]), built with sim's forward kinematics; dt: env.dt (default: the model's
+        timestep x 15 substeps, as BatchedHumanoidEnv has it)"""
+        from .sim import KpTakes
+        off = np.concatenate([[0], np.cumsum(self.lens)]).astype(np.int32)
+        return KpTakes(sim, np.concatenate([self.qpos[k] for k in self.data_keys], 0).astype(np.float32), off, sim.model.get_option("timestep") * 15 if dt is None else dt)

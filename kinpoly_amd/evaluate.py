@@ -86,3 +86,75 @@ def write_coverage(results: dict, result_dir: str, iter_num: int, data_file: str
     joblib.dump(cov, os.path.join(result_dir, f"{iter_num:04d}_{data_file}_coverage.pkl"))
     joblib.dump(results, os.path.join(result_dir, f"{iter_num:04d}_{data_file}_coverage_full.pkl"))
     return coverage
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# The UHC's own evaluation: run_seq / test_coverage of the reference's scripts/eval_uhc.py:158-241 (and AgentCopycat.eval_seq,
+# uhc/core/agent_copycat.py:101-131), env.n takes at a time on a take library (BatchedHumanoidEnv.load_takes).
+
+@torch.no_grad()
+def run_uhc_sequences(env, policy_net, running_state, take_ids, keys, fail_safe=False, max_steps=100000):
+    """Every env plays one WHOLE take (take_ids [env.n], library ids) with the mean action and running_state(update=False).  Per step, before the
+    action: gt = the expert's qpos at get_expert_index(t), pred = the simulated qpos (eval_uhc.py:175-178).  An env that ends early (percent != 1) is,
+    with fail_safe, put back on the expert and goes on (:188-196); without it the episode is over.  Returns {key: {gt, pred, percent, fail_safe}}
+    for the first len(keys) envs."""
+    n, dev, lib = env.n, env.device, env.takes
+    norm = (lambda o: running_state(o, update=False)) if running_state is not None else (lambda o: o)
+    everyone = torch.ones(n, dtype=torch.bool, device=dev)
+    obs = norm(env.reset(everyone, take_ids=np.ascontiguousarray(take_ids, np.int32)))
+    off, lens = torch.as_tensor(lib.take_off[:-1].astype(np.int64), device=dev), torch.as_tensor(lib.lens.astype(np.int64), device=dev)
+    qtab = lib.table("qpos")
+    active = everyone.clone()
+    used_fs = torch.zeros(n, dtype=torch.bool, device=dev)
+    percent = torch.zeros(n, device=dev)
+    gt, pred, act = [], [], []
+    for step in range(max_steps):
+        k = env.take_id.long()
+        row = off[k] + torch.minimum(env.start_ind.long() + env.cur_t.long(), lens[k] - 1)
+        gt.append(qtab[row]); pred.append(env.sim.get("qpos")); act.append(active.clone())
+        a = policy_net.select_action(obs, True, env.gen).contiguous()
+        obs, _, done, info = env.step(a)
+        newly = done & active
+        percent = torch.where(newly, info["percent"], percent)
+        if fail_safe:                               # masked on the device: no host read per step
+            early = newly & (info["percent"] != 1)
+            used_fs |= early
+            obs = env.fail_safe(early)
+            newly = newly & ~early
+        active = active & ~newly
+        obs = norm(env.reset(done & ~active))       # a finished env waits on its take's first frame; its records are dropped by `active`
+        if step % 8 == 7 and not bool(active.any()):
+            break
+    act = torch.stack(act, 0).cpu().numpy()
+    gt, pred = torch.stack(gt, 0).double().cpu().numpy(), torch.stack(pred, 0).double().cpu().numpy()
+    out = {}
+    for e, key in enumerate(keys):
+        steps = np.nonzero(act[:, e])[0]
+        out[key] = {"gt": [gt[t, e] for t in steps], "pred": [pred[t, e] for t in steps], "percent": float(percent[e]), "fail_safe": bool(used_fs[e])}
+    return out
+
+
+@torch.no_grad()
+def eval_uhc_takes(env, policy_net, running_state, dataset, fail_safe=False, inds=None, library=None):
+    """test_coverage's loop (eval_uhc.py:202-224) over the takes of an AmassSingleDataset, env.n at a time; a short last chunk is padded with copies of
+    its last take.  Loads the data set's library into env (library: one already built with env.sim).  Returns {take name: seq_result} in data-set order."""
+    lib = library if library is not None else dataset.to_library(env.sim)
+    env.load_takes(lib)
+    inds = list(range(dataset.get_len())) if inds is None else [int(i) for i in inds]
+    out = {}
+    for i in range(0, len(inds), env.n):
+        chunk = inds[i:i + env.n]
+        ids = chunk + [chunk[-1]] * (env.n - len(chunk))
+        out.update(run_uhc_sequences(env, policy_net, running_state, ids, [dataset.data_keys[j] for j in chunk], fail_safe=fail_safe))
+    return out
+
+
+def write_uhc_coverage(results: dict, output_dir: str, iter_num: int, data: str, no_full=False):
+    """`<iter>_<data>_coverage.pkl` ({take: {percent}}) and, unless no_full, `<iter>_<data>_coverage_full.pkl` (eval_uhc.py:225-241: the iteration is
+    not zero-padded there, unlike write_coverage's).  Returns the coverage count (percent == 1 and no fail-safe)."""
+    import joblib
+    os.makedirs(output_dir, exist_ok=True)
+    joblib.dump({k: {"percent": r["percent"]} for k, r in results.items()}, os.path.join(output_dir, f"{iter_num}_{data}_coverage.pkl"))
+    if not no_full:
+        joblib.dump(results, os.path.join(output_dir, f"{iter_num}_{data}_coverage_full.pkl"))
+    return sum(1 for r in results.values() if r["percent"] == 1 and not r["fail_safe"])

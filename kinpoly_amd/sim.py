@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "kp_sim_post_step", "kp_sim_reset_rows", "kp_mcp_compose", "kp_sim_step_head", "kp_model_compile", "kp_model_load_xml",
     "kp_mcp_tail", "kp_gru_cell_step", "kp_kin_advance", "kp_pool_advance", "kp_rollout_record_pre", "kp_rollout_record_post", "kp_rollout_record_pre_w", "kp_rollout_record_post_w", "kp_sim_ar_obs_dim", "kp_sim_field_device",
     "kp_sim_lean_state", "kp_sim_pose_contacts", "kp_sim_obs_cc_ex", "kp_sim_cc_obs_dim",
+    "kp_takes_create", "kp_takes_destroy", "kp_takes_table", "kp_takes_info", "kp_sim_step_ctrl_base", "kp_sim_uhc_track", "kp_sim_uhc_assign",
 ]
 
 
@@ -70,6 +71,17 @@ class KpRewardCfg(C.Structure):
     @classmethod
     def default(cls, use_gt_term=True):
         return cls(0.15, 0.15, 0.2, 0.2, 0.2, 0.1, 45.0, 45.0, 50.0, 50.0, 5.0, 0.005, 1.0 / 30.0, 10.0, 12.0, int(use_gt_term))
+
+
+class KpUhcState(C.Structure):
+    """mirror of kp_uhc_state"""
+    _fields_ = [(k, C.c_void_p) for k in ("take_id", "start_ind", "cur_t", "base_qpos")]
+
+
+class KpUhcCfg(C.Structure):
+    """mirror of kp_uhc_cfg"""
+    _fields_ = [(k, C.c_float) for k in ("w_p", "w_v", "w_e", "w_c", "w_vf", "k_p", "k_v", "k_e", "k_c", "k_vf")] + [("dt", C.c_double), ("body_diff_thresh", C.c_float)] + \
+               [(k, C.c_int) for k in ("term_body", "env_episode_len", "trail", "obs_v", "vf_dim", "action_dim")] + [("a_ref", C.c_void_p), ("b_diffw", C.c_void_p)]
 
 
 class KinPolyNativeError(RuntimeError):
@@ -145,6 +157,13 @@ def load_library(path: str | None = None):
     L.kp_sim_status_device.argtypes = [P]; L.kp_sim_status_device.restype = C.c_void_p
     L.kp_sim_mass_matrix.argtypes = [P, F, F]; L.kp_sim_mass_matrix.restype = C.c_int
     L.kp_sim_contacts.argtypes = [P, C.c_void_p]; L.kp_sim_contacts.restype = C.c_int
+    L.kp_takes_create.restype = P; L.kp_takes_create.argtypes = [P, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double]
+    L.kp_takes_destroy.argtypes = [P]
+    L.kp_takes_table.argtypes = [P, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int)]; L.kp_takes_table.restype = C.c_int
+    L.kp_takes_info.argtypes = [P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]; L.kp_takes_info.restype = C.c_int
+    L.kp_sim_step_ctrl_base.argtypes = [P, F, C.c_int, U8, F]; L.kp_sim_step_ctrl_base.restype = C.c_int
+    L.kp_sim_uhc_track.argtypes = [P, P, C.POINTER(KpUhcState), C.POINTER(KpUhcCfg), F, F, F, F, U8, U8, U8, F]; L.kp_sim_uhc_track.restype = C.c_int
+    L.kp_sim_uhc_assign.argtypes = [P, P, C.POINTER(KpUhcState), C.POINTER(KpUhcCfg), U8, C.c_void_p, C.c_void_p, C.c_int, F]; L.kp_sim_uhc_assign.restype = C.c_int
     L.kp_last_error.restype = C.c_char_p
     L.kp_version.restype = C.c_char_p
     _lib = L
@@ -298,6 +317,27 @@ class KpSim:
 
     def step_ctrl(self, cc_action, n_substeps=15, env_mask=None):
         _check(self.L.kp_sim_step_ctrl(self.h, _ptr(cc_action, self.n, self.cc_action_dim), int(n_substeps), _mask_ptr(env_mask, self.n)), "kp_sim_step_ctrl")
+
+    def step_ctrl_base(self, cc_action, base_qpos, n_substeps=15, env_mask=None):
+        """step_ctrl with compute_torque's base pose read from base_qpos [N,76] (kp_sim_step_ctrl_base); the stored target is left alone"""
+        _check(self.L.kp_sim_step_ctrl_base(self.h, _ptr(cc_action, self.n, self.cc_action_dim), int(n_substeps), _mask_ptr(env_mask, self.n),
+                                            _ptr(base_qpos, self.n, NQ)), "kp_sim_step_ctrl_base")
+
+    def uhc_track(self, takes, st, cfg, cc_action, reward, info, body_diff, fail, end, done, percent):
+        """the tail of HumanoidEnv.step in one launch (kp_sim_uhc_track); st: KpUhcState, cfg: KpUhcCfg; outputs are caller-owned device tensors"""
+        _check(self.L.kp_sim_uhc_track(self.h, takes.h, C.byref(st), C.byref(cfg), _ptr(cc_action, self.n, self.cc_action_dim), C.c_void_p(reward.data_ptr()),
+                                       _ptr(info, self.n, 5), C.c_void_p(body_diff.data_ptr()), _mask_ptr(fail, self.n), _mask_ptr(end, self.n), _mask_ptr(done, self.n),
+                                       C.c_void_p(percent.data_ptr())), "kp_sim_uhc_track")
+
+    def uhc_assign(self, takes, st, cfg, env_mask=None, take_ids=None, start=None, keep_t=False, noise=None):
+        """reset_model / fail_safe for the masked envs (kp_sim_uhc_assign); take_ids / start: host int32 arrays [N] or None"""
+        ids = None if take_ids is None else np.ascontiguousarray(take_ids, np.int32)
+        st0 = None if start is None else np.ascontiguousarray(start, np.int32)
+        for a in (ids, st0):
+            if a is not None and a.shape != (self.n,):
+                raise ValueError(f"uhc_assign: take_ids / start must have shape ({self.n},)")
+        _check(self.L.kp_sim_uhc_assign(self.h, takes.h, C.byref(st), C.byref(cfg), _mask_ptr(env_mask, self.n), None if ids is None else ids.ctypes.data_as(C.c_void_p),
+                                        None if st0 is None else st0.ctypes.data_as(C.c_void_p), int(bool(keep_t)), _ptr(noise, self.n, NU)), "kp_sim_uhc_assign")
 
     def step_head(self, kin_action):
         """step_begin + step_kin + set_target(step_kin's result) in one launch (kp_sim_step_head)"""
@@ -483,6 +523,62 @@ class KpSim:
 
     def last_step_seconds(self) -> float:
         return self.L.kp_sim_last_step_seconds(self.h)
+
+
+TAKE_TABLES = ("qpos", "qpos_fk", "wbpos", "wbquat", "bquat", "body_com", "com", "head_pose", "ee_wpos", "ee_pos", "rq_rmh", "qvel", "rlinv", "rangv",
+               "rlinv_local", "bangvel", "height_lb", "head_height_lb")
+
+
+class KpTakes:
+    """The device-resident take library (kp_takes): the expert tables of K takes of different lengths, concatenated row-wise.  Built once with a
+    KpSim's forward kinematics and model tables; independent of the number of envs.  `table(name)` is a zero-copy [R, width] view ([K, 1] for the
+    per-take minima); `take(k)` slices every per-row table to take k."""
+
+    def __init__(self, sim: KpSim, qpos_rows, take_off, dt: float = 1.0 / 30.0):
+        self.sim, self.L, self.device = sim, sim.L, sim.device
+        off = np.ascontiguousarray(np.asarray(take_off, np.int32).reshape(-1))
+        K = len(off) - 1
+        if torch.is_tensor(qpos_rows) and qpos_rows.is_cuda:
+            rows = qpos_rows.to(torch.float32).contiguous()
+            on_dev, ptr, shape = 1, rows.data_ptr(), tuple(rows.shape)
+        else:
+            rows = np.ascontiguousarray(qpos_rows.cpu().numpy() if torch.is_tensor(qpos_rows) else qpos_rows, np.float32)
+            on_dev, ptr, shape = 0, rows.ctypes.data, rows.shape
+        if len(shape) != 2 or shape[1] != NQ:
+            raise ValueError(f"KpTakes: qpos_rows must be [R, {NQ}], got {tuple(shape)}")
+        if K >= 1 and int(off[-1]) != shape[0]:
+            raise ValueError(f"KpTakes: take_off ends at {int(off[-1])}, qpos_rows has {shape[0]} rows")
+        with torch.cuda.device(self.device):
+            self.h = self.L.kp_takes_create(sim.h, C.c_void_p(ptr), on_dev, off.ctypes.data_as(C.c_void_p), K, float(dt))
+        if not self.h:
+            raise KinPolyNativeError(f"kp_takes_create: {self.L.kp_last_error().decode()}")
+        k, r = C.c_int(0), C.c_int(0)
+        lens = np.zeros(K, np.int32)
+        _check(self.L.kp_takes_info(self.h, C.byref(k), C.byref(r), lens.ctypes.data_as(C.c_void_p)), "kp_takes_info")
+        self.K, self.R, self.lens, self.take_off = k.value, r.value, lens, off.copy()
+        self._tabs = {}
+
+    def table(self, name: str) -> torch.Tensor:
+        if name not in self._tabs:
+            p, rows, w = C.c_void_p(0), C.c_int(0), C.c_int(0)
+            _check(self.L.kp_takes_table(self.h, name.encode(), C.byref(p), C.byref(rows), C.byref(w)), "kp_takes_table")
+            iface = {"shape": (rows.value, w.value), "typestr": "<f4", "data": (int(p.value), False), "version": 3, "strides": None}
+            self._tabs[name] = torch.as_tensor(type("_KpTable", (), {"__cuda_array_interface__": iface})(), device=self.device)
+        return self._tabs[name]
+
+    def take(self, k: int) -> dict:
+        a, b = int(self.take_off[k]), int(self.take_off[k + 1])
+        out = {n: self.table(n)[a:b] for n in TAKE_TABLES[:-2]}
+        out["len"] = b - a
+        out["height_lb"], out["head_height_lb"] = self.table("height_lb")[k, 0], self.table("head_height_lb")[k, 0]
+        return out
+
+    def __del__(self):
+        try:
+            self._tabs.clear()
+            self.L.kp_takes_destroy(self.h)
+        except Exception:
+            pass
 
 
 def job_schedule(n_substeps: int, substeps_per_job: int = 4, taper: int = 1) -> list:

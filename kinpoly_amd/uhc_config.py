@@ -56,6 +56,7 @@ class UhcConfig:
         with open(path) as f:
             self.yaml_data = y = yaml.safe_load(f) or {}
         self.id, self.path = cfg_id, path
+        self.data_specs = dict(y.get("data_specs", None) or {})          # DatasetAMASSSingle's settings (read here, used by kinpoly_amd.dataset.AmassSingleDataset)
         g = y.get
         # ---- training constants (copycat_config.py:16-44)
         self.gamma, self.tau = g("gamma", 0.95), g("tau", 0.95)

@@ -9,6 +9,7 @@ form of humanoid_im.py:719-726, threshold 0.5) are a handful of [N, .] tensor op
 from __future__ import annotations
 
 import math
+import os
 
 import numpy as np
 import torch
@@ -132,7 +133,7 @@ class BatchedHumanoidEnv:
         self.frame_skip, self.dt = 15, self.model.get_option("timestep") * 15
         self.gen = torch.Generator(device=self.device); self.gen.manual_seed(seed)
         self.cur_t = torch.zeros(self.n, dtype=torch.long, device=self.device)
-        self.expert = None
+        self.expert = self.takes = None
         self.obs_dim, self.action_dim = self.sim.cc_obs_dim, self.sim.cc_action_dim
         self._obs = torch.empty((self.n, self.obs_dim), dtype=torch.float32, device=self.device)
         self._ar = torch.arange(self.n, device=self.device)
@@ -141,6 +142,62 @@ class BatchedHumanoidEnv:
 
     def load_expert(self, expert_qpos: torch.Tensor):
         self.expert = get_expert_batch(self.sim, expert_qpos, self.body_mass, self.dt)
+        if self.takes is not None:
+            self.takes, self.cur_t = None, torch.zeros(self.n, dtype=torch.long, device=self.device)
+
+    def load_takes(self, library: kpsim.KpTakes, take_ids=None):
+        """Imitate takes of a device-resident library (kinpoly_amd.sim.KpTakes, built with this env's sim) instead of one rectangular clip: every env is
+        on a take of its own length (take_ids [N], default env e -> take e mod K), `step` runs the fused tracking kernel and `reset(mask, take_ids,
+        start)` moves envs between takes.  Call reset() before the first step."""
+        n, dev = self.n, self.device
+        self.takes, self.expert = library, None
+        self.take_id = torch.zeros(n, dtype=torch.int32, device=dev); self.start_ind = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.cur_t = torch.zeros(n, dtype=torch.int32, device=dev)
+        self._base = torch.zeros((n, 76), dtype=torch.float32, device=dev)
+        self._take_len = torch.as_tensor(library.lens, device=dev)
+        self._st = kpsim.KpUhcState(self.take_id.data_ptr(), self.start_ind.data_ptr(), self.cur_t.data_ptr(), self._base.data_ptr())
+        w = self.ws
+        self._tc = kpsim.KpUhcCfg(*[float(w[k]) for k in ("w_p", "w_v", "w_e", "w_c", "w_vf", "k_p", "k_v", "k_e", "k_c", "k_vf")], float(self.dt), float(self.body_diff_thresh),
+                                  int(self.term_body == "body"), int(self.env_episode_len), int(self.trail), int(self.obs_v), int(self.vf_dim), int(self.action_dim),
+                                  None if self.a_ref is None else self.a_ref.data_ptr(), self.b_diffw.data_ptr())
+        self._next_ids = np.arange(n, dtype=np.int32) % library.K if take_ids is None else np.ascontiguousarray(take_ids, np.int32)
+
+    def _noise(self):
+        return (torch.randn((self.n, 69), device=self.device, generator=self.gen) * self.env_init_noise).contiguous() if self.env_init_noise > 0 else None
+
+    def _obs_takes(self):
+        phase = (self.cur_t.float() / self._take_len[self.take_id.long()]).contiguous() if self.sim.cc_obs_phase else None
+        return self.sim.obs_cc(self._obs, phase=phase)
+
+    def _reset_takes(self, env_mask, take_ids, start):
+        m8 = None if env_mask is None else env_mask.to(self.device, torch.uint8).contiguous()
+        if take_ids is None and self._next_ids is not None:            # the first reset puts the envs on the takes load_takes was given
+            take_ids, m8 = self._next_ids, None
+        self._next_ids = None
+        self.sim.uhc_assign(self.takes, self._st, self._tc, m8, take_ids, start, keep_t=False, noise=self._noise())
+        return self._obs_takes()
+
+    def fail_safe(self, env_mask: torch.Tensor | None = None):
+        """HumanoidEnv.fail_safe (humanoid_im.py:235-238) for the masked envs: state := the expert's qpos / qvel at the current index; cur_t stays."""
+        if self.takes is None:
+            raise RuntimeError("fail_safe needs a take library (load_takes)")
+        m8 = None if env_mask is None else env_mask.to(self.device, torch.uint8).contiguous()
+        self.sim.uhc_assign(self.takes, self._st, self._tc, m8, None, None, keep_t=True, noise=None)
+        return self._obs_takes()
+
+    def _step_takes(self, a):
+        if self._next_ids is not None:
+            raise RuntimeError("load_takes: call reset() before the first step (the envs are on no take yet)")
+        sim, n, dev = self.sim, self.n, self.device
+        f = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)      # fresh outputs every step (the caller keeps them): allocator only, no launch
+        o = {"custom_reward": f(n), "custom_info": f(n, 5), "body_diff": f(n), "percent": f(n), "fail": f(n, dt=torch.uint8), "end": f(n, dt=torch.uint8),
+             "done": f(n, dt=torch.uint8)}
+        sim.step_begin()
+        sim.step_ctrl_base(a.contiguous(), self._base, self.frame_skip)
+        sim.uhc_track(self.takes, self._st, self._tc, a, o["custom_reward"], o["custom_info"], o["body_diff"], o["fail"], o["end"], o["done"], o["percent"])
+        obs = self._obs_takes()
+        info = {k: (v.view(torch.bool) if v.dtype == torch.uint8 else v) for k, v in o.items()}
+        return obs, torch.ones(self.n, device=self.device), info.pop("done"), info
 
     def _e(self, key, t):
         return self.expert[key][self._ar, t.clamp(max=self.expert["len"] - 1)].contiguous()
@@ -153,7 +210,12 @@ class BatchedHumanoidEnv:
         phase = (self.cur_t.float() / self.expert["len"]).contiguous() if self.sim.cc_obs_phase else None      # get_phase: cur_t / expert len (:141-142)
         return self.sim.obs_cc(self._obs, phase=phase)
 
-    def reset(self, env_mask: torch.Tensor | None = None):
+    def reset(self, env_mask: torch.Tensor | None = None, take_ids=None, start=None):
+        """take_ids / start (host int arrays [N], library path only): the take and start frame the masked envs move to; None keeps each env's take"""
+        if self.takes is not None:
+            return self._reset_takes(env_mask, take_ids, start)
+        if take_ids is not None or start is not None:
+            raise RuntimeError("reset(take_ids=...) needs a take library (load_takes)")
         m8 = None if env_mask is None else env_mask.to(self.device, torch.uint8).contiguous()
         if env_mask is None:
             self.cur_t.zero_()
@@ -166,6 +228,8 @@ class BatchedHumanoidEnv:
         return self._obs_now()
 
     def step(self, a: torch.Tensor):
+        if self.takes is not None:
+            return self._step_takes(a)
         sim = self.sim
         sim.step_begin()                                               # prev_bquat
         tq = self._e("qpos", self.cur_t)                               # compute_torque's base pose is get_expert_kin_pose(delta_t=0) (humanoid_im.py:441, 678)
@@ -225,7 +289,7 @@ class CopycatAgent:
     on the batched env: one process per GPU, gradients all-reduced like kinpoly_amd.rollout.PPOTrainer."""
 
     def __init__(self, env: BatchedHumanoidEnv, policy: PolicyMCP | None = None, value=None, gamma=0.95, tau=0.95, clip_epsilon=0.2,
-                 policy_lr=5e-5, value_lr=3e-4, num_optim_epoch=10, group=None):
+                 policy_lr=5e-5, value_lr=3e-4, num_optim_epoch=10, group=None, dataset=None, seed=0, output_dir=None):
         from .nets import MLP, Value
         from .rollout import _allreduce_grads, estimate_advantages, ppo_surrogate
         self.env, self.group = env, group
@@ -237,9 +301,104 @@ class CopycatAgent:
         self.opt_p = torch.optim.Adam([p for p in self.policy.parameters() if p.requires_grad], lr=policy_lr)
         self.opt_v = torch.optim.Adam(self.value.parameters(), lr=value_lr)
         self._ar, self._ea, self._surr = _allreduce_grads, estimate_advantages, ppo_surrogate
+        # a library of takes (kinpoly_amd.dataset.AmassSingleDataset): every episode plays a newly drawn whole take (agent_copycat.py:144)
+        self.dataset, self.output_dir, self.freq_dict, self.take_log = dataset, output_dir, None, []
+        if dataset is not None:
+            rank = 0
+            if group is not None:
+                import torch.distributed as dist
+                rank = dist.get_rank(group)
+            self.rng = np.random.default_rng([int(seed), rank])      # every rank draws its own takes
+            path = None if output_dir is None else os.path.join(output_dir, "freq_dict.pt")
+            if path is not None and os.path.exists(path):               # agent_copycat.py:27-28
+                import joblib
+                self.freq_dict = joblib.load(path)
+            else:
+                self.freq_dict = dataset.new_freq_dict()
+            if env.takes is None:
+                env.load_takes(dataset.to_library(env.sim), self._draw(1)[0])
+
+    FREQ_CAP = 5000                                                      # agent_copycat.py:220
+
+    def _draw(self, rows):
+        """take ids [rows, N] drawn ahead on the host from the data set's draw_probs(freq_dict): as in the reference, the dict a sample() draws from is
+        the one it started with (the workers hold a copy, agent_copycat.py:141-144, 210-220)"""
+        p = self.dataset.draw_probs(self.freq_dict)
+        return self.rng.choice(len(p), size=(rows, self.env.n), p=p).astype(np.int32)
+
+    def record_episodes(self, episodes):
+        """freq_dict[take] += [percent, fr_start] for every finished episode (agent_copycat.py:182, 210-220), the last FREQ_CAP kept per take"""
+        for k, percent, fr_start in episodes:
+            self.freq_dict[self.dataset.data_keys[k]].append([float(percent), int(fr_start)])
+        self.freq_dict = {k: v if len(v) < self.FREQ_CAP else v[-self.FREQ_CAP:] for k, v in self.freq_dict.items()}
+
+    def save_freq_dict(self, output_dir=None):
+        import joblib
+        d = output_dir or self.output_dir
+        os.makedirs(d, exist_ok=True)
+        joblib.dump(self.freq_dict, os.path.join(d, "freq_dict.pt"))
+
+    def feed_eval(self, results: dict, data_mode="train", i_iter=0, output_dir=None):
+        """eval_policy's bookkeeping (agent_copycat.py:72-85) for {take: {'percent': ...}}: a completed take enters freq_dict once, a failed one three
+        times; eval_dict_<mode>.pt[i_iter] = {take: percent}.  Returns the coverage count."""
+        coverage = 0
+        for k, res in results.items():
+            full = res["percent"] == 1
+            coverage += int(full)
+            if k in self.freq_dict:
+                self.freq_dict[k] += [[res["percent"], 0] for _ in range(1 if full else 3)]
+        d = output_dir or self.output_dir
+        if d is not None:
+            import joblib
+            from collections import defaultdict
+            os.makedirs(d, exist_ok=True)
+            path = os.path.join(d, f"eval_dict_{data_mode}.pt")
+            ev = joblib.load(path) if os.path.exists(path) else defaultdict(list)
+            ev[i_iter] = {k: v["percent"] for k, v in results.items()}
+            joblib.dump(ev, path)
+        return coverage
+
+    @torch.no_grad()
+    def eval_policy(self, data_mode="train", i_iter=0, dataset=None, output_dir=None):
+        """AgentCopycat.eval_policy (agent_copycat.py:46-85): every take of the data set (default: the training set) played whole with the mean action,
+        the result fed back into freq_dict (feed_eval) and kept in eval_dict_<mode>.pt.  The env returns to the training library afterwards."""
+        from .evaluate import eval_uhc_takes
+        ds = dataset if dataset is not None else self.dataset
+        train_lib = self.env.takes
+        res = eval_uhc_takes(self.env, self.policy, self.running_state, ds, library=train_lib if ds is self.dataset else None)
+        if train_lib is not None:
+            self.env.load_takes(train_lib, self._draw(1)[0])
+        coverage = self.feed_eval(res, data_mode, i_iter, output_dir)
+        return f"Coverage {data_mode} of {coverage} out of {ds.get_len()}"
+
+    @torch.no_grad()
+    def _sample_takes(self, horizon):
+        env = self.env
+        ids = self._draw(horizon)
+        S, A, R, M, D, P, K = [], [], [], [], [], [], []
+        obs = self.running_state(env.reset(torch.ones(env.n, dtype=torch.bool, device=env.device), take_ids=self._draw(1)[0]), update=True)
+        for t in range(horizon):
+            a = self.policy.select_action(obs, False, env.gen).contiguous()
+            K.append(env.take_id.clone())
+            nobs, _, done, info = env.step(a)
+            S.append(obs); A.append(a); R.append(info["custom_reward"]); M.append((~done).float()); D.append(done); P.append(info["percent"])
+            nobs = env.reset(done, take_ids=ids[t])
+            obs = self.running_state(nobs, update=True)
+        done, pct, take = torch.stack(D, 1).cpu().numpy(), torch.stack(P, 1).cpu().numpy(), torch.stack(K, 1).cpu().numpy()      # the one host read of the period
+        eps = [(int(take[e, t]), float(pct[e, t]), 0) for t in range(horizon) for e in np.nonzero(done[:, t])[0]]
+        if self.group is not None:                                       # ranks merge once per sample(), as the AR agent does
+            import torch.distributed as dist
+            allv = [None] * dist.get_world_size(self.group)
+            dist.all_gather_object(allv, eps, group=self.group)
+            eps = [x for v in allv for x in v]
+        self.take_log.append(eps)
+        self.record_episodes(eps)
+        return torch.stack(S, 1), torch.stack(A, 1), torch.stack(R, 1), torch.stack(M, 1)
 
     @torch.no_grad()
     def sample(self, horizon):
+        if self.dataset is not None:
+            return self._sample_takes(horizon)
         env = self.env
         S, A, R, M = [], [], [], []
         obs = self.running_state(env.reset(), update=True)

@@ -23,6 +23,52 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def save_uhc_checkpoint(path, agent, env):
+    from kinpoly_amd import checkpoint as ck
+    import pickle
+    rs = ck.ZFilter((env.obs_dim,), clip=agent.running_state.clip); rs.rs._n = agent.running_state.count
+    rs.rs._M = agent.running_state._mean64.cpu().numpy(); rs.rs._S = agent.running_state._m2.cpu().numpy()
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with ck._RefModulePath(), open(path, "wb") as f:
+        pickle.dump({"policy_dict": {k: v.cpu() for k, v in agent.policy.state_dict().items()},
+                     "value_dict": {k: v.cpu() for k, v in agent.value.state_dict().items()}, "running_state": rs}, f)
+
+
+def train_on_takes(args, rank, local, world):
+    """--data: the reference's training loop on a take library (agent_copycat.py): freq_dict.pt is read from / written next to the checkpoint"""
+    from kinpoly_amd.dataset import AmassSingleDataset
+    from kinpoly_amd.uhc_env import BatchedHumanoidEnv, CopycatAgent
+    cfg = None
+    if args.cfg:
+        from kinpoly_amd.uhc_config import UhcConfig
+        cfg = UhcConfig(args.cfg, config_root=args.config_root)
+    specs = {**(cfg.data_specs if cfg is not None else {}), "file_path": args.data, "test_file_path": args.test_data or args.data}
+    if args.t_min is not None:
+        specs["t_min"] = args.t_min
+    elif cfg is None:
+        specs.setdefault("t_min", 90)
+    ds = AmassSingleDataset(specs, "train")
+    out_dir = os.path.dirname(os.path.abspath(args.save)) if args.save else None
+    env = BatchedHumanoidEnv(args.num_envs, local, seed=1 + rank, cfg=cfg) if cfg is not None else BatchedHumanoidEnv(args.num_envs, local, env_init_noise=0.0, seed=1 + rank)
+    group = dist.group.WORLD if world > 1 else None
+    kw = {**(cfg.ppo_kwargs() if cfg is not None else {}), "num_optim_epoch": args.num_optim_epoch}
+    agent = CopycatAgent(env, group=group, dataset=ds, seed=1, output_dir=out_dir, **kw)
+    if world > 1:
+        for p in list(agent.policy.parameters()) + list(agent.value.parameters()):
+            dist.broadcast(p.data, 0)
+    for it in range(args.iters):
+        stats = agent.optimize_policy(args.horizon)
+        if rank == 0:
+            print(json.dumps({"iter": it, "episodes": len(agent.take_log[-1]), **{k: (round(v, 5) if isinstance(v, float) else v) for k, v in stats.items()}}), flush=True)
+    if args.test_data and rank == 0:
+        print(agent.eval_policy("test", args.iters, dataset=AmassSingleDataset(specs, "test")), flush=True)
+    if args.save and rank == 0:
+        save_uhc_checkpoint(args.save, agent, env)
+        agent.save_freq_dict(out_dir)
+    if world > 1:
+        dist.barrier(); dist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--num_envs", type=int, default=4096)
@@ -33,6 +79,9 @@ def main():
     ap.add_argument("--save", type=str, default="")
     ap.add_argument("--cfg", type=str, default="", help="UHC config id (config/**/<id>.yml under --config_root) or a .yml path")
     ap.add_argument("--config_root", type=str, default=None)
+    ap.add_argument("--data", type=str, default="", help="take pickle of the reference's UHC data ({take: {pose_aa, qpos, ...}}): train on its takes, a newly drawn whole take per episode")
+    ap.add_argument("--test_data", type=str, default="", help="take pickle evaluated (eval_policy, mode 'test') after the last iteration")
+    ap.add_argument("--t_min", type=int, default=None, help="shortest take kept (default: the config's data_specs, else 90)")
     args = ap.parse_args()
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local)
@@ -49,6 +98,8 @@ def main():
     tt = np.arange(T)[None, :, None] / 30.0
     clips[:, :, 7:] += amp * (np.sin(2 * np.pi * freq * tt + ph) - np.sin(ph))
     torch.manual_seed(1 + rank)
+    if args.data:
+        return train_on_takes(args, rank, local, world)
     if args.cfg:
         from kinpoly_amd.uhc_config import UhcConfig
         cfg = UhcConfig(args.cfg, config_root=args.config_root)

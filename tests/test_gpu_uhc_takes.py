@@ -1,0 +1,304 @@
+"""GPU: the UHC's device-resident take library (kp_takes), the fused tracking step (kp_sim_uhc_track / kp_sim_uhc_assign) and the take-drawing
+CopycatAgent, against the rectangular torch path of kinpoly_amd/uhc_env.py (get_expert_batch, BatchedHumanoidEnv.load_expert)."""
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+GOLD = os.path.join(os.path.dirname(__file__), "golden")
+PKL = os.path.join(GOLD, "uhc_takes_small.pkl")
+SPECS = {"file_path": PKL, "test_file_path": PKL, "t_min": 90}
+FK_TABLES = ("qpos", "wbpos", "wbquat", "bquat", "body_com", "head_pose", "ee_wpos")          # pure forward kinematics: copies of kp_sim_fk's outputs
+FD_TABLES = ("com", "ee_pos", "rq_rmh", "qvel", "rlinv", "rangv", "rlinv_local", "bangvel")
+
+
+def _dataset(**kw):
+    from kinpoly_amd.dataset import AmassSingleDataset
+    return AmassSingleDataset({**SPECS, **kw}, "train")
+
+
+def _env(n, **kw):
+    from kinpoly_amd.uhc_env import BatchedHumanoidEnv
+    return BatchedHumanoidEnv(n, 0, **kw)
+
+
+def _fixture():
+    return np.load(os.path.join(GOLD, "uhc_takes.npz"))
+
+
+def test_library_tables_against_the_fp64_fixture():
+    """Per take and table: max |library - fp64| <= 2 x max |torch path - fp64| (tests/golden/uhc_takes.npz: the reference's get_expert on the fp64 oracle);
+    both are fp32 finite differences over 1 / 30 s and differ only in operation order.  Pure forward-kinematics tables equal the torch path bit for bit.
+    Measured on MI355X (largest over the six takes, library / torch): see DESIGN.md section 9."""
+    from kinpoly_amd.uhc_env import get_expert_batch
+    g = _fixture()
+    ds = _dataset(t_min=10)
+    assert list(g["take_names"]) == ds.data_keys
+    env = _env(2)
+    lib = ds.to_library(env.sim)
+    assert lib.K == 6 and lib.R == int(ds.lens.sum()) and list(lib.lens) == list(ds.lens)
+    worst = {}
+    for k, key in enumerate(ds.data_keys):
+        q = torch.tensor(ds.qpos[key], dtype=torch.float32)[None]
+        ex = get_expert_batch(env.sim, q, env.body_mass, env.dt)
+        tk = lib.take(k)
+        assert tk["len"] == ex["len"]
+        for name in FK_TABLES:
+            assert torch.equal(tk[name], ex[name][0]), (key, name)
+        assert float(tk["height_lb"]) == float(ex["height_lb"][0]) and float(tk["head_height_lb"]) == float(ex["head_height_lb"][0])
+        assert abs(float(tk["height_lb"]) - float(g[f"t{k}_height_lb"])) < 1e-6 and abs(float(tk["head_height_lb"]) - float(g[f"t{k}_head_height_lb"])) < 1e-6
+        for name in FD_TABLES:
+            want = g[f"t{k}_qvel"][:, :3] if name == "rlinv" else g[f"t{k}_qvel"][:, 3:6] if name == "rangv" else g[f"t{k}_{name}"]
+            el = float(np.abs(tk[name].double().cpu().numpy() - want).max()); et = float(np.abs(ex[name][0].double().cpu().numpy() - want).max())
+            print(f"{key} {name}: library {el:.3e}  torch {et:.3e}")
+            w = worst.setdefault(name, [0.0, 0.0]); w[0], w[1] = max(w[0], el), max(w[1], et)
+            assert el <= 2 * et, (key, name, el, et)
+    print("worst over takes (library, torch):", {k: (f"{v[0]:.2e}", f"{v[1]:.2e}") for k, v in worst.items()})
+
+
+def test_no_leakage_across_takes():
+    ds = _dataset(t_min=10)
+    env = _env(2)
+    a = ds.to_library(env.sim)
+    far = np.array(ds.qpos[ds.data_keys[0]][0]); far[:3] = [500.0, -300.0, 40.0]; far[7:] = 1.0
+    rows = [ds.qpos[k].astype(np.float32) if i % 2 == 0 else np.tile(far.astype(np.float32), (len(ds.qpos[k]), 1)) for i, k in enumerate(ds.data_keys)]
+    from kinpoly_amd.sim import KpTakes, TAKE_TABLES
+    b = KpTakes(env.sim, np.concatenate(rows, 0), a.take_off)
+    for k in range(0, a.K, 2):
+        ta, tb = a.take(k), b.take(k)
+        for name in TAKE_TABLES:
+            assert torch.equal(ta[name], tb[name]), (k, name)          # first and last rows included
+    assert not torch.equal(a.take(1)["qvel"], b.take(1)["qvel"])
+
+
+def test_fused_step_matches_the_torch_path_bit_for_bit():
+    """The fixture's 8 clips tiled over 64 envs, loaded both ways, same seed, the fixture's actions, 8 control steps: the physics sees the same targets, so
+    the state is bit-identical; reward, its five terms and body_diff against the fixture's fp64 trajectory (the reference's reward on the oracle) with
+    library error <= 2 x torch error.  (These clips' roots do not turn; takes whose root turns: the next test.)"""
+    from kinpoly_amd.sim import KpTakes
+    g = _fixture()
+    assert float(np.abs(g["step_body_diff"] - 0.5).min()) >= 1e-3          # the condition on the fixture, before anything is compared
+    n, T = 64, g["step_clips"].shape[1]
+    clips = g["step_clips"][np.arange(n) % 8]
+    ea, eb = _env(n, seed=3), _env(n, seed=3)
+    ea.load_expert(torch.tensor(clips))
+    eb.load_takes(KpTakes(eb.sim, clips.reshape(-1, 76), np.arange(n + 1) * T, eb.dt))
+    oa, ob = ea.reset(), eb.reset()
+    assert torch.equal(oa, ob) and torch.equal(ea.sim.get("qpos"), eb.sim.get("qpos")) and torch.equal(ea.sim.get("qvel"), eb.sim.get("qvel"))
+    for step in range(8):
+        act = torch.tensor(g["step_actions"][step][np.arange(n) % 8], device=ea.device).contiguous()
+        oa, _, da, ia = ea.step(act)
+        ob, _, db, ib = eb.step(act)
+        for f in ("qpos", "qvel", "target_qpos", "target_wbpos", "target_wbquat", "target_bquat", "target_com"):
+            assert torch.equal(ea.sim.get(f), eb.sim.get(f)), (step, f)
+        assert torch.equal(oa, ob) and torch.equal(da, db), step
+        for f in ("fail", "end"):
+            assert torch.equal(ia[f], ib[f]), (step, f)
+        # percent = cur_t / len: the kernel divides (correctly rounded, so cur_t == len gives exactly 1, which evaluation compares against); torch evaluates
+        # `tensor / int` as a multiplication by the rounded reciprocal and may be one ulp off that
+        assert torch.equal(ib["percent"], torch.full((n,), np.float32(step + 1) / np.float32(T), device=eb.device)), step
+        assert float((ia["percent"] - ib["percent"]).abs().max()) <= 6e-8, step
+        for f, key in (("custom_reward", "step_reward"), ("custom_info", "step_info"), ("body_diff", "step_body_diff")):
+            want = g[key][step][np.arange(n) % 8]
+            et = float(np.abs(ia[f].double().cpu().numpy() - want).max()); el = float(np.abs(ib[f].double().cpu().numpy() - want).max())
+            print(f"step {step} {f}: library {el:.3e}  torch {et:.3e}")
+            assert el <= 2 * et, (step, f, el, et)
+
+
+def test_fixture_takes_track_the_torch_path():
+    """The fixture's takes drift and yaw, so their root angular velocity goes through atan2 and a rotation, which the kernel and torch evaluate in another
+    order: the expert qvel the two paths reset to differs in its last bits (fp32 round-off x 30, < 1e-5 rad/s), and from there the states are close, not
+    identical.  Bound: 1e-5 rad/s over 8 control steps (0.27 s) is 3e-6 rad; the stable-PD controller pulls both towards the same targets; a factor 30
+    for contact stiffness gives 1e-4 on qpos."""
+    ds = _dataset()
+    T = 95
+    clips = np.stack([ds.qpos[k][:T] for k in ds.data_keys]).astype(np.float32)
+    ea, eb = _env(4, seed=3), _env(4, seed=3)
+    ea.load_expert(torch.tensor(clips))
+    eb.load_takes(ds.to_library(eb.sim))
+    ea.reset(); eb.reset()
+    assert torch.equal(ea.sim.get("qpos"), eb.sim.get("qpos"))
+    dv = float((ea.sim.get("qvel") - eb.sim.get("qvel")).abs().max())
+    print(f"reset qvel: max |torch - library| = {dv:.3e}")
+    assert dv < 1e-5
+    a = torch.zeros((4, 75), device=ea.device)
+    for step in range(8):
+        ea.step(a); eb.step(a)
+        for f in ("target_qpos", "target_wbpos", "target_wbquat", "target_bquat", "target_com"):
+            assert torch.equal(ea.sim.get(f), eb.sim.get(f)), (step, f)
+        dq = float((ea.sim.get("qpos") - eb.sim.get("qpos")).abs().max())
+        print(f"step {step}: max |qpos torch - library| = {dq:.3e}")
+        assert dq <= 1e-4, (step, dq)
+
+
+def test_ragged_takes_end_on_their_own_length():
+    ds = _dataset()
+    ids = np.array([0, 2, 3], np.int32)                 # lengths 95, 130, 200
+    env = _env(3, env_expert_trail_steps=2)
+    env.term_body = "head"                              # never fails (humanoid_im.py:554-561)
+    lib = ds.to_library(env.sim)
+    env.load_takes(lib, ids)
+    env.reset()
+    lens = ds.lens[ids]
+    a = torch.zeros((3, 75), device=env.device)
+    ended = {}
+    for t in range(1, 204):
+        _, _, done, info = env.step(a)
+        cur = env.cur_t.cpu().numpy(); pct = info["percent"].cpu().numpy(); d = done.cpu().numpy()
+        assert list(cur) == [t] * 3 and not bool(info["fail"].any())
+        np.testing.assert_array_equal(pct, (np.float32(t) / lens.astype(np.float32)).astype(np.float32))
+        tq = env.sim.get("target_qpos")
+        for e in range(3):
+            if d[e] and e not in ended:
+                ended[e] = t
+            if t >= lens[e] - 1:                        # from cur_t = len - 1 on the target row stays the take's last row
+                assert torch.equal(tq[e], lib.take(int(ids[e]))["qpos_fk"][-1]), (t, e)
+            else:
+                assert torch.equal(tq[e], lib.take(int(ids[e]))["qpos_fk"][t + 1]), (t, e)
+    assert ended == {0: 97, 1: 132, 2: 202}             # each at its own len + trail
+
+
+def test_reassignment_and_fail_safe():
+    ds = _dataset()
+    env = _env(8)
+    lib = ds.to_library(env.sim)
+    env.load_takes(lib, np.zeros(8, np.int32))
+    env.reset()
+    a = torch.zeros((8, 75), device=env.device)
+    for _ in range(3):
+        env.step(a)
+    before = {f: env.sim.get(f) for f in ("qpos", "qvel", "target_qpos")}
+    mask = torch.tensor([0, 1, 0, 0, 1, 0, 0, 0], dtype=torch.bool, device=env.device)
+    ids = np.array([3, 2, 3, 3, 1, 3, 3, 3], np.int32)
+    env.reset(mask, take_ids=ids)
+    q, v = env.sim.get("qpos"), env.sim.get("qvel")
+    assert env.cur_t.tolist() == [3, 0, 3, 3, 0, 3, 3, 3] and env.take_id.tolist() == [0, 2, 0, 0, 1, 0, 0, 0]
+    for e in range(8):
+        if bool(mask[e]):
+            tk = lib.take(int(ids[e]))
+            assert torch.equal(q[e], tk["qpos"][0]) and torch.equal(v[e], tk["qvel"][0])
+            assert torch.equal(env.sim.get("target_qpos")[e], tk["qpos_fk"][1])
+        else:
+            for f in before:
+                assert torch.equal(env.sim.get(f)[e], before[f][e]), (e, f)
+    env.step(a); env.step(a)
+    m2 = torch.tensor([1, 0, 0, 0, 1, 0, 0, 0], dtype=torch.bool, device=env.device)
+    cur = env.cur_t.clone()
+    keep = env.sim.get("qpos")
+    env.fail_safe(m2)
+    q, v = env.sim.get("qpos"), env.sim.get("qvel")
+    assert torch.equal(env.cur_t, cur)
+    assert torch.equal(q[0], lib.take(0)["qpos"][5]) and torch.equal(v[0], lib.take(0)["qvel"][5])
+    assert torch.equal(q[4], lib.take(1)["qpos"][2]) and torch.equal(v[4], lib.take(1)["qvel"][2])
+    assert torch.equal(q[1], keep[1]) and torch.equal(q[7], keep[7])
+    # init noise is drawn in torch and added to the 69 joint angles
+    env2 = _env(2, env_init_noise=0.05, seed=9)
+    env2.load_takes(ds.to_library(env2.sim), np.array([1, 1], np.int32))
+    env2.reset()
+    g = torch.Generator(device=env2.device); g.manual_seed(9)
+    nz = torch.randn((2, 69), device=env2.device, generator=g) * 0.05
+    want = env2.takes.take(1)["qpos"][0][None].repeat(2, 1); want[:, 7:] += nz
+    assert torch.equal(env2.sim.get("qpos"), want)
+
+
+def test_agent_draws_takes_and_keeps_freq_dict():
+    from kinpoly_amd.uhc_env import CopycatAgent
+    ds = _dataset()
+    runs = []
+    for _ in range(2):
+        torch.manual_seed(0)
+        env = _env(256, seed=1, env_episode_len=40)      # every env finishes at least one episode inside the horizon
+        agent = CopycatAgent(env, num_optim_epoch=1, dataset=ds, seed=17)
+        agent.sample(48)
+        eps = agent.take_log[-1]
+        assert len(eps) >= 256
+        n_rec = sum(len(v) for v in agent.freq_dict.values())
+        assert n_rec == len(eps)                          # every finished episode once ...
+        for k, key in enumerate(ds.data_keys):            # ... under the take it played
+            assert len(agent.freq_dict[key]) == sum(1 for e in eps if e[0] == k)
+        runs.append([e[0] for e in eps])
+    assert runs[0] == runs[1]                             # one seed, one take sequence
+    agent.freq_dict = ds.new_freq_dict()
+    for key in ds.data_keys:
+        agent.freq_dict[key] = [[0.2, 0]] * 30 if key == "take_d_130" else [[1.0, 0]] * 30
+    p = ds.draw_probs(agent.freq_dict)[2]
+    draws = agent._draw(40)
+    share, nd = float((draws == 2).mean()), draws.size
+    assert p > 0.5 and abs(share - p) <= 3 * np.sqrt(p * (1 - p) / nd), (share, p)
+
+
+def test_abi_errors():
+    from kinpoly_amd.sim import KinPolyNativeError, KpTakes
+    ds = _dataset()
+    env = _env(4)
+    rows = np.zeros((10, 76), np.float32); rows[:, 3] = 1
+    for off, msg in (([0, 6, 4, 10], "increasing"), ([0, 1, 10], "one row"), ([1, 10], "take_off\\[0\\]"), ([0], "at least 1")):
+        with pytest.raises((KinPolyNativeError, ValueError), match=msg):
+            KpTakes(env.sim, rows[: off[-1]], off)
+    lib = ds.to_library(env.sim)
+    env.load_takes(lib)
+    env.reset()
+    q = env.sim.get("qpos")
+    with pytest.raises(KinPolyNativeError, match="out of range"):
+        env.reset(None, take_ids=np.array([0, 1, 4, 0], np.int32))
+    with pytest.raises(KinPolyNativeError, match="outside its take"):
+        env.reset(None, take_ids=np.array([0, 1, 2, 0], np.int32), start=np.array([0, 96, 0, 0], np.int32))
+    assert torch.equal(env.sim.get("qpos"), q) and env.take_id.tolist() == [0, 1, 2, 3]          # nothing was launched
+    other = _env(4)                                       # its own KpModel
+    other.load_takes(lib)
+    with pytest.raises(KinPolyNativeError, match="another model"):
+        other.reset()
+    with pytest.raises(KinPolyNativeError, match="no table named"):
+        lib.table("nope")
+
+
+class _ZeroPolicy:
+    def select_action(self, x, mean_action=False, generator=None, noise=None):
+        return torch.zeros((x.shape[0], 75), device=x.device)
+
+
+def test_evaluation_over_the_takes(tmp_path):
+    import subprocess
+    import sys
+    import joblib
+    from kinpoly_amd.evaluate import eval_uhc_takes
+    ds = _dataset()
+    env = _env(3)                                       # four takes at three envs: the last chunk is one take and two copies
+    assert env.term_body == "body"
+    lib = ds.to_library(env.sim)
+    res = eval_uhc_takes(env, _ZeroPolicy(), None, ds, library=lib)
+    assert list(res.keys()) == ds.data_keys
+    for k, key in enumerate(ds.data_keys):
+        r = res[key]
+        assert set(r.keys()) == {"gt", "pred", "percent", "fail_safe"} and r["fail_safe"] is False
+        q = ds.qpos[key].astype(np.float32).astype(np.float64)
+        steps = len(r["gt"])
+        assert steps == len(r["pred"]) and 1 <= steps <= len(q)
+        np.testing.assert_array_equal(np.stack(r["gt"]), q[np.minimum(np.arange(steps), len(q) - 1)])
+        np.testing.assert_array_equal(r["pred"][0], q[0])
+        assert abs(r["percent"] - np.float32(steps) / np.float32(len(q))) < 1e-7
+        alone = eval_uhc_takes(env, _ZeroPolicy(), None, ds, inds=[k], library=lib)[key]
+        assert alone["percent"] == r["percent"] and len(alone["pred"]) == steps
+        np.testing.assert_array_equal(np.stack(alone["pred"]), np.stack(r["pred"]))          # bit for bit: an env does not see its neighbours
+    fs = eval_uhc_takes(env, _ZeroPolicy(), None, ds, fail_safe=True, library=lib)
+    for key in ds.data_keys:
+        assert fs[key]["percent"] == 1.0 and len(fs[key]["gt"]) == len(ds.qpos[key])         # runs to the take's end ...
+        assert fs[key]["fail_safe"] == (res[key]["percent"] != 1.0)                           # ... on the fail-safe exactly where it ended early without it
+    # the scripts, as fresh child processes
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    ckpt = str(tmp_path / "models" / "iter_0002.p")
+    run = lambda *a: subprocess.run([sys.executable, *a], cwd=root, capture_output=True, text=True, timeout=600)
+    p = run("scripts/train_uhc.py", "--data", PKL, "--iters", "2", "--num_envs", "64", "--horizon", "8", "--num_optim_epoch", "1", "--save", ckpt)
+    assert p.returncode == 0, p.stderr[-2000:]
+    fd = joblib.load(str(tmp_path / "models" / "freq_dict.pt"))
+    assert list(fd.keys()) == ds.data_keys
+    p = run("scripts/eval_uhc.py", "--mode", "stats", "--ckpt", ckpt, "--takes", PKL, "--iter", "2", "--data", "usr", "--num_envs", "3", "--fail_safe")
+    assert p.returncode == 0, p.stderr[-2000:]
+    cov, full = joblib.load(str(tmp_path / "models" / "2_usr_coverage.pkl")), joblib.load(str(tmp_path / "models" / "2_usr_coverage_full.pkl"))
+    assert list(cov.keys()) == ds.data_keys and all(set(v.keys()) == {"percent"} for v in cov.values())
+    assert all(set(v.keys()) == {"gt", "pred", "percent", "fail_safe"} and v["percent"] == 1.0 for v in full.values())
+    p = run("scripts/eval_uhc.py", "--mode", "stats", "--ckpt", ckpt, "--takes", PKL, "--iter", "3", "--data", "usr", "--num_envs", "3", "--no_full")
+    assert p.returncode == 0 and os.path.exists(str(tmp_path / "models" / "3_usr_coverage.pkl")) and not os.path.exists(str(tmp_path / "models" / "3_usr_coverage_full.pkl"))
