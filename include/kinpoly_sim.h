@@ -201,7 +201,11 @@ int kp_sim_cc_obs_dim(const kp_sim*);
  * Arrays are [R, T, dim] device pointers (action_one_hot [R, 4]), R >= N context rows; env e reads row `row[e]` (int32 [N], or
  * NULL: row e, R = N).  The indirection lets a sampler keep the NEXT episodes' contexts resident next to the current ones and
  * switch an env to its new clip on `done` without copying (agent_ar.py:519-537 draws a new clip per episode).  cur_t is
- * int32 [N] (env.cur_t).  obj_qpos [N,7] (per env, not per row) may be NULL (then get_obj_qpos() == [0,0,0,1,0,0,0], :465-466). */
+ * int32 [N] (env.cur_t).  obj_qpos [N,7] (per env, not per row) may be NULL (then get_obj_qpos() == [0,0,0,1,0,0,0], :465-466).
+ * What the host can and cannot check: T and the null pointers are checked by every call that takes this struct: -1 and a kp_last_error text; cur_t [N] and
+ * row [N] live on the device, so their VALUES are not: cur_t is clamped into the clip by the kernels (any int32 is safe), but row[e] must lie in
+ * [0, R) -- a row outside the table is read out of bounds.  The same holds for the row / row_len arrays of kp_sim_reset_rows, kp_sim_post_step and of
+ * the kp_record_pre struct: row_len[r] must be < ctx_T, and cur_t[e] >= -1 there (gt_target_qpos reads frame min(cur_t + 1, row_len), unclamped from below). */
 typedef struct {
     int T;
     const float* head_pose;               /* [N,T,7]  ar_context['head_pose'] */
@@ -243,7 +247,8 @@ int kp_sim_term_reward(kp_sim*, const kp_ctx* ctx, const kp_reward_cfg* cfg, flo
  * done / end: uint8 [N]; percent: float [N]; done_count (optional, may be NULL): int32 device counter incremented by the number of done envs.
  * obj7 (optional, may be NULL): float [N,7] <- get_obj_qpos(ar_context['action_one_hot'][0]) of the state after the step (humanoid_ar_v1.py:171-172,
  * 466-477): the simulated pose of the action's first object, data.qpos[76 + action_index_map[a] : +7]; rows whose clip has no action are left
- * alone.  It is the buffer kp_ctx.obj_qpos points to, so the next kp_sim_obs_ar reads the objects where the physics left them. */
+ * alone.  It is the buffer kp_ctx.obj_qpos points to, so the next kp_sim_obs_ar reads the objects where the physics left them.  obj7 needs
+ * ctx->action_one_hot (refused with -1 otherwise); ctx->T < 2 is refused: the reward reads ground-truth frame t - 1 with t clamped into [1, T - 1]. */
 int kp_sim_post_step(kp_sim*, const kp_ctx* ctx, const kp_reward_cfg* cfg, int32_t* cur_t, const int32_t* row_len, int env_episode_len,
                      float* reward, float* info, uint8_t* fail, float* diffs, uint8_t* done, uint8_t* end, float* percent, int32_t* done_count, float* obj7);
 
@@ -304,7 +309,8 @@ int kp_gae_bootstrap(int n_envs, int T, const float* rewards, const float* masks
 
 /* PolicyMCP.forward / select_action after the primitives' and the composer's GEMMs (uhc/core/policy_mcp.py:30-38, uhc/khrylib/rl/core/policy.py:12-15):
  * out [n, A] = sum_k softmax(logits [n, K])_k * prim [K, n, A]  (+ stdv [A] * noise [n, A], rows noise_stride floats apart, when noise != NULL).
- * All device float32; logits are the composer MLP's output BEFORE its softmax. */
+ * All device float32; logits are the composer MLP's output BEFORE its softmax.  noise_stride < A (rows of the noise window overlapping, the last one read
+ * past the buffer) and K > 64 are refused (-1). */
 int kp_mcp_compose(int n, int K, int A, const float* logits, const float* prim, const float* noise, int noise_stride, const float* stdv, float* out, void* hip_stream);
 
 /* One frame of the kinematic roll-out behind PolicyAR.init_context (TrajARNet.step, kin_poly/models/traj_ar_smpl_net.py:292-330): next_qpos [n,76] =

@@ -108,9 +108,12 @@ __global__ void k_kin_advance(int n, const float* __restrict__ qpos, const float
     // sin(acos(w)) and 2 acos(w) of the reference (fp64 there) without the fp32 cancellation of 1 - w^2: for the unit quaternion qrel the sine is |xyz|.
     // The reference's `sin < 1e-5 -> no rotation` branch (rotation_from_quaternion_batch, torch_utils.py:126-128) is dead code there: its safe_acos
     // clamps w to +-(1 - 1e-7) (:32-36), so the sine it tests is never below 4.5e-4 and a rotation too small for 1 - w to show comes out as
-    // xyz / sin(acos(1 - 1e-7)) * 2 acos(1 - 1e-7) = 2 xyz -- which is what |xyz| and atan2 give; only the exact zero needs a guard.
+    // xyz / sin(acos(1 - 1e-7)) * 2 acos(1 - 1e-7) = 2 xyz -- which is what |xyz| and atan2 give.  Only "no rotation" needs a guard, and it is the
+    // exact condition: an action whose expmap argument dt * angv is zero (the fp64 reference then has qrel = identity to 1e-16 and returns 0; in fp32
+    // next (x) cur^-1 leaves 1e-7 of rounding in xyz, 6e-6 rad/s after 2 / dt), or a qrel whose xyz came out exactly zero.
     float sn = sqrtf(qrel.x * qrel.x + qrel.y * qrel.y + qrel.z * qrel.z);
-    const bool small = !(sn > 0.0f);
+    const V3 ev = dt * angv;
+    const bool small = !(sn > 0.0f) || (ev.x == 0.0f && ev.y == 0.0f && ev.z == 0.0f);
     sn = fmaxf(sn, 1e-30f);
     const V3 axis = small ? v3(1.f, 0.f, 0.f) : v3(qrel.x / sn, qrel.y / sn, qrel.z / sn);
     float angle = small ? 0.0f : 2.0f * atan2f(sn, qrel.w);

@@ -1114,6 +1114,7 @@ int kp_sim_post_step(kp_sim* s, const kp_ctx* c, const kp_reward_cfg* w, int32_t
     if (!s || !c || !w || !cur_t || !row_len || !reward || !info || !failp || !diffs || !done || !end || !percent || !c->head_pose || !c->gt_bquat || !c->gt_wbpos || c->T < 2)
         return fail("kp_sim_post_step: bad arguments");
     if (c->cur_t != cur_t) return fail("kp_sim_post_step: cur_t must be the buffer the context reads (kp_ctx.cur_t)");
+    if (obj7 && !c->action_one_hot) return fail("kp_sim_post_step: obj7 needs the context's action_one_hot");
     HIP_OK(hipSetDevice(s->device));
     kp::RewardW W{w->w_hp, w->w_hq, w->w_p, w->w_jp, w->w_act_p, w->w_act_v, w->k_hp, w->k_hq, w->k_p, w->k_jp, w->k_act_p, w->k_act_v,
                   w->dt, w->body_diff_thresh, w->body_diff_gt_thresh, w->use_gt_term};
@@ -1202,6 +1203,7 @@ int kp_rollout_record_post(const kp_record_post* r, void* stream) { return kp_ro
 
 int kp_mcp_compose(int n, int K, int A, const float* logits, const float* prim, const float* noise, int noise_stride, const float* stdv, float* out, void* stream) {
     if (n <= 0 || K <= 0 || K > 64 || A <= 0 || !logits || !prim || !out || (noise && !stdv)) return fail("kp_mcp_compose: bad arguments");
+    if (noise && noise_stride < A) return fail("kp_mcp_compose: noise_stride " + std::to_string(noise_stride) + " is smaller than the row width A = " + std::to_string(A));
     const size_t tot = (size_t)n * A;
     hipLaunchKernelGGL(kp::k_mcp_compose, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, K, A, logits, prim, noise, noise_stride, stdv, out);
     HIP_OK(hipGetLastError());
