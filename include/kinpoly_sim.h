@@ -107,7 +107,9 @@ void kp_model_free(kp_model*);
  * unwrapped to within pi of qpos; 0: the target row as it is, the caller installs cfg.a_ref), "cc_rfc" (1 default: implicit residual force from action
  * [69:75]; 0: none), "cc_meta_pd" (0 default; 1 meta_pd: kp / kd x clip(m + 1, 0, 10) with m = action[m0 + substep] / [m0 + substep + 15], at most 15
  * substeps per call; 2 meta_pd_joint: by joint, [m0 + j] / [m0 + 69 + j]; m0 = 69 + 6 cc_rfc).  cc_action_dim = 69 + 6 cc_rfc + (30 | 138 | 0); any
- * other value fails.  A non-default controller runs on the full layout (no lean job-queue form). */
+ * other value fails.  A non-default controller runs on the full layout (no lean job-queue form).
+ * Every name, where its value lives and how a set value is checked or clamped is one row of the OPTIONS table in kinpoly_amd/csrc/kp_sim.hip; a refusal
+ * reads "<name> must be ...", an unknown name fails to set and reads NaN. */
 int kp_model_set_option(kp_model*, const char* name, double value);
 double kp_model_get_option(const kp_model*, const char* name);
 

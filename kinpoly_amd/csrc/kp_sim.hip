@@ -2,6 +2,7 @@
 // and the extern "C" entry points declared in include/kinpoly_sim.h.  No torch types anywhere.
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cmath>
 #include <algorithm>
 #include <cstdlib>
@@ -25,12 +26,13 @@ thread_local std::string g_err;
 int fail(const std::string& m) { g_err = m; return -1; }
 #define HIP_OK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
 #define HIP_OK_NULL(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { fail(std::string(#expr) + ": " + hipGetErrorString(e_)); return nullptr; } } while (0)
+int launched() { HIP_OK(hipGetLastError()); return 0; }      // the status of the launches an entry point has just enqueued
 }  // namespace
 
 struct kp_model {
     kp::HostModel h;
     int contact = 1, limits = 1, stale = 1, solver_iter = 100, threads = 64, dynamic_objects = 1, lpt_order = -1, substeps_per_job = 4, queue_slots = 0, job_taper = 1, queue_fence = 1, queue_heavy = 160, queue_prio = -1, queue_late = -1, job_auto = 1, lean_queue = 1, lean_adaptive = 1, lds_pad = 0, lean_cap = kp::EnvLdsLean::MAXCON;
-    float warm_extrap = -1.f;      // < 0: automatic (0.75 when the scene's free objects are simulated, 0 otherwise); see kp_step_kernel.hpp
+    double warm_extrap = -1.0;     // a float's value; < 0: automatic (0.75 when the scene's free objects are simulated, 0 otherwise); see kp_step_kernel.hpp
     int planemesh_max = 3; double planemesh_tol = 0.3;   // mjc_PlaneConvex's maxplanemesh / tolplanemesh (the blob's `planemesh`)
     int ar_obs_action = 1;        // 0: kp_sim_obs_ar writes the 101-d observation without the action one-hot (use_action: false, humanoid_ar_v1.py:200-201)
     // the UHC controller's observation (kp_sim_obs_cc_ex): obs_v 0 / 1 / 2, obs_vel 'root', and obs_v 0's obs_heading / root_deheading / obs_phase
@@ -39,6 +41,43 @@ struct kp_model {
     int cc_action_v = 1, cc_rfc = 1, cc_meta_pd = 0;
     int actuation = 1;            // 0: no stable-PD torque, no residual force (ctrl = qfrc_applied = 0): torque-free flight for the energy test
     double solver_tol = 1e-8, gravity_z = -9.81, gravity_x = 0.0, gravity_y = 0.0;   // solver_iter / solver_tol: mjOption.iterations / tolerance of the reference model (kp_model_load)
+};
+
+// kp_sim's device rows, one group per concern; kp_sim_create allocates them group by group, kp_sim::allocs owns them all
+struct StateRows {        // the simulated state, its derived kinematics and the solver's warm starts
+    float *qpos = nullptr, *qvel = nullptr, *qpos_d = nullptr, *qvel_d = nullptr, *warm = nullptr, *warm2 = nullptr, *warm3 = nullptr;
+    float *xpos = nullptr, *xquat = nullptr, *xipos = nullptr, *prev_bquat = nullptr, *prev_hpos = nullptr;
+    int* diag = nullptr;
+};
+struct JobQueue {         // the control-step launch: LPT order, the job FIFO of kp_step_queue_kernel, the lean layout's overflow list
+    int* order = nullptr; unsigned* cost = nullptr;   // launch order of the control-step kernel (k_lpt_order)
+    unsigned *jobq = nullptr, *jobctr = nullptr, *ovfq = nullptr;      // ovfq: jobs handed from the lean queue kernel to kp_step_overflow_kernel
+    float* spd_next = nullptr;                        // [N, 80] torque hand-over between the jobs of a control step
+    int wave_slots = 2048;
+    int nsub = -1, layout = -1;                       // what the queue's "heavy job" yardstick (jobctr[32..33] -> [48..49]) was measured on
+};
+// how many envs the lean layout handed to the overflow kernel, read back WITHOUT waiting: every lean launch copies its count to pinned memory and records an
+// event; a later launch whose predecessor's event has completed looks at the number.  When more than 1 / 64 of the envs overflow (a policy at random init resets
+// every env onto a garbage pose, half buried, with 30 - 70 contacts) the overflow kernel's second pass over them costs more than the lean layout saves: the
+// next 64 launches use the full layout, then the lean one is tried again.  Results do not depend on the layout.
+struct OverflowReadback {
+    unsigned* host = nullptr; hipEvent_t ev[2] = {nullptr, nullptr}; bool pending[2] = {false, false};
+    long lean_off_until = -1; int fallbacks = 0;
+    unsigned last = 0;            // the most recent count that has arrived: sizes the overflow kernel's grid (an empty 2048-workgroup launch costs 34 us)
+};
+struct ObjectRows {
+    float *qpos = nullptr, *geoms = nullptr;          // [N,35], [N,8,17]
+    float *qvel = nullptr, *warm = nullptr, *warm2 = nullptr;   // [N,30], [N,12], [N,12]
+    signed char* slot = nullptr;                      // [N,2]
+    int* ngeom = nullptr;
+    const float* d_geoms = nullptr; const float* d_mass = nullptr; int n_geoms = 0, n_obj = 0;      // the model's object geoms / masses on the device
+    bool on = false;                                  // kp_sim_set_objects / kp_sim_reset_rows installed objects: the control step runs the object kernels
+};
+struct Timing {
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, last0 = nullptr, last1 = nullptr;      // the handle's own pair; the pair of the last timed launch
+    std::vector<hipEvent_t> ring;                     // event pairs of the recorded launches (kp_sim_timing_reset)
+    int ring_used = 0;
+    bool ring_on = false, timed = false;
 };
 
 struct kp_sim {
@@ -52,39 +91,17 @@ struct kp_sim {
     std::vector<void*> allocs;
     kp::DevTables T{};
     kp::Params P{};
-    float *qpos = nullptr, *qvel = nullptr, *qpos_d = nullptr, *qvel_d = nullptr, *warm = nullptr, *warm2 = nullptr;
-    float *xpos = nullptr, *xquat = nullptr, *xipos = nullptr, *scratch = nullptr;
-    float *prev_bquat = nullptr, *prev_hpos = nullptr, *diffw = nullptr;
-    float *t_qpos = nullptr, *t_wbpos = nullptr, *t_wbquat = nullptr, *t_bquat = nullptr, *t_com = nullptr;
-    int* diag = nullptr;
-    int* order = nullptr; unsigned* cost = nullptr;   // launch order of the control-step kernel (k_lpt_order)
-    unsigned *jobq = nullptr, *jobctr = nullptr, *ovfq = nullptr;      // ovfq: jobs handed from the lean queue kernel to kp_step_overflow_kernel
-    float* warm3 = nullptr;
-    // how many envs the lean layout handed to the overflow kernel, read back WITHOUT waiting: every lean launch copies its count to pinned memory and records an
-    // event; a later launch whose predecessor's event has completed looks at the number.  When more than 1 / 64 of the envs overflow (a policy at random init resets
-    // every env onto a garbage pose, half buried, with 30 - 70 contacts) the overflow kernel's second pass over them costs more than the lean layout saves: the
-    // next 64 launches use the full layout, then the lean one is tried again.  Results do not depend on the layout.
-    unsigned* ovf_host = nullptr; hipEvent_t ovf_ev[2] = {nullptr, nullptr}; bool ovf_pending[2] = {false, false};
-    long launch_index = 0, lean_off_until = -1; int lean_fallbacks = 0;
-    unsigned ovf_last = 0;            // the most recent count that has arrived: sizes the overflow kernel's grid (an empty 2048-workgroup launch costs 34 us)      // job FIFO of kp_step_queue_kernel
-    float* spd_next = nullptr;                        // [N, 80] torque hand-over between the jobs of a control step
-    int jobq_cap = 0, wave_slots = 2048;
-    int q_nsub = -1, q_layout = -1;                   // what the queue's "heavy job" yardstick (jobctr[32..33] -> [48..49]) was measured on
+    float* diffw = nullptr;                           // the model's body_diffw
+    StateRows st;
+    kp::TargetBufs tgt{};                             // the target dict {qpos, wbpos, wbquat, bquat, body_com}
+    JobQueue q;
+    OverflowReadback ovf;
+    ObjectRows obj;
+    Timing tm;
+    long launch_index = 0;
     int last_nsub = 15;                               // substeps of the last control step (kp_sim_lean_state)
     unsigned long long* prof = nullptr;
     float* dbg_contacts = nullptr;
-    float *obj_qpos = nullptr, *geoms = nullptr;      // [N,35], [N,8,17]
-    float *obj_qvel = nullptr, *obj_warm = nullptr, *obj_warm2 = nullptr;   // [N,30], [N,12], [N,12]
-    signed char* obj_slot = nullptr;                  // [N,2]
-    int* ngeom = nullptr;
-    const float* d_obj_geoms = nullptr; const float* d_obj_mass = nullptr; int n_obj_geoms = 0, n_obj = 0;
-    bool has_objects = false;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
-    std::vector<hipEvent_t> ring;  // event pairs of the recorded launches
-    int ring_used = 0;
-    bool ring_on = false;
-    hipEvent_t last0 = nullptr, last1 = nullptr;
     int32_t* uhc_stage = nullptr;                     // [2, N] kp_sim_uhc_assign's take ids and starts on their way to the device
 };
 
@@ -257,22 +274,22 @@ int job_schedule(int nsub, int spj, int taper, int* sizes) {
 // The lean layout (EnvLdsLean) serves floor scenes in stale mode only: its pAa shares words with jv3 | lim_jv, which in fresh mode (stale_kinematics = 0)
 // hold make_constraint's aref while the substep's aba_solve writes pAa (kp_device.hpp).  P.stale: the value the kernel receives.
 // (the extended controller has no lean-layout instantiation: plan_step sends it to the full layout)
-bool lean_eligible(const kp_sim& s) { return !s.has_objects && s.model->lean_queue && s.model->threads == 64 && s.P.stale && !s.xc_on; }
+bool lean_eligible(const kp_sim& s) { return !s.obj.on && s.model->lean_queue && s.model->threads == 64 && s.P.stale && !s.xc_on; }
 
 // resident envs per CU: LDS is allocated in 1 280-byte granules, 128 per CU (tools/micro/lds_granule_probe.hip); the register budgets allow 8 waves per CU
 // (full layout, <= 256 VGPRs) and 12 (lean layout, 168 VGPRs)
 int envs_per_cu(size_t lds_bytes, int reg_cap) { return std::min(reg_cap, 128 / (int)((lds_bytes + 1279) / 1280)); }
 
-// the adaptive lean / full fallback (kp_sim::ovf_host): take the overflow counts that have arrived; a failed query ends the slot's wait and fails the step
+// the adaptive lean / full fallback (OverflowReadback): take the overflow counts that have arrived; a failed query ends the slot's wait and fails the step
 int poll_overflow(kp_sim* s) {
     for (int k = 0; k < 2; k++) {
-        if (!s->ovf_pending[k]) continue;
-        const hipError_t e = hipEventQuery(s->ovf_ev[k]);
+        if (!s->ovf.pending[k]) continue;
+        const hipError_t e = hipEventQuery(s->ovf.ev[k]);
         if (e == hipErrorNotReady) continue;
-        s->ovf_pending[k] = false;
+        s->ovf.pending[k] = false;
         if (e != hipSuccess) return fail(std::string("hipEventQuery(ovf_ev): ") + hipGetErrorString(e));
-        s->ovf_last = s->ovf_host[k];
-        if ((size_t)s->ovf_host[k] * 64 > (size_t)s->n) { s->lean_off_until = s->launch_index + 64; s->lean_fallbacks++; }
+        s->ovf.last = s->ovf.host[k];
+        if ((size_t)s->ovf.host[k] * 64 > (size_t)s->n) { s->ovf.lean_off_until = s->launch_index + 64; s->ovf.fallbacks++; }
     }
     return 0;
 }
@@ -292,18 +309,18 @@ StepPlan plan_step(const kp_sim& s, int nsub, bool capturing) {
     // floor scenes: the job queue runs on the lean layout (EnvLdsLean) with a register budget for three waves per SIMD, except during a fallback (poll_overflow);
     // model option lean_queue = 0 keeps the full layout (two waves per SIMD; A / B measurements)
     bool lean = lean_eligible(s);
-    if (lean && nsub > 0 && s.ovf_host && !capturing && m.lean_adaptive && s.launch_index < s.lean_off_until) lean = false;
-    p.layout = s.has_objects ? OBJECTS : lean ? LEAN : FULL;
+    if (lean && nsub > 0 && s.ovf.host && !capturing && m.lean_adaptive && s.launch_index < s.ovf.lean_off_until) lean = false;
+    p.layout = s.obj.on ? OBJECTS : lean ? LEAN : FULL;
     p.threads = m.threads;
     // lpt_order: 1 on, 0 off, -1 (default) on when the scene's objects are simulated: an env whose hulls press on objects stays the launch's
     // longest for many control steps, so starting it first shortens the launch (objects workload 7.21 -> 6.62 ms); floor-only costs are not
     // predictable from step to step (correlation 0.25 .. 0.55) and gain nothing
-    p.lpt = nsub > 0 && (m.lpt_order > 0 || (m.lpt_order < 0 && s.has_objects));
+    p.lpt = nsub > 0 && (m.lpt_order > 0 || (m.lpt_order < 0 && s.obj.on));
     // lds_pad: allocate at least that many bytes per env (experiments: fewer envs per CU with the same binary)
-    const size_t lds = s.has_objects ? sizeof(kp::EnvLdsObj) : sizeof(kp::EnvLds);
+    const size_t lds = s.obj.on ? sizeof(kp::EnvLdsObj) : sizeof(kp::EnvLds);
     size_t lds_q = lean ? sizeof(kp::EnvLdsLean) : lds;
     if (m.lds_pad > 0) lds_q = std::max(lds_q, (size_t)m.lds_pad);
-    p.slots = m.queue_slots > 0 ? m.queue_slots : s.wave_slots / 8 * envs_per_cu(lds_q, lean ? 12 : 8);
+    p.slots = m.queue_slots > 0 ? m.queue_slots : s.q.wave_slots / 8 * envs_per_cu(lds_q, lean ? 12 : 8);
     // Schedule defaults.  Full layout (objects; floor with lean_queue = 0): 6 + 5 + 4 substeps, FIFO, no issue priorities (rounds 2 - 5).  Lean layout: 3072 slots hold
     // three quarters of BASELINE's 4096 envs, so a quarter of the envs start one job late and the launch ends on them (sum of env cycles / slots 1.83 ms, launch
     // 2.44 ms).  Three measures take the launch to 2.19 ms (profiles/r06/lean_schedule_knobs*.log): equal jobs 5 + 5 + 5 (the late envs start earlier), a late
@@ -322,14 +339,14 @@ StepPlan plan_step(const kp_sim& s, int nsub, bool capturing) {
     // more envs than resident wave slots: schedule the control step as jobs pulled from a FIFO by one resident wave per slot instead of one workgroup per env,
     // which ends on a long tail.  The queue pays from the env count on that one-workgroup-per-env launches (full layout) cannot hold resident at once; the lean
     // queue then runs with every env resident up to its own slot count and in rounds beyond it.  Env ids take 24 bits of a queue entry.
-    const int resident_full = s.wave_slots / 8 * envs_per_cu(lds, 8);
+    const int resident_full = s.q.wave_slots / 8 * envs_per_cu(lds, 8);
     p.queue = nsub > 0 && p.parts > 1 && m.threads == 64 && s.n > std::min(p.slots, resident_full) && s.n <= 0xFFFFFF && !s.prof;
     p.lds = p.queue ? lds_q : lds;
     p.queue_prio = m.queue_prio >= 0 ? m.queue_prio : (lean ? 3 : 0);
     p.queue_late = m.queue_late >= 0 ? m.queue_late : (lean ? 1 : 0);
     // overflow kernel: twice the overflow count last seen (the scenes that overflow keep doing so for a while), at least 128 workgroups -- an unexpected burst
     // is slow once and sized right from the next-but-one launch on; launching full residency every time costs 34 us per control step for nothing
-    p.ovf_grid = std::min(std::min(s.n, resident_full), std::max(128, 2 * (int)std::min<unsigned>(s.ovf_last, 1u << 20)));
+    p.ovf_grid = std::min(std::min(s.n, resident_full), std::max(128, 2 * (int)std::min<unsigned>(s.ovf.last, 1u << 20)));
     return p;
 }
 
@@ -341,81 +358,105 @@ void launch_per_env(const kp_sim* s, const kp::StepArgs& A, int nsub, size_t lds
     else hipLaunchKernelGGL((kp::kp_forward_kernel<NT, OBJ>), dim3(s->n), dim3(NT), lds, s->stream, A);
 }
 
-// base_qpos (optional): compute_torque's base pose for this launch instead of the stored target (kp_sim_step_ctrl_base)
+// the timed bracket of a launch: the handle's event pair, or the next pair of the ring while kp_sim_timing_reset's recording is on
+int timing_begin(kp_sim* s, hipEvent_t* e0, hipEvent_t* e1) {
+    Timing& t = s->tm;
+    *e0 = t.ev0; *e1 = t.ev1;
+    if (t.ring_on && t.ring_used < 4096) {
+        if ((int)t.ring.size() < 2 * (t.ring_used + 1)) {
+            hipEvent_t a, b;
+            HIP_OK(hipEventCreate(&a)); HIP_OK(hipEventCreate(&b));
+            t.ring.push_back(a); t.ring.push_back(b);
+        }
+        *e0 = t.ring[2 * t.ring_used]; *e1 = t.ring[2 * t.ring_used + 1];
+        t.ring_used++;
+    }
+    HIP_OK(hipEventRecord(*e0, s->stream));
+    return 0;
+}
+int timing_end(kp_sim* s, hipEvent_t e0, hipEvent_t e1) {
+    HIP_OK(hipEventRecord(e1, s->stream));
+    s->tm.last0 = e0; s->tm.last1 = e1; s->tm.timed = true;
+    return 0;
+}
+
+// the step kernels' argument pack for plan p; base_qpos (optional): compute_torque's base pose for this launch instead of the stored target
+kp::StepArgs step_args(const kp_sim* s, const StepPlan& p, int nsub, const float* action, const uint8_t* mask, const float* base_qpos) {
+    const kp_model& m = *s->model;
+    const StateRows& st = s->st; const ObjectRows& o = s->obj; const JobQueue& q = s->q;
+    kp::StepArgs A{};
+    A.T = s->T; A.P = s->P; A.n_envs = s->n; A.n_substeps = nsub;
+    A.qpos = st.qpos; A.qvel = st.qvel; A.qpos_d = st.qpos_d; A.qvel_d = st.qvel_d; A.warm = st.warm; A.warm2 = st.warm2; A.warm3 = st.warm3;
+    A.target_qpos = base_qpos ? base_qpos : s->tgt.qpos; A.action = action; A.env_mask = mask;
+    A.xpos = st.xpos; A.xquat = st.xquat; A.xipos = st.xipos; A.diag = st.diag; A.prof = s->prof; A.dbg_contacts = s->dbg_contacts;
+    A.geoms = o.geoms; A.ngeom = o.ngeom; A.obj_slot = o.slot; A.obj_qpos = o.qpos; A.obj_qvel = o.qvel; A.obj_warm = o.warm; A.obj_warm2 = o.warm2;
+    A.warm_extrap = m.warm_extrap < 0 ? (o.on ? 0.75f : 0.f) : (float)m.warm_extrap;      // the Newton solve's starting point (kp_step_kernel.hpp)
+    A.order = p.lpt ? q.order : nullptr; A.order_valid = p.lpt; A.cost = q.cost;
+    A.jobq = q.jobq; A.jobctr = q.jobctr; A.ovfq = q.ovfq; A.spd_next = q.spd_next; A.lean_cap = m.lean_cap;
+    A.n_parts = p.queue ? p.parts : 1; A.queue_fence = m.queue_fence; A.queue_heavy = m.queue_heavy; A.queue_prio = p.queue_prio; A.queue_late = p.queue_late;
+    for (int k = 0; p.queue && k < p.parts; k++) (k < 8 ? A.part_sub_lo : A.part_sub_hi) |= (unsigned long long)(p.sizes[k] & 255) << (8 * (k & 7));
+    return A;
+}
+
+// the control step as jobs pulled from a FIFO by resident waves (plan p.queue)
+int launch_queue(kp_sim* s, const StepPlan& p, kp::StepArgs& A, int nsub, bool capturing) {
+    JobQueue& q = s->q;
+    // the yardstick of queue_heavy is the previous launch's mean job time per substep: it only means something for the same kernel on the same
+    // schedule, so a change of the substep count or of the kernel instantiation starts it from nothing (that launch keeps no env)
+    if (nsub != q.nsub || (int)p.layout != q.layout) {
+        HIP_OK(hipMemsetAsync(q.jobctr + 32, 0, 2 * sizeof(unsigned), s->stream));
+        q.nsub = nsub; q.layout = (int)p.layout;
+    }
+    const unsigned total = (unsigned)s->n * (unsigned)p.parts;
+    hipLaunchKernelGGL(kp::k_queue_init, dim3((total + 255) / 256), dim3(256), 0, s->stream, s->n, total, q.jobq, q.jobctr, A.order);   // inside the timed bracket
+    A.order = nullptr;                                              // the queue kernel addresses envs by their queue entry
+    if (s->xc_on && p.layout == OBJECTS) hipLaunchKernelGGL((kp::kp_step_queue_kernel_xc<true>), dim3(p.slots), dim3(64), p.lds, s->stream, A, s->xc);
+    else if (s->xc_on) hipLaunchKernelGGL((kp::kp_step_queue_kernel_xc<false>), dim3(p.slots), dim3(64), p.lds, s->stream, A, s->xc);
+    else if (p.layout == OBJECTS) hipLaunchKernelGGL((kp::kp_step_queue_kernel<true>), dim3(p.slots), dim3(64), p.lds, s->stream, A);
+    else if (p.layout == FULL) hipLaunchKernelGGL((kp::kp_step_queue_kernel<false>), dim3(p.slots), dim3(64), p.lds, s->stream, A);
+    else {
+        hipLaunchKernelGGL((kp::kp_step_queue_kernel<false, true>), dim3(p.slots), dim3(64), p.lds, s->stream, A);
+        // the jobs whose contacts did not fit the lean layout (normally none: every wave leaves at its first read)
+        hipLaunchKernelGGL(kp::kp_step_overflow_kernel, dim3(p.ovf_grid), dim3(64), sizeof(kp::EnvLds), s->stream, A);
+        const int k = (int)(s->launch_index & 1);
+        if (s->ovf.host && !capturing && !s->ovf.pending[k]) {
+            HIP_OK(hipMemcpyAsync(s->ovf.host + k, q.jobctr + 64, sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
+            HIP_OK(hipEventRecord(s->ovf.ev[k], s->stream));
+            s->ovf.pending[k] = true;
+        }
+    }
+    return 0;
+}
+
+// one control step (nsub > 0) or the forward pass alone (nsub = 0) of the masked envs: timing bracket, plan, argument pack, launch
 int launch_step(kp_sim* s, const float* action, int nsub, const uint8_t* mask, bool time_it, const float* base_qpos = nullptr) {
-    const bool obj = s->has_objects;
-    if (obj && s->model->threads != 64) return fail("object contact needs threads_per_env = 64");
-    if (s->model->threads != 64 && s->model->threads != 128 && s->model->threads != 256) return fail("threads_per_env must be 64, 128 or 256");
+    const int threads = s->model->threads;
+    if (s->obj.on && threads != 64) return fail("object contact needs threads_per_env = 64");
+    if (threads != 64 && threads != 128 && threads != 256) return fail("threads_per_env must be 64, 128 or 256");
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     const bool capturing = hipStreamIsCapturing(s->stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
     time_it = time_it && !capturing;      // a launch that is being captured into a hipGraph carries no timing events (they could not be read back)
-    hipEvent_t e0 = s->ev0, e1 = s->ev1;
-    if (time_it && s->ring_on && s->ring_used < 4096) {
-        if ((int)s->ring.size() < 2 * (s->ring_used + 1)) {
-            hipEvent_t a, b;
-            HIP_OK(hipEventCreate(&a)); HIP_OK(hipEventCreate(&b));
-            s->ring.push_back(a); s->ring.push_back(b);
-        }
-        e0 = s->ring[2 * s->ring_used]; e1 = s->ring[2 * s->ring_used + 1];
-        s->ring_used++;
-    }
-    if (time_it) HIP_OK(hipEventRecord(e0, s->stream));
-    if (nsub > 0 && s->ovf_host && !capturing && lean_eligible(*s) && poll_overflow(s)) return -1;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (time_it && timing_begin(s, &e0, &e1)) return -1;
+    if (nsub > 0 && s->ovf.host && !capturing && lean_eligible(*s) && poll_overflow(s)) return -1;
     const StepPlan p = plan_step(*s, nsub, capturing);
     if (nsub > 0) { s->launch_index++; s->last_nsub = nsub; }
-    kp::StepArgs A{};
-    A.T = s->T; A.P = s->P; A.n_envs = s->n; A.n_substeps = nsub;
-    A.qpos = s->qpos; A.qvel = s->qvel; A.qpos_d = s->qpos_d; A.qvel_d = s->qvel_d; A.warm = s->warm; A.warm2 = s->warm2;
-    A.target_qpos = base_qpos ? base_qpos : s->t_qpos; A.action = action; A.env_mask = mask;
-    A.xpos = s->xpos; A.xquat = s->xquat; A.xipos = s->xipos; A.diag = s->diag; A.prof = s->prof;
-    A.geoms = s->geoms; A.ngeom = s->ngeom; A.dbg_contacts = s->dbg_contacts;
-    A.obj_slot = s->obj_slot; A.obj_qpos = s->obj_qpos; A.obj_qvel = s->obj_qvel; A.obj_warm = s->obj_warm; A.obj_warm2 = s->obj_warm2;
-    A.order = nullptr; A.cost = s->cost;
-    A.warm_extrap = s->model->warm_extrap < 0.f ? (obj ? 0.75f : 0.f) : s->model->warm_extrap;      // the Newton solve's starting point (kp_step_kernel.hpp)
-    if (p.lpt) {      // longest env first (inside the timed bracket): order the workgroups / the queue's first jobs by the cycles of the previous control step
-        hipLaunchKernelGGL(kp::k_lpt_order, dim3(1), dim3(1024), 0, s->stream, s->n, s->cost, s->order);
-        A.order = s->order;
-    }
-    A.jobq = s->jobq; A.jobctr = s->jobctr; A.ovfq = s->ovfq; A.lean_cap = s->model->lean_cap; A.warm3 = s->warm3; A.spd_next = s->spd_next; A.n_parts = p.queue ? p.parts : 1; A.queue_fence = s->model->queue_fence; A.queue_heavy = s->model->queue_heavy; A.queue_prio = p.queue_prio; A.queue_late = p.queue_late; A.order_valid = A.order != nullptr;
-    A.part_sub_lo = A.part_sub_hi = 0;
-    for (int k = 0; p.queue && k < p.parts; k++) (k < 8 ? A.part_sub_lo : A.part_sub_hi) |= (unsigned long long)(p.sizes[k] & 255) << (8 * (k & 7));
-    if (p.queue) {
-        // the yardstick of queue_heavy is the previous launch's mean job time per substep: it only means something for the same kernel on the same
-        // schedule, so a change of the substep count or of the kernel instantiation starts it from nothing (that launch keeps no env)
-        if (nsub != s->q_nsub || (int)p.layout != s->q_layout) {
-            HIP_OK(hipMemsetAsync(s->jobctr + 32, 0, 2 * sizeof(unsigned), s->stream));
-            s->q_nsub = nsub; s->q_layout = (int)p.layout;
-        }
-        const unsigned total = (unsigned)s->n * (unsigned)p.parts;
-        hipLaunchKernelGGL(kp::k_queue_init, dim3((total + 255) / 256), dim3(256), 0, s->stream, s->n, total, s->jobq, s->jobctr, A.order);   // inside the timed bracket
-        A.order = nullptr;                                              // the queue kernel addresses envs by their queue entry
-        if (s->xc_on && p.layout == OBJECTS) hipLaunchKernelGGL((kp::kp_step_queue_kernel_xc<true>), dim3(p.slots), dim3(64), p.lds, s->stream, A, s->xc);
-        else if (s->xc_on) hipLaunchKernelGGL((kp::kp_step_queue_kernel_xc<false>), dim3(p.slots), dim3(64), p.lds, s->stream, A, s->xc);
-        else if (p.layout == OBJECTS) hipLaunchKernelGGL((kp::kp_step_queue_kernel<true>), dim3(p.slots), dim3(64), p.lds, s->stream, A);
-        else if (p.layout == FULL) hipLaunchKernelGGL((kp::kp_step_queue_kernel<false>), dim3(p.slots), dim3(64), p.lds, s->stream, A);
-        else {
-            hipLaunchKernelGGL((kp::kp_step_queue_kernel<false, true>), dim3(p.slots), dim3(64), p.lds, s->stream, A);
-            // the jobs whose contacts did not fit the lean layout (normally none: every wave leaves at its first read)
-            hipLaunchKernelGGL(kp::kp_step_overflow_kernel, dim3(p.ovf_grid), dim3(64), sizeof(kp::EnvLds), s->stream, A);
-            if (s->ovf_host && !capturing) {
-                const int k = (int)(s->launch_index & 1);
-                if (!s->ovf_pending[k]) {
-                    HIP_OK(hipMemcpyAsync(s->ovf_host + k, s->jobctr + 64, sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
-                    HIP_OK(hipEventRecord(s->ovf_ev[k], s->stream));
-                    s->ovf_pending[k] = true;
-                }
-            }
-        }
-    } else if (obj) launch_per_env<64, true>(s, A, nsub, p.lds);
+    kp::StepArgs A = step_args(s, p, nsub, action, mask, base_qpos);
+    // longest env first (inside the timed bracket): order the workgroups / the queue's first jobs by the cycles of the previous control step
+    if (p.lpt) hipLaunchKernelGGL(kp::k_lpt_order, dim3(1), dim3(1024), 0, s->stream, s->n, s->q.cost, s->q.order);
+    if (p.queue) { if (launch_queue(s, p, A, nsub, capturing)) return -1; }
+    else if (s->obj.on) launch_per_env<64, true>(s, A, nsub, p.lds);
     else if (p.threads == 64) launch_per_env<64, false>(s, A, nsub, p.lds);
     else if (p.threads == 128) launch_per_env<128, false>(s, A, nsub, p.lds);
     else launch_per_env<256, false>(s, A, nsub, p.lds);
     HIP_OK(hipGetLastError());
-    if (time_it) {
-        HIP_OK(hipEventRecord(e1, s->stream));
-        s->last0 = e0; s->last1 = e1; s->timed = true;
-    }
-    return 0;
+    return time_it ? timing_end(s, e0, e1) : 0;
+}
+
+// the target dict's forward kinematics of n rows of tq into B; K (optional): the head of the env step in the same launch (kp_sim_step_head)
+void launch_target_fk(const kp_sim* s, int n, const float* tq, const uint8_t* mask, const kp::TargetBufs& B,
+                      const kp::KinStep& K = kp::KinStep{nullptr, nullptr, nullptr, nullptr, nullptr, 0.f}) {
+    hipLaunchKernelGGL(kp::k_target_fk, dim3((n + 3) / 4), dim3(256), 0, s->stream, n, tq, mask, B, s->T.body_pos, s->T.body_ipos, s->T.body_parent, s->T.body_depth, K);
 }
 
 }  // namespace
@@ -446,97 +487,94 @@ static int cc_obs_width(int v, int vel_root, int heading, int phase) {
     return v == 0 ? heading + 74 + lv + 69 + phase : 229 + lv + (v == 1 ? 4 : 2) * 72 + 2 * 96;
 }
 
+// ---- model options: ONE table behind kp_model_set_option and kp_model_get_option (include/kinpoly_sim.h describes what each option does).
+// A settable option lives in an int or a double member of kp_model; how a value is accepted:
+// O_BOOL: v != 0;  O_TRI: -1 (v < 0: automatic) / 0 / 1;  O_INT: (int)v and O_REAL: v, unchecked;  O_REAL32: v rounded to float;  O_ENUM: one of the integers
+// 0 .. hi or refused;  O_RANGE: lo <= v <= hi or refused (an int member stores (int)v);  O_CLAMP: (int)v clamped to lo .. hi;  O_THREADS: 64, 128 or 256;
+// O_READ_ONLY: derived, `get` computes it and set does not know the name.
+enum OptRule { O_BOOL, O_TRI, O_INT, O_REAL, O_REAL32, O_ENUM, O_RANGE, O_CLAMP, O_THREADS, O_READ_ONLY };
+struct Opt {
+    const char* name;
+    OptRule rule;
+    int kp_model::*i; double kp_model::*d;
+    double lo, hi;
+    const char* must;                    // the refusal reads "<name> must be <must>"; null: "0 or 1" (O_ENUM), "<lo> .. <hi>" (O_RANGE)
+    bool clears_job_auto;                // the caller's own job sizes switch the layout's default schedule off (plan_step)
+    double (*get)(const kp_model&);      // O_READ_ONLY
+};
+constexpr double INF = HUGE_VAL;
+#define OPT_I(name, rule, member, ...) Opt{name, rule, &kp_model::member, nullptr, __VA_ARGS__}
+#define OPT_D(name, rule, member, ...) Opt{name, rule, nullptr, &kp_model::member, __VA_ARGS__}
+#define OPT_RO(name, expr) Opt{name, O_READ_ONLY, nullptr, nullptr, 0, 0, nullptr, false, [](const kp_model& m) -> double { return expr; }}
+static const Opt OPTIONS[] = {
+    OPT_I("contact", O_BOOL, contact), OPT_I("limits", O_BOOL, limits), OPT_I("actuation", O_BOOL, actuation), OPT_I("stale_kinematics", O_BOOL, stale),
+    OPT_D("gravity_z", O_REAL, gravity_z), OPT_D("gravity_x", O_REAL, gravity_x), OPT_D("gravity_y", O_REAL, gravity_y),
+    OPT_I("solver_iter", O_INT, solver_iter), OPT_D("solver_tol", O_REAL, solver_tol), OPT_I("dynamic_objects", O_BOOL, dynamic_objects),
+    OPT_I("planemesh_max", O_RANGE, planemesh_max, 1, 8), OPT_D("planemesh_tol", O_RANGE, planemesh_tol, 0, INF, ">= 0"),
+    OPT_I("threads_per_env", O_THREADS, threads, 0, 0, "64, 128 or 256"),
+    OPT_D("warm_extrap", O_REAL32, warm_extrap),
+    // the kinematic policy's and the UHC's observation and controller (fixed in a kp_sim when it is created)
+    OPT_I("ar_obs_action", O_ENUM, ar_obs_action, 0, 1, "1 (105-d observation with the action one-hot) or 0 (101-d, use_action: false)"),
+    OPT_RO("ar_obs_dim", m.ar_obs_action ? KP_AR_OBS_DIM : KP_AR_OBS_DIM_NO_ACTION),
+    OPT_I("cc_obs_v", O_ENUM, cc_obs_v, 0, 2, "0 (get_full_obs), 1 (get_full_obs_v1) or 2 (get_full_obs_v2)"),
+    OPT_I("cc_obs_vel_root", O_ENUM, cc_obs_vel_root, 0, 1), OPT_I("cc_obs_heading", O_ENUM, cc_obs_heading, 0, 1),
+    OPT_I("cc_obs_deheading", O_ENUM, cc_obs_deheading, 0, 1), OPT_I("cc_obs_phase", O_ENUM, cc_obs_phase, 0, 1),
+    OPT_RO("cc_obs_dim", m.cc_obs_v == 0 ? cc_obs_width(0, m.cc_obs_vel_root, m.cc_obs_heading, m.cc_obs_phase) : cc_obs_width(m.cc_obs_v, m.cc_obs_vel_root, 0, 0)),
+    OPT_I("cc_action_v", O_ENUM, cc_action_v, 0, 1), OPT_I("cc_rfc", O_ENUM, cc_rfc, 0, 1),
+    OPT_I("cc_meta_pd", O_ENUM, cc_meta_pd, 0, 2, "0 (none), 1 (meta_pd: by substep) or 2 (meta_pd_joint: by joint)"),
+    OPT_RO("cc_action_dim", cc_action_width(m.cc_rfc, m.cc_meta_pd)),
+    OPT_RO("n_obj_geoms", (double)(m.h.obj_geoms.size() / 18)),     // columns of kp_sim_pose_contacts' hits
+    OPT_RO("timestep", m.h.opt[kp::OPT_TIMESTEP]),
+    // scheduling of the control-step launch (results do not depend on it)
+    OPT_I("lpt_order", O_TRI, lpt_order),
+    OPT_I("substeps_per_job", O_RANGE, substeps_per_job, 0, 255, "0 (whole control step per workgroup) .. 255", true),
+    OPT_I("job_taper", O_CLAMP, job_taper, 0, 8, nullptr, true),
+    OPT_RO("job_auto", m.job_auto),       // 1: the job sizes are the layout's defaults (lean queue: 5 + 5 + 5; otherwise substeps_per_job / job_taper = 6 + 5 + 4)
+    OPT_I("queue_slots", O_RANGE, queue_slots, 0, INF, ">= 0 (0 = resident wave slots of the device)"),
+    OPT_I("queue_fence", O_BOOL, queue_fence), OPT_I("queue_heavy", O_CLAMP, queue_heavy, 0, INT_MAX),
+    OPT_I("queue_late", O_TRI, queue_late), OPT_I("queue_prio", O_CLAMP, queue_prio, -1, 3),
+    OPT_I("lean_queue", O_BOOL, lean_queue), OPT_I("lean_adaptive", O_BOOL, lean_adaptive),
+    OPT_I("lean_max_contacts", O_RANGE, lean_cap, 0, kp::EnvLdsLean::MAXCON),
+    OPT_I("lds_pad", O_RANGE, lds_pad, 0, 65536, "0 .. 65536 bytes"),
+    OPT_RO("lds_bytes_per_env", (double)sizeof(kp::EnvLds)), OPT_RO("lds_bytes_per_env_objects", (double)sizeof(kp::EnvLdsObj)),
+    OPT_RO("lds_bytes_per_env_lean", (double)sizeof(kp::EnvLdsLean)),
+};
+#undef OPT_I
+#undef OPT_D
+#undef OPT_RO
+static const Opt* find_option(const char* name) {
+    for (const Opt& o : OPTIONS) if (name && !std::strcmp(name, o.name)) return &o;
+    return nullptr;
+}
+
 int kp_model_set_option(kp_model* m, const char* name, double v) {
     if (!m || !name) return fail("kp_model_set_option: null argument");
-    std::string k(name);
-    if (k == "contact") m->contact = v != 0;
-    else if (k == "limits") m->limits = v != 0;
-    else if (k == "gravity_z") m->gravity_z = v;
-    else if (k == "gravity_x") m->gravity_x = v;
-    else if (k == "gravity_y") m->gravity_y = v;
-    else if (k == "actuation") m->actuation = v != 0;
-    else if (k == "ar_obs_action") { if (v != 0 && v != 1) return fail("ar_obs_action must be 1 (105-d observation with the action one-hot) or 0 (101-d, use_action: false)"); m->ar_obs_action = (int)v; }
-    else if (k == "cc_action_v" || k == "cc_rfc") {
-        if (v != 0 && v != 1) return fail(k + " must be 0 or 1");
-        (k == "cc_action_v" ? m->cc_action_v : m->cc_rfc) = (int)v;
+    const Opt* o = find_option(name);
+    if (!o || o->rule == O_READ_ONLY) return fail(std::string("kp_model_set_option: unknown option ") + name);
+    bool ok = true;
+    double x = v;
+    switch (o->rule) {
+        case O_BOOL: x = v != 0; break;
+        case O_TRI: x = v < 0 ? -1 : (v != 0); break;
+        case O_REAL32: x = (float)v; break;
+        case O_ENUM: ok = false; for (int k = 0; k <= (int)o->hi; k++) ok = ok || v == k; break;
+        case O_RANGE: ok = !(v < o->lo || v > o->hi); break;
+        case O_CLAMP: x = std::max((int)o->lo, std::min((int)o->hi, (int)v)); break;
+        case O_THREADS: ok = v == 64 || v == 128 || v == 256; break;
+        default: break;
     }
-    else if (k == "cc_meta_pd") { if (v != 0 && v != 1 && v != 2) return fail("cc_meta_pd must be 0 (none), 1 (meta_pd: by substep) or 2 (meta_pd_joint: by joint)"); m->cc_meta_pd = (int)v; }
-    else if (k == "cc_obs_v") { if (v != 0 && v != 1 && v != 2) return fail("cc_obs_v must be 0 (get_full_obs), 1 (get_full_obs_v1) or 2 (get_full_obs_v2)"); m->cc_obs_v = (int)v; }
-    else if (k == "cc_obs_vel_root" || k == "cc_obs_heading" || k == "cc_obs_deheading" || k == "cc_obs_phase") {
-        if (v != 0 && v != 1) return fail(k + " must be 0 or 1");
-        (k == "cc_obs_vel_root" ? m->cc_obs_vel_root : k == "cc_obs_heading" ? m->cc_obs_heading : k == "cc_obs_deheading" ? m->cc_obs_deheading : m->cc_obs_phase) = (int)v;
+    if (!ok) {
+        const std::string must = o->must ? o->must : o->rule == O_ENUM ? "0 or 1" : std::to_string((int)o->lo) + " .. " + std::to_string((int)o->hi);
+        return fail(std::string(name) + " must be " + must);
     }
-    else if (k == "stale_kinematics") m->stale = v != 0;
-    else if (k == "solver_iter") m->solver_iter = (int)v;
-    else if (k == "solver_tol") m->solver_tol = v;
-    else if (k == "dynamic_objects") m->dynamic_objects = v != 0;
-    else if (k == "planemesh_max") { if (v < 1 || v > 8) return fail("planemesh_max must be 1 .. 8"); m->planemesh_max = (int)v; }
-    else if (k == "planemesh_tol") { if (v < 0) return fail("planemesh_tol must be >= 0"); m->planemesh_tol = v; }
-    else if (k == "lpt_order") m->lpt_order = v < 0 ? -1 : (v != 0);
-    else if (k == "job_taper") { m->job_taper = std::max(0, std::min(8, (int)v)); m->job_auto = 0; }
-    else if (k == "queue_fence") m->queue_fence = v != 0;
-    else if (k == "queue_heavy") m->queue_heavy = std::max(0, (int)v);
-    else if (k == "queue_late") m->queue_late = v < 0 ? -1 : (v != 0);
-    else if (k == "queue_prio") m->queue_prio = std::max(-1, std::min(3, (int)v));
-    else if (k == "warm_extrap") m->warm_extrap = (float)v;
-    else if (k == "lean_queue") m->lean_queue = v != 0;
-    else if (k == "lean_adaptive") m->lean_adaptive = v != 0;
-    else if (k == "lean_max_contacts") { if (v < 0 || v > kp::EnvLdsLean::MAXCON) return fail("lean_max_contacts must be 0 .. " + std::to_string(kp::EnvLdsLean::MAXCON)); m->lean_cap = (int)v; }
-    else if (k == "lds_pad") { if (v < 0 || v > 65536) return fail("lds_pad must be 0 .. 65536 bytes"); m->lds_pad = (int)v; }
-    else if (k == "queue_slots") { if (v < 0) return fail("queue_slots must be >= 0 (0 = resident wave slots of the device)"); m->queue_slots = (int)v; }
-    else if (k == "substeps_per_job") { if (v < 0 || v > 255) return fail("substeps_per_job must be 0 (whole control step per workgroup) .. 255"); m->substeps_per_job = (int)v; m->job_auto = 0; }
-    else if (k == "threads_per_env") { if (v != 64 && v != 128 && v != 256) return fail("threads_per_env must be 64, 128 or 256"); m->threads = (int)v; }
-    else return fail("kp_model_set_option: unknown option " + k);
+    if (o->i) m->*(o->i) = (int)x; else m->*(o->d) = x;
+    if (o->clears_job_auto) m->job_auto = 0;
     return 0;
 }
 double kp_model_get_option(const kp_model* m, const char* name) {
-    std::string k(name ? name : "");
-    if (!m) return NAN;
-    if (k == "contact") return m->contact;
-    if (k == "limits") return m->limits;
-    if (k == "gravity_z") return m->gravity_z;
-    if (k == "gravity_x") return m->gravity_x;
-    if (k == "gravity_y") return m->gravity_y;
-    if (k == "actuation") return m->actuation;
-    if (k == "ar_obs_action") return m->ar_obs_action;
-    if (k == "ar_obs_dim") return m->ar_obs_action ? KP_AR_OBS_DIM : KP_AR_OBS_DIM_NO_ACTION;
-    if (k == "cc_obs_v") return m->cc_obs_v;
-    if (k == "cc_obs_vel_root") return m->cc_obs_vel_root;
-    if (k == "cc_obs_heading") return m->cc_obs_heading;
-    if (k == "cc_obs_deheading") return m->cc_obs_deheading;
-    if (k == "cc_obs_phase") return m->cc_obs_phase;
-    if (k == "cc_obs_dim") return m->cc_obs_v == 0 ? cc_obs_width(0, m->cc_obs_vel_root, m->cc_obs_heading, m->cc_obs_phase) : cc_obs_width(m->cc_obs_v, m->cc_obs_vel_root, 0, 0);
-    if (k == "cc_action_dim") return cc_action_width(m->cc_rfc, m->cc_meta_pd);
-    if (k == "cc_action_v") return m->cc_action_v;
-    if (k == "cc_rfc") return m->cc_rfc;
-    if (k == "cc_meta_pd") return m->cc_meta_pd;
-    if (k == "stale_kinematics") return m->stale;
-    if (k == "solver_iter") return m->solver_iter;
-    if (k == "solver_tol") return m->solver_tol;
-    if (k == "dynamic_objects") return m->dynamic_objects;
-    if (k == "planemesh_max") return m->planemesh_max;
-    if (k == "planemesh_tol") return m->planemesh_tol;
-    if (k == "n_obj_geoms") return (double)(m->h.obj_geoms.size() / 18);     // columns of kp_sim_pose_contacts' hits
-    if (k == "lpt_order") return m->lpt_order;
-    if (k == "substeps_per_job") return m->substeps_per_job;
-    if (k == "queue_slots") return m->queue_slots;
-    if (k == "lean_queue") return m->lean_queue;
-    if (k == "lean_adaptive") return m->lean_adaptive;
-    if (k == "lean_max_contacts") return m->lean_cap;
-    if (k == "lds_pad") return m->lds_pad;
-    if (k == "lds_bytes_per_env_lean") return (double)sizeof(kp::EnvLdsLean);
-    if (k == "job_taper") return m->job_taper;
-    if (k == "job_auto") return m->job_auto;       // 1: the job sizes are the layout's defaults (lean queue: 5 + 5 + 5; otherwise substeps_per_job / job_taper = 6 + 5 + 4)
-    if (k == "queue_fence") return m->queue_fence;
-    if (k == "queue_heavy") return m->queue_heavy;
-    if (k == "queue_prio") return m->queue_prio;
-    if (k == "queue_late") return m->queue_late;
-    if (k == "warm_extrap") return m->warm_extrap;
-    if (k == "threads_per_env") return m->threads;
-    if (k == "timestep") return m->h.opt[kp::OPT_TIMESTEP];
-    if (k == "lds_bytes_per_env") return (double)sizeof(kp::EnvLds);
-    if (k == "lds_bytes_per_env_objects") return (double)sizeof(kp::EnvLdsObj);
-    return NAN;
+    const Opt* o = find_option(name);
+    if (!m || !o) return NAN;
+    return o->get ? o->get(*m) : o->i ? (double)(m->*(o->i)) : m->*(o->d);
 }
 
 kp_sim* kp_sim_create(const kp_model* m, int n_envs, int device_id, void* stream) {
@@ -553,31 +591,34 @@ kp_sim* kp_sim_create(const kp_model* m, int n_envs, int device_id, void* stream
     s->xc = kp::XcArgs{cc_action_width(m->cc_rfc, m->cc_meta_pd), m->cc_action_v == 0, m->cc_rfc, m->cc_meta_pd};
     s->xc_on = m->cc_action_v != 1 || m->cc_rfc != 1 || m->cc_meta_pd != 0;
     bool ok = build_tables(s);
-    size_t N = n_envs;
-    s->qpos = dalloc(s, N * 76, &ok); s->qvel = dalloc(s, N * 75, &ok); s->qpos_d = dalloc(s, N * 76, &ok);
-    s->qvel_d = dalloc(s, N * 75, &ok); s->warm = dalloc(s, N * 75, &ok); s->warm2 = dalloc(s, N * 75, &ok);
-    s->xpos = dalloc(s, N * 72, &ok); s->xquat = dalloc(s, N * 96, &ok); s->xipos = dalloc(s, N * 72, &ok);
-    s->t_qpos = dalloc(s, N * 76, &ok); s->t_wbpos = dalloc(s, N * 72, &ok); s->t_wbquat = dalloc(s, N * 96, &ok);
-    s->t_bquat = dalloc(s, N * 96, &ok); s->t_com = dalloc(s, N * 72, &ok);
-    s->scratch = dalloc(s, N * 96, &ok);
-    s->prev_bquat = dalloc(s, N * 96, &ok); s->prev_hpos = dalloc(s, N * 7, &ok);
-    s->diag = (int*)dalloc(s, N * 4, &ok);
-    s->order = (int*)dalloc(s, N, &ok); s->cost = (unsigned*)dalloc(s, N, &ok);
-    s->jobq_cap = (int)N * 16; s->jobq = (unsigned*)dalloc(s, (size_t)s->jobq_cap, &ok); s->jobctr = (unsigned*)dalloc(s, 128, &ok); s->ovfq = (unsigned*)dalloc(s, N, &ok); s->warm3 = dalloc(s, N * 75, &ok); s->spd_next = (float*)dalloc(s, N * 80, &ok);
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, s->device) == hipSuccess && prop.multiProcessorCount > 0) s->wave_slots = prop.multiProcessorCount * 8;
-    }
-    s->obj_qpos = dalloc(s, N * 35, &ok); s->geoms = dalloc(s, N * kp::D_MAXGEOM * 17, &ok); s->ngeom = (int*)dalloc(s, N, &ok);
-    s->obj_qvel = dalloc(s, N * 30, &ok); s->obj_warm = dalloc(s, N * 6 * kp::D_MAXOBJ, &ok); s->obj_warm2 = dalloc(s, N * 6 * kp::D_MAXOBJ, &ok); s->obj_slot = (signed char*)dalloc(s, (N * kp::D_MAXOBJ + 3) / 4 + 1, &ok);
+    const size_t N = n_envs;
+    StateRows& st = s->st;
+    st.qpos = dalloc(s, N * 76, &ok); st.qvel = dalloc(s, N * 75, &ok); st.qpos_d = dalloc(s, N * 76, &ok); st.qvel_d = dalloc(s, N * 75, &ok);
+    st.warm = dalloc(s, N * 75, &ok); st.warm2 = dalloc(s, N * 75, &ok); st.warm3 = dalloc(s, N * 75, &ok);
+    st.xpos = dalloc(s, N * 72, &ok); st.xquat = dalloc(s, N * 96, &ok); st.xipos = dalloc(s, N * 72, &ok);
+    st.prev_bquat = dalloc(s, N * 96, &ok); st.prev_hpos = dalloc(s, N * 7, &ok); st.diag = (int*)dalloc(s, N * 4, &ok);
+    s->tgt = kp::TargetBufs{dalloc(s, N * 76, &ok), dalloc(s, N * 72, &ok), dalloc(s, N * 96, &ok), dalloc(s, N * 96, &ok), dalloc(s, N * 72, &ok)};
+    JobQueue& q = s->q;
+    q.order = (int*)dalloc(s, N, &ok); q.cost = (unsigned*)dalloc(s, N, &ok);
+    q.jobq = (unsigned*)dalloc(s, N * 16, &ok); q.jobctr = (unsigned*)dalloc(s, 128, &ok); q.ovfq = (unsigned*)dalloc(s, N, &ok);
+    q.spd_next = dalloc(s, N * 80, &ok);
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, s->device) == hipSuccess && prop.multiProcessorCount > 0) q.wave_slots = prop.multiProcessorCount * 8;
+    ObjectRows& o = s->obj;
+    o.qpos = dalloc(s, N * 35, &ok); o.qvel = dalloc(s, N * 30, &ok); o.geoms = dalloc(s, N * kp::D_MAXGEOM * 17, &ok); o.ngeom = (int*)dalloc(s, N, &ok);
+    o.warm = dalloc(s, N * 6 * kp::D_MAXOBJ, &ok); o.warm2 = dalloc(s, N * 6 * kp::D_MAXOBJ, &ok); o.slot = (signed char*)dalloc(s, (N * kp::D_MAXOBJ + 3) / 4 + 1, &ok);
     if (!m->h.obj_geoms.empty()) {
-        s->d_obj_geoms = upload<float>(s, m->h.obj_geoms, &ok); s->d_obj_mass = upload<float>(s, m->h.obj_mass, &ok);
-        s->n_obj_geoms = (int)(m->h.obj_geoms.size() / 18); s->n_obj = (int)m->h.obj_mass.size();
+        o.d_geoms = upload<float>(s, m->h.obj_geoms, &ok); o.d_mass = upload<float>(s, m->h.obj_mass, &ok);
+        o.n_geoms = (int)(m->h.obj_geoms.size() / 18); o.n_obj = (int)m->h.obj_mass.size();
     }
     if (const char* e = std::getenv("KP_PROFILE")) if (e[0] == '1') s->prof = (unsigned long long*)dalloc(s, N * 16, &ok);
-    if (hipHostMalloc((void**)&s->ovf_host, 2 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) s->ovf_host = nullptr;
-    else { s->ovf_host[0] = s->ovf_host[1] = 0u; if (hipEventCreateWithFlags(&s->ovf_ev[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&s->ovf_ev[1], hipEventDisableTiming) != hipSuccess) { hipHostFree(s->ovf_host); s->ovf_host = nullptr; } }
-    if (!ok || hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess) {
+    OverflowReadback& v = s->ovf;      // optional: without the pinned word or its events the lean layout runs without the adaptive fallback
+    if (hipHostMalloc((void**)&v.host, 2 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) v.host = nullptr;
+    else {
+        v.host[0] = v.host[1] = 0u;
+        if (hipEventCreateWithFlags(&v.ev[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&v.ev[1], hipEventDisableTiming) != hipSuccess) { hipHostFree(v.host); v.host = nullptr; }
+    }
+    if (!ok || hipEventCreate(&s->tm.ev0) != hipSuccess || hipEventCreate(&s->tm.ev1) != hipSuccess) {
         fail("kp_sim_create: device allocation / table build failed");
         kp_sim_destroy(s);
         return nullptr;
@@ -590,10 +631,10 @@ void kp_sim_destroy(kp_sim* s) {
     hipSetDevice(s->device);
     hipStreamSynchronize(s->stream);
     for (void* p : s->allocs) hipFree(p);
-    for (hipEvent_t e : s->ring) hipEventDestroy(e);
-    if (s->ovf_host) { hipHostFree(s->ovf_host); for (hipEvent_t e : s->ovf_ev) if (e) hipEventDestroy(e); }
-    if (s->ev0) hipEventDestroy(s->ev0);
-    if (s->ev1) hipEventDestroy(s->ev1);
+    for (hipEvent_t e : s->tm.ring) hipEventDestroy(e);
+    if (s->ovf.host) { hipHostFree(s->ovf.host); for (hipEvent_t e : s->ovf.ev) if (e) hipEventDestroy(e); }
+    if (s->tm.ev0) hipEventDestroy(s->tm.ev0);
+    if (s->tm.ev1) hipEventDestroy(s->tm.ev1);
     delete s;
 }
 int kp_sim_n_envs(const kp_sim* s) { return s ? s->n : -1; }
@@ -604,7 +645,7 @@ int kp_sim_set_stream(kp_sim* s, void* stream) {
     return 0;
 }
 
-const uint32_t* kp_sim_status_device(kp_sim* s) { return s ? s->jobctr : nullptr; }
+const uint32_t* kp_sim_status_device(kp_sim* s) { return s ? s->q.jobctr : nullptr; }
 
 int kp_sim_contacts(kp_sim* s, float* out_host) {
     if (!s) return fail("kp_sim_contacts: null argument");
@@ -628,10 +669,9 @@ int kp_sim_mass_matrix(kp_sim* s, float* M, float* bias) {
     HIP_OK(hipSetDevice(s->device));
     kp::StepArgs A{};
     A.T = s->T; A.P = s->P; A.n_envs = s->n; A.n_substeps = 0;
-    A.qpos_d = s->qpos_d; A.qvel_d = s->qvel_d;
+    A.qpos_d = s->st.qpos_d; A.qvel_d = s->st.qvel_d;
     hipLaunchKernelGGL(kp::kp_mass_kernel, dim3(s->n), dim3(64), sizeof(kp::EnvLds), s->stream, A, M, bias);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return launched();
 }
 
 // masked row copy kernel (set_state writes only the masked envs)
@@ -645,14 +685,17 @@ __global__ void k_copy_rows(int n, int dim, const float* __restrict__ src, float
     dst[t] = v;
     if (dst2) dst2[t] = v;
 }
+// dst (and dst2) <- src, or zero without src, in the masked envs' rows of width dim
+static void copy_rows(const kp_sim* s, int dim, const float* src, float* dst, float* dst2, const uint8_t* mask) {
+    hipLaunchKernelGGL(k_copy_rows, dim3((s->n * dim + 255) / 256), dim3(256), 0, s->stream, s->n, dim, src, dst, dst2, mask);
+}
 
 int kp_sim_set_state(kp_sim* s, const float* qpos, const float* qvel, const uint8_t* mask) {
     if (!s || !qpos || !qvel) return fail("kp_sim_set_state: null argument");
     HIP_OK(hipSetDevice(s->device));
-    int n = s->n;
-    hipLaunchKernelGGL(k_copy_rows, dim3((n * 76 + 255) / 256), dim3(256), 0, s->stream, n, 76, qpos, s->qpos, s->qpos_d, mask);
-    hipLaunchKernelGGL(k_copy_rows, dim3((n * 75 + 255) / 256), dim3(256), 0, s->stream, n, 75, qvel, s->qvel, s->qvel_d, mask);
-    hipLaunchKernelGGL(k_copy_rows, dim3((n * 75 + 255) / 256), dim3(256), 0, s->stream, n, 75, (const float*)nullptr, s->warm, (float*)nullptr, mask);
+    copy_rows(s, 76, qpos, s->st.qpos, s->st.qpos_d, mask);
+    copy_rows(s, 75, qvel, s->st.qvel, s->st.qvel_d, mask);
+    copy_rows(s, 75, nullptr, s->st.warm, nullptr, mask);
     HIP_OK(hipGetLastError());
     return launch_step(s, nullptr, 0, mask, false);  // sim.forward(): derived quantities at the new state
 }
@@ -660,10 +703,8 @@ int kp_sim_set_state(kp_sim* s, const float* qpos, const float* qvel, const uint
 int kp_sim_set_target(kp_sim* s, const float* tq, const uint8_t* mask) {
     if (!s || !tq) return fail("kp_sim_set_target: null argument");
     HIP_OK(hipSetDevice(s->device));
-    kp::TargetBufs B{s->t_qpos, s->t_wbpos, s->t_wbquat, s->t_bquat, s->t_com};
-    hipLaunchKernelGGL(kp::k_target_fk, dim3((s->n + 3) / 4), dim3(256), 0, s->stream, s->n, tq, mask, B, s->T.body_pos, s->T.body_ipos, s->T.body_parent, s->T.body_depth);
-    HIP_OK(hipGetLastError());
-    return 0;
+    launch_target_fk(s, s->n, tq, mask, s->tgt);
+    return launched();
 }
 
 // objects that are not parked (convert_obj_qpos parks the inactive ones 100+ m away): dynamic mode -> they become the env's
@@ -719,27 +760,29 @@ __global__ void k_set_objects(int n, const float* __restrict__ obj_qpos_all, con
     ngeom[e] = ng;
 }
 
+// install the object block of the masked envs (k_set_objects); from now on the control step runs the object kernels
+static int launch_set_objects(kp_sim* s, const char* who, const float* obj_qpos, const uint8_t* mask, const int* row, const float* one_hot, float* obj7) {
+    ObjectRows& o = s->obj;
+    if (!o.d_geoms) return fail(std::string(who) + ": the model blob has no object geoms");
+    const int dynamic = s->model->dynamic_objects && s->T.obj_inertial != nullptr;
+    hipLaunchKernelGGL(k_set_objects, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, s->n, obj_qpos, mask, o.qpos, o.geoms, o.ngeom,
+                       o.d_geoms, o.d_mass, o.n_geoms, o.n_obj, dynamic, o.slot, o.qvel, o.warm, row, one_hot, obj7);
+    HIP_OK(hipGetLastError());
+    o.on = true;
+    return 0;
+}
+
 int kp_sim_set_objects(kp_sim* s, const float* obj_qpos, const uint8_t* mask) {
     if (!s || !obj_qpos) return fail("kp_sim_set_objects: null argument");
-    if (!s->d_obj_geoms) return fail("kp_sim_set_objects: the model blob has no object geoms");
-    const int dynamic = s->model->dynamic_objects && s->T.obj_inertial != nullptr;
     HIP_OK(hipSetDevice(s->device));
-    hipLaunchKernelGGL(k_set_objects, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, s->n, obj_qpos, mask, s->obj_qpos, s->geoms, s->ngeom,
-                       s->d_obj_geoms, s->d_obj_mass, s->n_obj_geoms, s->n_obj, dynamic, s->obj_slot, s->obj_qvel, s->obj_warm,
-                       (const int*)nullptr, (const float*)nullptr, (float*)nullptr);
-    HIP_OK(hipGetLastError());
-    s->has_objects = true;
-    return 0;
+    return launch_set_objects(s, "kp_sim_set_objects", obj_qpos, mask, nullptr, nullptr, nullptr);
 }
 
 int kp_sim_fk(kp_sim* s, int n_rows, const float* qpos, float* qpos_out, float* wbpos, float* wbquat, float* bquat, float* com) {
     if (!s || !qpos || n_rows <= 0) return fail("kp_sim_fk: bad arguments");
     HIP_OK(hipSetDevice(s->device));
-    kp::TargetBufs B{qpos_out, wbpos, wbquat, bquat, com};
-    hipLaunchKernelGGL(kp::k_target_fk, dim3((n_rows + 3) / 4), dim3(256), 0, s->stream, n_rows, qpos, (const uint8_t*)nullptr, B,
-                       s->T.body_pos, s->T.body_ipos, s->T.body_parent, s->T.body_depth);
-    HIP_OK(hipGetLastError());
-    return 0;
+    launch_target_fk(s, n_rows, qpos, nullptr, kp::TargetBufs{qpos_out, wbpos, wbquat, bquat, com});
+    return launched();
 }
 
 int kp_sim_pose_contacts(kp_sim* s, int n_rows, const float* xpos, const float* xquat, const float* obj_qpos, float pen_margin,
@@ -748,13 +791,13 @@ int kp_sim_pose_contacts(kp_sim* s, int n_rows, const float* xpos, const float* 
     if (n_rows < 0) return fail("kp_sim_pose_contacts: n_rows < 0");
     if (!xpos || !xquat) return fail("kp_sim_pose_contacts: null xpos / xquat");
     if (!pen || !ncon || !hits) return fail("kp_sim_pose_contacts: null output");
-    if (obj_qpos && !s->d_obj_geoms) return fail("kp_sim_pose_contacts: obj_qpos given but the model blob has no object geoms");
-    if (s->n_obj_geoms > kp::PC_MAXGEOM) return fail("kp_sim_pose_contacts: the model has more object geoms than the query holds (16)");
+    if (obj_qpos && !s->obj.d_geoms) return fail("kp_sim_pose_contacts: obj_qpos given but the model blob has no object geoms");
+    if (s->obj.n_geoms > kp::PC_MAXGEOM) return fail("kp_sim_pose_contacts: the model has more object geoms than the query holds (16)");
     if (n_rows == 0) return 0;
     HIP_OK(hipSetDevice(s->device));
     kp::PoseContactArgs A{};
-    A.T = s->T; A.P = s->P; A.n_rows = n_rows; A.n_og = s->n_obj_geoms; A.n_obj = s->n_obj;
-    A.xpos = xpos; A.xquat = xquat; A.obj_qpos = obj_qpos; A.og = s->d_obj_geoms; A.pen_margin = pen_margin;
+    A.T = s->T; A.P = s->P; A.n_rows = n_rows; A.n_og = s->obj.n_geoms; A.n_obj = s->obj.n_obj;
+    A.xpos = xpos; A.xquat = xquat; A.obj_qpos = obj_qpos; A.og = s->obj.d_geoms; A.pen_margin = pen_margin;
     A.pen = pen; A.ncon = ncon; A.hits = hits;
     HIP_OK(kp::launch_pose_contacts(A, s->stream));
     return 0;
@@ -765,22 +808,25 @@ int kp_sim_fk_backward(kp_sim* s, int n_rows, const float* qpos, const float* wb
     HIP_OK(hipSetDevice(s->device));
     hipLaunchKernelGGL(kp::k_fk_wbpos_grad, dim3((n_rows + 3) / 4), dim3(256), 0, s->stream, n_rows, qpos, wbpos, wbquat, grad_wbpos, grad_qpos,
                        s->T.body_parent, s->T.body_subtree);
-    HIP_OK(hipGetLastError());
+    return launched();
+}
+
+static int check_step_ctrl(const char* who, const kp_sim* s, const float* action, int nsub) {
+    if (!s || !action || nsub <= 0) return fail(std::string(who) + ": bad arguments");
+    if (s->xc.meta == 1 && nsub > 15)       // the reference's 30-entry meta_pd block holds kp / kd scales of 15 substeps (meta_pds[i_iter + 15], humanoid_im.py:456-458)
+        return fail(std::string(who) + ": cc_meta_pd = 1 (meta_pd) scales the gains of at most 15 substeps per control step, got " + std::to_string(nsub));
     return 0;
 }
 
 int kp_sim_step_ctrl(kp_sim* s, const float* action, int nsub, const uint8_t* mask) {
-    if (!s || !action || nsub <= 0) return fail("kp_sim_step_ctrl: bad arguments");
-    if (s->xc.meta == 1 && nsub > 15)       // the reference's 30-entry meta_pd block holds kp / kd scales of 15 substeps (meta_pds[i_iter + 15], humanoid_im.py:456-458)
-        return fail("kp_sim_step_ctrl: cc_meta_pd = 1 (meta_pd) scales the gains of at most 15 substeps per control step, got " + std::to_string(nsub));
+    if (check_step_ctrl("kp_sim_step_ctrl", s, action, nsub)) return -1;
     HIP_OK(hipSetDevice(s->device));
     return launch_step(s, action, nsub, mask, true);
 }
 
 int kp_sim_step_ctrl_base(kp_sim* s, const float* action, int nsub, const uint8_t* mask, const float* base_qpos) {
     if (!base_qpos) return fail("kp_sim_step_ctrl_base: null base_qpos");
-    if (!s || !action || nsub <= 0) return fail("kp_sim_step_ctrl_base: bad arguments");
-    if (s->xc.meta == 1 && nsub > 15) return fail("kp_sim_step_ctrl_base: cc_meta_pd = 1 (meta_pd) scales the gains of at most 15 substeps per control step, got " + std::to_string(nsub));
+    if (check_step_ctrl("kp_sim_step_ctrl_base", s, action, nsub)) return -1;
     HIP_OK(hipSetDevice(s->device));
     return launch_step(s, action, nsub, mask, true, base_qpos);
 }
@@ -820,9 +866,8 @@ kp_takes* kp_takes_create(kp_sim* s, const float* qpos_rows, int rows_on_device,
         return bail("kp_takes_create: upload of the take offsets failed");
     if (hipMemcpyAsync(t->L.tab[kp::TT_QPOS], qpos_rows, sizeof(float) * (size_t)R * 76, rows_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream) != hipSuccess)
         return bail("kp_takes_create: copy of qpos_rows failed");
-    kp::TargetBufs B{t->L.tab[kp::TT_QPOS_FK], t->L.tab[kp::TT_WBPOS], t->L.tab[kp::TT_WBQUAT], t->L.tab[kp::TT_BQUAT], t->L.tab[kp::TT_BODY_COM]};
-    hipLaunchKernelGGL(kp::k_target_fk, dim3((R + 3) / 4), dim3(256), 0, s->stream, R, (const float*)t->L.tab[kp::TT_QPOS], (const uint8_t*)nullptr, B,
-                       s->T.body_pos, s->T.body_ipos, s->T.body_parent, s->T.body_depth);
+    launch_target_fk(s, R, t->L.tab[kp::TT_QPOS], nullptr,
+                     kp::TargetBufs{t->L.tab[kp::TT_QPOS_FK], t->L.tab[kp::TT_WBPOS], t->L.tab[kp::TT_WBQUAT], t->L.tab[kp::TT_BQUAT], t->L.tab[kp::TT_BODY_COM]});
     kp::TakeBuildArgs A{t->L, s->T.body_mass, (float)(1.0 / dt)};
     if (hipGetLastError() != hipSuccess || kp::launch_take_tables(A, s->stream) != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess)
         return bail("kp_takes_create: building the tables failed");
@@ -880,8 +925,8 @@ int kp_sim_uhc_track(kp_sim* s, const kp_takes* t, const kp_uhc_state* st, const
     HIP_OK(hipSetDevice(s->device));
     kp::UhcTrackArgs A{};
     A.L = t->L; A.n = s->n; A.st = *st; A.cfg = *c; A.inv_dt = (float)(1.0 / c->dt);
-    A.qpos = s->qpos; A.xpos = s->xpos; A.xipos = s->xipos; A.prev_bquat = s->prev_bquat;
-    A.t_qpos = s->t_qpos; A.t_wbpos = s->t_wbpos; A.t_wbquat = s->t_wbquat; A.t_bquat = s->t_bquat; A.t_com = s->t_com;
+    A.qpos = s->st.qpos; A.xpos = s->st.xpos; A.xipos = s->st.xipos; A.prev_bquat = s->st.prev_bquat;
+    A.t_qpos = s->tgt.qpos; A.t_wbpos = s->tgt.wbpos; A.t_wbquat = s->tgt.wbquat; A.t_bquat = s->tgt.bquat; A.t_com = s->tgt.com;
     A.body_mass = s->T.body_mass; A.b_diffw = c->b_diffw; A.jpos_diffw = s->diffw; A.action = action;
     A.reward = reward; A.info = info; A.body_diff = body_diff; A.percent = percent; A.fail = failp; A.end = endp; A.done = donep;
     HIP_OK(kp::launch_uhc_track(A, s->stream));
@@ -911,8 +956,8 @@ int kp_sim_uhc_assign(kp_sim* s, const kp_takes* t, const kp_uhc_state* st, cons
         if (start) { HIP_OK(hipMemcpyAsync(s->uhc_stage + s->n, start, sizeof(int32_t) * s->n, hipMemcpyHostToDevice, s->stream)); A.start = s->uhc_stage + s->n; }
     }
     A.L = t->L; A.n = s->n; A.keep_t = keep_t; A.obs_v = c->obs_v; A.st = *st; A.mask = mask; A.noise = noise; A.a_ref = c->a_ref;
-    A.qpos = s->qpos; A.qpos_d = s->qpos_d; A.qvel = s->qvel; A.qvel_d = s->qvel_d; A.warm = s->warm;
-    A.t_qpos = s->t_qpos; A.t_wbpos = s->t_wbpos; A.t_wbquat = s->t_wbquat; A.t_bquat = s->t_bquat; A.t_com = s->t_com;
+    A.qpos = s->st.qpos; A.qpos_d = s->st.qpos_d; A.qvel = s->st.qvel; A.qvel_d = s->st.qvel_d; A.warm = s->st.warm;
+    A.t_qpos = s->tgt.qpos; A.t_wbpos = s->tgt.wbpos; A.t_wbquat = s->tgt.wbquat; A.t_bquat = s->tgt.bquat; A.t_com = s->tgt.com;
     HIP_OK(kp::launch_uhc_assign(A, s->stream));
     return launch_step(s, nullptr, 0, mask, false);      // sim.forward(): derived quantities at the new state
 }
@@ -920,34 +965,32 @@ int kp_sim_uhc_assign(kp_sim* s, const kp_takes* t, const kp_uhc_state* st, cons
 int kp_sim_step_head(kp_sim* s, const float* act) {
     if (!s || !act) return fail("kp_sim_step_head: null argument");
     HIP_OK(hipSetDevice(s->device));
-    kp::TargetBufs B{s->t_qpos, s->t_wbpos, s->t_wbquat, s->t_bquat, s->t_com};
-    kp::KinStep K{act, s->xpos, s->xquat, s->prev_bquat, s->prev_hpos, 1.0f / 30.0f};
-    hipLaunchKernelGGL(kp::k_target_fk, dim3((s->n + 3) / 4), dim3(256), 0, s->stream, s->n, s->qpos, (const uint8_t*)nullptr, B, s->T.body_pos, s->T.body_ipos,
-                       s->T.body_parent, s->T.body_depth, K);
-    HIP_OK(hipGetLastError());
-    return 0;
+    launch_target_fk(s, s->n, s->st.qpos, nullptr, s->tgt, kp::KinStep{act, s->st.xpos, s->st.xquat, s->st.prev_bquat, s->st.prev_hpos, 1.0f / 30.0f});
+    return launched();
 }
 
 int kp_sim_step_kin(kp_sim* s, const float* act, float* next_qpos) {
     if (!s || !act || !next_qpos) return fail("kp_sim_step_kin: null argument");
     HIP_OK(hipSetDevice(s->device));
-    hipLaunchKernelGGL(kp::k_step_kin, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, s->n, s->qpos, act, next_qpos, 1.0f / 30.0f);
-    HIP_OK(hipGetLastError());
-    return 0;
+    hipLaunchKernelGGL(kp::k_step_kin, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, s->n, s->st.qpos, act, next_qpos, 1.0f / 30.0f);
+    return launched();
+}
+
+static kp::ObsCcArgs obs_cc_args(const kp_sim* s, float* out, const float* zf_mean, const float* zf_std, float clip) {
+    kp::ObsCcArgs A;
+    A.n = s->n; A.qpos = s->st.qpos; A.qvel = s->st.qvel; A.xpos = s->st.xpos; A.xquat = s->st.xquat; A.xipos = s->st.xipos;
+    A.t_qpos = s->tgt.qpos; A.t_wbpos = s->tgt.wbpos; A.t_wbquat = s->tgt.wbquat; A.t_com = s->tgt.com;
+    for (int k = 0; k < 4; k++) A.br_inv[k] = s->P.br_inv[k];
+    A.zf_mean = zf_mean; A.zf_std = zf_std; A.clip = clip; A.out = out;
+    return A;
 }
 
 int kp_sim_obs_cc(kp_sim* s, float* out, const float* zf_mean, const float* zf_std, float clip) {
     if (!s || !out) return fail("kp_sim_obs_cc: null argument");
     if ((zf_mean == nullptr) != (zf_std == nullptr)) return fail("kp_sim_obs_cc: pass both zf_mean and zf_std or neither");
     HIP_OK(hipSetDevice(s->device));
-    kp::ObsCcArgs A;
-    A.n = s->n; A.qpos = s->qpos; A.qvel = s->qvel; A.xpos = s->xpos; A.xquat = s->xquat; A.xipos = s->xipos;
-    A.t_qpos = s->t_qpos; A.t_wbpos = s->t_wbpos; A.t_wbquat = s->t_wbquat; A.t_com = s->t_com;
-    for (int k = 0; k < 4; k++) A.br_inv[k] = s->P.br_inv[k];
-    A.zf_mean = zf_mean; A.zf_std = zf_std; A.clip = clip; A.out = out;
-    hipLaunchKernelGGL(kp::k_obs_cc, dim3(s->n), dim3(64), 0, s->stream, A);
-    HIP_OK(hipGetLastError());
-    return 0;
+    hipLaunchKernelGGL(kp::k_obs_cc, dim3(s->n), dim3(64), 0, s->stream, obs_cc_args(s, out, zf_mean, zf_std, clip));
+    return launched();
 }
 
 extern "C++" {   // the launchers are templates
@@ -977,36 +1020,35 @@ int kp_sim_obs_cc_ex(kp_sim* s, float* out, const float* zf_mean, const float* z
     if (s->cc_obs_phase && !phase) return fail("kp_sim_obs_cc_ex: this handle's observation ends with the phase (cc_obs_phase = 1): pass phase [N]");
     if (!s->cc_obs_phase && phase) return fail("kp_sim_obs_cc_ex: phase given, but this handle's observation has no phase slot (cc_obs_phase = 0 or cc_obs_v != 0)");
     HIP_OK(hipSetDevice(s->device));
-    kp::ObsCcArgs A;
-    A.n = s->n; A.qpos = s->qpos; A.qvel = s->qvel; A.xpos = s->xpos; A.xquat = s->xquat; A.xipos = s->xipos;
-    A.t_qpos = s->t_qpos; A.t_wbpos = s->t_wbpos; A.t_wbquat = s->t_wbquat; A.t_com = s->t_com;
-    for (int k = 0; k < 4; k++) A.br_inv[k] = s->P.br_inv[k];
-    A.zf_mean = zf_mean; A.zf_std = zf_std; A.clip = clip; A.out = out;
+    const kp::ObsCcArgs A = obs_cc_args(s, out, zf_mean, zf_std, clip);
     if (s->cc_obs_v == 1 && !s->cc_obs_vel_root) hipLaunchKernelGGL(kp::k_obs_cc, dim3(s->n), dim3(64), 0, s->stream, A);   // the uhc.yml layout: the same kernel as kp_sim_obs_cc
     else if (s->cc_obs_v == 1) launch_obs_cc_v<1, true, false, false, false>(s, A, nullptr);
     else if (s->cc_obs_v == 2 && s->cc_obs_vel_root) launch_obs_cc_v<2, true, false, false, false>(s, A, nullptr);
     else if (s->cc_obs_v == 2) launch_obs_cc_v<2, false, false, false, false>(s, A, nullptr);
     else if (s->cc_obs_vel_root) launch_obs_cc_v0<true>(s, A, phase);
     else launch_obs_cc_v0<false>(s, A, phase);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return launched();
 }
 int kp_sim_cc_obs_dim(const kp_sim* s) { return s ? s->cc_obs_dim : -1; }
 
-int kp_field_dim(int f) {
-    switch (f) {
-        case KP_QPOS: case KP_TARGET_QPOS: case KP_QPOS_D: return 76;
-        case KP_QVEL: case KP_QVEL_D: return 75;
-        case KP_XPOS: case KP_XIPOS: case KP_TARGET_WBPOS: case KP_TARGET_COM: return 72;
-        case KP_XQUAT: case KP_BQUAT: case KP_TARGET_WBQUAT: case KP_TARGET_BQUAT: case KP_PREV_BQUAT: return 96;
-        case KP_HEAD: case KP_PREV_HPOS: return 7;
-        case KP_OBJ_QPOS: return 35;
-        case KP_OBJ_QVEL: return 30;
-        case KP_M: return 75 * 75;
-        case KP_BIAS: return 75;
-        default: return -1;
-    }
-}
+// ---- state fields: ONE table behind kp_field_dim, kp_sim_field_device and kp_sim_get, indexed by kp_field.  row: where a stored field lives (null: a
+// derived read-out, computed by kp_sim_get); view: kp_sim_field_device hands the row out (not the target read-outs and the prev_* records).
+struct Field { int dim; bool view; float* (*row)(const kp_sim&); };
+#define ROW(member) [](const kp_sim& s) -> float* { return s.member; }
+static const Field FIELDS[] = {
+    /* KP_QPOS */ {76, true, ROW(st.qpos)}, /* KP_QVEL */ {75, true, ROW(st.qvel)}, /* KP_XPOS */ {72, true, ROW(st.xpos)}, /* KP_XQUAT */ {96, true, ROW(st.xquat)},
+    /* KP_XIPOS */ {72, true, ROW(st.xipos)}, /* KP_BQUAT */ {96, false, nullptr}, /* KP_HEAD */ {7, false, nullptr},
+    /* KP_TARGET_QPOS */ {76, true, ROW(tgt.qpos)}, /* KP_TARGET_WBPOS */ {72, false, ROW(tgt.wbpos)}, /* KP_TARGET_WBQUAT */ {96, false, ROW(tgt.wbquat)},
+    /* KP_TARGET_BQUAT */ {96, false, ROW(tgt.bquat)}, /* KP_TARGET_COM */ {72, false, ROW(tgt.com)},
+    /* KP_QPOS_D */ {76, true, ROW(st.qpos_d)}, /* KP_QVEL_D */ {75, true, ROW(st.qvel_d)},
+    /* KP_PREV_BQUAT */ {96, false, ROW(st.prev_bquat)}, /* KP_PREV_HPOS */ {7, false, ROW(st.prev_hpos)},
+    /* KP_OBJ_QPOS */ {35, true, ROW(obj.qpos)}, /* KP_OBJ_QVEL */ {30, true, ROW(obj.qvel)}, /* KP_M */ {75 * 75, false, nullptr}, /* KP_BIAS */ {75, false, nullptr},
+};
+#undef ROW
+static_assert(sizeof(FIELDS) / sizeof(FIELDS[0]) == KP_BIAS + 1, "one row per kp_field");
+static const Field* find_field(int f) { return f >= 0 && f <= KP_BIAS ? &FIELDS[f] : nullptr; }
+
+int kp_field_dim(int f) { const Field* d = find_field(f); return d ? d->dim : -1; }
 
 __global__ void k_head(int n, const float* __restrict__ xpos, const float* __restrict__ xquat, float* __restrict__ out) {
     int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1017,57 +1059,24 @@ __global__ void k_head(int n, const float* __restrict__ xpos, const float* __res
 }
 
 const float* kp_sim_field_device(kp_sim* s, int field) {
-    if (!s) return nullptr;
-    switch (field) {
-        case KP_QPOS: return s->qpos;
-        case KP_QVEL: return s->qvel;
-        case KP_XPOS: return s->xpos;
-        case KP_XQUAT: return s->xquat;
-        case KP_XIPOS: return s->xipos;
-        case KP_TARGET_QPOS: return s->t_qpos;
-        case KP_QPOS_D: return s->qpos_d;
-        case KP_QVEL_D: return s->qvel_d;
-        case KP_OBJ_QPOS: return s->obj_qpos;
-        case KP_OBJ_QVEL: return s->obj_qvel;
-        default: return nullptr;
-    }
+    const Field* d = find_field(field);
+    return s && d && d->view ? d->row(*s) : nullptr;
 }
 
 int kp_sim_get(kp_sim* s, int field, float* out) {
     if (!s || !out) return fail("kp_sim_get: null argument");
     HIP_OK(hipSetDevice(s->device));
-    const float* src = nullptr;
-    switch (field) {
-        case KP_QPOS: src = s->qpos; break;
-        case KP_QVEL: src = s->qvel; break;
-        case KP_XPOS: src = s->xpos; break;
-        case KP_XQUAT: src = s->xquat; break;
-        case KP_XIPOS: src = s->xipos; break;
-        case KP_TARGET_QPOS: src = s->t_qpos; break;
-        case KP_TARGET_WBPOS: src = s->t_wbpos; break;
-        case KP_TARGET_WBQUAT: src = s->t_wbquat; break;
-        case KP_TARGET_BQUAT: src = s->t_bquat; break;
-        case KP_TARGET_COM: src = s->t_com; break;
-        case KP_QPOS_D: src = s->qpos_d; break;
-        case KP_QVEL_D: src = s->qvel_d; break;
-        case KP_PREV_BQUAT: src = s->prev_bquat; break;
-        case KP_PREV_HPOS: src = s->prev_hpos; break;
-        case KP_OBJ_QPOS: src = s->obj_qpos; break;
-        case KP_OBJ_QVEL: src = s->obj_qvel; break;
-        case KP_BQUAT:
-            hipLaunchKernelGGL(kp::k_bquat, dim3((s->n * 24 + 255) / 256), dim3(256), 0, s->stream, s->n, s->qpos, out);
-            HIP_OK(hipGetLastError());
-            return 0;
-        case KP_M: return kp_sim_mass_matrix(s, out, nullptr);
-        case KP_BIAS: return kp_sim_mass_matrix(s, nullptr, out);
-        case KP_HEAD:
-            hipLaunchKernelGGL(k_head, dim3((s->n + 255) / 256), dim3(256), 0, s->stream, s->n, s->xpos, s->xquat, out);
-            HIP_OK(hipGetLastError());
-            return 0;
-        default: return fail("kp_sim_get: unknown field");
+    const Field* d = find_field(field);
+    if (!d) return fail("kp_sim_get: unknown field");
+    if (d->row) {
+        HIP_OK(hipMemcpyAsync(out, d->row(*s), sizeof(float) * (size_t)s->n * d->dim, hipMemcpyDeviceToDevice, s->stream));
+        return 0;
     }
-    HIP_OK(hipMemcpyAsync(out, src, sizeof(float) * (size_t)s->n * kp_field_dim(field), hipMemcpyDeviceToDevice, s->stream));
-    return 0;
+    if (field == KP_M) return kp_sim_mass_matrix(s, out, nullptr);
+    if (field == KP_BIAS) return kp_sim_mass_matrix(s, nullptr, out);
+    if (field == KP_BQUAT) hipLaunchKernelGGL(kp::k_bquat, dim3((s->n * 24 + 255) / 256), dim3(256), 0, s->stream, s->n, s->st.qpos, out);
+    else hipLaunchKernelGGL(k_head, dim3((s->n + 255) / 256), dim3(256), 0, s->stream, s->n, s->st.xpos, s->st.xquat, out);      // KP_HEAD
+    return launched();
 }
 
 static kp::CtxDev to_dev(const kp_ctx* c) {
@@ -1080,9 +1089,8 @@ static kp::CtxDev to_dev(const kp_ctx* c) {
 int kp_sim_step_begin(kp_sim* s) {
     if (!s) return fail("kp_sim_step_begin: null argument");
     HIP_OK(hipSetDevice(s->device));
-    hipLaunchKernelGGL(kp::k_snapshot, dim3((s->n * 24 + 255) / 256), dim3(256), 0, s->stream, s->n, s->qpos, s->xpos, s->xquat, s->prev_bquat, s->prev_hpos);
-    HIP_OK(hipGetLastError());
-    return 0;
+    hipLaunchKernelGGL(kp::k_snapshot, dim3((s->n * 24 + 255) / 256), dim3(256), 0, s->stream, s->n, s->st.qpos, s->st.xpos, s->st.xquat, s->st.prev_bquat, s->st.prev_hpos);
+    return launched();
 }
 
 int kp_sim_obs_ar(kp_sim* s, const kp_ctx* c, float* out) {
@@ -1090,23 +1098,31 @@ int kp_sim_obs_ar(kp_sim* s, const kp_ctx* c, float* out) {
         return fail("kp_sim_obs_ar: bad arguments");
     HIP_OK(hipSetDevice(s->device));
     if (s->ar_obs_dim == KP_AR_OBS_DIM)
-        hipLaunchKernelGGL(kp::k_obs_ar<true>, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, s->n, to_dev(c), s->qpos, s->xpos, s->xquat, out);
+        hipLaunchKernelGGL(kp::k_obs_ar<true>, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, s->n, to_dev(c), s->st.qpos, s->st.xpos, s->st.xquat, out);
     else
-        hipLaunchKernelGGL(kp::k_obs_ar<false>, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, s->n, to_dev(c), s->qpos, s->xpos, s->xquat, out);
-    HIP_OK(hipGetLastError());
-    return 0;
+        hipLaunchKernelGGL(kp::k_obs_ar<false>, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, s->n, to_dev(c), s->st.qpos, s->st.xpos, s->st.xquat, out);
+    return launched();
+}
+
+static kp::RewardW reward_w(const kp_reward_cfg* w) {
+    return kp::RewardW{w->w_hp, w->w_hq, w->w_p, w->w_jp, w->w_act_p, w->w_act_v, w->k_hp, w->k_hq, w->k_p, w->k_jp, w->k_act_p, w->k_act_v,
+                       w->dt, w->body_diff_thresh, w->body_diff_gt_thresh, w->use_gt_term};
+}
+// termination + reward of the env step; post (optional): with the tail of HumanoidAREnv.step in the same launch (kp_sim_post_step)
+static int launch_term_reward(kp_sim* s, const kp_ctx* c, const kp_reward_cfg* w, float* reward, float* info, uint8_t* failp, float* diffs, const kp::PostStep* post) {
+    const StateRows& st = s->st;
+    if (!post) hipLaunchKernelGGL(kp::k_term_reward<false>, dim3((s->n + 7) / 8), dim3(256), 0, s->stream, s->n, to_dev(c), reward_w(w), st.qpos, st.xpos, st.xquat,
+                                  s->tgt.wbpos, s->tgt.bquat, st.prev_bquat, st.prev_hpos, s->diffw, reward, info, failp, diffs, kp::PostStep{});
+    else hipLaunchKernelGGL(kp::k_term_reward<true>, dim3((s->n + 7) / 8), dim3(256), 0, s->stream, s->n, to_dev(c), reward_w(w), st.qpos, st.xpos, st.xquat,
+                            s->tgt.wbpos, s->tgt.bquat, st.prev_bquat, st.prev_hpos, s->diffw, reward, info, failp, diffs, *post);
+    return launched();
 }
 
 int kp_sim_term_reward(kp_sim* s, const kp_ctx* c, const kp_reward_cfg* w, float* reward, float* info, uint8_t* failp, float* diffs) {
     if (!s || !c || !w || !reward || !info || !failp || !diffs || !c->head_pose || !c->gt_bquat || !c->gt_wbpos || !c->cur_t || c->T < 2)
         return fail("kp_sim_term_reward: bad arguments");
     HIP_OK(hipSetDevice(s->device));
-    kp::RewardW W{w->w_hp, w->w_hq, w->w_p, w->w_jp, w->w_act_p, w->w_act_v, w->k_hp, w->k_hq, w->k_p, w->k_jp, w->k_act_p, w->k_act_v,
-                  w->dt, w->body_diff_thresh, w->body_diff_gt_thresh, w->use_gt_term};
-    hipLaunchKernelGGL(kp::k_term_reward<false>, dim3((s->n + 7) / 8), dim3(256), 0, s->stream, s->n, to_dev(c), W, s->qpos, s->xpos, s->xquat,
-                       s->t_wbpos, s->t_bquat, s->prev_bquat, s->prev_hpos, s->diffw, reward, info, failp, diffs, kp::PostStep{});
-    HIP_OK(hipGetLastError());
-    return 0;
+    return launch_term_reward(s, c, w, reward, info, failp, diffs, nullptr);
 }
 
 int kp_sim_post_step(kp_sim* s, const kp_ctx* c, const kp_reward_cfg* w, int32_t* cur_t, const int32_t* row_len, int env_episode_len,
@@ -1116,13 +1132,8 @@ int kp_sim_post_step(kp_sim* s, const kp_ctx* c, const kp_reward_cfg* w, int32_t
     if (c->cur_t != cur_t) return fail("kp_sim_post_step: cur_t must be the buffer the context reads (kp_ctx.cur_t)");
     if (obj7 && !c->action_one_hot) return fail("kp_sim_post_step: obj7 needs the context's action_one_hot");
     HIP_OK(hipSetDevice(s->device));
-    kp::RewardW W{w->w_hp, w->w_hq, w->w_p, w->w_jp, w->w_act_p, w->w_act_v, w->k_hp, w->k_hq, w->k_p, w->k_jp, w->k_act_p, w->k_act_v,
-                  w->dt, w->body_diff_thresh, w->body_diff_gt_thresh, w->use_gt_term};
-    kp::PostStep PS{cur_t, row_len, env_episode_len, done, end, percent, done_count, obj7, obj7 ? s->obj_qpos : nullptr};
-    hipLaunchKernelGGL(kp::k_term_reward<true>, dim3((s->n + 7) / 8), dim3(256), 0, s->stream, s->n, to_dev(c), W, s->qpos, s->xpos, s->xquat,
-                       s->t_wbpos, s->t_bquat, s->prev_bquat, s->prev_hpos, s->diffw, reward, info, failp, diffs, PS);
-    HIP_OK(hipGetLastError());
-    return 0;
+    const kp::PostStep PS{cur_t, row_len, env_episode_len, done, end, percent, done_count, obj7, obj7 ? s->obj.qpos : nullptr};
+    return launch_term_reward(s, c, w, reward, info, failp, diffs, &PS);
 }
 
 int kp_sim_reset_rows(kp_sim* s, const float* init_qpos, const float* init_qvel, const int32_t* row, const uint8_t* mask, int32_t* cur_t, int set_target,
@@ -1130,21 +1141,14 @@ int kp_sim_reset_rows(kp_sim* s, const float* init_qpos, const float* init_qvel,
     if (!s || !init_qpos || !init_qvel || (aux_rows && aux_cols <= 0)) return fail("kp_sim_reset_rows: null argument");
     if (obj7 && !row_obj_qpos) return fail("kp_sim_reset_rows: obj7 needs row_obj_qpos");
     HIP_OK(hipSetDevice(s->device));
-    if (row_obj_qpos) {       // the object block of reset_model (humanoid_ar_v1.py:377-382) from the env's context row, before sim.forward()
-        if (!s->d_obj_geoms) return fail("kp_sim_reset_rows: the model blob has no object geoms");
-        const int dynamic = s->model->dynamic_objects && s->T.obj_inertial != nullptr;
-        hipLaunchKernelGGL(k_set_objects, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, s->n, row_obj_qpos, mask, s->obj_qpos, s->geoms, s->ngeom,
-                           s->d_obj_geoms, s->d_obj_mass, s->n_obj_geoms, s->n_obj, dynamic, s->obj_slot, s->obj_qvel, s->obj_warm, row, row_action_one_hot, obj7);
-        HIP_OK(hipGetLastError());
-        s->has_objects = true;
-    }
-    hipLaunchKernelGGL(kp::k_reset_rows, dim3(s->n), dim3(128), 0, s->stream, s->n, init_qpos, init_qvel, row, mask, cur_t, s->qpos, s->qvel, s->qpos_d, s->qvel_d, s->warm,
-                       aux_rows, aux_rows ? aux_cols : 0);
+    // the object block of reset_model (humanoid_ar_v1.py:377-382) from the env's context row, before sim.forward()
+    if (row_obj_qpos && launch_set_objects(s, "kp_sim_reset_rows", row_obj_qpos, mask, row, row_action_one_hot, obj7)) return -1;
+    hipLaunchKernelGGL(kp::k_reset_rows, dim3(s->n), dim3(128), 0, s->stream, s->n, init_qpos, init_qvel, row, mask, cur_t, s->st.qpos, s->st.qvel, s->st.qpos_d, s->st.qvel_d,
+                       s->st.warm, aux_rows, aux_rows ? aux_cols : 0);
     HIP_OK(hipGetLastError());
     if (int rc = launch_step(s, nullptr, 0, mask, false)) return rc;      // sim.forward(): derived quantities at the new state
     if (set_target) {                                                     // target = smpl_humanoid.qpos_fk(init_qpos) (humanoid_ar_v1.py:384-386): the state just written
-        kp::TargetBufs B{s->t_qpos, s->t_wbpos, s->t_wbquat, s->t_bquat, s->t_com};
-        hipLaunchKernelGGL(kp::k_target_fk, dim3((s->n + 3) / 4), dim3(256), 0, s->stream, s->n, s->qpos, mask, B, s->T.body_pos, s->T.body_ipos, s->T.body_parent, s->T.body_depth);
+        launch_target_fk(s, s->n, s->st.qpos, mask, s->tgt);
         HIP_OK(hipGetLastError());
     }
     return 0;
@@ -1154,8 +1158,7 @@ int kp_gae_bootstrap(int n, int T, const float* rewards, const float* masks, con
                      float* adv, float* ret, void* stream) {
     if (n <= 0 || T <= 0 || !rewards || !masks || !values || !adv || !ret) return fail("kp_gae: bad arguments");
     hipLaunchKernelGGL(kp::k_gae, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, n, T, rewards, masks, values, last_values, gamma, tau, adv, ret);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return launched();
 }
 int kp_gae(int n, int T, const float* rewards, const float* masks, const float* values, float gamma, float tau, float* adv, float* ret, void* stream) {
     return kp_gae_bootstrap(n, T, rewards, masks, values, nullptr, gamma, tau, adv, ret, stream);
@@ -1164,8 +1167,7 @@ int kp_gae(int n, int T, const float* rewards, const float* masks, const float* 
 int kp_pool_advance(int n, int n_slots, const uint8_t* done, int32_t* head, int32_t* ahead, int32_t* row, void* stream) {
     if (n <= 0 || n_slots <= 0 || !done || !head || !ahead || !row) return fail("kp_pool_advance: bad arguments");
     hipLaunchKernelGGL(kp::k_pool_advance, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, n_slots, done, head, ahead, row);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return launched();
 }
 
 int kp_sim_ar_obs_dim(const kp_sim* s) { return s ? s->ar_obs_dim : -1; }
@@ -1180,8 +1182,7 @@ int kp_rollout_record_pre_w(const kp_record_pre* r, int obs_dim, void* stream) {
                     r->states, r->episode_start, r->curr_qpos, r->gt_target_qpos, r->meta};
     if (obs_dim == KP_AR_OBS_DIM) hipLaunchKernelGGL(kp::k_record_pre<KP_AR_OBS_DIM>, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
     else hipLaunchKernelGGL(kp::k_record_pre<KP_AR_OBS_DIM_NO_ACTION>, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return launched();
 }
 int kp_rollout_record_pre(const kp_record_pre* r, void* stream) { return kp_rollout_record_pre_w(r, KP_AR_OBS_DIM, stream); }
 
@@ -1196,8 +1197,7 @@ int kp_rollout_record_post_w(const kp_record_post* r, int obs_dim, void* stream)
                      r->actions, r->rewards, r->fails, r->dones, r->percents, r->c_infos, r->next_states, r->res_qpos, r->cc_actions, r->cc_states, r->v_metas};
     if (obs_dim == KP_AR_OBS_DIM) hipLaunchKernelGGL(kp::k_record_post<KP_AR_OBS_DIM>, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
     else hipLaunchKernelGGL(kp::k_record_post<KP_AR_OBS_DIM_NO_ACTION>, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return launched();
 }
 int kp_rollout_record_post(const kp_record_post* r, void* stream) { return kp_rollout_record_post_w(r, KP_AR_OBS_DIM, stream); }
 
@@ -1206,15 +1206,13 @@ int kp_mcp_compose(int n, int K, int A, const float* logits, const float* prim, 
     if (noise && noise_stride < A) return fail("kp_mcp_compose: noise_stride " + std::to_string(noise_stride) + " is smaller than the row width A = " + std::to_string(A));
     const size_t tot = (size_t)n * A;
     hipLaunchKernelGGL(kp::k_mcp_compose, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, K, A, logits, prim, noise, noise_stride, stdv, out);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return launched();
 }
 
 int kp_kin_advance(int n, const float* qpos, const float* kin_action, float dt, float* next_qpos, float* qvel_fd, void* stream) {
     if (n <= 0 || !qpos || !kin_action || !next_qpos || !qvel_fd || !(dt > 0.f)) return fail("kp_kin_advance: bad arguments");
     hipLaunchKernelGGL(kp::k_kin_advance, dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, n, qpos, kin_action, dt, next_qpos, qvel_fd);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return launched();
 }
 
 int kp_mcp_tail(int n, int K, int J, int A, const float* h2, const float* b2, const float* w3, int ldw, const float* b3, const float* logits, const float* noise,
@@ -1229,8 +1227,7 @@ int kp_mcp_tail(int n, int K, int J, int A, const float* h2, const float* b2, co
     else if (ldw >= 80 && ldw % 4 == 0 && ((uintptr_t)w3 & 15) == 0) KP_TAIL(5, true);      // rows padded to 80 columns: 16-byte operand loads
     else KP_TAIL(5, false);
 #undef KP_TAIL
-    HIP_OK(hipGetLastError());
-    return 0;
+    return launched();
 }
 
 int kp_gru_cell_step(int n, int H, int D, const float* gi, const float* gh, const float* b_ih, const float* b_hh, const float* h_in, const float* state,
@@ -1239,58 +1236,52 @@ int kp_gru_cell_step(int n, int H, int D, const float* gi, const float* gh, cons
         return fail("kp_gru_cell_step: bad arguments (the [state | h] row needs state and 0 < D <= H)");
     const size_t tot = (size_t)n * H;
     hipLaunchKernelGGL(kp::k_gru_cell_step, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, H, D, gi, gh, b_ih, b_hh, h_in, state, h_out, xcat);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return launched();
 }
 
 int kp_gru_gates_forward(int n, int H, const float* gi, const float* gh, const float* hm_prev, const float* next_keep, float* h_out, float* hm_next, void* stream) {
     if (n <= 0 || H <= 0 || !gi || !gh || !hm_prev || !h_out) return fail("kp_gru_gates_forward: bad arguments");
     const size_t tot = (size_t)n * H;
     hipLaunchKernelGGL(kp::k_gru_gates_fwd, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, H, gi, gh, hm_prev, next_keep, h_out, hm_next);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return launched();
 }
 int kp_gru_gates_backward(int n, int H, const float* gi, const float* gh, const float* hm_prev, const float* dh_out, const float* carry, const float* carry_keep,
                           float* dgi, float* dgh, float* dhz, void* stream) {
     if (n <= 0 || H <= 0 || !gi || !gh || !hm_prev || !dgi || !dgh || !dhz) return fail("kp_gru_gates_backward: bad arguments");
     const size_t tot = (size_t)n * H;
     hipLaunchKernelGGL(kp::k_gru_gates_bwd, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, H, gi, gh, hm_prev, dh_out, carry, carry_keep, dgi, dgh, dhz);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return launched();
 }
 
 int kp_sim_set_full_state(kp_sim* s, const float* qpos, const float* qvel, const float* qpos_d, const float* qvel_d, const uint8_t* mask) {
     if (!s || !qpos || !qvel || !qpos_d || !qvel_d) return fail("kp_sim_set_full_state: null argument");
     HIP_OK(hipSetDevice(s->device));
-    int n = s->n;
-    hipLaunchKernelGGL(k_copy_rows, dim3((n * 76 + 255) / 256), dim3(256), 0, s->stream, n, 76, qpos, s->qpos, (float*)nullptr, mask);
-    hipLaunchKernelGGL(k_copy_rows, dim3((n * 75 + 255) / 256), dim3(256), 0, s->stream, n, 75, qvel, s->qvel, (float*)nullptr, mask);
-    hipLaunchKernelGGL(k_copy_rows, dim3((n * 76 + 255) / 256), dim3(256), 0, s->stream, n, 76, qpos_d, s->qpos_d, (float*)nullptr, mask);
-    hipLaunchKernelGGL(k_copy_rows, dim3((n * 75 + 255) / 256), dim3(256), 0, s->stream, n, 75, qvel_d, s->qvel_d, (float*)nullptr, mask);
+    copy_rows(s, 76, qpos, s->st.qpos, nullptr, mask);
+    copy_rows(s, 75, qvel, s->st.qvel, nullptr, mask);
+    copy_rows(s, 76, qpos_d, s->st.qpos_d, nullptr, mask);
+    copy_rows(s, 75, qvel_d, s->st.qvel_d, nullptr, mask);
     HIP_OK(hipGetLastError());
     return launch_step(s, nullptr, 0, mask, false);
 }
 
 int kp_sim_set_obj_state(kp_sim* s, const float* obj_qpos, const float* obj_qvel, const uint8_t* mask) {
     if (!s || !obj_qpos || !obj_qvel) return fail("kp_sim_set_obj_state: null argument");
-    if (!s->has_objects) return fail("kp_sim_set_obj_state: call kp_sim_set_objects first (it decides which objects are simulated)");
+    if (!s->obj.on) return fail("kp_sim_set_obj_state: call kp_sim_set_objects first (it decides which objects are simulated)");
     HIP_OK(hipSetDevice(s->device));
-    int n = s->n;
-    hipLaunchKernelGGL(k_copy_rows, dim3((n * 35 + 255) / 256), dim3(256), 0, s->stream, n, 35, obj_qpos, s->obj_qpos, (float*)nullptr, mask);
-    hipLaunchKernelGGL(k_copy_rows, dim3((n * 30 + 255) / 256), dim3(256), 0, s->stream, n, 30, obj_qvel, s->obj_qvel, (float*)nullptr, mask);
-    HIP_OK(hipGetLastError());
-    return 0;
+    copy_rows(s, 35, obj_qpos, s->obj.qpos, nullptr, mask);
+    copy_rows(s, 30, obj_qvel, s->obj.qvel, nullptr, mask);
+    return launched();
 }
 
 int kp_sim_diag(kp_sim* s, int32_t* out_host) {
     if (!s || !out_host) return fail("kp_sim_diag: null argument");
     HIP_OK(hipSetDevice(s->device));
     HIP_OK(hipStreamSynchronize(s->stream));
-    HIP_OK(hipMemcpy(out_host, s->diag, sizeof(int) * 4 * (size_t)s->n, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out_host, s->st.diag, sizeof(int) * 4 * (size_t)s->n, hipMemcpyDeviceToHost));
     unsigned ctr[4] = {0, 0, 0, 0};
-    HIP_OK(hipMemcpy(ctr, s->jobctr, sizeof(ctr), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(ctr, s->q.jobctr, sizeof(ctr), hipMemcpyDeviceToHost));
     if (ctr[2]) {
-        hipMemset(s->jobctr + 2, 0, sizeof(unsigned));     // reported once
+        hipMemset(s->q.jobctr + 2, 0, sizeof(unsigned));     // reported once
         return fail("kp_step_queue_kernel: a wavefront gave up waiting for a job to be published (job queue stalled); states are incomplete");
     }
     return 0;
@@ -1305,7 +1296,7 @@ int kp_sim_lean_state(kp_sim* s, int32_t* out3) {
     if (!s || !out3) return fail("kp_sim_lean_state: null argument");
     const StepPlan p = plan_step(*s, s->last_nsub, false);
     out3[0] = p.queue && p.layout == LEAN;
-    out3[1] = s->lean_fallbacks; out3[2] = (int32_t)s->launch_index;
+    out3[1] = s->ovf.fallbacks; out3[2] = (int32_t)s->launch_index;
     return 0;
 }
 
@@ -1313,58 +1304,62 @@ int kp_sim_launch_cost(kp_sim* s, uint32_t* out_host) {
     if (!s || !out_host) return fail("kp_sim_launch_cost: null argument");
     HIP_OK(hipSetDevice(s->device));
     HIP_OK(hipStreamSynchronize(s->stream));
-    HIP_OK(hipMemcpy(out_host, s->cost, sizeof(unsigned) * (size_t)s->n, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out_host, s->q.cost, sizeof(unsigned) * (size_t)s->n, hipMemcpyDeviceToHost));
     return 0;
 }
 
 double kp_sim_last_step_seconds(kp_sim* s) {
-    if (!s || !s->timed) return -1.0;
-    if (hipEventSynchronize(s->last1) != hipSuccess) return -1.0;
+    if (!s || !s->tm.timed) return -1.0;
+    if (hipEventSynchronize(s->tm.last1) != hipSuccess) return -1.0;
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->last0, s->last1) != hipSuccess) return -1.0;
+    if (hipEventElapsedTime(&ms, s->tm.last0, s->tm.last1) != hipSuccess) return -1.0;
     return ms * 1e-3;
 }
 
-int kp_sim_phase_cycles(kp_sim* s, double* out) {
-    if (!s || !out) return fail("kp_sim_phase_cycles: null argument");
-    if (!s->prof) return fail("kp_sim_phase_cycles: create the simulator with KP_PROFILE=1");
+// the per-env phase cycles of the last control step (KP_PROFILE=1) on the host: [N, 8]
+static int read_profile(const char* who, kp_sim* s, const double* out, std::vector<unsigned long long>& h) {
+    if (!s || !out) return fail(std::string(who) + ": null argument");
+    if (!s->prof) return fail(std::string(who) + ": create the simulator with KP_PROFILE=1");
     HIP_OK(hipSetDevice(s->device));
     HIP_OK(hipStreamSynchronize(s->stream));
-    std::vector<unsigned long long> h((size_t)s->n * 8);
+    h.resize((size_t)s->n * 8);
     HIP_OK(hipMemcpy(h.data(), s->prof, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int kp_sim_phase_cycles(kp_sim* s, double* out) {
+    std::vector<unsigned long long> h;
+    if (read_profile("kp_sim_phase_cycles", s, out, h)) return -1;
     for (int k = 0; k < 8; k++) { double acc = 0; for (int e = 0; e < s->n; e++) acc += (double)h[(size_t)e * 8 + k]; out[k] = acc / s->n; }
     return 0;
 }
 
 int kp_sim_phase_cycles_env(kp_sim* s, double* out) {
-    if (!s || !out) return fail("kp_sim_phase_cycles_env: null argument");
-    if (!s->prof) return fail("kp_sim_phase_cycles_env: create the simulator with KP_PROFILE=1");
-    HIP_OK(hipSetDevice(s->device));
-    HIP_OK(hipStreamSynchronize(s->stream));
-    std::vector<unsigned long long> h((size_t)s->n * 8);
-    HIP_OK(hipMemcpy(h.data(), s->prof, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
+    std::vector<unsigned long long> h;
+    if (read_profile("kp_sim_phase_cycles_env", s, out, h)) return -1;
     for (size_t i = 0; i < h.size(); i++) out[i] = (double)h[i];
     return 0;
 }
 
 int kp_sim_timing_reset(kp_sim* s) {
     if (!s) return fail("kp_sim_timing_reset: null argument");
-    s->ring_used = 0; s->ring_on = true;
+    s->tm.ring_used = 0; s->tm.ring_on = true;
     return 0;
 }
 
 double kp_sim_timing_mean_seconds(kp_sim* s, int* n_launches) {
     if (n_launches) *n_launches = 0;
-    if (!s || s->ring_used == 0) return -1.0;
+    if (!s || s->tm.ring_used == 0) return -1.0;
+    const Timing& tm = s->tm;
     if (hipStreamSynchronize(s->stream) != hipSuccess) return -1.0;
     double tot = 0.0;
-    for (int i = 0; i < s->ring_used; i++) {
+    for (int i = 0; i < tm.ring_used; i++) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, s->ring[2 * i], s->ring[2 * i + 1]) != hipSuccess) return -1.0;
+        if (hipEventElapsedTime(&ms, tm.ring[2 * i], tm.ring[2 * i + 1]) != hipSuccess) return -1.0;
         tot += ms;
     }
-    if (n_launches) *n_launches = s->ring_used;
-    return tot * 1e-3 / s->ring_used;
+    if (n_launches) *n_launches = tm.ring_used;
+    return tot * 1e-3 / tm.ring_used;
 }
 
 }  // extern "C"

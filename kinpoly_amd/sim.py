@@ -27,21 +27,6 @@ FIELDS = dict(qpos=0, qvel=1, xpos=2, xquat=3, xipos=4, bquat=5, head=6, target_
 
 _lib = None
 
-# every symbol include/kinpoly_sim.h declares (tests check the .so exports all of them)
-ABI_SYMBOLS = [
-    "kp_model_load", "kp_model_free", "kp_model_set_option", "kp_model_get_option", "kp_sim_create", "kp_sim_destroy",
-    "kp_sim_n_envs", "kp_sim_set_state", "kp_sim_set_target", "kp_sim_step_ctrl", "kp_sim_step_kin", "kp_sim_obs_cc",
-    "kp_field_dim", "kp_sim_get", "kp_sim_diag", "kp_sim_last_step_seconds", "kp_last_error", "kp_version",
-    "kp_sim_step_begin", "kp_sim_obs_ar", "kp_sim_term_reward", "kp_gae", "kp_sim_set_full_state", "kp_sim_fk",
-    "kp_sim_timing_reset", "kp_sim_timing_mean_seconds", "kp_sim_phase_cycles", "kp_sim_set_objects", "kp_sim_set_obj_state",
-    "kp_sim_launch_cost", "kp_job_schedule", "kp_sim_fk_backward", "kp_sim_set_stream", "kp_sim_status_device", "kp_sim_mass_matrix",
-    "kp_sim_contacts", "kp_gae_bootstrap", "kp_gru_gates_forward", "kp_gru_gates_backward", "kp_sim_phase_cycles_env",
-    "kp_sim_post_step", "kp_sim_reset_rows", "kp_mcp_compose", "kp_sim_step_head", "kp_model_compile", "kp_model_load_xml",
-    "kp_mcp_tail", "kp_gru_cell_step", "kp_kin_advance", "kp_pool_advance", "kp_rollout_record_pre", "kp_rollout_record_post", "kp_rollout_record_pre_w", "kp_rollout_record_post_w", "kp_sim_ar_obs_dim", "kp_sim_field_device",
-    "kp_sim_lean_state", "kp_sim_pose_contacts", "kp_sim_obs_cc_ex", "kp_sim_cc_obs_dim",
-    "kp_takes_create", "kp_takes_destroy", "kp_takes_table", "kp_takes_info", "kp_sim_step_ctrl_base", "kp_sim_uhc_track", "kp_sim_uhc_assign",
-]
-
 
 class KpCtx(C.Structure):
     """mirror of kp_ctx (include/kinpoly_sim.h)"""
@@ -88,6 +73,47 @@ class KinPolyNativeError(RuntimeError):
     pass
 
 
+_V, _I, _F, _D, _S = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_char_p      # handles and device / host arrays are all void*
+_PI = C.POINTER(C.c_int)
+_CTX, _RW, _PRE, _POST, _UST, _UCFG = (C.POINTER(k) for k in (KpCtx, KpRewardCfg, KpRecordPre, KpRecordPost, KpUhcState, KpUhcCfg))
+# every symbol include/kinpoly_sim.h declares: symbol -> (restype, argtypes).  load_library types them all from here, and tests check the header against it.
+_SIGNATURES = {
+    "kp_last_error": (_S, []), "kp_version": (_S, []),
+    "kp_model_load": (_V, [_S]), "kp_model_compile": (_I, [_S, _S, _S]), "kp_model_load_xml": (_V, [_S, _S]), "kp_model_free": (None, [_V]),
+    "kp_model_set_option": (_I, [_V, _S, _D]), "kp_model_get_option": (_D, [_V, _S]),
+    "kp_sim_create": (_V, [_V, _I, _I, _V]), "kp_sim_destroy": (None, [_V]), "kp_sim_n_envs": (_I, [_V]), "kp_sim_set_stream": (_I, [_V, _V]),
+    "kp_sim_status_device": (_V, [_V]), "kp_sim_contacts": (_I, [_V, _V]), "kp_sim_mass_matrix": (_I, [_V, _V, _V]),
+    "kp_sim_set_state": (_I, [_V, _V, _V, _V]), "kp_sim_set_full_state": (_I, [_V, _V, _V, _V, _V, _V]), "kp_sim_set_target": (_I, [_V, _V, _V]),
+    "kp_sim_set_objects": (_I, [_V, _V, _V]), "kp_sim_set_obj_state": (_I, [_V, _V, _V, _V]),
+    "kp_sim_fk": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]), "kp_sim_fk_backward": (_I, [_V, _I, _V, _V, _V, _V, _V]),
+    "kp_sim_pose_contacts": (_I, [_V, _I, _V, _V, _V, _F, _V, _V, _V]),
+    "kp_sim_step_ctrl": (_I, [_V, _V, _I, _V]), "kp_sim_step_ctrl_base": (_I, [_V, _V, _I, _V, _V]), "kp_sim_step_kin": (_I, [_V, _V, _V]),
+    "kp_sim_step_head": (_I, [_V, _V]), "kp_sim_step_begin": (_I, [_V]),
+    "kp_sim_obs_cc": (_I, [_V, _V, _V, _V, _F]), "kp_sim_obs_cc_ex": (_I, [_V, _V, _V, _V, _F, _V]), "kp_sim_cc_obs_dim": (_I, [_V]),
+    "kp_sim_obs_ar": (_I, [_V, _CTX, _V]), "kp_sim_ar_obs_dim": (_I, [_V]),
+    "kp_field_dim": (_I, [_I]), "kp_sim_get": (_I, [_V, _I, _V]), "kp_sim_field_device": (_V, [_V, _I]),
+    "kp_sim_term_reward": (_I, [_V, _CTX, _RW, _V, _V, _V, _V]),
+    "kp_sim_post_step": (_I, [_V, _CTX, _RW, _V, _V, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    "kp_sim_reset_rows": (_I, [_V, _V, _V, _V, _V, _V, _I, _V, _I, _V, _V, _V]),
+    "kp_sim_diag": (_I, [_V, _V]), "kp_sim_lean_state": (_I, [_V, _V]), "kp_sim_launch_cost": (_I, [_V, _V]), "kp_job_schedule": (_I, [_I, _I, _I, _PI]),
+    "kp_sim_last_step_seconds": (_D, [_V]), "kp_sim_timing_reset": (_I, [_V]), "kp_sim_timing_mean_seconds": (_D, [_V, _PI]),
+    "kp_sim_phase_cycles": (_I, [_V, C.POINTER(_D)]), "kp_sim_phase_cycles_env": (_I, [_V, _V]),
+    "kp_takes_create": (_V, [_V, _V, _I, _V, _I, _D]), "kp_takes_destroy": (None, [_V]),
+    "kp_takes_table": (_I, [_V, _S, C.POINTER(_V), _PI, _PI]), "kp_takes_info": (_I, [_V, _PI, _PI, _V]),
+    "kp_sim_uhc_track": (_I, [_V, _V, _UST, _UCFG, _V, _V, _V, _V, _V, _V, _V, _V]), "kp_sim_uhc_assign": (_I, [_V, _V, _UST, _UCFG, _V, _V, _V, _I, _V]),
+    # stand-alone kernels (no kp_sim): sizes, device arrays, ..., stream
+    "kp_pool_advance": (_I, [_I, _I, _V, _V, _V, _V, _V]),
+    "kp_rollout_record_pre": (_I, [_PRE, _V]), "kp_rollout_record_post": (_I, [_POST, _V]),
+    "kp_rollout_record_pre_w": (_I, [_PRE, _I, _V]), "kp_rollout_record_post_w": (_I, [_POST, _I, _V]),
+    "kp_mcp_compose": (_I, [_I, _I, _I, _V, _V, _V, _I, _V, _V, _V]),
+    "kp_mcp_tail": (_I, [_I, _I, _I, _I, _V, _V, _V, _I, _V, _V, _V, _I, _V, _V, _V]),
+    "kp_kin_advance": (_I, [_I, _V, _V, _F, _V, _V, _V]), "kp_gru_cell_step": (_I, [_I, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    "kp_gae": (_I, [_I, _I, _V, _V, _V, _F, _F, _V, _V, _V]), "kp_gae_bootstrap": (_I, [_I, _I, _V, _V, _V, _V, _F, _F, _V, _V, _V]),
+    "kp_gru_gates_forward": (_I, [_I, _I, _V, _V, _V, _V, _V, _V, _V]), "kp_gru_gates_backward": (_I, [_I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+}
+ABI_SYMBOLS = list(_SIGNATURES)
+
+
 def load_library(path: str | None = None):
     """dlopen the in-tree extension (never builds implicitly on a GPU box: the .so must be there)."""
     global _lib
@@ -98,74 +124,9 @@ def load_library(path: str | None = None):
         raise KinPolyNativeError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                                  "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     L = C.CDLL(path)
-    P, F, U8 = C.c_void_p, C.c_void_p, C.c_void_p
-    L.kp_model_load.restype = P; L.kp_model_load.argtypes = [C.c_char_p]
-    L.kp_model_compile.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p]; L.kp_model_compile.restype = C.c_int
-    L.kp_model_load_xml.restype = P; L.kp_model_load_xml.argtypes = [C.c_char_p, C.c_char_p]
-    L.kp_model_free.argtypes = [P]
-    L.kp_model_set_option.argtypes = [P, C.c_char_p, C.c_double]; L.kp_model_set_option.restype = C.c_int
-    L.kp_model_get_option.argtypes = [P, C.c_char_p]; L.kp_model_get_option.restype = C.c_double
-    L.kp_sim_create.restype = P; L.kp_sim_create.argtypes = [P, C.c_int, C.c_int, C.c_void_p]
-    L.kp_sim_destroy.argtypes = [P]
-    L.kp_sim_n_envs.argtypes = [P]; L.kp_sim_n_envs.restype = C.c_int
-    L.kp_sim_set_state.argtypes = [P, F, F, U8]; L.kp_sim_set_state.restype = C.c_int
-    L.kp_sim_set_target.argtypes = [P, F, U8]; L.kp_sim_set_target.restype = C.c_int
-    L.kp_sim_step_ctrl.argtypes = [P, F, C.c_int, U8]; L.kp_sim_step_ctrl.restype = C.c_int
-    L.kp_sim_step_kin.argtypes = [P, F, F]; L.kp_sim_step_kin.restype = C.c_int
-    L.kp_sim_step_head.argtypes = [P, F]; L.kp_sim_step_head.restype = C.c_int
-    L.kp_sim_obs_cc.argtypes = [P, F, F, F, C.c_float]; L.kp_sim_obs_cc.restype = C.c_int
-    L.kp_sim_obs_cc_ex.argtypes = [P, F, F, F, C.c_float, F]; L.kp_sim_obs_cc_ex.restype = C.c_int
-    L.kp_sim_cc_obs_dim.argtypes = [P]; L.kp_sim_cc_obs_dim.restype = C.c_int
-    L.kp_field_dim.argtypes = [C.c_int]; L.kp_field_dim.restype = C.c_int
-    L.kp_sim_get.argtypes = [P, C.c_int, F]; L.kp_sim_get.restype = C.c_int
-    L.kp_sim_diag.argtypes = [P, C.c_void_p]; L.kp_sim_diag.restype = C.c_int
-    L.kp_sim_last_step_seconds.argtypes = [P]; L.kp_sim_last_step_seconds.restype = C.c_double
-    L.kp_sim_step_begin.argtypes = [P]; L.kp_sim_step_begin.restype = C.c_int
-    L.kp_sim_obs_ar.argtypes = [P, C.POINTER(KpCtx), F]; L.kp_sim_obs_ar.restype = C.c_int
-    L.kp_sim_ar_obs_dim.argtypes = [P]; L.kp_sim_ar_obs_dim.restype = C.c_int
-    L.kp_sim_term_reward.argtypes = [P, C.POINTER(KpCtx), C.POINTER(KpRewardCfg), F, F, U8, F]; L.kp_sim_term_reward.restype = C.c_int
-    L.kp_sim_post_step.argtypes = [P, C.POINTER(KpCtx), C.POINTER(KpRewardCfg), C.c_void_p, C.c_void_p, C.c_int, F, F, U8, F, U8, U8, F, C.c_void_p, F]; L.kp_sim_post_step.restype = C.c_int
-    L.kp_sim_reset_rows.argtypes = [P, F, F, C.c_void_p, U8, C.c_void_p, C.c_int, F, C.c_int, F, F, F]; L.kp_sim_reset_rows.restype = C.c_int
-    L.kp_pool_advance.argtypes = [C.c_int, C.c_int, U8, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]; L.kp_pool_advance.restype = C.c_int
-    L.kp_sim_field_device.argtypes = [P, C.c_int]; L.kp_sim_field_device.restype = C.c_void_p
-    L.kp_rollout_record_pre.argtypes = [C.POINTER(KpRecordPre), C.c_void_p]; L.kp_rollout_record_pre.restype = C.c_int
-    L.kp_rollout_record_post.argtypes = [C.POINTER(KpRecordPost), C.c_void_p]; L.kp_rollout_record_post.restype = C.c_int
-    L.kp_rollout_record_pre_w.argtypes = [C.POINTER(KpRecordPre), C.c_int, C.c_void_p]; L.kp_rollout_record_pre_w.restype = C.c_int
-    L.kp_rollout_record_post_w.argtypes = [C.POINTER(KpRecordPost), C.c_int, C.c_void_p]; L.kp_rollout_record_post_w.restype = C.c_int
-    L.kp_mcp_tail.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, F, F, F, C.c_int, F, F, F, C.c_int, F, F, C.c_void_p]; L.kp_mcp_tail.restype = C.c_int
-    L.kp_kin_advance.argtypes = [C.c_int, F, F, C.c_float, F, F, C.c_void_p]; L.kp_kin_advance.restype = C.c_int
-    L.kp_gru_cell_step.argtypes = [C.c_int, C.c_int, C.c_int, F, F, F, F, F, F, F, F, C.c_void_p]; L.kp_gru_cell_step.restype = C.c_int
-    L.kp_mcp_compose.argtypes = [C.c_int, C.c_int, C.c_int, F, F, F, C.c_int, F, F, C.c_void_p]; L.kp_mcp_compose.restype = C.c_int
-    L.kp_gae.argtypes = [C.c_int, C.c_int, F, F, F, C.c_float, C.c_float, F, F, C.c_void_p]; L.kp_gae.restype = C.c_int
-    L.kp_gae_bootstrap.argtypes = [C.c_int, C.c_int, F, F, F, F, C.c_float, C.c_float, F, F, C.c_void_p]; L.kp_gae_bootstrap.restype = C.c_int
-    L.kp_gru_gates_forward.argtypes = [C.c_int, C.c_int, F, F, F, F, F, F, C.c_void_p]; L.kp_gru_gates_forward.restype = C.c_int
-    L.kp_gru_gates_backward.argtypes = [C.c_int, C.c_int, F, F, F, F, F, F, F, F, F, C.c_void_p]; L.kp_gru_gates_backward.restype = C.c_int
-    L.kp_sim_set_full_state.argtypes = [P, F, F, F, F, U8]; L.kp_sim_set_full_state.restype = C.c_int
-    L.kp_sim_timing_reset.argtypes = [P]; L.kp_sim_timing_reset.restype = C.c_int
-    L.kp_sim_timing_mean_seconds.argtypes = [P, C.POINTER(C.c_int)]; L.kp_sim_timing_mean_seconds.restype = C.c_double
-    L.kp_sim_phase_cycles.argtypes = [P, C.POINTER(C.c_double)]; L.kp_sim_phase_cycles.restype = C.c_int
-    L.kp_sim_phase_cycles_env.argtypes = [P, C.c_void_p]; L.kp_sim_phase_cycles_env.restype = C.c_int
-    L.kp_job_schedule.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]; L.kp_job_schedule.restype = C.c_int
-    L.kp_sim_launch_cost.argtypes = [P, C.c_void_p]; L.kp_sim_launch_cost.restype = C.c_int
-    L.kp_sim_lean_state.argtypes = [P, C.c_void_p]; L.kp_sim_lean_state.restype = C.c_int
-    L.kp_sim_set_objects.argtypes = [P, F, U8]; L.kp_sim_set_objects.restype = C.c_int
-    L.kp_sim_set_obj_state.argtypes = [P, F, F, U8]; L.kp_sim_set_obj_state.restype = C.c_int
-    L.kp_sim_fk.argtypes = [P, C.c_int, F, F, F, F, F, F]; L.kp_sim_fk.restype = C.c_int
-    L.kp_sim_fk_backward.argtypes = [P, C.c_int, F, F, F, F, F]; L.kp_sim_fk_backward.restype = C.c_int
-    L.kp_sim_pose_contacts.argtypes = [P, C.c_int, F, F, F, C.c_float, F, F, F]; L.kp_sim_pose_contacts.restype = C.c_int
-    L.kp_sim_set_stream.argtypes = [P, C.c_void_p]; L.kp_sim_set_stream.restype = C.c_int
-    L.kp_sim_status_device.argtypes = [P]; L.kp_sim_status_device.restype = C.c_void_p
-    L.kp_sim_mass_matrix.argtypes = [P, F, F]; L.kp_sim_mass_matrix.restype = C.c_int
-    L.kp_sim_contacts.argtypes = [P, C.c_void_p]; L.kp_sim_contacts.restype = C.c_int
-    L.kp_takes_create.restype = P; L.kp_takes_create.argtypes = [P, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double]
-    L.kp_takes_destroy.argtypes = [P]
-    L.kp_takes_table.argtypes = [P, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int)]; L.kp_takes_table.restype = C.c_int
-    L.kp_takes_info.argtypes = [P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]; L.kp_takes_info.restype = C.c_int
-    L.kp_sim_step_ctrl_base.argtypes = [P, F, C.c_int, U8, F]; L.kp_sim_step_ctrl_base.restype = C.c_int
-    L.kp_sim_uhc_track.argtypes = [P, P, C.POINTER(KpUhcState), C.POINTER(KpUhcCfg), F, F, F, F, U8, U8, U8, F]; L.kp_sim_uhc_track.restype = C.c_int
-    L.kp_sim_uhc_assign.argtypes = [P, P, C.POINTER(KpUhcState), C.POINTER(KpUhcCfg), U8, C.c_void_p, C.c_void_p, C.c_int, F]; L.kp_sim_uhc_assign.restype = C.c_int
-    L.kp_last_error.restype = C.c_char_p
-    L.kp_version.restype = C.c_char_p
+    for sym, (restype, argtypes) in _SIGNATURES.items():
+        f = getattr(L, sym)
+        f.restype, f.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -207,20 +168,31 @@ class KpModel:
             pass
 
 
-def _ptr(t: torch.Tensor | None, n, dim, dtype=torch.float32):
+def _dev(name, t: torch.Tensor | None, shape, dtype=torch.float32):
+    """Device pointer of t (None -> NULL) after THE check every entry point's arrays pass: a contiguous `dtype` device tensor of `shape`, where a None
+    in `shape` stands for any size (the row count of a table) and shape = None for any shape.  The kernels index with fixed row widths: anything else would be read out of bounds."""
     if t is None:
         return None
-    if not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != (n, dim):
-        raise ValueError(f"expected contiguous {dtype} device tensor of shape ({n}, {dim}), got {t.dtype} {tuple(t.shape)} on {t.device}")
+    fits = shape is None or (t.dim() == len(shape) and all(w is None or w == d for w, d in zip(shape, t.shape)))
+    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and fits):
+        want = "any shape" if shape is None else "shape (" + ", ".join("*" if w is None else str(w) for w in shape) + ")"
+        raise ValueError(f"{name}: expected a contiguous {dtype} device tensor of {want}, got {t.dtype} {tuple(t.shape)} "
+                         f"{'contiguous' if t.is_contiguous() else 'strided'} on {t.device}")
     return C.c_void_p(t.data_ptr())
 
 
-def _mask_ptr(m: torch.Tensor | None, n):
-    if m is None:
-        return None
-    if not m.is_cuda or m.dtype != torch.uint8 or tuple(m.shape) != (n,) or not m.is_contiguous():
-        raise ValueError("env_mask must be a contiguous uint8 device tensor of shape (n_envs,)")
-    return C.c_void_p(m.data_ptr())
+def _ptr(t, n, dim):
+    return _dev("tensor", t, (n, dim))
+
+
+def _mask_ptr(m, n):
+    return _dev("env_mask", m, (n,), torch.uint8)
+
+
+def _device_view(ptr, shape, device, typestr="<f4") -> torch.Tensor:
+    """zero-copy tensor over device memory the library owns (valid for the life of the handle that returned ptr)"""
+    iface = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 3, "strides": None}
+    return torch.as_tensor(type("_KpDeviceView", (), {"__cuda_array_interface__": iface})(), device=device)
 
 
 class KpSim:
@@ -254,20 +226,14 @@ class KpSim:
     def status_tensor(self) -> torch.Tensor:
         """int32 [4] device view of the launch status words (kp_sim_status_device): [2] != 0 = a queue launch stalled."""
         if getattr(self, "_status", None) is None:
-            ptr = self.L.kp_sim_status_device(self.h)
-            iface = {"shape": (4,), "typestr": "<i4", "data": (int(ptr), False), "version": 3, "strides": None}
-            holder = type("_KpStatus", (), {"__cuda_array_interface__": iface})()
-            self._status = torch.as_tensor(holder, device=self.device)
+            self._status = _device_view(self.L.kp_sim_status_device(self.h), (4,), self.device, "<i4")
         return self._status
 
     def queue_counters(self) -> dict:
         """Counters of the last job-queue launch (host read): jobs claimed / published, jobs a wave kept instead of queueing, and the jobs the lean
         layout handed to kp_step_overflow_kernel (more contacts than EnvLdsLean::MAXCON)."""
         if getattr(self, "_qctr", None) is None:
-            ptr = self.L.kp_sim_status_device(self.h)
-            iface = {"shape": (128,), "typestr": "<i4", "data": (int(ptr), False), "version": 3, "strides": None}
-            holder = type("_KpQueueCounters", (), {"__cuda_array_interface__": iface})()
-            self._qctr = torch.as_tensor(holder, device=self.device)
+            self._qctr = _device_view(self.L.kp_sim_status_device(self.h), (128,), self.device, "<i4")
         c = self._qctr.cpu().numpy()
         st = (C.c_int32 * 3)()
         _check(self.L.kp_sim_lean_state(self.h, C.cast(st, C.c_void_p)), "kp_sim_lean_state")
@@ -352,11 +318,7 @@ class KpSim:
         """The UHC observation of the handle's layout (kp_sim_obs_cc_ex): [N, cc_obs_dim]; 784 = get_full_obs_v1 for a default model.
         phase: float [N] device tensor cur_t / expert len, required exactly when the layout has obs_v 0's phase slot."""
         out = self._new(self.cc_obs_dim) if out is None else out
-        for z in (zf_mean, zf_std):
-            if z is not None and (not z.is_cuda or z.dtype != torch.float32 or not z.is_contiguous() or z.numel() != self.cc_obs_dim):
-                raise ValueError(f"ZFilter mean / std must be contiguous float32 device tensors of {self.cc_obs_dim} elements")
-        zm = None if zf_mean is None else C.c_void_p(zf_mean.data_ptr())
-        zs = None if zf_std is None else C.c_void_p(zf_std.data_ptr())
+        zm, zs = (_dev("ZFilter mean / std", z if z is None or not z.is_contiguous() else z.view(-1), (self.cc_obs_dim,)) for z in (zf_mean, zf_std))
         ph = None if phase is None else _ptr(phase.view(self.n, 1), self.n, 1)
         _check(self.L.kp_sim_obs_cc_ex(self.h, _ptr(out, self.n, self.cc_obs_dim), zm, zs, float(clip), ph), "kp_sim_obs_cc_ex")
         return out
@@ -378,9 +340,7 @@ class KpSim:
             ptr = self.L.kp_sim_field_device(self.h, fid)
             if not ptr:
                 raise KinPolyNativeError(f"kp_sim_field_device: '{field}' is not a stored field")
-            dim = self.L.kp_field_dim(fid)
-            iface = {"shape": (self.n, dim), "typestr": "<f4", "data": (int(ptr), False), "version": 3, "strides": None}
-            cache[field] = torch.as_tensor(type("_KpField", (), {"__cuda_array_interface__": iface})(), device=self.device)
+            cache[field] = _device_view(ptr, (self.n, self.L.kp_field_dim(fid)), self.device)
         return cache[field]
 
     def set_full_state(self, qpos, qvel, qpos_d, qvel_d, env_mask=None):
@@ -389,33 +349,28 @@ class KpSim:
 
     def fk(self, qpos_rows: torch.Tensor):
         """qpos_fk_batch on [R,76] rows -> dict(qpos, wbpos, wbquat, bquat, body_com) of device tensors."""
+        rows = _dev("fk: qpos_rows", qpos_rows, (None, NQ))
         R = qpos_rows.shape[0]
-        if not qpos_rows.is_cuda or qpos_rows.dtype != torch.float32 or not qpos_rows.is_contiguous() or qpos_rows.shape[1] != NQ:
-            raise ValueError("fk: expected contiguous float32 device tensor [R,76]")
         out = {k: torch.empty((R, d), dtype=torch.float32, device=self.device) for k, d in
                (("qpos", 76), ("wbpos", 72), ("wbquat", 96), ("bquat", 96), ("body_com", 72))}
-        _check(self.L.kp_sim_fk(self.h, R, C.c_void_p(qpos_rows.data_ptr()), *[C.c_void_p(out[k].data_ptr()) for k in
-                                ("qpos", "wbpos", "wbquat", "bquat", "body_com")]), "kp_sim_fk")
+        _check(self.L.kp_sim_fk(self.h, R, rows, *[C.c_void_p(o.data_ptr()) for o in out.values()]), "kp_sim_fk")
         return out
 
     def fk_backward(self, qpos_rows, wbpos, wbquat, grad_wbpos):
         """(d wbpos / d qpos)^T grad_wbpos for the rows of an fk() call -> [R,76]."""
         R = qpos_rows.shape[0]
-        for t, d in ((qpos_rows, NQ), (wbpos, 72), (wbquat, 96), (grad_wbpos, 72)):
-            if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (R, d):
-                raise ValueError("fk_backward: expected contiguous float32 device tensors [R,76], [R,72], [R,96], [R,72]")
+        ins = [_dev("fk_backward: " + k, t, (R, d)) for k, t, d in (("qpos_rows", qpos_rows, NQ), ("wbpos", wbpos, 72), ("wbquat", wbquat, 96), ("grad_wbpos", grad_wbpos, 72))]
         out = torch.empty((R, NQ), dtype=torch.float32, device=self.device)
-        _check(self.L.kp_sim_fk_backward(self.h, R, *[C.c_void_p(t.data_ptr()) for t in (qpos_rows, wbpos, wbquat, grad_wbpos, out)]), "kp_sim_fk_backward")
+        _check(self.L.kp_sim_fk_backward(self.h, R, *ins, C.c_void_p(out.data_ptr())), "kp_sim_fk_backward")
         return out
 
     def pose_contacts(self, qpos_rows: torch.Tensor, obj_qpos: torch.Tensor | None = None, pen_margin: float = 0.005) -> dict:
         """compute_physcis_metris' per-frame contact walk (kp_sim_pose_contacts) on [R,76] rows (+ their [R,35] object blocks, or None: floor
         only) -> dict of device tensors: pen [R] (sum of max(0, -dist - pen_margin) over the hull - floor / hull - object contacts), ncon [R]
         int32, hits [R, n_obj_geoms] uint32 (bit b = hull b touches object geom g), xpos [R,72], xquat [R,96] (the rows' body poses, fk())."""
-        if qpos_rows.dim() != 2 or not qpos_rows.is_cuda or qpos_rows.dtype != torch.float32 or not qpos_rows.is_contiguous() or qpos_rows.shape[1] != NQ:
-            raise ValueError("pose_contacts: expected contiguous float32 device tensor [R,76]")
+        _dev("pose_contacts: qpos_rows", qpos_rows, (None, NQ))
         R = qpos_rows.shape[0]
-        op = _ptr(obj_qpos, R, 35)
+        op = _dev("pose_contacts: obj_qpos", obj_qpos, (R, 35))
         n_og = int(self.model.get_option("n_obj_geoms"))
         out = {"pen": torch.empty(R, dtype=torch.float32, device=self.device), "ncon": torch.empty(R, dtype=torch.int32, device=self.device),
                "hits": torch.empty((R, n_og), dtype=torch.int32, device=self.device).view(torch.uint32)}
@@ -435,14 +390,11 @@ class KpSim:
     def make_ctx(self, T, head_pose, head_vels, obj_rel, action_one_hot, gt_bquat, gt_wbpos, cur_t, obj_qpos=None, row=None) -> "KpCtx":
         n = self.n
         R = head_pose.shape[0] if row is not None else n        # context rows (>= n_envs with the row indirection)
-        if row is not None and (row.dtype != torch.int32 or tuple(row.shape) != (n,) or not row.is_cuda):
-            raise ValueError("row must be an int32 device tensor [n_envs]")
-        for t, shp in ((head_pose, (R, T, 7)), (head_vels, (R, T, 6)), (obj_rel, (R, T, 7)), (action_one_hot, (R, 4)),
-                       (gt_bquat, (R, T, 96)), (gt_wbpos, (R, T, 72))):
-            if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shp:
-                raise ValueError(f"context tensor must be contiguous float32 on device with shape {shp}, got {tuple(t.shape)}")
-        if cur_t.dtype != torch.int32 or tuple(cur_t.shape) != (n,) or not cur_t.is_cuda:
-            raise ValueError("cur_t must be an int32 device tensor [n_envs]")
+        _dev("row", row, (n,), torch.int32)
+        for k, t, shp in (("head_pose", head_pose, (R, T, 7)), ("head_vels", head_vels, (R, T, 6)), ("obj_rel", obj_rel, (R, T, 7)),
+                          ("action_one_hot", action_one_hot, (R, 4)), ("gt_bquat", gt_bquat, (R, T, 96)), ("gt_wbpos", gt_wbpos, (R, T, 72))):
+            _dev("context tensor " + k, t, shp)
+        _dev("cur_t", cur_t, (n,), torch.int32)
         ctx = KpCtx(int(T), head_pose.data_ptr(), head_vels.data_ptr(), obj_rel.data_ptr(), action_one_hot.data_ptr(), gt_bquat.data_ptr(),
                     gt_wbpos.data_ptr(), None if obj_qpos is None else obj_qpos.data_ptr(), cur_t.data_ptr(), None if row is None else row.data_ptr())
         ctx._keep = (head_pose, head_vels, obj_rel, action_one_hot, gt_bquat, gt_wbpos, obj_qpos, cur_t, row)
@@ -475,19 +427,10 @@ class KpSim:
         aux_rows [N, C]: caller-owned per-env rows zeroed for the same envs (the policy's GRU state).  row_obj_qpos [R, 35] (+ row_one_hot [R, 4],
         obj7 [N, 7]): the object block of reset_model from the env's context row, and get_obj_qpos(action_one_hot) of it."""
         R = init_qpos.shape[0]
-        for t, d in ((row_obj_qpos, 35), (row_one_hot, 4)):
-            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (R, d)):
-                raise ValueError(f"object row tables must be contiguous float32 device tensors [R, {d}]")
-        if aux_rows is not None and not (aux_rows.is_cuda and aux_rows.dtype == torch.float32 and aux_rows.is_contiguous() and aux_rows.dim() == 2 and aux_rows.shape[0] == self.n):
-            raise ValueError("aux_rows must be a contiguous float32 device tensor [N, C]")
-        for t, d in ((init_qpos, NQ), (init_qvel, NV)):
-            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == d):
-                raise ValueError("init rows must be contiguous float32 device tensors [R, dim]")
-        _check(self.L.kp_sim_reset_rows(self.h, C.c_void_p(init_qpos.data_ptr()), C.c_void_p(init_qvel.data_ptr()), None if row is None else C.c_void_p(row.data_ptr()),
+        _check(self.L.kp_sim_reset_rows(self.h, _dev("init_qpos", init_qpos, (None, NQ)), _dev("init_qvel", init_qvel, (None, NV)), None if row is None else C.c_void_p(row.data_ptr()),
                                         _mask_ptr(env_mask, self.n), None if cur_t is None else C.c_void_p(cur_t.data_ptr()), int(bool(set_target)),
-                                        None if aux_rows is None else C.c_void_p(aux_rows.data_ptr()), 0 if aux_rows is None else int(aux_rows.shape[1]),
-                                        None if row_obj_qpos is None else C.c_void_p(row_obj_qpos.data_ptr()), None if row_one_hot is None else C.c_void_p(row_one_hot.data_ptr()),
-                                        _ptr(obj7, self.n, 7)), "kp_sim_reset_rows")
+                                        _dev("aux_rows", aux_rows, (self.n, None)), 0 if aux_rows is None else int(aux_rows.shape[1]),
+                                        _dev("row_obj_qpos", row_obj_qpos, (R, 35)), _dev("row_one_hot", row_one_hot, (R, 4)), _ptr(obj7, self.n, 7)), "kp_sim_reset_rows")
 
     def diag(self) -> np.ndarray:
         out = np.zeros((self.n, 4), np.int32)
@@ -509,14 +452,12 @@ class KpSim:
 
     def phase_cycles_env(self):
         """per-env shader-clock cycles of the last control step's phases, numpy [N, 8] (KP_PROFILE=1)."""
-        import numpy as np
         out = np.zeros((self.n, 8), np.float64)
         _check(self.L.kp_sim_phase_cycles_env(self.h, out.ctypes.data_as(C.c_void_p)), "kp_sim_phase_cycles_env")
         return out
 
     def launch_cost(self):
         """shader-clock cycles every env took in the last control-step launch (numpy uint64 [N])."""
-        import numpy as np
         out = np.zeros(self.n, np.uint32)
         _check(self.L.kp_sim_launch_cost(self.h, out.ctypes.data_as(C.c_void_p)), "kp_sim_launch_cost")
         return out.astype(np.uint64) << 10
@@ -525,6 +466,7 @@ class KpSim:
         return self.L.kp_sim_last_step_seconds(self.h)
 
 
+# the names kp_takes_table answers (kp_sim.hip; tests/test_gpu_uhc_takes.py asks the library for each of them)
 TAKE_TABLES = ("qpos", "qpos_fk", "wbpos", "wbquat", "bquat", "body_com", "com", "head_pose", "ee_wpos", "ee_pos", "rq_rmh", "qvel", "rlinv", "rangv",
                "rlinv_local", "bangvel", "height_lb", "head_height_lb")
 
@@ -562,8 +504,7 @@ class KpTakes:
         if name not in self._tabs:
             p, rows, w = C.c_void_p(0), C.c_int(0), C.c_int(0)
             _check(self.L.kp_takes_table(self.h, name.encode(), C.byref(p), C.byref(rows), C.byref(w)), "kp_takes_table")
-            iface = {"shape": (rows.value, w.value), "typestr": "<f4", "data": (int(p.value), False), "version": 3, "strides": None}
-            self._tabs[name] = torch.as_tensor(type("_KpTable", (), {"__cuda_array_interface__": iface})(), device=self.device)
+            self._tabs[name] = _device_view(p.value, (rows.value, w.value), self.device)
         return self._tabs[name]
 
     def take(self, k: int) -> dict:
@@ -591,27 +532,15 @@ def job_schedule(n_substeps: int, substeps_per_job: int = 4, taper: int = 1) -> 
     return list(out[:n])
 
 
-def _dptr(t, dtype=None, name="tensor"):
-    """device pointer of a contiguous tensor (None -> NULL); bool tensors are passed as their uint8 storage"""
-    if t is None:
-        return None
-    if t.dtype == torch.bool:
-        t = t.view(torch.uint8)
-    if not (t.is_cuda and t.is_contiguous()) or (dtype is not None and t.dtype != dtype):
-        raise ValueError(f"{name}: expected a contiguous {dtype} device tensor, got {t.dtype} {'contiguous' if t.is_contiguous() else 'strided'} on {t.device}")
-    return t.data_ptr()
-
-
 def _obs_width(obs_dim):
     if obs_dim not in (AR_OBS_DIM, AR_OBS_DIM_NO_ACTION):
         raise ValueError(f"obs_dim must be {AR_OBS_DIM} or {AR_OBS_DIM_NO_ACTION} (without the action one-hot), got {obs_dim}")
     return int(obs_dim)
 
 
-def _want(name, x, *shape):
-    """the record kernels index their buffers with fixed row widths (kp_rollout_kernels.hpp): a tensor of another shape would be read / written out of bounds"""
-    if x is not None and tuple(x.shape) != tuple(shape):
-        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(x.shape)}")
+def _u8(t):
+    """bool tensors are passed as their uint8 storage"""
+    return t.view(torch.uint8) if t is not None and t.dtype == torch.bool else t
 
 
 def record_pre(t: int, T: int, obs=None, fresh=None, qpos=None, ctx_qpos=None, row=None, cur_t=None, row_len=None, row_meta=None,
@@ -619,20 +548,16 @@ def record_pre(t: int, T: int, obs=None, fresh=None, qpos=None, ctx_qpos=None, r
     """kp_rollout_record_pre: the before-the-step half of the sampler's per-step record, one launch (see include/kinpoly_sim.h).
     obs_dim: the width of obs / states (the env's KpSim.obs_ar_dim)."""
     L = load_library()
-    obs_dim = _obs_width(obs_dim)
+    w = _obs_width(obs_dim)
     first = next(x for x in (obs, qpos, fresh) if x is not None)
-    f32, i32, u8 = torch.float32, torch.int32, torch.uint8
+    i32, u8 = torch.int32, torch.uint8
     n = first.shape[0]
-    _want("obs", obs, n, obs_dim); _want("fresh", fresh, n); _want("qpos", qpos, n, 76); _want("row", row, n); _want("cur_t", cur_t, n)
-    _want("states", states, n, T, obs_dim); _want("episode_start", episode_start, n, T); _want("curr_qpos", curr_qpos, n, T, 76)
-    _want("gt_target_qpos", gt_target_qpos, n, T, 76); _want("meta", meta, n, T, 2)
-    if ctx_qpos is not None and (ctx_qpos.dim() != 3 or ctx_qpos.shape[2] != 76):
-        raise ValueError(f"ctx_qpos: expected [R, T_ctx, 76], got {tuple(ctx_qpos.shape)}")
-    r = KpRecordPre(first.shape[0], int(T), int(t), 0 if ctx_qpos is None else int(ctx_qpos.shape[1]),
-                    _dptr(obs, f32, "obs"), _dptr(fresh, u8, "fresh"), _dptr(qpos, f32, "qpos"), _dptr(ctx_qpos, f32, "ctx_qpos"), _dptr(row, i32, "row"), _dptr(cur_t, i32, "cur_t"),
-                    _dptr(row_len, i32, "row_len"), _dptr(row_meta, f32, "row_meta"), _dptr(states, f32, "states"), _dptr(episode_start, u8, "episode_start"),
-                    _dptr(curr_qpos, f32, "curr_qpos"), _dptr(gt_target_qpos, f32, "gt_target_qpos"), _dptr(meta, f32, "meta"))
-    _check(L.kp_rollout_record_pre_w(C.byref(r), obs_dim, C.c_void_p(torch.cuda.current_stream(first.device).cuda_stream)), "kp_rollout_record_pre")
+    r = KpRecordPre(n, int(T), int(t), 0 if ctx_qpos is None else int(ctx_qpos.shape[1]),
+                    _dev("obs", obs, (n, w)), _dev("fresh", _u8(fresh), (n,), u8), _dev("qpos", qpos, (n, 76)), _dev("ctx_qpos", ctx_qpos, (None, None, 76)),
+                    _dev("row", row, (n,), i32), _dev("cur_t", cur_t, (n,), i32), _dev("row_len", row_len, None, i32), _dev("row_meta", row_meta, None),
+                    _dev("states", states, (n, T, w)), _dev("episode_start", _u8(episode_start), (n, T), u8), _dev("curr_qpos", curr_qpos, (n, T, 76)),
+                    _dev("gt_target_qpos", gt_target_qpos, (n, T, 76)), _dev("meta", meta, (n, T, 2)))
+    _check(L.kp_rollout_record_pre_w(C.byref(r), w, C.c_void_p(torch.cuda.current_stream(first.device).cuda_stream)), "kp_rollout_record_pre")
 
 
 def record_post(t: int, T: int, fr_num=0.0, action=None, reward=None, fail=None, done=None, percent=None, c_info=None, obs=None, qpos=None, cc_action=None, cc_state=None, meta=None,
@@ -640,37 +565,35 @@ def record_post(t: int, T: int, fr_num=0.0, action=None, reward=None, fail=None,
                 obs_dim=AR_OBS_DIM):
     """kp_rollout_record_post: the after-the-step half (one launch); obs_dim: the width of obs / next_states."""
     L = load_library()
-    obs_dim = _obs_width(obs_dim)
+    w = _obs_width(obs_dim)
     first = next(x for x in (action, reward, done) if x is not None)
-    f32, u8 = torch.float32, torch.uint8
+    u8 = torch.uint8
     n = first.shape[0]
-    _want("action", action, n, 80); _want("reward", reward, n); _want("fail", fail, n); _want("done", done, n); _want("percent", percent, n); _want("c_info", c_info, n, 6)
-    _want("obs", obs, n, obs_dim); _want("qpos", qpos, n, 76); _want("cc_action", cc_action, n, CC_ACTION_DIM); _want("cc_state", cc_state, n, CC_OBS_DIM); _want("meta", meta, n, T, 2)
-    _want("actions", actions, n, T, 80); _want("rewards", rewards, n, T); _want("fails", fails, n, T); _want("dones", dones, n, T); _want("percents", percents, n, T)
-    _want("c_infos", c_infos, n, T, 6); _want("next_states", next_states, n, T, obs_dim); _want("res_qpos", res_qpos, n, T, 76); _want("cc_actions", cc_actions, n, T, CC_ACTION_DIM)
-    _want("cc_states", cc_states, n, T, CC_OBS_DIM); _want("v_metas", v_metas, n, T, 3)
-    r = KpRecordPost(first.shape[0], int(T), int(t), float(fr_num), _dptr(action, f32, "action"), _dptr(reward, f32, "reward"), _dptr(fail, u8, "fail"), _dptr(done, u8, "done"),
-                     _dptr(percent, f32, "percent"), _dptr(c_info, f32, "c_info"), _dptr(obs, f32, "obs"), _dptr(qpos, f32, "qpos"), _dptr(cc_action, f32, "cc_action"),
-                     _dptr(cc_state, f32, "cc_state"), _dptr(meta, f32, "meta"), _dptr(actions, f32, "actions"), _dptr(rewards, f32, "rewards"), _dptr(fails, u8, "fails"),
-                     _dptr(dones, u8, "dones"), _dptr(percents, f32, "percents"), _dptr(c_infos, f32, "c_infos"), _dptr(next_states, f32, "next_states"), _dptr(res_qpos, f32, "res_qpos"),
-                     _dptr(cc_actions, f32, "cc_actions"), _dptr(cc_states, f32, "cc_states"), _dptr(v_metas, f32, "v_metas"))
-    _check(L.kp_rollout_record_post_w(C.byref(r), obs_dim, C.c_void_p(torch.cuda.current_stream(first.device).cuda_stream)), "kp_rollout_record_post")
+    r = KpRecordPost(n, int(T), int(t), float(fr_num), _dev("action", action, (n, 80)), _dev("reward", reward, (n,)), _dev("fail", _u8(fail), (n,), u8),
+                     _dev("done", _u8(done), (n,), u8), _dev("percent", percent, (n,)), _dev("c_info", c_info, (n, 6)), _dev("obs", obs, (n, w)), _dev("qpos", qpos, (n, 76)),
+                     _dev("cc_action", cc_action, (n, CC_ACTION_DIM)), _dev("cc_state", cc_state, (n, CC_OBS_DIM)), _dev("meta", meta, (n, T, 2)),
+                     _dev("actions", actions, (n, T, 80)), _dev("rewards", rewards, (n, T)), _dev("fails", _u8(fails), (n, T), u8), _dev("dones", _u8(dones), (n, T), u8),
+                     _dev("percents", percents, (n, T)), _dev("c_infos", c_infos, (n, T, 6)), _dev("next_states", next_states, (n, T, w)), _dev("res_qpos", res_qpos, (n, T, 76)),
+                     _dev("cc_actions", cc_actions, (n, T, CC_ACTION_DIM)), _dev("cc_states", cc_states, (n, T, CC_OBS_DIM)), _dev("v_metas", v_metas, (n, T, 3)))
+    _check(L.kp_rollout_record_post_w(C.byref(r), w, C.c_void_p(torch.cuda.current_stream(first.device).cuda_stream)), "kp_rollout_record_post")
 
 
 def pool_advance(done: torch.Tensor, head: torch.Tensor, ahead: torch.Tensor, row: torch.Tensor, n_slots: int):
     """Episode turnover on a ring of n_slots context rows per env (kp_pool_advance): done uint8 / bool [N]; head, ahead, row int32 [N], in place."""
     L = load_library()
     n = done.shape[0]
-    if done.dtype == torch.bool:
-        done = done.view(torch.uint8)
-    for t in (head, ahead, row):
-        if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (n,)):
-            raise ValueError("pool_advance: head / ahead / row must be contiguous int32 device tensors [N]")
-    if not (done.is_cuda and done.dtype == torch.uint8 and done.is_contiguous()):
-        raise ValueError("pool_advance: done must be a contiguous uint8 / bool device tensor [N]")
     stream = torch.cuda.current_stream(done.device).cuda_stream
-    _check(L.kp_pool_advance(n, int(n_slots), C.c_void_p(done.data_ptr()), C.c_void_p(head.data_ptr()), C.c_void_p(ahead.data_ptr()), C.c_void_p(row.data_ptr()),
-                             C.c_void_p(stream)), "kp_pool_advance")
+    _check(L.kp_pool_advance(n, int(n_slots), _dev("pool_advance: done", _u8(done), None, torch.uint8),
+                             *(_dev("pool_advance: " + k, t, (n,), torch.int32) for k, t in (("head", head), ("ahead", ahead), ("row", row))), C.c_void_p(stream)), "kp_pool_advance")
+
+
+def _noise(who, noise, std, n, A):
+    """(pointer, row stride) of the exploration noise [N, A], which may be a column slice of a wider buffer; it needs std [A]"""
+    if noise is None:
+        return None, 0
+    if not (noise.is_cuda and noise.dtype == torch.float32 and tuple(noise.shape) == (n, A) and noise.stride(1) == 1 and std is not None and std.is_contiguous() and std.numel() == A):
+        raise ValueError(f"{who}: noise [N, A] (unit column stride) needs std [A]")
+    return C.c_void_p(noise.data_ptr()), int(noise.stride(0))
 
 
 def mcp_compose(logits: torch.Tensor, prim: torch.Tensor, noise: torch.Tensor | None = None, std: torch.Tensor | None = None, out: torch.Tensor | None = None):
@@ -680,11 +603,7 @@ def mcp_compose(logits: torch.Tensor, prim: torch.Tensor, noise: torch.Tensor | 
     K, n, A = prim.shape
     if not (logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and tuple(logits.shape) == (n, K) and prim.dtype == torch.float32 and prim.is_contiguous()):
         raise ValueError("mcp_compose: logits [N, K] and prim [K, N, A] must be contiguous float32 device tensors")
-    nz, stride = None, 0
-    if noise is not None:
-        if not (noise.is_cuda and noise.dtype == torch.float32 and tuple(noise.shape) == (n, A) and noise.stride(1) == 1 and std is not None and std.is_contiguous() and std.numel() == A):
-            raise ValueError("mcp_compose: noise [N, A] (unit column stride) needs std [A]")
-        nz, stride = C.c_void_p(noise.data_ptr()), int(noise.stride(0))
+    nz, stride = _noise("mcp_compose", noise, std, n, A)
     out = torch.empty((n, A), device=prim.device, dtype=torch.float32) if out is None else out
     stream = torch.cuda.current_stream(prim.device).cuda_stream
     _check(L.kp_mcp_compose(n, K, A, C.c_void_p(logits.data_ptr()), C.c_void_p(prim.data_ptr()), nz, stride, None if std is None else C.c_void_p(std.data_ptr()),
@@ -700,18 +619,13 @@ def mcp_tail(h2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor, b3: torch.Ten
     L = load_library()
     K, n, J = h2.shape
     A, ldw = b3.shape[1], w3.shape[2]
-    ok = all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (h2, b2, w3, b3, logits))
-    if not (ok and tuple(b2.shape) == (K, J) and tuple(w3.shape) == (K, J, ldw) and ldw >= A and tuple(b3.shape) == (K, A) and tuple(logits.shape) == (n, K)):
-        raise ValueError("mcp_tail: h2 [K, N, J], b2 [K, J], w3 [K, J, >= A], b3 [K, A], logits [N, K] must be contiguous float32 device tensors")
-    nz, stride = None, 0
-    if noise is not None:
-        if not (noise.is_cuda and noise.dtype == torch.float32 and tuple(noise.shape) == (n, A) and noise.stride(1) == 1 and std is not None and std.is_contiguous() and std.numel() == A):
-            raise ValueError("mcp_tail: noise [N, A] (unit column stride) needs std [A]")
-        nz, stride = C.c_void_p(noise.data_ptr()), int(noise.stride(0))
+    if ldw < A:
+        raise ValueError(f"mcp_tail: w3 [K, J, {ldw}] is narrower than b3 [K, {A}]")
+    ins = [_dev("mcp_tail: " + k, t, s) for k, t, s in (("h2", h2, (K, n, J)), ("b2", b2, (K, J)), ("w3", w3, (K, J, ldw)), ("b3", b3, (K, A)), ("logits", logits, (n, K)))]
+    nz, stride = _noise("mcp_tail", noise, std, n, A)
     out = torch.empty((n, A), device=h2.device, dtype=torch.float32) if out is None else out
     stream = torch.cuda.current_stream(h2.device).cuda_stream
-    _check(L.kp_mcp_tail(n, K, J, A, C.c_void_p(h2.data_ptr()), C.c_void_p(b2.data_ptr()), C.c_void_p(w3.data_ptr()), int(ldw), C.c_void_p(b3.data_ptr()),
-                         C.c_void_p(logits.data_ptr()), nz, stride,
+    _check(L.kp_mcp_tail(n, K, J, A, ins[0], ins[1], ins[2], int(ldw), ins[3], ins[4], nz, stride,
                          None if std is None else C.c_void_p(std.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(stream)), "kp_mcp_tail")
     return out
 
@@ -720,14 +634,13 @@ def kin_advance(qpos: torch.Tensor, action: torch.Tensor, dt: float = 1.0 / 30.0
     """One frame of TrajARNet's kinematic roll-out (kp_kin_advance): (next_qpos [N,76] with a unit root quaternion, finite-difference qvel [N,75])."""
     L = load_library()
     n = qpos.shape[0]
-    if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (qpos, action)) or tuple(qpos.shape) != (n, NQ) or tuple(action.shape) != (n, 80):
-        raise ValueError("kin_advance: qpos [N,76] and action [N,80] must be contiguous float32 device tensors")
+    qp, ap = _dev("kin_advance: qpos", qpos, (n, NQ)), _dev("kin_advance: action", action, (n, 80))
     next_qpos = torch.empty((n, NQ), device=qpos.device) if next_qpos is None else next_qpos
     qvel = torch.empty((n, NV), device=qpos.device) if qvel is None else qvel
     if not (next_qpos.is_contiguous() and qvel.is_contiguous()):
         raise ValueError("kin_advance: outputs must be contiguous")
     stream = torch.cuda.current_stream(qpos.device).cuda_stream
-    _check(L.kp_kin_advance(n, C.c_void_p(qpos.data_ptr()), C.c_void_p(action.data_ptr()), float(dt), C.c_void_p(next_qpos.data_ptr()), C.c_void_p(qvel.data_ptr()),
+    _check(L.kp_kin_advance(n, qp, ap, float(dt), C.c_void_p(next_qpos.data_ptr()), C.c_void_p(qvel.data_ptr()),
                             C.c_void_p(stream)), "kp_kin_advance")
     return next_qpos, qvel
 
@@ -757,14 +670,9 @@ def gae(rewards: torch.Tensor, masks: torch.Tensor, values: torch.Tensor, gamma:
     episodes the horizon cut (kp_gae_bootstrap)."""
     L = load_library()
     n, T = rewards.shape
-    for t in (rewards, masks, values):
-        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (n, T):
-            raise ValueError("gae: expected contiguous float32 device tensors [N, T]")
+    ins = [_dev("gae: " + k, t, (n, T)) for k, t in (("rewards", rewards), ("masks", masks), ("values", values))]
     adv = torch.empty_like(rewards); ret = torch.empty_like(rewards)
     stream = torch.cuda.current_stream(rewards.device).cuda_stream
-    if last_values is not None and (not last_values.is_cuda or last_values.dtype != torch.float32 or not last_values.is_contiguous() or tuple(last_values.shape) != (n,)):
-        raise ValueError("gae: last_values must be a contiguous float32 device tensor [N]")
-    _check(L.kp_gae_bootstrap(n, T, C.c_void_p(rewards.data_ptr()), C.c_void_p(masks.data_ptr()), C.c_void_p(values.data_ptr()),
-                              None if last_values is None else C.c_void_p(last_values.data_ptr()), float(gamma), float(tau),
+    _check(L.kp_gae_bootstrap(n, T, *ins, _dev("gae: last_values", last_values, (n,)), float(gamma), float(tau),
                               C.c_void_p(adv.data_ptr()), C.c_void_p(ret.data_ptr()), C.c_void_p(stream)), "kp_gae_bootstrap")
     return adv, ret

@@ -94,6 +94,33 @@ def test_abi_loads_and_errors(kp):
         s2.set_state(dev(np.tile(STD["qpos"], (2, 1))), dev(np.zeros((2, 75))))
 
 
+def test_views_of_the_stored_fields_are_what_get_copies(kp):
+    """kp_sim_field_device and kp_sim_get read one field table: after three control steps of an object scene the zero-copy view of each of the ten
+    stored fields equals the copy bit for bit, with kp_field_dim's width; the ten others (derived read-outs, target read-outs, prev_* records) have no view."""
+    stored = ("qpos", "qvel", "xpos", "xquat", "xipos", "target_qpos", "qpos_d", "qvel_d", "obj_qpos", "obj_qvel")
+    n = 16
+    sim = kp.KpSim(kp.KpModel(kp.STEP_KPM), n)
+    qpos, qvel = make_states(n, 5, lift=0.02, vel=0.2, noise=0.05)
+    sim.set_objects(dev(_obj_block(n, [{1: [STD["qpos"][0] + 1.2, STD["qpos"][1], 0.921, 1, 0, 0, 0], 2: [STD["qpos"][0] + 1.2, STD["qpos"][1], 0.7905, 1, 0, 0, 0]}] * n)))      # the push scene
+    sim.set_state(dev(qpos), dev(qvel)); sim.set_target(dev(qpos))
+    act = dev(np.random.default_rng(6).normal(size=(n, 75)) * 0.2)
+    for _ in range(3):
+        sim.step_begin()
+        sim.step_ctrl(act, 15)
+    assert int(sim.diag()[:, 2].max() & 1) == 0
+    for f in stored:
+        v, g = sim.view(f), sim.get(f)
+        assert tuple(v.shape) == tuple(g.shape) == (n, sim.L.kp_field_dim(kp.FIELDS[f])), f
+        assert torch.equal(v, g), f
+        assert torch.isfinite(g).all(), f
+    assert float(sim.get("obj_qpos").abs().max()) > 0 and float(sim.get("qvel").abs().max()) > 0
+    assert set(kp.FIELDS) - set(stored) == {"bquat", "head", "target_wbpos", "target_wbquat", "target_bquat", "target_com", "prev_bquat", "prev_hpos", "M", "bias"}
+    for f in sorted(set(kp.FIELDS) - set(stored)):
+        with pytest.raises(kp.KinPolyNativeError, match="not a stored field"):
+            sim.view(f)
+        assert tuple(sim.get(f).shape) == (n, sim.L.kp_field_dim(kp.FIELDS[f])), f      # ... but every one of them has a read-out
+
+
 @pytest.mark.parametrize("threads", [64, 128, 256])
 def test_freefall_matches_oracle(kp, threads):
     """BASELINE.json configs[1]: free fall, no contact (ABA/CRBA correctness)."""

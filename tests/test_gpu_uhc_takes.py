@@ -253,6 +253,10 @@ def test_abi_errors():
         other.reset()
     with pytest.raises(KinPolyNativeError, match="no table named"):
         lib.table("nope")
+    from kinpoly_amd.sim import TAKE_TABLES
+    assert len(TAKE_TABLES) == 18
+    for name in TAKE_TABLES:          # the binding's list is the library's: kp_takes_table answers every name in it, one row per frame or per take
+        assert lib.table(name).shape[0] == (lib.K if name in ("height_lb", "head_height_lb") else lib.R), name
 
 
 class _ZeroPolicy:

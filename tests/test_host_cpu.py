@@ -81,6 +81,57 @@ def test_no_gpu_fails_loudly():
         KpSim(m, 4)
 
 
+def test_model_options_answer_as_the_recorded_build():
+    """kp_model_set_option / kp_model_get_option against tests/golden/model_options.json, which tools/gen_model_options.py recorded on the build BEFORE
+    the options moved into one table: for every option name and probe value the same return code, the same stored value (and job_auto / ar_obs_dim /
+    cc_obs_dim / cc_action_dim) read back, the same refusal text; an unknown name fails to set and reads NaN."""
+    import json
+    import math
+    from kinpoly_amd.sim import load_library
+    L = load_library()
+    fix = json.load(open(os.path.join(ROOT, "tests", "golden", "model_options.json")))
+    assert len(fix["options"]) == 44 and sum(o["settable"] for o in fix["options"].values()) == 35
+    same = lambda got, want: math.isnan(got) if want == "nan" else got == want  # noqa: E731
+
+    def replay(name, want):
+        m = L.kp_model_load(DEFAULT_KPM.encode())
+        assert m
+        try:
+            rc = L.kp_model_set_option(m, name.encode(), want["v"])
+            assert rc == want["rc"], (name, want["v"], rc)
+            assert (L.kp_last_error().decode() if rc else None) == want["error"], (name, want["v"])
+            for key, opt in [("value", name)] + [(k, k) for k in ("job_auto", "ar_obs_dim", "cc_obs_dim", "cc_action_dim")]:
+                got = L.kp_model_get_option(m, opt.encode())
+                assert same(got, want[key]), (name, want["v"], key, got, want[key])
+        finally:
+            L.kp_model_free(m)
+
+    m = L.kp_model_load(DEFAULT_KPM.encode())
+    for name, o in fix["options"].items():
+        assert same(L.kp_model_get_option(m, name.encode()), o["default"]), name
+        assert len(o["probes"]) >= 17
+        for want in o["probes"]:
+            replay(name, want)
+    L.kp_model_free(m)
+    assert fix["unknown"]["rc"] == -1 and fix["unknown"]["value"] == "nan" and "unknown option" in fix["unknown"]["error"]
+    replay("no_such_option", fix["unknown"])
+    assert math.isnan(L.kp_model_get_option(None, b"contact")) and math.isnan(L.kp_model_get_option(m, None))
+
+
+def test_field_widths():
+    """kp_field_dim for every id of sim.FIELDS: the widths of the kp_field enum (include/kinpoly_sim.h), -1 outside it"""
+    from kinpoly_amd.sim import FIELDS, load_library
+    L = load_library()
+    widths = dict(qpos=76, qvel=75, xpos=72, xquat=96, xipos=72, bquat=96, head=7, target_qpos=76, target_wbpos=72, target_wbquat=96, target_bquat=96,
+                  target_com=72, qpos_d=76, qvel_d=75, prev_bquat=96, prev_hpos=7, obj_qpos=35, obj_qvel=30, M=75 * 75, bias=75)
+    assert set(widths) == set(FIELDS) and sorted(FIELDS.values()) == list(range(20))
+    for name, fid in FIELDS.items():
+        assert L.kp_field_dim(fid) == widths[name], name
+    for fid in (-1, 20, 999, -2 ** 31, 2 ** 31 - 1):
+        assert L.kp_field_dim(fid) == -1
+    assert L.kp_sim_field_device(None, 0) is None
+
+
 def test_product_never_imports_oracle():
     """oracle/ is test infrastructure: nothing under kinpoly_amd/ may import, include, dlopen or link it."""
     pat = re.compile(r"^\s*(from\s+oracle|import\s+oracle|from\s+\.\.?oracle)|#include\s+[\"<][^\">]*oracle|libkp_oracle|CDLL\([^)]*oracle", re.M)
