@@ -52,6 +52,14 @@ typedef struct kp_sim kp_sim;
 #define KP_AR_OBS_DIM 105   /* get_ar_obs_v1, humanoid_ar_v1.py:133-214 (kin_poly.yml flags): the action one-hot is the last block, [101..104] */
 #define KP_AR_OBS_DIM_NO_ACTION 101   /* the same without the one-hot (use_action: false, kin_poly_wo_action.yml; humanoid_ar_v1.py:200-201): the
                                          first 101 entries of the 105-d layout.  Model option "ar_obs_action" = 0 selects it (kp_model_set_option) */
+/* The observation's blocks in the reference's order (humanoid_ar_v1.py:183-201) and the model option that switches each (kp_model_set_option):
+ *     height, de-headed root quaternion, joint angles    74   always
+ *     qvel of the simulated humanoid (data.qvel[:75])     75   "ar_obs_vel" = 1      (use_vel, :184-185)
+ *     diff_hpos, diff_hrot                                 7   "ar_obs_head" = 1     (use_head, :187-189)
+ *     predicted object relative to head                    7   always                (:191-192)
+ *     t_havel, t_hlvel, t_obj_relative_head               13   "ar_obs_head" = 1     (:194-198)
+ *     action one-hot                                       4   "ar_obs_action" = 1   (use_action, :200-201)
+ * Row widths by (head, vel, action): (1,0,1) 105, (1,0,0) 101, (1,1,1) 180, (1,1,0) 176, (0,0,1) 85, (0,0,0) 81, (0,1,1) 160, (0,1,0) 156. */
 #define KP_KIN_ACTION_DIM 80
 #define KP_CC_ACTION_DIM 75
 
@@ -97,7 +105,10 @@ void kp_model_free(kp_model*);
  * depend on how a control step is cut into jobs.
  * "ar_obs_action" (1 / 0, default 1; anything else fails): the kinematic observation of a kp_sim created afterwards from this model -- 1: KP_AR_OBS_DIM
  * floats with the action one-hot (use_action), 0: the first KP_AR_OBS_DIM_NO_ACTION of them (use_action: false, humanoid_ar_v1.py:200-201).
- * kp_model_get_option also answers "ar_obs_dim" (105 or 101).
+ * "ar_obs_vel" (0 / 1, default 0; anything else fails): 1 puts the 75 generalised velocities the step leaves in the state rows (KP_QVEL) after the
+ * pose block of that observation (use_vel).  "ar_obs_head" (1 / 0, default 1; anything else fails): 0 removes the two head-tracking blocks
+ * (use_head: false).  Both are fixed in a kp_sim when it is created, like "ar_obs_action"; the layout is next to KP_AR_OBS_DIM.
+ * kp_model_get_option also answers "ar_obs_dim": the row width of the three switches (105 by default).
  * The UHC config's observation (kp_sim_obs_cc_ex of a kp_sim created afterwards; humanoid_im.py:105-318), each 0 / 1 unless said otherwise, anything
  * else fails: "cc_obs_v" (0 get_full_obs, 1 get_full_obs_v1 = default, 2 get_full_obs_v2), "cc_obs_vel_root" (obs_vel 'root': qvel[:6] instead of the
  * 75 of 'full'), and obs_v 0's "cc_obs_heading", "cc_obs_deheading", "cc_obs_phase" (obs_heading, root_deheading, obs_phase; ignored by obs_v 1 / 2).
@@ -226,7 +237,8 @@ int kp_sim_step_begin(kp_sim*);
 
 /* get_ar_obs_v1() [N,105]   (humanoid_ar_v1.py:133-214; use_head, use_action, use_obj on; use_vel/of/context off).  A handle created from a model
  * whose option "ar_obs_action" is 0 writes [N,101] instead: no action one-hot (use_action: false, :200-201); the one-hot still selects the object
- * of the "predicted object relative to head" block (:146-147, 466-476).  kp_sim_ar_obs_dim: the handle's width (105 or 101; -1 for NULL). */
+ * of the "predicted object relative to head" block (:146-147, 466-476).  "ar_obs_vel" = 1 and "ar_obs_head" = 0 give the other layouts listed next
+ * to KP_AR_OBS_DIM (use_vel / use_head: false); the velocity block is a copy of KP_QVEL.  kp_sim_ar_obs_dim: the handle's row width (-1 for NULL). */
 int kp_sim_obs_ar(kp_sim*, const kp_ctx* ctx, float* out);
 int kp_sim_ar_obs_dim(const kp_sim*);
 
@@ -295,7 +307,8 @@ typedef struct {
 } kp_record_post;
 int kp_rollout_record_pre(const kp_record_pre*, void* hip_stream);
 int kp_rollout_record_post(const kp_record_post*, void* hip_stream);
-/* the same with the observation width of obs / states / next_states: KP_AR_OBS_DIM (what the two above use) or KP_AR_OBS_DIM_NO_ACTION */
+/* the same with the observation width of obs / states / next_states: KP_AR_OBS_DIM (what the two above use), KP_AR_OBS_DIM_NO_ACTION or one of the six
+ * other widths of the layout next to KP_AR_OBS_DIM (180, 176, 85, 81, 160, 156); any other width fails and nothing is launched */
 int kp_rollout_record_pre_w(const kp_record_pre*, int obs_dim, void* hip_stream);
 int kp_rollout_record_post_w(const kp_record_post*, int obs_dim, void* hip_stream);
 

@@ -40,7 +40,8 @@ class AgentAR:
                  pool_depth=4, num_epoch_fix=100, num_epoch=10000, joint_controller=False, grad_joint=False, grad_alternate=False, train_uhc=False,
                  cache_init_context=False, log_std=-3.2, policy_weightdecay=0.0, value_weightdecay=0.0, smooth=True, result_dir=None, eval_envs=None,
                  init_update=False, num_init_update=5, step_update_dyna=False, num_step_dyna_update=10, full_update=False, num_sample=20000, batch_size=128,
-                 noise_std=0.0, cc_checkpoint=None, update_dtype=None, reference_bugs=True, min_batch_size=0, slice_ratio="slice_start", use_action=True):
+                 noise_std=0.0, cc_checkpoint=None, update_dtype=None, reference_bugs=True, min_batch_size=0, slice_ratio="slice_start", use_action=True,
+                 use_vel=False, use_head=True):
         """update_dtype: None = the update runs on the fp32 roll-out modules (fused HIP re-unroll); torch.float64 = the reference's training
         precision on fp64 master copies (kinpoly_amd/update.py).  reference_bugs: reproduce the reference's generator-consumed gradient clip
         (PPOTrainer) and LoggerRL.merge's max-of-mins; False = the corrected forms.
@@ -54,16 +55,18 @@ class AgentAR:
         slice moves it -- the importance ratio PPO defines; while the supervised step updates move the policy far between slices (random init: step loss 77 -> 5
         within one call) it leaves the clip range at once and the surrogate of the later slices has no gradient (profiles/r06/scripts_run.log).
         use_action (kin_poly.yml: True): False is the no-action-label ablation (kin_poly_wo_action.yml): 101-d observations for the policy, the value net
-        and the kinematic twin, a 13-d context GRU input; the reward, the resets and the clip sampling still read the action label."""
+        and the kinematic twin, a 13-d context GRU input; the reward, the resets and the clip sampling still read the action label.
+        use_vel / use_head (a statear yml's keys; kin_poly.yml: False / True): the other observation variants -- the 75 velocities in the state, no
+        head-tracking blocks in the state and no head columns in the context GRU's input (widths: kinpoly_amd.sim.ar_obs_dim); same physics and reward."""
         rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
         enable_tuned_gemms()          # library GEMM solution per shape (rollout and update shapes at 4096 envs); selection only
         torch.manual_seed(seed + rank)
         self.env = BatchedHumanoidAREnv(n_envs, device, mode="train", wild=wild, seed=seed + rank, model_options=model_options,
-                                        joint_controller=joint_controller, use_action=use_action)
+                                        joint_controller=joint_controller, use_action=use_action, use_vel=use_vel, use_head=use_head)
         self.device = self.env.device
         if cc_checkpoint is not None:      # the pre-trained UHC the env is built around (humanoid_ar_v1.py:60-81)
             self.env.load_uhc_checkpoint(cc_checkpoint, load_policy=not joint_controller)
-        self.policy_net = TrajARNet(log_std=log_std, use_action=self.env.use_action).to(self.device)
+        self.policy_net = TrajARNet(log_std=log_std, use_action=self.env.use_action, use_vel=self.env.use_vel, use_head=self.env.use_head).to(self.device)
         self.value_net = Value(MLP(self.env.obs_dim, (512, 256), "relu")).to(self.device)      # agent_ar.py:145-147: Value(MLP(policy_net.state_dim, ...))
         self._sync_params()
         self.kin_sim = kpsim.KpSim(self.env.model, n_envs, self.device.index)      # physics-free twin for the kinematic roll-out
@@ -229,7 +232,8 @@ class AgentAR:
         if wild not in self._eval:
             n = int(self.eval_envs or min(self.env.n, 256))
             env = BatchedHumanoidAREnv(n, self.device.index, mode="test", wild=wild, seed=0, cc_policy=self.env.cc_policy, cc_running_state=self.env.cc_running_state,
-                                       model_options=getattr(self.env, "model_options", None), use_action=self.env.use_action)
+                                       model_options=getattr(self.env, "model_options", None), use_action=self.env.use_action, use_vel=self.env.use_vel,
+                                       use_head=self.env.use_head)
             import copy
             gt_term = env.reward_cfg.use_gt_term                         # a property of the mode (test: no GT-diff termination), not of the configuration
             env.reward_cfg = copy.deepcopy(self.env.reward_cfg)          # thresholds AND the reward weights cfg.apply_reward_weights put on the training env

@@ -13,6 +13,8 @@ import pickle
 import numpy as np
 import torch
 
+from .sim import ar_obs_dim
+
 
 class RunningStat:
     def __init__(self, shape=()):
@@ -114,7 +116,8 @@ ALLOWED_MISSING_POLICY_KEYS = frozenset()
 
 
 class CheckpointWidthError(ValueError):
-    """A kinematic policy of one observation width loaded into a network of the other (use_action: true = 105, false = 101)."""
+    """A kinematic policy of one observation width loaded into a network of another (use_action: true = 105, false = 101; the use_vel / use_head
+    variants: obs_switches)."""
 
 
 def policy_obs_dim(state: dict) -> int | None:
@@ -123,8 +126,23 @@ def policy_obs_dim(state: dict) -> int | None:
     return None if w is None else int(w.shape[1])
 
 
+def obs_switches(d) -> dict | None:
+    """The (use_vel, use_head, use_action) whose observation is d wide (the eight widths are distinct: kinpoly_amd.sim.ar_obs_dim); None for another width."""
+    for vel in (False, True):
+        for head in (True, False):
+            for action in (True, False):
+                if ar_obs_dim(vel, head, action) == d:
+                    return dict(use_vel=vel, use_head=head, use_action=action)
+    return None
+
+
 def _width_name(d):
-    return {105: "105-d, use_action: true", 101: "101-d, use_action: false"}.get(d, f"{d}-d")
+    sw = obs_switches(d)
+    if sw is None:
+        return f"{d}-d"
+    if sw["use_head"] and not sw["use_vel"]:          # kin_poly.yml and its no-action ablation: the one switch they differ in
+        return f"{d}-d, use_action: {str(sw['use_action']).lower()}"
+    return f"{d}-d, " + ", ".join(f"{k}: {str(v).lower()}" for k, v in sw.items())
 
 
 def check_policy_obs_dim(state: dict, obs_dim: int, what="checkpoint"):
@@ -161,7 +179,7 @@ def load_bench_policies(policy_ckpt: str, cc_ckpt: str | None = None, device="cu
     from .nets import PolicyMCP
     cp = load_checkpoint(policy_ckpt)
     sd = split_policy_dict(cp["policy_dict"])
-    net = load_state_strict(TrajARNet(use_action=policy_obs_dim(sd) != 101), sd, what=policy_ckpt).to(device).float()     # the width the checkpoint was trained at
+    net = load_state_strict(TrajARNet(**(obs_switches(policy_obs_dim(sd)) or {})), sd, what=policy_ckpt).to(device).float()     # the width the checkpoint was trained at
     mcp, rs = PolicyMCP(), None
     cc_weights = cp.get("cc_dict")
     if cc_ckpt:

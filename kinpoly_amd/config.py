@@ -7,7 +7,8 @@
 
 Same directory layout as the reference (`results/all/statear/<id>/{models,models_policy,results,log}`, :33-41), same keys, same defaults where
 the reference gives one (`.get(key, default)` in Config / AgentAR).  What the engine does not take from the file, because the HIP path fixes it:
-`use_action` may be true (kin_poly.yml) or false (kin_poly_wo_action.yml: the 101-d observation without the action one-hot).
+`use_action` may be true (kin_poly.yml) or false (kin_poly_wo_action.yml: the 101-d observation without the action one-hot); `use_vel` (the 75
+velocities in the observation) and `use_head` (false: no head-tracking blocks) may be either too, except `use_head: false` with `use_action: false`.
 `mujoco_model` (the compiled blobs of kinpoly_amd/assets are humanoid_smpl_neutral_mesh_all[_step].xml, agent_ar.py:165-169), `model_specs`
 of another architecture than TrajARNet's (checked: a mismatch raises), `policy_optimizer` other than Adam (checked), `obs_*` switches other than the
 kin_poly.yml values (checked).  Nothing here needs a GPU.
@@ -23,7 +24,7 @@ ALL_ACTIONS = ("sit", "push", "avoid", "step")
 
 # what the kernels implement (kin_poly.yml); a config that asks for something else is refused instead of silently run differently
 # key: (what the kernels implement, the reference's default when the file omits the key -- statear_smpl_config.py:118-143)
-_FIXED = {"use_of": (False, True), "use_head": (True, True), "use_vel": (False, False), "use_context": (False, True),
+_FIXED = {"use_of": (False, True), "use_context": (False, True),
           "obs_coord": ("heading", "heading"), "root_deheading": (True, False), "obs_global": (True, False), "obs_quat": (True, False), "has_z": (True, True)}
 _FIXED_MODEL = {"model_v": 1, "rnn_hdim": 1024, "mlp_hsize": [1024, 512, 256], "mlp_htype": "relu", "rnn_type": "gru"}
 _FIXED_POLICY = {"policy_v": 1, "fix_std": True, "policy_htype": "relu", "policy_hsize": [512, 256], "value_htype": "relu", "value_hsize": [512, 256],
@@ -79,13 +80,17 @@ class Config:
         self.joint_controller = self.policy_specs.get("joint_controller", False)       # :149-150
         self.reward_weights = dict(self.policy_specs.get("reward_weights", {}))
         self.use_action = y.get("use_action", True)          # statear_smpl_config.py:141
+        self.use_vel, self.use_head = y.get("use_vel", False), y.get("use_head", True)      # :139-140
         self._check_supported()
 
     def _check_supported(self):
         y = self.yaml_data
         bad = [f"{k}: {y.get(k, ref)!r} (the HIP observation / step kernels implement {v!r})" for k, (v, ref) in _FIXED.items() if y.get(k, ref) != v]
-        if not isinstance(self.use_action, bool):
-            bad.append(f"use_action: {self.use_action!r} (true or false)")
+        for k in ("use_action", "use_vel", "use_head"):
+            if not isinstance(getattr(self, k), bool):
+                bad.append(f"{k}: {getattr(self, k)!r} (true or false)")
+        if self.use_head is False and self.use_action is False:
+            bad.append("use_head: False with use_action: False (the context GRU would have no input: get_context_dim is 0)")
         bad += [f"model_specs.{k}: {self.model_specs[k]!r} (TrajARNet here is {v!r})" for k, v in _FIXED_MODEL.items() if k in self.model_specs and self.model_specs[k] != v]
         bad += [f"policy_specs.{k}: {self.policy_specs[k]!r} (implemented: {v!r})" for k, v in _FIXED_POLICY.items() if k in self.policy_specs and self.policy_specs[k] != v]
         if bad:
@@ -111,7 +116,7 @@ class Config:
                     smooth=bool(self.smooth), init_update=ps.get("init_update", False), num_init_update=int(ps.get("num_init_update", 5)),
                     step_update_dyna=ps.get("step_update_dyna", False), num_step_dyna_update=int(ps.get("num_step_dyna_update", 10)), full_update=ps.get("full_update", False),
                     num_sample=int(self.yaml_data.get("num_sample", 20000)), batch_size=int(self.batch_size),
-                    noise_std=float(self.noise_std) if self.add_noise else 0.0, use_action=self.use_action)
+                    noise_std=float(self.noise_std) if self.add_noise else 0.0, use_action=self.use_action, use_vel=self.use_vel, use_head=self.use_head)
 
     def horizon(self, n_envs: int, world_size: int = 1, floor: int = 1) -> int:
         """Steps per env and iteration so that the job collects at least `min_batch_size` samples (agent_ar.py:277: `self.sample(min_batch_size)`;

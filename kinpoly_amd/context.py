@@ -119,29 +119,34 @@ class TrajARNet(KinPolicy):
     """KinPolicy (the per-step part) + the context network of TrajARNet."""
 
     def __init__(self, state_dim=None, action_dim=80, context_dim=None, rnn_hdim=1024, mlp_hsize=(1024, 512, 256), htype="relu", log_std=-3.2,
-                 use_action=True):
+                 use_action=True, use_vel=False, use_head=True):
         """use_action (kin_poly.yml): the action one-hot is an input of the policy (state 105) and of the context GRU (context 17 = 7 + 6 + 4); False
-        (kin_poly_wo_action.yml): state 101, context 13 (get_context_dim / get_context_feat / get_obs, traj_ar_smpl_net.py:121-167, 281-282)."""
-        state_dim = (105 if use_action else 101) if state_dim is None else state_dim
-        context_dim = (17 if use_action else 13) if context_dim is None else context_dim
+        (kin_poly_wo_action.yml): state 101, context 13 (get_context_dim / get_context_feat / get_obs, traj_ar_smpl_net.py:121-167, 281-282).
+        use_vel: the 75 velocities are part of the state (:265-266); use_head False: no head-tracking blocks in the state (:232-251, 268-277) and no head
+        columns in the context GRU's input (:125, 150-152).  state_dim = kpsim.ar_obs_dim of the three, context_dim = 13 * use_head + 4 * use_action."""
+        if not (use_head or use_action):
+            raise ValueError("TrajARNet: use_head False with use_action False leaves the context GRU without input (get_context_dim is 0)")
+        state_dim = kpsim.ar_obs_dim(use_vel, use_head, use_action) if state_dim is None else state_dim
+        context_dim = (13 * bool(use_head) + 4 * bool(use_action)) if context_dim is None else context_dim
         super().__init__(state_dim, action_dim, rnn_hdim, mlp_hsize, htype, log_std)
-        self.use_action = bool(use_action)
+        self.use_action, self.use_vel, self.use_head = bool(use_action), bool(use_vel), bool(use_head)
         self.context_dim, self.init_dim = context_dim, action_dim + 75
         self.context_rnn = _StepRNN(context_dim, rnn_hdim)
         self.context_mlp = MLP(rnn_hdim, mlp_hsize, htype)
         self.context_fc = nn.Linear(mlp_hsize[-1], self.init_dim)
 
     def _context_input(self, data):
+        head = [data["obj_head_relative_poses"], data["head_vels"]] if self.use_head else []
         if not self.use_action:
-            return torch.cat([data["obj_head_relative_poses"], data["head_vels"]], 2)
+            return torch.cat(head, 2)
         one_hot = data["action_one_hot"]
         T = data["head_vels"].shape[1]
         if one_hot.dim() == 2:
             one_hot = one_hot[:, None].expand(-1, T, -1)
-        return torch.cat([data["obj_head_relative_poses"], data["head_vels"], one_hot], 2)
+        return torch.cat(head + [one_hot], 2)
 
     def get_context_feat(self, data):
-        """get_context_feat (:138-167): GRU over [obj_head_relative_poses, head_vels, action_one_hot (use_action)] -> [N, T, rnn_hdim]."""
+        """get_context_feat (:138-167): GRU over [obj_head_relative_poses, head_vels (use_head), action_one_hot (use_action)] -> [N, T, rnn_hdim]."""
         feat = self._context_input(data)
         hx = torch.zeros((feat.shape[0], self.rnn_hdim), device=feat.device, dtype=feat.dtype)
         outs = []
@@ -221,7 +226,8 @@ class TrajARNet(KinPolicy):
         N, T = data["qpos"].shape[:2]
         if kin_sim.obs_ar_dim != self.state_dim:
             raise ValueError(f"TrajARNet.rollout: the kinematic simulator writes {kin_sim.obs_ar_dim}-d observations, the policy takes {self.state_dim}-d "
-                             "(a model with ar_obs_action = 0 gives the 101-d observation of use_action: false)")
+                             "(a model with ar_obs_action = 0 gives the 101-d observation of use_action: false; ar_obs_vel / ar_obs_head those of "
+                             "use_vel / use_head: kpsim.ar_obs_options)")
         dev = init_qpos.device
         one_hot = data["action_one_hot"] if data["action_one_hot"].dim() == 2 else data["action_one_hot"][:, 0]
         cur_t = torch.zeros(N, dtype=torch.int32, device=dev)

@@ -1,6 +1,7 @@
 // kp_rollout_kernels.hpp -- per-step bookkeeping of the kinematic-policy env and the rollout driver:
 //   k_obs_ar       HumanoidAREnv.get_ar_obs_v1        kin_poly/envs/humanoid_ar_v1.py:133-214 (kin_poly.yml flags; <false>: use_action off,
 //                                                      kin_poly_wo_action.yml, :200-201)
+//   k_obs_ar_v     the same with use_vel and / or without use_head (:157-169, 184-198): the six other (vel, head, action) layouts
 //   k_term_reward  calc_body_diff / calc_body_gt_diff  kin_poly/envs/humanoid_ar_v1.py:435-458
 //                  dynamic_supervision_v1              kin_poly/core/reward_function.py:931-995
 //   k_snapshot     prev_bquat / prev_hpos records      kin_poly/envs/humanoid_ar_v1.py:246-249
@@ -66,6 +67,79 @@ __global__ void k_obs_ar(int n, CtxDev C, const float* __restrict__ qpos, const 
     o[91] = hv[0]; o[92] = hv[1]; o[93] = hv[2];
     for (int k = 0; k < 7; k++) o[94 + k] = orl[k];
     if (ACTION) for (int k = 0; k < 4; k++) o[101 + k] = oh[k];
+}
+
+// The observation's other switches (humanoid_ar_v1.py:183-201; a statear yml's use_vel / use_head / use_action).  Blocks in the reference's order:
+//   [0, 74) height, de-headed root quaternion, joint angles | VEL: 75 qvel (data.qvel[:75], :184-185) | HEAD: diff_hpos 3, diff_hrot 4 (:187-189) |
+//   predicted object relative to head 7 (:191-192) | HEAD: t_havel 3, t_hlvel 3, t_obj_relative_head 7 (:194-198) | ACTION: one-hot 4 (:200-201)
+// D is the row width: 105 / 101 for <false, true, .> (k_obs_ar's layout), 180 / 176 with VEL, 85 / 81 without HEAD, 160 / 156 with VEL and without HEAD.
+template <bool VEL, bool HEAD, bool ACTION>
+struct ObsArLayout {
+    static constexpr int O_VEL = 74, O_DIFF = O_VEL + (VEL ? 75 : 0), O_OBJ = O_DIFF + (HEAD ? 7 : 0), O_TGT = O_OBJ + 7, O_ACT = O_TGT + (HEAD ? 13 : 0),
+                         D = O_ACT + (ACTION ? 4 : 0);
+};
+// 32 lanes per env, 8 envs per 256-thread block (k_term_reward's mapping): the 69 joint angles and the 75 velocities are copied lane-strided, so a
+// wavefront reads and writes runs of 32 consecutive floats of two consecutive rows; the five short blocks go to lanes 0 .. 4 of the env, each with
+// k_obs_ar's expressions on the same inputs (the blocks both kernels write are equal bit for bit).  No LDS, no cross-lane traffic.
+template <bool VEL, bool HEAD, bool ACTION>
+__global__ __launch_bounds__(256) void k_obs_ar_v(int n, CtxDev C, const float* __restrict__ qpos, const float* __restrict__ qvel,
+                                                   const float* __restrict__ xpos, const float* __restrict__ xquat, float* __restrict__ out) {
+    using L = ObsArLayout<VEL, HEAD, ACTION>;
+    const int l = threadIdx.x & 31, e = blockIdx.x * 8 + (threadIdx.x >> 5);
+    if (e >= n) return;
+    const float* q = qpos + (size_t)e * D_NQ;
+    float* o = out + (size_t)e * L::D;
+    for (int j = l; j < D_NU; j += 32) o[5 + j] = q[7 + j];
+    if (VEL) {
+        const float* v = qvel + (size_t)e * D_NV;
+        for (int j = l; j < D_NV; j += 32) o[L::O_VEL + j] = v[j];
+    }
+    if (l > 4) return;
+    if (l == 0) {
+        Q4 rq = Q4{q[3], q[4], q[5], q[6]};
+        Q4 dh = qmul(q_inverse(q_heading(rq)), rq);  // de_heading(qpos[3:7]) (:140-141)
+        o[0] = q[2]; o[1] = dh.w; o[2] = dh.x; o[3] = dh.y; o[4] = dh.z;
+        return;
+    }
+    int t = C.cur_t[e];
+    t = t < 0 ? 0 : (t >= C.T ? C.T - 1 : t);
+    const float* oh = C.action_one_hot + C.r(e) * 4;
+    if (l == 4) {
+        if (ACTION) for (int k = 0; k < 4; k++) o[L::O_ACT + k] = oh[k];
+        return;
+    }
+    if (l == 3) {
+        if (HEAD) {
+            const float* hv = C.head_vels + (C.r(e) * C.T + t) * 6;
+            const float* orl = C.obj_rel + (C.r(e) * C.T + t) * 7;
+            float* g = o + L::O_TGT;
+            g[0] = hv[3]; g[1] = hv[4]; g[2] = hv[5];
+            g[3] = hv[0]; g[4] = hv[1]; g[5] = hv[2];
+            for (int k = 0; k < 7; k++) g[6 + k] = orl[k];
+        }
+        return;
+    }
+    const int hb = 13;
+    V3 hpos = ld3(xpos + (size_t)e * 72 + 3 * hb);
+    const float* hq4 = xquat + (size_t)e * 96 + 4 * hb;
+    Q4 hrot = Q4{hq4[0], hq4[1], hq4[2], hq4[3]};
+    if (l == 1) {
+        if (HEAD) {
+            const float* hp = C.head_pose + (C.r(e) * C.T + t) * 7;
+            st3(o + L::O_DIFF, tv_heading(ld3(hp) - hpos, hrot));
+            Q4 dr = qmul(q_inverse(Q4{hp[3], hp[4], hp[5], hp[6]}), hrot);
+            float* g = o + L::O_DIFF + 3;
+            g[0] = dr.w; g[1] = dr.x; g[2] = dr.y; g[3] = dr.z;
+        }
+        return;
+    }
+    float ohs = oh[0] + oh[1] + oh[2] + oh[3];
+    V3 opos = v3(0.f, 0.f, 0.f); Q4 orot = Q4{1.f, 0.f, 0.f, 0.f};   // get_obj_qpos: [0,0,0,1,0,0,0] when no action (:465-466)
+    if (ohs != 0.f && C.obj_qpos) { const float* ob = C.obj_qpos + (size_t)e * 7; opos = ld3(ob); orot = Q4{ob[3], ob[4], ob[5], ob[6]}; }
+    st3(o + L::O_OBJ, tv_heading(opos - hpos, hrot));
+    Q4 ol = qmul(q_inverse(q_heading(hrot)), orot);
+    float* g = o + L::O_OBJ + 3;
+    g[0] = ol.w; g[1] = ol.x; g[2] = ol.y; g[3] = ol.z;
 }
 
 __global__ void k_snapshot(int n, const float* __restrict__ qpos, const float* __restrict__ xpos, const float* __restrict__ xquat,
@@ -242,7 +316,8 @@ __device__ __forceinline__ void copy_row(float* __restrict__ dst, const float* _
     for (int i = threadIdx.x; i < dim; i += blockDim.x) dst[i] = src[i];
 }
 
-// OBS: the observation width of states / next_states / obs (105, or 101 without the action one-hot): a compile-time row stride, as every other field's
+// OBS: the observation width of states / next_states / obs (105, or 101 without the action one-hot; 180 / 176 / 85 / 81 / 160 / 156 for the use_vel /
+// use_head variants, ObsArLayout): a compile-time row stride, as every other field's
 template <int OBS>
 __global__ void k_record_pre(RecordPre R) {
     const int e = blockIdx.x;

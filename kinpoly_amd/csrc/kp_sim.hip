@@ -35,6 +35,7 @@ struct kp_model {
     double warm_extrap = -1.0;     // a float's value; < 0: automatic (0.75 when the scene's free objects are simulated, 0 otherwise); see kp_step_kernel.hpp
     int planemesh_max = 3; double planemesh_tol = 0.3;   // mjc_PlaneConvex's maxplanemesh / tolplanemesh (the blob's `planemesh`)
     int ar_obs_action = 1;        // 0: kp_sim_obs_ar writes the 101-d observation without the action one-hot (use_action: false, humanoid_ar_v1.py:200-201)
+    int ar_obs_vel = 0, ar_obs_head = 1;   // use_vel: the 75 qvel after the pose block (:184-185); use_head: false drops the head-tracking blocks (:157-169, 187-198)
     // the UHC controller's observation (kp_sim_obs_cc_ex): obs_v 0 / 1 / 2, obs_vel 'root', and obs_v 0's obs_heading / root_deheading / obs_phase
     int cc_obs_v = 1, cc_obs_vel_root = 0, cc_obs_heading = 0, cc_obs_deheading = 0, cc_obs_phase = 0;
     // the UHC controller (kp_sim_step_ctrl): action_v 0 / 1, residual force off / on, meta-PD 0 none / 1 by substep / 2 by joint (humanoid_im.py:433-524)
@@ -83,7 +84,8 @@ struct Timing {
 struct kp_sim {
     const kp_model* model = nullptr;
     int n = 0, device = 0;
-    int ar_obs_dim = KP_AR_OBS_DIM;                   // the model's ar_obs_action when the handle was created: KP_AR_OBS_DIM or KP_AR_OBS_DIM_NO_ACTION
+    int ar_obs_vel = 0, ar_obs_head = 1, ar_obs_action = 1;   // the model's three ar_obs_* switches when the handle was created
+    int ar_obs_dim = KP_AR_OBS_DIM;                   // ar_obs_width of the three: one of the eight widths of KP_AR_OBS_WIDTHS
     int cc_obs_v = 1, cc_obs_vel_root = 0, cc_obs_heading = 0, cc_obs_deheading = 0, cc_obs_phase = 0, cc_obs_dim = KP_CC_OBS_DIM;   // the model's cc_obs_* at creation
     kp::XcArgs xc{KP_CC_ACTION_DIM, 0, 1, 0};        // the model's controller at creation; xc_on: not uhc.yml's (the extended-controller kernels, full layout)
     bool xc_on = false;
@@ -487,6 +489,14 @@ static int cc_obs_width(int v, int vel_root, int heading, int phase) {
     return v == 0 ? heading + 74 + lv + 69 + phase : 229 + lv + (v == 1 ? 4 : 2) * 72 + 2 * 96;
 }
 
+// width of the observation kp_sim_obs_ar writes for these switches (kp::ObsArLayout; the table next to KP_AR_OBS_DIM in include/kinpoly_sim.h)
+static int ar_obs_width(int vel, int head, int action) { return 74 + 75 * vel + 7 * head + 7 + 13 * head + 4 * action; }
+static bool ar_obs_width_known(int d) {
+    for (int k = 0; k < 8; k++) if (d == ar_obs_width(k & 1, (k >> 1) & 1, (k >> 2) & 1)) return true;
+    return false;
+}
+#define KP_AR_OBS_WIDTHS "105, 101, 180, 176, 85, 81, 160 or 156"
+
 // ---- model options: ONE table behind kp_model_set_option and kp_model_get_option (include/kinpoly_sim.h describes what each option does).
 // A settable option lives in an int or a double member of kp_model; how a value is accepted:
 // O_BOOL: v != 0;  O_TRI: -1 (v < 0: automatic) / 0 / 1;  O_INT: (int)v and O_REAL: v, unchecked;  O_REAL32: v rounded to float;  O_ENUM: one of the integers
@@ -515,7 +525,9 @@ static const Opt OPTIONS[] = {
     OPT_D("warm_extrap", O_REAL32, warm_extrap),
     // the kinematic policy's and the UHC's observation and controller (fixed in a kp_sim when it is created)
     OPT_I("ar_obs_action", O_ENUM, ar_obs_action, 0, 1, "1 (105-d observation with the action one-hot) or 0 (101-d, use_action: false)"),
-    OPT_RO("ar_obs_dim", m.ar_obs_action ? KP_AR_OBS_DIM : KP_AR_OBS_DIM_NO_ACTION),
+    OPT_I("ar_obs_vel", O_ENUM, ar_obs_vel, 0, 1, "0 (no velocities) or 1 (use_vel: the 75 qvel follow the pose block)"),
+    OPT_I("ar_obs_head", O_ENUM, ar_obs_head, 0, 1, "1 (with the head-tracking blocks) or 0 (use_head: false)"),
+    OPT_RO("ar_obs_dim", ar_obs_width(m.ar_obs_vel, m.ar_obs_head, m.ar_obs_action)),
     OPT_I("cc_obs_v", O_ENUM, cc_obs_v, 0, 2, "0 (get_full_obs), 1 (get_full_obs_v1) or 2 (get_full_obs_v2)"),
     OPT_I("cc_obs_vel_root", O_ENUM, cc_obs_vel_root, 0, 1), OPT_I("cc_obs_heading", O_ENUM, cc_obs_heading, 0, 1),
     OPT_I("cc_obs_deheading", O_ENUM, cc_obs_deheading, 0, 1), OPT_I("cc_obs_phase", O_ENUM, cc_obs_phase, 0, 1),
@@ -584,7 +596,8 @@ kp_sim* kp_sim_create(const kp_model* m, int n_envs, int device_id, void* stream
     HIP_OK_NULL(hipSetDevice(device_id));
     kp_sim* s = new kp_sim();
     s->model = m; s->n = n_envs; s->device = device_id; s->stream = (hipStream_t)stream;
-    s->ar_obs_dim = m->ar_obs_action ? KP_AR_OBS_DIM : KP_AR_OBS_DIM_NO_ACTION;
+    s->ar_obs_vel = m->ar_obs_vel; s->ar_obs_head = m->ar_obs_head; s->ar_obs_action = m->ar_obs_action;
+    s->ar_obs_dim = ar_obs_width(s->ar_obs_vel, s->ar_obs_head, s->ar_obs_action);
     s->cc_obs_v = m->cc_obs_v; s->cc_obs_vel_root = m->cc_obs_vel_root;
     s->cc_obs_heading = m->cc_obs_v == 0 && m->cc_obs_heading; s->cc_obs_deheading = m->cc_obs_v == 0 && m->cc_obs_deheading; s->cc_obs_phase = m->cc_obs_v == 0 && m->cc_obs_phase;
     s->cc_obs_dim = cc_obs_width(s->cc_obs_v, s->cc_obs_vel_root, s->cc_obs_heading, s->cc_obs_phase);
@@ -1093,11 +1106,30 @@ int kp_sim_step_begin(kp_sim* s) {
     return launched();
 }
 
+extern "C++" {   // the launcher is a template
+template <bool VEL, bool HEAD, bool ACTION>
+static void launch_obs_ar_v(kp_sim* s, const kp_ctx* c, float* out) {
+    static_assert(kp::ObsArLayout<VEL, HEAD, ACTION>::D == 74 + 75 * VEL + 7 * HEAD + 7 + 13 * HEAD + 4 * ACTION, "ar_obs_width is the kernel's row width");
+    hipLaunchKernelGGL((kp::k_obs_ar_v<VEL, HEAD, ACTION>), dim3((s->n + 7) / 8), dim3(256), 0, s->stream, s->n, to_dev(c), s->st.qpos, s->st.qvel, s->st.xpos, s->st.xquat, out);
+}
+}
+
 int kp_sim_obs_ar(kp_sim* s, const kp_ctx* c, float* out) {
     if (!s || !c || !out || !c->head_pose || !c->head_vels || !c->obj_head_relative_poses || !c->action_one_hot || !c->cur_t || c->T < 1)
         return fail("kp_sim_obs_ar: bad arguments");
     HIP_OK(hipSetDevice(s->device));
-    if (s->ar_obs_dim == KP_AR_OBS_DIM)
+    if (s->ar_obs_vel || !s->ar_obs_head) {      // the use_vel / use_head variants (kin_poly.yml's two layouts stay on k_obs_ar)
+        switch (s->ar_obs_vel | (s->ar_obs_head << 1) | (s->ar_obs_action << 2)) {
+            case 0: launch_obs_ar_v<false, false, false>(s, c, out); break;
+            case 1: launch_obs_ar_v<true, false, false>(s, c, out); break;
+            case 3: launch_obs_ar_v<true, true, false>(s, c, out); break;
+            case 4: launch_obs_ar_v<false, false, true>(s, c, out); break;
+            case 5: launch_obs_ar_v<true, false, true>(s, c, out); break;
+            case 7: launch_obs_ar_v<true, true, true>(s, c, out); break;
+            default: return fail("kp_sim_obs_ar: no kernel for ar_obs_vel / ar_obs_head / ar_obs_action = " + std::to_string(s->ar_obs_vel) + " / " +
+                                 std::to_string(s->ar_obs_head) + " / " + std::to_string(s->ar_obs_action));
+        }
+    } else if (s->ar_obs_dim == KP_AR_OBS_DIM)
         hipLaunchKernelGGL(kp::k_obs_ar<true>, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, s->n, to_dev(c), s->st.qpos, s->st.xpos, s->st.xquat, out);
     else
         hipLaunchKernelGGL(kp::k_obs_ar<false>, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, s->n, to_dev(c), s->st.qpos, s->st.xpos, s->st.xquat, out);
@@ -1174,29 +1206,37 @@ int kp_sim_ar_obs_dim(const kp_sim* s) { return s ? s->ar_obs_dim : -1; }
 
 int kp_rollout_record_pre_w(const kp_record_pre* r, int obs_dim, void* stream) {
     if (!r || r->n <= 0 || r->T <= 0 || r->t < 0 || r->t >= r->T) return fail("kp_rollout_record_pre: bad arguments");
-    if (obs_dim != KP_AR_OBS_DIM && obs_dim != KP_AR_OBS_DIM_NO_ACTION) return fail("kp_rollout_record_pre: obs_dim must be 105 or 101, got " + std::to_string(obs_dim));
+    if (!ar_obs_width_known(obs_dim)) return fail("kp_rollout_record_pre: obs_dim must be " KP_AR_OBS_WIDTHS ", got " + std::to_string(obs_dim));
     if ((r->states && !r->obs) || (r->episode_start && !r->fresh) || (r->curr_qpos && !r->qpos) || (r->meta && !r->row_meta) ||
         (r->gt_target_qpos && (!r->ctx_qpos || !r->cur_t || !r->row_len || r->ctx_T <= 0)))
         return fail("kp_rollout_record_pre: a destination without its source");
     kp::RecordPre R{r->n, r->T, r->t, r->ctx_T, r->obs, r->fresh, r->qpos, r->ctx_qpos, r->row, r->cur_t, r->row_len, r->row_meta,
                     r->states, r->episode_start, r->curr_qpos, r->gt_target_qpos, r->meta};
-    if (obs_dim == KP_AR_OBS_DIM) hipLaunchKernelGGL(kp::k_record_pre<KP_AR_OBS_DIM>, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
-    else hipLaunchKernelGGL(kp::k_record_pre<KP_AR_OBS_DIM_NO_ACTION>, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
+    switch (obs_dim) {
+#define KP_RECORD_W(W) case W: hipLaunchKernelGGL(kp::k_record_pre<W>, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R); break
+        KP_RECORD_W(KP_AR_OBS_DIM); KP_RECORD_W(KP_AR_OBS_DIM_NO_ACTION);
+        KP_RECORD_W(180); KP_RECORD_W(176); KP_RECORD_W(85); KP_RECORD_W(81); KP_RECORD_W(160); KP_RECORD_W(156);
+#undef KP_RECORD_W
+    }
     return launched();
 }
 int kp_rollout_record_pre(const kp_record_pre* r, void* stream) { return kp_rollout_record_pre_w(r, KP_AR_OBS_DIM, stream); }
 
 int kp_rollout_record_post_w(const kp_record_post* r, int obs_dim, void* stream) {
     if (!r || r->n <= 0 || r->T <= 0 || r->t < 0 || r->t >= r->T) return fail("kp_rollout_record_post: bad arguments");
-    if (obs_dim != KP_AR_OBS_DIM && obs_dim != KP_AR_OBS_DIM_NO_ACTION) return fail("kp_rollout_record_post: obs_dim must be 105 or 101, got " + std::to_string(obs_dim));
+    if (!ar_obs_width_known(obs_dim)) return fail("kp_rollout_record_post: obs_dim must be " KP_AR_OBS_WIDTHS ", got " + std::to_string(obs_dim));
     if ((r->actions && !r->action) || (r->rewards && !r->reward) || (r->fails && !r->fail) || (r->dones && !r->done) || (r->percents && !r->percent) ||
         (r->c_infos && !r->c_info) || (r->next_states && !r->obs) || (r->res_qpos && !r->qpos) || (r->cc_actions && !r->cc_action) ||
         (r->cc_states && !r->cc_state) || (r->v_metas && !r->meta))
         return fail("kp_rollout_record_post: a destination without its source");
     kp::RecordPost R{r->n, r->T, r->t, r->fr_num, r->action, r->reward, r->fail, r->done, r->percent, r->c_info, r->obs, r->qpos, r->cc_action, r->cc_state, r->meta,
                      r->actions, r->rewards, r->fails, r->dones, r->percents, r->c_infos, r->next_states, r->res_qpos, r->cc_actions, r->cc_states, r->v_metas};
-    if (obs_dim == KP_AR_OBS_DIM) hipLaunchKernelGGL(kp::k_record_post<KP_AR_OBS_DIM>, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
-    else hipLaunchKernelGGL(kp::k_record_post<KP_AR_OBS_DIM_NO_ACTION>, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
+    switch (obs_dim) {
+#define KP_RECORD_W(W) case W: hipLaunchKernelGGL(kp::k_record_post<W>, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R); break
+        KP_RECORD_W(KP_AR_OBS_DIM); KP_RECORD_W(KP_AR_OBS_DIM_NO_ACTION);
+        KP_RECORD_W(180); KP_RECORD_W(176); KP_RECORD_W(85); KP_RECORD_W(81); KP_RECORD_W(160); KP_RECORD_W(156);
+#undef KP_RECORD_W
+    }
     return launched();
 }
 int kp_rollout_record_post(const kp_record_post* r, void* stream) { return kp_rollout_record_post_w(r, KP_AR_OBS_DIM, stream); }

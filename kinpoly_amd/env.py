@@ -43,17 +43,20 @@ class RunningState:
 class BatchedHumanoidAREnv:
     def __init__(self, n_envs, device=0, kpm_path=None, cc_policy: PolicyMCP | None = None,
                  cc_running_state: RunningState | None = None, mode="train", wild=False, joint_controller=False,
-                 env_episode_len=100000, body_diff_thresh=10.0, body_diff_gt_thresh=12.0, model_options=None, seed=0, ar_mode=False, use_action=True):
+                 env_episode_len=100000, body_diff_thresh=10.0, body_diff_gt_thresh=12.0, model_options=None, seed=0, ar_mode=False, use_action=True,
+                 use_vel=False, use_head=True):
         """use_action (kin_poly.yml: true): the observation ends with the clip's action one-hot (105 floats); false (kin_poly_wo_action.yml): the first
-        101 of them (humanoid_ar_v1.py:200-201), from a model with the option ar_obs_action = 0 -- every other quantity still reads the one-hot."""
+        101 of them (humanoid_ar_v1.py:200-201), from a model with the option ar_obs_action = 0 -- every other quantity still reads the one-hot.
+        use_vel: the simulated humanoid's 75 velocities follow the pose block (:184-185, option ar_obs_vel = 1); use_head false: no head-tracking blocks
+        (:157-169, 187-198, option ar_obs_head = 0).  obs_dim is the handle's width (kpsim.ar_obs_dim); the physics, the reward and the resets do not change."""
         self.n = int(n_envs)
         self.ar_mode = bool(ar_mode)
         if kpm_path is None:  # agent_ar.py:165-169: mocap training uses ..._all_step.xml, --wild uses ..._all.xml
             kpm_path = kpsim.DEFAULT_KPM if wild else kpsim.STEP_KPM
         self.model_options = dict(model_options or {})
-        self.model = kpsim.KpModel(kpm_path, **(self.model_options if use_action else {**self.model_options, "ar_obs_action": 0}))
+        self.model = kpsim.KpModel(kpm_path, **{**self.model_options, **kpsim.ar_obs_options(use_vel, use_head, use_action)})
         self.sim = kpsim.KpSim(self.model, self.n, device)
-        self.use_action = self.sim.obs_ar_dim == kpsim.AR_OBS_DIM
+        self.use_action, self.use_vel, self.use_head = self.sim.obs_ar_action, self.sim.obs_ar_vel, self.sim.obs_ar_head
         self.device = self.sim.device
         self.mode, self.wild, self.joint_controller = mode, wild, joint_controller
         self.env_episode_len = env_episode_len
@@ -464,7 +467,7 @@ class _ModelView:
 class HumanoidAREnv:
     """Single-environment facade with the reference constructor and numpy float64 I/O
     (kin_poly/envs/humanoid_ar_v1.py:28).  `cfg` / `cc_cfg` are duck-typed: only `policy_specs` thresholds,
-    `joint_controller`, `env_episode_len`, `use_action` are read if present; a trained UHC checkpoint can be passed as
+    `joint_controller`, `env_episode_len`, `use_action`, `use_vel`, `use_head` are read if present; a trained UHC checkpoint can be passed as
     `cc_state=(policy_dict, running_state mean, std)`."""
 
     def __init__(self, cfg=None, cc_cfg=None, init_context=None, cc_iter=-1, mode="train", wild=False, ar_mode=False, cc_state=None, device=0):
@@ -481,7 +484,8 @@ class HumanoidAREnv:
                                       joint_controller=bool(getattr(cfg, "joint_controller", False)),
                                       env_episode_len=int(getattr(cc_cfg, "env_episode_len", 100000)),
                                       body_diff_thresh=ps.get("body_diff_thresh", 10), body_diff_gt_thresh=ps.get("body_diff_gt_thresh", 12), ar_mode=ar_mode,
-                                      use_action=bool(getattr(cfg, "use_action", True)))
+                                      use_action=bool(getattr(cfg, "use_action", True)), use_vel=bool(getattr(cfg, "use_vel", False)),
+                                      use_head=bool(getattr(cfg, "use_head", True)))
         self.kin_cfg, self.cc_cfg, self.ar_mode, self.wild, self.mode = cfg, cc_cfg, ar_mode, wild, mode
         self.cc_policy, self.cc_running_state = self.b.cc_policy, self.b.cc_running_state
         self.dt, self.end_reward = self.b.dt, 0.0

@@ -25,9 +25,11 @@ def _one_hot_at(data, t):
     return oh if oh.dim() == 2 else oh[:, t]
 
 
-def observe(fk: TorchFK, qpos, data, t, noise_std=0.0, generator=None, use_action=True):
-    """TrajARNet.get_obs (:203-290) for kin_poly.yml (use_head, use_action; no use_vel / use_of / use_context), differentiable in qpos.
-    Returns (obs [B, 105], features: pred_wbpos [B,72], obj_2_head [B,7]); use_action=False: obs [B, 101] without the one-hot (:281-282)."""
+def observe(fk: TorchFK, qpos, data, t, noise_std=0.0, generator=None, use_action=True, use_vel=False, use_head=True, qvel=None):
+    """TrajARNet.get_obs (:203-290) under the use_vel / use_head / use_action switches (no use_of / use_context), differentiable in qpos.
+    Returns (obs [B, kinpoly_amd.sim.ar_obs_dim(use_vel, use_head, use_action)], features: pred_wbpos [B,72], obj_2_head [B,7]); the defaults are
+    kin_poly.yml's 105-d row.  use_action=False: without the one-hot (:281-282); use_vel: `qvel` [B, 75] (the roll-out's current velocity,
+    sim['qvel']) follows the pose block (:265-266); use_head=False: no head-difference and no head-target blocks (:232-251, 268-277)."""
     wbpos = fk.wbpos(qpos)                     # float32 device rows: k_target_fk forward / k_fk_wbpos_grad backward (supervised.TorchFK)
     hpos, hrot = wbpos[:, HEAD], fk.body_quat(qpos, HEAD)
     local = torch.cat([qpos[:, 2:3], quat_mul(quat_inv(heading_q(qpos[:, 3:7])), qpos[:, 3:7]), qpos[:, 7:]], 1)        # height, de-headed root, pose: 74
@@ -41,7 +43,10 @@ def observe(fk: TorchFK, qpos, data, t, noise_std=0.0, generator=None, use_actio
     diff_hrot = quat_mul(quat_inv(t_hrot), hrot)
     obj = data["obj_pose"][:, t]
     obj_rel = torch.cat([quat_rotate_t(heading_q(hrot), obj[:, :3] - hpos), quat_mul(quat_inv(heading_q(hrot)), obj[:, 3:7])], 1)
-    obs = torch.cat([local, diff_hpos, diff_hrot, obj_rel, t_havel, t_hlvel, t_obj] + ([_one_hot_at(data, t)] if use_action else []), 1)
+    if use_vel and qvel is None:
+        raise ValueError("observe: use_vel needs the roll-out's current qvel")
+    obs = torch.cat([local] + ([qvel] if use_vel else []) + ([diff_hpos, diff_hrot] if use_head else []) + [obj_rel] +
+                    ([t_havel, t_hlvel, t_obj] if use_head else []) + ([_one_hot_at(data, t)] if use_action else []), 1)
     return obs, wbpos.reshape(qpos.shape[0], 72), obj_rel
 
 
@@ -58,7 +63,8 @@ def forward_supervised(net, fk: TorchFK, data, gt_rate=0.0, rng=None, noise_std=
     hx = torch.zeros((B, net.rnn_hdim), device=qpos.device, dtype=qpos.dtype)
     Q, V, A, W, O = [], [], [], [], []
     for t in range(T):
-        obs, wb, orel = observe(fk, qpos, data, t, noise_std, generator, getattr(net, "use_action", True))
+        obs, wb, orel = observe(fk, qpos, data, t, noise_std, generator, getattr(net, "use_action", True), getattr(net, "use_vel", False),
+                                getattr(net, "use_head", True), qvel)
         Q.append(qpos); V.append(qvel); W.append(wb); O.append(orel)
         action, hx = net.get_action(obs, hx)
         A.append(action)

@@ -33,7 +33,7 @@ from .nets import KinPolicy, Value
 @dataclass
 class RolloutBatch:
     """TrajBatchEgo (kin_poly/core/trajbatch_ego.py:5-14 over uhc/khrylib/rl/core/trajbatch.py:4-16), env-major [N, T, .]."""
-    states: torch.Tensor         # [N, T, 105] (101 without the action one-hot: env.obs_dim)
+    states: torch.Tensor         # [N, T, 105] (env.obs_dim: 101 without the action one-hot, other widths for use_vel / use_head)
     actions: torch.Tensor        # [N, T, 80]
     rewards: torch.Tensor        # [N, T]
     masks: torch.Tensor          # [N, T]   0 where the episode ended at this row

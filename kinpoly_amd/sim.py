@@ -18,6 +18,20 @@ from . import build as _build
 NQ, NV, NU, NBODY = 76, 75, 69, 24
 CC_OBS_DIM, AR_OBS_DIM, KIN_ACTION_DIM, CC_ACTION_DIM = 784, 105, 80, 75
 AR_OBS_DIM_NO_ACTION = 101      # get_ar_obs_v1 without the action one-hot (use_action: false): model option ar_obs_action = 0
+
+
+def ar_obs_dim(use_vel=False, use_head=True, use_action=True) -> int:
+    """Row width of get_ar_obs_v1 for a statear yml's switches (humanoid_ar_v1.py:183-201; model options ar_obs_vel / ar_obs_head / ar_obs_action):
+    74 pose + 75 velocities (use_vel) + 7 head difference (use_head) + 7 object + 13 head targets (use_head) + 4 action one-hot (use_action)."""
+    return 74 + 75 * bool(use_vel) + 7 * bool(use_head) + 7 + 13 * bool(use_head) + 4 * bool(use_action)
+
+
+AR_OBS_DIMS = tuple(ar_obs_dim(v, h, a) for h in (True, False) for v in (False, True) for a in (True, False))      # 105, 101, 180, 176, 85, 81, 160, 156
+
+
+def ar_obs_options(use_vel=False, use_head=True, use_action=True) -> dict:
+    """The model options of an observation variant that differ from the defaults (KpModel(**options))."""
+    return {k: int(v) for k, v, d in (("ar_obs_vel", use_vel, False), ("ar_obs_head", use_head, True), ("ar_obs_action", use_action, True)) if bool(v) != d}
 DEFAULT_KPM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets", "smpl_humanoid.kpm")
 STEP_KPM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets", "smpl_humanoid_step.kpm")
 
@@ -211,7 +225,8 @@ class KpSim:
         if not self.h:
             raise KinPolyNativeError(f"kp_sim_create: {self.L.kp_last_error().decode()}")
         self._stream = stream
-        self.obs_ar_dim = int(self.L.kp_sim_ar_obs_dim(self.h))      # AR_OBS_DIM, or AR_OBS_DIM_NO_ACTION for a model with ar_obs_action = 0
+        self.obs_ar_dim = int(self.L.kp_sim_ar_obs_dim(self.h))      # AR_OBS_DIM, or the width of the model's ar_obs_vel / ar_obs_head / ar_obs_action (ar_obs_dim)
+        self.obs_ar_vel, self.obs_ar_head, self.obs_ar_action = (bool(model.get_option(k)) for k in ("ar_obs_vel", "ar_obs_head", "ar_obs_action"))
         self.cc_obs_dim = int(self.L.kp_sim_cc_obs_dim(self.h))      # CC_OBS_DIM, or the width of the model's cc_obs_* options (UhcConfig.obs_dim)
         self.cc_obs_phase = bool(model.get_option("cc_obs_phase")) and int(model.get_option("cc_obs_v")) == 0
         self.cc_action_dim = int(model.get_option("cc_action_dim"))
@@ -533,8 +548,8 @@ def job_schedule(n_substeps: int, substeps_per_job: int = 4, taper: int = 1) -> 
 
 
 def _obs_width(obs_dim):
-    if obs_dim not in (AR_OBS_DIM, AR_OBS_DIM_NO_ACTION):
-        raise ValueError(f"obs_dim must be {AR_OBS_DIM} or {AR_OBS_DIM_NO_ACTION} (without the action one-hot), got {obs_dim}")
+    if obs_dim not in AR_OBS_DIMS:
+        raise ValueError(f"obs_dim must be one of {AR_OBS_DIMS} (ar_obs_dim of use_vel / use_head / use_action), got {obs_dim}")
     return int(obs_dim)
 
 

@@ -60,11 +60,12 @@ def main():
         args.result_dir, args.data_file, T = cfg.result_dir, cfg.data_file, int(cfg.fr_num)
         if args.iter > 0 and not args.ckpt:
             args.ckpt = cfg.checkpoint_path(args.iter)
-    use_action = cfg.use_action if cfg is not None else True          # false: kin_poly_wo_action.yml, the 101-d observation
-    env = BatchedHumanoidAREnv(n, 0, mode="test", wild=args.wild, ar_mode=args.ar_mode, seed=0, use_action=use_action)
+    # the observation variant of the yml (use_action false: kin_poly_wo_action.yml, 101-d; use_vel / use_head: kinpoly_amd.sim.ar_obs_dim)
+    obs_kw = dict(use_action=cfg.use_action, use_vel=cfg.use_vel, use_head=cfg.use_head) if cfg is not None else {}
+    env = BatchedHumanoidAREnv(n, 0, mode="test", wild=args.wild, ar_mode=args.ar_mode, seed=0, **obs_kw)
     if cfg is not None:
         cfg.apply_reward_weights(env)
-    net = TrajARNet(log_std=cfg.policy_specs["log_std"] if cfg else -3.2, use_action=use_action).to(env.device)
+    net = TrajARNet(log_std=cfg.policy_specs["log_std"] if cfg else -3.2, **obs_kw).to(env.device)
     if args.ckpt:
         cp = ck.load_checkpoint(args.ckpt)
         sd = ck.split_policy_dict(cp["policy_dict"])
