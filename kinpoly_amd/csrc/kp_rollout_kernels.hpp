@@ -1,12 +1,12 @@
 // kp_rollout_kernels.hpp -- per-step bookkeeping of the kinematic-policy env and the rollout driver:
-//   k_obs_ar       HumanoidAREnv.get_ar_obs_v1        kin_poly/envs/humanoid_ar_v1.py:133-214 (kin_poly.yml flags; <false>: use_action off,
-//                                                      kin_poly_wo_action.yml, :200-201)
-//   k_obs_ar_v     the same with use_vel and / or without use_head (:157-169, 184-198): the six other (vel, head, action) layouts
+//   k_obs_ar       HumanoidAREnv.get_ar_obs_v1        kin_poly/envs/humanoid_ar_v1.py:133-214: one template over use_vel / use_head / use_action
+//                                                      (:157-169, 184-201), eight layouts; <false, true, true> is kin_poly.yml's 105-d row
+//   k_obs_ar_thread  the 105 / 101 rows, one thread per env: the faster launch at these two widths, the same words
 //   k_term_reward  calc_body_diff / calc_body_gt_diff  kin_poly/envs/humanoid_ar_v1.py:435-458
 //                  dynamic_supervision_v1              kin_poly/core/reward_function.py:931-995
 //   k_snapshot     prev_bquat / prev_hpos records      kin_poly/envs/humanoid_ar_v1.py:246-249
 //   k_gae          estimate_advantages (un-normalised) uhc/khrylib/rl/core/common.py:5-25
-// One thread per environment: these are O(100)-flop gathers; the physics kernel dominates the step.
+// One thread or one 32-lane group per environment: these are O(100)-flop gathers; the physics kernel dominates the step.
 #pragma once
 #include "kp_obs_kernels.hpp"
 
@@ -31,48 +31,10 @@ __device__ __forceinline__ int obj_action_start(const float* one_hot) {
 
 __device__ __forceinline__ V3 tv_heading(V3 v, Q4 q) { return q_tmul_vec(q_heading(q), v); }  // transform_vec(v, q, 'heading')
 
-// ACTION: the action one-hot is the last block, o[101..104], of 105-float rows (use_action, kin_poly.yml).  Without it (use_action: false) the rows are
-// the first 101 floats of the same layout at stride 101 (humanoid_ar_v1.py:200-201); the object block o[81..87] still follows the one-hot (:146-147).
-template <bool ACTION>
-__global__ void k_obs_ar(int n, CtxDev C, const float* __restrict__ qpos, const float* __restrict__ xpos, const float* __restrict__ xquat,
-                         float* __restrict__ out) {
-    int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
-    const float* q = qpos + (size_t)e * D_NQ;
-    float* o = out + (size_t)e * (ACTION ? 105 : 101);
-    int t = C.cur_t[e];
-    t = t < 0 ? 0 : (t >= C.T ? C.T - 1 : t);
-    const int hb = 13;
-    Q4 rq = Q4{q[3], q[4], q[5], q[6]};
-    Q4 dh = qmul(q_inverse(q_heading(rq)), rq);  // de_heading(qpos[3:7]) -- no base_rot removal here (:140-141)
-    o[0] = q[2]; o[1] = dh.w; o[2] = dh.x; o[3] = dh.y; o[4] = dh.z;
-    for (int j = 0; j < D_NU; j++) o[5 + j] = q[7 + j];
-    V3 hpos = ld3(xpos + (size_t)e * 72 + 3 * hb);
-    const float* hq4 = xquat + (size_t)e * 96 + 4 * hb;
-    Q4 hrot = Q4{hq4[0], hq4[1], hq4[2], hq4[3]};
-    const float* hp = C.head_pose + (C.r(e) * C.T + t) * 7;
-    const float* hv = C.head_vels + (C.r(e) * C.T + t) * 6;
-    const float* orl = C.obj_rel + (C.r(e) * C.T + t) * 7;
-    const float* oh = C.action_one_hot + C.r(e) * 4;
-    st3(o + 74, tv_heading(ld3(hp) - hpos, hrot));
-    Q4 dr = qmul(q_inverse(Q4{hp[3], hp[4], hp[5], hp[6]}), hrot);
-    o[77] = dr.w; o[78] = dr.x; o[79] = dr.y; o[80] = dr.z;
-    float ohs = oh[0] + oh[1] + oh[2] + oh[3];
-    V3 opos = v3(0.f, 0.f, 0.f); Q4 orot = Q4{1.f, 0.f, 0.f, 0.f};   // get_obj_qpos: [0,0,0,1,0,0,0] when no action (:465-466)
-    if (ohs != 0.f && C.obj_qpos) { const float* ob = C.obj_qpos + (size_t)e * 7; opos = ld3(ob); orot = Q4{ob[3], ob[4], ob[5], ob[6]}; }
-    st3(o + 81, tv_heading(opos - hpos, hrot));
-    Q4 ol = qmul(q_inverse(q_heading(hrot)), orot);
-    o[84] = ol.w; o[85] = ol.x; o[86] = ol.y; o[87] = ol.z;
-    o[88] = hv[3]; o[89] = hv[4]; o[90] = hv[5];
-    o[91] = hv[0]; o[92] = hv[1]; o[93] = hv[2];
-    for (int k = 0; k < 7; k++) o[94 + k] = orl[k];
-    if (ACTION) for (int k = 0; k < 4; k++) o[101 + k] = oh[k];
-}
-
-// The observation's other switches (humanoid_ar_v1.py:183-201; a statear yml's use_vel / use_head / use_action).  Blocks in the reference's order:
+// The observation's switches (humanoid_ar_v1.py:183-201; a statear yml's use_vel / use_head / use_action).  Blocks in the reference's order:
 //   [0, 74) height, de-headed root quaternion, joint angles | VEL: 75 qvel (data.qvel[:75], :184-185) | HEAD: diff_hpos 3, diff_hrot 4 (:187-189) |
 //   predicted object relative to head 7 (:191-192) | HEAD: t_havel 3, t_hlvel 3, t_obj_relative_head 7 (:194-198) | ACTION: one-hot 4 (:200-201)
-// D is the row width: 105 / 101 for <false, true, .> (k_obs_ar's layout), 180 / 176 with VEL, 85 / 81 without HEAD, 160 / 156 with VEL and without HEAD.
+// D is the row width: 105 / 101 for <false, true, .> (kin_poly.yml / kin_poly_wo_action.yml), 180 / 176 with VEL, 85 / 81 without HEAD, 160 / 156 with VEL and without HEAD.
 template <bool VEL, bool HEAD, bool ACTION>
 struct ObsArLayout {
     static constexpr int O_VEL = 74, O_DIFF = O_VEL + (VEL ? 75 : 0), O_OBJ = O_DIFF + (HEAD ? 7 : 0), O_TGT = O_OBJ + 7, O_ACT = O_TGT + (HEAD ? 13 : 0),
@@ -80,10 +42,10 @@ struct ObsArLayout {
 };
 // 32 lanes per env, 8 envs per 256-thread block (k_term_reward's mapping): the 69 joint angles and the 75 velocities are copied lane-strided, so a
 // wavefront reads and writes runs of 32 consecutive floats of two consecutive rows; the five short blocks go to lanes 0 .. 4 of the env, each with
-// k_obs_ar's expressions on the same inputs (the blocks both kernels write are equal bit for bit).  No LDS, no cross-lane traffic.
+// the same expressions in every layout (a block two layouts share is equal bit for bit).  No LDS, no cross-lane traffic.
 template <bool VEL, bool HEAD, bool ACTION>
-__global__ __launch_bounds__(256) void k_obs_ar_v(int n, CtxDev C, const float* __restrict__ qpos, const float* __restrict__ qvel,
-                                                   const float* __restrict__ xpos, const float* __restrict__ xquat, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_obs_ar(int n, CtxDev C, const float* __restrict__ qpos, const float* __restrict__ qvel,
+                                                 const float* __restrict__ xpos, const float* __restrict__ xquat, float* __restrict__ out) {
     using L = ObsArLayout<VEL, HEAD, ACTION>;
     const int l = threadIdx.x & 31, e = blockIdx.x * 8 + (threadIdx.x >> 5);
     if (e >= n) return;
@@ -140,6 +102,45 @@ __global__ __launch_bounds__(256) void k_obs_ar_v(int n, CtxDev C, const float* 
     Q4 ol = qmul(q_inverse(q_heading(hrot)), orot);
     float* g = o + L::O_OBJ + 3;
     g[0] = ol.w; g[1] = ol.x; g[2] = ol.y; g[3] = ol.z;
+}
+
+// The 105 / 101 layouts (<false, true, ACTION>) with one thread per env and hand-numbered columns: the kernel these two rows were first written by, and
+// still are -- at 4096 envs it takes 6.8 us where k_obs_ar<false, true, .> takes 8.8 / 8.5.  It writes the words k_obs_ar writes
+// (tests/golden/obs_ar_parent_bits.npz); the launcher's table entry is the only place that knows of it.
+template <bool ACTION>
+__global__ void k_obs_ar_thread(int n, CtxDev C, const float* __restrict__ qpos, const float* __restrict__ xpos, const float* __restrict__ xquat,
+                                float* __restrict__ out) {
+    int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const float* q = qpos + (size_t)e * D_NQ;
+    float* o = out + (size_t)e * (ACTION ? 105 : 101);
+    int t = C.cur_t[e];
+    t = t < 0 ? 0 : (t >= C.T ? C.T - 1 : t);
+    const int hb = 13;
+    Q4 rq = Q4{q[3], q[4], q[5], q[6]};
+    Q4 dh = qmul(q_inverse(q_heading(rq)), rq);  // de_heading(qpos[3:7]) -- no base_rot removal here (:140-141)
+    o[0] = q[2]; o[1] = dh.w; o[2] = dh.x; o[3] = dh.y; o[4] = dh.z;
+    for (int j = 0; j < D_NU; j++) o[5 + j] = q[7 + j];
+    V3 hpos = ld3(xpos + (size_t)e * 72 + 3 * hb);
+    const float* hq4 = xquat + (size_t)e * 96 + 4 * hb;
+    Q4 hrot = Q4{hq4[0], hq4[1], hq4[2], hq4[3]};
+    const float* hp = C.head_pose + (C.r(e) * C.T + t) * 7;
+    const float* hv = C.head_vels + (C.r(e) * C.T + t) * 6;
+    const float* orl = C.obj_rel + (C.r(e) * C.T + t) * 7;
+    const float* oh = C.action_one_hot + C.r(e) * 4;
+    st3(o + 74, tv_heading(ld3(hp) - hpos, hrot));
+    Q4 dr = qmul(q_inverse(Q4{hp[3], hp[4], hp[5], hp[6]}), hrot);
+    o[77] = dr.w; o[78] = dr.x; o[79] = dr.y; o[80] = dr.z;
+    float ohs = oh[0] + oh[1] + oh[2] + oh[3];
+    V3 opos = v3(0.f, 0.f, 0.f); Q4 orot = Q4{1.f, 0.f, 0.f, 0.f};   // get_obj_qpos: [0,0,0,1,0,0,0] when no action (:465-466)
+    if (ohs != 0.f && C.obj_qpos) { const float* ob = C.obj_qpos + (size_t)e * 7; opos = ld3(ob); orot = Q4{ob[3], ob[4], ob[5], ob[6]}; }
+    st3(o + 81, tv_heading(opos - hpos, hrot));
+    Q4 ol = qmul(q_inverse(q_heading(hrot)), orot);
+    o[84] = ol.w; o[85] = ol.x; o[86] = ol.y; o[87] = ol.z;
+    o[88] = hv[3]; o[89] = hv[4]; o[90] = hv[5];
+    o[91] = hv[0]; o[92] = hv[1]; o[93] = hv[2];
+    for (int k = 0; k < 7; k++) o[94 + k] = orl[k];
+    if (ACTION) for (int k = 0; k < 4; k++) o[101 + k] = oh[k];
 }
 
 __global__ void k_snapshot(int n, const float* __restrict__ qpos, const float* __restrict__ xpos, const float* __restrict__ xquat,
@@ -300,12 +301,12 @@ __global__ void k_pool_advance(int n, int n_slots, const uint8_t* __restrict__ d
 // percent, custom_info and -- for the full 12-field record -- next_states, res_qpos, cc_action, cc_state, v_metas.  One workgroup per env, lanes over
 // the row's floats; every destination pointer may be null (field not recorded).
 struct RecordPre {
-    int n, T, t, ctx_T;
+    int n, T, t, ctx_T, obs_dim;      // obs_dim: the row width of obs / states (an ObsArLayout::D)
     const float* obs; const uint8_t* fresh; const float* qpos; const float* ctx_qpos; const int* row; const int* cur_t; const int* row_len; const float* row_meta;
     float* states; uint8_t* episode_start; float* curr_qpos; float* gt_target_qpos; float* meta;
 };
 struct RecordPost {
-    int n, T, t; float fr_num;
+    int n, T, t, obs_dim; float fr_num;      // obs_dim: the row width of obs / next_states
     const float* action; const float* reward; const uint8_t* fail; const uint8_t* done; const float* percent; const float* c_info;
     const float* obs; const float* qpos; const float* cc_action; const float* cc_state; const float* meta_t;      // meta_t: this step's [n, 2] rows of `meta` (pre wrote them)
     float* actions; float* rewards; uint8_t* fails; uint8_t* dones; float* percents; float* c_infos;
@@ -316,14 +317,11 @@ __device__ __forceinline__ void copy_row(float* __restrict__ dst, const float* _
     for (int i = threadIdx.x; i < dim; i += blockDim.x) dst[i] = src[i];
 }
 
-// OBS: the observation width of states / next_states / obs (105, or 101 without the action one-hot; 180 / 176 / 85 / 81 / 160 / 156 for the use_vel /
-// use_head variants, ObsArLayout): a compile-time row stride, as every other field's
-template <int OBS>
 __global__ void k_record_pre(RecordPre R) {
     const int e = blockIdx.x;
     if (e >= R.n) return;
     const size_t at = (size_t)e * R.T + R.t;
-    if (R.states) copy_row(R.states + at * OBS, R.obs + (size_t)e * OBS, OBS);
+    if (R.states) copy_row(R.states + at * R.obs_dim, R.obs + (size_t)e * R.obs_dim, R.obs_dim);
     if (R.curr_qpos) copy_row(R.curr_qpos + at * 76, R.qpos + (size_t)e * 76, 76);
     const int r = R.row ? R.row[e] : e;
     if (R.gt_target_qpos) {
@@ -338,13 +336,12 @@ __global__ void k_record_pre(RecordPre R) {
     }
 }
 
-template <int OBS>
 __global__ void k_record_post(RecordPost R) {
     const int e = blockIdx.x;
     if (e >= R.n) return;
     const size_t at = (size_t)e * R.T + R.t;
     if (R.actions) copy_row(R.actions + at * 80, R.action + (size_t)e * 80, 80);
-    if (R.next_states) copy_row(R.next_states + at * OBS, R.obs + (size_t)e * OBS, OBS);
+    if (R.next_states) copy_row(R.next_states + at * R.obs_dim, R.obs + (size_t)e * R.obs_dim, R.obs_dim);
     if (R.res_qpos) copy_row(R.res_qpos + at * 76, R.qpos + (size_t)e * 76, 76);
     if (R.cc_actions) copy_row(R.cc_actions + at * 75, R.cc_action + (size_t)e * 75, 75);
     if (R.cc_states) copy_row(R.cc_states + at * 784, R.cc_state + (size_t)e * 784, 784);

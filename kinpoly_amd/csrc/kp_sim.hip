@@ -5,11 +5,13 @@
 #include <climits>
 #include <cmath>
 #include <algorithm>
+#include <array>
 #include <cstdlib>
 #include <cstring>
 #include <cstdio>
 #include <unistd.h>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/kinpoly_sim.h"
@@ -998,34 +1000,30 @@ static kp::ObsCcArgs obs_cc_args(const kp_sim* s, float* out, const float* zf_me
     return A;
 }
 
+// ---- the UHC observation: ONE table of the 20 layouts, the 16 of obs_v 0 first (index vel_root | heading << 1 | deheading << 2 | phase << 3),
+// then obs_v 1 and 2, which have the obs_vel switch only (a handle of theirs holds the other three as 0)
+extern "C++" {   // the launcher is a template
+using ObsCcLaunch = void (*)(kp_sim*, const kp::ObsCcArgs&, const float*);
+template <int V, int I>
+static void launch_obs_cc(kp_sim* s, const kp::ObsCcArgs& A, const float* phase) {
+    if constexpr (V == 1 && I == 0) hipLaunchKernelGGL(kp::k_obs_cc_uhc, dim3(s->n), dim3(64), 0, s->stream, A);      // uhc.yml's: no phase argument
+    else hipLaunchKernelGGL((kp::k_obs_cc<V, (I & 1) != 0, (I & 2) != 0, (I & 4) != 0, (I & 8) != 0>), dim3(s->n), dim3(64), 0, s->stream, A, phase);
+}
+template <int... I>
+static constexpr std::array<ObsCcLaunch, 20> obs_cc_table(std::integer_sequence<int, I...>) {
+    return {launch_obs_cc<0, I>..., launch_obs_cc<1, 0>, launch_obs_cc<1, 1>, launch_obs_cc<2, 0>, launch_obs_cc<2, 1>};
+}
+static constexpr auto OBS_CC = obs_cc_table(std::make_integer_sequence<int, 16>{});
+static constexpr int OBS_CC_V1 = 16;      // get_full_obs_v1 with the full velocities: uhc.yml's 784-wide row
+}
+
 int kp_sim_obs_cc(kp_sim* s, float* out, const float* zf_mean, const float* zf_std, float clip) {
     if (!s || !out) return fail("kp_sim_obs_cc: null argument");
     if ((zf_mean == nullptr) != (zf_std == nullptr)) return fail("kp_sim_obs_cc: pass both zf_mean and zf_std or neither");
     HIP_OK(hipSetDevice(s->device));
-    hipLaunchKernelGGL(kp::k_obs_cc, dim3(s->n), dim3(64), 0, s->stream, obs_cc_args(s, out, zf_mean, zf_std, clip));
+    OBS_CC[OBS_CC_V1](s, obs_cc_args(s, out, zf_mean, zf_std, clip), nullptr);      // whatever the handle's layout
     return launched();
 }
-
-extern "C++" {   // the launchers are templates
-template <int V, bool VROOT, bool HEAD, bool DEHEAD, bool PHASE>
-static void launch_obs_cc_v(kp_sim* s, const kp::ObsCcArgs& A, const float* phase) {
-    hipLaunchKernelGGL((kp::k_obs_cc_v<V, VROOT, HEAD, DEHEAD, PHASE>), dim3(s->n), dim3(64), 0, s->stream, A, phase);
-}
-template <bool VROOT>
-static void launch_obs_cc_v0(kp_sim* s, const kp::ObsCcArgs& A, const float* phase) {
-    const int sw = s->cc_obs_heading * 4 + s->cc_obs_deheading * 2 + s->cc_obs_phase;
-    switch (sw) {
-        case 0: launch_obs_cc_v<0, VROOT, false, false, false>(s, A, phase); break;
-        case 1: launch_obs_cc_v<0, VROOT, false, false, true>(s, A, phase); break;
-        case 2: launch_obs_cc_v<0, VROOT, false, true, false>(s, A, phase); break;
-        case 3: launch_obs_cc_v<0, VROOT, false, true, true>(s, A, phase); break;
-        case 4: launch_obs_cc_v<0, VROOT, true, false, false>(s, A, phase); break;
-        case 5: launch_obs_cc_v<0, VROOT, true, false, true>(s, A, phase); break;
-        case 6: launch_obs_cc_v<0, VROOT, true, true, false>(s, A, phase); break;
-        default: launch_obs_cc_v<0, VROOT, true, true, true>(s, A, phase); break;
-    }
-}
-}  // extern "C++"
 
 int kp_sim_obs_cc_ex(kp_sim* s, float* out, const float* zf_mean, const float* zf_std, float clip, const float* phase) {
     if (!s || !out) return fail("kp_sim_obs_cc_ex: null argument");
@@ -1033,13 +1031,9 @@ int kp_sim_obs_cc_ex(kp_sim* s, float* out, const float* zf_mean, const float* z
     if (s->cc_obs_phase && !phase) return fail("kp_sim_obs_cc_ex: this handle's observation ends with the phase (cc_obs_phase = 1): pass phase [N]");
     if (!s->cc_obs_phase && phase) return fail("kp_sim_obs_cc_ex: phase given, but this handle's observation has no phase slot (cc_obs_phase = 0 or cc_obs_v != 0)");
     HIP_OK(hipSetDevice(s->device));
-    const kp::ObsCcArgs A = obs_cc_args(s, out, zf_mean, zf_std, clip);
-    if (s->cc_obs_v == 1 && !s->cc_obs_vel_root) hipLaunchKernelGGL(kp::k_obs_cc, dim3(s->n), dim3(64), 0, s->stream, A);   // the uhc.yml layout: the same kernel as kp_sim_obs_cc
-    else if (s->cc_obs_v == 1) launch_obs_cc_v<1, true, false, false, false>(s, A, nullptr);
-    else if (s->cc_obs_v == 2 && s->cc_obs_vel_root) launch_obs_cc_v<2, true, false, false, false>(s, A, nullptr);
-    else if (s->cc_obs_v == 2) launch_obs_cc_v<2, false, false, false, false>(s, A, nullptr);
-    else if (s->cc_obs_vel_root) launch_obs_cc_v0<true>(s, A, phase);
-    else launch_obs_cc_v0<false>(s, A, phase);
+    const int i = s->cc_obs_v == 0 ? s->cc_obs_vel_root | s->cc_obs_heading << 1 | s->cc_obs_deheading << 2 | s->cc_obs_phase << 3
+                                   : OBS_CC_V1 + 2 * (s->cc_obs_v - 1) + s->cc_obs_vel_root;
+    OBS_CC[i](s, obs_cc_args(s, out, zf_mean, zf_std, clip), phase);
     return launched();
 }
 int kp_sim_cc_obs_dim(const kp_sim* s) { return s ? s->cc_obs_dim : -1; }
@@ -1107,32 +1101,24 @@ int kp_sim_step_begin(kp_sim* s) {
 }
 
 extern "C++" {   // the launcher is a template
-template <bool VEL, bool HEAD, bool ACTION>
-static void launch_obs_ar_v(kp_sim* s, const kp_ctx* c, float* out) {
+template <int I>      // I = vel | head << 1 | action << 2
+static void launch_obs_ar(kp_sim* s, const kp_ctx* c, float* out) {
+    constexpr bool VEL = (I & 1) != 0, HEAD = (I & 2) != 0, ACTION = (I & 4) != 0;
     static_assert(kp::ObsArLayout<VEL, HEAD, ACTION>::D == 74 + 75 * VEL + 7 * HEAD + 7 + 13 * HEAD + 4 * ACTION, "ar_obs_width is the kernel's row width");
-    hipLaunchKernelGGL((kp::k_obs_ar_v<VEL, HEAD, ACTION>), dim3((s->n + 7) / 8), dim3(256), 0, s->stream, s->n, to_dev(c), s->st.qpos, s->st.qvel, s->st.xpos, s->st.xquat, out);
+    if constexpr (!VEL && HEAD)      // 105 / 101: the one-thread-per-env kernel, 2 us faster than k_obs_ar<false, true, .> at 4096 envs; the same words
+        hipLaunchKernelGGL(kp::k_obs_ar_thread<ACTION>, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, s->n, to_dev(c), s->st.qpos, s->st.xpos, s->st.xquat, out);
+    else
+        hipLaunchKernelGGL((kp::k_obs_ar<VEL, HEAD, ACTION>), dim3((s->n + 7) / 8), dim3(256), 0, s->stream, s->n, to_dev(c), s->st.qpos, s->st.qvel, s->st.xpos, s->st.xquat, out);
 }
 }
+static void (*const OBS_AR[8])(kp_sim*, const kp_ctx*, float*) = {launch_obs_ar<0>, launch_obs_ar<1>, launch_obs_ar<2>, launch_obs_ar<3>,
+                                                                  launch_obs_ar<4>, launch_obs_ar<5>, launch_obs_ar<6>, launch_obs_ar<7>};
 
 int kp_sim_obs_ar(kp_sim* s, const kp_ctx* c, float* out) {
     if (!s || !c || !out || !c->head_pose || !c->head_vels || !c->obj_head_relative_poses || !c->action_one_hot || !c->cur_t || c->T < 1)
         return fail("kp_sim_obs_ar: bad arguments");
     HIP_OK(hipSetDevice(s->device));
-    if (s->ar_obs_vel || !s->ar_obs_head) {      // the use_vel / use_head variants (kin_poly.yml's two layouts stay on k_obs_ar)
-        switch (s->ar_obs_vel | (s->ar_obs_head << 1) | (s->ar_obs_action << 2)) {
-            case 0: launch_obs_ar_v<false, false, false>(s, c, out); break;
-            case 1: launch_obs_ar_v<true, false, false>(s, c, out); break;
-            case 3: launch_obs_ar_v<true, true, false>(s, c, out); break;
-            case 4: launch_obs_ar_v<false, false, true>(s, c, out); break;
-            case 5: launch_obs_ar_v<true, false, true>(s, c, out); break;
-            case 7: launch_obs_ar_v<true, true, true>(s, c, out); break;
-            default: return fail("kp_sim_obs_ar: no kernel for ar_obs_vel / ar_obs_head / ar_obs_action = " + std::to_string(s->ar_obs_vel) + " / " +
-                                 std::to_string(s->ar_obs_head) + " / " + std::to_string(s->ar_obs_action));
-        }
-    } else if (s->ar_obs_dim == KP_AR_OBS_DIM)
-        hipLaunchKernelGGL(kp::k_obs_ar<true>, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, s->n, to_dev(c), s->st.qpos, s->st.xpos, s->st.xquat, out);
-    else
-        hipLaunchKernelGGL(kp::k_obs_ar<false>, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, s->n, to_dev(c), s->st.qpos, s->st.xpos, s->st.xquat, out);
+    OBS_AR[s->ar_obs_vel | s->ar_obs_head << 1 | s->ar_obs_action << 2](s, c, out);
     return launched();
 }
 
@@ -1210,14 +1196,9 @@ int kp_rollout_record_pre_w(const kp_record_pre* r, int obs_dim, void* stream) {
     if ((r->states && !r->obs) || (r->episode_start && !r->fresh) || (r->curr_qpos && !r->qpos) || (r->meta && !r->row_meta) ||
         (r->gt_target_qpos && (!r->ctx_qpos || !r->cur_t || !r->row_len || r->ctx_T <= 0)))
         return fail("kp_rollout_record_pre: a destination without its source");
-    kp::RecordPre R{r->n, r->T, r->t, r->ctx_T, r->obs, r->fresh, r->qpos, r->ctx_qpos, r->row, r->cur_t, r->row_len, r->row_meta,
+    kp::RecordPre R{r->n, r->T, r->t, r->ctx_T, obs_dim, r->obs, r->fresh, r->qpos, r->ctx_qpos, r->row, r->cur_t, r->row_len, r->row_meta,
                     r->states, r->episode_start, r->curr_qpos, r->gt_target_qpos, r->meta};
-    switch (obs_dim) {
-#define KP_RECORD_W(W) case W: hipLaunchKernelGGL(kp::k_record_pre<W>, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R); break
-        KP_RECORD_W(KP_AR_OBS_DIM); KP_RECORD_W(KP_AR_OBS_DIM_NO_ACTION);
-        KP_RECORD_W(180); KP_RECORD_W(176); KP_RECORD_W(85); KP_RECORD_W(81); KP_RECORD_W(160); KP_RECORD_W(156);
-#undef KP_RECORD_W
-    }
+    hipLaunchKernelGGL(kp::k_record_pre, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
     return launched();
 }
 int kp_rollout_record_pre(const kp_record_pre* r, void* stream) { return kp_rollout_record_pre_w(r, KP_AR_OBS_DIM, stream); }
@@ -1229,14 +1210,9 @@ int kp_rollout_record_post_w(const kp_record_post* r, int obs_dim, void* stream)
         (r->c_infos && !r->c_info) || (r->next_states && !r->obs) || (r->res_qpos && !r->qpos) || (r->cc_actions && !r->cc_action) ||
         (r->cc_states && !r->cc_state) || (r->v_metas && !r->meta))
         return fail("kp_rollout_record_post: a destination without its source");
-    kp::RecordPost R{r->n, r->T, r->t, r->fr_num, r->action, r->reward, r->fail, r->done, r->percent, r->c_info, r->obs, r->qpos, r->cc_action, r->cc_state, r->meta,
+    kp::RecordPost R{r->n, r->T, r->t, obs_dim, r->fr_num, r->action, r->reward, r->fail, r->done, r->percent, r->c_info, r->obs, r->qpos, r->cc_action, r->cc_state, r->meta,
                      r->actions, r->rewards, r->fails, r->dones, r->percents, r->c_infos, r->next_states, r->res_qpos, r->cc_actions, r->cc_states, r->v_metas};
-    switch (obs_dim) {
-#define KP_RECORD_W(W) case W: hipLaunchKernelGGL(kp::k_record_post<W>, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R); break
-        KP_RECORD_W(KP_AR_OBS_DIM); KP_RECORD_W(KP_AR_OBS_DIM_NO_ACTION);
-        KP_RECORD_W(180); KP_RECORD_W(176); KP_RECORD_W(85); KP_RECORD_W(81); KP_RECORD_W(160); KP_RECORD_W(156);
-#undef KP_RECORD_W
-    }
+    hipLaunchKernelGGL(kp::k_record_post, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
     return launched();
 }
 int kp_rollout_record_post(const kp_record_post* r, void* stream) { return kp_rollout_record_post_w(r, KP_AR_OBS_DIM, stream); }

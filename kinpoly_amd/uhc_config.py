@@ -6,7 +6,7 @@ its controller and scripts/train_uhc.py read, with the reference's defaults wher
     env = BatchedHumanoidEnv(n_envs, cfg=cfg)
 
 What the engine runs of the file: the observation switches obs_v (0 get_full_obs, 1 get_full_obs_v1, 2 get_full_obs_v2), obs_vel ('full' / 'root'),
-and obs_v 0's obs_heading / root_deheading / obs_phase (the HIP kernel k_obs_cc_v); actor_type 'gauss' (PolicyGaussian) or 'mcp' (PolicyMCP);
+and obs_v 0's obs_heading / root_deheading / obs_phase (the HIP kernel k_obs_cc); actor_type 'gauss' (PolicyGaussian) or 'mcp' (PolicyMCP);
 env_term_body 'body' (calc_body_diff > 0.5) or the default 'head', which the reference's if / elif chain never matches (humanoid_im.py:554-561), so
 such an episode never fails; the PPO constants and reward_weights; the controller's action_v (1: PD target about the expert's kinematic pose, 0: about
 a_ref = deg2rad of joint_params column 3, without the 2 pi unwrap), residual_force (implicit, or off) and meta_pd / meta_pd_joint (the step kernel's

@@ -1,9 +1,9 @@
 """GPU tests of the kinematic observation's use_vel / use_head variants (model options ar_obs_vel / ar_obs_head next to ar_obs_action):
-k_obs_ar_v through kp_sim_obs_ar against the reference's rows (tests/golden/ar_obs_variants.npz) and, swept over batch sizes and edge rows, against the
+the k_obs_ar template (the 105 / 101 rows: k_obs_ar_thread) through kp_sim_obs_ar against the reference's rows (tests/golden/ar_obs_variants.npz) and, swept over batch sizes and edge rows, against the
 fp64 restatement (tests/ar_obs_variants_oracle.py); the record kernels at the six new widths; the agent end to end from a variant yml.
 
 Bounds: the fixture rows are held to 5e-6, what tests/test_gpu_no_action.py applies to the 101-d rows against its fixture, and the sweep to
-tests/test_gpu_side_kernels.py::test_obs_ar_sweep's 5e-6 (random rows) / 6.6e-6 (edge rows): the blocks are k_obs_ar's arithmetic on the same
+tests/test_gpu_side_kernels.py::test_obs_ar_sweep's 5e-6 (random rows) / 6.6e-6 (edge rows): the blocks are the 105-d row's arithmetic on the same
 inputs (checked bit for bit below), and the one new block, the velocities, is a copy (checked bit for bit).  Every figure is printed before it is asserted."""
 import ctypes as C
 import os
@@ -48,7 +48,8 @@ def _present(s, block):
 
 
 def _same_as_105(obs, base, s):
-    """every block the variant shares with the 105-d row equals k_obs_ar<true>'s output bit for bit"""
+    """every block the variant shares with the 105-d row equals that row's bit for bit: k_obs_ar's instantiation against k_obs_ar_thread<true>'s hand-numbered
+    columns, so this holds ObsArLayout's offsets and the shared expressions; the 105-d row itself is held to its recorded words below"""
     o, o5 = V.offsets(*s), V.offsets(False, True, True)
     for block, w in COMMON:
         if _present(s, block):
@@ -146,6 +147,33 @@ def test_observation_variant_is_position_independent(kp, s):
     K._position_independent(kp, _opts(kp, s), rows, run)
     for key in [k for k in K._SIMS if k[1]]:
         del K._SIMS[key]
+
+
+@pytest.mark.parametrize("n", [67, 1, 8, 9])
+def test_the_105_and_101_rows_are_the_recorded_words(kp, golden, n):
+    """kp_sim_obs_ar's 105- and 101-wide rows against the words recorded from the one-thread-per-env kernel (now k_obs_ar_thread) at the commit before
+    kp_sim_obs_ar's dispatch became one table (tests/golden/obs_ar_parent_bits.npz, written by tools/make_golden_obs_ar_bits.py: inputs and uint32 views of the
+    rows): not one word may differ, whichever kernel the table's two entries launch (k_obs_ar<false, true, .> wrote the same words when it was tried there).  67 envs are eight full blocks of the 8-envs-per-block mapping and a partial one of 3; 1, 8 and 9 are the first rows of the same inputs (below one
+    block, one block, one block and one env).  The inputs hold cur_t below 0, at T - 1 and above it, a row map with repeats, all-zero one-hots, root
+    quaternions with negative w, and every case once with an obj_qpos pointer and once with a null one."""
+    g = golden("obs_ar_parent_bits")
+    R, T = g["head_pose"].shape[:2]
+    assert len(g["qpos"]) == 67 and g["cur_t"].min() < 0 and (g["cur_t"] == T - 1).any() and g["cur_t"].max() > T - 1 and (g["qpos"][:, 3] < 0).any()
+    assert len(set(g["row"])) < 67 and (g["action_one_hot"][g["row"]].sum(1) == 0).any()
+    z = torch.zeros((R, T, 96), device="cuda")
+    for action in (True, False):
+        sim = kp.KpSim(kp.KpModel(**kp.ar_obs_options(use_action=action)), n)
+        K.load(sim, **{k: g[k][:n] for k in ("qpos", "xpos", "xquat")})
+        for with_obj in (True, False):
+            ctx = sim.make_ctx(T, dev(g["head_pose"]), dev(g["head_vels"]), dev(g["obj_rel"]), dev(g["action_one_hot"]), z, z[:, :, :72].contiguous(),
+                               torch.tensor(g["cur_t"][:n], device="cuda"), obj_qpos=dev(g["obj_qpos"][:n]) if with_obj else None,
+                               row=torch.tensor(g["row"][:n], device="cuda"))
+            got = host(sim.obs_ar(ctx)).view(np.uint32)
+            want = g[f"bits_{105 if action else 101}{'' if with_obj else '_null_obj'}"][:n]
+            differ = int((got != want).sum())
+            print(f"MEASURED obs_ar words that differ from the recorded ones, n = {n}, action {action}, obj_qpos {with_obj}: {differ} of {want.size}",
+                  sorted(set(np.nonzero(got != want)[1].tolist())))
+            assert got.shape == want.shape and differ == 0
 
 
 @pytest.mark.parametrize("obs_dim", [180, 176, 85, 81, 160, 156])

@@ -1,5 +1,5 @@
-"""GPU tests of the UHC config's observation variants (kp_sim_obs_cc_ex / k_obs_cc_v against the reference's get_full_obs / _v1 / _v2 fixture),
-the default handle's bit equality with kp_sim_obs_cc, the option checks, the env's 'head' termination rule, and train_uhc.py --cfg end to end."""
+"""GPU tests of the UHC config's observation variants (kp_sim_obs_cc_ex / the k_obs_cc template against the reference's get_full_obs / _v1 / _v2 fixture),
+the default handle's bit equality with kp_sim_obs_cc and kp_sim_obs_cc's 784-wide row on a handle of another layout, the option checks, the env's 'head' termination rule, and train_uhc.py --cfg end to end."""
 import os
 import subprocess
 import sys
@@ -80,6 +80,20 @@ def test_default_handle_is_bit_identical_to_obs_cc(kp):
         assert sim.L.kp_sim_obs_cc(sim.h, p(old), p(args[0]), p(args[1]), C.c_float(args[2])) == 0
         torch.cuda.synchronize()
         assert torch.equal(ex, old)
+    # kp_sim_obs_cc is the 784-wide get_full_obs_v1 row whatever the handle's layout: a cc_obs_v = 2 handle (640-wide rows of its own) on the same state
+    n = 5
+    assert len(g["qpos"]) >= n
+    rows = []
+    for opts in ({}, _opts(2, 0, 0, 0, 0)):
+        sim = kp.KpSim(kp.KpModel(**opts), n)
+        sim.set_state(dev(g["qpos"][:n]), dev(g["qvel"][:n])); sim.set_target(dev(g["clip"][g["t"][:n] + 1]))
+        for args in ((None, None, 0.0), (zm, zs, 5.0)):
+            out = torch.full((n, 784), float("nan"), device="cuda")
+            assert sim.L.kp_sim_obs_cc(sim.h, p(out), p(args[0]), p(args[1]), C.c_float(args[2])) == 0
+            torch.cuda.synchronize()
+            rows.append(out)
+    assert sim.cc_obs_dim == 640 and torch.isfinite(rows[0]).all()
+    assert torch.equal(rows[0], rows[2]) and torch.equal(rows[1], rows[3])
 
 
 def test_options_and_phase_are_checked(kp):

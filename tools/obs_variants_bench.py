@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Env-steps/s of the rollout (VectorSampler.sample: kinematic policy GEMMs, UHC GEMMs, physics, observation, reward, record) for the 105-d observation of
-kin_poly.yml and for each use_vel / use_head variant (kinpoly_amd.sim.ar_obs_dim: 180, 176, 85, 160 -- and 81, 156 with --all, the two widths Config
+kin_poly.yml and for each use_vel / use_head variant (kinpoly_amd.sim.ar_obs_dim: 180, 176, 85, 160 -- and, with --all, 101 and 81, 156, the two widths Config
 refuses), alternating them in one process.  The yardstick is the 105-d figure of the same run.
 
 The variants' GEMM shapes (the GRU input GEMM at K = state_dim, the action MLP's first layer at K = 1024 + state_dim, the value net's first layer) are not
@@ -27,6 +27,7 @@ from kinpoly_amd.rollout import VectorSampler  # noqa: E402
 # (use_vel, use_head, use_action): 105 first (the yardstick), then the variants a yml can ask for
 VARIANTS = [(False, True, True), (True, True, True), (True, True, False), (False, False, True), (True, False, True)]
 KERNEL_ONLY = [(False, False, False), (True, False, False)]
+NO_ACTION = (False, True, False)        # 101: kin_poly_wo_action.yml (tools/no_action_bench.py measures it end to end)
 
 
 def setup(n, s, std, seed=0):
@@ -44,7 +45,7 @@ def main():
     n = int(args[0]) if len(args) > 0 else 4096
     steps = int(args[1]) if len(args) > 1 else 40
     blocks = int(args[2]) if len(args) > 2 else 3
-    variants = VARIANTS + (KERNEL_ONLY if "--all" in sys.argv else [])
+    variants = VARIANTS + ([NO_ACTION] + KERNEL_ONLY if "--all" in sys.argv else [])
     torch.cuda.set_device(0)
     enable_tuned_gemms()
     std = np.load(os.path.join(ROOT, "tests", "golden", "standing_neutral.npz"))
