@@ -29,7 +29,8 @@ from .context import PolicyARContext, TrajARNet
 from .env import BatchedHumanoidAREnv
 from .model_compiler import read_kpm
 from .nets import MLP, Value, enable_tuned_gemms
-from .rollout import EpisodeSource, LoggerRL, VectorSampler, _allreduce_grads, _collective_on
+from .ppo import _allreduce_grads, _collective_on
+from .rollout import EpisodeSource, LoggerRL, VectorSampler
 from .update import ParamUpdate
 
 
@@ -176,12 +177,8 @@ class AgentAR:
             info = self.update_params(batch)
             self.epoch += 1
         else:
-            N, T, _ = batch.states.shape
-            if self.slice_ratio == "behaviour":
-                with torch.no_grad():                           # the behaviour policy's log-probabilities of the whole batch, before any slice moves the parameters
-                    pol, tr = self.upd.policy, self.trainer
-                    means = pol.unroll(tr._cast(batch.states), batch.episode_start, tr._cast(batch.hx0))
-                    batch.behaviour_log_probs = pol.log_prob(means.reshape(N * T, -1), tr._cast(batch.actions).reshape(N * T, -1)).detach()
+            if self.slice_ratio == "behaviour":                   # of the whole batch, before any slice moves the parameters
+                batch.behaviour_log_probs = self.trainer.behaviour_log_probs(batch)
             infos = []
             for k, (lo, hi) in enumerate(slices):
                 if k > 0:

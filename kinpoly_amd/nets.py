@@ -44,6 +44,11 @@ def enable_tuned_gemms(path: str = TUNED_GEMMS) -> bool:
         return False
 
 
+def gaussian_log_prob(mean, log_std, action):
+    """DiagGaussian.log_prob summed over the action dims (uhc/khrylib/rl/core/distributions.py:22-23); log_std: anything that broadcasts against mean"""
+    return (-(action - mean) ** 2 / (2 * torch.exp(2 * log_std)) - 0.5 * math.log(2 * math.pi) - log_std).sum(1, keepdim=True)
+
+
 class MLP(nn.Module):
     def __init__(self, input_dim, hidden_dims=(128, 128), activation="tanh"):
         super().__init__()
@@ -262,10 +267,7 @@ class KinPolicy(nn.Module):
         return torch.addcmul(mean, self.std(), noise), hx
 
     def log_prob(self, mean, action):
-        """DiagGaussian.log_prob summed over the action dims (uhc/khrylib/rl/core/distributions.py:22-23)."""
-        log_std = self.action_log_std
-        var = torch.exp(2 * log_std)
-        return (-(action - mean) ** 2 / (2 * var) - 0.5 * math.log(2 * math.pi) - log_std).sum(1, keepdim=True)
+        return gaussian_log_prob(mean, self.action_log_std, action)
 
     def unroll(self, states, episode_start, hx0=None):
         """Training-time forward over an env-major rollout [N, T, state_dim]: re-runs the GRU through time,

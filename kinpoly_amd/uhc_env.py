@@ -18,7 +18,8 @@ from . import sim as kpsim
 from .context import quat_acos_w, quat_inv, quat_mul, quat_rotate_t, quat_sin_half, quat_small
 from .env import RunningState
 from .model_compiler import read_kpm
-from .nets import PolicyMCP
+from .nets import MLP, PolicyMCP, Value, gaussian_log_prob
+from .ppo import optimizer_step, ppo_surrogate, value_step, value_targets
 
 EE_BODIES = (4, 8, 17, 22, 13)          # L_Toe, R_Toe, L_Wrist, R_Wrist, Head (humanoid_im.py:329)
 UHC_REWARD_WEIGHTS = dict(w_p=0.3, w_v=0.1, w_e=0.45, w_c=0.1, w_vf=0.05, k_p=2.0, k_v=0.005, k_e=5.0, k_c=100.0, k_vf=1.0)   # uhc.yml:37-48
@@ -286,12 +287,10 @@ class RunningStateOnline(RunningState):
 
 class CopycatAgent:
     """The UHC training iteration (uhc/agents/agent_copycat.py: sample with the running state updating, GAE, PPO on PolicyMCP)
-    on the batched env: one process per GPU, gradients all-reduced like kinpoly_amd.rollout.PPOTrainer."""
+    on the batched env: one process per GPU, built from the same steps as kinpoly_amd.ppo.PPOTrainer."""
 
     def __init__(self, env: BatchedHumanoidEnv, policy: PolicyMCP | None = None, value=None, gamma=0.95, tau=0.95, clip_epsilon=0.2,
                  policy_lr=5e-5, value_lr=3e-4, num_optim_epoch=10, group=None, dataset=None, seed=0, output_dir=None):
-        from .nets import MLP, Value
-        from .rollout import _allreduce_grads, estimate_advantages, ppo_surrogate
         self.env, self.group = env, group
         cfg = getattr(env, "cfg", None)
         self.policy = (policy or (cfg.make_policy() if cfg is not None else PolicyMCP())).to(env.device).float()
@@ -300,7 +299,6 @@ class CopycatAgent:
         self.gamma, self.tau, self.clip_epsilon, self.num_optim_epoch = gamma, tau, clip_epsilon, num_optim_epoch
         self.opt_p = torch.optim.Adam([p for p in self.policy.parameters() if p.requires_grad], lr=policy_lr)
         self.opt_v = torch.optim.Adam(self.value.parameters(), lr=value_lr)
-        self._ar, self._ea, self._surr = _allreduce_grads, estimate_advantages, ppo_surrogate
         # a library of takes (kinpoly_amd.dataset.AmassSingleDataset): every episode plays a newly drawn whole take (agent_copycat.py:144)
         self.dataset, self.output_dir, self.freq_dict, self.take_log = dataset, output_dir, None, []
         if dataset is not None:
@@ -372,65 +370,51 @@ class CopycatAgent:
         return f"Coverage {data_mode} of {coverage} out of {ds.get_len()}"
 
     @torch.no_grad()
-    def _sample_takes(self, horizon):
-        env = self.env
-        ids = self._draw(horizon)
+    def sample(self, horizon):
+        """`horizon` steps of every env with the running state updating -> S, A, R, M [N, horizon, .].  With a data set every episode plays a newly drawn
+        take: the ids of the whole call are drawn ahead on the host, the finished episodes go to take_log / freq_dict after the call's one host read"""
+        env, takes = self.env, self.dataset is not None
         S, A, R, M, D, P, K = [], [], [], [], [], [], []
-        obs = self.running_state(env.reset(torch.ones(env.n, dtype=torch.bool, device=env.device), take_ids=self._draw(1)[0]), update=True)
+        ids = self._draw(horizon) if takes else None
+        first = env.reset(torch.ones(env.n, dtype=torch.bool, device=env.device), take_ids=self._draw(1)[0]) if takes else env.reset()
+        obs = self.running_state(first, update=True)
         for t in range(horizon):
             a = self.policy.select_action(obs, False, env.gen).contiguous()
-            K.append(env.take_id.clone())
-            nobs, _, done, info = env.step(a)
-            S.append(obs); A.append(a); R.append(info["custom_reward"]); M.append((~done).float()); D.append(done); P.append(info["percent"])
-            nobs = env.reset(done, take_ids=ids[t])
-            obs = self.running_state(nobs, update=True)
-        done, pct, take = torch.stack(D, 1).cpu().numpy(), torch.stack(P, 1).cpu().numpy(), torch.stack(K, 1).cpu().numpy()      # the one host read of the period
-        eps = [(int(take[e, t]), float(pct[e, t]), 0) for t in range(horizon) for e in np.nonzero(done[:, t])[0]]
-        if self.group is not None:                                       # ranks merge once per sample(), as the AR agent does
-            import torch.distributed as dist
-            allv = [None] * dist.get_world_size(self.group)
-            dist.all_gather_object(allv, eps, group=self.group)
-            eps = [x for v in allv for x in v]
-        self.take_log.append(eps)
-        self.record_episodes(eps)
-        return torch.stack(S, 1), torch.stack(A, 1), torch.stack(R, 1), torch.stack(M, 1)
-
-    @torch.no_grad()
-    def sample(self, horizon):
-        if self.dataset is not None:
-            return self._sample_takes(horizon)
-        env = self.env
-        S, A, R, M = [], [], [], []
-        obs = self.running_state(env.reset(), update=True)
-        for _ in range(horizon):
-            a = self.policy.select_action(obs, False, env.gen).contiguous()
+            if takes:
+                K.append(env.take_id.clone())
             nobs, _, done, info = env.step(a)
             S.append(obs); A.append(a); R.append(info["custom_reward"]); M.append((~done).float())
-            nobs = env.reset(done)
+            if takes:
+                D.append(done); P.append(info["percent"])
+            nobs = env.reset(done, take_ids=ids[t] if takes else None)
             obs = self.running_state(nobs, update=True)
+        if takes:
+            done, pct, take = torch.stack(D, 1).cpu().numpy(), torch.stack(P, 1).cpu().numpy(), torch.stack(K, 1).cpu().numpy()      # the one host read of the period
+            eps = [(int(take[e, t]), float(pct[e, t]), 0) for t in range(horizon) for e in np.nonzero(done[:, t])[0]]
+            if self.group is not None:                                   # ranks merge once per sample(), as the AR agent does
+                import torch.distributed as dist
+                allv = [None] * dist.get_world_size(self.group)
+                dist.all_gather_object(allv, eps, group=self.group)
+                eps = [x for v in allv for x in v]
+            self.take_log.append(eps)
+            self.record_episodes(eps)
         return torch.stack(S, 1), torch.stack(A, 1), torch.stack(R, 1), torch.stack(M, 1)
 
     def log_prob(self, states, actions):
-        mean, log_std = self.policy(states)
-        return (-(actions - mean) ** 2 / (2 * torch.exp(2 * log_std)) - 0.5 * math.log(2 * math.pi) - log_std).sum(1, keepdim=True)
+        return gaussian_log_prob(*self.policy(states), actions)
 
     def optimize_policy(self, horizon=32):
         S, A, R, M = self.sample(horizon)
         N, T, _ = S.shape
         fs, fa = S.reshape(N * T, -1), A.reshape(N * T, -1)
+        adv, ret = value_targets(self.value, fs, R, M, self.gamma, self.tau, self.group)
         with torch.no_grad():
-            values = self.value(fs).view(N, T)
             fixed = self.log_prob(fs, fa)
-        adv, ret = self._ea(R, M, values, self.gamma, self.tau, self.group)
-        adv, ret = adv.reshape(-1, 1), ret.reshape(-1, 1)
         stats = {}
-        for _ in range(self.num_optim_epoch):
-            vloss = (self.value(fs) - ret).pow(2).mean()
-            self.opt_v.zero_grad(); vloss.backward(); self._ar(list(self.value.parameters()), self.group); self.opt_v.step()
-            surr = self._surr(self.log_prob(fs, fa), fixed, adv, self.clip_epsilon)
-            self.opt_p.zero_grad(); surr.backward()
-            params = [p for p in self.policy.parameters() if p.requires_grad]
-            self._ar(params, self.group); torch.nn.utils.clip_grad_norm_(params, 40.0); self.opt_p.step()
+        for _ in range(self.num_optim_epoch):        # per epoch one value step, then one policy step clipped to 40 (every step: the UHC agent's clip list is a list)
+            vloss = value_step(self.value, self.opt_v, fs, ret, self.group)
+            surr = ppo_surrogate(self.log_prob(fs, fa), fixed, adv, self.clip_epsilon)
+            optimizer_step(self.opt_p, surr, self.group, max_norm=40.0)
             stats = {"value_loss": float(vloss.detach()), "surr_loss": float(surr.detach())}
         stats.update(avg_reward=float(R.mean()), fail_rate=float((1 - M).mean()), num_steps=N * T)
         return stats

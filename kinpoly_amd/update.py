@@ -3,6 +3,7 @@
 (agent_ar.py:264-269) and the update itself (agent_ar.py:682-752: rl_update -> init_update -> step_update -> step_update_dyna -> full_update,
 or the grad_joint branch; update_controller; `policy_net.step_lr()`).
 
+The PPO half is kinpoly_amd/ppo.py::PPOTrainer (no environment either); this module adds the supervised optimiser and the order of the branches.
 Kept apart from `AgentAR` so that the whole loop can be run -- and pinned -- on a recorded batch with no simulator: tests/golden/update_params.npz
 holds two consecutive iterations of the REFERENCE's update_params in fp64 (tools/make_golden.py::gen_update_params), and
 tests/test_update_cpu.py replays them here.
@@ -17,7 +18,7 @@ import copy
 
 import torch
 
-from .rollout import PPOTrainer, _allreduce_grads, lambda_lr
+from .ppo import PPOTrainer, _allreduce_grads, lambda_lr
 from .supervised import TorchFK, update_supervised_step
 
 

@@ -1,5 +1,5 @@
 """Worker of tests/test_gpu_round3.py::test_one_rank_nccl_group_moves_device_tensors: a 1-rank `nccl` (= RCCL) process group on the box's
-GPU, with the exchange step of the PPO iteration forced through it (rollout.FORCE_COLLECTIVES): the all-gather of advantages / returns
+GPU, with the exchange step of the PPO iteration forced through it (ppo.FORCE_COLLECTIVES): the all-gather of advantages / returns
 (normalize_advantages_global, uhc/khrylib/rl/core/common.py:22 made job-wide) and the gradient all-reduce of the data-parallel update."""
 import os
 import sys
@@ -16,7 +16,8 @@ def main():
     os.environ.setdefault("MASTER_PORT", "29547")
     torch.cuda.set_device(0)
     dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-    from kinpoly_amd import rollout as R
+    from kinpoly_amd import ppo as R
+    from kinpoly_amd.rollout import EpisodeSource, _agree_status
     R.FORCE_COLLECTIVES = True
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(5)
@@ -47,7 +48,7 @@ def main():
     # the job-wide freq_dict exchange (EpisodeSource.record: all_gather_object of the finished episodes, agent_ar.py:664-673) through RCCL
     class _DS:
         takes = ["a", "b"]
-    src = R.EpisodeSource.__new__(R.EpisodeSource)
+    src = EpisodeSource.__new__(EpisodeSource)
     src.dataset, src.freq_dict, src._probs = _DS(), {"a": [], "b": []}, None
     ago, n_ago = dist.all_gather_object, [0]
 
@@ -57,7 +58,7 @@ def main():
     dist.all_gather_object = count_ago
     src.record([0, 1, 1], [3, 5, 7], [1.0, 0.25, 0.5])
     ok4 = n_ago[0] == 1 and src.freq_dict == {"a": [[1.0, 3]], "b": [[0.25, 5], [0.5, 7]]}
-    ok5 = R._agree_status(0, dev) == 0
+    ok5 = _agree_status(0, dev) == 0
     print("NCCL_ONE_RANK_OK" if (ok1 and ok2 and ok3 and ok4 and ok5) else f"NCCL_ONE_RANK_FAIL {ok1} {ok2} {ok3} {ok4} {ok5} {calls}", flush=True)
     dist.destroy_process_group()
 

@@ -17,7 +17,8 @@ def _free_port():
 def _worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    from kinpoly_amd.rollout import _allreduce_grads, env_shard, normalize_advantages_global
+    from kinpoly_amd.ppo import _allreduce_grads, normalize_advantages_global
+    from kinpoly_amd.rollout import env_shard
     g = torch.Generator().manual_seed(123)
     full_adv = torch.randn(2 * 64 * 10, generator=g); full_ret = torch.randn(2 * 64 * 10, generator=g)
     n = full_adv.numel() // world
@@ -91,7 +92,7 @@ def test_freq_dict_is_one_job_wide_dict_world2():
 
 
 def test_single_process_normalisation_matches_reference_golden(golden):
-    from kinpoly_amd.rollout import normalize_advantages_global
+    from kinpoly_amd.ppo import normalize_advantages_global
     from oracle import np_oracle as O
     g = golden("gae_zfilter")
     adv_raw, ret = O.estimate_advantages(g["rewards"], g["masks"], g["values"], 0.95, 0.95)
@@ -153,7 +154,7 @@ def _spawn(fn, world, *args, timeout=240):
 def _none_grad_worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    from kinpoly_amd.rollout import _allreduce_grads
+    from kinpoly_amd.ppo import _allreduce_grads
     torch.manual_seed(0)
     a, b, c = torch.nn.Linear(3, 2), torch.nn.Linear(3, 2), torch.nn.Linear(3, 2)
     x = torch.ones(4, 3) * (rank + 1)
@@ -188,7 +189,7 @@ def _warm_start_worker(rank, world, port, q):
     from kinpoly_amd import pretrain as P
     from kinpoly_amd.context import TrajARNet
     from kinpoly_amd.model_compiler import DEFAULT_KPM, read_kpm
-    from kinpoly_amd.rollout import _allreduce_grads
+    from kinpoly_amd.ppo import _allreduce_grads
     from kinpoly_amd.supervised import TorchFK
     kpm = read_kpm(DEFAULT_KPM)
     fk = TorchFK(kpm["body_pos"], kpm["body_parent"], "cpu", dtype=torch.float64)

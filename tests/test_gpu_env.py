@@ -171,7 +171,8 @@ def test_ar_mode_and_fail_safe():
 
 def test_sampler_autoreset_and_ppo_update():
     from kinpoly_amd.nets import KinPolicy, MLP, Value
-    from kinpoly_amd.rollout import PPOTrainer, VectorSampler
+    from kinpoly_amd.ppo import PPOTrainer
+    from kinpoly_amd.rollout import VectorSampler
     n, T = 64, 12
     env, _ = _mk_env(n, T=8, mode="train", seed=1)      # clip length 8 => episodes end every 7 steps
     torch.manual_seed(1)

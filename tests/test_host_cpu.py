@@ -143,10 +143,10 @@ def test_product_never_imports_oracle():
 
 
 def test_ppo_surrogate_and_log_prob_match_reference(golden):
-    """KinPolicy.log_prob (DiagGaussian) + rollout.ppo_surrogate against AgentPPO.ppo_loss run in the reference (fixture)."""
+    """KinPolicy.log_prob (DiagGaussian) + ppo.ppo_surrogate against AgentPPO.ppo_loss run in the reference (fixture)."""
     import torch
     from kinpoly_amd.nets import KinPolicy
-    from kinpoly_amd.rollout import ppo_surrogate
+    from kinpoly_amd.ppo import ppo_surrogate
     g = golden("ppo_loss")
     pol = KinPolicy(log_std=float(g["log_std"])).double()
     pol.action_log_std.data.fill_(float(g["log_std"]))      # the fp32-constructed parameter carries -3.2 rounded to float

@@ -137,7 +137,7 @@ def test_fp64_master_copies_feed_fp32_rollout_modules(golden):
 
 
 def test_gae_scan_equals_the_reference_recurrence(golden):
-    from kinpoly_amd.rollout import gae_scan
+    from kinpoly_amd.ppo import gae_scan
     g = golden("gae_zfilter")
     n = g["rewards"].shape[0]
     r, m, v = (torch.tensor(np.asarray(g[k]).reshape(1, n)) for k in ("rewards", "masks", "values"))

@@ -35,7 +35,7 @@ def main():
                 print(f"horizon {hz} iter {it}: episodes {int(done.sum())} fails {int(fails.sum())} | done per step index:", done.sum(0).int().tolist(), flush=True)
             agent.trainer.update(batch)
             from kinpoly_amd.supervised import update_supervised_step
-            from kinpoly_amd.rollout import _allreduce_grads
+            from kinpoly_amd.ppo import _allreduce_grads
             update_supervised_step(agent.policy_net, agent.opt_sup, agent.fk, batch, 20, _allreduce_grads)
         pc = np.asarray(batch.episodes["percent"])
         print(f"horizon {hz}: percent of the finished episodes: mean {pc.mean():.3f}, quantiles", np.quantile(pc, [0.1, 0.5, 0.9]).round(3).tolist(), "share == 1:", float((pc == 1).mean()), flush=True)

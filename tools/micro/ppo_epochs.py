@@ -12,7 +12,7 @@ sys.path.insert(0, ROOT)
 
 
 def epochs(agent, batch, n_ep):
-    from kinpoly_amd.rollout import estimate_advantages, ppo_surrogate
+    from kinpoly_amd.ppo import estimate_advantages, ppo_surrogate
     tr, pol = agent.trainer, agent.policy_net
     N, T, _ = batch.states.shape
     flat = batch.states.reshape(N * T, -1)
