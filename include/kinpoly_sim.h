@@ -508,6 +508,38 @@ int kp_sim_uhc_assign(kp_sim*, const kp_takes*, const kp_uhc_state* st, const kp
 const char* kp_last_error(void);
 const char* kp_version(void);
 
+/* ---- the backward side of the kinematic roll-out in train form (kinpoly_amd/csrc/kp_kin_tape.hip) ----
+ *
+ * TrajARNet.forward with a tape (kin_poly/models/traj_ar_smpl_net.py:346-383): the three gradients autograd takes through get_obs (:203-290), step
+ * (:292-330) and get_qvel_fd_batch (kin_poly/utils/torch_utils.py:315-331), as one kernel beside each forward kernel.  fp32, rows independent, no
+ * atomics.  They are the derivatives of the forward KERNELS' formulas: a rotation normalises its quaternion there, so a raw root quaternion gets no
+ * radial gradient.  Every entry refuses (-1, kp_last_error, nothing launched) a null required pointer and a negative row count; zero rows do nothing.
+ *
+ * kp_kin_advance_backward: (d kp_kin_advance)^T.  qpos [n,76], kin_action [n,80], dt: the forward call's inputs; grad_next_qpos [n,76] and
+ * grad_qvel [n,75]: cotangents of its outputs, either may be NULL (zero); -> grad_qpos [n,76], grad_action [n,80].  Rows of the forward kernel's
+ * `no rotation` branch (dt * angv exactly zero, or |xyz| of next (x) cur^-1 exactly zero) get a zero angular-velocity gradient, as torch.where
+ * gives in get_qvel_fd_batch; rows with 0 < |dt * angv| < 1e-12 (quat_from_expmap's guard) are outside the domain. */
+int kp_kin_advance_backward(int n, const float* qpos, const float* kin_action, float dt, const float* grad_next_qpos, const float* grad_qvel,
+                            float* grad_qpos, float* grad_action, void* hip_stream);
+
+/* (d kp_sim_obs_ar)^T for the first n_rows (<= N) rows of the handle's layout (get_ar_obs_v1, humanoid_ar_v1.py:133-214; TrajARNet.get_obs,
+ * traj_ar_smpl_net.py:203-290): grad_obs [n_rows, grad_width], grad_width = kp_sim_ar_obs_dim (refused otherwise); grad_obj_2_head [n_rows,7]
+ * (may be NULL) is added to the object block's cotangent (the loss reads that block as a feature, :281-287).  qpos [n_rows,76] are the rows the
+ * observation was taken of, wbpos / wbquat their kp_sim_fk outputs; ctx as for kp_sim_obs_ar (head_pose, action_one_hot, obj_qpos, cur_t, row).
+ * -> grad_qpos [n_rows,76]: the local pose block's part only; grad_qvel [n_rows,75]: the velocity block's cotangent (use_vel layouts, else
+ * ignored and may be NULL); grad_hpos [n_rows,3], grad_hquat [n_rows,4]: cotangents of the head's position and world quaternion, for
+ * kp_sim_fk_head_backward.  The 81 / 156 layouts (use_head and use_action both off, which Config refuses) are refused. */
+int kp_sim_obs_ar_backward(kp_sim*, const kp_ctx* ctx, int n_rows, int grad_width, const float* qpos, const float* wbpos, const float* wbquat,
+                           const float* grad_obs, const float* grad_obj_2_head, float* grad_qpos, float* grad_qvel, float* grad_hpos, float* grad_hquat);
+
+/* kp_sim_fk_backward plus the head's world quaternion (Humanoid.qpos_fk, kin_poly/utils/torch_smpl_humanoid.py:125-202, as get_obs reads it,
+ * traj_ar_smpl_net.py:222-230): grad_qpos [n_rows,76] = (d wbpos / d qpos)^T (grad_wbpos [n_rows,72] with grad_hpos [n_rows,3] added to the head's
+ * slot) + (d head quaternion / d qpos)^T grad_hquat [n_rows,4] + grad_qpos_add [n_rows,76].  The four cotangents may each be NULL (zero);
+ * grad_qpos_add may be grad_qpos itself. */
+int kp_sim_fk_head_backward(kp_sim*, int n_rows, const float* qpos, const float* wbpos, const float* wbquat, const float* grad_wbpos,
+                            const float* grad_hpos, const float* grad_hquat, const float* grad_qpos_add, float* grad_qpos);
+
+
 #ifdef __cplusplus
 }
 #endif

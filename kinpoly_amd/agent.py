@@ -120,20 +120,24 @@ class AgentAR:
     def _setup_supervised_optimizer(self):
         self.upd.setup_supervised_optimizer()
 
-    def train_init(self, warm_update_init=500, warm_update_full=50, num_sample=2000, batch_size=256, scheduled_sampling=0.3, noise_std=0.0):
+    def train_init(self, warm_update_init=500, warm_update_full=50, num_sample=2000, batch_size=256, scheduled_sampling=0.3, noise_std=0.0, fused=False):
         """AgentAR.train_init (agent_ar.py:366-385), run once before the first iteration of a fresh run: `update_init_supervised` x
         warm_update_init epochs (the context network learns the clip's first pose), `train_full_supervised(scheduled_sampling=0.3)` x
         warm_update_full epochs (whole-clip kinematic roll-outs against the GT clip), then fresh supervised optimiser / schedule
         (`setup_optimizers`).  cfg.num_sample / cfg.batch_size clips per epoch; kinpoly_amd/pretrain.py.  Gradients are all-reduced over ranks
         (over a fixed parameter list); the scheduled-sampling coins come from ONE job-wide stream, so every rank throws the same frames back
-        onto the GT clip and the same parameters get a gradient everywhere."""
+        onto the GT clip and the same parameters get a gradient everywhere.  fused: the whole-clip roll-outs run on the taped HIP
+        kernels (kinpoly_amd/kin_tape.py; fp32 only, raises otherwise)."""
         from . import pretrain as P
         ds = self.source.dataset
         assert ds is not None and "wbpos" in ds.data, "the warm start needs a training data set (GT joint positions)"
         u = self.upd
+        if fused:                      # refused before the first epoch of either phase
+            from . import kin_tape
+            kin_tape.check_fused(u.policy, u.fk)
         li = P.update_init_supervised(u.policy, u.opt_sup, u.fk, ds, warm_update_init, num_sample, batch_size, grad_allreduce=_allreduce_grads)
         lf = P.train_full_supervised(u.policy, u.opt_sup, u.fk, ds, warm_update_full, scheduled_sampling, num_sample, batch_size,
-                                     noise_std=noise_std, scheduler=u.sched_sup, grad_allreduce=_allreduce_grads, rng=P.job_wide_rng(-1))
+                                     noise_std=noise_std, scheduler=u.sched_sup, grad_allreduce=_allreduce_grads, rng=P.job_wide_rng(-1), fused=fused)
         u.setup_supervised_optimizer()
         u.sync_rollout()
         self.restart_sampler()

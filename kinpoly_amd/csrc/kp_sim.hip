@@ -22,6 +22,7 @@
 #include "kp_step_kernel.hpp"
 #include "kp_pose_contacts.hpp"
 #include "kp_takes.hpp"
+#include "kp_kin_tape.hpp"
 
 namespace {
 thread_local std::string g_err;
@@ -1376,6 +1377,53 @@ double kp_sim_timing_mean_seconds(kp_sim* s, int* n_launches) {
     }
     if (n_launches) *n_launches = tm.ring_used;
     return tot * 1e-3 / tm.ring_used;
+}
+
+// ---- the backward side of the kinematic roll-out (kp_kin_tape.hip): every refusal comes before any launch
+int kp_kin_advance_backward(int n, const float* qpos, const float* kin_action, float dt, const float* grad_next_qpos, const float* grad_qvel,
+                            float* grad_qpos, float* grad_action, void* stream) {
+    if (n < 0) return fail("kp_kin_advance_backward: n < 0");
+    if (!qpos || !kin_action) return fail("kp_kin_advance_backward: null qpos / kin_action");
+    if (!grad_qpos || !grad_action) return fail("kp_kin_advance_backward: null output");
+    if (!(dt > 0.f)) return fail("kp_kin_advance_backward: dt must be positive");
+    if (n == 0) return 0;
+    HIP_OK(kp::launch_kin_advance_grad(kp::KinAdvanceGradArgs{n, qpos, kin_action, dt, grad_next_qpos, grad_qvel, grad_qpos, grad_action}, (hipStream_t)stream));
+    return 0;
+}
+
+int kp_sim_obs_ar_backward(kp_sim* s, const kp_ctx* c, int n_rows, int grad_width, const float* qpos, const float* wbpos, const float* wbquat,
+                           const float* grad_obs, const float* grad_obj_2_head, float* grad_qpos, float* grad_qvel, float* grad_hpos, float* grad_hquat) {
+    if (!s) return fail("kp_sim_obs_ar_backward: null sim");
+    if (!s->ar_obs_head && !s->ar_obs_action)
+        return fail("kp_sim_obs_ar_backward: the " + std::to_string(s->ar_obs_dim) + "-d layout (use_head and use_action both off) has no gradient kernel");
+    if (n_rows < 0 || n_rows > s->n) return fail("kp_sim_obs_ar_backward: n_rows must be in [0, " + std::to_string(s->n) + "], got " + std::to_string(n_rows));
+    if (grad_width != s->ar_obs_dim)
+        return fail("kp_sim_obs_ar_backward: grad_obs is " + std::to_string(grad_width) + " wide, the handle's observation " + std::to_string(s->ar_obs_dim));
+    if (!c || !c->action_one_hot || !c->cur_t || c->T < 1 || (s->ar_obs_head && !c->head_pose)) return fail("kp_sim_obs_ar_backward: null or empty context");
+    if (!qpos || !wbpos || !wbquat || !grad_obs) return fail("kp_sim_obs_ar_backward: null qpos / wbpos / wbquat / grad_obs");
+    if (!grad_qpos || !grad_hpos || !grad_hquat || (s->ar_obs_vel && !grad_qvel)) return fail("kp_sim_obs_ar_backward: null output");
+    if (n_rows == 0) return 0;
+    HIP_OK(hipSetDevice(s->device));
+    kp::ObsArGradArgs A{};
+    A.n = n_rows; A.vel = s->ar_obs_vel; A.head = s->ar_obs_head; A.width = s->ar_obs_dim;
+    A.T = c->T; A.head_pose = c->head_pose; A.action_one_hot = c->action_one_hot; A.obj_qpos = c->obj_qpos; A.cur_t = c->cur_t; A.row = c->row;
+    A.qpos = qpos; A.wbpos = wbpos; A.wbquat = wbquat; A.g_obs = grad_obs; A.g_obj = grad_obj_2_head;
+    A.g_qpos = grad_qpos; A.g_qvel = grad_qvel; A.g_hpos = grad_hpos; A.g_hquat = grad_hquat;
+    HIP_OK(kp::launch_obs_ar_grad(A, s->stream));
+    return 0;
+}
+
+int kp_sim_fk_head_backward(kp_sim* s, int n_rows, const float* qpos, const float* wbpos, const float* wbquat, const float* grad_wbpos,
+                            const float* grad_hpos, const float* grad_hquat, const float* grad_qpos_add, float* grad_qpos) {
+    if (!s) return fail("kp_sim_fk_head_backward: null sim");
+    if (n_rows < 0) return fail("kp_sim_fk_head_backward: n_rows < 0");
+    if (!qpos || !wbpos || !wbquat) return fail("kp_sim_fk_head_backward: null qpos / wbpos / wbquat");
+    if (!grad_qpos) return fail("kp_sim_fk_head_backward: null output");
+    if (n_rows == 0) return 0;
+    HIP_OK(hipSetDevice(s->device));
+    HIP_OK(kp::launch_fk_head_grad(kp::FkHeadGradArgs{n_rows, qpos, wbpos, wbquat, grad_wbpos, grad_hpos, grad_hquat, grad_qpos_add, grad_qpos,
+                                                      s->T.body_parent, s->T.body_subtree}, s->stream));
+    return 0;
 }
 
 }  // extern "C"

@@ -63,7 +63,8 @@ def forward_supervised(net, fk: TorchFK, data, gt_rate=0.0, rng=None, noise_std=
     hx = torch.zeros((B, net.rnn_hdim), device=qpos.device, dtype=qpos.dtype)
     Q, V, A, W, O = [], [], [], [], []
     for t in range(T):
-        obs, wb, orel = observe(fk, qpos, data, t, noise_std, generator, getattr(net, "use_action", True), getattr(net, "use_vel", False),
+        # obs_action: a network whose state lacks the one-hot although its context GRU reads it (exp_arnet.build_net, the reference's as_policy=False)
+        obs, wb, orel = observe(fk, qpos, data, t, noise_std, generator, getattr(net, "obs_action", getattr(net, "use_action", True)), getattr(net, "use_vel", False),
                                 getattr(net, "use_head", True), qvel)
         Q.append(qpos); V.append(qvel); W.append(wb); O.append(orel)
         action, hx = net.get_action(obs, hx)
@@ -157,13 +158,19 @@ def update_init_supervised(net, optimizer, fk: TorchFK, dataset, num_epoch=500, 
 
 
 def train_full_supervised(net, optimizer, fk: TorchFK, dataset, num_epoch=50, scheduled_sampling=0.3, num_sample=2000, batch_size=256, weights=None,
-                          noise_std=0.0, scheduler=None, rng=None, grad_allreduce=None):
-    """PolicyAR.train_full_supervised (:243-258): whole-clip roll-outs against the GT clip with scheduled sampling; `scheduler.step()` per epoch."""
+                          noise_std=0.0, scheduler=None, rng=None, grad_allreduce=None, fused=False):
+    """PolicyAR.train_full_supervised (:243-258): whole-clip roll-outs against the GT clip with scheduled sampling; `scheduler.step()` per epoch.
+    fused: the roll-out and its backward pass on the HIP kernels (kin_tape.forward_supervised_taped) instead of torch ops; fp32 on the device only."""
     dev = next(net.parameters()).device
     last = None
+    forward = forward_supervised
+    if fused:
+        from . import kin_tape
+        kin_tape.check_fused(net, fk)
+        forward = kin_tape.forward_supervised_taped
     for _ in range(num_epoch):
         for data in sampling_batches(dataset, num_sample, batch_size, dev, next(net.parameters()).dtype):
-            pred = forward_supervised(net, fk, data, scheduled_sampling, rng, noise_std)
+            pred = forward(net, fk, data, scheduled_sampling, rng, noise_std)
             loss, _ = compute_loss(pred, data, weights)
             optimizer.zero_grad(); loss.backward()
             if grad_allreduce is not None:

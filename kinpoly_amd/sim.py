@@ -124,6 +124,10 @@ _SIGNATURES = {
     "kp_kin_advance": (_I, [_I, _V, _V, _F, _V, _V, _V]), "kp_gru_cell_step": (_I, [_I, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     "kp_gae": (_I, [_I, _I, _V, _V, _V, _F, _F, _V, _V, _V]), "kp_gae_bootstrap": (_I, [_I, _I, _V, _V, _V, _V, _F, _F, _V, _V, _V]),
     "kp_gru_gates_forward": (_I, [_I, _I, _V, _V, _V, _V, _V, _V, _V]), "kp_gru_gates_backward": (_I, [_I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    # the backward side of the kinematic roll-out (kp_kin_tape.hip)
+    "kp_kin_advance_backward": (_I, [_I, _V, _V, _F, _V, _V, _V, _V, _V]),
+    "kp_sim_obs_ar_backward": (_I, [_V, _CTX, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    "kp_sim_fk_head_backward": (_I, [_V, _I, _V, _V, _V, _V, _V, _V, _V, _V]),
 }
 ABI_SYMBOLS = list(_SIGNATURES)
 
@@ -377,6 +381,30 @@ class KpSim:
         ins = [_dev("fk_backward: " + k, t, (R, d)) for k, t, d in (("qpos_rows", qpos_rows, NQ), ("wbpos", wbpos, 72), ("wbquat", wbquat, 96), ("grad_wbpos", grad_wbpos, 72))]
         out = torch.empty((R, NQ), dtype=torch.float32, device=self.device)
         _check(self.L.kp_sim_fk_backward(self.h, R, *ins, C.c_void_p(out.data_ptr())), "kp_sim_fk_backward")
+        return out
+
+    def obs_ar_backward(self, ctx: "KpCtx", qpos_rows, wbpos, wbquat, grad_obs, grad_obj_2_head=None):
+        """(d obs_ar)^T grad_obs for the first R <= N rows (kp_sim_obs_ar_backward; wbpos / wbquat: fk() of qpos_rows) -> (grad_qpos [R,76], the local
+        pose block's part; grad_qvel [R,75] or None without use_vel; grad_hpos [R,3]; grad_hquat [R,4]).  grad_obj_2_head [R,7]: cotangent of the
+        object block read as a feature, added to that block's."""
+        _dev("obs_ar_backward: grad_obs", grad_obs, (None, None))
+        R, W = grad_obs.shape
+        ins = [_dev("obs_ar_backward: " + k, t, (R, d)) for k, t, d in (("qpos_rows", qpos_rows, NQ), ("wbpos", wbpos, 72), ("wbquat", wbquat, 96), ("grad_obs", grad_obs, W),
+                                                                          ("grad_obj_2_head", grad_obj_2_head, 7))]
+        new = lambda d: torch.empty((R, d), dtype=torch.float32, device=self.device)      # noqa: E731
+        gq, gv, gp, gh = new(NQ), (new(NV) if self.obs_ar_vel else None), new(3), new(4)
+        _check(self.L.kp_sim_obs_ar_backward(self.h, C.byref(ctx), R, W, *ins, *[None if o is None else C.c_void_p(o.data_ptr()) for o in (gq, gv, gp, gh)]),
+               "kp_sim_obs_ar_backward")
+        return gq, gv, gp, gh
+
+    def fk_head_backward(self, qpos_rows, wbpos, wbquat, grad_wbpos=None, grad_hpos=None, grad_hquat=None, grad_qpos_add=None):
+        """fk_backward plus the head's world quaternion (kp_sim_fk_head_backward): (d wbpos / d qpos)^T (grad_wbpos, grad_hpos added to the head's slot)
+        + (d head quaternion / d qpos)^T grad_hquat + grad_qpos_add -> [R,76]; a None cotangent is zero."""
+        R = qpos_rows.shape[0]
+        ins = [_dev("fk_head_backward: " + k, t, (R, d)) for k, t, d in (("qpos_rows", qpos_rows, NQ), ("wbpos", wbpos, 72), ("wbquat", wbquat, 96), ("grad_wbpos", grad_wbpos, 72),
+                                                                           ("grad_hpos", grad_hpos, 3), ("grad_hquat", grad_hquat, 4), ("grad_qpos_add", grad_qpos_add, NQ))]
+        out = torch.empty((R, NQ), dtype=torch.float32, device=self.device)
+        _check(self.L.kp_sim_fk_head_backward(self.h, R, *ins, C.c_void_p(out.data_ptr())), "kp_sim_fk_head_backward")
         return out
 
     def pose_contacts(self, qpos_rows: torch.Tensor, obj_qpos: torch.Tensor | None = None, pen_margin: float = 0.005) -> dict:
@@ -658,6 +686,18 @@ def kin_advance(qpos: torch.Tensor, action: torch.Tensor, dt: float = 1.0 / 30.0
     _check(L.kp_kin_advance(n, qp, ap, float(dt), C.c_void_p(next_qpos.data_ptr()), C.c_void_p(qvel.data_ptr()),
                             C.c_void_p(stream)), "kp_kin_advance")
     return next_qpos, qvel
+
+
+def kin_advance_backward(qpos: torch.Tensor, action: torch.Tensor, dt: float, grad_next_qpos: torch.Tensor | None, grad_qvel: torch.Tensor | None):
+    """(d kin_advance)^T (kp_kin_advance_backward): cotangents of next_qpos [N,76] / qvel [N,75] (None: zero) -> (grad_qpos [N,76], grad_action [N,80])."""
+    L = load_library()
+    n = qpos.shape[0]
+    ins = [_dev("kin_advance_backward: " + k, t, (n, d)) for k, t, d in (("qpos", qpos, NQ), ("action", action, 80))]
+    gs = [_dev("kin_advance_backward: " + k, t, (n, d)) for k, t, d in (("grad_next_qpos", grad_next_qpos, NQ), ("grad_qvel", grad_qvel, NV))]
+    gq, ga = torch.empty((n, NQ), device=qpos.device), torch.empty((n, 80), device=qpos.device)
+    stream = torch.cuda.current_stream(qpos.device).cuda_stream
+    _check(L.kp_kin_advance_backward(n, *ins, float(dt), *gs, C.c_void_p(gq.data_ptr()), C.c_void_p(ga.data_ptr()), C.c_void_p(stream)), "kp_kin_advance_backward")
+    return gq, ga
 
 
 def gru_cell_step(gi: torch.Tensor, gh: torch.Tensor, b_ih: torch.Tensor, b_hh: torch.Tensor, h: torch.Tensor, state: torch.Tensor | None = None,

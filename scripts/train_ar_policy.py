@@ -46,6 +46,8 @@ def main():
     ap.add_argument("--iter", type=int, default=0, help="resume from models_policy/iter_%%04d.p (the reference's --iter)")
     ap.add_argument("--warm_start", action="store_true", help="AgentAR.train_init before the first iteration of a fresh run: supervised warm start of the kinematic policy "
                     "(policy_specs.warm_update_init / warm_update_full epochs, default 500 / 50; the reference always runs it at --iter 0)")
+    ap.add_argument("--fused_warm_start", action="store_true", help="with --warm_start: the whole-clip roll-outs of train_full_supervised on the taped HIP kernels "
+                    "(kinpoly_amd/kin_tape.py) instead of torch ops; fp32 only (refused with --update_dtype fp64)")
     ap.add_argument("--warm_update_init", type=int, default=None); ap.add_argument("--warm_update_full", type=int, default=None)
     ap.add_argument("--num_sample", type=int, default=None); ap.add_argument("--batch_size", type=int, default=None)
     ap.add_argument("--cc_ckpt", type=str, default="", help="trained UHC checkpoint in the reference's layout (scripts/train_uhc.py --save); with --cfg the default is "
@@ -143,7 +145,7 @@ def main():
         pick = lambda a, d: d if a is None else a      # noqa: E731
         ws = agent.train_init(pick(args.warm_update_init, int(ps.get("warm_update_init", 500))), pick(args.warm_update_full, int(ps.get("warm_update_full", 50))),
                               pick(args.num_sample, int(y.get("num_sample", 20000))), pick(args.batch_size, int(y.get("batch_size", 128))),
-                              noise_std=float(y.get("noise_std", 0.0)) if y.get("add_noise", False) else 0.0)
+                              noise_std=float(y.get("noise_std", 0.0)) if y.get("add_noise", False) else 0.0, fused=args.fused_warm_start)
         if rank == 0:
             print(json.dumps({"warm_start": ws}), flush=True)
             if cfg is not None:
