@@ -454,11 +454,22 @@ int kp_sim_phase_cycles_env(kp_sim*, double* out_host);
  *
  * kp_takes_create: qpos_rows [R,76] on the host (rows_on_device = 0) or on the handle's device; take_off_host: K + 1 increasing offsets on
  * the host, take_off_host[0] == 0, take_off_host[K] == R, every take at least 2 rows, K >= 1; dt = env.dt (1 / 30; a finite difference is multiplied by (float)(1 / dt)).  Returns NULL and sets
- * kp_last_error on a bad argument (nothing is launched).  The library keeps no reference to qpos_rows.  Synchronises the handle's stream once. */
+ * kp_last_error on a bad argument (nothing is launched).  The library keeps no reference to qpos_rows.  Synchronises the handle's stream once.
+ *
+ * kp_takes_create_obj: the same with obj_rows [R,35], the object block data.qpos[76:111] of every row as DatasetSMPLObj.convert_obj_qpos builds it
+ * (uhc/data_loaders/dataset_smpl_obj.py:230-243: five objects, the inactive ones parked 100+ m away), on the same side as qpos_rows (one
+ * rows_on_device for both).  The library keeps a copy as the table "obj_pose" [R,35], beside the tables above, and kp_sim_uhc_assign places the
+ * objects from it.  obj_rows == NULL is kp_takes_create.  Refused, besides kp_takes_create's errors, before anything is launched: a model blob
+ * without object geoms (or with more than 64), obj_rows in host memory with rows_on_device = 1 or in device memory with rows_on_device = 0.
+ * What is still refused elsewhere: the UHC observation and reward read nothing of the objects (the reference's have no such term). */
 typedef struct kp_takes kp_takes;
 kp_takes* kp_takes_create(kp_sim*, const float* qpos_rows, int rows_on_device, const int32_t* take_off_host, int n_takes, double dt);
+kp_takes* kp_takes_create_obj(kp_sim*, const float* qpos_rows, const float* obj_rows, int rows_on_device, const int32_t* take_off_host, int n_takes, double dt);
 void kp_takes_destroy(kp_takes*);
-/* device pointer, row count (R, or K for the per-take tables) and width of a table by its name above; -1 for an unknown name */
+/* 1: the library was built with obj_rows (it answers "obj_pose"); 0: without, or a NULL library */
+int kp_takes_has_objects(const kp_takes*);
+/* device pointer, row count (R, or K for the per-take tables) and width of a table by its name above, or "obj_pose" [R,35] of a library with
+ * objects; -1 for an unknown name and for "obj_pose" on a library without objects */
 int kp_takes_table(const kp_takes*, const char* name, const float** ptr, int* rows, int* width);
 /* K, R and (lens_host != NULL) the K take lengths */
 int kp_takes_info(const kp_takes*, int* n_takes, int* n_rows, int32_t* lens_host);
@@ -501,7 +512,12 @@ int kp_sim_uhc_track(kp_sim*, const kp_takes*, const kp_uhc_state* st, const kp_
  * start_host (host int32 [N], may be NULL: keep) are checked (0 <= take_id < K, 0 <= start < len; nothing is launched on an error) and
  * assigned; keep_t == 0 zeroes cur_t; then qpos <- the take's raw row at min(start_ind + cur_t, len - 1) (+ noise [N,69] on the joint angles,
  * device, may be NULL), qvel <- that row's qvel, sim.forward(), and target / base pose as kp_sim_uhc_track leaves them.  keep_t = 1 with
- * NULL ids is fail_safe(). */
+ * NULL ids is fail_safe().
+ * A library with objects (kp_takes_create_obj): with keep_t == 0 the same launch installs the env's object block from the library row the humanoid
+ * state comes from (reset_model's has_obj branch, :613-616) -- pose, zero velocities and warm start, and the slot list (dynamic_objects) or the
+ * frozen world-frame geoms, exactly what kp_sim_set_objects installs from that row -- and the handle runs the object layout from then on, as after
+ * kp_sim_set_objects.  keep_t == 1 leaves the object block alone (fail_safe overwrites qpos[:76] / qvel[:75] only, :235-238); envs outside the mask
+ * are untouched.  Needs threads_per_env = 64 (-1, nothing launched).  A library without objects never touches the object block. */
 int kp_sim_uhc_assign(kp_sim*, const kp_takes*, const kp_uhc_state* st, const kp_uhc_cfg* cfg, const uint8_t* env_mask,
                       const int32_t* take_ids_host, const int32_t* start_host, int keep_t, const float* noise);
 

@@ -115,6 +115,7 @@ struct kp_takes {
     const kp_model* model = nullptr;
     int device = 0;
     kp::TakeTables L{};
+    float* obj = nullptr;                             // [R,35] the rows' object block (kp_takes_create_obj), or null: a library without objects
     std::vector<int32_t> off;
     std::vector<void*> allocs;
 };
@@ -847,16 +848,28 @@ int kp_sim_step_ctrl_base(kp_sim* s, const float* action, int nsub, const uint8_
     return launch_step(s, action, nsub, mask, true, base_qpos);
 }
 
-kp_takes* kp_takes_create(kp_sim* s, const float* qpos_rows, int rows_on_device, const int32_t* take_off, int K, double dt) {
-    if (!s || !qpos_rows || !take_off) { fail("kp_takes_create: null argument"); return nullptr; }
-    if (K < 1) { fail("kp_takes_create: n_takes must be at least 1, got " + std::to_string(K)); return nullptr; }
-    if (!(dt > 0.0)) { fail("kp_takes_create: dt must be positive"); return nullptr; }
-    if (take_off[0] != 0) { fail("kp_takes_create: take_off[0] must be 0, got " + std::to_string(take_off[0])); return nullptr; }
+// kp_takes_create (obj_rows null) and kp_takes_create_obj
+static kp_takes* takes_create(const std::string& w, kp_sim* s, const float* qpos_rows, const float* obj_rows, int rows_on_device, const int32_t* take_off, int K, double dt) {
+    if (!s || !qpos_rows || !take_off) { fail(w + ": null argument"); return nullptr; }
+    if (K < 1) { fail(w + ": n_takes must be at least 1, got " + std::to_string(K)); return nullptr; }
+    if (!(dt > 0.0)) { fail(w + ": dt must be positive"); return nullptr; }
+    if (take_off[0] != 0) { fail(w + ": take_off[0] must be 0, got " + std::to_string(take_off[0])); return nullptr; }
     for (int k = 0; k < K; k++) {
-        if (take_off[k + 1] <= take_off[k]) { fail("kp_takes_create: take_off must be increasing (take " + std::to_string(k) + ")"); return nullptr; }
-        if (take_off[k + 1] - take_off[k] < 2) { fail("kp_takes_create: take " + std::to_string(k) + " has one row; a take needs at least 2"); return nullptr; }
+        if (take_off[k + 1] <= take_off[k]) { fail(w + ": take_off must be increasing (take " + std::to_string(k) + ")"); return nullptr; }
+        if (take_off[k + 1] - take_off[k] < 2) { fail(w + ": take " + std::to_string(k) + " has one row; a take needs at least 2"); return nullptr; }
     }
+    if (obj_rows && !s->obj.d_geoms) { fail(w + ": obj_rows given but the model blob has no object geoms"); return nullptr; }
+    if (obj_rows && s->obj.n_geoms > 64) { fail(w + ": the model has more object geoms than the reset kernel has lanes (64)"); return nullptr; }
     HIP_OK_NULL(hipSetDevice(s->device));
+    if (obj_rows) {                                   // one flag describes both arrays: obj_rows must live where it says qpos_rows does
+        hipPointerAttribute_t at{};
+        const bool on_dev = hipPointerGetAttributes(&at, obj_rows) == hipSuccess && at.type == hipMemoryTypeDevice;
+        (void)hipGetLastError();                      // a plain host pointer is "invalid value" to some runtimes: not an error here
+        if (on_dev != (rows_on_device != 0)) {
+            fail(w + ": obj_rows is " + (on_dev ? "device" : "host") + " memory but rows_on_device = " + std::to_string(rows_on_device) + " (qpos_rows and obj_rows must be on the same side)");
+            return nullptr;
+        }
+    }
     kp_takes* t = new kp_takes();
     t->model = s->model; t->device = s->device; t->off.assign(take_off, take_off + K + 1);
     const int R = take_off[K];
@@ -875,20 +888,33 @@ kp_takes* kp_takes_create(kp_sim* s, const float* qpos_rows, int rows_on_device,
     int32_t* d_off = (int32_t*)alloc(sizeof(int32_t) * (K + 1));
     int32_t* d_rt = (int32_t*)alloc(sizeof(int32_t) * (size_t)R);
     t->L.take_off = d_off; t->L.row_take = d_rt;
-    auto bail = [&](const std::string& m) -> kp_takes* { fail(m); kp_takes_destroy(t); return nullptr; };
-    if (!ok) return bail("kp_takes_create: device allocation failed");
+    if (obj_rows) t->obj = (float*)alloc(sizeof(float) * (size_t)R * 35);
+    auto bail = [&](const std::string& m) -> kp_takes* { fail(w + m); kp_takes_destroy(t); return nullptr; };
+    if (!ok) return bail(": device allocation failed");
     if (hipMemcpy(d_off, take_off, sizeof(int32_t) * (K + 1), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_rt, row_take.data(), sizeof(int32_t) * (size_t)R, hipMemcpyHostToDevice) != hipSuccess)
-        return bail("kp_takes_create: upload of the take offsets failed");
+        return bail(": upload of the take offsets failed");
     if (hipMemcpyAsync(t->L.tab[kp::TT_QPOS], qpos_rows, sizeof(float) * (size_t)R * 76, rows_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream) != hipSuccess)
-        return bail("kp_takes_create: copy of qpos_rows failed");
+        return bail(": copy of qpos_rows failed");
+    if (obj_rows && hipMemcpyAsync(t->obj, obj_rows, sizeof(float) * (size_t)R * 35, rows_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream) != hipSuccess)
+        return bail(": copy of obj_rows failed");
     launch_target_fk(s, R, t->L.tab[kp::TT_QPOS], nullptr,
                      kp::TargetBufs{t->L.tab[kp::TT_QPOS_FK], t->L.tab[kp::TT_WBPOS], t->L.tab[kp::TT_WBQUAT], t->L.tab[kp::TT_BQUAT], t->L.tab[kp::TT_BODY_COM]});
     kp::TakeBuildArgs A{t->L, s->T.body_mass, (float)(1.0 / dt)};
     if (hipGetLastError() != hipSuccess || kp::launch_take_tables(A, s->stream) != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess)
-        return bail("kp_takes_create: building the tables failed");
+        return bail(": building the tables failed");
     return t;
 }
+
+kp_takes* kp_takes_create(kp_sim* s, const float* qpos_rows, int rows_on_device, const int32_t* take_off, int K, double dt) {
+    return takes_create("kp_takes_create", s, qpos_rows, nullptr, rows_on_device, take_off, K, dt);
+}
+
+kp_takes* kp_takes_create_obj(kp_sim* s, const float* qpos_rows, const float* obj_rows, int rows_on_device, const int32_t* take_off, int K, double dt) {
+    return takes_create("kp_takes_create_obj", s, qpos_rows, obj_rows, rows_on_device, take_off, K, dt);
+}
+
+int kp_takes_has_objects(const kp_takes* t) { return t && t->obj ? 1 : 0; }
 
 void kp_takes_destroy(kp_takes* t) {
     if (!t) return;
@@ -909,6 +935,13 @@ int kp_takes_table(const kp_takes* t, const char* name, const float** ptr, int* 
             if (width) *width = kp::TAKE_TAB_WIDTH[i];
             return 0;
         }
+    if (!std::strcmp(name, "obj_pose")) {             // kept beside the table set: only a library built by kp_takes_create_obj with obj_rows has it
+        if (!t->obj) return fail("kp_takes_table: 'obj_pose' asked of a library without objects");
+        if (ptr) *ptr = t->obj;
+        if (rows) *rows = t->L.R;
+        if (width) *width = 35;
+        return 0;
+    }
     return fail(std::string("kp_takes_table: no table named '") + name + "'");
 }
 
@@ -959,6 +992,8 @@ int kp_sim_uhc_assign(kp_sim* s, const kp_takes* t, const kp_uhc_state* st, cons
         if (start && (start[e] < 0 || start[e] >= t->off[take_ids[e] + 1] - t->off[take_ids[e]]))
             return fail("kp_sim_uhc_assign: start " + std::to_string(start[e]) + " of env " + std::to_string(e) + " is outside its take");
     }
+    if (t->obj && !s->obj.d_geoms) return fail("kp_sim_uhc_assign: the take library carries objects but the model blob has no object geoms");
+    if (t->obj && s->model->threads != 64) return fail("kp_sim_uhc_assign: a take library with objects needs threads_per_env = 64");
     HIP_OK(hipSetDevice(s->device));
     if (take_ids && !s->uhc_stage) {
         bool ok = true;
@@ -974,7 +1009,16 @@ int kp_sim_uhc_assign(kp_sim* s, const kp_takes* t, const kp_uhc_state* st, cons
     A.L = t->L; A.n = s->n; A.keep_t = keep_t; A.obs_v = c->obs_v; A.st = *st; A.mask = mask; A.noise = noise; A.a_ref = c->a_ref;
     A.qpos = s->st.qpos; A.qpos_d = s->st.qpos_d; A.qvel = s->st.qvel; A.qvel_d = s->st.qvel_d; A.warm = s->st.warm;
     A.t_qpos = s->tgt.qpos; A.t_wbpos = s->tgt.wbpos; A.t_wbquat = s->tgt.wbquat; A.t_bquat = s->tgt.bquat; A.t_com = s->tgt.com;
-    HIP_OK(kp::launch_uhc_assign(A, s->stream));
+    if (t->obj) {                                        // reset_model's has_obj branch: the object block comes from the same library row (k_uhc_assign_obj)
+        ObjectRows& o = s->obj;
+        kp::UhcAssignObjArgs B{};
+        B.A = A; B.obj_tab = t->obj; B.obj_qpos = o.qpos; B.obj_qvel = o.qvel; B.obj_warm = o.warm; B.geoms = o.geoms; B.ngeom = o.ngeom; B.slot = o.slot;
+        B.og = o.d_geoms; B.omass = o.d_mass; B.n_og = o.n_geoms; B.n_obj = o.n_obj;
+        B.dynamic = s->model->dynamic_objects && s->T.obj_inertial != nullptr;
+        HIP_OK(kp::launch_uhc_assign_obj(B, s->stream));
+        o.on = true;                                     // from now on the control step and the forward pass below run the object kernels
+    } else
+        HIP_OK(kp::launch_uhc_assign(A, s->stream));
     return launch_step(s, nullptr, 0, mask, false);      // sim.forward(): derived quantities at the new state
 }
 

@@ -196,12 +196,9 @@ __global__ __launch_bounds__(64) void k_uhc_track(UhcTrackArgs A) {
     tk_write_targets(L, e, ro, row, A.t_qpos, A.t_wbpos, A.t_wbquat, A.t_bquat, A.t_com, A.st.base_qpos, C.a_ref, lane);
 }
 
-// grid = n workgroups of one wavefront; the caller runs sim.forward() on the same mask afterwards
-__global__ __launch_bounds__(64) void k_uhc_assign(UhcAssignArgs A) {
+// k_uhc_assign's body for env e; returns the library row the state was read from
+__device__ __forceinline__ size_t tk_assign(const UhcAssignArgs& A, size_t e, int lane) {
     const TakeTables& L = A.L;
-    const int lane = threadIdx.x;
-    const size_t e = blockIdx.x;
-    if ((int)e >= A.n || (A.mask && !A.mask[e])) return;
     const int k = A.take_ids ? A.take_ids[e] : A.st.take_id[e];
     const int start = A.start ? A.start[e] : (A.take_ids ? 0 : A.st.start_ind[e]);
     const int t = A.keep_t ? A.st.cur_t[e] : 0;
@@ -218,6 +215,69 @@ __global__ __launch_bounds__(64) void k_uhc_assign(UhcAssignArgs A) {
     }
     const size_t ro = (size_t)o0 + (size_t)min(start + (A.obs_v == 0 ? t : t + 1), len - 1);
     tk_write_targets(L, e, ro, row, A.t_qpos, A.t_wbpos, A.t_wbquat, A.t_bquat, A.t_com, A.st.base_qpos, A.a_ref, lane);
+    return row;
+}
+
+// grid = n workgroups of one wavefront; the caller runs sim.forward() on the same mask afterwards
+__global__ __launch_bounds__(64) void k_uhc_assign(UhcAssignArgs A) {
+    const int lane = threadIdx.x;
+    const size_t e = blockIdx.x;
+    if ((int)e >= A.n || (A.mask && !A.mask[e])) return;
+    tk_assign(A, e, lane);
+}
+
+// k_uhc_assign, and for keep_t == 0 (reset_model; fail_safe leaves the objects where the physics put them) the env's object block from the same library
+// row: kp_sim.hip's k_set_objects spread over the wave.  Lanes 0..34 copy the pose, lanes 0..4 test "parked" (convert_obj_qpos parks the inactive objects
+// 100+ m away), lanes < n_og transform one geom each; an active lane's slot / geom index is the number of active lanes below it (ballot + popcount), so the
+// ascending order and the D_MAXOBJ / D_MAXGEOM caps are the serial loop's.  The geom transform is k_set_objects' expressions, operation for operation.
+__global__ __launch_bounds__(64) void k_uhc_assign_obj(UhcAssignObjArgs B) {
+    const int lane = threadIdx.x;
+    const size_t e = blockIdx.x;
+    if ((int)e >= B.A.n || (B.A.mask && !B.A.mask[e])) return;
+    const size_t row = tk_assign(B.A, e, lane);
+    if (B.A.keep_t) return;
+    const float* src = B.obj_tab + row * 35;
+    if (lane < 35) B.obj_qpos[e * 35 + lane] = src[lane];
+    if (lane < 30) B.obj_qvel[e * 30 + lane] = 0.f;
+    if (lane < 6 * D_MAXOBJ) B.obj_warm[e * 6 * D_MAXOBJ + lane] = 0.f;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if (B.dynamic) {
+        const int oi = lane;
+        bool active = oi < B.n_obj && oi < 5;
+        if (active) {
+            const float* pose = src + 7 * oi;
+            active = !(sqrtf(pose[0] * pose[0] + pose[1] * pose[1] + pose[2] * pose[2]) > 50.0f);
+        }
+        const unsigned long long bal = __ballot(active);
+        const int ns = __popcll(bal & below), total = __popcll(bal);
+        if (active && ns < D_MAXOBJ) B.slot[e * D_MAXOBJ + ns] = (signed char)oi;
+        if (lane < D_MAXOBJ && lane >= total) B.slot[e * D_MAXOBJ + lane] = -1;
+        if (lane == 0) B.ngeom[e] = 0;
+        return;
+    }
+    if (lane < D_MAXOBJ) B.slot[e * D_MAXOBJ + lane] = -1;
+    const int gi = lane;
+    bool active = gi < B.n_og;
+    const float* g = B.og + 18 * (active ? gi : 0);
+    const int oi = (int)g[0];
+    active = active && !(oi >= B.n_obj || oi >= 5);
+    const float* pose = src + 7 * (active ? oi : 0);
+    active = active && !(sqrtf(pose[0] * pose[0] + pose[1] * pose[1] + pose[2] * pose[2]) > 50.0f);
+    const unsigned long long bal = __ballot(active);
+    const int ng = __popcll(bal & below), total = __popcll(bal);
+    if (active && ng < D_MAXGEOM) {
+        Q4 q = qnormalize(Q4{pose[3], pose[4], pose[5], pose[6]});
+        float R[9], Rg[9];
+        q2mat(q, R);
+        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) Rg[3 * i + j] = R[3 * i] * g[8 + j] + R[3 * i + 1] * g[11 + j] + R[3 * i + 2] * g[14 + j];
+        V3 p = mulmat(R, ld3(g + 5));
+        float* o = B.geoms + (e * D_MAXGEOM + ng) * 17;
+        o[0] = g[1]; o[1] = g[2]; o[2] = g[3]; o[3] = g[4];
+        o[4] = pose[0] + p.x; o[5] = pose[1] + p.y; o[6] = pose[2] + p.z;
+        for (int k = 0; k < 9; k++) o[7 + k] = Rg[k];
+        o[16] = 1.0f / B.omass[oi];
+    }
+    if (lane == 0) B.ngeom[e] = min(total, D_MAXGEOM);
 }
 
 hipError_t launch_take_tables(const TakeBuildArgs& A, hipStream_t stream) {
@@ -233,6 +293,11 @@ hipError_t launch_uhc_track(const UhcTrackArgs& A, hipStream_t stream) {
 
 hipError_t launch_uhc_assign(const UhcAssignArgs& A, hipStream_t stream) {
     hipLaunchKernelGGL(k_uhc_assign, dim3(A.n), dim3(64), 0, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_uhc_assign_obj(const UhcAssignObjArgs& A, hipStream_t stream) {
+    hipLaunchKernelGGL(k_uhc_assign_obj, dim3(A.A.n), dim3(64), 0, stream, A);
     return hipGetLastError();
 }
 

@@ -5,6 +5,8 @@
 //   k_uhc_track     the tail of HumanoidEnv.step after do_simulation (uhc/envs/humanoid_im.py:527-572): cur_t, calc_body_diff, termination,
 //                   world_rfc_implicit_reward (uhc/core/reward_function.py:4-53), and the expert rows of the next observation / control step
 //   k_uhc_assign    reset_model / fail_safe (humanoid_im.py:574-623, 235-238): take, start and state of the masked envs
+//   k_uhc_assign_obj  the same for a library that carries object poses (kp_takes_create_obj): reset_model's has_obj branch (:613-616) installs the env's
+//                   object block from the library row the humanoid state comes from -- what kp_sim.hip's k_set_objects installs from a caller's rows
 //
 // One wavefront per row / take / env, lane = body; reductions are kp_collide.hpp's DPP butterflies, so there is no LDS, no atomic and every
 // store is a plain vector store.  The kernels live in their own translation unit (kp_takes.hip) for the reason kp_pose_contacts.hpp gives: the step
@@ -62,8 +64,20 @@ struct UhcAssignArgs {
     float *t_qpos, *t_wbpos, *t_wbquat, *t_bquat, *t_com;
 };
 
+// k_uhc_assign's arguments stay as they are; the object block rides beside them
+struct UhcAssignObjArgs {
+    UhcAssignArgs A;
+    const float* obj_tab;             // [R,35] data.qpos[76:111] per library row (outside TakeTables::tab: the three kernels above never see it)
+    float *obj_qpos, *obj_qvel, *obj_warm, *geoms;             // kp_sim's object rows [N,35], [N,30], [N,6 D_MAXOBJ], [N,D_MAXGEOM,17]
+    int* ngeom;
+    signed char* slot;                // [N,D_MAXOBJ]
+    const float *og, *omass;          // the model's object geoms [n_og,18] and masses [n_obj]
+    int n_og, n_obj, dynamic;         // n_og <= 64: one lane per geom
+};
+
 hipError_t launch_take_tables(const TakeBuildArgs& A, hipStream_t stream);
 hipError_t launch_uhc_track(const UhcTrackArgs& A, hipStream_t stream);
 hipError_t launch_uhc_assign(const UhcAssignArgs& A, hipStream_t stream);
+hipError_t launch_uhc_assign_obj(const UhcAssignObjArgs& A, hipStream_t stream);
 
 }  // namespace kp

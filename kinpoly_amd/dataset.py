@@ -262,8 +262,11 @@ class AmassSingleDataset:
 
     Reads the reference's take pickle `{take: {pose_aa, pose_6d, trans, qpos, obj_pose}}` from data_specs['file_path'] (data_mode 'train') or
     ['test_file_path'] ('test'), keeps the takes of at least t_min (default 90) frames in the file's order -- or, with mode 'singles', those of
-    data_specs['key_subsets'] -- and hands them to the device as one KpTakes library.  Takes that carry objects (`obj_pose` of another shape than
-    `qpos`: has_obj, :223) are refused by name: object placement for the UHC env is not part of this engine."""
+    data_specs['key_subsets'] -- and hands them to the device as one KpTakes library.  A take that carries objects (`obj_pose` of another shape than
+    `qpos`: has_obj, :223) has its obj_pose appended raw to the 76 humanoid coordinates by the reference's reset_model, which only works when it is the
+    model's whole object block: such a take is accepted when its obj_pose is [T, 35] (the library then carries objects and every reset places them; the
+    takes without an own obj_pose get all five objects parked) and refused by name for every other width -- a 7- or 14-wide obj_pose needs the action's
+    slot, which this file format does not carry (SmplObjDataset reads the format that does)."""
 
     SAMPLING_TEMP, SAMPLING_FREQ = 0.2, 0.75          # sample_seq's constants (:162-163)
 
@@ -282,7 +285,7 @@ class AmassSingleDataset:
             keys = list(data_specs["key_subsets"])
         else:
             raise ValueError(f"data_specs['mode'] must be 'all' or 'singles', got {self.mode!r}")
-        self.data_keys, self.qpos = [], {}
+        self.data_keys, self.qpos, self.obj_pose = [], {}, {}      # obj_pose: the takes that keep a [T, 35] object block of their own
         for k in keys:
             v = takes[k]
             if v["pose_aa"].shape[0] < self.t_min:             # :94-97
@@ -292,7 +295,10 @@ class AmassSingleDataset:
             # for a take that has such a key; every other take gets its qpos, and has_obj (:223) is False
             obj = v["obj_pose"] if ("obj_pose" in v) and ((v["obj_pose"] is not None) in v) else v["qpos"]
             if np.shape(obj) != qpos.shape:
-                raise NotImplementedError(f"take '{k}' carries objects (obj_pose {np.shape(obj)} against qpos {qpos.shape}): objects in UHC takes are not supported")
+                if np.shape(obj) != (qpos.shape[0], OBJ_QPOS_DIM):
+                    raise NotImplementedError(f"take '{k}' carries objects (obj_pose {np.shape(obj)} against qpos {qpos.shape}): objects in UHC takes are not supported "
+                                              f"unless obj_pose is the whole [T, {OBJ_QPOS_DIM}] object block")
+                self.obj_pose[k] = np.asarray(obj, np.float64)
             if qpos.ndim != 2 or qpos.shape[1] != 76 or qpos.shape[0] < 2:
                 raise ValueError(f"take '{k}': qpos must be [T >= 2, 76], got {qpos.shape}")
             self.data_keys.append(k); self.qpos[k] = qpos
@@ -321,4 +327,124 @@ class AmassSingleDataset:
         timestep x 15 substeps, as BatchedHumanoidEnv has it)"""
         from .sim import KpTakes
         off = np.concatenate([[0], np.cumsum(self.lens)]).astype(np.int32)
-        return KpTakes(sim, np.concatenate([self.qpos[k] for k in self.data_keys], 0).astype(np.float32), off, sim.model.get_option("timestep") * 15 if dt is None else dt)
+        obj = None
+        if any(k in self.obj_pose for k in self.data_keys):
+            obj = np.concatenate([self.obj_pose[k] if k in self.obj_pose else convert_obj_qpos_np(np.zeros((len(self.qpos[k]), 7)), None) for k in self.data_keys], 0).astype(np.float32)
+        return KpTakes(sim, np.concatenate([self.qpos[k] for k in self.data_keys], 0).astype(np.float32), off, sim.model.get_option("timestep") * 15 if dt is None else dt,
+                       obj_rows=obj)
+
+
+OBJ_QPOS_DIM = 35                                       # data.qpos[76:111]: five free joints
+OBJ_ACTION_IDX = {"sit": 0, "push": 7, "avoid": 21, "step": 28}      # dataset_smpl_obj.py:62-67
+OBJ_ACTION_LEN = {"sit": 7, "push": 14, "avoid": 7, "step": 7}       # :56-61
+
+
+def convert_obj_qpos_np(obj_pose, action):
+    """DatasetSMPLObj.convert_obj_qpos (dataset_smpl_obj.py:230-243) in fp64: [T, 35], all five objects parked at [(i + 1) * 100, 100, 0] with an all-zero
+    quaternion, the take's own 7 (push: 14) floats written at the action's offset; an action outside the four (None) leaves everything parked."""
+    obj_pose = np.asarray(obj_pose)
+    out = np.zeros((obj_pose.shape[0], OBJ_QPOS_DIM))
+    for i in range(5):
+        out[:, 7 * i:7 * i + 3] = [(i + 1) * 100, 100, 0]
+    if action in OBJ_ACTION_IDX:
+        a = OBJ_ACTION_IDX[action]
+        out[:, a:a + OBJ_ACTION_LEN[action]] = obj_pose
+    return out
+
+
+class SmplObjDataset:
+    """DatasetSMPLObj (uhc/data_loaders/dataset_smpl_obj.py:25-243): the UHC's library of whole MoCap takes that carry objects, as
+    scripts/eval_pose_all.py:560 runs the controller on the sit, push, avoid and step takes.
+
+    Reads the pickle `{take: {qpos [T,76], obj_pose [T,7] or [T,14], action_one_hot [T,4], ...}}` from data_specs['file_path'] ('train') or
+    ['test_file_path'] ('test'); keeps the takes in the file's order (mode 'all') or those of data_specs['key_subsets'] (mode 'singles') -- every one of
+    them: this loader has no t_min filter (process_data_pickle, :96-130).  A take's action is argmax(action_one_hot[0]) over (sit, push, avoid, step) and
+    `obj_qpos[take]` its [T, 35] object block (convert_obj_qpos).  Departure: a take whose action_one_hot[0] is all zero has no action here and gets all
+    five objects parked, where the reference's argmax calls it a sit take and puts its placeholder obj_pose (a chair at the origin) under the humanoid.
+    has_obj is True and num_obj 5 for every take (get_single_sample, :213-214).
+
+    `iter_seq()` walks data_keys from frame 0 (:187-198); `sample_seq()` draws a take from sample_keys and fr_start honouring t_min / t_max (:154-178).
+    `to_library(sim)` hands all takes to the device as one KpTakes with objects.  For CopycatAgent it offers AmassSingleDataset's sampling-frequency
+    interface (data_keys, lens, new_freq_dict, draw_probs): the reference's class has NO success-weighted form (its sample_seq is random.choice over
+    sample_keys, or value-based hard-negative mining, which needs recorded states), so draw_probs is that uniform draw over sample_keys -- a take
+    counts qpos_len // t_max + 1 times when t_max is set -- whatever the freq_dict says; the agent still records every episode in it."""
+
+    ACTIONS = ACTIONS
+
+    def __init__(self, data_specs: dict, data_mode: str = "train", takes: dict | None = None):
+        if data_mode not in ("train", "test"):
+            raise ValueError(f"data_mode must be 'train' or 'test', got {data_mode!r}")
+        self.data_specs, self.data_mode = dict(data_specs), data_mode
+        self.t_min, self.t_max, self.mode = data_specs.get("t_min", 90), data_specs.get("t_max", -1), data_specs.get("mode", "all")
+        if takes is None:
+            self.data_root = data_specs["file_path" if data_mode == "train" else "test_file_path"]
+            import joblib
+            takes = joblib.load(self.data_root)
+        if self.mode == "all":
+            keys = list(takes.keys())
+        elif self.mode == "singles":
+            keys = list(data_specs["key_subsets"])
+        else:
+            raise ValueError(f"data_specs['mode'] must be 'all' or 'singles', got {self.mode!r}")
+        self.data_keys, self.sample_keys, self.qpos, self.obj_qpos, self.action = [], [], {}, {}, {}
+        for k in keys:
+            v = takes[k]
+            qpos = np.asarray(v["qpos"], np.float64)
+            if qpos.ndim != 2 or qpos.shape[1] != 76 or qpos.shape[0] < 2:
+                raise ValueError(f"take '{k}': qpos must be [T >= 2, 76], got {qpos.shape}")
+            first = np.asarray(v["action_one_hot"])[0]
+            action = ACTIONS[int(np.argmax(first))] if np.any(first != 0) else None
+            obj = np.asarray(v["obj_pose"], np.float64)
+            if action is not None and obj.shape != (qpos.shape[0], OBJ_ACTION_LEN[action]):
+                raise ValueError(f"take '{k}': a '{action}' take needs obj_pose [{qpos.shape[0]}, {OBJ_ACTION_LEN[action]}], got {obj.shape}")
+            self.qpos[k], self.action[k], self.obj_qpos[k] = qpos, action, convert_obj_qpos_np(obj if action is not None else np.zeros((qpos.shape[0], 7)), action)
+            self.sample_keys += [k] * (qpos.shape[0] // self.t_max + 1 if self.t_max != -1 else 1)      # :123-126
+            self.data_keys.append(k)
+        if not self.data_keys:
+            raise ValueError("the take file holds no take")
+        self.lens = np.array([self.qpos[k].shape[0] for k in self.data_keys], np.int64)
+        self.seq_counter, self.curr_key = 0, ""
+        self.rng = np.random.RandomState(0)
+
+    def get_len(self):
+        return len(self.data_keys)
+
+    def set_seq_counter(self, idx):
+        self.seq_counter = idx
+
+    def get_single_sample(self, key, fr_start, fr_end):
+        return {"qpos": self.qpos[key][fr_start:fr_end], "obj_pose": self.obj_qpos[key][fr_start:fr_end], "action": self.action[key], "seq_name": key,
+                "has_obj": True, "num_obj": 5, "fr_start": int(fr_start)}
+
+    def iter_seq(self):
+        self.curr_key = self.data_keys[self.seq_counter % len(self.data_keys)]
+        self.seq_counter += 1
+        return self.get_single_sample(self.curr_key, 0, self.qpos[self.curr_key].shape[0])
+
+    def sample_seq(self):
+        """:154-178 without hard-negative mining: a uniform draw over sample_keys; with t_max a window of at most t_max frames from a uniform fr_start,
+        without it the rest of the take from a uniform fr_start in [0, len - t_min)"""
+        self.curr_key = self.sample_keys[self.rng.randint(len(self.sample_keys))]
+        n = self.qpos[self.curr_key].shape[0]
+        if self.t_max != -1:
+            fr_start = int(self.rng.randint(n - self.t_max)) if n - self.t_max > 0 else 0
+            fr_end = min(fr_start + self.t_max, n)
+        else:
+            fr_start = int(self.rng.randint(n - self.t_min)) if n - self.t_min > 0 else 0
+            fr_end = n
+        return self.get_single_sample(self.curr_key, fr_start, fr_end)
+
+    def new_freq_dict(self):
+        return {k: [] for k in self.data_keys}
+
+    def draw_probs(self, freq_dict: dict | None = None) -> np.ndarray:
+        """the distribution one sample_seq draw follows: uniform over sample_keys (see the class docstring), the freq_dict plays no part"""
+        p = np.array([self.sample_keys.count(k) for k in self.data_keys], np.float64)
+        return p / p.sum()
+
+    def to_library(self, sim, dt=None):
+        """all takes as one device-resident KpTakes with objects (take k = data_keys[k]); dt as AmassSingleDataset.to_library"""
+        from .sim import KpTakes
+        off = np.concatenate([[0], np.cumsum(self.lens)]).astype(np.int32)
+        return KpTakes(sim, np.concatenate([self.qpos[k] for k in self.data_keys], 0).astype(np.float32), off, sim.model.get_option("timestep") * 15 if dt is None else dt,
+                       obj_rows=np.concatenate([self.obj_qpos[k] for k in self.data_keys], 0).astype(np.float32))

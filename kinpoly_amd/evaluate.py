@@ -95,7 +95,8 @@ def write_coverage(results: dict, result_dir: str, iter_num: int, data_file: str
 @torch.no_grad()
 def run_uhc_sequences(env, policy_net, running_state, take_ids, keys, fail_safe=False, max_steps=100000):
     """Every env plays one WHOLE take (take_ids [env.n], library ids) with the mean action and running_state(update=False).  Per step, before the
-    action: gt = the expert's qpos at get_expert_index(t), pred = the simulated qpos (eval_uhc.py:175-178).  An env that ends early (percent != 1) is,
+    action: gt = the expert's qpos at get_expert_index(t), pred = the simulated qpos (eval_uhc.py:175-178; on a library with objects env.data.qpos is
+    the full 111-wide row, so pred = [qpos 76 | object block 35] while gt stays 76 wide).  An env that ends early (percent != 1) is,
     with fail_safe, put back on the expert and goes on (:188-196); without it the episode is over.  Returns {key: {gt, pred, percent, fail_safe}}
     for the first len(keys) envs."""
     n, dev, lib = env.n, env.device, env.takes
@@ -111,7 +112,8 @@ def run_uhc_sequences(env, policy_net, running_state, take_ids, keys, fail_safe=
     for step in range(max_steps):
         k = env.take_id.long()
         row = off[k] + torch.minimum(env.start_ind.long() + env.cur_t.long(), lens[k] - 1)
-        gt.append(qtab[row]); pred.append(env.sim.get("qpos")); act.append(active.clone())
+        gt.append(qtab[row]); act.append(active.clone())
+        pred.append(torch.cat([env.sim.get("qpos"), env.sim.get("obj_qpos")], 1) if lib.has_objects else env.sim.get("qpos"))
         a = policy_net.select_action(obs, True, env.gen).contiguous()
         obs, _, done, info = env.step(a)
         newly = done & active
@@ -136,7 +138,7 @@ def run_uhc_sequences(env, policy_net, running_state, take_ids, keys, fail_safe=
 
 @torch.no_grad()
 def eval_uhc_takes(env, policy_net, running_state, dataset, fail_safe=False, inds=None, library=None):
-    """test_coverage's loop (eval_uhc.py:202-224) over the takes of an AmassSingleDataset, env.n at a time; a short last chunk is padded with copies of
+    """test_coverage's loop (eval_uhc.py:202-224) over the takes of an AmassSingleDataset or SmplObjDataset, env.n at a time; a short last chunk is padded with copies of
     its last take.  Loads the data set's library into env (library: one already built with env.sim).  Returns {take name: seq_result} in data-set order."""
     lib = library if library is not None else dataset.to_library(env.sim)
     env.load_takes(lib)

@@ -113,6 +113,7 @@ _SIGNATURES = {
     "kp_sim_last_step_seconds": (_D, [_V]), "kp_sim_timing_reset": (_I, [_V]), "kp_sim_timing_mean_seconds": (_D, [_V, _PI]),
     "kp_sim_phase_cycles": (_I, [_V, C.POINTER(_D)]), "kp_sim_phase_cycles_env": (_I, [_V, _V]),
     "kp_takes_create": (_V, [_V, _V, _I, _V, _I, _D]), "kp_takes_destroy": (None, [_V]),
+    "kp_takes_create_obj": (_V, [_V, _V, _V, _I, _V, _I, _D]), "kp_takes_has_objects": (_I, [_V]),
     "kp_takes_table": (_I, [_V, _S, C.POINTER(_V), _PI, _PI]), "kp_takes_info": (_I, [_V, _PI, _PI, _V]),
     "kp_sim_uhc_track": (_I, [_V, _V, _UST, _UCFG, _V, _V, _V, _V, _V, _V, _V, _V]), "kp_sim_uhc_assign": (_I, [_V, _V, _UST, _UCFG, _V, _V, _V, _I, _V]),
     # stand-alone kernels (no kp_sim): sizes, device arrays, ..., stream
@@ -514,33 +515,52 @@ TAKE_TABLES = ("qpos", "qpos_fk", "wbpos", "wbquat", "bquat", "body_com", "com",
                "rlinv_local", "bangvel", "height_lb", "head_height_lb")
 
 
+def _take_rows(what, rows, width):
+    """(keep-alive, on_device, pointer) of a library's row array [R, width]: a device tensor stays where it is, anything else becomes a host fp32 array"""
+    if torch.is_tensor(rows) and rows.is_cuda:
+        rows = rows.to(torch.float32).contiguous()
+        on_dev, ptr, shape = 1, rows.data_ptr(), tuple(rows.shape)
+    else:
+        rows = np.ascontiguousarray(rows.cpu().numpy() if torch.is_tensor(rows) else rows, np.float32)
+        on_dev, ptr, shape = 0, rows.ctypes.data, rows.shape
+    if len(shape) != 2 or shape[1] != width:
+        raise ValueError(f"KpTakes: {what} must be [R, {width}], got {tuple(shape)}")
+    return rows, on_dev, ptr
+
+
 class KpTakes:
     """The device-resident take library (kp_takes): the expert tables of K takes of different lengths, concatenated row-wise.  Built once with a
     KpSim's forward kinematics and model tables; independent of the number of envs.  `table(name)` is a zero-copy [R, width] view ([K, 1] for the
-    per-take minima); `take(k)` slices every per-row table to take k."""
+    per-take minima); `take(k)` slices every per-row table to take k.
 
-    def __init__(self, sim: KpSim, qpos_rows, take_off, dt: float = 1.0 / 30.0):
+    obj_rows [R, 35] (kp_takes_create_obj): the object block data.qpos[76:111] of every row, on the same side (host / device) as qpos_rows.  Such a
+    library `has_objects`, answers table("obj_pose") and take(k)["obj_pose"], and KpSim.uhc_assign places every reset env's objects from it."""
+
+    def __init__(self, sim: KpSim, qpos_rows, take_off, dt: float = 1.0 / 30.0, obj_rows=None):
         self.sim, self.L, self.device = sim, sim.L, sim.device
         off = np.ascontiguousarray(np.asarray(take_off, np.int32).reshape(-1))
         K = len(off) - 1
-        if torch.is_tensor(qpos_rows) and qpos_rows.is_cuda:
-            rows = qpos_rows.to(torch.float32).contiguous()
-            on_dev, ptr, shape = 1, rows.data_ptr(), tuple(rows.shape)
-        else:
-            rows = np.ascontiguousarray(qpos_rows.cpu().numpy() if torch.is_tensor(qpos_rows) else qpos_rows, np.float32)
-            on_dev, ptr, shape = 0, rows.ctypes.data, rows.shape
-        if len(shape) != 2 or shape[1] != NQ:
-            raise ValueError(f"KpTakes: qpos_rows must be [R, {NQ}], got {tuple(shape)}")
-        if K >= 1 and int(off[-1]) != shape[0]:
-            raise ValueError(f"KpTakes: take_off ends at {int(off[-1])}, qpos_rows has {shape[0]} rows")
+        rows, on_dev, ptr = _take_rows("qpos_rows", qpos_rows, NQ)
+        if K >= 1 and int(off[-1]) != rows.shape[0]:
+            raise ValueError(f"KpTakes: take_off ends at {int(off[-1])}, qpos_rows has {rows.shape[0]} rows")
+        if obj_rows is not None:
+            orows, obj_on_dev, optr = _take_rows("obj_rows", obj_rows, 35)
+            if orows.shape[0] != rows.shape[0]:
+                raise ValueError(f"KpTakes: obj_rows has {orows.shape[0]} rows, qpos_rows has {rows.shape[0]}")
+            if obj_on_dev != on_dev:
+                raise ValueError("KpTakes: qpos_rows and obj_rows must both be device tensors or both be host arrays")
         with torch.cuda.device(self.device):
-            self.h = self.L.kp_takes_create(sim.h, C.c_void_p(ptr), on_dev, off.ctypes.data_as(C.c_void_p), K, float(dt))
+            if obj_rows is None:
+                self.h = self.L.kp_takes_create(sim.h, C.c_void_p(ptr), on_dev, off.ctypes.data_as(C.c_void_p), K, float(dt))
+            else:
+                self.h = self.L.kp_takes_create_obj(sim.h, C.c_void_p(ptr), C.c_void_p(optr), on_dev, off.ctypes.data_as(C.c_void_p), K, float(dt))
         if not self.h:
-            raise KinPolyNativeError(f"kp_takes_create: {self.L.kp_last_error().decode()}")
+            raise KinPolyNativeError(f"kp_takes_create{'' if obj_rows is None else '_obj'}: {self.L.kp_last_error().decode()}")
         k, r = C.c_int(0), C.c_int(0)
         lens = np.zeros(K, np.int32)
         _check(self.L.kp_takes_info(self.h, C.byref(k), C.byref(r), lens.ctypes.data_as(C.c_void_p)), "kp_takes_info")
         self.K, self.R, self.lens, self.take_off = k.value, r.value, lens, off.copy()
+        self.has_objects = bool(self.L.kp_takes_has_objects(self.h))
         self._tabs = {}
 
     def table(self, name: str) -> torch.Tensor:
@@ -553,6 +573,8 @@ class KpTakes:
     def take(self, k: int) -> dict:
         a, b = int(self.take_off[k]), int(self.take_off[k + 1])
         out = {n: self.table(n)[a:b] for n in TAKE_TABLES[:-2]}
+        if self.has_objects:
+            out["obj_pose"] = self.table("obj_pose")[a:b]
         out["len"] = b - a
         out["height_lb"], out["head_height_lb"] = self.table("height_lb")[k, 0], self.table("head_height_lb")[k, 0]
         return out

@@ -149,8 +149,22 @@ class BatchedHumanoidEnv:
     def load_takes(self, library: kpsim.KpTakes, take_ids=None):
         """Imitate takes of a device-resident library (kinpoly_amd.sim.KpTakes, built with this env's sim) instead of one rectangular clip: every env is
         on a take of its own length (take_ids [N], default env e -> take e mod K), `step` runs the fused tracking kernel and `reset(mask, take_ids,
-        start)` moves envs between takes.  Call reset() before the first step."""
+        start)` moves envs between takes.  Call reset() before the first step.
+
+        A library with objects (KpTakes(obj_rows=...), SmplObjDataset.to_library): reset() also places every reset env's objects from the library row its
+        humanoid state comes from (reset_model's has_obj branch) and the handle simulates them from then on; fail_safe() leaves them where the physics put
+        them.  Refused: a model blob without object geoms, threads_per_env other than 64.  A library WITHOUT objects loaded onto a handle that already
+        runs objects parks all five objects of every env (the handle stays on the object layout; parked objects touch nothing)."""
         n, dev = self.n, self.device
+        if library.has_objects:
+            if int(self.model.get_option("n_obj_geoms")) == 0:
+                raise ValueError("load_takes: the take library carries objects but the model blob has no object geoms")
+            if int(self.model.get_option("threads_per_env")) != 64:
+                raise ValueError(f"load_takes: a take library with objects needs threads_per_env = 64, the model has {int(self.model.get_option('threads_per_env'))}")
+            self._objects_on = True
+        elif getattr(self, "_objects_on", False):
+            from .dataset import convert_obj_qpos_np
+            self.sim.set_objects(torch.tensor(convert_obj_qpos_np(np.zeros((n, 7)), None), dtype=torch.float32, device=dev).contiguous())
         self.takes, self.expert = library, None
         self.take_id = torch.zeros(n, dtype=torch.int32, device=dev); self.start_ind = torch.zeros(n, dtype=torch.int32, device=dev)
         self.cur_t = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -185,6 +199,18 @@ class BatchedHumanoidEnv:
         m8 = None if env_mask is None else env_mask.to(self.device, torch.uint8).contiguous()
         self.sim.uhc_assign(self.takes, self._st, self._tc, m8, None, None, keep_t=True, noise=None)
         return self._obs_takes()
+
+    def get_obj_qpos(self):
+        """data.qpos[76:111] of every env: a zero-copy [N, 35] view of KP_OBJ_QPOS (follows the simulator; clone to keep)"""
+        return self.sim.view("obj_qpos")
+
+    def get_obj_qvel(self):
+        """data.qvel[75:105] of every env: a zero-copy [N, 30] view of KP_OBJ_QVEL"""
+        return self.sim.view("obj_qvel")
+
+    @property
+    def has_objects(self):
+        return self.takes is not None and self.takes.has_objects
 
     def _step_takes(self, a):
         if self._next_ids is not None:

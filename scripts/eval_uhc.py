@@ -5,7 +5,8 @@ a take pickle played whole by a trained UHC, env.n takes at a time; writes `<ite
     python scripts/eval_uhc.py --cfg uhc --config_root /path/to/KinPoly --iter 1000 --mode stats --data test --fail_safe
     python scripts/eval_uhc.py --mode stats --ckpt out/iter_0002.p --takes takes.pkl --iter 2 --data usr
 
---cfg names the controller's yml (its data_specs give test_file_path and t_min); --takes overrides the take file, --ckpt the checkpoint
+--cfg names the controller's yml (its data_specs give test_file_path and t_min); --takes overrides the take file, --ckpt the checkpoint;
+--dataset smpl_obj reads the take file as DatasetSMPLObj's (takes that carry objects: the objects are simulated and `pred` rows are 111 wide)
 (default <config_root>/results/motion_im/<cfg>/models/iter_%04d.p).  The viewer modes of the reference (--mode vis / disp_stats, --record, --preview)
 need its MuJoCo viewer and are refused by name.
 """
@@ -44,6 +45,8 @@ def build_parser():
     p.add_argument("--takes", type=str, default="")
     p.add_argument("--t_min", type=int, default=None)
     p.add_argument("--num_envs", type=int, default=64)
+    p.add_argument("--dataset", choices=("amass_single", "smpl_obj"), default="amass_single",
+                   help="the loader of the take file: amass_single (DatasetAMASSSingle's pickle) or smpl_obj (DatasetSMPLObj's: takes that carry objects)")
     return p
 
 
@@ -63,7 +66,7 @@ def main(argv=None):
     import numpy as np
     import torch
     from kinpoly_amd import checkpoint as ck
-    from kinpoly_amd.dataset import AmassSingleDataset
+    from kinpoly_amd.dataset import AmassSingleDataset, SmplObjDataset
     from kinpoly_amd.evaluate import eval_uhc_takes, write_uhc_coverage
     from kinpoly_amd.uhc_env import BatchedHumanoidEnv, CopycatAgent
     cfg = None
@@ -78,7 +81,7 @@ def main(argv=None):
     if "test_file_path" not in specs:
         raise SystemExit("eval_uhc.py: no take file: give --takes, or a --cfg whose data_specs has test_file_path")
     ckpt = args.ckpt or os.path.join(args.config_root or os.getcwd(), "results", "motion_im", str(args.cfg), "models", "iter_%04d.p" % args.iter)
-    ds = AmassSingleDataset(specs, "test")
+    ds = {"amass_single": AmassSingleDataset, "smpl_obj": SmplObjDataset}[args.dataset](specs, "test")
     torch.cuda.set_device(0)
     n = min(args.num_envs, ds.get_len())
     env = BatchedHumanoidEnv(n, 0, cfg=cfg) if cfg is not None else BatchedHumanoidEnv(n, 0, env_init_noise=0.0)

@@ -36,8 +36,9 @@ def save_uhc_checkpoint(path, agent, env):
 
 def train_on_takes(args, rank, local, world):
     """--data: the reference's training loop on a take library (agent_copycat.py): freq_dict.pt is read from / written next to the checkpoint"""
-    from kinpoly_amd.dataset import AmassSingleDataset
+    from kinpoly_amd.dataset import AmassSingleDataset, SmplObjDataset
     from kinpoly_amd.uhc_env import BatchedHumanoidEnv, CopycatAgent
+    Dataset = {"amass_single": AmassSingleDataset, "smpl_obj": SmplObjDataset}[args.dataset]
     cfg = None
     if args.cfg:
         from kinpoly_amd.uhc_config import UhcConfig
@@ -47,7 +48,7 @@ def train_on_takes(args, rank, local, world):
         specs["t_min"] = args.t_min
     elif cfg is None:
         specs.setdefault("t_min", 90)
-    ds = AmassSingleDataset(specs, "train")
+    ds = Dataset(specs, "train")
     out_dir = os.path.dirname(os.path.abspath(args.save)) if args.save else None
     env = BatchedHumanoidEnv(args.num_envs, local, seed=1 + rank, cfg=cfg) if cfg is not None else BatchedHumanoidEnv(args.num_envs, local, env_init_noise=0.0, seed=1 + rank)
     group = dist.group.WORLD if world > 1 else None
@@ -61,7 +62,7 @@ def train_on_takes(args, rank, local, world):
         if rank == 0:
             print(json.dumps({"iter": it, "episodes": len(agent.take_log[-1]), **{k: (round(v, 5) if isinstance(v, float) else v) for k, v in stats.items()}}), flush=True)
     if args.test_data and rank == 0:
-        print(agent.eval_policy("test", args.iters, dataset=AmassSingleDataset(specs, "test")), flush=True)
+        print(agent.eval_policy("test", args.iters, dataset=Dataset(specs, "test")), flush=True)
     if args.save and rank == 0:
         save_uhc_checkpoint(args.save, agent, env)
         agent.save_freq_dict(out_dir)
@@ -69,7 +70,7 @@ def train_on_takes(args, rank, local, world):
         dist.barrier(); dist.destroy_process_group()
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--num_envs", type=int, default=4096)
     ap.add_argument("--iters", type=int, default=3)
@@ -82,7 +83,13 @@ def main():
     ap.add_argument("--data", type=str, default="", help="take pickle of the reference's UHC data ({take: {pose_aa, qpos, ...}}): train on its takes, a newly drawn whole take per episode")
     ap.add_argument("--test_data", type=str, default="", help="take pickle evaluated (eval_policy, mode 'test') after the last iteration")
     ap.add_argument("--t_min", type=int, default=None, help="shortest take kept (default: the config's data_specs, else 90)")
-    args = ap.parse_args()
+    ap.add_argument("--dataset", choices=("amass_single", "smpl_obj"), default="amass_single",
+                    help="the loader of --data / --test_data: amass_single (DatasetAMASSSingle's pickle) or smpl_obj (DatasetSMPLObj's: takes that carry objects)")
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local)
     if world > 1:
