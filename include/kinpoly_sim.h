@@ -344,7 +344,8 @@ int kp_mcp_tail(int n, int K, int J, int A, const float* h2, const float* b2, co
 /* One roll-out step of torch.nn.GRUCell after its two gate GEMMs (TrajARNet.get_action, kin_poly/models/traj_ar_smpl_net.py:333-343;
  * RNN.forward in step mode, uhc/khrylib/models/rnn.py:24-36): gi [n, 3H] = x W_ih^T and gh [n, 3H] = h_in W_hh^T WITHOUT biases, b_ih / b_hh [3H]
  * -> h_out [n, H] (may alias h_in); xcat (optional) [n, D + H] <- [state | h_out], the row `torch.cat((state, hx), dim=1)` builds for
- * the action MLP (state [n, D], D <= H). */
+ * the action MLP (state [n, D]; a state wider than the hidden state, D > H -- 357 against 256 under kin_only.yml -- takes the kernel of
+ * kp_obs_ctx.hip whose copy loops over the columns: the same gate math, the same h_out). */
 int kp_gru_cell_step(int n, int H, int D, const float* gi, const float* gh, const float* b_ih, const float* b_hh, const float* h_in, const float* state,
                      float* h_out, float* xcat, void* hip_stream);
 
@@ -554,6 +555,23 @@ int kp_sim_obs_ar_backward(kp_sim*, const kp_ctx* ctx, int n_rows, int grad_widt
  * grad_qpos_add may be grad_qpos itself. */
 int kp_sim_fk_head_backward(kp_sim*, int n_rows, const float* qpos, const float* wbpos, const float* wbquat, const float* grad_wbpos,
                             const float* grad_hpos, const float* grad_hquat, const float* grad_qpos_add, float* grad_qpos);
+
+/* The kinematic model's observation under `use_context` / `use_of` (config/statear/kin_only.yml, use_of.yml; TrajARNet.get_obs,
+ * traj_ar_smpl_net.py:226-230, 284-285): one launch writes out [N, ctx_dim + kp_sim_ar_obs_dim + of_dim] = [context GRU's hidden state at the row's
+ * frame | kp_sim_obs_ar's row, the same words | the frame's image feature].  Both tables are read at the frame and row kp_sim_obs_ar reads
+ * (ctx->cur_t clamped into [0, T - 1], ctx->row): element (row r, frame t, column c) of a table is at r * stride_row + t * stride_t + c, strides in
+ * floats, so [R, T, .] and [T, R, .] storage both serve.  ctx_feat NULL with ctx_dim > 0 writes zeros (the row before init_states, :229-230).
+ * Refused with -1 before any launch: a negative dim, of_dim > 0 with of NULL, a stride < 1 of a non-NULL table, and what kp_sim_obs_ar refuses. */
+typedef struct { int ctx_dim; const float* ctx_feat; long ctx_stride_row, ctx_stride_t;   /* strides in floats: env-major or time-major */
+                 int of_dim;  const float* of;       long of_stride_row,  of_stride_t; } kp_obs_ext;
+int kp_sim_obs_ar_ex(kp_sim*, const kp_ctx* ctx, const kp_obs_ext* ext, float* out);
+/* (d kp_sim_obs_ar_ex)^T: kp_sim_obs_ar_backward on the base block of grad_obs [n_rows, grad_width], grad_width = ext->ctx_dim + kp_sim_ar_obs_dim
+ * + ext->of_dim (refused otherwise), and grad_ctx [n_rows, ctx_dim] <- the context block's cotangent, grad_obs's first ctx_dim columns (may be NULL
+ * when ctx_dim is 0).  The `of` block is data.  The other arguments, outputs and refusals (the 81 / 156 layouts among them) are
+ * kp_sim_obs_ar_backward's. */
+int kp_sim_obs_ar_ex_backward(kp_sim*, const kp_ctx* ctx, const kp_obs_ext* ext, int n_rows, int grad_width, const float* qpos, const float* wbpos,
+                              const float* wbquat, const float* grad_obs, const float* grad_obj_2_head, float* grad_qpos, float* grad_qvel,
+                              float* grad_hpos, float* grad_hquat, float* grad_ctx);
 
 
 #ifdef __cplusplus

@@ -11,7 +11,8 @@ the reference gives one (`.get(key, default)` in Config / AgentAR).  What the en
 velocities in the observation) and `use_head` (false: no head-tracking blocks) may be either too, except `use_head: false` with `use_action: false`.
 `mujoco_model` (the compiled blobs of kinpoly_amd/assets are humanoid_smpl_neutral_mesh_all[_step].xml, agent_ar.py:165-169), `model_specs`
 of another architecture than TrajARNet's (checked: a mismatch raises), `policy_optimizer` other than Adam (checked), `obs_*` switches other than the
-kin_poly.yml values (checked).  Nothing here needs a GPU.
+kin_poly.yml values (checked).  `use_of` / `use_context` (kin_only.yml, use_of.yml) are refused by the default entry and taken by
+`Config(..., entry="kin_model")`, the supervised kinematic model of scripts/exp_arnet_all.py, with the file's net sizes (`model_kwargs()`).  Nothing here needs a GPU.
 """
 from __future__ import annotations
 
@@ -29,6 +30,8 @@ _FIXED = {"use_of": (False, True), "use_context": (False, True),
 _FIXED_MODEL = {"model_v": 1, "rnn_hdim": 1024, "mlp_hsize": [1024, 512, 256], "mlp_htype": "relu", "rnn_type": "gru"}
 _FIXED_POLICY = {"policy_v": 1, "fix_std": True, "policy_htype": "relu", "policy_hsize": [512, 256], "value_htype": "relu", "value_hsize": [512, 256],
                  "policy_optimizer": "Adam", "value_optimizer": "Adam", "reward_id": "dynamic_supervision_v1", "end_reward": False}
+# what Config(entry="kin_model") takes from the file instead: the supervised kinematic model runs with a context / `of` block and any net sizes
+_KIN_MODEL_FREE = ("use_of", "use_context", "rnn_hdim", "mlp_hsize", "cnn_fdim")
 
 
 class ConfigError(ValueError):
@@ -36,7 +39,14 @@ class ConfigError(ValueError):
 
 
 class Config:
-    def __init__(self, cfg_id: str, action: str = "all", wild: bool = False, base_dir: str = "results", config_root: str | None = None, create_dirs: bool = False):
+    def __init__(self, cfg_id: str, action: str = "all", wild: bool = False, base_dir: str = "results", config_root: str | None = None, create_dirs: bool = False,
+                 entry: str = "policy"):
+        """entry: "policy" (the rollout / PPO scripts: every check below) or "kin_model" (scripts/exp_arnet_all.py, the supervised kinematic model: `use_of`
+        / `use_context` may be true and model_specs' rnn_hdim / mlp_hsize / cnn_fdim are the file's -- config/statear/kin_only.yml, use_of.yml; the reference's
+        exp_arnet_all.py never reads policy_specs, so they are not checked)."""
+        if entry not in ("policy", "kin_model"):
+            raise ConfigError(f"Config: entry must be 'policy' or 'kin_model', got {entry!r}")
+        self.entry = entry
         if os.path.isfile(cfg_id):
             path, cfg_id = cfg_id, os.path.splitext(os.path.basename(cfg_id))[0]
         else:
@@ -81,18 +91,29 @@ class Config:
         self.reward_weights = dict(self.policy_specs.get("reward_weights", {}))
         self.use_action = y.get("use_action", True)          # statear_smpl_config.py:141
         self.use_vel, self.use_head = y.get("use_vel", False), y.get("use_head", True)      # :139-140
+        self.use_of, self.use_context = y.get("use_of", True), y.get("use_context", True)  # :137-138 (refused unless entry == "kin_model")
         self._check_supported()
 
     def _check_supported(self):
         y = self.yaml_data
-        bad = [f"{k}: {y.get(k, ref)!r} (the HIP observation / step kernels implement {v!r})" for k, (v, ref) in _FIXED.items() if y.get(k, ref) != v]
-        for k in ("use_action", "use_vel", "use_head"):
+        kin = self.entry == "kin_model"
+        bad = [f"{k}: {y.get(k, ref)!r} (the HIP observation / step kernels implement {v!r})" for k, (v, ref) in _FIXED.items()
+               if y.get(k, ref) != v and not (kin and k in _KIN_MODEL_FREE)]
+        for k in ("use_action", "use_vel", "use_head") + (("use_of", "use_context") if kin else ()):
             if not isinstance(getattr(self, k), bool):
                 bad.append(f"{k}: {getattr(self, k)!r} (true or false)")
         if self.use_head is False and self.use_action is False:
             bad.append("use_head: False with use_action: False (the context GRU would have no input: get_context_dim is 0)")
-        bad += [f"model_specs.{k}: {self.model_specs[k]!r} (TrajARNet here is {v!r})" for k, v in _FIXED_MODEL.items() if k in self.model_specs and self.model_specs[k] != v]
-        bad += [f"policy_specs.{k}: {self.policy_specs[k]!r} (implemented: {v!r})" for k, v in _FIXED_POLICY.items() if k in self.policy_specs and self.policy_specs[k] != v]
+        bad += [f"model_specs.{k}: {self.model_specs[k]!r} (TrajARNet here is {v!r})" for k, v in _FIXED_MODEL.items()
+                if k in self.model_specs and self.model_specs[k] != v and not (kin and k in _KIN_MODEL_FREE)]
+        if kin:
+            hs = self.model_specs.get("mlp_hsize", [1024, 512, 256])
+            if not (isinstance(self.model_specs.get("rnn_hdim", 1024), int) and self.model_specs.get("rnn_hdim", 1024) > 0):
+                bad.append(f"model_specs.rnn_hdim: {self.model_specs.get('rnn_hdim')!r} (a positive integer)")
+            if not (isinstance(hs, list) and hs and all(isinstance(h, int) and h > 0 for h in hs)):
+                bad.append(f"model_specs.mlp_hsize: {hs!r} (a list of positive integers)")
+        else:
+            bad += [f"policy_specs.{k}: {self.policy_specs[k]!r} (implemented: {v!r})" for k, v in _FIXED_POLICY.items() if k in self.policy_specs and self.policy_specs[k] != v]
         if bad:
             raise ConfigError(f"{self.path}: not supported by the batched engine -- " + "; ".join(bad))
 
@@ -100,6 +121,13 @@ class Config:
     def feature_path(self, data_file: str | None = None) -> str:
         """<dataset_path>/features/<data_file>.p (DatasetAMASSBatch / StateARDataset, statear_smpl_dataset.py:38-39)"""
         return os.path.join(self.data_dir, "features", (data_file or self.data_file) + ".p")
+
+    def model_kwargs(self) -> dict:
+        """What scripts/exp_arnet_all.py passes on from model_specs: the net sizes (exp_arnet.build_net) and compute_loss's weights (the reference's
+        defaults where the file omits one, traj_ar_smpl_net.py:40-41, 391-399); kin_poly.yml gives the engine's own defaults."""
+        ms = self.model_specs
+        w = {k: float(ms.get(k, d)) for k, d in (("w_rp", 50), ("w_rr", 50), ("w_p", 1), ("w_v", 1), ("w_ee", 1), ("w_op", 1), ("w_or", 1))}
+        return dict(rnn_hdim=int(ms.get("rnn_hdim", 512)), mlp_hsize=tuple(ms.get("mlp_hsize", [1024, 512])), **w)
 
     def agent_kwargs(self) -> dict:
         """AgentAR(...) keyword arguments for this file (agent_ar.py:60-99, 184-225: the optimisers, schedules, PPO and sampling constants)."""

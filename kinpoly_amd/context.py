@@ -119,17 +119,25 @@ class TrajARNet(KinPolicy):
     """KinPolicy (the per-step part) + the context network of TrajARNet."""
 
     def __init__(self, state_dim=None, action_dim=80, context_dim=None, rnn_hdim=1024, mlp_hsize=(1024, 512, 256), htype="relu", log_std=-3.2,
-                 use_action=True, use_vel=False, use_head=True):
+                 use_action=True, use_vel=False, use_head=True, use_context=False, of_dim=0, of_in_state=False):
         """use_action (kin_poly.yml): the action one-hot is an input of the policy (state 105) and of the context GRU (context 17 = 7 + 6 + 4); False
         (kin_poly_wo_action.yml): state 101, context 13 (get_context_dim / get_context_feat / get_obs, traj_ar_smpl_net.py:121-167, 281-282).
         use_vel: the 75 velocities are part of the state (:265-266); use_head False: no head-tracking blocks in the state (:232-251, 268-277) and no head
-        columns in the context GRU's input (:125, 150-152).  state_dim = kpsim.ar_obs_dim of the three, context_dim = 13 * use_head + 4 * use_action."""
-        if not (use_head or use_action):
+        columns in the context GRU's input (:125, 150-152).  use_context / of_dim > 0 (kin_only.yml, use_of.yml: `use_of` with image features of_dim
+        wide): the state starts with the context GRU's hidden state at the frame (ctx_block = rnn_hdim columns, :226-230), the context GRU reads
+        data['of'] first (:124, 140-147), and of_in_state (the reference's as_policy) ends the state with the frame's feature (:284-285).
+        state_dim = ctx_block + kpsim.ar_obs_dim of the three switches + of_dim * of_in_state, context_dim = of_dim + 13 * use_head + 4 * use_action."""
+        of_dim = int(of_dim)
+        if not (use_head or use_action or of_dim):
             raise ValueError("TrajARNet: use_head False with use_action False leaves the context GRU without input (get_context_dim is 0)")
-        state_dim = kpsim.ar_obs_dim(use_vel, use_head, use_action) if state_dim is None else state_dim
-        context_dim = (13 * bool(use_head) + 4 * bool(use_action)) if context_dim is None else context_dim
+        self_ctx_block = int(rnn_hdim) if (use_context or of_dim) else 0
+        of_state = of_dim if of_in_state else 0
+        state_dim = self_ctx_block + kpsim.ar_obs_dim(use_vel, use_head, use_action) + of_state if state_dim is None else state_dim
+        context_dim = (of_dim + 13 * bool(use_head) + 4 * bool(use_action)) if context_dim is None else context_dim
         super().__init__(state_dim, action_dim, rnn_hdim, mlp_hsize, htype, log_std)
         self.use_action, self.use_vel, self.use_head = bool(use_action), bool(use_vel), bool(use_head)
+        self.use_context, self.of_dim, self.of_in_state, self.ctx_block = bool(use_context), of_dim, bool(of_in_state), self_ctx_block
+        self.base_dim = state_dim - self_ctx_block - of_state          # the kinematic handle's row (kp_sim_obs_ar) inside the state
         self.context_dim, self.init_dim = context_dim, action_dim + 75
         self.context_rnn = _StepRNN(context_dim, rnn_hdim)
         self.context_mlp = MLP(rnn_hdim, mlp_hsize, htype)
@@ -137,6 +145,10 @@ class TrajARNet(KinPolicy):
 
     def _context_input(self, data):
         head = [data["obj_head_relative_poses"], data["head_vels"]] if self.use_head else []
+        if self.of_dim:
+            if "of" not in data or data["of"].shape[-1] != self.of_dim:
+                raise ValueError(f"TrajARNet: the context GRU reads data['of'] [N, T, {self.of_dim}] (StateARDataset(of_features=...))")
+            head = [data["of"]] + head
         if not self.use_action:
             return torch.cat(head, 2)
         one_hot = data["action_one_hot"]
@@ -145,15 +157,36 @@ class TrajARNet(KinPolicy):
             one_hot = one_hot[:, None].expand(-1, T, -1)
         return torch.cat(head + [one_hot], 2)
 
-    def get_context_feat(self, data):
-        """get_context_feat (:138-167): GRU over [obj_head_relative_poses, head_vels (use_head), action_one_hot (use_action)] -> [N, T, rnn_hdim]."""
+    def context_sequence(self, data):
+        """The context GRU's hidden states, TIME-MAJOR [T, N, rnn_hdim]: a frame's block -- what the `use_context` / `use_of` observation reads at frame
+        t, and its cotangent -- is one contiguous [N, H] slab, and autograd's backward over the frames is a stack (env-major storage would fill T
+        zero [N, T, H] tensors).  A network with a context block in fp32 on the device: with grad enabled the fused node of gru_unroll.py (no episode
+        starts), without grad the two gate GEMMs + kp_gru_cell_step writing straight into the slab; otherwise the GRUCell loop."""
         feat = self._context_input(data)
-        hx = torch.zeros((feat.shape[0], self.rnn_hdim), device=feat.device, dtype=feat.dtype)
+        N, T = feat.shape[:2]
+        cell = self.context_rnn.rnn_f
+        fast = bool(self.ctx_block) and feat.is_cuda and feat.dtype == torch.float32
+        if fast and torch.is_grad_enabled():
+            from .gru_unroll import gru_unroll
+            return gru_unroll(cell, feat, torch.zeros((N, T), dtype=torch.bool, device=feat.device)).transpose(0, 1)
+        ft = feat.transpose(0, 1).contiguous()
+        hx = torch.zeros((N, self.rnn_hdim), device=feat.device, dtype=feat.dtype)
+        if fast:
+            seq = torch.empty((T, N, self.rnn_hdim), device=feat.device, dtype=feat.dtype)
+            gi = torch.nn.functional.linear(ft.view(T * N, -1), cell.weight_ih).view(T, N, 3 * self.rnn_hdim)
+            for t in range(T):
+                hx = kpsim.gru_cell_step(gi[t], torch.nn.functional.linear(hx, cell.weight_hh), cell.bias_ih, cell.bias_hh, hx, h_out=seq[t])
+            return seq
         outs = []
-        for t in range(feat.shape[1]):
-            hx = self.context_rnn.rnn_f(feat[:, t], hx)
+        for t in range(T):
+            hx = cell(ft[t], hx)
             outs.append(hx)
-        return torch.stack(outs, 1)
+        return torch.stack(outs, 0)
+
+    def get_context_feat(self, data):
+        """get_context_feat (:138-167): GRU over [of (of_dim), obj_head_relative_poses, head_vels (use_head), action_one_hot (use_action)] ->
+        [N, T, rnn_hdim], the env-major view of context_sequence's time-major storage."""
+        return self.context_sequence(data).transpose(0, 1)
 
     def get_context_mean(self, data):
         """context_feat_rnn.mean(dim=1) of init_states (:185-186) without keeping the [N, T, rnn_hdim] sequence: the only consumer of the
@@ -206,7 +239,7 @@ class TrajARNet(KinPolicy):
     def init_states(self, data, keep_feat: bool = True):
         """init_states (:180-201) + init_pred_qpos (:169-178): -> (init_qpos [N,76], init_qvel [N,75], context_feat_rnn or None)."""
         if keep_feat:
-            ctx = self.get_context_feat(data)
+            ctx = self.get_context_feat(data)                      # [N, T, H] view of the time-major sequence (ctx.transpose(0, 1) is contiguous)
             w = self._frame_weights(data, ctx.shape[1], ctx)
             mean = ctx.mean(1) if w is None else (ctx * w[:, :, None]).sum(1)
         else:
@@ -219,13 +252,22 @@ class TrajARNet(KinPolicy):
         pred_qpos = torch.cat([pred_qpos[:, :3], root / root.norm(dim=1, keepdim=True), pred_qpos[:, 7:]], 1)
         return pred_qpos, vel, ctx
 
-    @torch.no_grad()
-    def rollout(self, data, kin_sim: kpsim.KpSim, init_qpos, init_qvel, dt=1.0 / 30.0):
-        """TrajARNet.forward (:346-383) in test mode: kinematic roll-out of the whole clip.
-        Returns ar_qpos [N,T,76], ar_qvel [N,T,75] (after fix_qvel), action [N,T,80]."""
+    def obs_ext(self, kin_sim: kpsim.KpSim, data, seq):
+        """kp_obs_ext of this network's wide row for the clips of `data` (kp_sim_obs_ar_ex): seq = context_sequence's [T, N, H] (None: zeros) and
+        data['of'] when the state carries it; None for a network whose state is the kinematic handle's row."""
+        if self.state_dim == self.base_dim:
+            return None
         N, T = data["qpos"].shape[:2]
-        if kin_sim.obs_ar_dim != self.state_dim:
-            raise ValueError(f"TrajARNet.rollout: the kinematic simulator writes {kin_sim.obs_ar_dim}-d observations, the policy takes {self.state_dim}-d "
+        return kin_sim.make_obs_ext(T, N, self.ctx_block, seq, data["of"].contiguous() if self.of_in_state else None)
+
+    @torch.no_grad()
+    def rollout(self, data, kin_sim: kpsim.KpSim, init_qpos, init_qvel, dt=1.0 / 30.0, ctx_feat=None):
+        """TrajARNet.forward (:346-383) in test mode: kinematic roll-out of the whole clip.
+        Returns ar_qpos [N,T,76], ar_qvel [N,T,75] (after fix_qvel), action [N,T,80].  ctx_feat: init_states' third value (a network with a context
+        block reads its frame t in the observation; None there = the zero block of a network without a sequence, :229-230)."""
+        N, T = data["qpos"].shape[:2]
+        if kin_sim.obs_ar_dim != self.base_dim:
+            raise ValueError(f"TrajARNet.rollout: the kinematic simulator writes {kin_sim.obs_ar_dim}-d observations, the policy takes {self.base_dim}-d "
                              "(a model with ar_obs_action = 0 gives the 101-d observation of use_action: false; ar_obs_vel / ar_obs_head those of "
                              "use_vel / use_head: kpsim.ar_obs_options)")
         dev = init_qpos.device
@@ -239,11 +281,12 @@ class TrajARNet(KinPolicy):
         Qb = torch.empty((T, N, 76), device=dev); Vb = torch.empty((T, N, 75), device=dev); Ab = torch.empty((T, N, 80), device=dev)
         Qb[0].copy_(init_qpos); Vb[0].copy_(init_qvel)
         hx = self.init_hidden(N, dev)
+        ext = self.obs_ext(kin_sim, data, None if ctx_feat is None else ctx_feat.transpose(0, 1))      # None for a network without a context / `of` block
         for t in range(T):
             cur_t.fill_(t)
             obj.copy_(data["obj_pose"][:, t, :7])
             kin_sim.set_state(Qb[t], Vb[t])                    # forward kinematics of the kinematic state
-            state = kin_sim.obs_ar(ctx)
+            state = kin_sim.obs_ar(ctx) if ext is None else kin_sim.obs_ar_ex(ctx, ext)
             action, hx = self.get_action(state, hx)
             Ab[t].copy_(action)
             if t == T - 1:
@@ -271,20 +314,22 @@ class PolicyARContext:
         self.net, self.kin_sim, self.smooth, self.smooth_time_axis = net, kin_sim, smooth, smooth_time_axis
         self.need_rollout, self.keep_context_feat = need_rollout, keep_context_feat
 
-    def _rollout_any(self, data, init_qpos, init_qvel):
+    def _rollout_any(self, data, init_qpos, init_qvel, ctx_feat=None):
         """TrajARNet.rollout for any number of clips: the kinematic twin simulator holds kin_sim.n rows, so other batch sizes go through it in
-        chunks of that many (the last one padded with copies of its last clip)."""
+        chunks of that many (the last one padded with copies of its last clip).  ctx_feat [N, T, H] (a network with a context block) and data['of']
+        are chunked along."""
         m, n = init_qpos.shape[0], self.kin_sim.n
         if m == n:
-            q, v, _ = self.net.rollout(data, self.kin_sim, init_qpos, init_qvel)
+            q, v, _ = self.net.rollout(data, self.kin_sim, init_qpos, init_qvel, ctx_feat=ctx_feat)
             return q, v
-        keys = ("qpos", "head_pose", "head_vels", "obj_head_relative_poses", "action_one_hot", "obj_pose")
+        keys = ("qpos", "head_pose", "head_vels", "obj_head_relative_poses", "action_one_hot", "obj_pose") + (("of",) if self.net.of_in_state else ())
         qs, vs = [], []
         for i in range(0, m, n):
             k = min(n, m - i)
             idx = torch.arange(i, i + n, device=init_qpos.device).clamp_(max=m - 1)
             part = {key: data[key][idx].contiguous() for key in keys}
-            q, v, _ = self.net.rollout(part, self.kin_sim, init_qpos[idx].contiguous(), init_qvel[idx].contiguous())
+            part_ctx = None if ctx_feat is None else ctx_feat[idx].transpose(0, 1).contiguous().transpose(0, 1)      # the chunk's own time-major storage
+            q, v, _ = self.net.rollout(part, self.kin_sim, init_qpos[idx].contiguous(), init_qvel[idx].contiguous(), ctx_feat=part_ctx)
             qs.append(q[:k]); vs.append(v[:k])
         return torch.cat(qs, 0), torch.cat(vs, 0)
 
@@ -292,7 +337,7 @@ class PolicyARContext:
     def init_context(self, data: dict, fix_height: bool = False, need_rollout: bool | None = None) -> dict:
         out = dict(data)
         need_rollout = self.need_rollout if need_rollout is None else need_rollout
-        init_qpos, init_qvel, ctx_feat = self.net.init_states(data, keep_feat=self.keep_context_feat)
+        init_qpos, init_qvel, ctx_feat = self.net.init_states(data, keep_feat=self.keep_context_feat or (need_rollout and bool(self.net.ctx_block)))
         out["init_qpos"], out["init_qvel"] = init_qpos.contiguous(), init_qvel.contiguous()
         if ctx_feat is not None:
             out["context_feat_rnn"] = ctx_feat
@@ -304,7 +349,7 @@ class PolicyARContext:
             out["init_qpos"] = torch.cat([out["init_qpos"][:, :2], (out["init_qpos"][:, 2] - feet)[:, None], out["init_qpos"][:, 3:]], 1).contiguous()
         if not need_rollout:
             return out
-        ar_qpos, ar_qvel = self._rollout_any(data, init_qpos, init_qvel)
+        ar_qpos, ar_qvel = self._rollout_any(data, init_qpos, init_qvel, ctx_feat if self.net.ctx_block else None)
         N, T = ar_qpos.shape[:2]
         if self.smooth:
             if self.smooth_time_axis:      # NOT what the reference computes (its filter call is a no-op, module docstring)

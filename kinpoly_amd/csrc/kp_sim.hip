@@ -23,6 +23,7 @@
 #include "kp_pose_contacts.hpp"
 #include "kp_takes.hpp"
 #include "kp_kin_tape.hpp"
+#include "kp_obs_ctx.hpp"
 
 namespace {
 thread_local std::string g_err;
@@ -1293,8 +1294,12 @@ int kp_mcp_tail(int n, int K, int J, int A, const float* h2, const float* b2, co
 
 int kp_gru_cell_step(int n, int H, int D, const float* gi, const float* gh, const float* b_ih, const float* b_hh, const float* h_in, const float* state,
                      float* h_out, float* xcat, void* stream) {
-    if (n <= 0 || H <= 0 || !gi || !gh || !b_ih || !b_hh || !h_in || !h_out || (xcat && (!state || D <= 0 || D > H)))
-        return fail("kp_gru_cell_step: bad arguments (the [state | h] row needs state and 0 < D <= H)");
+    if (n <= 0 || H <= 0 || !gi || !gh || !b_ih || !b_hh || !h_in || !h_out || (xcat && (!state || D <= 0)))
+        return fail("kp_gru_cell_step: bad arguments (the [state | h] row needs state and D > 0)");
+    if (xcat && D > H) {      // a state wider than the hidden state (use_context / use_of): the kernel whose copy loops over the columns
+        HIP_OK(kp::launch_gru_cell_step_wide(n, H, D, gi, gh, b_ih, b_hh, h_in, state, h_out, xcat, (hipStream_t)stream));
+        return 0;
+    }
     const size_t tot = (size_t)n * H;
     hipLaunchKernelGGL(kp::k_gru_cell_step, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, H, D, gi, gh, b_ih, b_hh, h_in, state, h_out, xcat);
     return launched();
@@ -1467,6 +1472,60 @@ int kp_sim_fk_head_backward(kp_sim* s, int n_rows, const float* qpos, const floa
     HIP_OK(hipSetDevice(s->device));
     HIP_OK(kp::launch_fk_head_grad(kp::FkHeadGradArgs{n_rows, qpos, wbpos, wbquat, grad_wbpos, grad_hpos, grad_hquat, grad_qpos_add, grad_qpos,
                                                       s->T.body_parent, s->T.body_subtree}, s->stream));
+    return 0;
+}
+
+// ---- the observation with a context / `of` block (kp_obs_ctx.hip)
+static int check_obs_ext(const char* who, const kp_obs_ext* x) {
+    const std::string w(who);
+    if (!x) return fail(w + ": null kp_obs_ext");
+    if (x->ctx_dim < 0 || x->of_dim < 0) return fail(w + ": negative ctx_dim / of_dim");
+    if (x->of_dim > 0 && !x->of) return fail(w + ": of_dim > 0 with a null `of` table");
+    if (x->ctx_dim > 0 && x->ctx_feat && (x->ctx_stride_row < 1 || x->ctx_stride_t < 1)) return fail(w + ": ctx_feat needs strides >= 1 (in floats)");
+    if (x->of_dim > 0 && (x->of_stride_row < 1 || x->of_stride_t < 1)) return fail(w + ": `of` needs strides >= 1 (in floats)");
+    return 0;
+}
+
+int kp_sim_obs_ar_ex(kp_sim* s, const kp_ctx* c, const kp_obs_ext* x, float* out) {
+    if (!s || !c || !out || !c->head_pose || !c->head_vels || !c->obj_head_relative_poses || !c->action_one_hot || !c->cur_t || c->T < 1)
+        return fail("kp_sim_obs_ar_ex: bad arguments");
+    if (check_obs_ext("kp_sim_obs_ar_ex", x)) return -1;
+    HIP_OK(hipSetDevice(s->device));
+    kp::ObsArCtxArgs A{};
+    A.n = s->n; A.vel = s->ar_obs_vel; A.head = s->ar_obs_head; A.action = s->ar_obs_action;
+    A.T = c->T; A.head_pose = c->head_pose; A.head_vels = c->head_vels; A.obj_rel = c->obj_head_relative_poses; A.action_one_hot = c->action_one_hot;
+    A.obj_qpos = c->obj_qpos; A.cur_t = c->cur_t; A.row = c->row;
+    A.ctx_dim = x->ctx_dim; A.ctx_feat = x->ctx_dim > 0 ? x->ctx_feat : nullptr; A.ctx_stride_row = x->ctx_stride_row; A.ctx_stride_t = x->ctx_stride_t;
+    A.of_dim = x->of_dim; A.of = x->of_dim > 0 ? x->of : nullptr; A.of_stride_row = x->of_stride_row; A.of_stride_t = x->of_stride_t;
+    A.qpos = s->st.qpos; A.qvel = s->st.qvel; A.xpos = s->st.xpos; A.xquat = s->st.xquat; A.out = out;
+    HIP_OK(kp::launch_obs_ar_ctx(A, s->stream));
+    return 0;
+}
+
+int kp_sim_obs_ar_ex_backward(kp_sim* s, const kp_ctx* c, const kp_obs_ext* x, int n_rows, int grad_width, const float* qpos, const float* wbpos,
+                              const float* wbquat, const float* grad_obs, const float* grad_obj_2_head, float* grad_qpos, float* grad_qvel,
+                              float* grad_hpos, float* grad_hquat, float* grad_ctx) {
+    if (!s) return fail("kp_sim_obs_ar_ex_backward: null sim");
+    if (!s->ar_obs_head && !s->ar_obs_action)
+        return fail("kp_sim_obs_ar_ex_backward: the " + std::to_string(s->ar_obs_dim) + "-d layout (use_head and use_action both off) has no gradient kernel");
+    if (check_obs_ext("kp_sim_obs_ar_ex_backward", x)) return -1;
+    if (n_rows < 0 || n_rows > s->n) return fail("kp_sim_obs_ar_ex_backward: n_rows must be in [0, " + std::to_string(s->n) + "], got " + std::to_string(n_rows));
+    const int pitch = x->ctx_dim + s->ar_obs_dim + x->of_dim;
+    if (grad_width != pitch)
+        return fail("kp_sim_obs_ar_ex_backward: grad_obs is " + std::to_string(grad_width) + " wide, the row " + std::to_string(pitch) + " (" +
+                    std::to_string(x->ctx_dim) + " + " + std::to_string(s->ar_obs_dim) + " + " + std::to_string(x->of_dim) + ")");
+    if (!c || !c->action_one_hot || !c->cur_t || c->T < 1 || (s->ar_obs_head && !c->head_pose)) return fail("kp_sim_obs_ar_ex_backward: null or empty context");
+    if (!qpos || !wbpos || !wbquat || !grad_obs) return fail("kp_sim_obs_ar_ex_backward: null qpos / wbpos / wbquat / grad_obs");
+    if (!grad_qpos || !grad_hpos || !grad_hquat || (s->ar_obs_vel && !grad_qvel) || (x->ctx_dim > 0 && !grad_ctx)) return fail("kp_sim_obs_ar_ex_backward: null output");
+    if (n_rows == 0) return 0;
+    HIP_OK(hipSetDevice(s->device));
+    kp::ObsArGradArgs A{};
+    A.n = n_rows; A.vel = s->ar_obs_vel; A.head = s->ar_obs_head; A.width = pitch;      // the base block at its offset, rows `pitch` floats apart
+    A.T = c->T; A.head_pose = c->head_pose; A.action_one_hot = c->action_one_hot; A.obj_qpos = c->obj_qpos; A.cur_t = c->cur_t; A.row = c->row;
+    A.qpos = qpos; A.wbpos = wbpos; A.wbquat = wbquat; A.g_obs = grad_obs + x->ctx_dim; A.g_obj = grad_obj_2_head;
+    A.g_qpos = grad_qpos; A.g_qvel = grad_qvel; A.g_hpos = grad_hpos; A.g_hquat = grad_hquat;
+    HIP_OK(kp::launch_obs_ar_grad(A, s->stream));
+    if (x->ctx_dim > 0) HIP_OK(kp::launch_obs_ctx_grad(n_rows, x->ctx_dim, grad_obs, pitch, grad_ctx, s->stream));
     return 0;
 }
 

@@ -94,10 +94,17 @@ def write_features(path, takes: dict):
 class StateARDataset:
     KEYS = ("qvel", "target", "qpos", "head_vels", "head_pose", "action_one_hot", "obj_head_relative_poses", "obj_pose")
 
-    def __init__(self, features, takes=None, data_mode="train", fr_num=100, wild=False, dt=1.0 / 30.0, seed=0, device="cpu"):
+    def __init__(self, features, takes=None, data_mode="train", fr_num=100, wild=False, dt=1.0 / 30.0, seed=0, device="cpu", of_features=None):
+        """of_features (`use_of`): <dataset_path>/features/<of_file>.p or its content, a dict take -> [T, F] of per-frame image features
+        (statear_smpl_dataset.py:87-90, 286, 369); batches then carry data['of'] [n, T, F], gathered like every other key.  F is the file's: every
+        take must have the same, and as many frames as the take."""
         if isinstance(features, (str, os.PathLike)):
             import joblib
             features = joblib.load(features)
+        if isinstance(of_features, (str, os.PathLike)):
+            import joblib
+            of_features = joblib.load(of_features)
+        self.of_dim = 0
         self.rng = np.random.RandomState(seed)
         self.data_mode, self.fr_num, self.dt, self.wild, self.device = data_mode, int(fr_num), dt, wild, torch.device(device)
         self.takes, self.data = [], {k: [] for k in self.KEYS + (TRAIN_KEYS if data_mode == "train" and not wild else ())}
@@ -107,10 +114,22 @@ class StateARDataset:
             if data_mode == "train" and q.shape[0] < self.fr_num and not wild:
                 continue                                        # :100-102
             assert len(e["of_files"]) == q.shape[0]
+            if of_features is not None:
+                if take not in of_features:
+                    raise ValueError(f"StateARDataset: take '{take}' is absent from the of features")
+                of = torch.as_tensor(np.asarray(of_features[take]), dtype=torch.float32)
+                if of.dim() != 2 or of.shape[0] != q.shape[0]:
+                    raise ValueError(f"StateARDataset: the of features of take '{take}' have shape {tuple(of.shape)}, the take has {q.shape[0]} frames")
+                if self.of_dim and of.shape[1] != self.of_dim:
+                    raise ValueError(f"StateARDataset: the of features of take '{take}' are {of.shape[1]} wide, those of '{self.takes[0]}' {self.of_dim}")
+                self.of_dim = int(of.shape[1])
+                self.data.setdefault("of", []).append(of)
             target = torch.cat([get_traj_de_heading(q), torch.cat([_fd_vel(q[:-1, :7], q[1:, :7], dt)] + [_fd_vel(q[-2:-1, :7], q[-1:, :7], dt)], 0)], 1)
             row = dict(qvel=e["qvel"], target=target, qpos=q, head_vels=e["head_vels"], head_pose=e["head_pose"], action_one_hot=e["action_one_hot"],
                        obj_head_relative_poses=np.asarray(e["obj_head_relative_poses"])[:, :7], obj_pose=e["obj_pose"])
             for k in self.data:
+                if k == "of":
+                    continue
                 v = row[k] if k in row else e[k]
                 v = torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v, dtype=torch.float32)
                 if k == "obj_pose" and v.shape[1] < 14:       # one width for every take (push carries two objects): zero-padded, the env
@@ -247,6 +266,21 @@ def synthetic_takes(sim, std_qpos, n_per_action=2, T_range=(110, 160), body_mass
             else:
                 takes[f"none-synthetic-{a}-{j:02d}"] = build_take_features(sim, q, None, None, body_mass)
     return takes
+
+
+def synthetic_of_features(takes: dict, dim: int = 512, seed: int = 0) -> dict:
+    """A stand-in of THIS repository for <dataset_path>/features/<of_file>.p (the reference's per-frame image features, which no public sample
+    carries), as synthetic_takes stands in for the MoCap set: take -> [T, dim] float32, a seeded random projection of the take's head velocities
+    and pose -- smooth in time and a function of the motion, as an optical-flow feature is -- plus N(0, 0.1) noise.  A workload and a test input,
+    not a learning target."""
+    rng = np.random.default_rng(seed)
+    proj = rng.standard_normal((6 + 69, int(dim))) / np.sqrt(75.0)
+    out = {}
+    for take in sorted(takes):
+        e = takes[take]
+        x = np.concatenate([np.asarray(e["head_vels"], np.float64), np.asarray(e["qpos"], np.float64)[:, 7:]], 1)
+        out[take] = (np.tanh(x @ proj) + 0.1 * rng.standard_normal((x.shape[0], int(dim)))).astype(np.float32)
+    return out
 
 
 def _ewma(x, alpha=0.05):

@@ -20,6 +20,8 @@ FR_NUM_START, FR_NUM_END = 80, 150         # exp_arnet_all.py:116-117
 # what `scripts/exp_arnet_all.py --dtype fp32` trains on without --path: the taped roll-out, measured faster than the torch path by the rule of
 # tools/warm_start_time.py --fused (DESIGN.md section 10 holds the record)
 DEFAULT_PATH = "taped"
+# the same for a network with a context block (kin_only.yml, use_of.yml): section 10's second record
+DEFAULT_PATH_CONTEXT = "taped"
 
 
 def sampling_rate_at(i_epoch: int, num_epoch: int) -> float:
@@ -32,12 +34,15 @@ def fr_num_at(i_epoch: int, num_epoch: int) -> int:
     return int(FR_NUM_START + i_epoch / num_epoch * (FR_NUM_END - FR_NUM_START) // 5 * 5)
 
 
-def build_net(use_vel=False, use_head=True, use_action=True, as_policy=False, **kw) -> TrajARNet:
+def build_net(use_vel=False, use_head=True, use_action=True, as_policy=False, use_context=False, of_dim=0, **kw) -> TrajARNet:
     """The reference's TrajARNet(as_policy=False): the state has no action one-hot whatever use_action says, the context GRU's input follows
-    use_action.  as_policy: the state carries the one-hot when use_action does (the network train_ar_policy.py --load can start from)."""
+    use_action.  as_policy: the state carries the one-hot when use_action does (the network train_ar_policy.py --load can start from) and, with
+    of_dim > 0 (`use_of`), the frame's image feature (traj_ar_smpl_net.py:281-285).  use_context / of_dim: kin_only.yml / use_of.yml's context block.
+    kw: rnn_hdim, mlp_hsize (Config.model_kwargs)."""
     state_action = bool(use_action) and bool(as_policy)
-    net = TrajARNet(state_dim=kpsim.ar_obs_dim(use_vel, use_head, state_action), context_dim=13 * bool(use_head) + 4 * bool(use_action),
-                    use_action=use_action, use_vel=use_vel, use_head=use_head, **kw)
+    ctx_block = int(kw.get("rnn_hdim", 1024)) if (use_context or of_dim) else 0
+    net = TrajARNet(state_dim=ctx_block + kpsim.ar_obs_dim(use_vel, use_head, state_action) + int(of_dim) * bool(as_policy),
+                    use_action=use_action, use_vel=use_vel, use_head=use_head, use_context=use_context, of_dim=of_dim, of_in_state=bool(as_policy) and bool(of_dim), **kw)
     net.obs_action = state_action          # the kinematic handle's ar_obs_action
     return net
 
@@ -100,7 +105,7 @@ def test_takes(net, kin_model, dataset, device):
     for ind, take in enumerate(dataset.takes):
         data = dataset.batch([ind], [0], None)
         data = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in data.items()}
-        q0, v0, _ = net.init_states(data, keep_feat=False)
-        Q, _, _ = net.rollout(data, sim, q0.contiguous(), v0.contiguous())
+        q0, v0, ctx_feat = net.init_states(data, keep_feat=bool(net.ctx_block))      # a context block reads the sequence in every frame's observation
+        Q, _, _ = net.rollout(data, sim, q0.contiguous(), v0.contiguous(), ctx_feat=ctx_feat)
         out[take] = {"qpos": Q[0].cpu().numpy(), "qpos_gt": data["qpos"][0].cpu().numpy(), "obj_pose": data["obj_pose"][0].cpu().numpy()}
     return out

@@ -42,18 +42,20 @@ class KinAdvance(torch.autograd.Function):
 
 
 class ObserveFrame(torch.autograd.Function):
-    """(qpos [N,76], qvel [N,75]) -> (obs [N,W], wbpos [N,72], obj_2_head [N,7]) of one frame on a physics-free KpSim of N rows: set_state +
+    """(qpos [N,76], qvel [N,75], slab) -> (obs [N,W], wbpos [N,72], obj_2_head [N,7]) of one frame on a physics-free KpSim of N rows: set_state +
     kp_sim_obs_ar + kp_sim_fk forward, kp_sim_obs_ar_backward + kp_sim_fk_head_backward backward.  `frame` is the frame's own kp_ctx (its cur_t and
-    object rows are not reused by later frames: the backward pass reads them again)."""
+    object rows are not reused by later frames: the backward pass reads them again).  With `ext` (a network with a context / `of` block) the row is
+    kp_sim_obs_ar_ex's [context | base | of]; slab [N,H] is then the frame's slab of the time-major context sequence ext points into -- the third
+    differentiable input, whose gradient is the first H columns of the row's cotangent; the `of` block is data.  Without ext, slab is None."""
 
     @staticmethod
-    def forward(ctx, qpos, qvel, sim, frame):
+    def forward(ctx, qpos, qvel, slab, sim, frame, ext=None):
         q, v = qpos.contiguous(), qvel.contiguous()
         sim.set_state(q, v)
-        obs = sim.obs_ar(frame)
+        obs = sim.obs_ar(frame) if ext is None else sim.obs_ar_ex(frame, ext)
         fk = sim.fk(q)
-        o = 74 + 75 * sim.obs_ar_vel + 7 * sim.obs_ar_head
-        ctx.sim, ctx.frame = sim, frame
+        o = (0 if ext is None else ext.ctx_dim) + 74 + 75 * sim.obs_ar_vel + 7 * sim.obs_ar_head
+        ctx.sim, ctx.frame, ctx.ext = sim, frame, ext
         ctx.save_for_backward(q, fk["wbpos"], fk["wbquat"])
         ctx.set_materialize_grads(False)
         return obs, fk["wbpos"], obs[:, o:o + 7].clone()
@@ -61,11 +63,17 @@ class ObserveFrame(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_obs, g_wb, g_obj):
         q, wbpos, wbquat = ctx.saved_tensors
-        sim = ctx.sim
-        g_obs = torch.zeros((q.shape[0], sim.obs_ar_dim), device=q.device) if g_obs is None else g_obs.contiguous()
-        gq, gv, ghp, ghq = sim.obs_ar_backward(ctx.frame, q, wbpos, wbquat, g_obs, None if g_obj is None else g_obj.contiguous())
+        sim, ext = ctx.sim, ctx.ext
+        g_obj = None if g_obj is None else g_obj.contiguous()
+        gc = None
+        if ext is None:
+            g_obs = torch.zeros((q.shape[0], sim.obs_ar_dim), device=q.device) if g_obs is None else g_obs.contiguous()
+            gq, gv, ghp, ghq = sim.obs_ar_backward(ctx.frame, q, wbpos, wbquat, g_obs, g_obj)
+        else:
+            g_obs = torch.zeros((q.shape[0], ext.ctx_dim + sim.obs_ar_dim + ext.of_dim), device=q.device) if g_obs is None else g_obs.contiguous()
+            gq, gv, ghp, ghq, gc = sim.obs_ar_ex_backward(ctx.frame, ext, q, wbpos, wbquat, g_obs, g_obj)
         gq = sim.fk_head_backward(q, wbpos, wbquat, None if g_wb is None else g_wb.contiguous(), ghp, ghq, gq)
-        return gq, gv, None, None
+        return gq, gv, (gc if ctx.needs_input_grad[2] else None), None, None, None
 
 
 _TWINS: dict = {}
@@ -93,18 +101,19 @@ def twin_sim(sim: kpsim.KpSim, n: int) -> kpsim.KpSim:
 
 def check_fused(net, fk, data=None):
     """Raises with the reason when the taped path cannot run: it needs an fp32 network on a HIP device, the library's FK behind `fk`, and one of the six
-    layouts Config accepts."""
+    layouts Config accepts as the network's base row (a context block before it and an `of` block after it ride along: kp_sim_obs_ar_ex)."""
     p = next(net.parameters())
     if not (p.is_cuda and p.dtype == torch.float32):
         raise ValueError(f"fused=True runs the fp32 HIP kernels: the network is {p.dtype} on {p.device} (fp64 master copies, --update_dtype fp64, stay on the torch path)")
     if getattr(fk, "sim", None) is None:
         raise ValueError("fused=True needs a TorchFK built on a KpSim (sim=...): the taped roll-out runs on a physics-free twin of it")
-    if net.state_dim not in FUSED_LAYOUTS:
-        raise ValueError(f"fused=True: no gradient kernel for the {net.state_dim}-d observation (layouts: {', '.join(map(str, FUSED_LAYOUTS))})")
-    if fk.sim.obs_ar_dim != net.state_dim:
-        raise ValueError(f"fused=True: the kinematic simulator writes {fk.sim.obs_ar_dim}-d observations, the policy takes {net.state_dim}-d (kpsim.ar_obs_options)")
+    base = getattr(net, "base_dim", net.state_dim)
+    if base not in FUSED_LAYOUTS:
+        raise ValueError(f"fused=True: no gradient kernel for the {base}-d observation (layouts: {', '.join(map(str, FUSED_LAYOUTS))})")
+    if fk.sim.obs_ar_dim != base:
+        raise ValueError(f"fused=True: the kinematic simulator writes {fk.sim.obs_ar_dim}-d observations, the policy takes {base}-d (kpsim.ar_obs_options)")
     if data is not None:
-        for k in ("qpos", "head_pose", "head_vels", "obj_head_relative_poses", "obj_pose"):
+        for k in ("qpos", "head_pose", "head_vels", "obj_head_relative_poses", "obj_pose") + (("of",) if getattr(net, "of_dim", 0) else ()):
             if not (data[k].is_cuda and data[k].dtype == torch.float32):
                 raise ValueError(f"fused=True: data['{k}'] is {data[k].dtype} on {data[k].device}, the kernels read fp32 device tensors")
 
@@ -128,7 +137,13 @@ def forward_supervised_taped(net, fk, data, gt_rate=0.0, rng=None, noise_std=0.0
     B, T = data["qpos"].shape[:2]
     sim = twin_sim(fk.sim, B)
     dev = data["qpos"].device
-    qpos, qvel, _ = net.init_states(data, keep_feat=False)
+    ctx_block = getattr(net, "ctx_block", 0)
+    qpos, qvel, ctx_feat = net.init_states(data, keep_feat=bool(ctx_block))
+    # a context block: the time-major sequence the init mean came from (clean tables: the noise below is the observation's); frame t's slab is a view
+    # of it, so a frame put on the ground-truth pose still hands its context cotangent back, and the backward over the frames is one stack
+    seq = ctx_feat.transpose(0, 1) if ctx_block else None
+    slabs = seq.unbind(0) if ctx_block else None
+    ext = net.obs_ext(sim, data, None if seq is None else seq.detach())
     if gt_rate > 0.0 and rng.binomial(1, gt_rate):
         qpos, qvel = data["qpos"][:, 0], data["qvel"][:, 0]
     tabs = [data[k].contiguous() for k in ("head_pose", "head_vels", "obj_head_relative_poses")]
@@ -142,7 +157,7 @@ def forward_supervised_taped(net, fk, data, gt_rate=0.0, rng=None, noise_std=0.0
     hx = torch.zeros((B, net.rnn_hdim), device=dev, dtype=qpos.dtype)
     Q, V, A, W, O = [], [], [], [], []
     for t in range(T):
-        obs, wb, orel = ObserveFrame.apply(qpos, qvel, sim, _frame_ctx(base, cur[t], obj[t]))
+        obs, wb, orel = ObserveFrame.apply(qpos, qvel, slabs[t] if ctx_block else None, sim, _frame_ctx(base, cur[t], obj[t]), ext)
         Q.append(qpos); V.append(qvel); W.append(wb); O.append(orel)
         action, hx = net.get_action(obs, hx)
         A.append(action)

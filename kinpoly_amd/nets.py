@@ -236,7 +236,7 @@ class KinPolicy(nn.Module):
 
     def get_action(self, state, hx):
         cell = self.action_rnn.rnn_f
-        if state.is_cuda and state.dtype == torch.float32 and state.dim() == 2 and not torch.is_grad_enabled() and state.shape[1] <= self.rnn_hdim:
+        if state.is_cuda and state.dtype == torch.float32 and state.dim() == 2 and not torch.is_grad_enabled():
             # roll-out step on the device: the two gate GEMMs (library, MFMA) + one kernel for the gate math that also writes [state | h'],
             # the action MLP's input row, in place of gru_cell_forward (+ its backward workspace) and torch.cat
             from . import sim as kpsim

@@ -25,11 +25,14 @@ def _one_hot_at(data, t):
     return oh if oh.dim() == 2 else oh[:, t]
 
 
-def observe(fk: TorchFK, qpos, data, t, noise_std=0.0, generator=None, use_action=True, use_vel=False, use_head=True, qvel=None):
-    """TrajARNet.get_obs (:203-290) under the use_vel / use_head / use_action switches (no use_of / use_context), differentiable in qpos.
-    Returns (obs [B, kinpoly_amd.sim.ar_obs_dim(use_vel, use_head, use_action)], features: pred_wbpos [B,72], obj_2_head [B,7]); the defaults are
-    kin_poly.yml's 105-d row.  use_action=False: without the one-hot (:281-282); use_vel: `qvel` [B, 75] (the roll-out's current velocity,
-    sim['qvel']) follows the pose block (:265-266); use_head=False: no head-difference and no head-target blocks (:232-251, 268-277)."""
+def observe(fk: TorchFK, qpos, data, t, noise_std=0.0, generator=None, use_action=True, use_vel=False, use_head=True, qvel=None, ctx=None, of=None):
+    """TrajARNet.get_obs (:203-290) under the use_vel / use_head / use_action switches, differentiable in qpos (and ctx).
+    Returns (obs [B, kinpoly_amd.sim.ar_obs_dim(use_vel, use_head, use_action) (+ the two blocks below)], features: pred_wbpos [B,72], obj_2_head [B,7]);
+    the defaults are kin_poly.yml's 105-d row.  use_action=False: without the one-hot (:281-282); use_vel: `qvel` [B, 75] (the roll-out's current velocity,
+    sim['qvel']) follows the pose block (:265-266); use_head=False: no head-difference and no head-target blocks (:232-251, 268-277).
+    ctx [B, H]: the context GRU's hidden state at frame t, the row's first block under use_context / use_of (:226-230; zeros while there is no
+    sequence); of [B, F]: the frame's image feature, the row's last block of a network built as a policy (:284-285).  The noise stays on the five
+    head quantities."""
     wbpos = fk.wbpos(qpos)                     # float32 device rows: k_target_fk forward / k_fk_wbpos_grad backward (supervised.TorchFK)
     hpos, hrot = wbpos[:, HEAD], fk.body_quat(qpos, HEAD)
     local = torch.cat([qpos[:, 2:3], quat_mul(quat_inv(heading_q(qpos[:, 3:7])), qpos[:, 3:7]), qpos[:, 7:]], 1)        # height, de-headed root, pose: 74
@@ -45,8 +48,8 @@ def observe(fk: TorchFK, qpos, data, t, noise_std=0.0, generator=None, use_actio
     obj_rel = torch.cat([quat_rotate_t(heading_q(hrot), obj[:, :3] - hpos), quat_mul(quat_inv(heading_q(hrot)), obj[:, 3:7])], 1)
     if use_vel and qvel is None:
         raise ValueError("observe: use_vel needs the roll-out's current qvel")
-    obs = torch.cat([local] + ([qvel] if use_vel else []) + ([diff_hpos, diff_hrot] if use_head else []) + [obj_rel] +
-                    ([t_havel, t_hlvel, t_obj] if use_head else []) + ([_one_hot_at(data, t)] if use_action else []), 1)
+    obs = torch.cat(([ctx] if ctx is not None else []) + [local] + ([qvel] if use_vel else []) + ([diff_hpos, diff_hrot] if use_head else []) + [obj_rel] +
+                    ([t_havel, t_hlvel, t_obj] if use_head else []) + ([_one_hot_at(data, t)] if use_action else []) + ([of] if of is not None else []), 1)
     return obs, wbpos.reshape(qpos.shape[0], 72), obj_rel
 
 
@@ -57,7 +60,9 @@ def forward_supervised(net, fk: TorchFK, data, gt_rate=0.0, rng=None, noise_std=
     qpos [B,T,76], qvel [B,T,75] (after fix_qvel), action [B,T,80], pred_wbpos [B,T,72], obj_2_head [B,T,7]."""
     rng = np.random if rng is None else rng
     B, T = data["qpos"].shape[:2]
-    qpos, qvel, _ = net.init_states(data, keep_feat=False)
+    ctx_block, of_in_state = getattr(net, "ctx_block", 0), getattr(net, "of_in_state", False)
+    qpos, qvel, ctx_feat = net.init_states(data, keep_feat=bool(ctx_block))        # a context block reads the sequence the mean came from
+    slabs = ctx_feat.transpose(0, 1).unbind(0) if ctx_block else None                # time-major: frame t's [B, H] slab
     if gt_rate > 0.0 and rng.binomial(1, gt_rate):
         qpos, qvel = data["qpos"][:, 0], data["qvel"][:, 0]
     hx = torch.zeros((B, net.rnn_hdim), device=qpos.device, dtype=qpos.dtype)
@@ -65,7 +70,7 @@ def forward_supervised(net, fk: TorchFK, data, gt_rate=0.0, rng=None, noise_std=
     for t in range(T):
         # obs_action: a network whose state lacks the one-hot although its context GRU reads it (exp_arnet.build_net, the reference's as_policy=False)
         obs, wb, orel = observe(fk, qpos, data, t, noise_std, generator, getattr(net, "obs_action", getattr(net, "use_action", True)), getattr(net, "use_vel", False),
-                                getattr(net, "use_head", True), qvel)
+                                getattr(net, "use_head", True), qvel, slabs[t] if ctx_block else None, data["of"][:, t] if of_in_state else None)
         Q.append(qpos); V.append(qvel); W.append(wb); O.append(orel)
         action, hx = net.get_action(obs, hx)
         A.append(action)

@@ -49,6 +49,12 @@ class KpCtx(C.Structure):
                 ("cur_t", C.c_void_p), ("row", C.c_void_p)]
 
 
+class KpObsExt(C.Structure):
+    """mirror of kp_obs_ext (include/kinpoly_sim.h): the context and `of` tables of kp_sim_obs_ar_ex, strides in floats"""
+    _fields_ = [("ctx_dim", C.c_int), ("ctx_feat", C.c_void_p), ("ctx_stride_row", C.c_long), ("ctx_stride_t", C.c_long),
+                ("of_dim", C.c_int), ("of", C.c_void_p), ("of_stride_row", C.c_long), ("of_stride_t", C.c_long)]
+
+
 class KpRecordPre(C.Structure):
     """mirror of kp_record_pre (include/kinpoly_sim.h)"""
     _fields_ = [(k, C.c_int) for k in ("n", "T", "t", "ctx_T")] + [(k, C.c_void_p) for k in (
@@ -89,7 +95,7 @@ class KinPolyNativeError(RuntimeError):
 
 _V, _I, _F, _D, _S = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_char_p      # handles and device / host arrays are all void*
 _PI = C.POINTER(C.c_int)
-_CTX, _RW, _PRE, _POST, _UST, _UCFG = (C.POINTER(k) for k in (KpCtx, KpRewardCfg, KpRecordPre, KpRecordPost, KpUhcState, KpUhcCfg))
+_CTX, _RW, _PRE, _POST, _UST, _UCFG, _EXT = (C.POINTER(k) for k in (KpCtx, KpRewardCfg, KpRecordPre, KpRecordPost, KpUhcState, KpUhcCfg, KpObsExt))
 # every symbol include/kinpoly_sim.h declares: symbol -> (restype, argtypes).  load_library types them all from here, and tests check the header against it.
 _SIGNATURES = {
     "kp_last_error": (_S, []), "kp_version": (_S, []),
@@ -129,6 +135,9 @@ _SIGNATURES = {
     "kp_kin_advance_backward": (_I, [_I, _V, _V, _F, _V, _V, _V, _V, _V]),
     "kp_sim_obs_ar_backward": (_I, [_V, _CTX, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     "kp_sim_fk_head_backward": (_I, [_V, _I, _V, _V, _V, _V, _V, _V, _V, _V]),
+    # the observation with a context / `of` block (kp_obs_ctx.hip)
+    "kp_sim_obs_ar_ex": (_I, [_V, _CTX, _EXT, _V]),
+    "kp_sim_obs_ar_ex_backward": (_I, [_V, _CTX, _EXT, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
 }
 ABI_SYMBOLS = list(_SIGNATURES)
 
@@ -448,6 +457,43 @@ class KpSim:
         out = self._new(self.obs_ar_dim) if out is None else out
         _check(self.L.kp_sim_obs_ar(self.h, C.byref(ctx), _ptr(out, self.n, self.obs_ar_dim)), "kp_sim_obs_ar")
         return out
+
+    def make_obs_ext(self, T, rows, ctx_dim=0, ctx_feat=None, of=None, ctx_time_major=True, of_time_major=False) -> "KpObsExt":
+        """kp_obs_ext for a kp_ctx of `rows` context rows and T frames: ctx_feat [T, rows, ctx_dim] (time-major, what get_context_feat keeps) or
+        [rows, T, ctx_dim], None = the zero block; of [rows, T, F] (the data set's) or [T, rows, F], None = no `of` block."""
+        def table(name, t, time_major, dim):
+            _dev("obs_ext: " + name, t, (T, rows, dim) if time_major else (rows, T, dim))
+            return (dim, rows * dim) if time_major else (T * dim, dim)          # (stride_row, stride_t)
+        x = KpObsExt(int(ctx_dim), None, 0, 0, 0, None, 0, 0)
+        if ctx_feat is not None:
+            x.ctx_feat = ctx_feat.data_ptr()
+            x.ctx_stride_row, x.ctx_stride_t = table("ctx_feat", ctx_feat, ctx_time_major, int(ctx_dim))
+        if of is not None:
+            _dev("obs_ext: of", of, (None, None, None))
+            x.of_dim, x.of = int(of.shape[2]), of.data_ptr()
+            x.of_stride_row, x.of_stride_t = table("of", of, of_time_major, int(of.shape[2]))
+        x._keep = (ctx_feat, of)
+        return x
+
+    def obs_ar_ex(self, ctx: "KpCtx", ext: "KpObsExt", out=None):
+        """[context block | obs_ar's row | of block] in one launch (kp_sim_obs_ar_ex) -> [N, ext.ctx_dim + obs_ar_dim + ext.of_dim]"""
+        W = ext.ctx_dim + self.obs_ar_dim + ext.of_dim
+        out = self._new(W) if out is None else out
+        _check(self.L.kp_sim_obs_ar_ex(self.h, C.byref(ctx), C.byref(ext), _ptr(out, self.n, W)), "kp_sim_obs_ar_ex")
+        return out
+
+    def obs_ar_ex_backward(self, ctx: "KpCtx", ext: "KpObsExt", qpos_rows, wbpos, wbquat, grad_obs, grad_obj_2_head=None):
+        """obs_ar_backward for the wide row (kp_sim_obs_ar_ex_backward): -> (grad_qpos, grad_qvel or None, grad_hpos, grad_hquat, grad_ctx [R, ctx_dim] --
+        the context block's cotangent, None when ctx_dim is 0)."""
+        _dev("obs_ar_ex_backward: grad_obs", grad_obs, (None, None))
+        R, W = grad_obs.shape
+        ins = [_dev("obs_ar_ex_backward: " + k, t, (R, d)) for k, t, d in (("qpos_rows", qpos_rows, NQ), ("wbpos", wbpos, 72), ("wbquat", wbquat, 96), ("grad_obs", grad_obs, W),
+                                                                             ("grad_obj_2_head", grad_obj_2_head, 7))]
+        new = lambda d: torch.empty((R, d), dtype=torch.float32, device=self.device)      # noqa: E731
+        gq, gv, gp, gh, gc = new(NQ), (new(NV) if self.obs_ar_vel else None), new(3), new(4), (new(ext.ctx_dim) if ext.ctx_dim > 0 else None)
+        _check(self.L.kp_sim_obs_ar_ex_backward(self.h, C.byref(ctx), C.byref(ext), R, W, *ins,
+                                                *[None if o is None else C.c_void_p(o.data_ptr()) for o in (gq, gv, gp, gh, gc)]), "kp_sim_obs_ar_ex_backward")
+        return gq, gv, gp, gh, gc
 
     def term_reward(self, ctx: "KpCtx", cfg: "KpRewardCfg", reward=None, info=None, fail=None, diffs=None):
         reward = torch.empty(self.n, device=self.device) if reward is None else reward

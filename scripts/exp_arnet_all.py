@@ -54,29 +54,38 @@ def main():
     from kinpoly_amd.supervised import TorchFK
     if args.config_root:
         os.chdir(args.config_root)
-    cfg = Config(args.cfg, action=args.action, wild=args.wild, create_dirs=True)
+    cfg = Config(args.cfg, action=args.action, wild=args.wild, create_dirs=True, entry="kin_model")
     torch.cuda.set_device(args.gpu_index)
     device = torch.device("cuda", args.gpu_index)
     dtype = torch.float64 if args.dtype == "fp64" else torch.float32
     if args.dtype == "fp64" and args.path == "taped":
         ap.error("--path taped runs the fp32 kernels; --dtype fp64 stays on the torch path")
-    fused = args.dtype == "fp32" and (args.path or E.DEFAULT_PATH) == "taped"
     np.random.seed(cfg.seed); torch.manual_seed(cfg.seed)
-    net = E.build_net(cfg.use_vel, cfg.use_head, cfg.use_action, as_policy=args.as_policy).to(device)
-    kin_model = kpsim.KpModel(kpsim.STEP_KPM, **E.model_options(net))
+    mk = cfg.model_kwargs()
+    loss_weights = {k: mk.pop(k) for k in list(mk) if k.startswith("w_")}
+    kin_model = kpsim.KpModel(kpsim.STEP_KPM, **kpsim.ar_obs_options(cfg.use_vel, cfg.use_head, bool(cfg.use_action) and args.as_policy))
     fk_sim = kpsim.KpSim(kin_model, 1, args.gpu_index)
     y = cfg.yaml_data
     num_sample = int(y.get("num_sample", 20000)) if args.num_sample is None else args.num_sample
     batch_size = int(cfg.batch_size) if args.batch_size is None else args.batch_size
     feat = cfg.feature_path()
     data_mode = "train" if args.mode == "train" else "test"
+    of_path = cfg.feature_path(cfg.of_file)
     if os.path.exists(feat):
-        ds = D.StateARDataset(feat, takes=cfg.takes[args.data if args.data in ("train", "test") else data_mode] or None, data_mode=data_mode,
-                              fr_num=E.FR_NUM_START, wild=args.wild, seed=cfg.seed, device=device)
+        import joblib
+        takes, take_list = joblib.load(feat), cfg.takes[args.data if args.data in ("train", "test") else data_mode] or None
     else:
         std = np.load(os.path.join(ROOT, "tests", "golden", "standing_neutral.npz"))
         takes = D.synthetic_takes(fk_sim, std["qpos"], n_per_action=4, T_range=(E.FR_NUM_END + 10, E.FR_NUM_END + 60), body_mass=read_kpm(kpsim.STEP_KPM)["body_mass"], seed=4)
-        ds = D.StateARDataset(takes, data_mode=data_mode, fr_num=E.FR_NUM_START, wild=args.wild, seed=cfg.seed, device=device)
+        take_list = None
+    of = None
+    if cfg.use_of:      # the file's features (their width is the file's), or this repository's synthetic stand-in model_specs.cnn_fdim wide
+        of = of_path if os.path.exists(of_path) else D.synthetic_of_features(takes, int(cfg.model_specs.get("cnn_fdim", 512)), seed=cfg.seed)
+        print(f"of features: {of_path if isinstance(of, str) else 'synthetic stand-in (no ' + of_path + ')'}", flush=True)
+    ds = D.StateARDataset(takes, takes=take_list, data_mode=data_mode, fr_num=E.FR_NUM_START, wild=args.wild, seed=cfg.seed, device=device, of_features=of)
+    net = E.build_net(cfg.use_vel, cfg.use_head, cfg.use_action, as_policy=args.as_policy, use_context=bool(cfg.use_context), of_dim=ds.of_dim, **mk).to(device)
+    # the training path: --path, else the default measured for the file's kind (DESIGN.md section 10 holds both records)
+    fused = args.dtype == "fp32" and (args.path or (E.DEFAULT_PATH_CONTEXT if net.ctx_block else E.DEFAULT_PATH)) == "taped"
     print(f"dataset: {ds.get_len()} takes; net: state {net.state_dim}, context {net.context_dim}; {'taped HIP roll-out' if fused else 'torch path'} {args.dtype}", flush=True)
     if args.iter > 0:
         cp_path = os.path.join(cfg.model_dir, "iter_%04d.p" % args.iter)
@@ -97,7 +106,7 @@ def main():
         for i_epoch in range(args.iter, last):
             t0 = time.time()
             loss, comp, rate, fr_num = E.train_epoch(net, fk, ds, i_epoch, cfg.num_epoch, cfg.lr, cfg.weightdecay, num_sample, batch_size,
-                                                     noise_std=float(cfg.noise_std) if cfg.add_noise else 0.0, fused=fused)
+                                                     noise_std=float(cfg.noise_std) if cfg.add_noise else 0.0, fused=fused, weights=loss_weights)
             line = (f"epoch {i_epoch:4d}    time {time.time() - t0:.2f}   loss {loss:.4f} {np.round(np.array(comp) * 100, 4).tolist()} lr: {cfg.lr} "
                     f"sampling_rate: {rate:.3f}, fr_num: {fr_num}")
             print(line, flush=True); log.write(line + "\n"); log.flush()

@@ -6,7 +6,8 @@ seconds per epoch of update_init_supervised (x 500 in the reference) and of trai
 
 compares train_full_supervised on the torch path and on the taped HIP roll-out (fused=True) in ONE process, alternating: one warm-up epoch each, then
 three repeats of three epochs; prints each path's median and min .. max seconds per epoch.  The taped path counts as faster when its median is below
-the torch path's median by more than the torch path's own max - min.  --unfused_only: the torch path alone, same protocol; to time a commit that lacks this flag, copy this file into that checkout's tools/ and run it there."""
+the torch path's median by more than the torch path's own max - min.  --context: the same comparison at kin_only.yml's sizes -- the kinematic model
+with a context block and the synthetic 512-wide `of` features (rnn_hdim 256, state 357, kinpoly_amd.exp_arnet.build_net), 256 clips x 100 frames.  --unfused_only: the torch path alone, same protocol; to time a commit that lacks this flag, copy this file into that checkout's tools/ and run it there."""
 import os
 import sys
 import time
@@ -30,10 +31,29 @@ def _setup():
     return AgentAR(256, dataset=ds, device=0, horizon=4), ds
 
 
-def compare(paths, epochs=3, repeats=3):
+def _setup_context(of_dim=512):
+    """kin_only.yml: use_context + use_of, model_specs.rnn_hdim 256, cnn_fdim 512; the network of scripts/exp_arnet_all.py (as_policy=False: 357-d state)"""
+    from types import SimpleNamespace
+    from kinpoly_amd import dataset as D
+    from kinpoly_amd import exp_arnet as E
+    from kinpoly_amd import sim as kpsim
+    from kinpoly_amd.model_compiler import DEFAULT_KPM, read_kpm
+    from kinpoly_amd.supervised import TorchFK
+    std = np.load(os.path.join(ROOT, "tests", "golden", "standing_neutral.npz"))
+    net = E.build_net(use_context=True, of_dim=of_dim, rnn_hdim=256).cuda()
+    fk_sim = kpsim.KpSim(kpsim.KpModel(kpsim.STEP_KPM, **E.model_options(net)), 256, 0)
+    takes = D.synthetic_takes(fk_sim, std["qpos"], n_per_action=4, T_range=(110, 160), body_mass=read_kpm(kpsim.STEP_KPM)["body_mass"], seed=4)
+    ds = D.StateARDataset(takes, fr_num=100, seed=4, device=fk_sim.device, of_features=D.synthetic_of_features(takes, of_dim, seed=4))
+    kpm = read_kpm(DEFAULT_KPM)
+    fk = TorchFK(kpm["body_pos"], kpm["body_parent"], fk_sim.device, sim=fk_sim)
+    print(f"context model: state {net.state_dim}, context {net.context_dim}, rnn_hdim {net.rnn_hdim}, of {of_dim} (synthetic)", flush=True)
+    return SimpleNamespace(policy_net=net, opt_sup=torch.optim.Adam(net.parameters(), lr=1e-4), fk=fk), ds
+
+
+def compare(paths, epochs=3, repeats=3, context=False):
     """paths: names out of ("torch", "fused")"""
     from kinpoly_amd import pretrain as P
-    agent, ds = _setup()
+    agent, ds = _setup_context() if context else _setup()
     run = lambda name, n: P.train_full_supervised(agent.policy_net, agent.opt_sup, agent.fk, ds, n, 0.3, 2000, 256, noise_std=0.01,      # noqa: E731
                                                   rng=np.random.RandomState(0), **({"fused": True} if name == "fused" else {}))
     times = {p: [] for p in paths}
@@ -56,7 +76,7 @@ def compare(paths, epochs=3, repeats=3):
 
 def main():
     if "--fused" in sys.argv or "--unfused_only" in sys.argv:
-        return compare(("torch",) if "--unfused_only" in sys.argv else ("torch", "fused"))
+        return compare(("torch",) if "--unfused_only" in sys.argv else ("torch", "fused"), context="--context" in sys.argv)
     from kinpoly_amd import pretrain as P
     ep = int(sys.argv[1]) if len(sys.argv) > 1 else 3
     agent, ds = _setup()
