@@ -573,6 +573,22 @@ int kp_sim_obs_ar_ex_backward(kp_sim*, const kp_ctx* ctx, const kp_obs_ext* ext,
                               const float* wbquat, const float* grad_obs, const float* grad_obj_2_head, float* grad_qpos, float* grad_qvel,
                               float* grad_hpos, float* grad_hquat, float* grad_ctx);
 
+/* kp_rollout_record_pre_w / _post_w for the rows of an env whose observation carries a context / `of` block (kp_sim_obs_ar_ex): obs_dim = ctx_dim +
+ * base + of_dim with base one of the eight layout widths; anything else fails and nothing is launched.  The kernels are the ones above (the width is
+ * their argument). */
+int kp_rollout_record_pre_x(const kp_record_pre*, int obs_dim, int ctx_dim, int of_dim, void* hip_stream);
+int kp_rollout_record_post_x(const kp_record_post*, int obs_dim, int ctx_dim, int of_dim, void* hip_stream);
+
+/* The ring refill of the two wide context tables (the tables kp_obs_ext points to, row-major [R, T, .]), one launch: for clip c < m, frame t < T
+ *   ctx_table[rows[c], t, :ctx_dim] = seq[min(t, Tp - 1), c, :]     seq: time-major [Tp, m, ctx_dim], the context GRU's hidden states as its step writes them
+ *   of_table [rows[c], t, :of_dim]  = of [c, min(t, Tp - 1), :]     of:  [m, Tp, of_dim], the data set's image features
+ * (a clip shorter than the tables is padded with its last frame).  A table whose width is 0 is not written and its source not read.  rows: device
+ * int64 [m]; rows_host: the same values in host memory, checked here.  Refused with -1 before any launch: a row outside [0, R), Tp < 1 or Tp > T, a
+ * NULL table with a non-zero width, a table without its source, rows / sources / tables that are not device memory.  m == 0 returns 0 without a
+ * launch.  Duplicate rows are the caller's error: two clips would race for one row (the sampler's refill plan never names a row twice). */
+int kp_ctx_rows_write(int m, int R, int T, int Tp, int ctx_dim, int of_dim, const int64_t* rows, const int64_t* rows_host, const float* seq, const float* of,
+                      float* ctx_table, float* of_table, void* hip_stream);
+
 
 #ifdef __cplusplus
 }

@@ -42,7 +42,7 @@ class AgentAR:
                  cache_init_context=False, log_std=-3.2, policy_weightdecay=0.0, value_weightdecay=0.0, smooth=True, result_dir=None, eval_envs=None,
                  init_update=False, num_init_update=5, step_update_dyna=False, num_step_dyna_update=10, full_update=False, num_sample=20000, batch_size=128,
                  noise_std=0.0, cc_checkpoint=None, update_dtype=None, reference_bugs=True, min_batch_size=0, slice_ratio="slice_start", use_action=True,
-                 use_vel=False, use_head=True):
+                 use_vel=False, use_head=True, use_context=False, of_dim=0, rnn_hdim=1024, mlp_hsize=(1024, 512, 256)):
         """update_dtype: None = the update runs on the fp32 roll-out modules (fused HIP re-unroll); torch.float64 = the reference's training
         precision on fp64 master copies (kinpoly_amd/update.py).  reference_bugs: reproduce the reference's generator-consumed gradient clip
         (PPOTrainer) and LoggerRL.merge's max-of-mins; False = the corrected forms.
@@ -58,22 +58,37 @@ class AgentAR:
         use_action (kin_poly.yml: True): False is the no-action-label ablation (kin_poly_wo_action.yml): 101-d observations for the policy, the value net
         and the kinematic twin, a 13-d context GRU input; the reward, the resets and the clip sampling still read the action label.
         use_vel / use_head (a statear yml's keys; kin_poly.yml: False / True): the other observation variants -- the 75 velocities in the state, no
-        head-tracking blocks in the state and no head columns in the context GRU's input (widths: kinpoly_amd.sim.ar_obs_dim); same physics and reward."""
+        head-tracking blocks in the state and no head columns in the context GRU's input (widths: kinpoly_amd.sim.ar_obs_dim); same physics and reward.
+        use_context / of_dim (a statear yml's `use_context` / `use_of` with image features of_dim wide; Config(entry="policy_ctx").agent_kwargs()) and
+        rnn_hdim / mlp_hsize (its model_specs): the video-conditioned policy.  The observation, the policy's and the value net's input are
+        [context GRU state of the frame (rnn_hdim) | the row above | the frame's image feature (of_dim)]; the env keeps the two blocks of every ring row
+        resident (BatchedHumanoidAREnv(ctx_dim=, of_dim=): see there for the HBM that takes) and every drawn clip's context sequence is kept.  The data
+        set must carry the features (StateARDataset(of_features=...)) when of_dim > 0.  As in the reference (policy_ar.py:216-234) the recorded context
+        block is data to the PPO surrogate and the step loss: context_rnn is trained by init_update / full_update only."""
         rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
         enable_tuned_gemms()          # library GEMM solution per shape (rollout and update shapes at 4096 envs); selection only
         torch.manual_seed(seed + rank)
+        of_dim, rnn_hdim, mlp_hsize = int(of_dim), int(rnn_hdim), tuple(mlp_hsize)
+        ctx_block = rnn_hdim if (use_context or of_dim) else 0          # TrajARNet.ctx_block (the env is built first: the order of the parameter draws is kept)
+        if ctx_block and cache_init_context:
+            raise ValueError("cache_init_context memoises init_qpos / init_qvel only; a policy with a context block needs every drawn clip's context sequence")
+        if of_dim and dataset is not None and "of" not in dataset.data:
+            raise ValueError(f"use_of: the data set carries no image features (StateARDataset(of_features=...), {of_dim} wide)")
         self.env = BatchedHumanoidAREnv(n_envs, device, mode="train", wild=wild, seed=seed + rank, model_options=model_options,
-                                        joint_controller=joint_controller, use_action=use_action, use_vel=use_vel, use_head=use_head)
+                                        joint_controller=joint_controller, use_action=use_action, use_vel=use_vel, use_head=use_head, ctx_dim=ctx_block, of_dim=of_dim)
         self.device = self.env.device
         if cc_checkpoint is not None:      # the pre-trained UHC the env is built around (humanoid_ar_v1.py:60-81)
             self.env.load_uhc_checkpoint(cc_checkpoint, load_policy=not joint_controller)
-        self.policy_net = TrajARNet(log_std=log_std, use_action=self.env.use_action, use_vel=self.env.use_vel, use_head=self.env.use_head).to(self.device)
-        self.value_net = Value(MLP(self.env.obs_dim, (512, 256), "relu")).to(self.device)      # agent_ar.py:145-147: Value(MLP(policy_net.state_dim, ...))
+        self.policy_net = TrajARNet(rnn_hdim=rnn_hdim, mlp_hsize=mlp_hsize, log_std=log_std, use_action=self.env.use_action, use_vel=self.env.use_vel,
+                                    use_head=self.env.use_head, use_context=bool(use_context), of_dim=of_dim, of_in_state=bool(of_dim)).to(self.device)
+        assert self.policy_net.state_dim == self.env.obs_dim and self.policy_net.ctx_block == self.env.ctx_dim
+        self.value_net = Value(MLP(self.policy_net.state_dim, (512, 256), "relu")).to(self.device)      # agent_ar.py:145-147: Value(MLP(policy_net.state_dim, ...))
         self._sync_params()
         self.kin_sim = kpsim.KpSim(self.env.model, n_envs, self.device.index)      # physics-free twin for the kinematic roll-out
         # a training episode reads init_qpos / init_qvel of its context only: the whole-clip kinematic roll-out and the [N, T, 1024] context
         # feature sequence of init_context are not computed (PolicyARContext; evaluate.py builds its own with need_rollout=True)
-        self.ctx_builder = PolicyARContext(self.policy_net, self.kin_sim, smooth=smooth, need_rollout=False, keep_context_feat=False)
+        # a policy with a context block keeps the sequence: it is the first block of every observation of the episode
+        self.ctx_builder = PolicyARContext(self.policy_net, self.kin_sim, smooth=smooth, need_rollout=False, keep_context_feat=bool(ctx_block))
         # sampling_temp / sampling_freq: kin_poly.yml:67-68; freq_dict lives in the source (agent_ar.py:228-234)
         self.source = EpisodeSource(dataset=dataset, context_fn=context_fn if dataset is None else None,
                                     ctx_builder=self.ctx_builder if use_init_context else None,
@@ -234,14 +249,15 @@ class AgentAR:
             n = int(self.eval_envs or min(self.env.n, 256))
             env = BatchedHumanoidAREnv(n, self.device.index, mode="test", wild=wild, seed=0, cc_policy=self.env.cc_policy, cc_running_state=self.env.cc_running_state,
                                        model_options=getattr(self.env, "model_options", None), use_action=self.env.use_action, use_vel=self.env.use_vel,
-                                       use_head=self.env.use_head)
+                                       use_head=self.env.use_head, ctx_dim=self.env.ctx_dim, of_dim=self.env.of_dim)
             import copy
             gt_term = env.reward_cfg.use_gt_term                         # a property of the mode (test: no GT-diff termination), not of the configuration
             env.reward_cfg = copy.deepcopy(self.env.reward_cfg)          # thresholds AND the reward weights cfg.apply_reward_weights put on the training env
             env.reward_cfg.use_gt_term = gt_term
             if hasattr(self.env, "env_episode_len"):
                 env.env_episode_len = self.env.env_episode_len
-            builder = PolicyARContext(self.policy_net, kpsim.KpSim(env.model, n, self.device.index), smooth=self.ctx_builder.smooth, need_rollout=True, keep_context_feat=False)
+            builder = PolicyARContext(self.policy_net, kpsim.KpSim(env.model, n, self.device.index), smooth=self.ctx_builder.smooth, need_rollout=True,
+                                      keep_context_feat=bool(self.env.ctx_dim))
             self._eval[wild] = (env, builder)
         return self._eval[wild]
 
@@ -284,7 +300,14 @@ class AgentAR:
         return ck.save_checkpoint(path, self.policy_net, self.value_net, None, self.env.cc_policy)
 
     def load_checkpoint(self, path):
+        """A checkpoint in the reference's layout; or the supervised kinematic model's own (scripts/exp_arnet_all.py --as_policy: `models/iter_%04d.p` =
+        ({'stateAR_net_dict': ...}, {})), which replaces the policy and leaves the value net as it is.  Shapes that do not fit are refused by name."""
         cp = ck.load_checkpoint(path)
+        if isinstance(cp, tuple) and cp and isinstance(cp[0], dict) and "stateAR_net_dict" in cp[0]:
+            ck.load_state_strict(self.policy_net, dict(cp[0]["stateAR_net_dict"]), allow_missing=frozenset({"action_log_std"}), what=str(path))
+            self.upd.load_from_rollout()
+            self.restart_sampler()
+            return cp
         ck.load_state_strict(self.policy_net, ck.split_policy_dict(cp["policy_dict"]), what=str(path))      # missing / unknown keys raise (allow-list: checkpoint.py)
         self.value_net.load_state_dict(cp["value_dict"])
         self.upd.load_from_rollout()

@@ -153,9 +153,19 @@ def check_policy_obs_dim(state: dict, obs_dim: int, what="checkpoint"):
                                    "(train and evaluate with the config the checkpoint was trained with)")
 
 
+def check_state_shapes(state: dict, module: torch.nn.Module, what="checkpoint"):
+    """Raise CheckpointWidthError, naming the tensor and both shapes, when a tensor of `state` has another shape than the module's of that name: the
+    net sizes of another config (model_specs.rnn_hdim / mlp_hsize, the width of a context or `of` block)."""
+    shapes = module.state_dict()
+    for k in sorted(set(shapes) & set(state)):
+        if tuple(state[k].shape) != tuple(shapes[k].shape):
+            raise CheckpointWidthError(f"{what}: {k} is {tuple(state[k].shape)} in the checkpoint and {tuple(shapes[k].shape)} in the network it is loaded into "
+                                       "(train and evaluate with the config the checkpoint was trained with)")
+
+
 def load_state_strict(module: torch.nn.Module, state: dict, allow_missing=ALLOWED_MISSING_POLICY_KEYS, what="checkpoint"):
     """load_state_dict that names what does not fit: keys missing from `state` (beyond `allow_missing`) or not known to `module` raise; a kinematic
-    policy of another observation width raises CheckpointWidthError."""
+    policy of another observation width, or any tensor of another shape, raises CheckpointWidthError with both shapes."""
     state = {k: (v if torch.is_tensor(v) else torch.as_tensor(v)) for k, v in state.items()}
     if hasattr(module, "state_dim"):
         check_policy_obs_dim(state, module.state_dim, what)
@@ -164,6 +174,7 @@ def load_state_strict(module: torch.nn.Module, state: dict, allow_missing=ALLOWE
     unexpected = sorted(set(state) - own)
     if missing or unexpected:
         raise KeyError(f"{what}: does not match {type(module).__name__} -- missing {missing[:8]}{' ...' if len(missing) > 8 else ''}, unexpected {unexpected[:8]}{' ...' if len(unexpected) > 8 else ''}")
+    check_state_shapes(state, module, what)
     module.load_state_dict(state, strict=False)          # strict=False only for the allow-listed keys, checked above
     return module
 

@@ -12,7 +12,9 @@ velocities in the observation) and `use_head` (false: no head-tracking blocks) m
 `mujoco_model` (the compiled blobs of kinpoly_amd/assets are humanoid_smpl_neutral_mesh_all[_step].xml, agent_ar.py:165-169), `model_specs`
 of another architecture than TrajARNet's (checked: a mismatch raises), `policy_optimizer` other than Adam (checked), `obs_*` switches other than the
 kin_poly.yml values (checked).  `use_of` / `use_context` (kin_only.yml, use_of.yml) are refused by the default entry and taken by
-`Config(..., entry="kin_model")`, the supervised kinematic model of scripts/exp_arnet_all.py, with the file's net sizes (`model_kwargs()`).  Nothing here needs a GPU.
+`Config(..., entry="kin_model")`, the supervised kinematic model of scripts/exp_arnet_all.py, with the file's net sizes (`model_kwargs()`), and by
+`Config(..., entry="policy_ctx")`, the roll-out / PPO scripts with the video-conditioned policy (every other check of the default entry holds there:
+`policy_v: 2` and `reward_id: dynamic_supervision_v3`, which kin_only.yml and use_of.yml declare, stay refused by name).  Nothing here needs a GPU.
 """
 from __future__ import annotations
 
@@ -32,6 +34,10 @@ _FIXED_POLICY = {"policy_v": 1, "fix_std": True, "policy_htype": "relu", "policy
                  "policy_optimizer": "Adam", "value_optimizer": "Adam", "reward_id": "dynamic_supervision_v1", "end_reward": False}
 # what Config(entry="kin_model") takes from the file instead: the supervised kinematic model runs with a context / `of` block and any net sizes
 _KIN_MODEL_FREE = ("use_of", "use_context", "rnn_hdim", "mlp_hsize", "cnn_fdim")
+ENTRIES = ("policy", "kin_model", "policy_ctx")
+# why a policy entry refuses them (the error text and INTEGRATION.md say it): in the reference that path cannot run
+_REFUSED_WHY = {"policy_v": "policy_v 2: PolicyAR.step_lr reads a scheduler that only policy_v == 1 creates, policy_ar.py:33-37, 88-89",
+                "reward_id": "dynamic_supervision_v3 reads env.cc_cfg.policy_specs, which the UHC config does not have, reward_function.py:1055-1056"}
 
 
 class ConfigError(ValueError):
@@ -43,9 +49,10 @@ class Config:
                  entry: str = "policy"):
         """entry: "policy" (the rollout / PPO scripts: every check below) or "kin_model" (scripts/exp_arnet_all.py, the supervised kinematic model: `use_of`
         / `use_context` may be true and model_specs' rnn_hdim / mlp_hsize / cnn_fdim are the file's -- config/statear/kin_only.yml, use_of.yml; the reference's
-        exp_arnet_all.py never reads policy_specs, so they are not checked)."""
-        if entry not in ("policy", "kin_model"):
-            raise ConfigError(f"Config: entry must be 'policy' or 'kin_model', got {entry!r}")
+        exp_arnet_all.py never reads policy_specs, so they are not checked) or "policy_ctx" (scripts/train_ar_policy.py, eval_ar_policy.py: "policy" in every
+        check, except that `use_of` / `use_context` may be true and the three net sizes are the file's, as under "kin_model")."""
+        if entry not in ENTRIES:
+            raise ConfigError(f"Config: entry must be 'policy', 'kin_model' or 'policy_ctx', got {entry!r}")
         self.entry = entry
         if os.path.isfile(cfg_id):
             path, cfg_id = cfg_id, os.path.splitext(os.path.basename(cfg_id))[0]
@@ -91,29 +98,34 @@ class Config:
         self.reward_weights = dict(self.policy_specs.get("reward_weights", {}))
         self.use_action = y.get("use_action", True)          # statear_smpl_config.py:141
         self.use_vel, self.use_head = y.get("use_vel", False), y.get("use_head", True)      # :139-140
-        self.use_of, self.use_context = y.get("use_of", True), y.get("use_context", True)  # :137-138 (refused unless entry == "kin_model")
+        self.use_of, self.use_context = y.get("use_of", True), y.get("use_context", True)  # :137-138 (refused by the default entry)
         self._check_supported()
 
     def _check_supported(self):
         y = self.yaml_data
         kin = self.entry == "kin_model"
+        free = self.entry in ("kin_model", "policy_ctx")          # the context / `of` block and the file's net sizes
         bad = [f"{k}: {y.get(k, ref)!r} (the HIP observation / step kernels implement {v!r})" for k, (v, ref) in _FIXED.items()
-               if y.get(k, ref) != v and not (kin and k in _KIN_MODEL_FREE)]
-        for k in ("use_action", "use_vel", "use_head") + (("use_of", "use_context") if kin else ()):
+               if y.get(k, ref) != v and not (free and k in _KIN_MODEL_FREE)]
+        for k in ("use_action", "use_vel", "use_head") + (("use_of", "use_context") if free else ()):
             if not isinstance(getattr(self, k), bool):
                 bad.append(f"{k}: {getattr(self, k)!r} (true or false)")
         if self.use_head is False and self.use_action is False:
             bad.append("use_head: False with use_action: False (the context GRU would have no input: get_context_dim is 0)")
         bad += [f"model_specs.{k}: {self.model_specs[k]!r} (TrajARNet here is {v!r})" for k, v in _FIXED_MODEL.items()
-                if k in self.model_specs and self.model_specs[k] != v and not (kin and k in _KIN_MODEL_FREE)]
-        if kin:
+                if k in self.model_specs and self.model_specs[k] != v and not (free and k in _KIN_MODEL_FREE)]
+        if free:
             hs = self.model_specs.get("mlp_hsize", [1024, 512, 256])
             if not (isinstance(self.model_specs.get("rnn_hdim", 1024), int) and self.model_specs.get("rnn_hdim", 1024) > 0):
                 bad.append(f"model_specs.rnn_hdim: {self.model_specs.get('rnn_hdim')!r} (a positive integer)")
             if not (isinstance(hs, list) and hs and all(isinstance(h, int) and h > 0 for h in hs)):
                 bad.append(f"model_specs.mlp_hsize: {hs!r} (a list of positive integers)")
-        else:
-            bad += [f"policy_specs.{k}: {self.policy_specs[k]!r} (implemented: {v!r})" for k, v in _FIXED_POLICY.items() if k in self.policy_specs and self.policy_specs[k] != v]
+            cf = self.model_specs.get("cnn_fdim", 128)
+            if not (isinstance(cf, int) and not isinstance(cf, bool) and cf > 0):
+                bad.append(f"model_specs.cnn_fdim: {cf!r} (a positive integer)")
+        if not kin:
+            bad += [f"policy_specs.{k}: {self.policy_specs[k]!r} (implemented: {v!r}" + (f"; {_REFUSED_WHY[k]}" if k in _REFUSED_WHY else "") + ")"
+                    for k, v in _FIXED_POLICY.items() if k in self.policy_specs and self.policy_specs[k] != v]
         if bad:
             raise ConfigError(f"{self.path}: not supported by the batched engine -- " + "; ".join(bad))
 
@@ -129,8 +141,23 @@ class Config:
         w = {k: float(ms.get(k, d)) for k, d in (("w_rp", 50), ("w_rr", 50), ("w_p", 1), ("w_v", 1), ("w_ee", 1), ("w_op", 1), ("w_or", 1))}
         return dict(rnn_hdim=int(ms.get("rnn_hdim", 512)), mlp_hsize=tuple(ms.get("mlp_hsize", [1024, 512])), **w)
 
-    def agent_kwargs(self) -> dict:
-        """AgentAR(...) keyword arguments for this file (agent_ar.py:60-99, 184-225: the optimisers, schedules, PPO and sampling constants)."""
+    def of_feature_path(self) -> str:
+        """<dataset_path>/features/<of_file>.p: the image features of `use_of` (of_file / of_file_wild; statear_smpl_dataset.py:40-41)"""
+        return os.path.join(self.data_dir, "features", self.of_file + ".p")
+
+    def context_kwargs(self, of_dim: int | None = None) -> dict:
+        """The video-conditioned part of AgentAR's arguments under entry "policy_ctx": use_context, of_dim (the feature file's width when the caller
+        has read it, else model_specs.cnn_fdim) and the net sizes the file names, read through model_kwargs(); a size the file omits stays the
+        engine's (AgentAR's default, what the default entry has always run such a file with).  Empty under another entry."""
+        if self.entry != "policy_ctx":
+            return {}
+        mk = self.model_kwargs()
+        of = (int(of_dim) if of_dim is not None else int(self.model_specs.get("cnn_fdim", 128))) if self.use_of else 0
+        return dict(use_context=bool(self.use_context), of_dim=of, **{k: mk[k] for k in ("rnn_hdim", "mlp_hsize") if k in self.model_specs})
+
+    def agent_kwargs(self, of_dim: int | None = None) -> dict:
+        """AgentAR(...) keyword arguments for this file (agent_ar.py:60-99, 184-225: the optimisers, schedules, PPO and sampling constants); under entry
+        "policy_ctx" also context_kwargs(of_dim)."""
         ps = self.policy_specs
         missing = [k for k in ("num_optim_epoch", "gamma", "tau", "clip_epsilon", "policy_lr", "value_lr", "log_std") if k not in ps]     # indexed without a default (:88-91, 190, 204)
         if missing:
@@ -144,7 +171,8 @@ class Config:
                     smooth=bool(self.smooth), init_update=ps.get("init_update", False), num_init_update=int(ps.get("num_init_update", 5)),
                     step_update_dyna=ps.get("step_update_dyna", False), num_step_dyna_update=int(ps.get("num_step_dyna_update", 10)), full_update=ps.get("full_update", False),
                     num_sample=int(self.yaml_data.get("num_sample", 20000)), batch_size=int(self.batch_size),
-                    noise_std=float(self.noise_std) if self.add_noise else 0.0, use_action=self.use_action, use_vel=self.use_vel, use_head=self.use_head)
+                    noise_std=float(self.noise_std) if self.add_noise else 0.0, use_action=self.use_action, use_vel=self.use_vel, use_head=self.use_head,
+                    **self.context_kwargs(of_dim))
 
     def horizon(self, n_envs: int, world_size: int = 1, floor: int = 1) -> int:
         """Steps per env and iteration so that the job collects at least `min_batch_size` samples (agent_ar.py:277: `self.sample(min_batch_size)`;

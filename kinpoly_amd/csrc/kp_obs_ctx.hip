@@ -156,6 +156,26 @@ __global__ void k_obs_ctx_grad(int n, int H, const float* __restrict__ g_obs, in
     g_ctx[idx] = g_obs[e * (size_t)pitch + (idx - e * H)];
 }
 
+// ---------------------------------------------------------------- ring refill of the wide context tables: block = (clip, frame), lanes along the features
+__global__ __launch_bounds__(256) void k_ctx_rows_write(CtxRowsArgs A) {
+    const int c = blockIdx.x / A.T, t = blockIdx.x - c * A.T;
+    if (c >= A.m) return;
+    const long long r = A.rows[c];
+    if (r < 0 || r >= (long long)A.R) return;                       // refused by the entry point; never written through
+    const int ts = t < A.Tp ? t : A.Tp - 1;                        // last-frame padding of a clip shorter than the tables
+    const size_t dst = (size_t)r * A.T + t;
+    if (A.ctx_table) {
+        const float* __restrict__ s = A.seq + ((size_t)ts * A.m + c) * A.H;
+        float* __restrict__ d = A.ctx_table + dst * A.H;
+        for (int j = threadIdx.x; j < A.H; j += 256) d[j] = s[j];
+    }
+    if (A.of_table) {
+        const float* __restrict__ s = A.of + ((size_t)c * A.Tp + ts) * A.F;
+        float* __restrict__ d = A.of_table + dst * A.F;
+        for (int j = threadIdx.x; j < A.F; j += 256) d[j] = s[j];
+    }
+}
+
 hipError_t launch_obs_ar_ctx(const ObsArCtxArgs& A, hipStream_t stream) {
     const dim3 grid((A.n + 7) / 8), block(256);
     CtxLike C;
@@ -187,6 +207,11 @@ hipError_t launch_gru_cell_step_wide(int n, int H, int D, const float* gi, const
 hipError_t launch_obs_ctx_grad(int n, int H, const float* grad_obs, int pitch, float* grad_ctx, hipStream_t stream) {
     const size_t tot = (size_t)n * H;
     hipLaunchKernelGGL(k_obs_ctx_grad, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, n, H, grad_obs, pitch, grad_ctx);
+    return hipGetLastError();
+}
+
+hipError_t launch_ctx_rows_write(const CtxRowsArgs& A, hipStream_t stream) {
+    hipLaunchKernelGGL(k_ctx_rows_write, dim3((unsigned)((size_t)A.m * A.T)), dim3(256), 0, stream, A);
     return hipGetLastError();
 }
 

@@ -6,6 +6,11 @@
 //                        frame's image feature.  A null context table writes zeros (the reference's row before init_states)
 //   k_gru_cell_step_wide k_gru_cell_step (kp_policy_kernels.hpp) whose [state | h'] copy covers D > H columns; gate math and h' are that kernel's
 //   k_obs_ctx_grad       the context block's cotangent: the first H columns of grad_obs as a contiguous [n, H] slab (the `of` block is data)
+//   k_ctx_rows_write     the sampler's ring refill of the two wide context tables (kp_ctx_rows_write): m drawn clips' context sequence (time-major
+//                        [T', m, H], what the GRU step writes) and image features ([m, T', F]) into row-major tables [R, T, .] at scattered rows, clips
+//                        shorter than T padded with their last frame.  A pure copy: one block per (clip, frame), lanes along the feature axis,
+//                        plain dwords (H and F need not be multiples of 4).  Duplicate rows are the caller's error (two clips would race for one
+//                        row; ring_refill_plan never produces them); a row outside [0, R) is refused by the entry point and skipped by the kernel
 //
 // fp32, rows independent, no LDS, no cross-lane traffic, no atomics.  The kernels live in their own translation unit (kp_obs_ctx.hip) for the reason
 // kp_pose_contacts.hpp gives: the step kernels' code generation must not move.
@@ -33,5 +38,15 @@ hipError_t launch_gru_cell_step_wide(int n, int H, int D, const float* gi, const
                                      float* h_out, float* xcat, hipStream_t stream);
 // grad_ctx [n, H] <- grad_obs[:, :H] of rows `pitch` floats apart
 hipError_t launch_obs_ctx_grad(int n, int H, const float* grad_obs, int pitch, float* grad_ctx, hipStream_t stream);
+
+// ctx_table[rows[c], t, :] <- seq[min(t, Tp - 1), c, :], of_table[rows[c], t, :] <- of[c, min(t, Tp - 1), :] for c < m, t < T; either table may be null
+// (its source is then not read).  rows: device int64 [m], every one in [0, R).  m >= 1, 1 <= Tp <= T, m * T < 2^31.
+struct CtxRowsArgs {
+    int m, R, T, Tp, H, F;
+    const long long* rows;
+    const float *seq, *of;
+    float *ctx_table, *of_table;
+};
+hipError_t launch_ctx_rows_write(const CtxRowsArgs& A, hipStream_t stream);
 
 }  // namespace kp

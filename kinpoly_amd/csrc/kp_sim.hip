@@ -1529,6 +1529,68 @@ int kp_sim_obs_ar_ex_backward(kp_sim* s, const kp_ctx* c, const kp_obs_ext* x, i
     return 0;
 }
 
+
+// ---- the sampler's records at a row with a context / `of` block: the same kernels (the width is their argument), obs_dim = ctx_dim + base + of_dim
+static int check_wide_width(const char* who, int obs_dim, int ctx_dim, int of_dim) {
+    if (ctx_dim < 0 || of_dim < 0 || !ar_obs_width_known(obs_dim - ctx_dim - of_dim))
+        return fail(std::string(who) + ": obs_dim must be ctx_dim + one of " KP_AR_OBS_WIDTHS " + of_dim, got " + std::to_string(obs_dim) + " with ctx_dim " +
+                    std::to_string(ctx_dim) + ", of_dim " + std::to_string(of_dim));
+    return 0;
+}
+
+int kp_rollout_record_pre_x(const kp_record_pre* r, int obs_dim, int ctx_dim, int of_dim, void* stream) {
+    if (!r || r->n <= 0 || r->T <= 0 || r->t < 0 || r->t >= r->T) return fail("kp_rollout_record_pre_x: bad arguments");
+    if (check_wide_width("kp_rollout_record_pre_x", obs_dim, ctx_dim, of_dim)) return -1;
+    if ((r->states && !r->obs) || (r->episode_start && !r->fresh) || (r->curr_qpos && !r->qpos) || (r->meta && !r->row_meta) ||
+        (r->gt_target_qpos && (!r->ctx_qpos || !r->cur_t || !r->row_len || r->ctx_T <= 0)))
+        return fail("kp_rollout_record_pre_x: a destination without its source");
+    kp::RecordPre R{r->n, r->T, r->t, r->ctx_T, obs_dim, r->obs, r->fresh, r->qpos, r->ctx_qpos, r->row, r->cur_t, r->row_len, r->row_meta,
+                    r->states, r->episode_start, r->curr_qpos, r->gt_target_qpos, r->meta};
+    hipLaunchKernelGGL(kp::k_record_pre, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
+    return launched();
+}
+
+int kp_rollout_record_post_x(const kp_record_post* r, int obs_dim, int ctx_dim, int of_dim, void* stream) {
+    if (!r || r->n <= 0 || r->T <= 0 || r->t < 0 || r->t >= r->T) return fail("kp_rollout_record_post_x: bad arguments");
+    if (check_wide_width("kp_rollout_record_post_x", obs_dim, ctx_dim, of_dim)) return -1;
+    if ((r->actions && !r->action) || (r->rewards && !r->reward) || (r->fails && !r->fail) || (r->dones && !r->done) || (r->percents && !r->percent) ||
+        (r->c_infos && !r->c_info) || (r->next_states && !r->obs) || (r->res_qpos && !r->qpos) || (r->cc_actions && !r->cc_action) ||
+        (r->cc_states && !r->cc_state) || (r->v_metas && !r->meta))
+        return fail("kp_rollout_record_post_x: a destination without its source");
+    kp::RecordPost R{r->n, r->T, r->t, obs_dim, r->fr_num, r->action, r->reward, r->fail, r->done, r->percent, r->c_info, r->obs, r->qpos, r->cc_action, r->cc_state, r->meta,
+                     r->actions, r->rewards, r->fails, r->dones, r->percents, r->c_infos, r->next_states, r->res_qpos, r->cc_actions, r->cc_states, r->v_metas};
+    hipLaunchKernelGGL(kp::k_record_post, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
+    return launched();
+}
+
+// ---- the ring refill of the wide context tables (k_ctx_rows_write, kp_obs_ctx.hip)
+static bool on_device(const void* p) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }      // plain host memory: not registered with the runtime
+    return at.type == hipMemoryTypeDevice;
+}
+
+int kp_ctx_rows_write(int m, int R, int T, int Tp, int ctx_dim, int of_dim, const int64_t* rows, const int64_t* rows_host, const float* seq, const float* of,
+                      float* ctx_table, float* of_table, void* stream) {
+    const std::string w("kp_ctx_rows_write: ");
+    if (m < 0 || R < 1 || T < 1 || ctx_dim < 0 || of_dim < 0) return fail(w + "bad sizes");
+    if (Tp < 1 || Tp > T) return fail(w + "clips of " + std::to_string(Tp) + " frames do not fit tables of " + std::to_string(T) + " (1 <= T' <= T)");
+    if (ctx_dim > 0 && !ctx_table) return fail(w + "ctx_dim " + std::to_string(ctx_dim) + " with a null context table");
+    if (of_dim > 0 && !of_table) return fail(w + "of_dim " + std::to_string(of_dim) + " with a null `of` table");
+    if (ctx_dim == 0) ctx_table = nullptr;
+    if (of_dim == 0) of_table = nullptr;
+    if (m == 0 || (!ctx_table && !of_table)) return 0;
+    if (!rows || !rows_host) return fail(w + "null rows (the device array and its host copy)");
+    if ((ctx_table && !seq) || (of_table && !of)) return fail(w + "a table without its source");
+    if ((long long)m * T > INT_MAX) return fail(w + "m * T exceeds 2^31 - 1 blocks");
+    for (int c = 0; c < m; c++)
+        if (rows_host[c] < 0 || rows_host[c] >= R) return fail(w + "row " + std::to_string((long long)rows_host[c]) + " of clip " + std::to_string(c) + " is outside [0, " + std::to_string(R) + ")");
+    for (const void* p : {(const void*)rows, (const void*)(ctx_table ? seq : nullptr), (const void*)(of_table ? of : nullptr), (const void*)ctx_table, (const void*)of_table})
+        if (p && !on_device(p)) return fail(w + "rows, sources and tables must be device memory (a host pointer was given)");
+    HIP_OK(kp::launch_ctx_rows_write(kp::CtxRowsArgs{m, R, T, Tp, ctx_dim, of_dim, (const long long*)rows, seq, of, ctx_table, of_table}, (hipStream_t)stream));
+    return 0;
+}
+
 }  // extern "C"
 
 // ---- model compiler behind the ABI (host only).  Included last: its `#pragma clang fp contract(off)` (bit-reproducible double arithmetic,

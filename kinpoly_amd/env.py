@@ -44,11 +44,18 @@ class BatchedHumanoidAREnv:
     def __init__(self, n_envs, device=0, kpm_path=None, cc_policy: PolicyMCP | None = None,
                  cc_running_state: RunningState | None = None, mode="train", wild=False, joint_controller=False,
                  env_episode_len=100000, body_diff_thresh=10.0, body_diff_gt_thresh=12.0, model_options=None, seed=0, ar_mode=False, use_action=True,
-                 use_vel=False, use_head=True):
+                 use_vel=False, use_head=True, ctx_dim=0, of_dim=0):
         """use_action (kin_poly.yml: true): the observation ends with the clip's action one-hot (105 floats); false (kin_poly_wo_action.yml): the first
         101 of them (humanoid_ar_v1.py:200-201), from a model with the option ar_obs_action = 0 -- every other quantity still reads the one-hot.
         use_vel: the simulated humanoid's 75 velocities follow the pose block (:184-185, option ar_obs_vel = 1); use_head false: no head-tracking blocks
-        (:157-169, 187-198, option ar_obs_head = 0).  obs_dim is the handle's width (kpsim.ar_obs_dim); the physics, the reward and the resets do not change."""
+        (:157-169, 187-198, option ar_obs_head = 0).  obs_dim is the handle's width (kpsim.ar_obs_dim); the physics, the reward and the resets do not change.
+        ctx_dim / of_dim (`use_context` / `use_of`, get_ar_obs_v1 :151-155, 203-205): the observation is [ar_context['context_feat_rnn'][t] (ctx_dim) | the
+        handle's row | ar_context['of'][t] (of_dim)], obs_dim = ctx_dim + sim.obs_ar_dim + of_dim, written by one kp_sim_obs_ar_ex launch from two more
+        context tables (alloc_context).  Both 0: the same buffers and the same kp_sim_obs_ar calls as before.
+
+        What the wide tables cost: a context row grows by T (ctx_dim + of_dim) 4 B.  A sampler's ring holds 2 pool_depth + 1 = 9 rows per env at the default
+        pool_depth of 4; at fr_num 100, ctx_dim 256 and of_dim 512 a row adds 307 KB, 11.3 GB for 4096 envs (arithmetic; DESIGN section 8 has what was
+        measured), next to the 0.11 MB per row of the base tables."""
         self.n = int(n_envs)
         self.ar_mode = bool(ar_mode)
         if kpm_path is None:  # agent_ar.py:165-169: mocap training uses ..._all_step.xml, --wild uses ..._all.xml
@@ -78,7 +85,12 @@ class BatchedHumanoidAREnv:
         self._row_obj_qpos = None  # [R,35] = convert_obj_qpos(action_one_hot, obj_pose[0]) of every context row
         self._ctx_struct = None
         self.end_reward = 0.0
-        self.action_dim, self.obs_dim, self.cc_action_dim = 80, self.sim.obs_ar_dim, kpsim.CC_ACTION_DIM
+        self.ctx_dim, self.of_dim = int(ctx_dim), int(of_dim)
+        if self.ctx_dim < 0 or self.of_dim < 0:
+            raise ValueError(f"ctx_dim / of_dim must be >= 0, got {ctx_dim} / {of_dim}")
+        self.wide = bool(self.ctx_dim or self.of_dim)      # the observation carries a context / `of` block
+        self._ext = None                                   # kp_obs_ext over the two wide tables (_bind_context)
+        self.action_dim, self.obs_dim, self.cc_action_dim = 80, self.ctx_dim + self.sim.obs_ar_dim + self.of_dim, kpsim.CC_ACTION_DIM
         # persistent I/O buffers (no per-step allocation)
         f = lambda d: torch.empty((self.n, d), dtype=torch.float32, device=self.device)  # noqa: E731
         self._next_qpos, self._cc_obs, self._obs, self._obs_next = f(76), f(784), f(self.obs_dim), f(self.obs_dim)
@@ -103,7 +115,8 @@ class BatchedHumanoidAREnv:
         """Empty context tables [R, T, .] (R a multiple of n_envs) that `write_context_rows` fills in place: what a sampler that keeps the next
         episodes' clips resident allocates once (VectorSampler's ring of pool_depth + 1 rows per env).  objects: the clips carry action objects
         (the per-row object block of reset_model is kept next to them); with_ar: room for the kinematic roll-out (ar_qpos / ar_qvel: ar_mode,
-        ar_fail_safe, evaluation)."""
+        ar_fail_safe, evaluation).  An env with a context / `of` block also gets the row-major tables context_feat_rnn [R, T, ctx_dim] and
+        of [R, T, of_dim] (see the constructor for what they cost)."""
         if R % self.n != 0:
             raise ValueError(f"context rows ({R}) must be a multiple of n_envs ({self.n})")
         dev = self.device
@@ -114,6 +127,10 @@ class BatchedHumanoidAREnv:
             self.ctx["obj_pose"] = z(R, T, obj_width)
         if with_ar or self.ar_mode:
             self.ctx["ar_qpos"], self.ctx["ar_qvel"] = z(R, T, 76), z(R, T, 75)
+        if self.ctx_dim:
+            self.ctx["context_feat_rnn"] = z(R, T, self.ctx_dim)
+        if self.of_dim:
+            self.ctx["of"] = z(R, T, self.of_dim)
         self.row_len = torch.full((R,), T - 1, dtype=torch.int32, device=dev)
         self.row_meta = z(R, 2)
         self.row = torch.arange(self.n, device=dev, dtype=torch.int32)
@@ -133,16 +150,45 @@ class BatchedHumanoidAREnv:
         T = c["qpos"].shape[1]
         self._ctx_struct = self.sim.make_ctx(T, c["head_pose"], c["head_vels"], c["obj_head_relative_poses"], c["action_one_hot"],
                                              c["gt_bquat"], c["gt_wbpos"], self.cur_t, obj_qpos=self.obj7, row=self.row)
+        if self.wide:
+            self._ext = self.sim.make_obs_ext(T, c["qpos"].shape[0], self.ctx_dim, c.get("context_feat_rnn"), c.get("of"), ctx_time_major=False)
         # rows a reset starts from (reset_model, humanoid_ar_v1.py:339-341): the kinematic roll-out's first frame in ar_mode, else init_qpos / init_qvel
         if self.ar_mode:
             self._init_q, self._init_v = c["ar_qpos"][:, 0].contiguous(), c["ar_qvel"][:, 0].contiguous()
         else:
             self._init_q, self._init_v = c["init_qpos"], c["init_qvel"]
 
+    def _obs_ar(self, out):
+        """get_ar_obs_v1 of every env into `out`: the handle's row, or the wide row when the env has a context / `of` block"""
+        if self.wide:
+            return self.sim.obs_ar_ex(self._ctx_struct, self._ext, out)
+        return self.sim.obs_ar(self._ctx_struct, out)
+
+    def _wide_sources(self, data, m=None, frames=None, build=True):
+        """(seq [T', m, ctx_dim] time-major or None, of [m, T', of_dim] or None) of a context for an env with wide tables (build=False: the checks
+        only).  A missing key is refused: the reference's zero block, np.zeros(256), exists only before init_context and is not built here."""
+        out = []
+        for key, dim, hint in (("context_feat_rnn", self.ctx_dim, "PolicyARContext(keep_context_feat=True).init_context"), ("of", self.of_dim, "StateARDataset(of_features=...)")):
+            if not dim:
+                out.append(None)
+                continue
+            if key not in data:
+                raise ValueError(f"this env's observation carries a {dim}-d data['{key}'] block and the context has no '{key}' ([m, T', {dim}]: {hint})")
+            v = data[key]
+            if v.dim() != 3 or v.shape[2] != dim or (m is not None and v.shape[0] != m) or (frames is not None and v.shape[1] != frames):
+                raise ValueError(f"data['{key}'] must be [{'m' if m is None else m}, {'T' if frames is None else frames}, {dim}], got {tuple(v.shape)}")
+            if build:
+                v = v.to(self.device, torch.float32)
+                # time-major for the sequence: no copy for init_context's env-major view of context_sequence's storage
+                v = v.transpose(0, 1).contiguous() if key == "context_feat_rnn" else v.contiguous()
+            out.append(v)
+        return out
+
     def write_context_rows(self, rows: torch.Tensor, data: dict):
         """Overwrite the context rows `rows` (int64 [m]) in place with m freshly drawn clips: data[k] is [m, T', .] with T' <= the tables' T (shorter
         clips are padded with their last frame, as StateARDataset.batch pads), action_one_hot [m, T', 4] or [m, 4], init_qpos / init_qvel [m, .],
-        optional len [m], take_ind / fr_start [m], obj_pose, ar_qpos / ar_qvel.  The GT clip's FK (load_context's gt_targets, humanoid_ar_v1.py:87)
+        optional len [m], take_ind / fr_start [m], obj_pose, ar_qpos / ar_qvel; context_feat_rnn [m, T', ctx_dim] / of [m, T', of_dim] for an env with a
+        context / `of` block (one kp_ctx_rows_write launch for the two: no [m, T, .] temporaries; `rows` must then name no row twice).  The GT clip's FK (load_context's gt_targets, humanoid_ar_v1.py:87)
         is computed for those rows only.  Envs that are playing one of these rows must be reset afterwards."""
         c, dev = self.ctx, self.device
         rows = rows.to(dev, torch.int64)
@@ -157,12 +203,16 @@ class BatchedHumanoidAREnv:
             return v
         if data["qpos"].shape[1] > T:
             raise ValueError(f"clips of {data['qpos'].shape[1]} frames do not fit context tables of {T}")
+        if self.wide:               # refused before anything is written
+            seq, of = self._wide_sources(data, m, data["qpos"].shape[1])
         one_hot = data["action_one_hot"].to(dev, torch.float32)
         if one_hot.dim() == 3:
             one_hot = one_hot[:, 0]
         for k in ("qpos", "head_pose", "head_vels", "obj_head_relative_poses", "init_qpos", "init_qvel"):
             c[k].index_copy_(0, rows, fit(data[k]))
         c["action_one_hot"].index_copy_(0, rows, one_hot)
+        if self.wide:
+            kpsim.ctx_rows_write(rows, seq, of, c.get("context_feat_rnn"), c.get("of"))
         for k in ("ar_qpos", "ar_qvel"):
             if k in c:
                 if k not in data:
@@ -200,6 +250,8 @@ class BatchedHumanoidAREnv:
         R, T = ctx["qpos"].shape[:2]
         if R % self.n != 0:
             raise ValueError(f"context rows ({R}) must be a multiple of n_envs ({self.n})")
+        if self.wide:
+            self._wide_sources(ctx, R, T, build=False)          # a context without the sequence / the features is refused before anything is allocated or written
         if env_mask is not None and (R != self.n or row is not None):
             raise ValueError("masked load_context works on one row per env")
         lens = ctx.get("len")
@@ -306,7 +358,7 @@ class BatchedHumanoidAREnv:
         m8 = self._mask8(env_mask, self.device)
         self.sim.reset_rows(self._init_q, self._init_v, self.row, m8, self.cur_t, set_target=True, aux_rows=policy_state,
                             row_obj_qpos=self._row_obj_qpos, row_one_hot=None if self._row_obj_qpos is None else self.ctx["action_one_hot"], obj7=self.obj7)
-        return self.sim.obs_ar(self._ctx_struct, self._obs)
+        return self._obs_ar(self._obs)
 
     def _ar_frame(self, key):
         """ar_context[key][cur_t + 1] per env."""
@@ -342,7 +394,7 @@ class BatchedHumanoidAREnv:
         o = self._outs[self._flip]
         sim.post_step(self._ctx_struct, self.reward_cfg, self.cur_t, self.row_len, int(min(self.env_episode_len, 2 ** 31 - 1)),
                       o["reward"], o["info"], o["fail"], o["diffs"], o["done"], o["end"], o["percent"], self.done_count, self.obj7)
-        obs = sim.obs_ar(self._ctx_struct, self._obs_next) if need_obs else None
+        obs = self._obs_ar(self._obs_next) if need_obs else None
         info = {"fail": o["fail"].view(torch.bool), "end": o["end"].view(torch.bool), "percent": o["percent"], "cc_action": cc_action, "cc_state": cc_obs,
                 "custom_reward": o["reward"], "custom_info": o["info"], "body_diff": o["diffs"]}
         return obs, self._unit_reward, o["done"].view(torch.bool), info        # the env's own reward is the constant 1.0 (humanoid_ar_v1.py:311); one shared read-only tensor

@@ -37,7 +37,7 @@ def run_sequences(env, policy_net, keys, fail_safe=False, max_steps=100000):
         if fail_safe:                               # masked on the device (no host read per step): envs that ended early go back onto the kinematic roll-out
             used_fs |= early
             env.ar_fail_safe(early)
-            obs = env.sim.obs_ar(env._ctx_struct, env._obs)
+            obs = env._obs_ar(env._obs)
             newly = newly & ~early
         active = active & ~newly
         if step % 8 == 7 and not bool(active.any()):      # one host read every 8 steps; the records of finished envs are dropped by `active` below

@@ -33,7 +33,7 @@ from .ppo import _collective_on
 @dataclass
 class RolloutBatch:
     """TrajBatchEgo (kin_poly/core/trajbatch_ego.py:5-14 over uhc/khrylib/rl/core/trajbatch.py:4-16), env-major [N, T, .]."""
-    states: torch.Tensor         # [N, T, 105] (env.obs_dim: 101 without the action one-hot, other widths for use_vel / use_head)
+    states: torch.Tensor         # [N, T, 105] (env.obs_dim: 101 without the action one-hot, other widths for use_vel / use_head; [context | row | of] under use_context / use_of)
     actions: torch.Tensor        # [N, T, 80]
     rewards: torch.Tensor        # [N, T]
     masks: torch.Tensor          # [N, T]   0 where the episode ended at this row
@@ -173,6 +173,9 @@ class EpisodeSource:
         # context_rnn / context_mlp / context_fc; they get no gradient and Adam skips them): a window that was seen under the same parameter
         # version is looked up instead of recomputed.  Needs a ctx_builder with need_rollout=False; any change of the parameters' versions
         # (load_state_dict, an optimiser that does train them) empties the memo.
+        if cache_init_context and ctx_builder is not None and getattr(ctx_builder.net, "ctx_block", 0):
+            raise ValueError("EpisodeSource(cache_init_context=True): the memo keeps init_qpos / init_qvel only, and a policy with a context block "
+                             f"(ctx_block {ctx_builder.net.ctx_block}) reads every drawn clip's context sequence in its observations")
         self.cache_init_context = bool(cache_init_context) and dataset is not None and ctx_builder is not None and not ctx_builder.need_rollout
         self._memo = None
         self.n_memo_hits = 0
@@ -404,7 +407,7 @@ class VectorSampler:
             # Memory.push, first half (one launch): state, episode start, the pose before the step, the GT pose of the clip's next frame, (take, fr_start)
             kpsim.record_pre(t, T, obs=self.obs, fresh=self.fresh, qpos=qview if self.record_qpos else None, ctx_qpos=env.ctx["qpos"] if self.record_qpos else None,
                              row=env.row, cur_t=env.cur_t, row_len=env.row_len, row_meta=env.row_meta,
-                             states=S, episode_start=E, curr_qpos=Q, gt_target_qpos=G, meta=MT, obs_dim=env.obs_dim)
+                             states=S, episode_start=E, curr_qpos=Q, gt_target_qpos=G, meta=MT, obs_dim=env.obs_dim, ctx_dim=env.ctx_dim, of_dim=env.of_dim)
             action, self.hx = pol.select_action(self.obs, self.hx, self.mean_action, env.gen, nz[:, :n_kin] if n_kin else None)
             action = action.contiguous()
             obs, _, done, info = env.step(action, need_obs=full, cc_noise=nz[:, n_kin:] if n_cc else None)
@@ -412,7 +415,7 @@ class VectorSampler:
             kpsim.record_post(t, T, fr_num, action=action, reward=info["custom_reward"], fail=info["fail"], done=done, percent=info["percent"], c_info=info["custom_info"],
                               obs=obs if full else None, qpos=qview if full else None, cc_action=info["cc_action"] if full else None, cc_state=info["cc_state"] if full else None,
                               meta=MT, actions=A, rewards=R, fails=F, dones=D, percents=PC, c_infos=CI, next_states=NS, res_qpos=RQ, cc_actions=CA, cc_states=CS, v_metas=VM,
-                              obs_dim=env.obs_dim)
+                              obs_dim=env.obs_dim, ctx_dim=env.ctx_dim, of_dim=env.of_dim)
             # device-side episode turnover: a finished env moves to the next clip of its ring (env.row in place), then the masked reset
             if self.source is not None:
                 kpsim.pool_advance(done, self.head, self.ahead, env.row, self.n_slots)

@@ -138,6 +138,9 @@ _SIGNATURES = {
     # the observation with a context / `of` block (kp_obs_ctx.hip)
     "kp_sim_obs_ar_ex": (_I, [_V, _CTX, _EXT, _V]),
     "kp_sim_obs_ar_ex_backward": (_I, [_V, _CTX, _EXT, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    # the sampler's records at a wide row, and the ring refill of the two wide context tables
+    "kp_rollout_record_pre_x": (_I, [_PRE, _I, _I, _I, _V]), "kp_rollout_record_post_x": (_I, [_POST, _I, _I, _I, _V]),
+    "kp_ctx_rows_write": (_I, [_I, _I, _I, _I, _I, _I, _V, _V, _V, _V, _V, _V, _V]),
 }
 ABI_SYMBOLS = list(_SIGNATURES)
 
@@ -643,9 +646,11 @@ def job_schedule(n_substeps: int, substeps_per_job: int = 4, taper: int = 1) -> 
     return list(out[:n])
 
 
-def _obs_width(obs_dim):
-    if obs_dim not in AR_OBS_DIMS:
-        raise ValueError(f"obs_dim must be one of {AR_OBS_DIMS} (ar_obs_dim of use_vel / use_head / use_action), got {obs_dim}")
+def _obs_width(obs_dim, ctx_dim=0, of_dim=0):
+    """The row width the record kernels are launched with: one of the eight layout widths, between a context block and an `of` block when given."""
+    if ctx_dim < 0 or of_dim < 0 or obs_dim - ctx_dim - of_dim not in AR_OBS_DIMS:
+        wide = f" between a {ctx_dim}-d context block and a {of_dim}-d `of` block" if (ctx_dim or of_dim) else ""
+        raise ValueError(f"obs_dim must be one of {AR_OBS_DIMS} (ar_obs_dim of use_vel / use_head / use_action){wide}, got {obs_dim}")
     return int(obs_dim)
 
 
@@ -655,11 +660,12 @@ def _u8(t):
 
 
 def record_pre(t: int, T: int, obs=None, fresh=None, qpos=None, ctx_qpos=None, row=None, cur_t=None, row_len=None, row_meta=None,
-               states=None, episode_start=None, curr_qpos=None, gt_target_qpos=None, meta=None, obs_dim=AR_OBS_DIM):
+               states=None, episode_start=None, curr_qpos=None, gt_target_qpos=None, meta=None, obs_dim=AR_OBS_DIM, ctx_dim=0, of_dim=0):
     """kp_rollout_record_pre: the before-the-step half of the sampler's per-step record, one launch (see include/kinpoly_sim.h).
-    obs_dim: the width of obs / states (the env's KpSim.obs_ar_dim)."""
+    obs_dim: the width of obs / states (the env's obs_dim); ctx_dim / of_dim: the context and `of` blocks around the KpSim.obs_ar_dim columns in it
+    (kp_rollout_record_pre_x; both 0: kp_rollout_record_pre_w)."""
     L = load_library()
-    w = _obs_width(obs_dim)
+    w = _obs_width(obs_dim, ctx_dim, of_dim)
     first = next(x for x in (obs, qpos, fresh) if x is not None)
     i32, u8 = torch.int32, torch.uint8
     n = first.shape[0]
@@ -668,15 +674,19 @@ def record_pre(t: int, T: int, obs=None, fresh=None, qpos=None, ctx_qpos=None, r
                     _dev("row", row, (n,), i32), _dev("cur_t", cur_t, (n,), i32), _dev("row_len", row_len, None, i32), _dev("row_meta", row_meta, None),
                     _dev("states", states, (n, T, w)), _dev("episode_start", _u8(episode_start), (n, T), u8), _dev("curr_qpos", curr_qpos, (n, T, 76)),
                     _dev("gt_target_qpos", gt_target_qpos, (n, T, 76)), _dev("meta", meta, (n, T, 2)))
-    _check(L.kp_rollout_record_pre_w(C.byref(r), w, C.c_void_p(torch.cuda.current_stream(first.device).cuda_stream)), "kp_rollout_record_pre")
+    stream = C.c_void_p(torch.cuda.current_stream(first.device).cuda_stream)
+    if ctx_dim or of_dim:
+        _check(L.kp_rollout_record_pre_x(C.byref(r), w, int(ctx_dim), int(of_dim), stream), "kp_rollout_record_pre_x")
+    else:
+        _check(L.kp_rollout_record_pre_w(C.byref(r), w, stream), "kp_rollout_record_pre")
 
 
 def record_post(t: int, T: int, fr_num=0.0, action=None, reward=None, fail=None, done=None, percent=None, c_info=None, obs=None, qpos=None, cc_action=None, cc_state=None, meta=None,
                 actions=None, rewards=None, fails=None, dones=None, percents=None, c_infos=None, next_states=None, res_qpos=None, cc_actions=None, cc_states=None, v_metas=None,
-                obs_dim=AR_OBS_DIM):
-    """kp_rollout_record_post: the after-the-step half (one launch); obs_dim: the width of obs / next_states."""
+                obs_dim=AR_OBS_DIM, ctx_dim=0, of_dim=0):
+    """kp_rollout_record_post: the after-the-step half (one launch); obs_dim: the width of obs / next_states, ctx_dim / of_dim as in record_pre."""
     L = load_library()
-    w = _obs_width(obs_dim)
+    w = _obs_width(obs_dim, ctx_dim, of_dim)
     first = next(x for x in (action, reward, done) if x is not None)
     u8 = torch.uint8
     n = first.shape[0]
@@ -686,7 +696,43 @@ def record_post(t: int, T: int, fr_num=0.0, action=None, reward=None, fail=None,
                      _dev("actions", actions, (n, T, 80)), _dev("rewards", rewards, (n, T)), _dev("fails", _u8(fails), (n, T), u8), _dev("dones", _u8(dones), (n, T), u8),
                      _dev("percents", percents, (n, T)), _dev("c_infos", c_infos, (n, T, 6)), _dev("next_states", next_states, (n, T, w)), _dev("res_qpos", res_qpos, (n, T, 76)),
                      _dev("cc_actions", cc_actions, (n, T, CC_ACTION_DIM)), _dev("cc_states", cc_states, (n, T, CC_OBS_DIM)), _dev("v_metas", v_metas, (n, T, 3)))
-    _check(L.kp_rollout_record_post_w(C.byref(r), w, C.c_void_p(torch.cuda.current_stream(first.device).cuda_stream)), "kp_rollout_record_post")
+    stream = C.c_void_p(torch.cuda.current_stream(first.device).cuda_stream)
+    if ctx_dim or of_dim:
+        _check(L.kp_rollout_record_post_x(C.byref(r), w, int(ctx_dim), int(of_dim), stream), "kp_rollout_record_post_x")
+    else:
+        _check(L.kp_rollout_record_post_w(C.byref(r), w, stream), "kp_rollout_record_post")
+
+
+def ctx_rows_write(rows, seq: torch.Tensor | None, of: torch.Tensor | None, ctx_table: torch.Tensor | None, of_table: torch.Tensor | None):
+    """The ring refill of the two wide context tables in one launch (kp_ctx_rows_write): ctx_table [R, T, H] rows `rows` <- seq [T', m, H] (time-major,
+    TrajARNet.context_sequence), of_table [R, T, F] rows `rows` <- of [m, T', F]; clips of T' < T frames are padded with their last frame.  Either table
+    (with its source) may be None.  rows: int64 [m], a host tensor / array (checked as it is, uploaded) or a device tensor (one host read for the
+    check); no row twice.  Refused before any launch: a row outside [0, R), T' < 1 or T' > T, shapes that do not fit, host tensors."""
+    L = load_library()
+    tab = ctx_table if ctx_table is not None else of_table
+    if tab is None:
+        return
+    _dev("ctx_rows_write: a table", tab, (None, None, None))
+    R, T = tab.shape[:2]
+    src = seq if ctx_table is not None else of
+    if src is None:
+        raise ValueError("ctx_rows_write: a table without its source")
+    _dev("ctx_rows_write: a source", src, (None, None, None))
+    m, Tp = (src.shape[1], src.shape[0]) if ctx_table is not None else (src.shape[0], src.shape[1])
+    H = 0 if ctx_table is None else int(ctx_table.shape[2])
+    F = 0 if of_table is None else int(of_table.shape[2])
+    ptrs = [_dev("ctx_rows_write: " + k, t, shp) for k, t, shp in (("seq", seq if H else None, (Tp, m, H)), ("of", of if F else None, (m, Tp, F)),
+                                                                   ("ctx_table", ctx_table, (R, T, H)), ("of_table", of_table, (R, T, F)))]
+    if torch.is_tensor(rows) and rows.is_cuda:
+        rows_dev = rows.to(torch.int64).contiguous()
+        rows_host = rows_dev.cpu()
+    else:
+        rows_host = torch.as_tensor(np.asarray(rows) if not torch.is_tensor(rows) else rows).to(torch.int64).contiguous()
+        rows_dev = rows_host.to(tab.device)
+    if rows_host.dim() != 1 or rows_host.numel() != m:
+        raise ValueError(f"ctx_rows_write: rows must be int64 [{m}] (one per clip), got {tuple(rows_host.shape)}")
+    stream = C.c_void_p(torch.cuda.current_stream(tab.device).cuda_stream)
+    _check(L.kp_ctx_rows_write(int(m), int(R), int(T), int(Tp), H, F, C.c_void_p(rows_dev.data_ptr()), C.c_void_p(rows_host.data_ptr()), *ptrs, stream), "kp_ctx_rows_write")
 
 
 def pool_advance(done: torch.Tensor, head: torch.Tensor, ahead: torch.Tensor, row: torch.Tensor, n_slots: int):

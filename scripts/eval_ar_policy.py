@@ -9,7 +9,9 @@ The reference's test sets are not part of its repository; without `--data` this 
     python scripts/eval_ar_policy.py --cfg kin_poly --config_root /path/to/KinPoly --iter 750 [--data test]     # the reference's command line (--mode stats)
 
 With --cfg the feature file, the take list (`meta/<meta_id>.yml`), the checkpoint (`models_policy/iter_%04d.p`) and the result directory come from
-the reference's yml (kinpoly_amd/config.py), and the coverage pickles land where eval_pose_all.py looks for them.
+the reference's yml (kinpoly_amd/config.py), and the coverage pickles land where eval_pose_all.py looks for them.  A yml with `use_context` / `use_of` evaluates
+the video-conditioned policy: the image features are `<dataset_path>/features/<of_file>.p` (`of_file_wild` with --wild) or, without that file, this repository's
+synthetic stand-in (said on stdout); such a policy needs takes (--data or the yml's feature file), not the synthetic standing sequences.
 """
 import argparse
 import os
@@ -53,7 +55,7 @@ def main():
         from kinpoly_amd.config import Config
         if args.config_root:
             os.chdir(args.config_root)
-        cfg = Config(args.cfg, wild=args.wild)
+        cfg = Config(args.cfg, wild=args.wild, entry="policy_ctx")
         mode = args.data if args.data in ("train", "test") else "test"
         takes = cfg.takes[mode] or None
         args.data = cfg.feature_path() if args.data in ("", "train", "test") else args.data
@@ -62,20 +64,38 @@ def main():
             args.ckpt = cfg.checkpoint_path(args.iter)
     # the observation variant of the yml (use_action false: kin_poly_wo_action.yml, 101-d; use_vel / use_head: kinpoly_amd.sim.ar_obs_dim)
     obs_kw = dict(use_action=cfg.use_action, use_vel=cfg.use_vel, use_head=cfg.use_head) if cfg is not None else {}
-    env = BatchedHumanoidAREnv(n, 0, mode="test", wild=args.wild, ar_mode=args.ar_mode, seed=0, **obs_kw)
+    # the video-conditioned policy of the yml (use_context / use_of): the features first, their width is the `of` block's
+    ctx_kw, feats, of = {}, None, None
+    if cfg is not None and (cfg.use_context or cfg.use_of):
+        if not args.data:
+            raise SystemExit("use_context / use_of: the policy reads a context sequence of real takes; give --data (or a yml whose feature file exists)")
+        import joblib
+        from kinpoly_amd import dataset as D
+        feats = joblib.load(args.data)
+        if cfg.use_of:
+            of_path = cfg.of_feature_path()
+            have = os.path.exists(of_path)
+            print(f"of features: {of_path if have else 'synthetic stand-in (no ' + of_path + ')'}", flush=True)
+            of = joblib.load(of_path) if have else D.synthetic_of_features(feats, int(cfg.model_specs.get("cnn_fdim", 512)), seed=cfg.seed)
+    if cfg is not None:          # the net sizes the yml names (as train_ar_policy.py builds the agent), the context block and the `of` block
+        ctx_kw = cfg.context_kwargs(int(np.asarray(next(iter(of.values()))).shape[1]) if of else None)
+    ctx_block = int(ctx_kw.get("rnn_hdim", 1024)) if (ctx_kw.get("use_context") or ctx_kw.get("of_dim")) else 0          # TrajARNet.ctx_block
+    env = BatchedHumanoidAREnv(n, 0, mode="test", wild=args.wild, ar_mode=args.ar_mode, seed=0, **obs_kw, ctx_dim=ctx_block, of_dim=ctx_kw.get("of_dim", 0))
     if cfg is not None:
         cfg.apply_reward_weights(env)
-    net = TrajARNet(log_std=cfg.policy_specs["log_std"] if cfg else -3.2, **obs_kw).to(env.device)
+    net = TrajARNet(log_std=cfg.policy_specs["log_std"] if cfg else -3.2, **obs_kw, **ctx_kw, of_in_state=bool(ctx_kw.get("of_dim", 0))).to(env.device)
+    assert net.ctx_block == ctx_block and net.state_dim == env.obs_dim
     if args.ckpt:
         cp = ck.load_checkpoint(args.ckpt)
         sd = ck.split_policy_dict(cp["policy_dict"])
         ck.check_policy_obs_dim(sd, net.state_dim, args.ckpt)
+        ck.check_state_shapes(sd, net, args.ckpt)          # other net sizes (rnn_hdim, mlp_hsize): refused with both shapes
         net.load_state_dict(sd, strict=False)
     if args.data:                                   # every take of the feature file, whole, env.n at a time (run_seq over data_loader.iter_seq)
         from kinpoly_amd import dataset as D
         from kinpoly_amd.evaluate import eval_dataset
-        ds = D.StateARDataset(args.data, takes=takes, data_mode="test", fr_num=T, wild=args.wild, seed=0, device=env.device)
-        builder = PolicyARContext(net, kpsim.KpSim(env.model, n, 0), smooth=bool(cfg.smooth) if cfg else True, keep_context_feat=False)
+        ds = D.StateARDataset(args.data if feats is None else feats, takes=takes, data_mode="test", fr_num=T, wild=args.wild, seed=0, device=env.device, of_features=of)
+        builder = PolicyARContext(net, kpsim.KpSim(env.model, n, 0), smooth=bool(cfg.smooth) if cfg else True, keep_context_feat=bool(ctx_block))
         res = eval_dataset(env, net, builder, ds, fail_safe=args.fail_safe)
         cov = write_coverage(res, args.result_dir, args.iter, args.data_file if args.cfg else os.path.splitext(os.path.basename(args.data))[0])
         pct = np.array([r["percent"] for r in res.values()])

@@ -8,7 +8,10 @@
 With --cfg the run is configured by the reference's `config/statear/<cfg>.yml` (kinpoly_amd/config.py): optimisers, schedules, PPO and sampling
 constants, reward weights, the horizon from `min_batch_size`, `results/all/statear/<cfg>/` for checkpoints (`models_policy/iter_%04d.p`, every
 `save_model_interval` iterations, agent_ar.py:341-364), `freq_dict.pt`, `eval_dict_*.pt` and `log/log.txt`; `--iter N` resumes from that checkpoint
-(train_ar_policy.py:92-104); every `save_model_interval` iterations the test sets are evaluated (`eval_policy("test")`, agent_ar.py:291-293).
+(train_ar_policy.py:92-104); every `save_model_interval` iterations the test sets are evaluated (`eval_policy("test")`, agent_ar.py:291-293).  A yml with `use_context` / `use_of` (kin_poly.yml with
+the two switches on: tests/golden/kin_poly_of.yml) trains the video-conditioned policy through the physics: the image features come from
+`<dataset_path>/features/<of_file>.p` (`of_file_wild` with --wild) or, without that file, from this repository's synthetic stand-in (said on stdout); `--iter N`
+also takes the kinematic model's own checkpoint `models/iter_%04d.p` of `scripts/exp_arnet_all.py --as_policy` when `models_policy/` has none.
 
 The reference's MoCap dataset and trained UHC weights are not part of its repository (downlaod_data.sh), so this
 driver builds synthetic takes in the reference's feature-file schema (all four action classes with their objects, SURVEY.md
@@ -87,18 +90,30 @@ def main():
         from kinpoly_amd.config import Config
         if args.config_root:
             os.chdir(args.config_root)                 # the yml's dataset_path and the results/ tree are relative to it, as in the reference
-        cfg = Config(args.cfg, wild=args.wild, create_dirs=(rank == 0))
+        cfg = Config(args.cfg, wild=args.wild, create_dirs=(rank == 0), entry="policy_ctx")
         args.clip_len = int(cfg.fr_num)
         if not args.data and os.path.exists(cfg.feature_path()):
             args.data = cfg.feature_path()
+    def of_features(takes):
+        """`use_of`: the yml's feature file, or the synthetic stand-in model_specs.cnn_fdim wide (as scripts/exp_arnet_all.py); None without use_of"""
+        if cfg is None or not cfg.use_of:
+            return None
+        of_path = cfg.of_feature_path()
+        have = os.path.exists(of_path)
+        if rank == 0:
+            print(f"of features: {of_path if have else 'synthetic stand-in (no ' + of_path + ')'}", flush=True)
+        return of_path if have else D.synthetic_of_features(takes, int(cfg.model_specs.get("cnn_fdim", 512)), seed=cfg.seed)
     if args.data:
-        ds = D.StateARDataset(args.data, takes=(cfg.takes["train"] or None) if cfg else None, fr_num=args.clip_len, wild=args.wild, seed=4 + rank, device=fk_sim.device)
+        import joblib
+        feats = joblib.load(args.data)
+        ds = D.StateARDataset(feats, takes=(cfg.takes["train"] or None) if cfg else None, fr_num=args.clip_len, wild=args.wild, seed=4 + rank, device=fk_sim.device,
+                              of_features=of_features(feats))
     else:       # the reference's MoCap features are not in its repository: same schema, synthetic takes (SURVEY.md 8(d) config 4).  ONE
         # data set for the whole job (take seed independent of the rank): the job-wide freq_dict is keyed by take name, so a name must
         # mean the same motion on every rank; only the draw stream (dataset seed) differs per rank
         takes = D.synthetic_takes(fk_sim, std["qpos"], n_per_action=4, T_range=(args.clip_len + 10, args.clip_len + 60),
                                   body_mass=read_kpm(kpsim.STEP_KPM)["body_mass"], seed=4, amp_max=args.synthetic_amp)
-        ds = D.StateARDataset(takes, fr_num=args.clip_len, seed=4 + rank, device=fk_sim.device)
+        ds = D.StateARDataset(takes, fr_num=args.clip_len, seed=4 + rank, device=fk_sim.device, of_features=of_features(takes))
     if rank == 0:
         print(f"dataset: {ds.get_len()} takes, {len(ds.freq_indices)} windows of {args.clip_len} frames", flush=True)
 
@@ -123,13 +138,21 @@ def main():
         if rank == 0:
             print(f"horizon {horizon} steps per env = {horizon * args.num_envs * world} samples per iteration (min_batch_size {cfg.policy_specs.get('min_batch_size', 10000)})", flush=True)
         agent = AgentAR(args.num_envs, dataset=ds, device=local, horizon=horizon, pool_depth=args.pool_depth, **upd_kw,
-                        cache_init_context=args.cache_init_context, result_dir=cfg.result_dir, cc_checkpoint=cc_ckpt, **cfg.agent_kwargs(),
+                        cache_init_context=args.cache_init_context, result_dir=cfg.result_dir, cc_checkpoint=cc_ckpt, **cfg.agent_kwargs(ds.of_dim or None),
                         min_batch_size=int(cfg.policy_specs.get("min_batch_size", 10000)) if args.min_batch_size is None else args.min_batch_size)
         cfg.apply_reward_weights(agent.env)
+        if cfg.use_of and (args.test_data or args.test_data_wild):
+            raise SystemExit("--test_data / --test_data_wild with use_of: the test sets' image features have no command-line option yet")
         agent.test_datasets = ([D.StateARDataset(p, data_mode="test", fr_num=args.clip_len, wild=args.wild, seed=4, device=fk_sim.device) for p in args.test_data]
                                + [D.StateARDataset(p, data_mode="test", fr_num=args.clip_len, wild=True, seed=4, device=fk_sim.device) for p in args.test_data_wild])
         if args.iter > 0:                              # AgentAR(checkpoint_epoch=args.iter) -> load_checkpoint (agent_ar.py:72-73, 318-339)
-            agent.load_checkpoint(cfg.checkpoint_path(args.iter))
+            cp_path = cfg.checkpoint_path(args.iter)
+            kin_path = os.path.join(cfg.model_dir, "iter_%04d.p" % args.iter)
+            if not os.path.exists(cp_path) and os.path.exists(kin_path):      # the supervised kinematic model of scripts/exp_arnet_all.py --as_policy
+                cp_path = kin_path
+            if rank == 0:
+                print(f"loading model from checkpoint: {cp_path}", flush=True)
+            agent.load_checkpoint(cp_path)
             agent.epoch = args.iter
             # the reference builds FRESH LambdaLR schedulers on resume (setup_optimizer runs before load_checkpoint and nothing restores them,
             # agent_ar.py:60-73, 215-225): a resumed run restarts its learning-rate decay at epoch 0.  Reproduced; --no_reference_bugs continues it
