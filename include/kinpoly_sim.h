@@ -180,6 +180,32 @@ int kp_sim_fk(kp_sim*, int n_rows, const float* qpos, float* qpos_out, float* wb
 int kp_sim_pose_contacts(kp_sim*, int n_rows, const float* xpos, const float* xquat, const float* obj_qpos, float pen_margin,
                          float* pen, int32_t* ncon, uint32_t* hits);
 
+/* The face planes of the model's 24 convex hulls, built from the blob's hull vertices (the blob holds vertices and a neighbour graph, not faces):
+ * planes4 [n,4] = (unit outward normal, d) in the body frame, n.x <= d inside; adr [nb + 1] = first plane of every body.  Either array may be NULL;
+ * returns n (2302 for the shipped blobs), -1 on a null model.  Host only: works without a device.  This is the geometry kp_sim_render draws where the
+ * reference's viewer (Visualizer.render, uhc/khrylib/rl/utils/visualizer.py; scripts/eval_uhc.py:85-131) draws the mesh geoms MuJoCo compiled. */
+int kp_model_hull_planes(const kp_model*, float* planes4, int32_t* adr);
+
+/* colours (r, g, b in 0..1) and far plane of kp_sim_render: one base colour per figure, one for the object geoms, the two greys of the floor's
+ * 1 m checker (parity (floor(x) + floor(y)) & 1), the sky; floor hits beyond zfar metres along the ray are sky */
+typedef struct { float figure[4][3], object[3], floor[2][3], sky[3], zfar; } kp_render_style;
+/* light grey for figure 0, the reference's expert red (0.7, 0, 0) for figure 1, zfar = 100 */
+void kp_render_style_default(kp_render_style*);
+
+/* Offscreen frames: replaces Visualizer.render / save_screen_shots of the reference's MuJoCo GL viewer as scripts/eval_uhc.py:85-131 (--mode vis,
+ * --record, --preview) and scripts/eval_pose_all.py:468-531 (--mode vis) drive it, with a ray-caster over the collision geometry: per row n_fig
+ * figures (1..4, e.g. simulated and expert) given as body poses xpos [R,n_fig,72] / xquat [R,n_fig,96] (kp_sim_fk's wbpos / wbquat), the row's object
+ * block obj_qpos [R,35] or NULL (floor and figures only; objects are placed as kp_sim_pose_contacts places them) and the floor z = 0.
+ * camera [camera_rows,7] on the device, camera_rows = 1 or R: lookat[3], distance, azimuth, elevation, fovy (degrees), the viewer's free camera;
+ * one ray per pixel centre, row 0 at the top.  style: NULL = kp_render_style_default.  Outputs [R,height,width], each may be NULL but not all:
+ * geom (int32: -1 nothing, 0 floor, 100 k + 1 + b body b of figure k, 25 + g object geom g -- for figure 0 and the objects the reference's
+ * geom ids), depth (float, distance along the normalised ray, +inf where nothing is hit), rgba (4 x uint8, base colour x (0.35 + 0.65 max(0,
+ * -n.dir)), alpha 255).  Refused before anything is launched: n_fig outside 1..4, width or height outside 1..4096, null inputs, all outputs null,
+ * obj_qpos on a blob without object geoms, more than 16 object geoms, obj_qpos on a blob with an object geom that is neither box nor cylinder or
+ * that belongs to no object of the block.  Enqueued on the sim's stream; the first call uploads the plane table. */
+int kp_sim_render(kp_sim*, int n_rows, int n_fig, const float* xpos, const float* xquat, const float* obj_qpos, const float* camera, int camera_rows,
+                  int width, int height, const kp_render_style* style, int32_t* geom, float* depth, uint8_t* rgba);
+
 /* backward of qpos -> wbpos of the same rows (the autograd path through Humanoid.qpos_fk that TrajARNet.compute_loss_lite's
  * end-effector term takes, traj_ar_smpl_net.py:459-497, torch_smpl_humanoid.py:125-202): grad_qpos [n_rows,76] =
  * (d wbpos / d qpos)^T grad_wbpos [n_rows,72]; wbpos / wbquat are the outputs of the kp_sim_fk call on those rows. */

@@ -21,6 +21,7 @@
 #include "kp_policy_kernels.hpp"
 #include "kp_step_kernel.hpp"
 #include "kp_pose_contacts.hpp"
+#include "kp_render.hpp"
 #include "kp_takes.hpp"
 #include "kp_kin_tape.hpp"
 #include "kp_obs_ctx.hpp"
@@ -85,6 +86,10 @@ struct Timing {
     bool ring_on = false, timed = false;
 };
 
+struct RenderTables {     // the hulls' face planes (kp::hull_planes), uploaded by the first kp_sim_render
+    const float* planes = nullptr; const int32_t* adr = nullptr;
+};
+
 struct kp_sim {
     const kp_model* model = nullptr;
     int n = 0, device = 0;
@@ -103,6 +108,7 @@ struct kp_sim {
     JobQueue q;
     OverflowReadback ovf;
     ObjectRows obj;
+    RenderTables rd;
     Timing tm;
     long launch_index = 0;
     int last_nsub = 15;                               // substeps of the last control step (kp_sim_lean_state)
@@ -818,6 +824,67 @@ int kp_sim_pose_contacts(kp_sim* s, int n_rows, const float* xpos, const float* 
     A.xpos = xpos; A.xquat = xquat; A.obj_qpos = obj_qpos; A.og = s->obj.d_geoms; A.pen_margin = pen_margin;
     A.pen = pen; A.ncon = ncon; A.hits = hits;
     HIP_OK(kp::launch_pose_contacts(A, s->stream));
+    return 0;
+}
+
+int kp_model_hull_planes(const kp_model* m, float* planes4, int32_t* adr) {
+    if (!m) return fail("kp_model_hull_planes: null model");
+    std::vector<float> pl; std::vector<int32_t> ad;
+    const int n = kp::hull_planes(m->h, pl, ad);
+    if (planes4) std::memcpy(planes4, pl.data(), sizeof(float) * pl.size());
+    if (adr) std::memcpy(adr, ad.data(), sizeof(int32_t) * ad.size());
+    return n;
+}
+
+void kp_render_style_default(kp_render_style* st) {
+    if (!st) return;
+    const kp_render_style d = {{{0.8f, 0.8f, 0.8f}, {0.7f, 0.f, 0.f}, {0.1f, 0.5f, 0.1f}, {0.1f, 0.2f, 0.7f}}, {0.75f, 0.6f, 0.35f},
+                               {{0.45f, 0.45f, 0.45f}, {0.6f, 0.6f, 0.6f}}, {0.75f, 0.85f, 1.0f}, 100.0f};
+    *st = d;
+}
+
+int kp_sim_render(kp_sim* s, int n_rows, int n_fig, const float* xpos, const float* xquat, const float* obj_qpos, const float* camera, int camera_rows,
+                  int width, int height, const kp_render_style* style, int32_t* geom, float* depth, uint8_t* rgba) {
+    static_assert(sizeof(kp_render_style) == sizeof(kp::RenderStyle), "kp_render_style and kp::RenderStyle are one layout");
+    if (!s) return fail("kp_sim_render: null sim");
+    if (n_rows < 0) return fail("kp_sim_render: n_rows < 0");
+    if (n_fig < 1 || n_fig > kp::RD_MAXFIG) return fail("kp_sim_render: n_fig outside 1..4");
+    if (width < 1 || width > kp::RD_MAXDIM || height < 1 || height > kp::RD_MAXDIM) return fail("kp_sim_render: width / height outside 1..4096");
+    if (!xpos || !xquat) return fail("kp_sim_render: null xpos / xquat");
+    if (!camera) return fail("kp_sim_render: null camera");
+    if (camera_rows != 1 && camera_rows != n_rows) return fail("kp_sim_render: camera_rows is neither 1 nor n_rows");
+    if (!geom && !depth && !rgba) return fail("kp_sim_render: null output (geom, depth and rgba are all null)");
+    if (obj_qpos && !s->obj.d_geoms) return fail("kp_sim_render: obj_qpos given but the model blob has no object geoms");
+    if (s->obj.n_geoms > kp::RD_MAXGEOM) return fail("kp_sim_render: the model has more object geoms than the renderer holds (16)");
+    if (obj_qpos)
+        for (int g = 0; g < s->obj.n_geoms; g++) {      // what the kernel draws: boxes and cylinders of the five objects of the 35-float block
+            const double* og = s->model->h.obj_geoms.data() + 18 * g;
+            if (og[1] != 0.0 && og[1] != 1.0) return fail("kp_sim_render: the model has an object geom that is neither a box (0) nor a cylinder (1)");
+            if (og[0] < 0.0 || og[0] >= 5.0 || og[0] >= (double)s->obj.n_obj) return fail("kp_sim_render: the model has an object geom of an object outside the 35-float object block");
+        }
+    if (style && !(style->zfar > 0.f)) return fail("kp_sim_render: style.zfar must be positive");
+    const long tiles = (long)((width + 7) / 8) * ((height + 7) / 8), blocks = (tiles + kp::RD_TILES - 1) / kp::RD_TILES * (long)n_rows;
+    if (blocks > INT_MAX) return fail("kp_sim_render: n_rows x image tiles exceed one launch (render fewer rows per call)");
+    if (n_rows == 0) return 0;
+    HIP_OK(hipSetDevice(s->device));
+    if (!s->rd.planes) {
+        std::vector<float> pl; std::vector<int32_t> ad;
+        kp::hull_planes(s->model->h, pl, ad);
+        bool ok = true;
+        const float* dp = upload<float>(s, pl, &ok);
+        const int32_t* da = upload<int32_t>(s, ad, &ok);
+        if (!ok) return fail("kp_sim_render: uploading the hull planes failed");
+        s->rd.planes = dp; s->rd.adr = da;
+    }
+    kp::RenderArgs A{};
+    A.n_rows = n_rows; A.n_fig = n_fig; A.width = width; A.height = height; A.cam_rows = camera_rows; A.n_og = s->obj.n_geoms; A.n_obj = s->obj.n_obj;
+    A.xpos = xpos; A.xquat = xquat; A.obj_qpos = obj_qpos; A.camera = camera; A.og = s->obj.d_geoms; A.rbound = s->T.body_rbound;
+    A.planes = (const float4*)s->rd.planes; A.plane_adr = s->rd.adr;
+    kp_render_style st;
+    if (style) st = *style; else kp_render_style_default(&st);
+    std::memcpy(&A.style, &st, sizeof(st));
+    A.geom = geom; A.depth = depth; A.rgba = (uint32_t*)rgba;
+    HIP_OK(kp::launch_render(A, s->stream));
     return 0;
 }
 

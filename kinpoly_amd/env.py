@@ -324,6 +324,12 @@ class BatchedHumanoidAREnv:
         """data.qpos[76:111] of every env [N, 35] (get_obj_qpos(), humanoid_ar_v1.py:466-477), or None when the clips carry no objects"""
         return self.sim.get("obj_qpos") if self.has_objects else None
 
+    def render_rgb(self, envs=None, camera=None, width=320, height=240):
+        """Frames of the envs (all, or the indices `envs`): figure 0 the simulated pose, figure 1 the kinematic target, the clip's objects -> uint8
+        [n, H, W, 4] on the device (kinpoly_amd.render.render_env; camera None follows every env's root).  What the reference shows with env.render()."""
+        from .render import render_env
+        return render_env(self.sim, self.obj_qpos, envs, camera, width, height)
+
     @property
     def ctx_len(self):
         """ar_context['len'] of every env's current clip (int32 [N])."""

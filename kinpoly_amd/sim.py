@@ -89,13 +89,24 @@ class KpUhcCfg(C.Structure):
                [(k, C.c_int) for k in ("term_body", "env_episode_len", "trail", "obs_v", "vf_dim", "action_dim")] + [("a_ref", C.c_void_p), ("b_diffw", C.c_void_p)]
 
 
+class KpRenderStyle(C.Structure):
+    """mirror of kp_render_style: base colours (r, g, b in 0..1) of the figures, the objects, the floor checker's two cells and the sky; zfar in metres"""
+    _fields_ = [("figure", C.c_float * 3 * 4), ("object", C.c_float * 3), ("floor", C.c_float * 3 * 2), ("sky", C.c_float * 3), ("zfar", C.c_float)]
+
+    @classmethod
+    def default(cls):
+        st = cls()
+        load_library().kp_render_style_default(C.byref(st))
+        return st
+
+
 class KinPolyNativeError(RuntimeError):
     pass
 
 
 _V, _I, _F, _D, _S = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_char_p      # handles and device / host arrays are all void*
 _PI = C.POINTER(C.c_int)
-_CTX, _RW, _PRE, _POST, _UST, _UCFG, _EXT = (C.POINTER(k) for k in (KpCtx, KpRewardCfg, KpRecordPre, KpRecordPost, KpUhcState, KpUhcCfg, KpObsExt))
+_CTX, _RW, _PRE, _POST, _UST, _UCFG, _EXT, _STYLE = (C.POINTER(k) for k in (KpCtx, KpRewardCfg, KpRecordPre, KpRecordPost, KpUhcState, KpUhcCfg, KpObsExt, KpRenderStyle))
 # every symbol include/kinpoly_sim.h declares: symbol -> (restype, argtypes).  load_library types them all from here, and tests check the header against it.
 _SIGNATURES = {
     "kp_last_error": (_S, []), "kp_version": (_S, []),
@@ -107,6 +118,9 @@ _SIGNATURES = {
     "kp_sim_set_objects": (_I, [_V, _V, _V]), "kp_sim_set_obj_state": (_I, [_V, _V, _V, _V]),
     "kp_sim_fk": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]), "kp_sim_fk_backward": (_I, [_V, _I, _V, _V, _V, _V, _V]),
     "kp_sim_pose_contacts": (_I, [_V, _I, _V, _V, _V, _F, _V, _V, _V]),
+    # the offscreen renderer (kp_render.hip); kp_model_hull_planes is host only
+    "kp_model_hull_planes": (_I, [_V, _V, _V]), "kp_render_style_default": (None, [_STYLE]),
+    "kp_sim_render": (_I, [_V, _I, _I, _V, _V, _V, _V, _I, _I, _I, _STYLE, _V, _V, _V]),
     "kp_sim_step_ctrl": (_I, [_V, _V, _I, _V]), "kp_sim_step_ctrl_base": (_I, [_V, _V, _I, _V, _V]), "kp_sim_step_kin": (_I, [_V, _V, _V]),
     "kp_sim_step_head": (_I, [_V, _V]), "kp_sim_step_begin": (_I, [_V]),
     "kp_sim_obs_cc": (_I, [_V, _V, _V, _V, _F]), "kp_sim_obs_cc_ex": (_I, [_V, _V, _V, _V, _F, _V]), "kp_sim_cc_obs_dim": (_I, [_V]),
@@ -185,6 +199,16 @@ class KpModel:
             raise KinPolyNativeError(f"kp_model_load: {self.L.kp_last_error().decode()}")
         for k, v in options.items():
             self.set_option(k, v)
+
+    def hull_planes(self):
+        """The face planes of the 24 hulls (kp_model_hull_planes; host only, no device needed): (planes [n, 4] float32 = unit outward normal and d
+        in the body frame, n.x <= d inside; adr [25] int32 = first plane of every body)."""
+        n = self.L.kp_model_hull_planes(self.h, None, None)
+        if n < 0:
+            raise KinPolyNativeError(f"kp_model_hull_planes: {self.L.kp_last_error().decode()}")
+        planes, adr = np.empty((n, 4), np.float32), np.empty(NBODY + 1, np.int32)
+        self.L.kp_model_hull_planes(self.h, planes.ctypes.data_as(C.c_void_p), adr.ctypes.data_as(C.c_void_p))
+        return planes, adr
 
     def set_option(self, name, value):
         _check(self.L.kp_model_set_option(self.h, name.encode(), float(value)), "kp_model_set_option")
@@ -439,6 +463,44 @@ class KpSim:
         _check(self.L.kp_sim_pose_contacts(self.h, R, C.c_void_p(out["xpos"].data_ptr()), C.c_void_p(out["xquat"].data_ptr()), op, float(pen_margin),
                                            *[C.c_void_p(out[k].data_ptr()) for k in ("pen", "ncon", "hits")]), "kp_sim_pose_contacts")
         return out
+
+    RENDER_OUTPUTS = {"rgba": (torch.uint8, (4,)), "geom": (torch.int32, ()), "depth": (torch.float32, ())}
+
+    def render_poses(self, xpos: torch.Tensor, xquat: torch.Tensor, obj_qpos: torch.Tensor | None = None, camera=None, width: int = 320, height: int = 240,
+                     want=("rgba",), style: "KpRenderStyle | None" = None) -> dict:
+        """kp_sim_render on body poses: xpos [R,K,72] / xquat [R,K,96] (K = 1..4 figures per row, fk()'s wbpos / wbquat), obj_qpos [R,35] or None
+        (floor and figures only), camera = a kinpoly_amd.render.Camera, a [7] / [1,7] / [R,7] tensor (lookat[3], distance, azimuth, elevation, fovy;
+        degrees) or None (the reference viewer's default) -> dict of device tensors for the names in `want`: rgba uint8 [R,H,W,4], geom int32 [R,H,W]
+        (-1 nothing, 0 floor, 100 k + 1 + b body b of figure k, 25 + g object geom g), depth float32 [R,H,W] (+inf where nothing is hit)."""
+        _dev("render: xpos", xpos, (None, None, 72))
+        R, K = xpos.shape[:2]
+        xq = _dev("render: xquat", xquat, (R, K, 96))
+        op = _dev("render: obj_qpos", obj_qpos, (R, 35))
+        if camera is None or hasattr(camera, "tensor"):
+            from .render import Camera
+            camera = (camera or Camera()).tensor(self.device)
+        cam = camera.reshape(1, 7) if camera.dim() == 1 else camera
+        if cam.dim() != 2 or cam.shape[0] not in (1, R):
+            raise ValueError(f"render: camera must be [7], [1,7] or [{R},7], got {tuple(camera.shape)}")
+        cp = _dev("render: camera", cam, (cam.shape[0], 7))
+        unknown = [k for k in want if k not in self.RENDER_OUTPUTS]
+        if unknown or not want:
+            raise ValueError(f"render: want must name some of {sorted(self.RENDER_OUTPUTS)}, got {tuple(want)}")
+        out = {k: torch.empty((R, int(height), int(width)) + self.RENDER_OUTPUTS[k][1], dtype=self.RENDER_OUTPUTS[k][0], device=self.device) for k in want}
+        ptr = lambda k: C.c_void_p(out[k].data_ptr()) if k in out else None      # noqa: E731
+        _check(self.L.kp_sim_render(self.h, R, K, C.c_void_p(xpos.data_ptr()), xq, op, cp, cam.shape[0], int(width), int(height),
+                                    None if style is None else C.byref(style), ptr("geom"), ptr("depth"), ptr("rgba")), "kp_sim_render")
+        return out
+
+    def render(self, qpos_rows: torch.Tensor, obj_qpos: torch.Tensor | None = None, camera=None, width: int = 320, height: int = 240, want=("rgba",),
+               style: "KpRenderStyle | None" = None) -> dict:
+        """Frames of qpos rows [R,76], or [R,K,76] for K figures per row (e.g. simulated and expert): fk() of every figure, then render_poses."""
+        if qpos_rows.dim() == 2:
+            qpos_rows = qpos_rows[:, None]
+        _dev("render: qpos_rows", qpos_rows, (None, None, NQ))
+        R, K = qpos_rows.shape[:2]
+        f = self.fk(qpos_rows.reshape(R * K, NQ)) if R else {"wbpos": qpos_rows.new_empty((0, 72)), "wbquat": qpos_rows.new_empty((0, 96))}
+        return self.render_poses(f["wbpos"].view(R, K, 72), f["wbquat"].view(R, K, 96), obj_qpos, camera, width, height, want, style)
 
     def step_begin(self):
         _check(self.L.kp_sim_step_begin(self.h), "kp_sim_step_begin")

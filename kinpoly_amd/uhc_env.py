@@ -212,6 +212,12 @@ class BatchedHumanoidEnv:
     def has_objects(self):
         return self.takes is not None and self.takes.has_objects
 
+    def render_rgb(self, envs=None, camera=None, width=320, height=240):
+        """Frames of the envs (all, or the indices `envs`): figure 0 the simulated pose, figure 1 the expert frame the controller tracks, the take's
+        objects -> uint8 [n, H, W, 4] on the device (kinpoly_amd.render.render_env; camera None follows every env's root)."""
+        from .render import render_env
+        return render_env(self.sim, self.get_obj_qpos().clone() if self.has_objects else None, envs, camera, width, height)
+
     def _step_takes(self, a):
         if self._next_ids is not None:
             raise RuntimeError("load_takes: call reset() before the first step (the envs are on no take yet)")

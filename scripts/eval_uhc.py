@@ -8,7 +8,8 @@ a take pickle played whole by a trained UHC, env.n takes at a time; writes `<ite
 --cfg names the controller's yml (its data_specs give test_file_path and t_min); --takes overrides the take file, --ckpt the checkpoint;
 --dataset smpl_obj reads the take file as DatasetSMPLObj's (takes that carry objects: the objects are simulated and `pred` rows are 111 wide)
 (default <config_root>/results/motion_im/<cfg>/models/iter_%04d.p).  The viewer modes of the reference (--mode vis / disp_stats, --record, --preview)
-need its MuJoCo viewer and are refused by name.
+need its MuJoCo viewer and are refused by name; scripts/render_results.py turns the `_coverage_full.pkl` this writes into frames with the engine's own
+ray-caster.
 """
 import argparse
 import os
