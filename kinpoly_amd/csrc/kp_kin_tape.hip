@@ -1,40 +1,24 @@
 // kp_kin_tape.hip -- the kernels declared in kp_kin_tape.hpp (see there).  Every forward quantity a gradient needs is recomputed from the forward
-// call's inputs with the forward kernel's own expressions (kp_obs_kernels.hpp: k_kin_advance; kp_rollout_kernels.hpp: k_obs_ar), so the tape holds
-// tensors the roll-out keeps anyway and no kernel-private state.
+// call's inputs with the forward kernel's own expressions (kp_obs_kernels.hpp: k_kin_advance; kp_obs_ar_row.hpp: obs_ar_row) and the helpers those
+// kernels use (kp_quat.hpp), so the tape holds tensors the roll-out keeps anyway and no kernel-private state.
 //
 // Two identities carry every rotation gradient:
 //   * R(r / |r|) with r -> r + dr turns its image by the world rotation vector dphi, (0, dphi) = 2 (du (x) u^-1), u = r / |r|.  A cotangent that meets dphi as
 //     dphi . tau (a torque) is therefore the quaternion gradient 2 (0, tau) (x) u / |r| -- orthogonal to u: no radial component (k_fk_wbpos_grad's root rule);
 //   * p = a (x) b: cotangent g gives g (x) conj(b) for a and conj(a) (x) g for b.
 #include "kp_kin_tape.hpp"
+#include "kp_quat.hpp"
 
 namespace kp {
 
 namespace {
 
-constexpr float KT_PI = 3.14159265358979f, KT_2PI = 6.28318530717959f;      // the constants k_kin_advance wraps with
 constexpr int KT_HEAD = 13;                                                  // body "Head" of the SMPL tree
 
-__device__ __forceinline__ Q4 kt_ldq(const float* p) { return Q4{p[0], p[1], p[2], p[3]}; }
-__device__ __forceinline__ void kt_stq(float* p, Q4 q) { p[0] = q.w; p[1] = q.x; p[2] = q.y; p[3] = q.z; }
-__device__ __forceinline__ Q4 kt_conj(Q4 q) { return Q4{q.w, -q.x, -q.y, -q.z}; }
 __device__ __forceinline__ Q4 operator+(Q4 a, Q4 b) { return Q4{a.w + b.w, a.x + b.x, a.y + b.y, a.z + b.z}; }
 __device__ __forceinline__ Q4 operator*(float s, Q4 a) { return Q4{s * a.w, s * a.x, s * a.y, s * a.z}; }
 __device__ __forceinline__ float kt_dot4(Q4 a, Q4 b) { return a.w * b.w + a.x * b.x + a.y * b.y + a.z * b.z; }
 __device__ __forceinline__ V3 kt_vec(Q4 q) { return v3(q.x, q.y, q.z); }
-// quaternion_matrix as the forward kernels evaluate it (kp_obs_kernels.hpp: q_matrix): the rotation of q / |q|
-__device__ __forceinline__ void kt_matrix(Q4 q, float* m) {
-    const float n = q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z;
-    if (n < 8.881784197001252e-16f) { m[0] = m[4] = m[8] = 1.f; m[1] = m[2] = m[3] = m[5] = m[6] = m[7] = 0.f; return; }
-    const float s = sqrtf(2.0f / n);
-    const float w = q.w * s, x = q.x * s, y = q.y * s, z = q.z * s;
-    m[0] = 1.f - y * y - z * z; m[1] = x * y - z * w; m[2] = x * z + y * w;
-    m[3] = x * y + z * w; m[4] = 1.f - x * x - z * z; m[5] = y * z - x * w;
-    m[6] = x * z - y * w; m[7] = y * z + x * w; m[8] = 1.f - x * x - y * y;
-}
-__device__ __forceinline__ V3 kt_tmulmat(const float* m, V3 v) {
-    return V3{m[0] * v.x + m[3] * v.y + m[6] * v.z, m[1] * v.x + m[4] * v.y + m[7] * v.z, m[2] * v.x + m[5] * v.y + m[8] * v.z};
-}
 // the quaternion gradient of a torque on R(r / |r|): u = r / |r|, inv_n = 1 / |r|
 __device__ __forceinline__ Q4 kt_torque_grad(V3 tau, Q4 u, float inv_n) { return inv_n * qmul(Q4{0.f, 2.0f * tau.x, 2.0f * tau.y, 2.0f * tau.z}, u); }
 // get_heading_q of q as a turn about z by theta = 2 atan2(z, w): cos, sin, and d theta / d (w, z)
@@ -65,7 +49,7 @@ __global__ __launch_bounds__(128) void k_kin_advance_grad(KinAdvanceGradArgs A) 
     const float dt = A.dt, idt = 1.0f / dt;
 #define KT_GN(i) (gn ? gn[i] : 0.f)
 #define KT_GV(i) (gv ? gv[i] : 0.f)
-    const Q4 rot = kt_ldq(q + 3);
+    const Q4 rot = ldq(q + 3);
     // ---- linear part: next.xy = q.xy + dt Rz(heading) a[74:76], v.xy = (next.xy - q.xy) / dt; next.z = a[0], v.z = (a[0] - q.z) / dt
     const KtHeading H = kt_heading(rot);
     const float glx = (KT_GN(0) + KT_GV(0) * idt) * dt, gly = (KT_GN(1) + KT_GV(1) * idt) * dt;
@@ -78,7 +62,7 @@ __global__ __launch_bounds__(128) void k_kin_advance_grad(KinAdvanceGradArgs A) 
     for (int j = 0; j < D_NU; j++) { const float g = KT_GV(6 + j) * idt; oa[5 + j] = KT_GN(7 + j) + g; oq[7 + j] = -g; }
     // ---- angular part, forward (k_kin_advance's expressions)
     float m[9];
-    kt_matrix(rot, m);
+    q_matrix(rot, m);
     const V3 angv = mulmat(m, v3(a[77], a[78], a[79]));
     const V3 ev = dt * angv;
     const float ang = sqrtf(dot(ev, ev));
@@ -90,7 +74,7 @@ __global__ __launch_bounds__(128) void k_kin_advance_grad(KinAdvanceGradArgs A) 
     const float nn = sqrtf(kt_dot4(nraw, nraw));
     const Q4 nr = (1.0f / nn) * nraw;
     const float c2 = kt_dot4(rot, rot), cn = sqrtf(c2);
-    const Q4 rinv = (1.0f / c2) * kt_conj(rot);
+    const Q4 rinv = (1.0f / c2) * qconj(rot);
     const Q4 qrel = qmul(nr, rinv);
     const Q4 u = (1.0f / cn) * rot;
     const float sn = sqrtf(qrel.x * qrel.x + qrel.y * qrel.y + qrel.z * qrel.z);
@@ -101,8 +85,8 @@ __global__ __launch_bounds__(128) void k_kin_advance_grad(KinAdvanceGradArgs A) 
         const V3 g_rv = qrot(u, v3(KT_GV(3), KT_GV(4), KT_GV(5)));     // wv = R(u)^T rv
         const V3 axis = (1.0f / sn) * kt_vec(qrel);
         float angle = 2.0f * atan2f(sn, qrel.w);
-        if (angle > KT_PI) angle -= KT_2PI;
-        if (angle < -KT_PI) angle += KT_2PI;
+        if (angle > KP_PI) angle -= KP_2PI;
+        if (angle < -KP_PI) angle += KP_2PI;
         const V3 rv = (angle * idt) * axis;
         grot = grot + kt_torque_grad(cross(g_rv, rv), u, 1.0f / cn);
         const float g_angle = idt * dot(axis, g_rv);
@@ -110,13 +94,13 @@ __global__ __launch_bounds__(128) void k_kin_advance_grad(KinAdvanceGradArgs A) 
         const float d = sn * sn + qrel.w * qrel.w;                     // atan2(sn, w): d / d sn = w / d, d / d w = -sn / d
         const V3 g_xyz = (1.0f / sn) * (g_axis - dot(axis, g_axis) * axis) + (g_angle * 2.0f * qrel.w / d) * axis;
         const Q4 g_qrel = Q4{-g_angle * 2.0f * sn / d, g_xyz.x, g_xyz.y, g_xyz.z};
-        gnr = gnr + qmul(g_qrel, kt_conj(rinv));
-        const Q4 h = qmul(kt_conj(nr), g_qrel);                        // cotangent of rinv = conj(rot) / |rot|^2
-        grot = grot + (1.0f / c2) * kt_conj(h) + (-2.0f * kt_dot4(h, rinv) / c2) * rot;
+        gnr = gnr + qmul(g_qrel, qconj(rinv));
+        const Q4 h = qmul(qconj(nr), g_qrel);                          // cotangent of rinv = conj(rot) / |rot|^2
+        grot = grot + (1.0f / c2) * qconj(h) + (-2.0f * kt_dot4(h, rinv) / c2) * rot;
     }
     const Q4 graw = (1.0f / nn) * (gnr + (-kt_dot4(nr, gnr)) * nr);   // next = nraw / |nraw|
-    const Q4 gex = qmul(graw, kt_conj(rot));
-    grot = grot + qmul(kt_conj(ex), graw);
+    const Q4 gex = qmul(graw, qconj(rot));
+    grot = grot + qmul(qconj(ex), graw);
     V3 g_angv = v3(0.f, 0.f, 0.f);
     if (!guard) {
         // ex = (cos(ang / 2), f ev), f = sin(ang / 2) / ang; f' next to 0 from its series (the closed form cancels)
@@ -125,9 +109,9 @@ __global__ __launch_bounds__(128) void k_kin_advance_grad(KinAdvanceGradArgs A) 
         const V3 gx = kt_vec(gex);
         g_angv = dt * (f * gx + (-0.5f * hs * gex.w + fp * dot(ev, gx)) * nh);
     }
-    st3(oa + 77, kt_tmulmat(m, g_angv));
+    st3(oa + 77, tmulmat(m, g_angv));
     grot = grot + kt_torque_grad(cross(angv, g_angv), u, 1.0f / cn);
-    kt_stq(oq + 3, grot);
+    stq(oq + 3, grot);
 #undef KT_GN
 #undef KT_GV
 }
@@ -143,15 +127,15 @@ __global__ __launch_bounds__(64) void k_obs_ar_grad(ObsArGradArgs A) {
     const float* q = A.qpos + (size_t)e * D_NQ;
     float* oq = A.g_qpos + (size_t)e * D_NQ;
     // local pose: height, de_heading(root) = inverse(heading(root)) (x) root, joint angles
-    const Q4 rq = kt_ldq(q + 3);
-    const Q4 gd = kt_ldq(g + 1);
+    const Q4 rq = ldq(q + 3);
+    const Q4 gd = ldq(g + 1);
     float gw, gz;
-    kt_inv_heading_grad(rq, qmul(gd, kt_conj(rq)), gw, gz);
+    kt_inv_heading_grad(rq, qmul(gd, qconj(rq)), gw, gz);
     const float rn = sqrtf(rq.w * rq.w + rq.z * rq.z);
     Q4 gr = qmul(Q4{rq.w / rn, 0.f, 0.f, rq.z / rn}, gd);
     gr.w += gw; gr.z += gz;
     oq[0] = 0.f; oq[1] = 0.f; oq[2] = g[0];
-    kt_stq(oq + 3, gr);
+    stq(oq + 3, gr);
     for (int j = 0; j < D_NU; j++) oq[7 + j] = g[5 + j];
     if (VEL) {
         float* ov = A.g_qvel + (size_t)e * D_NV;
@@ -159,7 +143,7 @@ __global__ __launch_bounds__(64) void k_obs_ar_grad(ObsArGradArgs A) {
     }
     // the head's position and world quaternion
     const V3 hpos = ld3(A.wbpos + (size_t)e * 72 + 3 * KT_HEAD);
-    const Q4 hrot = kt_ldq(A.wbquat + (size_t)e * 96 + 4 * KT_HEAD);
+    const Q4 hrot = ldq(A.wbquat + (size_t)e * 96 + 4 * KT_HEAD);
     const KtHeading H = kt_heading(hrot);
     V3 ghp = v3(0.f, 0.f, 0.f);
     Q4 ghq = Q4{0.f, 0.f, 0.f, 0.f};
@@ -176,20 +160,20 @@ __global__ __launch_bounds__(64) void k_obs_ar_grad(ObsArGradArgs A) {
         t = t < 0 ? 0 : (t >= A.T ? A.T - 1 : t);
         const float* hp = A.head_pose + (r * A.T + t) * 7;
         pos_block(ld3(hp) - hpos, ld3(g + O_DIFF));
-        const Q4 th = kt_ldq(hp + 3);                                  // diff_hrot = inverse(t_hrot) (x) hrot, inverse = conj / dot
-        ghq = ghq + qmul((1.0f / kt_dot4(th, th)) * th, kt_ldq(g + O_DIFF + 3));
+        const Q4 th = ldq(hp + 3);                                     // diff_hrot = inverse(t_hrot) (x) hrot, inverse = conj / dot
+        ghq = ghq + qmul((1.0f / kt_dot4(th, th)) * th, ldq(g + O_DIFF + 3));
     }
     float gob[7];
     for (int k = 0; k < 7; k++) gob[k] = g[O_OBJ + k] + (A.g_obj ? A.g_obj[(size_t)e * 7 + k] : 0.f);
     const float* oh = A.action_one_hot + r * 4;
     const float ohs = oh[0] + oh[1] + oh[2] + oh[3];
     V3 opos = v3(0.f, 0.f, 0.f); Q4 orot = Q4{1.f, 0.f, 0.f, 0.f};
-    if (ohs != 0.f && A.obj_qpos) { const float* ob = A.obj_qpos + (size_t)e * 7; opos = ld3(ob); orot = kt_ldq(ob + 3); }
+    if (ohs != 0.f && A.obj_qpos) { const float* ob = A.obj_qpos + (size_t)e * 7; opos = ld3(ob); orot = ldq(ob + 3); }
     pos_block(opos - hpos, v3(gob[0], gob[1], gob[2]));
-    kt_inv_heading_grad(hrot, qmul(Q4{gob[3], gob[4], gob[5], gob[6]}, kt_conj(orot)), gw, gz);      // inverse(heading(hrot)) (x) orot
+    kt_inv_heading_grad(hrot, qmul(Q4{gob[3], gob[4], gob[5], gob[6]}, qconj(orot)), gw, gz);      // inverse(heading(hrot)) (x) orot
     ghq.w += gw; ghq.z += gz;
     st3(A.g_hpos + (size_t)e * 3, ghp);
-    kt_stq(A.g_hquat + (size_t)e * 4, ghq);
+    stq(A.g_hquat + (size_t)e * 4, ghq);
 }
 
 // ---------------------------------------------------------------- (d k_target_fk)^T for wbpos and the head's world quaternion
@@ -217,7 +201,7 @@ __global__ __launch_bounds__(256) void k_fk_head_grad(FkHeadGradArgs A) {
         F = F + g; M = M + cross(ld3(sp[w] + 3 * j) - pb, g);
     }
     if (A.g_hquat && b <= KT_HEAD && KT_HEAD < b + nb) {
-        const Q4 t = qmul(kt_ldq(A.g_hquat + (size_t)e * 4), kt_conj(kt_ldq(A.wbquat + (size_t)e * 96 + 4 * KT_HEAD)));
+        const Q4 t = qmul(ldq(A.g_hquat + (size_t)e * 4), qconj(ldq(A.wbquat + (size_t)e * 96 + 4 * KT_HEAD)));
         M = M + 0.5f * kt_vec(t);
     }
     const float* q = A.qpos + (size_t)e * D_NQ;
@@ -226,13 +210,13 @@ __global__ __launch_bounds__(256) void k_fk_head_grad(FkHeadGradArgs A) {
     if (b == 0) {
         const V3 f0 = F + ld3(sg[w]);
         const float qn = sqrtf(q[3] * q[3] + q[4] * q[4] + q[5] * q[5] + q[6] * q[6]);
-        const Q4 G = kt_torque_grad(M, kt_ldq(A.wbquat + (size_t)e * 96), 1.0f / qn);
+        const Q4 G = kt_torque_grad(M, ldq(A.wbquat + (size_t)e * 96), 1.0f / qn);
         const float r[7] = {f0.x, f0.y, f0.z, G.w, G.x, G.y, G.z};
         for (int i = 0; i < 7; i++) o[i] = r[i] + (add ? add[i] : 0.f);
     } else {
         const int p = A.parent[b];
         float R[9];
-        kt_matrix(kt_ldq(A.wbquat + (size_t)e * 96 + 4 * p), R);
+        q_matrix(ldq(A.wbquat + (size_t)e * 96 + 4 * p), R);
         const int c = 7 + 3 * (b - 1);
         const float tz = q[c], ty = q[c + 1];
         float sz, cz, sy, cy;

@@ -1,10 +1,9 @@
 // kp_obs_ctx.hpp -- the kinematic model's observation row under `use_context` / `use_of` (config/statear/kin_only.yml, use_of.yml;
-// kin_poly/models/traj_ar_smpl_net.py:226-230, 284-285; humanoid_ar_v1.py:151-155) and the GRU step of a state wider than the hidden state:
+// kin_poly/models/traj_ar_smpl_net.py:226-230, 284-285; humanoid_ar_v1.py:151-155):
 //
 //   k_obs_ar_ctx         one launch writes [context block H | k_obs_ar's row W | of block F] at pitch H + W + F: the context GRU's hidden state at the
-//                        row's frame, the base observation with k_obs_ar's expressions (kp_rollout_kernels.hpp; the words are kp_sim_obs_ar's), the
+//                        row's frame, the base observation as obs_ar_row writes it (kp_obs_ar_row.hpp: k_obs_ar's text, the words are kp_sim_obs_ar's), the
 //                        frame's image feature.  A null context table writes zeros (the reference's row before init_states)
-//   k_gru_cell_step_wide k_gru_cell_step (kp_policy_kernels.hpp) whose [state | h'] copy covers D > H columns; gate math and h' are that kernel's
 //   k_obs_ctx_grad       the context block's cotangent: the first H columns of grad_obs as a contiguous [n, H] slab (the `of` block is data)
 //   k_ctx_rows_write     the sampler's ring refill of the two wide context tables (kp_ctx_rows_write): m drawn clips' context sequence (time-major
 //                        [T', m, H], what the GRU step writes) and image features ([m, T', F]) into row-major tables [R, T, .] at scattered rows, clips
@@ -13,7 +12,8 @@
 //                        row; ring_refill_plan never produces them); a row outside [0, R) is refused by the entry point and skipped by the kernel
 //
 // fp32, rows independent, no LDS, no cross-lane traffic, no atomics.  The kernels live in their own translation unit (kp_obs_ctx.hip) for the reason
-// kp_pose_contacts.hpp gives: the step kernels' code generation must not move.
+// kp_pose_contacts.hpp gives: the step kernels' code generation must not move.  Inline device math is shared with kp_sim.hip's kernels through
+// kp_quat.hpp and kp_obs_ar_row.hpp, which define no kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,9 +33,6 @@ struct ObsArCtxArgs {
 };
 
 hipError_t launch_obs_ar_ctx(const ObsArCtxArgs& A, hipStream_t stream);
-// D > H, xcat and state non-null
-hipError_t launch_gru_cell_step_wide(int n, int H, int D, const float* gi, const float* gh, const float* b_ih, const float* b_hh, const float* h_in, const float* state,
-                                     float* h_out, float* xcat, hipStream_t stream);
 // grad_ctx [n, H] <- grad_obs[:, :H] of rows `pitch` floats apart
 hipError_t launch_obs_ctx_grad(int n, int H, const float* grad_obs, int pitch, float* grad_ctx, hipStream_t stream);
 

@@ -4,63 +4,11 @@
 //   k_obs_cc       HumanoidEnv.get_full_obs / _v1 / _v2 (+ZFilter) per the UHC config, one body, 20 layouts   uhc/envs/humanoid_im.py:105-318,
 //                  zfilter.py:58-67; uhc.yml's is get_full_obs_v1 (:144-233), entry kernel k_obs_cc_uhc
 //   k_bquat        HumanoidEnv.get_body_quat            uhc/envs/humanoid_im.py:342-354
-// Quaternion helpers restate uhc/khrylib/utils/math.py:102-198 and transformation.py (Gohlke).
+// The quaternion helpers (uhc/khrylib/utils/math.py:102-198 and transformation.py, Gohlke) are kp_quat.hpp's.
 #pragma once
-#include "kp_device.hpp"
+#include "kp_quat.hpp"
 
 namespace kp {
-
-// ---- reference quaternion helpers (w,x,y,z); these do NOT assume unit quaternions where the reference does not
-__device__ __forceinline__ Q4 q_inverse(Q4 q) {  // quaternion_inverse: conj / dot
-    float n = q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z;
-    return Q4{q.w / n, -q.x / n, -q.y / n, -q.z / n};
-}
-__device__ __forceinline__ void q_matrix(Q4 q, float* m) {  // quaternion_matrix: normalises by dot, identity if ~0
-    float n = q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z;
-    if (n < 8.881784197001252e-16f) { m[0] = m[4] = m[8] = 1.f; m[1] = m[2] = m[3] = m[5] = m[6] = m[7] = 0.f; return; }
-    float s = sqrtf(2.0f / n);
-    float w = q.w * s, x = q.x * s, y = q.y * s, z = q.z * s;
-    m[0] = 1.f - y * y - z * z; m[1] = x * y - z * w; m[2] = x * z + y * w;
-    m[3] = x * y + z * w; m[4] = 1.f - x * x - z * z; m[5] = y * z - x * w;
-    m[6] = x * z - y * w; m[7] = y * z + x * w; m[8] = 1.f - x * x - y * y;
-}
-__device__ __forceinline__ V3 q_mul_vec(Q4 q, V3 v) { float m[9]; q_matrix(q, m); return mulmat(m, v); }            // quat_mul_vec
-__device__ __forceinline__ V3 q_tmul_vec(Q4 q, V3 v) {                                                              // transform_vec(.., 'root')
-    float m[9]; q_matrix(q, m);
-    return V3{m[0] * v.x + m[3] * v.y + m[6] * v.z, m[1] * v.x + m[4] * v.y + m[7] * v.z, m[2] * v.x + m[5] * v.y + m[8] * v.z};
-}
-__device__ __forceinline__ Q4 q_heading(Q4 q) {  // get_heading_q
-    float n = sqrtf(q.w * q.w + q.z * q.z);
-    return Q4{q.w / n, 0.f, 0.f, q.z / n};
-}
-__device__ __forceinline__ float heading_angle(Q4 q) {  // get_heading
-    float w = q.w, z = q.z;
-    if (z < 0.f) { w = -w; z = -z; }
-    // 2 acos(w / |(w, z)|) with z >= 0, as the angle of the point (w, z): acos next to 1 would turn the 6e-8 of an fp32 cosine into 1e-4 rad
-    // for a heading of 1e-3 rad (the reference works in fp64)
-    return 2.0f * atan2f(fabsf(z), w);
-}
-__device__ __forceinline__ Q4 q_from_expmap(V3 e) {  // quat_from_expmap + quaternion_about_axis
-    float angle = sqrtf(dot(e, e));
-    V3 axis = angle < 1e-12f ? v3(1.f, 0.f, 0.f) : (1.0f / angle) * e;
-    float sn, cs; sincosf(0.5f * angle, &sn, &cs);
-    float ql = sqrtf(dot(axis, axis));
-    float k = ql > 8.881784197001252e-16f ? sn / ql : 1.0f;
-    return Q4{cs, axis.x * k, axis.y * k, axis.z * k};
-}
-// local hinge rotation: Gohlke quaternion_from_euler(tz, ty, tx, 'rzyx') = qz (x) qy (x) qx
-__device__ __forceinline__ Q4 q_euler_rzyx(float tz, float ty, float tx) {
-    float sz, cz, sy, cy, sx, cx;
-    sincosf(0.5f * tz, &sz, &cz); sincosf(0.5f * ty, &sy, &cy); sincosf(0.5f * tx, &sx, &cx);
-    return qmul(qmul(Q4{cz, 0.f, 0.f, sz}, Q4{cy, 0.f, sy, 0.f}), Q4{cx, sx, 0.f, 0.f});
-}
-// the reference's "bquat" quirk: quaternion_from_euler(a0, a1, a2) with default 'sxyz' on (tz, ty, tx)
-__device__ __forceinline__ Q4 q_euler_sxyz(float ai, float aj, float ak) {
-    float si, ci, sj, cj, sk, ck;
-    sincosf(0.5f * ai, &si, &ci); sincosf(0.5f * aj, &sj, &cj); sincosf(0.5f * ak, &sk, &ck);
-    float cc = ci * ck, cs = ci * sk, sc = si * ck, ss = si * sk;
-    return Q4{cj * cc + sj * ss, cj * sc - sj * cs, cj * ss + sj * cc, cj * cs - sj * sc};
-}
 
 // ---------------------------------------------------------------- step_ar: one thread per env
 __global__ void k_step_kin(int n, const float* __restrict__ qpos, const float* __restrict__ act, float* __restrict__ next_qpos, float dt) {
@@ -117,8 +65,8 @@ __global__ void k_kin_advance(int n, const float* __restrict__ qpos, const float
     sn = fmaxf(sn, 1e-30f);
     const V3 axis = small ? v3(1.f, 0.f, 0.f) : v3(qrel.x / sn, qrel.y / sn, qrel.z / sn);
     float angle = small ? 0.0f : 2.0f * atan2f(sn, qrel.w);
-    if (angle > 3.14159265358979f) angle -= 6.28318530717959f;
-    if (angle < -3.14159265358979f) angle += 6.28318530717959f;
+    if (angle > KP_PI) angle -= KP_2PI;
+    if (angle < -KP_PI) angle += KP_2PI;
     const V3 rv = (angle * idt) * axis;
     // transform_vec_batch(rv, cur, 'root'): R(cur / |cur|)^T rv
     const float cn = sqrtf(c2);
@@ -334,8 +282,8 @@ __device__ __forceinline__ void obs_cc_body(const ObsCcArgs& A, const float* __r
             V3 v = q_tmul_vec(crq, q_tmul_vec(rq, v3(qvel[0], qvel[1], qvel[2])));  // transformed twice (:150, :173)
             ob[226] = v.x; ob[227] = v.y; ob[228] = v.z;
             float rel_h = heading_angle(trq) - heading_angle(crq);
-            if (rel_h > 3.14159265358979f) rel_h -= 6.28318530717959f;
-            if (rel_h < -3.14159265358979f) rel_h += 6.28318530717959f;
+            if (rel_h > KP_PI) rel_h -= KP_2PI;
+            if (rel_h < -KP_PI) rel_h += KP_2PI;
             ob[P - 3] = rel_h;
             V3 rp = q_tmul_vec(crq, v3(trq.w, trq.x, trq.y) - root);  // sic: quaternion components used as a position (:187; v2 keeps it, :265)
             ob[P - 2] = rp.x; ob[P - 1] = rp.y;

@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kp_quat.hpp"
+
 namespace kp {
 
 typedef float kp_f32x4 __attribute__((ext_vector_type(4)));
@@ -121,8 +123,6 @@ __global__ __launch_bounds__(64 * MCP_WAVES) void k_mcp_tail(int n, int K, int J
     }
 }
 
-__device__ __forceinline__ float kp_sigmoid(float x) { return 1.0f / (1.0f + __expf(-x)); }
-
 // gi = x W_ih^T, gh = h W_hh^T WITHOUT their biases (the plain GEMMs whose library solutions are pinned in assets/tunableop_gfx950.csv);
 // r = sigma(gi_r + b_ir + gh_r + b_hr), z likewise, n = tanh(gi_n + b_in + r (gh_n + b_hn)), h' = (1 - z) n + z h        (torch.nn.GRUCell)
 // h_out [n, H] (may alias h_in); xcat [n, D + H] (optional) <- [state | h'].
@@ -140,7 +140,8 @@ __global__ void k_gru_cell_step(int n, int H, int D, const float* __restrict__ g
     if (xcat) {
         float* xr = xcat + (size_t)e * (D + H);
         xr[D + j] = h;
-        if (j < D) xr[j] = state[(size_t)e * D + j];
+        const float* s = state + (size_t)e * D;
+        for (int c = j; c < D; c += H) xr[c] = s[c];      // thread (e, j) copies columns j, j + H, ...: D may exceed H (use_context / use_of)
     }
 }
 

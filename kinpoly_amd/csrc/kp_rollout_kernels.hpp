@@ -9,16 +9,9 @@
 // One thread or one 32-lane group per environment: these are O(100)-flop gathers; the physics kernel dominates the step.
 #pragma once
 #include "kp_obs_kernels.hpp"
+#include "kp_obs_ar_row.hpp"
 
 namespace kp {
-
-struct CtxDev {  // mirrors kp_ctx in include/kinpoly_sim.h
-    int T;
-    const float *head_pose, *head_vels, *obj_rel, *action_one_hot, *gt_bquat, *gt_wbpos, *obj_qpos;
-    const int* cur_t;
-    const int* row;      // optional: env e reads context row row[e] of the [R, T, .] arrays (null: row e)
-    __device__ __forceinline__ size_t r(int e) const { return row ? (size_t)row[e] : (size_t)e; }
-};
 
 // action_index_map of HumanoidAREnv (humanoid_ar_v1.py:37-39): first column of the action's object(s) inside data.qpos[76:111]
 // (sit -> chair 0, push -> box 7 (+ table 14), avoid -> Can 21, step -> step 28); -1 when the one-hot is all zero (no object, :465-466)
@@ -29,79 +22,14 @@ __device__ __forceinline__ int obj_action_start(const float* one_hot) {
     return a < 0 ? -1 : (a == 0 ? 0 : (a == 1 ? 7 : (a == 2 ? 21 : 28)));
 }
 
-__device__ __forceinline__ V3 tv_heading(V3 v, Q4 q) { return q_tmul_vec(q_heading(q), v); }  // transform_vec(v, q, 'heading')
-
-// The observation's switches (humanoid_ar_v1.py:183-201; a statear yml's use_vel / use_head / use_action).  Blocks in the reference's order:
-//   [0, 74) height, de-headed root quaternion, joint angles | VEL: 75 qvel (data.qvel[:75], :184-185) | HEAD: diff_hpos 3, diff_hrot 4 (:187-189) |
-//   predicted object relative to head 7 (:191-192) | HEAD: t_havel 3, t_hlvel 3, t_obj_relative_head 7 (:194-198) | ACTION: one-hot 4 (:200-201)
-// D is the row width: 105 / 101 for <false, true, .> (kin_poly.yml / kin_poly_wo_action.yml), 180 / 176 with VEL, 85 / 81 without HEAD, 160 / 156 with VEL and without HEAD.
-template <bool VEL, bool HEAD, bool ACTION>
-struct ObsArLayout {
-    static constexpr int O_VEL = 74, O_DIFF = O_VEL + (VEL ? 75 : 0), O_OBJ = O_DIFF + (HEAD ? 7 : 0), O_TGT = O_OBJ + 7, O_ACT = O_TGT + (HEAD ? 13 : 0),
-                         D = O_ACT + (ACTION ? 4 : 0);
-};
-// 32 lanes per env, 8 envs per 256-thread block (k_term_reward's mapping): the 69 joint angles and the 75 velocities are copied lane-strided, so a
-// wavefront reads and writes runs of 32 consecutive floats of two consecutive rows; the five short blocks go to lanes 0 .. 4 of the env, each with
-// the same expressions in every layout (a block two layouts share is equal bit for bit).  No LDS, no cross-lane traffic.
+// 32 lanes per env, 8 envs per 256-thread block (k_term_reward's mapping), so a wavefront reads and writes runs of 32 consecutive floats of two
+// consecutive rows; the row itself is obs_ar_row (kp_obs_ar_row.hpp).
 template <bool VEL, bool HEAD, bool ACTION>
 __global__ __launch_bounds__(256) void k_obs_ar(int n, CtxDev C, const float* __restrict__ qpos, const float* __restrict__ qvel,
                                                  const float* __restrict__ xpos, const float* __restrict__ xquat, float* __restrict__ out) {
-    using L = ObsArLayout<VEL, HEAD, ACTION>;
     const int l = threadIdx.x & 31, e = blockIdx.x * 8 + (threadIdx.x >> 5);
     if (e >= n) return;
-    const float* q = qpos + (size_t)e * D_NQ;
-    float* o = out + (size_t)e * L::D;
-    for (int j = l; j < D_NU; j += 32) o[5 + j] = q[7 + j];
-    if (VEL) {
-        const float* v = qvel + (size_t)e * D_NV;
-        for (int j = l; j < D_NV; j += 32) o[L::O_VEL + j] = v[j];
-    }
-    if (l > 4) return;
-    if (l == 0) {
-        Q4 rq = Q4{q[3], q[4], q[5], q[6]};
-        Q4 dh = qmul(q_inverse(q_heading(rq)), rq);  // de_heading(qpos[3:7]) (:140-141)
-        o[0] = q[2]; o[1] = dh.w; o[2] = dh.x; o[3] = dh.y; o[4] = dh.z;
-        return;
-    }
-    int t = C.cur_t[e];
-    t = t < 0 ? 0 : (t >= C.T ? C.T - 1 : t);
-    const float* oh = C.action_one_hot + C.r(e) * 4;
-    if (l == 4) {
-        if (ACTION) for (int k = 0; k < 4; k++) o[L::O_ACT + k] = oh[k];
-        return;
-    }
-    if (l == 3) {
-        if (HEAD) {
-            const float* hv = C.head_vels + (C.r(e) * C.T + t) * 6;
-            const float* orl = C.obj_rel + (C.r(e) * C.T + t) * 7;
-            float* g = o + L::O_TGT;
-            g[0] = hv[3]; g[1] = hv[4]; g[2] = hv[5];
-            g[3] = hv[0]; g[4] = hv[1]; g[5] = hv[2];
-            for (int k = 0; k < 7; k++) g[6 + k] = orl[k];
-        }
-        return;
-    }
-    const int hb = 13;
-    V3 hpos = ld3(xpos + (size_t)e * 72 + 3 * hb);
-    const float* hq4 = xquat + (size_t)e * 96 + 4 * hb;
-    Q4 hrot = Q4{hq4[0], hq4[1], hq4[2], hq4[3]};
-    if (l == 1) {
-        if (HEAD) {
-            const float* hp = C.head_pose + (C.r(e) * C.T + t) * 7;
-            st3(o + L::O_DIFF, tv_heading(ld3(hp) - hpos, hrot));
-            Q4 dr = qmul(q_inverse(Q4{hp[3], hp[4], hp[5], hp[6]}), hrot);
-            float* g = o + L::O_DIFF + 3;
-            g[0] = dr.w; g[1] = dr.x; g[2] = dr.y; g[3] = dr.z;
-        }
-        return;
-    }
-    float ohs = oh[0] + oh[1] + oh[2] + oh[3];
-    V3 opos = v3(0.f, 0.f, 0.f); Q4 orot = Q4{1.f, 0.f, 0.f, 0.f};   // get_obj_qpos: [0,0,0,1,0,0,0] when no action (:465-466)
-    if (ohs != 0.f && C.obj_qpos) { const float* ob = C.obj_qpos + (size_t)e * 7; opos = ld3(ob); orot = Q4{ob[3], ob[4], ob[5], ob[6]}; }
-    st3(o + L::O_OBJ, tv_heading(opos - hpos, hrot));
-    Q4 ol = qmul(q_inverse(q_heading(hrot)), orot);
-    float* g = o + L::O_OBJ + 3;
-    g[0] = ol.w; g[1] = ol.x; g[2] = ol.y; g[3] = ol.z;
+    obs_ar_row<VEL, HEAD, ACTION>(C, e, l, qpos, qvel, xpos, xquat, out + (size_t)e * ObsArLayout<VEL, HEAD, ACTION>::D);
 }
 
 // The 105 / 101 layouts (<false, true, ACTION>) with one thread per env and hand-numbered columns: the kernel these two rows were first written by, and
@@ -380,8 +308,6 @@ __global__ void k_gae(int n, int T, const float* __restrict__ rewards, const flo
 // and these two kernels do everything else of a step, forward and backward, in one pass over [N, H]:
 //     r = sigma(gi_r + gh_r), z = sigma(gi_z + gh_z), n = tanh(gi_n + r gh_n), h = (1 - z) n + z hm_prev     (torch.nn.GRUCell)
 // hm = h masked by the NEXT step's episode-start flag, ready to be the next step's GEMM input.
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
-
 // PolicyMCP's mixing stage (uhc/core/policy_mcp.py:30-38) in one pass: weight = softmax(composer output) over the K primitives,
 // mean = sum_k weight_k * prim_k, optionally action = mean + std * noise (select_action, policy.py:12-15).  prim is the third batched GEMM's
 // output in its own layout [K, N, A] (no transpose pass); one thread per (env, action dim), the K <= 16 logits of an env are re-read by its A threads (L1).
@@ -410,7 +336,7 @@ __global__ void k_gru_gates_fwd(int n, int H, const float* __restrict__ gi, cons
     if (i >= (size_t)n * H) return;
     const int e = (int)(i / H), j = (int)(i - (size_t)e * H);
     const float* a = gi + (size_t)e * 3 * H; const float* b = gh + (size_t)e * 3 * H;
-    const float r = sigmoidf_(a[j] + b[j]), z = sigmoidf_(a[H + j] + b[H + j]), nn = tanhf(a[2 * H + j] + r * b[2 * H + j]);
+    const float r = kp_sigmoid(a[j] + b[j]), z = kp_sigmoid(a[H + j] + b[H + j]), nn = tanhf(a[2 * H + j] + r * b[2 * H + j]);
     const float h = (1.0f - z) * nn + z * hm_prev[i];
     h_out[i] = h;
     if (hm_next) hm_next[i] = next_keep ? h * next_keep[e] : h;
@@ -426,7 +352,7 @@ __global__ void k_gru_gates_bwd(int n, int H, const float* __restrict__ gi, cons
     const int e = (int)(i / H), j = (int)(i - (size_t)e * H);
     const float* a = gi + (size_t)e * 3 * H; const float* b = gh + (size_t)e * 3 * H;
     const float ghn = b[2 * H + j];
-    const float r = sigmoidf_(a[j] + b[j]), z = sigmoidf_(a[H + j] + b[H + j]), nn = tanhf(a[2 * H + j] + r * ghn);
+    const float r = kp_sigmoid(a[j] + b[j]), z = kp_sigmoid(a[H + j] + b[H + j]), nn = tanhf(a[2 * H + j] + r * ghn);
     float dh = dh_out ? dh_out[i] : 0.f;
     if (carry) dh += carry[i] * (carry_keep ? carry_keep[e] : 1.0f);
     const float dn = dh * (1.0f - z), dz = dh * (hm_prev[i] - nn);

@@ -1227,9 +1227,15 @@ static void launch_obs_ar(kp_sim* s, const kp_ctx* c, float* out) {
 static void (*const OBS_AR[8])(kp_sim*, const kp_ctx*, float*) = {launch_obs_ar<0>, launch_obs_ar<1>, launch_obs_ar<2>, launch_obs_ar<3>,
                                                                   launch_obs_ar<4>, launch_obs_ar<5>, launch_obs_ar<6>, launch_obs_ar<7>};
 
-int kp_sim_obs_ar(kp_sim* s, const kp_ctx* c, float* out) {
+// the arguments kp_sim_obs_ar and kp_sim_obs_ar_ex share: the handle, the row's context tables, the destination
+static int check_obs_ar_args(const char* who, const kp_sim* s, const kp_ctx* c, const float* out) {
     if (!s || !c || !out || !c->head_pose || !c->head_vels || !c->obj_head_relative_poses || !c->action_one_hot || !c->cur_t || c->T < 1)
-        return fail("kp_sim_obs_ar: bad arguments");
+        return fail(std::string(who) + ": bad arguments");
+    return 0;
+}
+
+int kp_sim_obs_ar(kp_sim* s, const kp_ctx* c, float* out) {
+    if (check_obs_ar_args("kp_sim_obs_ar", s, c, out)) return -1;
     HIP_OK(hipSetDevice(s->device));
     OBS_AR[s->ar_obs_vel | s->ar_obs_head << 1 | s->ar_obs_action << 2](s, c, out);
     return launched();
@@ -1303,30 +1309,39 @@ int kp_pool_advance(int n, int n_slots, const uint8_t* done, int32_t* head, int3
 
 int kp_sim_ar_obs_dim(const kp_sim* s) { return s ? s->ar_obs_dim : -1; }
 
-int kp_rollout_record_pre_w(const kp_record_pre* r, int obs_dim, void* stream) {
-    if (!r || r->n <= 0 || r->T <= 0 || r->t < 0 || r->t >= r->T) return fail("kp_rollout_record_pre: bad arguments");
-    if (!ar_obs_width_known(obs_dim)) return fail("kp_rollout_record_pre: obs_dim must be " KP_AR_OBS_WIDTHS ", got " + std::to_string(obs_dim));
+// The sampler's records, one path per half-step: the source / destination checks and the launch.  The row width is the kernel's argument; every
+// entry point checks its own width first (`who` is the name its errors carry).
+static int record_pre(const char* who, const kp_record_pre* r, int obs_dim, void* stream) {
     if ((r->states && !r->obs) || (r->episode_start && !r->fresh) || (r->curr_qpos && !r->qpos) || (r->meta && !r->row_meta) ||
         (r->gt_target_qpos && (!r->ctx_qpos || !r->cur_t || !r->row_len || r->ctx_T <= 0)))
-        return fail("kp_rollout_record_pre: a destination without its source");
+        return fail(std::string(who) + ": a destination without its source");
     kp::RecordPre R{r->n, r->T, r->t, r->ctx_T, obs_dim, r->obs, r->fresh, r->qpos, r->ctx_qpos, r->row, r->cur_t, r->row_len, r->row_meta,
                     r->states, r->episode_start, r->curr_qpos, r->gt_target_qpos, r->meta};
     hipLaunchKernelGGL(kp::k_record_pre, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
     return launched();
+}
+static int record_post(const char* who, const kp_record_post* r, int obs_dim, void* stream) {
+    if ((r->actions && !r->action) || (r->rewards && !r->reward) || (r->fails && !r->fail) || (r->dones && !r->done) || (r->percents && !r->percent) ||
+        (r->c_infos && !r->c_info) || (r->next_states && !r->obs) || (r->res_qpos && !r->qpos) || (r->cc_actions && !r->cc_action) ||
+        (r->cc_states && !r->cc_state) || (r->v_metas && !r->meta))
+        return fail(std::string(who) + ": a destination without its source");
+    kp::RecordPost R{r->n, r->T, r->t, obs_dim, r->fr_num, r->action, r->reward, r->fail, r->done, r->percent, r->c_info, r->obs, r->qpos, r->cc_action, r->cc_state, r->meta,
+                     r->actions, r->rewards, r->fails, r->dones, r->percents, r->c_infos, r->next_states, r->res_qpos, r->cc_actions, r->cc_states, r->v_metas};
+    hipLaunchKernelGGL(kp::k_record_post, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
+    return launched();
+}
+
+int kp_rollout_record_pre_w(const kp_record_pre* r, int obs_dim, void* stream) {
+    if (!r || r->n <= 0 || r->T <= 0 || r->t < 0 || r->t >= r->T) return fail("kp_rollout_record_pre: bad arguments");
+    if (!ar_obs_width_known(obs_dim)) return fail("kp_rollout_record_pre: obs_dim must be " KP_AR_OBS_WIDTHS ", got " + std::to_string(obs_dim));
+    return record_pre("kp_rollout_record_pre", r, obs_dim, stream);
 }
 int kp_rollout_record_pre(const kp_record_pre* r, void* stream) { return kp_rollout_record_pre_w(r, KP_AR_OBS_DIM, stream); }
 
 int kp_rollout_record_post_w(const kp_record_post* r, int obs_dim, void* stream) {
     if (!r || r->n <= 0 || r->T <= 0 || r->t < 0 || r->t >= r->T) return fail("kp_rollout_record_post: bad arguments");
     if (!ar_obs_width_known(obs_dim)) return fail("kp_rollout_record_post: obs_dim must be " KP_AR_OBS_WIDTHS ", got " + std::to_string(obs_dim));
-    if ((r->actions && !r->action) || (r->rewards && !r->reward) || (r->fails && !r->fail) || (r->dones && !r->done) || (r->percents && !r->percent) ||
-        (r->c_infos && !r->c_info) || (r->next_states && !r->obs) || (r->res_qpos && !r->qpos) || (r->cc_actions && !r->cc_action) ||
-        (r->cc_states && !r->cc_state) || (r->v_metas && !r->meta))
-        return fail("kp_rollout_record_post: a destination without its source");
-    kp::RecordPost R{r->n, r->T, r->t, obs_dim, r->fr_num, r->action, r->reward, r->fail, r->done, r->percent, r->c_info, r->obs, r->qpos, r->cc_action, r->cc_state, r->meta,
-                     r->actions, r->rewards, r->fails, r->dones, r->percents, r->c_infos, r->next_states, r->res_qpos, r->cc_actions, r->cc_states, r->v_metas};
-    hipLaunchKernelGGL(kp::k_record_post, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
-    return launched();
+    return record_post("kp_rollout_record_post", r, obs_dim, stream);
 }
 int kp_rollout_record_post(const kp_record_post* r, void* stream) { return kp_rollout_record_post_w(r, KP_AR_OBS_DIM, stream); }
 
@@ -1363,10 +1378,6 @@ int kp_gru_cell_step(int n, int H, int D, const float* gi, const float* gh, cons
                      float* h_out, float* xcat, void* stream) {
     if (n <= 0 || H <= 0 || !gi || !gh || !b_ih || !b_hh || !h_in || !h_out || (xcat && (!state || D <= 0)))
         return fail("kp_gru_cell_step: bad arguments (the [state | h] row needs state and D > 0)");
-    if (xcat && D > H) {      // a state wider than the hidden state (use_context / use_of): the kernel whose copy loops over the columns
-        HIP_OK(kp::launch_gru_cell_step_wide(n, H, D, gi, gh, b_ih, b_hh, h_in, state, h_out, xcat, (hipStream_t)stream));
-        return 0;
-    }
     const size_t tot = (size_t)n * H;
     hipLaunchKernelGGL(kp::k_gru_cell_step, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, H, D, gi, gh, b_ih, b_hh, h_in, state, h_out, xcat);
     return launched();
@@ -1507,26 +1518,46 @@ int kp_kin_advance_backward(int n, const float* qpos, const float* kin_action, f
     return 0;
 }
 
-int kp_sim_obs_ar_backward(kp_sim* s, const kp_ctx* c, int n_rows, int grad_width, const float* qpos, const float* wbpos, const float* wbquat,
-                           const float* grad_obs, const float* grad_obj_2_head, float* grad_qpos, float* grad_qvel, float* grad_hpos, float* grad_hquat) {
-    if (!s) return fail("kp_sim_obs_ar_backward: null sim");
+// (d obs_ar)^T for both row forms.  The handle and the layout first (`who`: the entry point's name in every message) ...
+static int check_obs_ar_grad(const char* who, const kp_sim* s) {
+    const std::string w(who);
+    if (!s) return fail(w + ": null sim");
     if (!s->ar_obs_head && !s->ar_obs_action)
-        return fail("kp_sim_obs_ar_backward: the " + std::to_string(s->ar_obs_dim) + "-d layout (use_head and use_action both off) has no gradient kernel");
-    if (n_rows < 0 || n_rows > s->n) return fail("kp_sim_obs_ar_backward: n_rows must be in [0, " + std::to_string(s->n) + "], got " + std::to_string(n_rows));
-    if (grad_width != s->ar_obs_dim)
-        return fail("kp_sim_obs_ar_backward: grad_obs is " + std::to_string(grad_width) + " wide, the handle's observation " + std::to_string(s->ar_obs_dim));
-    if (!c || !c->action_one_hot || !c->cur_t || c->T < 1 || (s->ar_obs_head && !c->head_pose)) return fail("kp_sim_obs_ar_backward: null or empty context");
-    if (!qpos || !wbpos || !wbquat || !grad_obs) return fail("kp_sim_obs_ar_backward: null qpos / wbpos / wbquat / grad_obs");
-    if (!grad_qpos || !grad_hpos || !grad_hquat || (s->ar_obs_vel && !grad_qvel)) return fail("kp_sim_obs_ar_backward: null output");
+        return fail(w + ": the " + std::to_string(s->ar_obs_dim) + "-d layout (use_head and use_action both off) has no gradient kernel");
+    return 0;
+}
+static int check_obs_ar_grad_rows(const char* who, const kp_sim* s, int n_rows) {
+    if (n_rows < 0 || n_rows > s->n) return fail(std::string(who) + ": n_rows must be in [0, " + std::to_string(s->n) + "], got " + std::to_string(n_rows));
+    return 0;
+}
+// ... then, once the entry point has checked its row width, the backward of the base block: it sits at column `offset` of grad_obs rows `pitch` floats
+// apart (the plain row: 0 and its own width).  The columns before it are the context block, whose cotangent goes to grad_ctx (kp_obs_ctx.hip).
+static int obs_ar_base_backward(const char* who, kp_sim* s, const kp_ctx* c, int n_rows, int pitch, int offset, const float* qpos, const float* wbpos,
+                                const float* wbquat, const float* grad_obs, const float* grad_obj_2_head, float* grad_qpos, float* grad_qvel,
+                                float* grad_hpos, float* grad_hquat, float* grad_ctx) {
+    const std::string w(who);
+    if (!c || !c->action_one_hot || !c->cur_t || c->T < 1 || (s->ar_obs_head && !c->head_pose)) return fail(w + ": null or empty context");
+    if (!qpos || !wbpos || !wbquat || !grad_obs) return fail(w + ": null qpos / wbpos / wbquat / grad_obs");
+    if (!grad_qpos || !grad_hpos || !grad_hquat || (s->ar_obs_vel && !grad_qvel) || (offset > 0 && !grad_ctx)) return fail(w + ": null output");
     if (n_rows == 0) return 0;
     HIP_OK(hipSetDevice(s->device));
     kp::ObsArGradArgs A{};
-    A.n = n_rows; A.vel = s->ar_obs_vel; A.head = s->ar_obs_head; A.width = s->ar_obs_dim;
+    A.n = n_rows; A.vel = s->ar_obs_vel; A.head = s->ar_obs_head; A.width = pitch;
     A.T = c->T; A.head_pose = c->head_pose; A.action_one_hot = c->action_one_hot; A.obj_qpos = c->obj_qpos; A.cur_t = c->cur_t; A.row = c->row;
-    A.qpos = qpos; A.wbpos = wbpos; A.wbquat = wbquat; A.g_obs = grad_obs; A.g_obj = grad_obj_2_head;
+    A.qpos = qpos; A.wbpos = wbpos; A.wbquat = wbquat; A.g_obs = grad_obs + offset; A.g_obj = grad_obj_2_head;
     A.g_qpos = grad_qpos; A.g_qvel = grad_qvel; A.g_hpos = grad_hpos; A.g_hquat = grad_hquat;
     HIP_OK(kp::launch_obs_ar_grad(A, s->stream));
+    if (offset > 0) HIP_OK(kp::launch_obs_ctx_grad(n_rows, offset, grad_obs, pitch, grad_ctx, s->stream));
     return 0;
+}
+
+int kp_sim_obs_ar_backward(kp_sim* s, const kp_ctx* c, int n_rows, int grad_width, const float* qpos, const float* wbpos, const float* wbquat,
+                           const float* grad_obs, const float* grad_obj_2_head, float* grad_qpos, float* grad_qvel, float* grad_hpos, float* grad_hquat) {
+    const char* who = "kp_sim_obs_ar_backward";
+    if (check_obs_ar_grad(who, s) || check_obs_ar_grad_rows(who, s, n_rows)) return -1;
+    if (grad_width != s->ar_obs_dim)
+        return fail("kp_sim_obs_ar_backward: grad_obs is " + std::to_string(grad_width) + " wide, the handle's observation " + std::to_string(s->ar_obs_dim));
+    return obs_ar_base_backward(who, s, c, n_rows, s->ar_obs_dim, 0, qpos, wbpos, wbquat, grad_obs, grad_obj_2_head, grad_qpos, grad_qvel, grad_hpos, grad_hquat, nullptr);
 }
 
 int kp_sim_fk_head_backward(kp_sim* s, int n_rows, const float* qpos, const float* wbpos, const float* wbquat, const float* grad_wbpos,
@@ -1554,8 +1585,7 @@ static int check_obs_ext(const char* who, const kp_obs_ext* x) {
 }
 
 int kp_sim_obs_ar_ex(kp_sim* s, const kp_ctx* c, const kp_obs_ext* x, float* out) {
-    if (!s || !c || !out || !c->head_pose || !c->head_vels || !c->obj_head_relative_poses || !c->action_one_hot || !c->cur_t || c->T < 1)
-        return fail("kp_sim_obs_ar_ex: bad arguments");
+    if (check_obs_ar_args("kp_sim_obs_ar_ex", s, c, out)) return -1;
     if (check_obs_ext("kp_sim_obs_ar_ex", x)) return -1;
     HIP_OK(hipSetDevice(s->device));
     kp::ObsArCtxArgs A{};
@@ -1572,30 +1602,15 @@ int kp_sim_obs_ar_ex(kp_sim* s, const kp_ctx* c, const kp_obs_ext* x, float* out
 int kp_sim_obs_ar_ex_backward(kp_sim* s, const kp_ctx* c, const kp_obs_ext* x, int n_rows, int grad_width, const float* qpos, const float* wbpos,
                               const float* wbquat, const float* grad_obs, const float* grad_obj_2_head, float* grad_qpos, float* grad_qvel,
                               float* grad_hpos, float* grad_hquat, float* grad_ctx) {
-    if (!s) return fail("kp_sim_obs_ar_ex_backward: null sim");
-    if (!s->ar_obs_head && !s->ar_obs_action)
-        return fail("kp_sim_obs_ar_ex_backward: the " + std::to_string(s->ar_obs_dim) + "-d layout (use_head and use_action both off) has no gradient kernel");
-    if (check_obs_ext("kp_sim_obs_ar_ex_backward", x)) return -1;
-    if (n_rows < 0 || n_rows > s->n) return fail("kp_sim_obs_ar_ex_backward: n_rows must be in [0, " + std::to_string(s->n) + "], got " + std::to_string(n_rows));
+    const char* who = "kp_sim_obs_ar_ex_backward";
+    if (check_obs_ar_grad(who, s) || check_obs_ext(who, x) || check_obs_ar_grad_rows(who, s, n_rows)) return -1;
     const int pitch = x->ctx_dim + s->ar_obs_dim + x->of_dim;
     if (grad_width != pitch)
         return fail("kp_sim_obs_ar_ex_backward: grad_obs is " + std::to_string(grad_width) + " wide, the row " + std::to_string(pitch) + " (" +
                     std::to_string(x->ctx_dim) + " + " + std::to_string(s->ar_obs_dim) + " + " + std::to_string(x->of_dim) + ")");
-    if (!c || !c->action_one_hot || !c->cur_t || c->T < 1 || (s->ar_obs_head && !c->head_pose)) return fail("kp_sim_obs_ar_ex_backward: null or empty context");
-    if (!qpos || !wbpos || !wbquat || !grad_obs) return fail("kp_sim_obs_ar_ex_backward: null qpos / wbpos / wbquat / grad_obs");
-    if (!grad_qpos || !grad_hpos || !grad_hquat || (s->ar_obs_vel && !grad_qvel) || (x->ctx_dim > 0 && !grad_ctx)) return fail("kp_sim_obs_ar_ex_backward: null output");
-    if (n_rows == 0) return 0;
-    HIP_OK(hipSetDevice(s->device));
-    kp::ObsArGradArgs A{};
-    A.n = n_rows; A.vel = s->ar_obs_vel; A.head = s->ar_obs_head; A.width = pitch;      // the base block at its offset, rows `pitch` floats apart
-    A.T = c->T; A.head_pose = c->head_pose; A.action_one_hot = c->action_one_hot; A.obj_qpos = c->obj_qpos; A.cur_t = c->cur_t; A.row = c->row;
-    A.qpos = qpos; A.wbpos = wbpos; A.wbquat = wbquat; A.g_obs = grad_obs + x->ctx_dim; A.g_obj = grad_obj_2_head;
-    A.g_qpos = grad_qpos; A.g_qvel = grad_qvel; A.g_hpos = grad_hpos; A.g_hquat = grad_hquat;
-    HIP_OK(kp::launch_obs_ar_grad(A, s->stream));
-    if (x->ctx_dim > 0) HIP_OK(kp::launch_obs_ctx_grad(n_rows, x->ctx_dim, grad_obs, pitch, grad_ctx, s->stream));
-    return 0;
+    return obs_ar_base_backward(who, s, c, n_rows, pitch, x->ctx_dim, qpos, wbpos, wbquat, grad_obs, grad_obj_2_head, grad_qpos, grad_qvel, grad_hpos, grad_hquat,
+                                grad_ctx);
 }
-
 
 // ---- the sampler's records at a row with a context / `of` block: the same kernels (the width is their argument), obs_dim = ctx_dim + base + of_dim
 static int check_wide_width(const char* who, int obs_dim, int ctx_dim, int of_dim) {
@@ -1608,26 +1623,13 @@ static int check_wide_width(const char* who, int obs_dim, int ctx_dim, int of_di
 int kp_rollout_record_pre_x(const kp_record_pre* r, int obs_dim, int ctx_dim, int of_dim, void* stream) {
     if (!r || r->n <= 0 || r->T <= 0 || r->t < 0 || r->t >= r->T) return fail("kp_rollout_record_pre_x: bad arguments");
     if (check_wide_width("kp_rollout_record_pre_x", obs_dim, ctx_dim, of_dim)) return -1;
-    if ((r->states && !r->obs) || (r->episode_start && !r->fresh) || (r->curr_qpos && !r->qpos) || (r->meta && !r->row_meta) ||
-        (r->gt_target_qpos && (!r->ctx_qpos || !r->cur_t || !r->row_len || r->ctx_T <= 0)))
-        return fail("kp_rollout_record_pre_x: a destination without its source");
-    kp::RecordPre R{r->n, r->T, r->t, r->ctx_T, obs_dim, r->obs, r->fresh, r->qpos, r->ctx_qpos, r->row, r->cur_t, r->row_len, r->row_meta,
-                    r->states, r->episode_start, r->curr_qpos, r->gt_target_qpos, r->meta};
-    hipLaunchKernelGGL(kp::k_record_pre, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
-    return launched();
+    return record_pre("kp_rollout_record_pre_x", r, obs_dim, stream);
 }
 
 int kp_rollout_record_post_x(const kp_record_post* r, int obs_dim, int ctx_dim, int of_dim, void* stream) {
     if (!r || r->n <= 0 || r->T <= 0 || r->t < 0 || r->t >= r->T) return fail("kp_rollout_record_post_x: bad arguments");
     if (check_wide_width("kp_rollout_record_post_x", obs_dim, ctx_dim, of_dim)) return -1;
-    if ((r->actions && !r->action) || (r->rewards && !r->reward) || (r->fails && !r->fail) || (r->dones && !r->done) || (r->percents && !r->percent) ||
-        (r->c_infos && !r->c_info) || (r->next_states && !r->obs) || (r->res_qpos && !r->qpos) || (r->cc_actions && !r->cc_action) ||
-        (r->cc_states && !r->cc_state) || (r->v_metas && !r->meta))
-        return fail("kp_rollout_record_post_x: a destination without its source");
-    kp::RecordPost R{r->n, r->T, r->t, obs_dim, r->fr_num, r->action, r->reward, r->fail, r->done, r->percent, r->c_info, r->obs, r->qpos, r->cc_action, r->cc_state, r->meta,
-                     r->actions, r->rewards, r->fails, r->dones, r->percents, r->c_infos, r->next_states, r->res_qpos, r->cc_actions, r->cc_states, r->v_metas};
-    hipLaunchKernelGGL(kp::k_record_post, dim3(r->n), dim3(128), 0, (hipStream_t)stream, R);
-    return launched();
+    return record_post("kp_rollout_record_post_x", r, obs_dim, stream);
 }
 
 // ---- the ring refill of the wide context tables (k_ctx_rows_write, kp_obs_ctx.hip)

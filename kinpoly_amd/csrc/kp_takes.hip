@@ -1,7 +1,9 @@
 // kp_takes.hip -- the kernels declared in kp_takes.hpp (see there).  The fp32 forms of the quaternion logarithm (|xyz| and atan2 instead of
 // sqrt(1 - w^2) and acos) are those of kinpoly_amd/uhc_env.py, which the rectangular torch path uses and explains (kinpoly_amd/context.py:54-75).
+// quaternion_inverse and get_body_quat's 'sxyz' joint quaternion (humanoid_im.py:342-354) are kp_quat.hpp's q_inverse and q_euler_sxyz.
 #include "kp_takes.hpp"
 #include "kp_collide.hpp"
+#include "kp_quat.hpp"
 
 namespace kp {
 
@@ -10,18 +12,6 @@ namespace {
 constexpr float TK_PI = 3.14159265358979323846f;
 __device__ const int TK_EE[5] = {4, 8, 17, 22, 13};      // L_Toe, R_Toe, L_Wrist, R_Wrist, Head (humanoid_im.py:329)
 
-__device__ __forceinline__ Q4 ldq(const float* p) { return Q4{p[0], p[1], p[2], p[3]}; }
-__device__ __forceinline__ Q4 tk_qinv(Q4 q) {            // quaternion_inverse: conj / dot
-    const float n = q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z;
-    return Q4{q.w / n, -q.x / n, -q.y / n, -q.z / n};
-}
-// get_body_quat's joint quaternion: quaternion_from_euler(a0, a1, a2) with the default 'sxyz' axes (humanoid_im.py:342-354)
-__device__ __forceinline__ Q4 tk_euler_sxyz(float ai, float aj, float ak) {
-    float si, ci, sj, cj, sk, ck;
-    sincosf(0.5f * ai, &si, &ci); sincosf(0.5f * aj, &sj, &cj); sincosf(0.5f * ak, &sk, &ck);
-    const float cc = ci * ck, cs = ci * sk, sc = si * ck, ss = si * sk;
-    return Q4{cj * cc + sj * ss, cj * sc - sj * cs, cj * ss + sj * cc, cj * cs - sj * sc};
-}
 // rotation_from_quaternion (uhc/khrylib/utils/transformation.py:348-356): axis * angle, no wrap, exactly 0 for `1 - |w| < 1e-8`
 __device__ __forceinline__ V3 tk_rotvec(Q4 q) {
     const float n2 = q.x * q.x + q.y * q.y + q.z * q.z;
@@ -32,7 +22,7 @@ __device__ __forceinline__ V3 tk_rotvec(Q4 q) {
 // get_angvel_fd (math.py:68-74) of one body.  The division by dt is a multiplication by (float)(1 / dt), the reciprocal taken in fp64, here and in k_take_tables: that is how the
 // torch path's `tensor / dt` is evaluated, and an expert velocity that differs from it in the last bit would start the physics from another state.
 __device__ __forceinline__ V3 tk_angvel(Q4 prev, Q4 cur, float inv_dt) {
-    const V3 r = tk_rotvec(qmul(cur, tk_qinv(prev)));
+    const V3 r = tk_rotvec(qmul(cur, q_inverse(prev)));
     return v3(r.x * inv_dt, r.y * inv_dt, r.z * inv_dt);
 }
 // transform_vec(v, q, 'root'): R(q / |q|)^T v
@@ -91,7 +81,7 @@ __global__ __launch_bounds__(64) void k_take_tables(TakeBuildArgs A) {
     }
     if (lane == 5) {                                          // rq_rmh = de_heading(q) = inverse(heading q) (x) q
         const float hn = sqrtf(rq.w * rq.w + rq.z * rq.z);
-        const Q4 o = qmul(tk_qinv(Q4{rq.w / hn, 0.f, 0.f, rq.z / hn}), rq);
+        const Q4 o = qmul(q_inverse(Q4{rq.w / hn, 0.f, 0.f, rq.z / hn}), rq);
         float* d = L.tab[TT_RQ_RMH] + row * 4;
         d[0] = o.w; d[1] = o.x; d[2] = o.y; d[3] = o.z;
     }
@@ -99,7 +89,7 @@ __global__ __launch_bounds__(64) void k_take_tables(TakeBuildArgs A) {
     float* qv = L.tab[TT_QVEL] + row * 75;
     if (lane == 6) {
         const V3 v = v3(tk_clamp10((qn[0] - qc[0]) * inv_dt), tk_clamp10((qn[1] - qc[1]) * inv_dt), tk_clamp10((qn[2] - qc[2]) * inv_dt));
-        const Q4 cq = ldq(qc + 3), qrel = qmul(ldq(qn + 3), tk_qinv(cq));
+        const Q4 cq = ldq(qc + 3), qrel = qmul(ldq(qn + 3), q_inverse(cq));
         const float n2 = qrel.x * qrel.x + qrel.y * qrel.y + qrel.z * qrel.z;
         V3 axis = v3(1.f, 0.f, 0.f);
         float angle = 0.f;
@@ -164,9 +154,9 @@ __global__ __launch_bounds__(64) void k_uhc_track(UhcTrackArgs A) {
     const V3 com = v3(wave_sum(m * xi.x) / msum, wave_sum(m * xi.y) / msum, wave_sum(m * xi.z) / msum);
     // world_rfc_implicit_reward (reward_function.py:4-53)
     const float* q = A.qpos + e * 76;
-    const Q4 bq = b == 0 ? ldq(q + 3) : tk_euler_sxyz(q[7 + 3 * (b - 1)], q[8 + 3 * (b - 1)], q[9 + 3 * (b - 1)]);
+    const Q4 bq = b == 0 ? ldq(q + 3) : q_euler_sxyz(q[7 + 3 * (b - 1)], q[8 + 3 * (b - 1)], q[9 + 3 * (b - 1)]);
     const Q4 ebq = ldq(L.tab[TT_BQUAT] + row * 96 + 4 * b);
-    const Q4 qd = qmul(bq, tk_qinv(ebq));
+    const Q4 qd = qmul(bq, q_inverse(ebq));
     const float pd = atan2f(sqrtf(qd.x * qd.x + qd.y * qd.y + qd.z * qd.z), fabsf(qd.w)) * A.b_diffw[b];       // acos(|w|)
     const float pose_s = wave_sum(body ? pd * pd : 0.f);
     const V3 dv = tk_angvel(ldq(A.prev_bquat + e * 96 + 4 * b), bq, A.inv_dt) - ld3(L.tab[TT_BANGVEL] + row * 72 + 3 * b);

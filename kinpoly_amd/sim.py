@@ -420,19 +420,26 @@ class KpSim:
         _check(self.L.kp_sim_fk_backward(self.h, R, *ins, C.c_void_p(out.data_ptr())), "kp_sim_fk_backward")
         return out
 
+    def _obs_ar_backward(self, name, ctx, ext, qpos_rows, wbpos, wbquat, grad_obs, grad_obj_2_head):
+        """kp_sim_<name> for obs_ar_backward (ext None) and obs_ar_ex_backward: the shape checks, the outputs (grad_ctx for a wide row with a context
+        block) and the call -> the outputs in the ABI's order, None for the ones the row does not have"""
+        _dev(f"{name}: grad_obs", grad_obs, (None, None))
+        R, W = grad_obs.shape
+        ins = [_dev(f"{name}: {k}", t, (R, d)) for k, t, d in (("qpos_rows", qpos_rows, NQ), ("wbpos", wbpos, 72), ("wbquat", wbquat, 96), ("grad_obs", grad_obs, W),
+                                                              ("grad_obj_2_head", grad_obj_2_head, 7))]
+        new = lambda d: torch.empty((R, d), dtype=torch.float32, device=self.device)      # noqa: E731
+        outs = [new(NQ), (new(NV) if self.obs_ar_vel else None), new(3), new(4)]
+        if ext is not None:
+            outs.append(new(ext.ctx_dim) if ext.ctx_dim > 0 else None)
+        _check(getattr(self.L, "kp_sim_" + name)(self.h, C.byref(ctx), *([] if ext is None else [C.byref(ext)]), R, W, *ins,
+                                                 *[None if o is None else C.c_void_p(o.data_ptr()) for o in outs]), "kp_sim_" + name)
+        return tuple(outs)
+
     def obs_ar_backward(self, ctx: "KpCtx", qpos_rows, wbpos, wbquat, grad_obs, grad_obj_2_head=None):
         """(d obs_ar)^T grad_obs for the first R <= N rows (kp_sim_obs_ar_backward; wbpos / wbquat: fk() of qpos_rows) -> (grad_qpos [R,76], the local
         pose block's part; grad_qvel [R,75] or None without use_vel; grad_hpos [R,3]; grad_hquat [R,4]).  grad_obj_2_head [R,7]: cotangent of the
         object block read as a feature, added to that block's."""
-        _dev("obs_ar_backward: grad_obs", grad_obs, (None, None))
-        R, W = grad_obs.shape
-        ins = [_dev("obs_ar_backward: " + k, t, (R, d)) for k, t, d in (("qpos_rows", qpos_rows, NQ), ("wbpos", wbpos, 72), ("wbquat", wbquat, 96), ("grad_obs", grad_obs, W),
-                                                                          ("grad_obj_2_head", grad_obj_2_head, 7))]
-        new = lambda d: torch.empty((R, d), dtype=torch.float32, device=self.device)      # noqa: E731
-        gq, gv, gp, gh = new(NQ), (new(NV) if self.obs_ar_vel else None), new(3), new(4)
-        _check(self.L.kp_sim_obs_ar_backward(self.h, C.byref(ctx), R, W, *ins, *[None if o is None else C.c_void_p(o.data_ptr()) for o in (gq, gv, gp, gh)]),
-               "kp_sim_obs_ar_backward")
-        return gq, gv, gp, gh
+        return self._obs_ar_backward("obs_ar_backward", ctx, None, qpos_rows, wbpos, wbquat, grad_obs, grad_obj_2_head)
 
     def fk_head_backward(self, qpos_rows, wbpos, wbquat, grad_wbpos=None, grad_hpos=None, grad_hquat=None, grad_qpos_add=None):
         """fk_backward plus the head's world quaternion (kp_sim_fk_head_backward): (d wbpos / d qpos)^T (grad_wbpos, grad_hpos added to the head's slot)
@@ -550,15 +557,7 @@ class KpSim:
     def obs_ar_ex_backward(self, ctx: "KpCtx", ext: "KpObsExt", qpos_rows, wbpos, wbquat, grad_obs, grad_obj_2_head=None):
         """obs_ar_backward for the wide row (kp_sim_obs_ar_ex_backward): -> (grad_qpos, grad_qvel or None, grad_hpos, grad_hquat, grad_ctx [R, ctx_dim] --
         the context block's cotangent, None when ctx_dim is 0)."""
-        _dev("obs_ar_ex_backward: grad_obs", grad_obs, (None, None))
-        R, W = grad_obs.shape
-        ins = [_dev("obs_ar_ex_backward: " + k, t, (R, d)) for k, t, d in (("qpos_rows", qpos_rows, NQ), ("wbpos", wbpos, 72), ("wbquat", wbquat, 96), ("grad_obs", grad_obs, W),
-                                                                             ("grad_obj_2_head", grad_obj_2_head, 7))]
-        new = lambda d: torch.empty((R, d), dtype=torch.float32, device=self.device)      # noqa: E731
-        gq, gv, gp, gh, gc = new(NQ), (new(NV) if self.obs_ar_vel else None), new(3), new(4), (new(ext.ctx_dim) if ext.ctx_dim > 0 else None)
-        _check(self.L.kp_sim_obs_ar_ex_backward(self.h, C.byref(ctx), C.byref(ext), R, W, *ins,
-                                                *[None if o is None else C.c_void_p(o.data_ptr()) for o in (gq, gv, gp, gh, gc)]), "kp_sim_obs_ar_ex_backward")
-        return gq, gv, gp, gh, gc
+        return self._obs_ar_backward("obs_ar_ex_backward", ctx, ext, qpos_rows, wbpos, wbquat, grad_obs, grad_obj_2_head)
 
     def term_reward(self, ctx: "KpCtx", cfg: "KpRewardCfg", reward=None, info=None, fail=None, diffs=None):
         reward = torch.empty(self.n, device=self.device) if reward is None else reward

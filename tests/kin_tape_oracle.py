@@ -1,5 +1,5 @@
 """A torch restatement of the FORWARD kernels of the kinematic roll-out, formula for formula, for any dtype and device: k_kin_advance
-(kinpoly_amd/csrc/kp_obs_kernels.hpp), the chain of k_target_fk, and the blocks of k_obs_ar (kp_rollout_kernels.hpp).  Run in fp64 on the CPU with
+(kinpoly_amd/csrc/kp_obs_kernels.hpp), the chain of k_target_fk, and the blocks of k_obs_ar (kp_obs_ar_row.hpp).  Run in fp64 on the CPU with
 autograd it is the reference of the gradient kernels (kp_kin_tape.hip); run in fp32 on the device it is their yardstick.  Not a test module.
 
 Where the kernels branch (the expmap's constant axis, the `no rotation` rows of the finite-difference velocity) the restatement selects with

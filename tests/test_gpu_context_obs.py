@@ -1,5 +1,5 @@
 """GPU: the kinematic model's observation row with a context block and an `of` block (kinpoly_amd/csrc/kp_obs_ctx.hip: k_obs_ar_ctx through
-kp_sim_obs_ar_ex, its backward, k_gru_cell_step_wide through kp_gru_cell_step), and the roll-outs, the taped path and kinpoly_amd.exp_arnet on top of it.
+kp_sim_obs_ar_ex, its backward, kp_gru_cell_step with a state wider than the hidden state), and the roll-outs, the taped path and kinpoly_amd.exp_arnet on top of it.
 
 The row's three blocks are copies or the base kernel's own expressions, so the row-level checks are bit equality: the base block against
 kp_sim_obs_ar on the same handle, the two wide blocks against the tables' rows at the clamped frame, h' of the wide GRU step against the D <= H
@@ -150,17 +150,19 @@ def test_fixture_rows(kp, golden, case):
 
 
 @pytest.mark.parametrize("n", [1, 65])
-@pytest.mark.parametrize("H,D", [(32, 33), (32, 64), (32, 65), (256, 357)])
+@pytest.mark.parametrize("H,D", [(32, 1), (32, 31), (32, 32), (32, 33), (32, 64), (32, 65), (256, 357)])
 def test_gru_cell_step_with_a_state_wider_than_the_hidden_state(kp, n, H, D):
+    """one kernel for every width: thread (e, j) copies the state's columns j, j + H, ...; D <= H (one column at most, the former `if`) is checked at 1, H - 1 and H"""
     g = torch.Generator().manual_seed(H + D + n)
     r = lambda *s: torch.randn(*s, generator=g).cuda()      # noqa: E731
     gi, gh, bi, bh, h, x = r(n, 3 * H), r(n, 3 * H), r(3 * H), r(3 * H), r(n, H), r(n, D)
-    want = kp.gru_cell_step(gi, gh, bi, bh, h)                                   # the D <= H kernel, no [state | h] row
+    want = kp.gru_cell_step(gi, gh, bi, bh, h)                                   # no [state | h] row
     buf, xcat = _guarded(n, D + H)
     got = kp.gru_cell_step(gi, gh, bi, bh, h, x, None, xcat)
     assert torch.equal(got, want) and torch.equal(xcat[:, :D], x) and torch.equal(xcat[:, D:], want) and _guards_intact(buf, n, D + H)
-    narrow = torch.empty((n, 2 * H), device="cuda")
-    assert torch.equal(kp.gru_cell_step(gi, gh, bi, bh, h, x[:, :H].contiguous(), None, narrow), want)      # and the D <= H kernel with its row
+    Dn = min(D, H)
+    narrow = torch.empty((n, Dn + H), device="cuda")
+    assert torch.equal(kp.gru_cell_step(gi, gh, bi, bh, h, x[:, :Dn].contiguous(), None, narrow), want)      # and with a row no wider than the hidden state
     h2 = h.clone()
     kp.gru_cell_step(gi, gh, bi, bh, h2, x, h2, xcat)                           # in place
     assert torch.equal(h2, want)
