@@ -292,6 +292,26 @@ int kp_sim_term_reward(kp_sim*, const kp_ctx* ctx, const kp_reward_cfg* cfg, flo
 int kp_sim_post_step(kp_sim*, const kp_ctx* ctx, const kp_reward_cfg* cfg, int32_t* cur_t, const int32_t* row_len, int env_episode_len,
                      float* reward, float* info, uint8_t* fail, float* diffs, uint8_t* done, uint8_t* end, float* percent, int32_t* done_count, float* obj7);
 
+/* kp_sim_term_reward / kp_sim_post_step with dynamic_supervision_v2 (kin_poly/core/reward_function.py:999-1050), the "ground truth, no dynamics
+ * regulation" reward: the head position and orientation terms of v1, then against ar_context frame cur_t (clamped into [1, T - 1] as for v1)
+ *   pose  exp(-k_p |multi_quat_norm(bquat (x) gt_bquat^-1) * (1, b_diffw)|^2)        vel  exp(-k_v |get_angvel_fd(prev_bquat, bquat) - get_angvel_fd(gt_bquat[t - 1], gt_bquat[t])|^2)
+ *   ee    exp(-k_e |wbpos - gt_wbpos|^2) over all 24 bodies
+ * and reward = w_hp hp + w_hq hq + w_p pose + w_v vel + w_e ee (not normalised).  multi_quat_norm is kin_poly's (kin_poly/utils/math_utils.py:105-109:
+ * acos(w), no absolute value, so a body quaternion of the opposite sign counts as a turn of 2 pi - angle) and get_angvel_fd's rotation_from_quaternion
+ * kin_poly's too (kin_poly/utils/transformation.py:362-372: zero if |1 - w| < 1e-6 or |1 + w| < 1e-6).  info stays [N,6] so that records keep their shape: (hp, hq, pose,
+ * vel, ee, 0).  Termination, end / done / percent and the obj7 write-back are v1's, bit for bit; every other argument and refusal is the v1 entry's,
+ * plus a NULL b_diffw. */
+typedef struct {
+    float w_hp, w_hq, w_p, w_v, w_e;
+    float k_hp, k_hq, k_p, k_v, k_e;
+    float dt, body_diff_thresh, body_diff_gt_thresh;
+    int use_gt_term;
+    const float* b_diffw;      /* device [24]: root 1, then cc_cfg.b_diffw (the blob's uhc_b_diffw) */
+} kp_reward_cfg_v2;
+int kp_sim_term_reward_v2(kp_sim*, const kp_ctx* ctx, const kp_reward_cfg_v2* cfg, float* reward, float* info, uint8_t* fail, float* diffs);
+int kp_sim_post_step_v2(kp_sim*, const kp_ctx* ctx, const kp_reward_cfg_v2* cfg, int32_t* cur_t, const int32_t* row_len, int env_episode_len,
+                        float* reward, float* info, uint8_t* fail, float* diffs, uint8_t* done, uint8_t* end, float* percent, int32_t* done_count, float* obj7);
+
 /* Masked reset in one gather + sim.forward() (mujoco_env.py:86-103, humanoid_ar_v1.py:334-387): for the envs with env_mask != 0 (NULL: all)
  * qpos / qvel <- init_qpos / init_qvel [R, 76] / [R, 75] of context row row[e] (NULL: row e), cur_t[e] = 0 (cur_t may be NULL), warm start
  * zeroed, derived quantities recomputed; set_target != 0: target = qpos_fk(init_qpos) for those envs as reset_model does (:384-386).
@@ -547,6 +567,47 @@ int kp_sim_uhc_track(kp_sim*, const kp_takes*, const kp_uhc_state* st, const kp_
  * are untouched.  Needs threads_per_env = 64 (-1, nothing launched).  A library without objects never touches the object block. */
 int kp_sim_uhc_assign(kp_sim*, const kp_takes*, const kp_uhc_state* st, const kp_uhc_cfg* cfg, const uint8_t* env_mask,
                       const int32_t* take_ids_host, const int32_t* start_host, int keep_t, const float* noise);
+
+/* ---- the UHC's other tracking rewards (uhc/core/reward_function.py:453-460, the registry) ----
+ *
+ * kp_sim_uhc_track computes world_rfc_implicit_reward; kp_sim_uhc_track_r is the same launch with the reward function chosen by reward_id:
+ *   KP_UHC_WORLD_RFC_IMPLICIT         :4-53     what kp_sim_uhc_track computes, by the same kernel: every output is bit-identical; info [N,5]
+ *   KP_UHC_WORLD_RFC_IMPLICIT_V1_MUL  :56-102   the five terms of the above multiplied, the vf term always on (w_* unused); info [N,5]
+ *   KP_UHC_LOCAL_RFC_IMPLICIT         :172-231  pose and velocity without the root, end effectors in root coordinates against the table ee_pos, root
+ *                                               pose (height, de-headed root quaternion against rq_rmh), root velocity (get_qvel_fd_new(prev_qpos, qpos,
+ *                                               dt, 'root')[:6] against rlinv_local / rangv), vf if w_vf > 0; weighted sum over the sum of the weights;
+ *                                               info [N,6] = pose, vel, ee, root pose, root vel, vf
+ *   KP_UHC_WORLD_RFC_IMPLICIT_V2      :301-372  pose, world pose (xquat against wbquat), per-body COM (xipos against body_com), joint positions (xpos
+ *                                               against wbpos), velocity, vf: every distance a MEAN of squares, the terms multiplied;
+ *                                               info [N,6] = pose, wpose, com, jpos, vel, vf
+ *   KP_UHC_WORLD_RFC_IMPLICIT_V3      :376-450  v2's terms in a weighted sum that is NOT normalised; info [N,6] as v2
+ * The termination outputs, cur_t, the stored target and base_qpos do not depend on reward_id. */
+enum { KP_UHC_WORLD_RFC_IMPLICIT = 0, KP_UHC_WORLD_RFC_IMPLICIT_V1_MUL = 1, KP_UHC_LOCAL_RFC_IMPLICIT = 2, KP_UHC_WORLD_RFC_IMPLICIT_V2 = 3,
+       KP_UHC_WORLD_RFC_IMPLICIT_V3 = 4, KP_UHC_REWARD_COUNT = 5 };
+
+/* kp_uhc_cfg -- the weights the five functions share by name, and the episode constants -- plus the union of the others' `ws.get` keys.  A weight
+ * a function does not read is ignored. */
+typedef struct {
+    kp_uhc_cfg base;           /* w_p w_v w_e w_c w_vf k_p k_v k_e k_c k_vf: each function's own keys of these names */
+    int reward_id;             /* KP_UHC_* */
+    float w_rp, w_rv;          /* local_rfc_implicit: root pose, root velocity (:176) */
+    float k_rh, k_rq, k_rl, k_ra;      /* local_rfc_implicit: root height, root quaternion, root linear / angular velocity (:178) */
+    float w_wp, w_j;           /* v3: world pose, joint positions (:380-381) */
+    float k_wp, k_j;           /* v2 / v3 (:305-306, 383-384) */
+    const float* jpos_diffw;   /* device [24]: reward_weights.jpos_diffw of v2 / v3 (:307; NOT the env's cfg.jpos_diffw); NULL for the other ids */
+    const float* prev_qpos;    /* device [N,76]: env.prev_qpos, the qpos before the control step (humanoid_im.py:538), read by local_rfc_implicit;
+                                  NULL for the other ids */
+} kp_uhc_cfg_r;
+
+/* the width of kp_sim_uhc_track_r's info row: 5 or 6; -1 for an unknown reward_id */
+int kp_uhc_reward_info_dim(int reward_id);
+
+/* kp_sim_uhc_track with cfg->reward_id's reward (the table above): the tail of HumanoidEnv.step (humanoid_im.py:527-572) and
+ * reward_func[cfg.reward_id] (reward_function.py:453-460) in one launch, one wavefront per env.  info [N, kp_uhc_reward_info_dim(reward_id)]; the
+ * other arguments are kp_sim_uhc_track's.  Errors (nothing launched): kp_sim_uhc_track's, an unknown reward_id, NULL jpos_diffw for v2 / v3, NULL
+ * prev_qpos for local_rfc_implicit. */
+int kp_sim_uhc_track_r(kp_sim*, const kp_takes*, const kp_uhc_state* st, const kp_uhc_cfg_r* cfg, const float* cc_action,
+                       float* reward, float* info, float* body_diff, uint8_t* fail, uint8_t* end, uint8_t* done, float* percent);
 
 const char* kp_last_error(void);
 const char* kp_version(void);

@@ -250,10 +250,9 @@ class AgentAR:
             env = BatchedHumanoidAREnv(n, self.device.index, mode="test", wild=wild, seed=0, cc_policy=self.env.cc_policy, cc_running_state=self.env.cc_running_state,
                                        model_options=getattr(self.env, "model_options", None), use_action=self.env.use_action, use_vel=self.env.use_vel,
                                        use_head=self.env.use_head, ctx_dim=self.env.ctx_dim, of_dim=self.env.of_dim)
-            import copy
-            gt_term = env.reward_cfg.use_gt_term                         # a property of the mode (test: no GT-diff termination), not of the configuration
-            env.reward_cfg = copy.deepcopy(self.env.reward_cfg)          # thresholds AND the reward weights cfg.apply_reward_weights put on the training env
-            env.reward_cfg.use_gt_term = gt_term
+            # the reward function, thresholds AND the reward weights cfg.apply_reward_weights put on the training env; use_gt_term stays the
+            # mode's (test: no GT-diff termination)
+            env.copy_reward(self.env)
             if hasattr(self.env, "env_episode_len"):
                 env.env_episode_len = self.env.env_episode_len
             builder = PolicyARContext(self.policy_net, kpsim.KpSim(env.model, n, self.device.index), smooth=self.ctx_builder.smooth, need_rollout=True,

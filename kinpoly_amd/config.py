@@ -14,7 +14,8 @@ of another architecture than TrajARNet's (checked: a mismatch raises), `policy_o
 kin_poly.yml values (checked).  `use_of` / `use_context` (kin_only.yml, use_of.yml) are refused by the default entry and taken by
 `Config(..., entry="kin_model")`, the supervised kinematic model of scripts/exp_arnet_all.py, with the file's net sizes (`model_kwargs()`), and by
 `Config(..., entry="policy_ctx")`, the roll-out / PPO scripts with the video-conditioned policy (every other check of the default entry holds there:
-`policy_v: 2` and `reward_id: dynamic_supervision_v3`, which kin_only.yml and use_of.yml declare, stay refused by name).  Nothing here needs a GPU.
+`policy_v: 2` and `reward_id: dynamic_supervision_v3`, which kin_only.yml and use_of.yml declare, stay refused by name).  `policy_specs.reward_id` may be
+`dynamic_supervision_v1` or `dynamic_supervision_v2` (REWARD_DEFAULTS; v3 .. v6 are refused).  Nothing here needs a GPU.
 """
 from __future__ import annotations
 
@@ -35,6 +36,12 @@ _FIXED_POLICY = {"policy_v": 1, "fix_std": True, "policy_htype": "relu", "policy
 # what Config(entry="kin_model") takes from the file instead: the supervised kinematic model runs with a context / `of` block and any net sizes
 _KIN_MODEL_FREE = ("use_of", "use_context", "rnn_hdim", "mlp_hsize", "cnn_fdim")
 ENTRIES = ("policy", "kin_model", "policy_ctx")
+# the policy entries' reward functions and each one's own `ws.get(key, default)` list (kin_poly/core/reward_function.py:935-940, 1003-1004)
+REWARD_DEFAULTS = {
+    "dynamic_supervision_v1": {"w_hp": 1.0, "w_hq": 1.0, "w_p": 1.0, "w_jp": 1.0, "w_act_p": 1.0, "w_act_v": 1.0,
+                               "k_hp": 1.0, "k_hq": 1.0, "k_p": 1.0, "k_jp": 0.1, "k_act_p": 0.1, "k_act_v": 0.1},
+    "dynamic_supervision_v2": {"w_hp": 1.0, "w_hq": 1.0, "w_p": 0.6, "w_v": 0.1, "w_e": 0.2, "k_hp": 1.0, "k_hq": 1.0, "k_p": 2.0, "k_v": 0.005, "k_e": 20.0},
+}
 # why a policy entry refuses them (the error text and INTEGRATION.md say it): in the reference that path cannot run
 _REFUSED_WHY = {"policy_v": "policy_v 2: PolicyAR.step_lr reads a scheduler that only policy_v == 1 creates, policy_ar.py:33-37, 88-89",
                 "reward_id": "dynamic_supervision_v3 reads env.cc_cfg.policy_specs, which the UHC config does not have, reward_function.py:1055-1056"}
@@ -96,6 +103,7 @@ class Config:
         self.model_specs, self.policy_specs = dict(g("model_specs", {})), dict(g("policy_specs", {}))
         self.joint_controller = self.policy_specs.get("joint_controller", False)       # :149-150
         self.reward_weights = dict(self.policy_specs.get("reward_weights", {}))
+        self.reward_id = self.policy_specs.get("reward_id", _FIXED_POLICY["reward_id"])      # a file without the key has always run dynamic_supervision_v1
         self.use_action = y.get("use_action", True)          # statear_smpl_config.py:141
         self.use_vel, self.use_head = y.get("use_vel", False), y.get("use_head", True)      # :139-140
         self.use_of, self.use_context = y.get("use_of", True), y.get("use_context", True)  # :137-138 (refused by the default entry)
@@ -125,7 +133,9 @@ class Config:
                 bad.append(f"model_specs.cnn_fdim: {cf!r} (a positive integer)")
         if not kin:
             bad += [f"policy_specs.{k}: {self.policy_specs[k]!r} (implemented: {v!r}" + (f"; {_REFUSED_WHY[k]}" if k in _REFUSED_WHY else "") + ")"
-                    for k, v in _FIXED_POLICY.items() if k in self.policy_specs and self.policy_specs[k] != v]
+                    for k, v in _FIXED_POLICY.items() if k in self.policy_specs and self.policy_specs[k] != v and k != "reward_id"]
+            if self.reward_id not in REWARD_DEFAULTS:
+                bad.append(f"policy_specs.reward_id: {self.reward_id!r} (implemented: {', '.join(map(repr, REWARD_DEFAULTS))}; {_REFUSED_WHY['reward_id']})")
         if bad:
             raise ConfigError(f"{self.path}: not supported by the batched engine -- " + "; ".join(bad))
 
@@ -181,10 +191,11 @@ class Config:
         return max(floor, -(-need // (n_envs * world_size)))
 
     def apply_reward_weights(self, env):
-        """policy_specs.reward_weights -> the reward kernel's constants (dynamic_supervision_v1's `ws.get(key, default)`, reward_function.py:935-940)."""
-        defaults = {"w_hp": 1.0, "w_hq": 1.0, "w_p": 1.0, "w_jp": 1.0, "w_act_p": 1.0, "w_act_v": 1.0,
-                    "k_hp": 1.0, "k_hq": 1.0, "k_p": 1.0, "k_jp": 0.1, "k_act_p": 0.1, "k_act_v": 0.1}
-        for k, d in defaults.items():
+        """policy_specs.reward_id / reward_weights -> the reward kernel and its constants: dynamic_supervision_v1's or _v2's own `ws.get(key, default)`
+        list (REWARD_DEFAULTS).  An env that knows one reward only (no set_reward) keeps it: v1."""
+        if hasattr(env, "set_reward"):
+            env.set_reward(self.reward_id)
+        for k, d in REWARD_DEFAULTS[self.reward_id].items():
             setattr(env.reward_cfg, k, float(self.reward_weights.get(k, d)))
         if int(self.reward_weights.get("v_ord", 2)) != 2:
             raise ConfigError("reward_weights.v_ord must be 2 (the angular-velocity term of the reward kernel is the L2 norm)")

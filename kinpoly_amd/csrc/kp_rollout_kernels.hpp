@@ -3,7 +3,7 @@
 //                                                      (:157-169, 184-201), eight layouts; <false, true, true> is kin_poly.yml's 105-d row
 //   k_obs_ar_thread  the 105 / 101 rows, one thread per env: the faster launch at these two widths, the same words
 //   k_term_reward  calc_body_diff / calc_body_gt_diff  kin_poly/envs/humanoid_ar_v1.py:435-458
-//                  dynamic_supervision_v1              kin_poly/core/reward_function.py:931-995
+//                  dynamic_supervision_v1 / _v2        kin_poly/core/reward_function.py:931-995, 999-1050
 //   k_snapshot     prev_bquat / prev_hpos records      kin_poly/envs/humanoid_ar_v1.py:246-249
 //   k_gae          estimate_advantages (un-normalised) uhc/khrylib/rl/core/common.py:5-25
 // One thread or one 32-lane group per environment: these are O(100)-flop gathers; the physics kernel dominates the step.
@@ -90,11 +90,12 @@ __device__ __forceinline__ float quat_norm_v2(Q4 q) {  // multi_quat_norm_v2 of 
     float a = fabsf(q.w) - 1.0f;
     return sqrtf(a * a + q.x * q.x + q.y * q.y + q.z * q.z);
 }
-__device__ __forceinline__ V3 rot_from_quat(Q4 q) {  // rotation_from_quaternion (transformation.py:348-356)
+__device__ __forceinline__ V3 rot_from_quat(Q4 q, float eps = 1e-8f) {  // rotation_from_quaternion (transformation.py:348-356)
     // the reference (fp64): zero if 1 - |w| < 1e-8, else xyz / sqrt(1 - w^2) * 2 acos(w).  In fp32 1 - w^2 of a small rotation (a body turning at
-    // 0.1 rad/s between two control steps: 2e-6) is known to 3 %; for the unit quaternion q it equals |xyz|^2, and 1 - |w| = |xyz|^2 / (1 + |w|)
+    // 0.1 rad/s between two control steps: 2e-6) is known to 3 %; for the unit quaternion q it equals |xyz|^2, and 1 - |w| = |xyz|^2 / (1 + |w|).
+    // eps = 1e-6 is kin_poly's own copy (kin_poly/utils/transformation.py:362-372: zero if |1 - w| < 1e-6 or |1 + w| < 1e-6), which dynamic_supervision_v2 is held to
     const float s2 = q.x * q.x + q.y * q.y + q.z * q.z;
-    if (s2 < 1e-8f * (1.0f + fabsf(q.w))) return v3(0.f, 0.f, 0.f);
+    if (s2 < eps * (1.0f + fabsf(q.w))) return v3(0.f, 0.f, 0.f);
     const float s = sqrtf(s2), ang = 2.0f * atan2f(s, q.w);
     return (ang / s) * v3(q.x, q.y, q.z);
 }
@@ -116,8 +117,14 @@ struct PostStep {
     float* obj7;                // optional [N,7]: get_obj_qpos(action_one_hot) after the step = the simulated pose of the action's (first) object,
     const float* sim_obj_qpos;  //   read from the simulator's data.qpos[76:111] rows [N,35]; envs whose clip has no action keep their obj7
 };
-template <bool POST>
-__global__ __launch_bounds__(256) void k_term_reward(int n, CtxDev C, RewardW W, const float* __restrict__ qpos, const float* __restrict__ xpos,
+// dynamic_supervision_v2 (kin_poly/core/reward_function.py:999-1050): the head terms of v1, then pose (multi_quat_norm against the ground truth's
+// bquat, cc_cfg.b_diffw on bodies 1..23), finite-difference angular velocity and all 24 body positions against the ground truth; a weighted sum
+struct RewardW2 { float w_hp, w_hq, w_p, w_v, w_e, k_hp, k_hq, k_p, k_v, k_e, dt, thresh, gt_thresh; int use_gt; const float* b_diffw; /* [24], root 1 */ };
+
+// RV: dynamic_supervision_v<RV>; W is RewardW (RV 1, the default: k_term_reward<POST> is v1's kernel) or RewardW2 (RV 2).  Termination, the POST tail
+// and the obj7 write-back do not depend on RV; RV 1 is the kernel as it was before v2 existed, statement for statement.
+template <bool POST, int RV = 1, class WT = RewardW>
+__global__ __launch_bounds__(256) void k_term_reward(int n, CtxDev C, WT W, const float* __restrict__ qpos, const float* __restrict__ xpos,
                               const float* __restrict__ xquat, const float* __restrict__ t_wbpos, const float* __restrict__ t_bquat,
                               const float* __restrict__ prev_bquat, const float* __restrict__ prev_hpos, const float* __restrict__ diffw,
                               float* __restrict__ reward, float* __restrict__ info, uint8_t* __restrict__ fail, float* __restrict__ diffs, PostStep PS) {
@@ -136,7 +143,7 @@ __global__ __launch_bounds__(256) void k_term_reward(int n, CtxDev C, RewardW W,
     if (b < D_NB) {
         const Q4 cb = b == 0 ? Q4{q[3], q[4], q[5], q[6]} : q_euler_sxyz(q[7 + 3 * (b - 1)], q[8 + 3 * (b - 1)], q[9 + 3 * (b - 1)]);
         const float* tb = t_bquat + (size_t)e * 96 + 4 * b;
-        pq = quat_norm_v2(qmul(cb, q_inverse(Q4{tb[0], tb[1], tb[2], tb[3]})));
+        if constexpr (RV == 1) pq = quat_norm_v2(qmul(cb, q_inverse(Q4{tb[0], tb[1], tb[2], tb[3]})));
         const V3 x = ld3(xp + 3 * b);
         const V3 dpos = x - ld3(t_wbpos + (size_t)e * 72 + 3 * b);
         pp = sqrtf(dot(dpos, dpos));
@@ -146,10 +153,18 @@ __global__ __launch_bounds__(256) void k_term_reward(int n, CtxDev C, RewardW W,
         bgd = wgt * sqrtf(dot(dg, dg));
         const Q4 g = Q4{gtb[4 * b], gtb[4 * b + 1], gtb[4 * b + 2], gtb[4 * b + 3]};
         const Q4 gpv = Q4{gtp[4 * b], gtp[4 * b + 1], gtp[4 * b + 2], gtp[4 * b + 3]};
-        pg = quat_norm_v2(qmul(g, q_inverse(cb)));
+        if constexpr (RV == 1) pg = quat_norm_v2(qmul(g, q_inverse(cb)));
+        else {       // pq: (multi_quat_norm * b_diffw)^2 with kin_poly's multi_quat_norm (kin_poly/utils/math_utils.py:105-109), acos(w) WITHOUT the
+                     // absolute value the UHC's has, taken as the angle of the point (w, |xyz|) (unit quaternions); pg: |x - gt|^2 of the body
+            const Q4 qd = qmul(cb, q_inverse(g));
+            const float pa = atan2f(sqrtf(qd.x * qd.x + qd.y * qd.y + qd.z * qd.z), qd.w) * W.b_diffw[b];
+            pq = pa * pa;
+            pg = dot(dg, dg);
+        }
         const float* pb = prev_bquat + (size_t)e * 96 + 4 * b;
-        const V3 cv = (1.0f / W.dt) * rot_from_quat(qmul(cb, q_inverse(Q4{pb[0], pb[1], pb[2], pb[3]})));
-        const V3 gv = (1.0f / W.dt) * rot_from_quat(qmul(g, q_inverse(gpv)));
+        constexpr float rot_eps = RV == 1 ? 1e-8f : 1e-6f;
+        const V3 cv = (1.0f / W.dt) * rot_from_quat(qmul(cb, q_inverse(Q4{pb[0], pb[1], pb[2], pb[3]})), rot_eps);
+        const V3 gv = (1.0f / W.dt) * rot_from_quat(qmul(g, q_inverse(gpv)), rot_eps);
         const V3 dv = cv - gv;
         vel2 = dot(dv, dv);
     }
@@ -166,12 +181,19 @@ __global__ __launch_bounds__(256) void k_term_reward(int n, CtxDev C, RewardW W,
     const Q4 hq = qmul(Q4{xq[52], xq[53], xq[54], xq[55]}, q_inverse(Q4{hp[3], hp[4], hp[5], hp[6]}));
     const float hqd = quat_norm_v2(hq);
     const float hq_r = expf(-W.k_hq * hqd * hqd);
-    pq *= (1.0f / 24.0f); pp *= (1.0f / 24.0f); pg *= (1.0f / 24.0f);
-    const float p_r = expf(-W.k_p * pq * pq), jp_r = expf(-W.k_jp * pp * pp);
-    const float gt_r = expf(-W.k_act_p * pg), av_r = expf(-W.k_act_v * vel2);
-    reward[e] = W.w_hp * hp_r + W.w_hq * hq_r + W.w_p * p_r + W.w_jp * jp_r + W.w_act_p * gt_r + W.w_act_v * av_r;
-    float* inf = info + (size_t)e * 6;
-    inf[0] = hp_r; inf[1] = hq_r; inf[2] = p_r; inf[3] = jp_r; inf[4] = gt_r; inf[5] = av_r;
+    if constexpr (RV == 1) {
+        pq *= (1.0f / 24.0f); pp *= (1.0f / 24.0f); pg *= (1.0f / 24.0f);
+        const float p_r = expf(-W.k_p * pq * pq), jp_r = expf(-W.k_jp * pp * pp);
+        const float gt_r = expf(-W.k_act_p * pg), av_r = expf(-W.k_act_v * vel2);
+        reward[e] = W.w_hp * hp_r + W.w_hq * hq_r + W.w_p * p_r + W.w_jp * jp_r + W.w_act_p * gt_r + W.w_act_v * av_r;
+        float* inf = info + (size_t)e * 6;
+        inf[0] = hp_r; inf[1] = hq_r; inf[2] = p_r; inf[3] = jp_r; inf[4] = gt_r; inf[5] = av_r;
+    } else {         // :1037-1050; the row stays 6 wide for the records, its last entry is 0
+        const float p_r = expf(-W.k_p * pq), v_r = expf(-W.k_v * vel2), e_r = expf(-W.k_e * pg);
+        reward[e] = W.w_hp * hp_r + W.w_hq * hq_r + W.w_p * p_r + W.w_v * v_r + W.w_e * e_r;
+        float* inf = info + (size_t)e * 6;
+        inf[0] = hp_r; inf[1] = hq_r; inf[2] = p_r; inf[3] = v_r; inf[4] = e_r; inf[5] = 0.f;
+    }
     const bool failed = (bd > W.thresh) || (W.use_gt && bgd > W.gt_thresh) || !(bd == bd);
     fail[e] = failed;
     diffs[2 * e] = bd; diffs[2 * e + 1] = bgd;

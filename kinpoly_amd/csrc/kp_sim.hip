@@ -1035,18 +1035,44 @@ static int uhc_check(const char* who, const kp_sim* s, const kp_takes* t, const 
     return 0;
 }
 
-int kp_sim_uhc_track(kp_sim* s, const kp_takes* t, const kp_uhc_state* st, const kp_uhc_cfg* c, const float* action,
-                     float* reward, float* info, float* body_diff, uint8_t* failp, uint8_t* endp, uint8_t* donep, float* percent) {
-    if (uhc_check("kp_sim_uhc_track", s, t, st, c)) return -1;
-    if (!action || !reward || !info || !body_diff || !failp || !endp || !donep || !percent) return fail("kp_sim_uhc_track: null argument");
-    HIP_OK(hipSetDevice(s->device));
+static kp::UhcTrackArgs uhc_track_args(kp_sim* s, const kp_takes* t, const kp_uhc_state* st, const kp_uhc_cfg* c, const float* action,
+                                       float* reward, float* info, float* body_diff, uint8_t* failp, uint8_t* endp, uint8_t* donep, float* percent) {
     kp::UhcTrackArgs A{};
     A.L = t->L; A.n = s->n; A.st = *st; A.cfg = *c; A.inv_dt = (float)(1.0 / c->dt);
     A.qpos = s->st.qpos; A.xpos = s->st.xpos; A.xipos = s->st.xipos; A.prev_bquat = s->st.prev_bquat;
     A.t_qpos = s->tgt.qpos; A.t_wbpos = s->tgt.wbpos; A.t_wbquat = s->tgt.wbquat; A.t_bquat = s->tgt.bquat; A.t_com = s->tgt.com;
     A.body_mass = s->T.body_mass; A.b_diffw = c->b_diffw; A.jpos_diffw = s->diffw; A.action = action;
     A.reward = reward; A.info = info; A.body_diff = body_diff; A.percent = percent; A.fail = failp; A.end = endp; A.done = donep;
-    HIP_OK(kp::launch_uhc_track(A, s->stream));
+    return A;
+}
+
+int kp_sim_uhc_track(kp_sim* s, const kp_takes* t, const kp_uhc_state* st, const kp_uhc_cfg* c, const float* action,
+                     float* reward, float* info, float* body_diff, uint8_t* failp, uint8_t* endp, uint8_t* donep, float* percent) {
+    if (uhc_check("kp_sim_uhc_track", s, t, st, c)) return -1;
+    if (!action || !reward || !info || !body_diff || !failp || !endp || !donep || !percent) return fail("kp_sim_uhc_track: null argument");
+    HIP_OK(hipSetDevice(s->device));
+    HIP_OK(kp::launch_uhc_track(uhc_track_args(s, t, st, c, action, reward, info, body_diff, failp, endp, donep, percent), s->stream));
+    return 0;
+}
+
+int kp_uhc_reward_info_dim(int reward_id) {
+    if (reward_id < 0 || reward_id >= KP_UHC_REWARD_COUNT) return -1;
+    return reward_id == KP_UHC_WORLD_RFC_IMPLICIT || reward_id == KP_UHC_WORLD_RFC_IMPLICIT_V1_MUL ? 5 : 6;
+}
+
+int kp_sim_uhc_track_r(kp_sim* s, const kp_takes* t, const kp_uhc_state* st, const kp_uhc_cfg_r* c, const float* action,
+                       float* reward, float* info, float* body_diff, uint8_t* failp, uint8_t* endp, uint8_t* donep, float* percent) {
+    if (!c) return fail("kp_sim_uhc_track_r: null argument");
+    if (uhc_check("kp_sim_uhc_track_r", s, t, st, &c->base)) return -1;
+    if (!action || !reward || !info || !body_diff || !failp || !endp || !donep || !percent) return fail("kp_sim_uhc_track_r: null argument");
+    const int id = c->reward_id;
+    if (kp_uhc_reward_info_dim(id) < 0) return fail("kp_sim_uhc_track_r: unknown reward_id " + std::to_string(id));
+    if ((id == KP_UHC_WORLD_RFC_IMPLICIT_V2 || id == KP_UHC_WORLD_RFC_IMPLICIT_V3) && !c->jpos_diffw)
+        return fail("kp_sim_uhc_track_r: world_rfc_implicit_v2 / _v3 need kp_uhc_cfg_r.jpos_diffw");
+    if (id == KP_UHC_LOCAL_RFC_IMPLICIT && !c->prev_qpos) return fail("kp_sim_uhc_track_r: local_rfc_implicit needs kp_uhc_cfg_r.prev_qpos");
+    HIP_OK(hipSetDevice(s->device));
+    const kp::UhcRewardExt X{c->w_rp, c->w_rv, c->k_rh, c->k_rq, c->k_rl, c->k_ra, c->w_wp, c->w_j, c->k_wp, c->k_j, c->jpos_diffw, c->prev_qpos, s->st.xquat};
+    HIP_OK(kp::launch_uhc_track_r(id, uhc_track_args(s, t, st, &c->base, action, reward, info, body_diff, failp, endp, donep, percent), X, s->stream));
     return 0;
 }
 
@@ -1271,6 +1297,37 @@ int kp_sim_post_step(kp_sim* s, const kp_ctx* c, const kp_reward_cfg* w, int32_t
     HIP_OK(hipSetDevice(s->device));
     const kp::PostStep PS{cur_t, row_len, env_episode_len, done, end, percent, done_count, obj7, obj7 ? s->obj.qpos : nullptr};
     return launch_term_reward(s, c, w, reward, info, failp, diffs, &PS);
+}
+
+// dynamic_supervision_v2: the same two entries on k_term_reward<POST, 2, RewardW2>
+static int launch_term_reward_v2(kp_sim* s, const kp_ctx* c, const kp_reward_cfg_v2* w, float* reward, float* info, uint8_t* failp, float* diffs, const kp::PostStep* post) {
+    const StateRows& st = s->st;
+    const kp::RewardW2 W{w->w_hp, w->w_hq, w->w_p, w->w_v, w->w_e, w->k_hp, w->k_hq, w->k_p, w->k_v, w->k_e, w->dt, w->body_diff_thresh, w->body_diff_gt_thresh,
+                         w->use_gt_term, w->b_diffw};
+    if (!post) hipLaunchKernelGGL((kp::k_term_reward<false, 2, kp::RewardW2>), dim3((s->n + 7) / 8), dim3(256), 0, s->stream, s->n, to_dev(c), W, st.qpos, st.xpos, st.xquat,
+                                  s->tgt.wbpos, s->tgt.bquat, st.prev_bquat, st.prev_hpos, s->diffw, reward, info, failp, diffs, kp::PostStep{});
+    else hipLaunchKernelGGL((kp::k_term_reward<true, 2, kp::RewardW2>), dim3((s->n + 7) / 8), dim3(256), 0, s->stream, s->n, to_dev(c), W, st.qpos, st.xpos, st.xquat,
+                            s->tgt.wbpos, s->tgt.bquat, st.prev_bquat, st.prev_hpos, s->diffw, reward, info, failp, diffs, *post);
+    return launched();
+}
+
+int kp_sim_term_reward_v2(kp_sim* s, const kp_ctx* c, const kp_reward_cfg_v2* w, float* reward, float* info, uint8_t* failp, float* diffs) {
+    if (!s || !c || !w || !w->b_diffw || !reward || !info || !failp || !diffs || !c->head_pose || !c->gt_bquat || !c->gt_wbpos || !c->cur_t || c->T < 2)
+        return fail("kp_sim_term_reward_v2: bad arguments");
+    HIP_OK(hipSetDevice(s->device));
+    return launch_term_reward_v2(s, c, w, reward, info, failp, diffs, nullptr);
+}
+
+int kp_sim_post_step_v2(kp_sim* s, const kp_ctx* c, const kp_reward_cfg_v2* w, int32_t* cur_t, const int32_t* row_len, int env_episode_len,
+                        float* reward, float* info, uint8_t* failp, float* diffs, uint8_t* done, uint8_t* end, float* percent, int32_t* done_count, float* obj7) {
+    if (!s || !c || !w || !w->b_diffw || !cur_t || !row_len || !reward || !info || !failp || !diffs || !done || !end || !percent || !c->head_pose || !c->gt_bquat ||
+        !c->gt_wbpos || c->T < 2)
+        return fail("kp_sim_post_step_v2: bad arguments");
+    if (c->cur_t != cur_t) return fail("kp_sim_post_step_v2: cur_t must be the buffer the context reads (kp_ctx.cur_t)");
+    if (obj7 && !c->action_one_hot) return fail("kp_sim_post_step_v2: obj7 needs the context's action_one_hot");
+    HIP_OK(hipSetDevice(s->device));
+    const kp::PostStep PS{cur_t, row_len, env_episode_len, done, end, percent, done_count, obj7, obj7 ? s->obj.qpos : nullptr};
+    return launch_term_reward_v2(s, c, w, reward, info, failp, diffs, &PS);
 }
 
 int kp_sim_reset_rows(kp_sim* s, const float* init_qpos, const float* init_qvel, const int32_t* row, const uint8_t* mask, int32_t* cur_t, int set_target,

@@ -33,6 +33,24 @@ __device__ __forceinline__ V3 tk_rotate_t(Q4 q, V3 v) {
     return v + (q.w / n) * t + cross(u, t);
 }
 __device__ __forceinline__ float tk_clamp10(float v) { return fminf(fmaxf(v, -10.0f), 10.0f); }
+// get_qvel_fd_new's root angular velocity (math.py:47-54): axis * angle of next (x) cur^-1 over dt, the angle wrapped to below pi, in cur's frame
+__device__ __forceinline__ V3 tk_root_angvel(Q4 cq, Q4 nq, float inv_dt) {
+    const Q4 qrel = qmul(nq, q_inverse(cq));
+    const float n2 = qrel.x * qrel.x + qrel.y * qrel.y + qrel.z * qrel.z;
+    V3 axis = v3(1.f, 0.f, 0.f);
+    float angle = 0.f;
+    if (!(n2 < 1e-8f * (1.0f + fabsf(qrel.w)))) {
+        const float sn = sqrtf(n2), s = fmaxf(sn, 1e-30f);
+        axis = v3(qrel.x / s, qrel.y / s, qrel.z / s); angle = 2.0f * atan2f(sn, qrel.w);
+    }
+    if (angle > TK_PI) angle -= 2.0f * TK_PI;
+    return tk_rotate_t(cq, v3(axis.x * angle * inv_dt, axis.y * angle * inv_dt, axis.z * angle * inv_dt));
+}
+// multi_quat_norm (math.py:170-174) of q1 (x) q0^-1 for unit quaternions: acos(|w|) as the angle of the point (|w|, |xyz|)
+__device__ __forceinline__ float tk_quat_dist(Q4 q1, Q4 q0) {
+    const Q4 qd = qmul(q1, q_inverse(q0));
+    return atan2f(sqrtf(qd.x * qd.x + qd.y * qd.y + qd.z * qd.z), fabsf(qd.w));
+}
 
 // the expert row `ro` becomes the stored target (what kp_sim_set_target computes from the same qpos row: the tables ARE k_target_fk's outputs, the
 // target's bquat has the normalised root) and row `rb` the next control step's base pose (joint angles a_ref for action_v 0)
@@ -89,16 +107,7 @@ __global__ __launch_bounds__(64) void k_take_tables(TakeBuildArgs A) {
     float* qv = L.tab[TT_QVEL] + row * 75;
     if (lane == 6) {
         const V3 v = v3(tk_clamp10((qn[0] - qc[0]) * inv_dt), tk_clamp10((qn[1] - qc[1]) * inv_dt), tk_clamp10((qn[2] - qc[2]) * inv_dt));
-        const Q4 cq = ldq(qc + 3), qrel = qmul(ldq(qn + 3), q_inverse(cq));
-        const float n2 = qrel.x * qrel.x + qrel.y * qrel.y + qrel.z * qrel.z;
-        V3 axis = v3(1.f, 0.f, 0.f);
-        float angle = 0.f;
-        if (!(n2 < 1e-8f * (1.0f + fabsf(qrel.w)))) {
-            const float sn = sqrtf(n2), s = fmaxf(sn, 1e-30f);
-            axis = v3(qrel.x / s, qrel.y / s, qrel.z / s); angle = 2.0f * atan2f(sn, qrel.w);
-        }
-        if (angle > TK_PI) angle -= 2.0f * TK_PI;
-        V3 w = tk_rotate_t(cq, v3(axis.x * angle * inv_dt, axis.y * angle * inv_dt, axis.z * angle * inv_dt));
+        V3 w = tk_root_angvel(ldq(qc + 3), ldq(qn + 3), inv_dt);
         w = v3(tk_clamp10(w.x), tk_clamp10(w.y), tk_clamp10(w.z));
         st3(qv, v); st3(qv + 3, w);
         st3(L.tab[TT_RLINV] + row * 3, v); st3(L.tab[TT_RANGV] + row * 3, w);
@@ -130,8 +139,13 @@ __global__ __launch_bounds__(64) void k_take_minima(TakeTables L) {
     if (lane == 0) { L.tab[TT_HEIGHT_LB][k] = h; L.tab[TT_HEAD_HEIGHT_LB][k] = hh; }
 }
 
-// grid = n workgroups of one wavefront, lane = body
-__global__ __launch_bounds__(64) void k_uhc_track(UhcTrackArgs A) {
+// k_uhc_track's body for one function RID (KP_UHC_*) of the reward registry.  Everything but the reward section is the same for every RID; X is read
+// only by the RIDs that need it, and RID 0 is the kernel as it was before the family existed, statement for statement.
+template <int RID>
+__device__ __forceinline__ void tk_track(const UhcTrackArgs& A, const UhcRewardExt& X) {
+    constexpr bool WORLD_V1 = RID == KP_UHC_WORLD_RFC_IMPLICIT || RID == KP_UHC_WORLD_RFC_IMPLICIT_V1_MUL;
+    constexpr bool LOCAL = RID == KP_UHC_LOCAL_RFC_IMPLICIT;
+    constexpr bool WORLD_V2 = RID == KP_UHC_WORLD_RFC_IMPLICIT_V2 || RID == KP_UHC_WORLD_RFC_IMPLICIT_V3;
     const TakeTables& L = A.L;
     const int lane = threadIdx.x;
     const size_t e = blockIdx.x;
@@ -152,30 +166,78 @@ __global__ __launch_bounds__(64) void k_uhc_track(UhcTrackArgs A) {
     const V3 xi = ld3(A.xipos + e * 72 + 3 * b);
     const float msum = wave_sum(m);
     const V3 com = v3(wave_sum(m * xi.x) / msum, wave_sum(m * xi.y) / msum, wave_sum(m * xi.z) / msum);
-    // world_rfc_implicit_reward (reward_function.py:4-53)
+    // world_rfc_implicit_reward (reward_function.py:4-53) and its siblings: the per-body sums every function starts from
     const float* q = A.qpos + e * 76;
     const Q4 bq = b == 0 ? ldq(q + 3) : q_euler_sxyz(q[7 + 3 * (b - 1)], q[8 + 3 * (b - 1)], q[9 + 3 * (b - 1)]);
     const Q4 ebq = ldq(L.tab[TT_BQUAT] + row * 96 + 4 * b);
     const Q4 qd = qmul(bq, q_inverse(ebq));
-    const float pd = atan2f(sqrtf(qd.x * qd.x + qd.y * qd.y + qd.z * qd.z), fabsf(qd.w)) * A.b_diffw[b];       // acos(|w|)
-    const float pose_s = wave_sum(body ? pd * pd : 0.f);
+    const float pd = atan2f(sqrtf(qd.x * qd.x + qd.y * qd.y + qd.z * qd.z), fabsf(qd.w)) * (WORLD_V2 ? X.jw[b] : A.b_diffw[b]);       // acos(|w|)
+    const bool in_pose = LOCAL ? (body && lane > 0) : body;                     // local_rfc_implicit ignores the root (:204, 209)
+    const float pose_s = wave_sum(in_pose ? pd * pd : 0.f);
     const V3 dv = tk_angvel(ldq(A.prev_bquat + e * 96 + 4 * b), bq, A.inv_dt) - ld3(L.tab[TT_BANGVEL] + row * 72 + 3 * b);
-    const float vel_s = wave_sum(body ? dot(dv, dv) : 0.f);
-    const int eb = TK_EE[lane < 5 ? lane : 0];
-    const V3 de = ld3(A.xpos + e * 72 + 3 * eb) - ld3(L.tab[TT_EE_WPOS] + row * 15 + 3 * (lane < 5 ? lane : 0));
-    const float ee_s = wave_sum(lane < 5 ? dot(de, de) : 0.f);
-    const V3 dc = com - ld3(L.tab[TT_COM] + row * 3);
+    const float vel_s = wave_sum(in_pose ? dot(dv, dv) : 0.f);
+    float ee_s = 0.f, wpose_s = 0.f, bcom_s = 0.f, jpos_s = 0.f;
+    V3 dc = v3(0.f, 0.f, 0.f);
+    if constexpr (WORLD_V2) {                                                   // world pose, per-body COM, joint positions (:339-361)
+        const float wd = tk_quat_dist(ldq(X.xquat + e * 96 + 4 * b), ldq(L.tab[TT_WBQUAT] + row * 96 + 4 * b)) * X.jw[b];
+        wpose_s = wave_sum(body ? wd * wd : 0.f);
+        const V3 db = X.jw[b] * (ld3(L.tab[TT_BODY_COM] + row * 72 + 3 * b) - xi);
+        bcom_s = wave_sum(body ? dot(db, db) : 0.f);
+        const V3 dj = X.jw[b] * (xp - ld3(L.tab[TT_WBPOS] + row * 72 + 3 * b));
+        jpos_s = wave_sum(body ? dot(dj, dj) : 0.f);
+    } else {
+        const int eb = TK_EE[lane < 5 ? lane : 0];
+        V3 de;
+        if constexpr (LOCAL)                                                    // get_ee_pos('root') against the table ee_pos (:192, 200)
+            de = tk_rotate_t(ldq(q + 3), ld3(A.xpos + e * 72 + 3 * eb) - ld3(q)) - ld3(L.tab[TT_EE_POS] + row * 15 + 3 * (lane < 5 ? lane : 0));
+        else
+            de = ld3(A.xpos + e * 72 + 3 * eb) - ld3(L.tab[TT_EE_WPOS] + row * 15 + 3 * (lane < 5 ? lane : 0));
+        ee_s = wave_sum(lane < 5 ? dot(de, de) : 0.f);
+        if constexpr (WORLD_V1) dc = com - ld3(L.tab[TT_COM] + row * 3);
+    }
     const int nvf = C.vf_dim > 0 ? C.vf_dim : C.action_dim;                     // action[-vf_dim:]; [-0:] is the whole action
     float vf = 0.f;
     for (int i = lane; i < nvf; i += 64) { const float a = A.action[e * C.action_dim + (C.action_dim - nvf) + i]; vf += a * a; }
     vf = wave_sum(vf);
     if (lane == 0) {
-        const float pose_r = expf(-C.k_p * pose_s), vel_r = expf(-C.k_v * vel_s), ee_r = expf(-C.k_e * ee_s), com_r = expf(-C.k_c * dot(dc, dc));
-        const float vf_r = C.w_vf > 0.f ? expf(-C.k_vf * vf) : 0.f;
-        const float r = C.w_p * pose_r + C.w_v * vel_r + C.w_e * ee_r + C.w_c * com_r + C.w_vf * vf_r;
-        A.reward[e] = r / (C.w_p + C.w_v + C.w_e + C.w_c + C.w_vf);
-        float* io = A.info + e * 5;
-        io[0] = pose_r; io[1] = vel_r; io[2] = ee_r; io[3] = com_r; io[4] = vf_r;
+        if constexpr (RID == KP_UHC_WORLD_RFC_IMPLICIT) {
+            const float pose_r = expf(-C.k_p * pose_s), vel_r = expf(-C.k_v * vel_s), ee_r = expf(-C.k_e * ee_s), com_r = expf(-C.k_c * dot(dc, dc));
+            const float vf_r = C.w_vf > 0.f ? expf(-C.k_vf * vf) : 0.f;
+            const float r = C.w_p * pose_r + C.w_v * vel_r + C.w_e * ee_r + C.w_c * com_r + C.w_vf * vf_r;
+            A.reward[e] = r / (C.w_p + C.w_v + C.w_e + C.w_c + C.w_vf);
+            float* io = A.info + e * 5;
+            io[0] = pose_r; io[1] = vel_r; io[2] = ee_r; io[3] = com_r; io[4] = vf_r;
+        } else if constexpr (RID == KP_UHC_WORLD_RFC_IMPLICIT_V1_MUL) {         // :80-102: the same terms multiplied, vf always on
+            const float pose_r = expf(-C.k_p * pose_s), vel_r = expf(-C.k_v * vel_s), ee_r = expf(-C.k_e * ee_s), com_r = expf(-C.k_c * dot(dc, dc));
+            const float vf_r = expf(-C.k_vf * vf);
+            A.reward[e] = pose_r * vel_r * ee_r * com_r * vf_r;
+            float* io = A.info + e * 5;
+            io[0] = pose_r; io[1] = vel_r; io[2] = ee_r; io[3] = com_r; io[4] = vf_r;
+        } else if constexpr (LOCAL) {                                           // :203-231
+            const float* pq = X.prev_qpos + e * 76;
+            const float* eq = L.tab[TT_QPOS] + row * 76;
+            const Q4 rq = ldq(q + 3);
+            const float rh = q[2] - eq[2];
+            const float rqd = tk_quat_dist(qmul(q_inverse(q_heading(rq)), rq), ldq(L.tab[TT_RQ_RMH] + row * 4));      // de_heading(qpos[3:7]) vs rq_rmh
+            // get_qvel_fd_new(prev_qpos, qpos, dt, 'root')[:6]: both velocities in the frame of prev_qpos' root (math.py:46-64), not clamped
+            const Q4 pr = ldq(pq + 3);
+            const V3 lv = tk_rotate_t(pr, v3((q[0] - pq[0]) * A.inv_dt, (q[1] - pq[1]) * A.inv_dt, (q[2] - pq[2]) * A.inv_dt)) - ld3(L.tab[TT_RLINV_LOCAL] + row * 3);
+            const V3 av = tk_root_angvel(pr, rq, A.inv_dt) - ld3(L.tab[TT_RANGV] + row * 3);
+            const float pose_r = expf(-C.k_p * pose_s), vel_r = expf(-C.k_v * vel_s), ee_r = expf(-C.k_e * ee_s);
+            const float rp_r = expf(-X.k_rh * (rh * rh) - X.k_rq * (rqd * rqd)), rv_r = expf(-X.k_rl * dot(lv, lv) - X.k_ra * dot(av, av));
+            const float vf_r = C.w_vf > 0.f ? expf(-C.k_vf * vf) : 0.f;
+            const float r = C.w_p * pose_r + C.w_v * vel_r + C.w_e * ee_r + X.w_rp * rp_r + X.w_rv * rv_r + C.w_vf * vf_r;
+            A.reward[e] = r / (C.w_p + C.w_v + C.w_e + X.w_rp + X.w_rv + C.w_vf);
+            float* io = A.info + e * 6;
+            io[0] = pose_r; io[1] = vel_r; io[2] = ee_r; io[3] = rp_r; io[4] = rv_r; io[5] = vf_r;
+        } else {                                                                // v2 :333-372, v3 :411-450: means of squares
+            const float pose_r = expf(-C.k_p * (pose_s / 24.0f)), wpose_r = expf(-X.k_wp * (wpose_s / 24.0f)), vel_r = expf(-C.k_v * (vel_s / 72.0f));
+            const float com_r = expf(-C.k_c * (bcom_s / 24.0f)), jpos_r = expf(-X.k_j * (jpos_s / 24.0f)), vf_r = expf(-C.k_vf * vf);
+            if constexpr (RID == KP_UHC_WORLD_RFC_IMPLICIT_V2) A.reward[e] = pose_r * wpose_r * com_r * jpos_r * vel_r * vf_r;
+            else A.reward[e] = C.w_p * pose_r + X.w_wp * wpose_r + C.w_c * com_r + X.w_j * jpos_r + C.w_v * vel_r + C.w_vf * vf_r;
+            float* io = A.info + e * 6;
+            io[0] = pose_r; io[1] = wpose_r; io[2] = com_r; io[3] = jpos_r; io[4] = vel_r; io[5] = vf_r;
+        }
         const bool fail = C.term_body && body_diff > C.body_diff_thresh;
         const bool end = t >= C.env_episode_len || start + t >= len + C.trail;        // cur_t + start_ind >= len + trail (humanoid_im.py:564)
         A.body_diff[e] = body_diff; A.fail[e] = fail; A.end[e] = end; A.done[e] = fail || end;
@@ -185,6 +247,11 @@ __global__ __launch_bounds__(64) void k_uhc_track(UhcTrackArgs A) {
     const size_t ro = (size_t)o0 + (size_t)min(start + (C.obs_v == 0 ? t : t + 1), len - 1);
     tk_write_targets(L, e, ro, row, A.t_qpos, A.t_wbpos, A.t_wbquat, A.t_bquat, A.t_com, A.st.base_qpos, C.a_ref, lane);
 }
+
+// grid = n workgroups of one wavefront, lane = body
+__global__ __launch_bounds__(64) void k_uhc_track(UhcTrackArgs A) { tk_track<KP_UHC_WORLD_RFC_IMPLICIT>(A, UhcRewardExt{}); }
+template <int RID>
+__global__ __launch_bounds__(64) void k_uhc_track_r(UhcTrackArgs A, UhcRewardExt X) { tk_track<RID>(A, X); }
 
 // k_uhc_assign's body for env e; returns the library row the state was read from
 __device__ __forceinline__ size_t tk_assign(const UhcAssignArgs& A, size_t e, int lane) {
@@ -278,6 +345,19 @@ hipError_t launch_take_tables(const TakeBuildArgs& A, hipStream_t stream) {
 
 hipError_t launch_uhc_track(const UhcTrackArgs& A, hipStream_t stream) {
     hipLaunchKernelGGL(k_uhc_track, dim3(A.n), dim3(64), 0, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_uhc_track_r(int reward_id, const UhcTrackArgs& A, const UhcRewardExt& X, hipStream_t stream) {
+    const dim3 grid(A.n), block(64);
+    switch (reward_id) {
+        case KP_UHC_WORLD_RFC_IMPLICIT: return launch_uhc_track(A, stream);      // the kernel kp_sim_uhc_track launches
+        case KP_UHC_WORLD_RFC_IMPLICIT_V1_MUL: hipLaunchKernelGGL(k_uhc_track_r<KP_UHC_WORLD_RFC_IMPLICIT_V1_MUL>, grid, block, 0, stream, A, X); break;
+        case KP_UHC_LOCAL_RFC_IMPLICIT: hipLaunchKernelGGL(k_uhc_track_r<KP_UHC_LOCAL_RFC_IMPLICIT>, grid, block, 0, stream, A, X); break;
+        case KP_UHC_WORLD_RFC_IMPLICIT_V2: hipLaunchKernelGGL(k_uhc_track_r<KP_UHC_WORLD_RFC_IMPLICIT_V2>, grid, block, 0, stream, A, X); break;
+        case KP_UHC_WORLD_RFC_IMPLICIT_V3: hipLaunchKernelGGL(k_uhc_track_r<KP_UHC_WORLD_RFC_IMPLICIT_V3>, grid, block, 0, stream, A, X); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 //   k_take_minima   height_lb / head_height_lb per take (tools.py:82-83)
 //   k_uhc_track     the tail of HumanoidEnv.step after do_simulation (uhc/envs/humanoid_im.py:527-572): cur_t, calc_body_diff, termination,
 //                   world_rfc_implicit_reward (uhc/core/reward_function.py:4-53), and the expert rows of the next observation / control step
+//   k_uhc_track_r   k_uhc_track with another function of the reward registry (reward_function.py:453-460; kp_sim_uhc_track_r), one instantiation each
 //   k_uhc_assign    reset_model / fail_safe (humanoid_im.py:574-623, 235-238): take, start and state of the masked envs
 //   k_uhc_assign_obj  the same for a library that carries object poses (kp_takes_create_obj): reset_model's has_obj branch (:613-616) installs the env's
 //                   object block from the library row the humanoid state comes from -- what kp_sim.hip's k_set_objects installs from a caller's rows
@@ -52,6 +53,14 @@ struct UhcTrackArgs {
     uint8_t *fail, *end, *done;
 };
 
+// what the other reward functions read beside UhcTrackArgs (k_uhc_track's arguments stay as they are)
+struct UhcRewardExt {
+    float w_rp, w_rv, k_rh, k_rq, k_rl, k_ra, w_wp, w_j, k_wp, k_j;
+    const float* jw;                  // [24] reward_weights.jpos_diffw (v2 / v3)
+    const float* prev_qpos;           // [N,76] the qpos before the control step (local_rfc_implicit)
+    const float* xquat;               // sim state after the control step (v2 / v3)
+};
+
 struct UhcAssignArgs {
     TakeTables L;
     int n, keep_t, obs_v;
@@ -77,6 +86,7 @@ struct UhcAssignObjArgs {
 
 hipError_t launch_take_tables(const TakeBuildArgs& A, hipStream_t stream);
 hipError_t launch_uhc_track(const UhcTrackArgs& A, hipStream_t stream);
+hipError_t launch_uhc_track_r(int reward_id, const UhcTrackArgs& A, const UhcRewardExt& X, hipStream_t stream);      // reward_id: KP_UHC_*
 hipError_t launch_uhc_assign(const UhcAssignArgs& A, hipStream_t stream);
 hipError_t launch_uhc_assign_obj(const UhcAssignObjArgs& A, hipStream_t stream);
 

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import sim as kpsim
+from .model_compiler import read_kpm
 from .nets import PolicyMCP
 
 CTX_KEYS = ("qpos", "head_pose", "head_vels", "obj_head_relative_poses", "action_one_hot", "init_qpos", "init_qvel")
@@ -74,6 +75,7 @@ class BatchedHumanoidAREnv:
         self.reward_cfg = kpsim.KpRewardCfg.default(use_gt_term=(mode == "train" and not wild))
         self.reward_cfg.body_diff_thresh = body_diff_thresh
         self.reward_cfg.body_diff_gt_thresh = body_diff_gt_thresh
+        self.reward_id, self._kpm_path, self._b_diffw = "dynamic_supervision_v1", kpm_path, None      # set_reward switches to dynamic_supervision_v2
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(seed)
         self.cur_t = torch.zeros(self.n, dtype=torch.int32, device=self.device)
@@ -110,6 +112,33 @@ class BatchedHumanoidAREnv:
     def set_mode(self, mode):
         self.mode = mode
         self.reward_cfg.use_gt_term = int(mode == "train" and not self.wild)
+
+    REWARD_IDS = ("dynamic_supervision_v1", "dynamic_supervision_v2")
+
+    def set_reward(self, reward_id: str):
+        """policy_specs.reward_id: the reward function of the step's tail, dynamic_supervision_v1 (kin_poly.yml) or dynamic_supervision_v2 (ground truth,
+        no dynamics regulation; reward_function.py:999-1050) with that function's default weights; the thresholds and the mode's use_gt_term carry over.
+        Config.apply_reward_weights calls this and then fills in the file's weights."""
+        if reward_id not in self.REWARD_IDS:
+            raise ValueError(f"reward_id {reward_id!r} (implemented: {', '.join(self.REWARD_IDS)})")
+        if reward_id != self.reward_id:
+            old = self.reward_cfg
+            if reward_id == "dynamic_supervision_v2":
+                if self._b_diffw is None:        # cc_cfg.b_diffw behind a root weight of 1: the blob's uhc_b_diffw
+                    self._b_diffw = torch.tensor(read_kpm(self._kpm_path)["uhc_b_diffw"], dtype=torch.float32, device=self.device)
+                new = kpsim.KpRewardCfgV2.default(self._b_diffw)
+            else:
+                new = kpsim.KpRewardCfg.default()
+            new.dt, new.body_diff_thresh, new.body_diff_gt_thresh, new.use_gt_term = old.dt, old.body_diff_thresh, old.body_diff_gt_thresh, old.use_gt_term
+            self.reward_cfg, self.reward_id = new, reward_id
+        return self.reward_cfg
+
+    def copy_reward(self, other):
+        """the reward function, weights and thresholds of another env; use_gt_term stays this env's (a property of the mode, not of the configuration)"""
+        self.set_reward(other.reward_id)
+        for k, _ in self.reward_cfg._fields_:
+            if k not in ("use_gt_term", "b_diffw"):
+                setattr(self.reward_cfg, k, getattr(other.reward_cfg, k))
 
     def alloc_context(self, R: int, T: int, objects: bool = False, with_ar: bool = False, obj_width: int = 14):
         """Empty context tables [R, T, .] (R a multiple of n_envs) that `write_context_rows` fills in place: what a sampler that keeps the next

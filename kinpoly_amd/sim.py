@@ -78,6 +78,17 @@ class KpRewardCfg(C.Structure):
         return cls(0.15, 0.15, 0.2, 0.2, 0.2, 0.1, 45.0, 45.0, 50.0, 50.0, 5.0, 0.005, 1.0 / 30.0, 10.0, 12.0, int(use_gt_term))
 
 
+class KpRewardCfgV2(C.Structure):
+    """mirror of kp_reward_cfg_v2 (dynamic_supervision_v2); defaults = its `ws.get(key, default)` list (reward_function.py:1003-1004) and the v1 thresholds"""
+    _fields_ = [(k, C.c_float) for k in ("w_hp", "w_hq", "w_p", "w_v", "w_e", "k_hp", "k_hq", "k_p", "k_v", "k_e", "dt", "body_diff_thresh",
+                                          "body_diff_gt_thresh")] + [("use_gt_term", C.c_int), ("b_diffw", C.c_void_p)]
+
+    @classmethod
+    def default(cls, b_diffw, use_gt_term=True):
+        """b_diffw: device float tensor [24] (root 1, then cc_cfg.b_diffw); the caller keeps it alive"""
+        return cls(1.0, 1.0, 0.6, 0.1, 0.2, 1.0, 1.0, 2.0, 0.005, 20.0, 1.0 / 30.0, 10.0, 12.0, int(use_gt_term), b_diffw.data_ptr())
+
+
 class KpUhcState(C.Structure):
     """mirror of kp_uhc_state"""
     _fields_ = [(k, C.c_void_p) for k in ("take_id", "start_ind", "cur_t", "base_qpos")]
@@ -87,6 +98,21 @@ class KpUhcCfg(C.Structure):
     """mirror of kp_uhc_cfg"""
     _fields_ = [(k, C.c_float) for k in ("w_p", "w_v", "w_e", "w_c", "w_vf", "k_p", "k_v", "k_e", "k_c", "k_vf")] + [("dt", C.c_double), ("body_diff_thresh", C.c_float)] + \
                [(k, C.c_int) for k in ("term_body", "env_episode_len", "trail", "obs_v", "vf_dim", "action_dim")] + [("a_ref", C.c_void_p), ("b_diffw", C.c_void_p)]
+
+
+UHC_REWARD_IDS = ("world_rfc_implicit", "world_rfc_implicit_v1_mul", "local_rfc_implicit", "world_rfc_implicit_v2", "world_rfc_implicit_v3")      # KP_UHC_*, in order
+
+
+def uhc_reward_info_dim(reward_id) -> int:
+    """the width of a reward function's info row (kp_uhc_reward_info_dim): reward_id a name of UHC_REWARD_IDS or its index"""
+    i = UHC_REWARD_IDS.index(reward_id) if isinstance(reward_id, str) else int(reward_id)
+    return 5 if i in (0, 1) else 6
+
+
+class KpUhcCfgR(C.Structure):
+    """mirror of kp_uhc_cfg_r"""
+    _fields_ = [("base", KpUhcCfg), ("reward_id", C.c_int)] + [(k, C.c_float) for k in ("w_rp", "w_rv", "k_rh", "k_rq", "k_rl", "k_ra", "w_wp", "w_j", "k_wp", "k_j")] + \
+               [("jpos_diffw", C.c_void_p), ("prev_qpos", C.c_void_p)]
 
 
 class KpRenderStyle(C.Structure):
@@ -128,7 +154,9 @@ _SIGNATURES = {
     "kp_field_dim": (_I, [_I]), "kp_sim_get": (_I, [_V, _I, _V]), "kp_sim_field_device": (_V, [_V, _I]),
     "kp_sim_term_reward": (_I, [_V, _CTX, _RW, _V, _V, _V, _V]),
     "kp_sim_post_step": (_I, [_V, _CTX, _RW, _V, _V, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
-    "kp_sim_reset_rows": (_I, [_V, _V, _V, _V, _V, _V, _I, _V, _I, _V, _V, _V]),
+    "kp_sim_term_reward_v2": (_I, [_V, _CTX, C.POINTER(KpRewardCfgV2), _V, _V, _V, _V]),
+    "kp_sim_post_step_v2": (_I, [_V, _CTX, C.POINTER(KpRewardCfgV2), _V, _V, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    "kp_sim_reset_rows": (_I,[_V, _V, _V, _V, _V, _V, _I, _V, _I, _V, _V, _V]),
     "kp_sim_diag": (_I, [_V, _V]), "kp_sim_lean_state": (_I, [_V, _V]), "kp_sim_launch_cost": (_I, [_V, _V]), "kp_job_schedule": (_I, [_I, _I, _I, _PI]),
     "kp_sim_last_step_seconds": (_D, [_V]), "kp_sim_timing_reset": (_I, [_V]), "kp_sim_timing_mean_seconds": (_D, [_V, _PI]),
     "kp_sim_phase_cycles": (_I, [_V, C.POINTER(_D)]), "kp_sim_phase_cycles_env": (_I, [_V, _V]),
@@ -136,6 +164,7 @@ _SIGNATURES = {
     "kp_takes_create_obj": (_V, [_V, _V, _V, _I, _V, _I, _D]), "kp_takes_has_objects": (_I, [_V]),
     "kp_takes_table": (_I, [_V, _S, C.POINTER(_V), _PI, _PI]), "kp_takes_info": (_I, [_V, _PI, _PI, _V]),
     "kp_sim_uhc_track": (_I, [_V, _V, _UST, _UCFG, _V, _V, _V, _V, _V, _V, _V, _V]), "kp_sim_uhc_assign": (_I, [_V, _V, _UST, _UCFG, _V, _V, _V, _I, _V]),
+    "kp_uhc_reward_info_dim": (_I, [_I]), "kp_sim_uhc_track_r": (_I, [_V, _V, _UST, C.POINTER(KpUhcCfgR), _V, _V, _V, _V, _V, _V, _V, _V]),
     # stand-alone kernels (no kp_sim): sizes, device arrays, ..., stream
     "kp_pool_advance": (_I, [_I, _I, _V, _V, _V, _V, _V]),
     "kp_rollout_record_pre": (_I, [_PRE, _V]), "kp_rollout_record_post": (_I, [_POST, _V]),
@@ -351,6 +380,12 @@ class KpSim:
                                        _ptr(info, self.n, 5), C.c_void_p(body_diff.data_ptr()), _mask_ptr(fail, self.n), _mask_ptr(end, self.n), _mask_ptr(done, self.n),
                                        C.c_void_p(percent.data_ptr())), "kp_sim_uhc_track")
 
+    def uhc_track_r(self, takes, st, cfg, cc_action, reward, info, body_diff, fail, end, done, percent):
+        """uhc_track with the reward function cfg.reward_id names (kp_sim_uhc_track_r); cfg: KpUhcCfgR; info [N, uhc_reward_info_dim(cfg.reward_id)]"""
+        _check(self.L.kp_sim_uhc_track_r(self.h, takes.h, C.byref(st), C.byref(cfg), _ptr(cc_action, self.n, self.cc_action_dim), C.c_void_p(reward.data_ptr()),
+                                         _ptr(info, self.n, uhc_reward_info_dim(cfg.reward_id)), C.c_void_p(body_diff.data_ptr()), _mask_ptr(fail, self.n),
+                                         _mask_ptr(end, self.n), _mask_ptr(done, self.n), C.c_void_p(percent.data_ptr())), "kp_sim_uhc_track_r")
+
     def uhc_assign(self, takes, st, cfg, env_mask=None, take_ids=None, start=None, keep_t=False, noise=None):
         """reset_model / fail_safe for the masked envs (kp_sim_uhc_assign); take_ids / start: host int32 arrays [N] or None"""
         ids = None if take_ids is None else np.ascontiguousarray(take_ids, np.int32)
@@ -559,22 +594,28 @@ class KpSim:
         the context block's cotangent, None when ctx_dim is 0)."""
         return self._obs_ar_backward("obs_ar_ex_backward", ctx, ext, qpos_rows, wbpos, wbquat, grad_obs, grad_obj_2_head)
 
-    def term_reward(self, ctx: "KpCtx", cfg: "KpRewardCfg", reward=None, info=None, fail=None, diffs=None):
+    def term_reward(self, ctx: "KpCtx", cfg: "KpRewardCfg | KpRewardCfgV2", reward=None, info=None, fail=None, diffs=None):
+        """termination + reward; the cfg's type names the reward: KpRewardCfg dynamic_supervision_v1, KpRewardCfgV2 dynamic_supervision_v2"""
+        v2 = isinstance(cfg, KpRewardCfgV2)
         reward = torch.empty(self.n, device=self.device) if reward is None else reward
         info = self._new(6) if info is None else info
         fail = torch.empty(self.n, dtype=torch.uint8, device=self.device) if fail is None else fail
         diffs = self._new(2) if diffs is None else diffs
-        _check(self.L.kp_sim_term_reward(self.h, C.byref(ctx), C.byref(cfg), C.c_void_p(reward.data_ptr()), _ptr(info, self.n, 6),
-                                         C.c_void_p(fail.data_ptr()), _ptr(diffs, self.n, 2)), "kp_sim_term_reward")
+        fn = self.L.kp_sim_term_reward_v2 if v2 else self.L.kp_sim_term_reward
+        _check(fn(self.h, C.byref(ctx), C.byref(cfg), C.c_void_p(reward.data_ptr()), _ptr(info, self.n, 6), C.c_void_p(fail.data_ptr()), _ptr(diffs, self.n, 2)),
+               "kp_sim_term_reward_v2" if v2 else "kp_sim_term_reward")
         return reward, info, fail, diffs
 
-    def post_step(self, ctx: "KpCtx", cfg: "KpRewardCfg", cur_t, row_len, episode_len, reward, info, fail, diffs, done, end, percent, done_count=None, obj7=None):
+    def post_step(self, ctx: "KpCtx", cfg: "KpRewardCfg | KpRewardCfgV2", cur_t, row_len, episode_len, reward, info, fail, diffs, done, end, percent, done_count=None, obj7=None):
         """cur_t += 1; termination + reward; end / done / percent -- the tail of HumanoidAREnv.step in one launch (kp_sim_post_step).
-        obj7 [N,7]: refreshed with the simulated pose of every env's action object (get_obj_qpos(action_one_hot))."""
-        _check(self.L.kp_sim_post_step(self.h, C.byref(ctx), C.byref(cfg), C.c_void_p(cur_t.data_ptr()), C.c_void_p(row_len.data_ptr()), int(episode_len),
-                                       C.c_void_p(reward.data_ptr()), _ptr(info, self.n, 6), C.c_void_p(fail.data_ptr()), _ptr(diffs, self.n, 2),
-                                       C.c_void_p(done.data_ptr()), C.c_void_p(end.data_ptr()), C.c_void_p(percent.data_ptr()),
-                                       None if done_count is None else C.c_void_p(done_count.data_ptr()), _ptr(obj7, self.n, 7)), "kp_sim_post_step")
+        obj7 [N,7]: refreshed with the simulated pose of every env's action object (get_obj_qpos(action_one_hot)).  A KpRewardCfgV2 runs
+        kp_sim_post_step_v2 (dynamic_supervision_v2)."""
+        v2 = isinstance(cfg, KpRewardCfgV2)
+        fn = self.L.kp_sim_post_step_v2 if v2 else self.L.kp_sim_post_step
+        _check(fn(self.h, C.byref(ctx), C.byref(cfg), C.c_void_p(cur_t.data_ptr()), C.c_void_p(row_len.data_ptr()), int(episode_len),
+                  C.c_void_p(reward.data_ptr()), _ptr(info, self.n, 6), C.c_void_p(fail.data_ptr()), _ptr(diffs, self.n, 2),
+                  C.c_void_p(done.data_ptr()), C.c_void_p(end.data_ptr()), C.c_void_p(percent.data_ptr()),
+                  None if done_count is None else C.c_void_p(done_count.data_ptr()), _ptr(obj7, self.n, 7)), "kp_sim_post_step_v2" if v2 else "kp_sim_post_step")
 
     def reset_rows(self, init_qpos, init_qvel, row=None, env_mask=None, cur_t=None, set_target=True, aux_rows=None, row_obj_qpos=None, row_one_hot=None, obj7=None):
         """masked reset from context rows: state <- init rows, cur_t = 0, sim.forward(), target = FK(init) (kp_sim_reset_rows).

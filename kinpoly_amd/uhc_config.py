@@ -8,7 +8,8 @@ its controller and scripts/train_uhc.py read, with the reference's defaults wher
 What the engine runs of the file: the observation switches obs_v (0 get_full_obs, 1 get_full_obs_v1, 2 get_full_obs_v2), obs_vel ('full' / 'root'),
 and obs_v 0's obs_heading / root_deheading / obs_phase (the HIP kernel k_obs_cc); actor_type 'gauss' (PolicyGaussian) or 'mcp' (PolicyMCP);
 env_term_body 'body' (calc_body_diff > 0.5) or the default 'head', which the reference's if / elif chain never matches (humanoid_im.py:554-561), so
-such an episode never fails; the PPO constants and reward_weights; the controller's action_v (1: PD target about the expert's kinematic pose, 0: about
+such an episode never fails; the PPO constants; reward_id (the five implicit-RFC functions of the reward registry, REWARD_DEFAULTS; the two explicit
+ones and the default 'quat' are refused, REFUSED_REWARDS) and reward_weights with that function's own defaults; the controller's action_v (1: PD target about the expert's kinematic pose, 0: about
 a_ref = deg2rad of joint_params column 3, without the 2 pi unwrap), residual_force (implicit, or off) and meta_pd / meta_pd_joint (the step kernel's
 extended controller, cc_action_v / cc_rfc / cc_meta_pd).  Any other value of a key the engine reads is refused with a ConfigError that names the key,
 the value and what is implemented, instead of running as if the file were uhc.yml.  Nothing here needs a GPU.
@@ -24,6 +25,23 @@ import yaml
 from .config import ConfigError
 
 NDOF = 69                   # actuated joint angles (model.actuator_ctrlrange.shape[0])
+
+
+# the reward registry (uhc/core/reward_function.py:453-460): every function's own `ws.get(key, default)` list -- the same key has different defaults
+# in different functions (k_p 2 / 0.4, k_c 1000 / 100, w_vf 0 / 0.1 / 1)
+REWARD_DEFAULTS = {
+    "world_rfc_implicit": dict(w_p=0.6, w_v=0.1, w_e=0.2, w_c=0.1, w_vf=0.0, k_p=2.0, k_v=0.005, k_e=20.0, k_c=1000.0, k_vf=1.0),                      # :7-9
+    "world_rfc_implicit_v1_mul": dict(k_p=2.0, k_v=0.005, k_e=20.0, k_c=1000.0, k_vf=1.0),                                                             # :60
+    "local_rfc_implicit": dict(w_p=0.5, w_v=0.0, w_e=0.2, w_rp=0.1, w_rv=0.1, w_vf=0.1, k_p=2.0, k_v=0.005, k_e=20.0, k_vf=1.0,
+                               k_rh=300.0, k_rq=300.0, k_rl=5.0, k_ra=0.5),                                                                            # :176-178
+    "world_rfc_implicit_v2": dict(k_p=0.4, k_wp=0.4, k_v=0.005, k_j=100.0, k_c=100.0, k_vf=1.0),                                                       # :305-307
+    "world_rfc_implicit_v3": dict(w_p=0.4, w_wp=0.4, w_v=0.005, w_j=100.0, w_c=100.0, w_vf=1.0, k_p=0.4, k_wp=0.4, k_v=0.005, k_j=100.0, k_c=100.0,
+                                  k_vf=1.0),                                                                                                           # :380-385
+}
+_EXPLICIT_WHY = ("it reads env.vf_bodies / env.body_vf_dim, which only residual_force_mode 'explicit' sets (humanoid_im.py:76-82), and that mode "
+                 "cannot run in the reference")
+REFUSED_REWARDS = {"world_rfc_explicit": _EXPLICIT_WHY, "local_rfc_explicit": _EXPLICIT_WHY,
+                   "quat": "the reference's default names no function of its registry (reward_function.py:453-460)"}
 
 
 def uhc_obs_dim(obs_v: int, obs_vel: str = "full", obs_heading: bool = False, obs_phase: bool = True) -> int:
@@ -120,7 +138,13 @@ class UhcConfig:
         need("actor_type", self.actor_type, self.actor_type in ("gauss", "mcp"), "'gauss' (PolicyGaussian) or 'mcp' (PolicyMCP)")
         need("env_term_body", self.env_term_body, self.env_term_body in ("head", "body"),
              "'body' (calc_body_diff) or 'head' (never fails, as in the reference)")
-        need("reward_id", self.reward_id, self.reward_id == "world_rfc_implicit", "'world_rfc_implicit'")
+        if self.reward_id in REFUSED_REWARDS:
+            bad.append(f"reward_id: {self.reward_id!r} (implemented: {', '.join(map(repr, REWARD_DEFAULTS))}; {REFUSED_REWARDS[self.reward_id]})")
+        else:
+            need("reward_id", self.reward_id, self.reward_id in REWARD_DEFAULTS, ", ".join(map(repr, REWARD_DEFAULTS)))
+        jw = self.reward_weights.get("jpos_diffw")
+        if jw is not None and (not isinstance(jw, (list, tuple)) or len(jw) != 24):
+            bad.append(f"reward_weights.jpos_diffw: {jw!r} (implemented: 24 numbers, one per body)")
         for k, v in (("residual_force_scale", 100.0), ("residual_force_lim", 100.0)):
             need(k, getattr(self, k), float(getattr(self, k)) == v, f"{v:g} (the compiled model blob carries uhc.yml's)")
         for k in ("jkp_multiplier", "jkd_multiplier", "torque_limit_multiplier"):
@@ -165,9 +189,12 @@ class UhcConfig:
         return Value(MLP(self.obs_dim, tuple(self.value_hsize), self.value_htype))
 
     def full_reward_weights(self) -> dict:
-        """world_rfc_implicit_reward's `ws.get(key, default)` (uhc/core/reward_function.py:7-9)."""
-        d = dict(w_p=0.6, w_v=0.1, w_e=0.2, w_c=0.1, w_vf=0.0, k_p=2.0, k_v=0.005, k_e=20.0, k_c=1000.0, k_vf=1.0)
+        """reward_func[reward_id]'s `ws.get(key, default)` with that function's own defaults (REWARD_DEFAULTS); for v2 / v3 also `jpos_diffw`, the
+        24 numbers of reward_weights.jpos_diffw (default all 1; not cfg.jpos_diffw)."""
+        d = dict(REWARD_DEFAULTS.get(self.reward_id, REWARD_DEFAULTS["world_rfc_implicit"]))
         d.update({k: float(v) for k, v in self.reward_weights.items() if k in d})
+        if self.reward_id in ("world_rfc_implicit_v2", "world_rfc_implicit_v3"):
+            d["jpos_diffw"] = [float(v) for v in self.reward_weights.get("jpos_diffw", [1.0] * 24)]
         return d
 
     def ppo_kwargs(self) -> dict:

@@ -5,6 +5,8 @@ It runs on the same C-ABI entry points as the kinematic-policy env: `kp_sim_step
 `get_full_obs_v1` against the expert frame t + 1 (installed with `kp_sim_set_target`), `kp_sim_fk` does the clip's forward
 kinematics.  Reward (`world_rfc_implicit_reward`, uhc/core/reward_function.py:4-53) and termination (`calc_body_diff`, the MEAN
 form of humanoid_im.py:719-726, threshold 0.5) are a handful of [N, .] tensor ops.  SURVEY.md section 8(f) row 3.
+The other functions of the reward registry (:453-460) are the `*_reward_t` functions below on this single-clip path and
+`kp_sim_uhc_track_r` on a take library; `reward_id` comes from the UhcConfig (or the constructor).
 """
 from __future__ import annotations
 
@@ -103,20 +105,104 @@ def world_rfc_implicit_reward_t(xpos, bquat, prev_bquat, com, action, e_bquat, e
     return r / (ws["w_p"] + ws["w_v"] + ws["w_e"] + ws["w_c"] + ws["w_vf"]), torch.stack([pose_r, vel_r, ee_r, com_r, vf_r], 1)
 
 
+def quat_angle_t(q1, q0):
+    """multi_quat_norm(multi_quat_diff(q1, q0)) (math.py:158-174) on [..., 4]: acos(|w|) of q1 (x) q0^-1, in fp32 as the angle of the point (|w|, |xyz|)."""
+    qd = quat_mul(q1, quat_inv(q0))
+    return torch.acos(qd[..., 0].abs().clamp(-1.0, 1.0)) if qd.dtype == torch.float64 else torch.atan2(quat_sin_half(qd), qd[..., 0].abs())
+
+
+def _vf_term(action, ws, vf_dim):
+    vf = action[:, -vf_dim:] if vf_dim > 0 else action                  # action[-env.vf_dim:]; [-0:] is the whole action
+    return torch.exp(-ws["k_vf"] * (vf ** 2).sum(1))
+
+
+def world_rfc_implicit_v1_mul_reward_t(xpos, bquat, prev_bquat, com, action, e_bquat, e_bangvel, e_ee_wpos, e_com, b_diffw, dt=1.0 / 30.0, ws=None, vf_dim=6):
+    """uhc/core/reward_function.py:56-102 -> (reward [N], info [N, 5]): world_rfc_implicit's five terms multiplied, the vf term always on."""
+    N = xpos.shape[0]
+    cur_ee = xpos.view(N, 24, 3)[:, list(EE_BODIES)].reshape(N, 15)
+    pose_diff = quat_angle_t(bquat.view(N, 24, 4), e_bquat.view(N, 24, 4)) * b_diffw[None]
+    pose_r = torch.exp(-ws["k_p"] * (pose_diff ** 2).sum(1))
+    vel_r = torch.exp(-ws["k_v"] * ((get_angvel_fd_t(prev_bquat, bquat, dt) - e_bangvel) ** 2).sum(1))
+    ee_r = torch.exp(-ws["k_e"] * ((cur_ee - e_ee_wpos) ** 2).sum(1))
+    com_r = torch.exp(-ws["k_c"] * ((com - e_com) ** 2).sum(1))
+    vf_r = _vf_term(action, ws, vf_dim)
+    return pose_r * vel_r * ee_r * com_r * vf_r, torch.stack([pose_r, vel_r, ee_r, com_r, vf_r], 1)
+
+
+def local_rfc_implicit_reward_t(qpos, prev_qpos, xpos, bquat, prev_bquat, action, e_qpos, e_bquat, e_bangvel, e_ee_pos, e_rq_rmh, e_rlinv_local, e_rangv,
+                                b_diffw, dt=1.0 / 30.0, ws=None, vf_dim=6):
+    """uhc/core/reward_function.py:172-231 -> (reward [N], info [N, 6] = pose, vel, ee, root pose, root vel, vf).  b_diffw [24] as the world rewards take
+    it (its root entry is not read: pose and velocity ignore the root).  The root velocities are get_qvel_fd_new(prev_qpos, qpos, dt, 'root')[:6]: both in
+    the frame of prev_qpos' root, unclamped."""
+    N = xpos.shape[0]
+    rootq = qpos[:, 3:7]
+    ee = xpos.view(N, 24, 3)[:, list(EE_BODIES)]
+    cur_ee = quat_rotate_t(rootq[:, None].expand(N, 5, 4), ee - qpos[:, None, :3]).reshape(N, 15)
+    pose_diff = quat_angle_t(bquat.view(N, 24, 4)[:, 1:], e_bquat.view(N, 24, 4)[:, 1:]) * b_diffw[None, 1:]
+    pose_r = torch.exp(-ws["k_p"] * (pose_diff ** 2).sum(1))
+    vel_r = torch.exp(-ws["k_v"] * ((get_angvel_fd_t(prev_bquat, bquat, dt) - e_bangvel)[:, 3:] ** 2).sum(1))
+    ee_r = torch.exp(-ws["k_e"] * ((cur_ee - e_ee_pos) ** 2).sum(1))
+    h = torch.zeros_like(rootq); h[:, 0] = rootq[:, 0]; h[:, 3] = rootq[:, 3]
+    h = h / h.norm(dim=-1, keepdim=True)
+    rq_dist = quat_angle_t(quat_mul(quat_inv(h), rootq), e_rq_rmh)       # de_heading(qpos[3:7]) against rq_rmh
+    rp_r = torch.exp(-ws["k_rh"] * (qpos[:, 2] - e_qpos[:, 2]) ** 2 - ws["k_rq"] * rq_dist ** 2)
+    qv = get_qvel_fd_new_t(prev_qpos, qpos, dt)
+    linv = quat_rotate_t(prev_qpos[:, 3:7], qv[:, :3])
+    rv_r = torch.exp(-ws["k_rl"] * ((linv - e_rlinv_local) ** 2).sum(1) - ws["k_ra"] * ((qv[:, 3:6] - e_rangv) ** 2).sum(1))
+    vf_r = _vf_term(action, ws, vf_dim) if ws["w_vf"] > 0 else torch.zeros_like(pose_r)
+    r = ws["w_p"] * pose_r + ws["w_v"] * vel_r + ws["w_e"] * ee_r + ws["w_rp"] * rp_r + ws["w_rv"] * rv_r + ws["w_vf"] * vf_r
+    return r / (ws["w_p"] + ws["w_v"] + ws["w_e"] + ws["w_rp"] + ws["w_rv"] + ws["w_vf"]), torch.stack([pose_r, vel_r, ee_r, rp_r, rv_r, vf_r], 1)
+
+
+def _world_v2_terms(xpos, xquat, xipos, bquat, prev_bquat, action, e_bquat, e_wbquat, e_bangvel, e_wbpos, e_body_com, jw, dt, ws, vf_dim):
+    N = xpos.shape[0]
+    pose_r = torch.exp(-ws["k_p"] * ((quat_angle_t(bquat.view(N, 24, 4), e_bquat.view(N, 24, 4)) * jw[None]) ** 2).mean(1))
+    wpose_r = torch.exp(-ws["k_wp"] * ((quat_angle_t(xquat.view(N, 24, 4), e_wbquat.view(N, 24, 4)) * jw[None]) ** 2).mean(1))
+    vel_r = torch.exp(-ws["k_v"] * ((get_angvel_fd_t(prev_bquat, bquat, dt) - e_bangvel) ** 2).mean(1))
+    com_r = torch.exp(-ws["k_c"] * ((((e_body_com - xipos).view(N, 24, 3) * jw[None, :, None]) ** 2).sum(2)).mean(1))
+    jpos_r = torch.exp(-ws["k_j"] * ((((xpos - e_wbpos).view(N, 24, 3) * jw[None, :, None]) ** 2).sum(2)).mean(1))
+    return pose_r, wpose_r, com_r, jpos_r, vel_r, _vf_term(action, ws, vf_dim)
+
+
+def world_rfc_implicit_v2_reward_t(xpos, xquat, xipos, bquat, prev_bquat, action, e_bquat, e_wbquat, e_bangvel, e_wbpos, e_body_com, jw, dt=1.0 / 30.0, ws=None, vf_dim=6):
+    """uhc/core/reward_function.py:301-372 -> (reward [N], info [N, 6] = pose, wpose, com, jpos, vel, vf): every distance a mean of squares, the terms
+    multiplied.  jw [24] is reward_weights.jpos_diffw."""
+    terms = _world_v2_terms(xpos, xquat, xipos, bquat, prev_bquat, action, e_bquat, e_wbquat, e_bangvel, e_wbpos, e_body_com, jw, dt, ws, vf_dim)
+    pose_r, wpose_r, com_r, jpos_r, vel_r, vf_r = terms
+    return pose_r * wpose_r * com_r * jpos_r * vel_r * vf_r, torch.stack(terms, 1)
+
+
+def world_rfc_implicit_v3_reward_t(xpos, xquat, xipos, bquat, prev_bquat, action, e_bquat, e_wbquat, e_bangvel, e_wbpos, e_body_com, jw, dt=1.0 / 30.0, ws=None, vf_dim=6):
+    """uhc/core/reward_function.py:376-450: v2's terms in a weighted sum that is not normalised."""
+    terms = _world_v2_terms(xpos, xquat, xipos, bquat, prev_bquat, action, e_bquat, e_wbquat, e_bangvel, e_wbpos, e_body_com, jw, dt, ws, vf_dim)
+    pose_r, wpose_r, com_r, jpos_r, vel_r, vf_r = terms
+    r = ws["w_p"] * pose_r + ws["w_wp"] * wpose_r + ws["w_c"] * com_r + ws["w_j"] * jpos_r + ws["w_v"] * vel_r + ws["w_vf"] * vf_r
+    return r, torch.stack(terms, 1)
+
+
 class BatchedHumanoidEnv:
-    """HumanoidEnv (UHC imitation env) x N.  `load_expert(qpos [N, T, 76])`, `reset(mask)`, `step(a [N, action_dim])`.
+    """HumanoidEnv (UHC imitation env) x N. `load_expert(qpos [N, T, 76])`, `reset(mask)`, `step(a [N, action_dim])`.
 
     cfg (a UhcConfig) selects the controller's observation (obs_v 0 / 1 / 2, obs_vel, obs_v 0's heading / de-heading / phase), the termination body
     and the episode / reward constants of its file; without it the env is uhc.yml's (784-d get_full_obs_v1, env_term_body 'body')."""
 
     def __init__(self, n_envs, device=0, kpm_path=None, env_episode_len=100000, env_init_noise=0.0, env_expert_trail_steps=0,
-                 body_diff_thresh=0.5, reward_weights=None, model_options=None, seed=0, cfg=None):
+                 body_diff_thresh=0.5, reward_weights=None, model_options=None, seed=0, cfg=None, reward_id=None):
         self.n = int(n_envs)
         self.cfg = cfg
         if cfg is not None:
             env_episode_len, env_init_noise, env_expert_trail_steps = cfg.env_episode_len, cfg.env_init_noise, cfg.env_expert_trail_steps
             reward_weights = reward_weights or cfg.full_reward_weights()
             model_options = {**(model_options or {}), **cfg.model_options()}
+            reward_id = reward_id or cfg.reward_id
+        # the function of the reward registry (reward_function.py:453-460); without a cfg and a reward_id the env is uhc.yml's, world_rfc_implicit
+        self.reward_id = reward_id or "world_rfc_implicit"
+        if self.reward_id not in kpsim.UHC_REWARD_IDS:
+            raise ValueError(f"reward_id {self.reward_id!r} (implemented: {', '.join(kpsim.UHC_REWARD_IDS)})")
+        if self.reward_id != "world_rfc_implicit":
+            from .uhc_config import REWARD_DEFAULTS
+            reward_weights = {**REWARD_DEFAULTS[self.reward_id], **(reward_weights or {})}      # that function's own `ws.get` defaults
+        self.info_dim = kpsim.uhc_reward_info_dim(self.reward_id)
         self.obs_v = cfg.obs_v if cfg is not None else 1
         self.vf_dim = cfg.vf_dim if cfg is not None else 6
         self.a_ref = None if cfg is None or cfg.action_v != 0 else cfg.a_ref
@@ -131,6 +217,9 @@ class BatchedHumanoidEnv:
         self.jpos_diffw = torch.tensor(kpm["body_diffw"], dtype=torch.float32, device=self.device)
         self.env_episode_len, self.env_init_noise, self.trail = env_episode_len, env_init_noise, env_expert_trail_steps
         self.body_diff_thresh, self.ws = body_diff_thresh, dict(reward_weights or UHC_REWARD_WEIGHTS)
+        # reward_weights.jpos_diffw of v2 / v3 (reward_function.py:307): 24 body weights of the reward alone, default all 1
+        self.rw_jpos_diffw = torch.tensor(self.ws.get("jpos_diffw") or [1.0] * 24, dtype=torch.float32, device=self.device)
+        self._prev_qpos = torch.zeros((self.n, 76), dtype=torch.float32, device=self.device) if self.reward_id == "local_rfc_implicit" else None
         self.frame_skip, self.dt = 15, self.model.get_option("timestep") * 15
         self.gen = torch.Generator(device=self.device); self.gen.manual_seed(seed)
         self.cur_t = torch.zeros(self.n, dtype=torch.long, device=self.device)
@@ -172,9 +261,16 @@ class BatchedHumanoidEnv:
         self._take_len = torch.as_tensor(library.lens, device=dev)
         self._st = kpsim.KpUhcState(self.take_id.data_ptr(), self.start_ind.data_ptr(), self.cur_t.data_ptr(), self._base.data_ptr())
         w = self.ws
-        self._tc = kpsim.KpUhcCfg(*[float(w[k]) for k in ("w_p", "w_v", "w_e", "w_c", "w_vf", "k_p", "k_v", "k_e", "k_c", "k_vf")], float(self.dt), float(self.body_diff_thresh),
+        other = self.reward_id != "world_rfc_implicit"
+        g = lambda k: float(w.get(k, 0.0)) if other else float(w[k])    # a key the env's reward function does not read is 0; world_rfc_implicit reads all ten
+        self._tc = kpsim.KpUhcCfg(*[g(k) for k in ("w_p", "w_v", "w_e", "w_c", "w_vf", "k_p", "k_v", "k_e", "k_c", "k_vf")], float(self.dt), float(self.body_diff_thresh),
                                   int(self.term_body == "body"), int(self.env_episode_len), int(self.trail), int(self.obs_v), int(self.vf_dim), int(self.action_dim),
                                   None if self.a_ref is None else self.a_ref.data_ptr(), self.b_diffw.data_ptr())
+        # the other functions of the registry go through kp_sim_uhc_track_r; world_rfc_implicit stays on kp_sim_uhc_track
+        self._tcr = None
+        if other:
+            self._tcr = kpsim.KpUhcCfgR(self._tc, kpsim.UHC_REWARD_IDS.index(self.reward_id), *[g(k) for k in ("w_rp", "w_rv", "k_rh", "k_rq", "k_rl", "k_ra", "w_wp", "w_j", "k_wp", "k_j")],
+                                        self.rw_jpos_diffw.data_ptr(), None if self._prev_qpos is None else self._prev_qpos.data_ptr())
         self._next_ids = np.arange(n, dtype=np.int32) % library.K if take_ids is None else np.ascontiguousarray(take_ids, np.int32)
 
     def _noise(self):
@@ -223,11 +319,14 @@ class BatchedHumanoidEnv:
             raise RuntimeError("load_takes: call reset() before the first step (the envs are on no take yet)")
         sim, n, dev = self.sim, self.n, self.device
         f = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)      # fresh outputs every step (the caller keeps them): allocator only, no launch
-        o = {"custom_reward": f(n), "custom_info": f(n, 5), "body_diff": f(n), "percent": f(n), "fail": f(n, dt=torch.uint8), "end": f(n, dt=torch.uint8),
+        o = {"custom_reward": f(n), "custom_info": f(n, self.info_dim), "body_diff": f(n), "percent": f(n), "fail": f(n, dt=torch.uint8), "end": f(n, dt=torch.uint8),
              "done": f(n, dt=torch.uint8)}
         sim.step_begin()
+        if self._prev_qpos is not None:                                # env.prev_qpos (humanoid_im.py:538): local_rfc_implicit's root velocities
+            self._prev_qpos.copy_(sim.view("qpos"))
         sim.step_ctrl_base(a.contiguous(), self._base, self.frame_skip)
-        sim.uhc_track(self.takes, self._st, self._tc, a, o["custom_reward"], o["custom_info"], o["body_diff"], o["fail"], o["end"], o["done"], o["percent"])
+        track, tc = (sim.uhc_track, self._tc) if self._tcr is None else (sim.uhc_track_r, self._tcr)
+        track(self.takes, self._st, tc, a, o["custom_reward"], o["custom_info"], o["body_diff"], o["fail"], o["end"], o["done"], o["percent"])
         obs = self._obs_takes()
         info = {k: (v.view(torch.bool) if v.dtype == torch.uint8 else v) for k, v in o.items()}
         return obs, torch.ones(self.n, device=self.device), info.pop("done"), info
@@ -260,6 +359,20 @@ class BatchedHumanoidEnv:
         self.sim.set_state(q0.contiguous(), self.expert["qvel"][:, 0].contiguous(), m8)
         return self._obs_now()
 
+    def _reward_clip(self, a, xpos, bquat, com, prev_qpos):
+        """reward_func[reward_id] of the single-clip path: the torch functions above on the expert rows of cur_t"""
+        sim, e, t = self.sim, self._e, self.cur_t
+        prev_bquat, tail = sim.get("prev_bquat"), (self.dt, self.ws, self.vf_dim)
+        if self.reward_id in ("world_rfc_implicit", "world_rfc_implicit_v1_mul"):
+            fn = world_rfc_implicit_reward_t if self.reward_id == "world_rfc_implicit" else world_rfc_implicit_v1_mul_reward_t
+            return fn(xpos, bquat, prev_bquat, com, a, e("bquat", t), e("bangvel", t), e("ee_wpos", t), e("com", t), self.b_diffw, *tail)
+        if self.reward_id == "local_rfc_implicit":
+            return local_rfc_implicit_reward_t(sim.get("qpos"), prev_qpos, xpos, bquat, prev_bquat, a, e("qpos", t), e("bquat", t), e("bangvel", t), e("ee_pos", t),
+                                               e("rq_rmh", t), e("rlinv_local", t), e("rangv", t), self.b_diffw, *tail)
+        fn = world_rfc_implicit_v2_reward_t if self.reward_id == "world_rfc_implicit_v2" else world_rfc_implicit_v3_reward_t
+        return fn(xpos, sim.get("xquat"), sim.get("xipos"), bquat, prev_bquat, a, e("bquat", t), e("wbquat", t), e("bangvel", t), e("wbpos", t), e("body_com", t),
+                  self.rw_jpos_diffw, *tail)
+
     def step(self, a: torch.Tensor):
         if self.takes is not None:
             return self._step_takes(a)
@@ -269,6 +382,7 @@ class BatchedHumanoidEnv:
         if self.a_ref is not None:                                     # action_v 0: cfg.a_ref (:451-452); the kernel skips the unwrap for it
             tq = tq.clone(); tq[:, 7:] = self.a_ref
         sim.set_target(tq)
+        prev_qpos = sim.get("qpos") if self._prev_qpos is not None else None       # env.prev_qpos (humanoid_im.py:538)
         sim.step_ctrl(a.contiguous(), self.frame_skip)
         self.cur_t += 1
         xpos, bquat = sim.get("xpos"), sim.get("bquat")
@@ -280,8 +394,7 @@ class BatchedHumanoidEnv:
         else:   # 'head': the reference's chain tests 'Head', 'root' and 'body' only (humanoid_im.py:554-561), so the default never fails an episode
             fail = torch.zeros_like(body_diff, dtype=torch.bool)
         end = (self.cur_t >= self.env_episode_len) | (self.cur_t >= self.expert["len"] + self.trail)
-        reward, rinfo = world_rfc_implicit_reward_t(xpos, bquat, sim.get("prev_bquat"), com, a, self._e("bquat", self.cur_t), self._e("bangvel", self.cur_t),
-                                                    self._e("ee_wpos", self.cur_t), self._e("com", self.cur_t), self.b_diffw, self.dt, self.ws, self.vf_dim)
+        reward, rinfo = self._reward_clip(a, xpos, bquat, com, prev_qpos)
         obs = self._obs_now()
         return obs, torch.ones(self.n, device=self.device), fail | end, {"fail": fail, "end": end, "percent": self.cur_t.float() / self.expert["len"],
                                                                         "custom_reward": reward, "custom_info": rinfo, "body_diff": body_diff}
