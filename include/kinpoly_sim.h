@@ -415,6 +415,24 @@ int kp_sim_set_full_state(kp_sim*, const float* qpos, const float* qvel, const f
  * (read them back with KP_OBJ_QPOS / KP_OBJ_QVEL).  Which objects are simulated stays as kp_sim_set_objects decided. */
 int kp_sim_set_obj_state(kp_sim*, const float* obj_qpos, const float* obj_qvel, const uint8_t* env_mask);
 
+/* An impulse push between two control steps; no reference counterpart (the reference never disturbs the character).  It is what a mujoco-py user
+ * gets from `data.qvel[:75] += dv` between two env.step calls, with dv = M(qpos)^-1 J_b(r)^T [p; l] worked out on the device: momentum-exact, and
+ * the same as kp_sim_set_full_state(qpos, qvel + dv, qpos_d, qvel_d) with the solver's warm start kept.  Per env:
+ *   entity  int32 [N] device: 0..23 the humanoid's bodies, 24 + k simulated object slot k (the numbering of kp_sim_contacts); -1 and every other
+ *           value = no push for this env (the values live on the device: the kernel checks them before it indexes with them);
+ *   offset  [N,3] or NULL (= the origin): the point the impulse acts at, in the entity's own frame, metres from its frame origin;
+ *   impulse [N,6]: p (linear, N s) and l (angular, N m s), world axes;
+ *   dqvel   [N,75] or NULL: receives dv of the humanoid; zero rows for object pushes and for envs without a push.
+ * Humanoid body b: r = xpos_b + R_b offset from kinematics computed anew at the CURRENT KP_QPOS (not the stale KP_QPOS_D of the read-outs),
+ * M = the joint-space inertia there, armature included (mj_fullM), solved matrix-free; KP_QVEL += dv.  Object slot k (a no-op unless that slot is
+ * simulated in the env): KP_OBJ_QVEL of the slot's object += M_obj^-1 g with the 6 x 6 free-joint inertia (armature included; 3 world translations
+ * of the body origin, 3 rotations about the body axes); the humanoid is untouched.  Everything else in the handle stays bit for bit: qpos,
+ * KP_QPOS_D / KP_QVEL_D and the derived arrays that belong to them, warm starts, targets, prev_*, the other entity's velocities, masked-out envs.
+ * An impulse of exact zeros stores nothing; two pushes in a row add.  The jump is applied with no constraint active: contacts and joint limits answer
+ * from the next substep on.  Works on every handle (floor / objects, any threads_per_env, lean or full launch form): it touches the stored rows only.
+ * Enqueued on the handle's stream, no sync.  Refused (-1, kp_last_error) before anything is launched: null handle, null entity, null impulse. */
+int kp_sim_apply_impulse(kp_sim*, const int32_t* entity, const float* offset, const float* impulse, const uint8_t* env_mask, float* dqvel);
+
 /* read-outs of the mujoco-py data fields the env uses (humanoid_im.py:342-416, humanoid_ar_v1.py:460-512) */
 typedef enum {
     KP_QPOS = 0,        /* data.qpos[:76]                    [N,76]  */

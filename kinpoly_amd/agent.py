@@ -42,8 +42,9 @@ class AgentAR:
                  cache_init_context=False, log_std=-3.2, policy_weightdecay=0.0, value_weightdecay=0.0, smooth=True, result_dir=None, eval_envs=None,
                  init_update=False, num_init_update=5, step_update_dyna=False, num_step_dyna_update=10, full_update=False, num_sample=20000, batch_size=128,
                  noise_std=0.0, cc_checkpoint=None, update_dtype=None, reference_bugs=True, min_batch_size=0, slice_ratio="slice_start", use_action=True,
-                 use_vel=False, use_head=True, use_context=False, of_dim=0, rnn_hdim=1024, mlp_hsize=(1024, 512, 256)):
-        """update_dtype: None = the update runs on the fp32 roll-out modules (fused HIP re-unroll); torch.float64 = the reference's training
+                 use_vel=False, use_head=True, use_context=False, of_dim=0, rnn_hdim=1024, mlp_hsize=(1024, 512, 256), push_schedule=None):
+        """push_schedule (kinpoly_amd.push.PushSchedule for n_envs, or None): the training env pushes its humanoids at the tail of every step it falls due.
+        update_dtype: None = the update runs on the fp32 roll-out modules (fused HIP re-unroll); torch.float64 = the reference's training
         precision on fp64 master copies (kinpoly_amd/update.py).  reference_bugs: reproduce the reference's generator-consumed gradient clip
         (PPOTrainer) and LoggerRL.merge's max-of-mins; False = the corrected forms.
         min_batch_size (kin_poly.yml:56, 10 000 in the reference; 0 = off): the reference updates once per >= min_batch_size samples.  4096 envs x H steps are ten
@@ -75,7 +76,8 @@ class AgentAR:
         if of_dim and dataset is not None and "of" not in dataset.data:
             raise ValueError(f"use_of: the data set carries no image features (StateARDataset(of_features=...), {of_dim} wide)")
         self.env = BatchedHumanoidAREnv(n_envs, device, mode="train", wild=wild, seed=seed + rank, model_options=model_options,
-                                        joint_controller=joint_controller, use_action=use_action, use_vel=use_vel, use_head=use_head, ctx_dim=ctx_block, of_dim=of_dim)
+                                        joint_controller=joint_controller, use_action=use_action, use_vel=use_vel, use_head=use_head, ctx_dim=ctx_block, of_dim=of_dim,
+                                        push_schedule=push_schedule)
         self.device = self.env.device
         if cc_checkpoint is not None:      # the pre-trained UHC the env is built around (humanoid_ar_v1.py:60-81)
             self.env.load_uhc_checkpoint(cc_checkpoint, load_policy=not joint_controller)

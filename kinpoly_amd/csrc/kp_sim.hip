@@ -20,6 +20,7 @@
 #include "kp_rollout_kernels.hpp"
 #include "kp_policy_kernels.hpp"
 #include "kp_step_kernel.hpp"
+#include "kp_push.hpp"
 #include "kp_pose_contacts.hpp"
 #include "kp_render.hpp"
 #include "kp_takes.hpp"
@@ -1471,6 +1472,19 @@ int kp_sim_set_obj_state(kp_sim* s, const float* obj_qpos, const float* obj_qvel
     HIP_OK(hipSetDevice(s->device));
     copy_rows(s, 35, obj_qpos, s->obj.qpos, nullptr, mask);
     copy_rows(s, 30, obj_qvel, s->obj.qvel, nullptr, mask);
+    return launched();
+}
+
+int kp_sim_apply_impulse(kp_sim* s, const int32_t* entity, const float* offset, const float* impulse, const uint8_t* mask, float* dqvel) {
+    if (!s || !entity || !impulse) return fail("kp_sim_apply_impulse: null argument");
+    HIP_OK(hipSetDevice(s->device));
+    kp::StepArgs A{};
+    A.T = s->T; A.P = s->P; A.n_envs = s->n; A.n_substeps = 0;
+    A.qpos = s->st.qpos; A.qvel = s->st.qvel;
+    // the object slots mean something once kp_sim_set_objects / kp_sim_reset_rows have installed a block (zero-filled before that)
+    const ObjectRows& o = s->obj;
+    if (o.on && s->T.obj_inertial) { A.obj_slot = o.slot; A.obj_qpos = o.qpos; A.obj_qvel = o.qvel; }
+    hipLaunchKernelGGL(kp::k_apply_impulse, dim3(s->n), dim3(64), sizeof(kp::EnvLds), s->stream, A, entity, offset, impulse, mask, dqvel);
     return launched();
 }
 

@@ -45,7 +45,7 @@ class BatchedHumanoidAREnv:
     def __init__(self, n_envs, device=0, kpm_path=None, cc_policy: PolicyMCP | None = None,
                  cc_running_state: RunningState | None = None, mode="train", wild=False, joint_controller=False,
                  env_episode_len=100000, body_diff_thresh=10.0, body_diff_gt_thresh=12.0, model_options=None, seed=0, ar_mode=False, use_action=True,
-                 use_vel=False, use_head=True, ctx_dim=0, of_dim=0):
+                 use_vel=False, use_head=True, ctx_dim=0, of_dim=0, push_schedule=None):
         """use_action (kin_poly.yml: true): the observation ends with the clip's action one-hot (105 floats); false (kin_poly_wo_action.yml): the first
         101 of them (humanoid_ar_v1.py:200-201), from a model with the option ar_obs_action = 0 -- every other quantity still reads the one-hot.
         use_vel: the simulated humanoid's 75 velocities follow the pose block (:184-185, option ar_obs_vel = 1); use_head false: no head-tracking blocks
@@ -58,6 +58,7 @@ class BatchedHumanoidAREnv:
         pool_depth of 4; at fr_num 100, ctx_dim 256 and of_dim 512 a row adds 307 KB, 11.3 GB for 4096 envs (arithmetic; DESIGN section 8 has what was
         measured), next to the 0.11 MB per row of the base tables."""
         self.n = int(n_envs)
+        self.push_schedule = push_schedule       # kinpoly_amd.push.PushSchedule or None: pushes at the tail of step() (None: no launch is added)
         self.ar_mode = bool(ar_mode)
         if kpm_path is None:  # agent_ar.py:165-169: mocap training uses ..._all_step.xml, --wild uses ..._all.xml
             kpm_path = kpsim.DEFAULT_KPM if wild else kpsim.STEP_KPM
@@ -429,10 +430,21 @@ class BatchedHumanoidAREnv:
         o = self._outs[self._flip]
         sim.post_step(self._ctx_struct, self.reward_cfg, self.cur_t, self.row_len, int(min(self.env_episode_len, 2 ** 31 - 1)),
                       o["reward"], o["info"], o["fail"], o["diffs"], o["done"], o["end"], o["percent"], self.done_count, self.obj7)
+        if self.push_schedule is not None:     # the tail of the step: the envs that go on are pushed before the next state is observed
+            bad = (~torch.isfinite(o["diffs"]).all(1)).to(torch.uint8)      # a push that drove the fp32 state to inf / nan: the env fails (nan > thresh is False)
+            o["fail"] |= bad; o["done"] |= bad
+            entity, impulse, offset = self.push_schedule.draw(self.cur_t, o["done"] == 0)
+            sim.apply_impulse(entity, impulse, offset)
         obs = self._obs_ar(self._obs_next) if need_obs else None
         info = {"fail": o["fail"].view(torch.bool), "end": o["end"].view(torch.bool), "percent": o["percent"], "cc_action": cc_action, "cc_state": cc_obs,
                 "custom_reward": o["reward"], "custom_info": o["info"], "body_diff": o["diffs"]}
         return obs, self._unit_reward, o["done"].view(torch.bool), info        # the env's own reward is the constant 1.0 (humanoid_ar_v1.py:311); one shared read-only tensor
+
+    def push(self, entity, impulse, offset=None, env_mask=None):
+        """An impulse push of the current state (KpSim.apply_impulse): entity int32 [N] (0..23 body, 24 + k object slot, -1 none), impulse [N, 6] = (p, l),
+        offset [N, 3] or None, env_mask bool / uint8 [N] or None.  Call it between two step()s; the observation step() returned is then one push old."""
+        self.sim.apply_impulse(entity.to(self.device, torch.int32).contiguous(), impulse.to(self.device, torch.float32).contiguous(),
+                               None if offset is None else offset.to(self.device, torch.float32).contiguous(), self._mask8(env_mask, self.device))
 
     # getters (device tensors; reference names)
     def get_humanoid_qpos(self):
@@ -644,6 +656,12 @@ class HumanoidAREnv:
                     "cc_action": info["cc_action"][0].double().cpu().numpy(), "cc_state": info["cc_state"][0].double().cpu().numpy()}
         self._last_reward = (float(info["custom_reward"][0]), info["custom_info"][0].double().cpu().numpy())
         return obs[0].double().cpu().numpy(), 1.0, bool(done[0]), out_info
+
+    def push(self, body, impulse, offset=None):
+        """An impulse push of the current state: body 0..23 (or 24 + k: object slot k), impulse [6] = (p in N s, l in N m s) in world axes, offset [3] in the
+        body frame or None (BatchedHumanoidAREnv.push; no reference counterpart)."""
+        t = lambda v, dt: torch.as_tensor(np.asarray(v), dtype=dt, device=self.b.device).reshape(1, -1)      # noqa: E731
+        self.b.push(t(int(body), torch.int32).reshape(1), t(impulse, torch.float32), None if offset is None else t(offset, torch.float32))
 
     def _g(self, name):
         return self.b.sim.get(name)[0].double().cpu().numpy()

@@ -14,8 +14,12 @@ import torch
 
 
 @torch.no_grad()
-def run_sequences(env, policy_net, keys, fail_safe=False, max_steps=100000):
-    """env: BatchedHumanoidAREnv with its context loaded (one sequence per env, mode 'test').  Returns {key: seq_result}."""
+def run_sequences(env, policy_net, keys, fail_safe=False, max_steps=100000, push_schedule=None):
+    """env: BatchedHumanoidAREnv with its context loaded (one sequence per env, mode 'test').  Returns {key: seq_result}.
+    push_schedule (kinpoly_amd.push.PushSchedule for env.n envs): the env pushes its humanoids while the sequences play; a recording schedule gets the
+    pushes of every sequence in its by_take."""
+    if push_schedule is not None:
+        return _with_pushes(env, push_schedule, lambda: run_sequences(env, policy_net, keys, fail_safe, max_steps), keys)
     n = env.n
     if fail_safe and "ar_qpos" not in env.ctx:            # checked once, up front: the fail-safe runs (masked) every step, whether or not an env ended early
         raise ValueError("run_sequences(fail_safe=True) needs the kinematic roll-out in the context (ctx['ar_qpos'] / ['ar_qvel']: PolicyARContext(need_rollout=True))")
@@ -43,6 +47,7 @@ def run_sequences(env, policy_net, keys, fail_safe=False, max_steps=100000):
         if step % 8 == 7 and not bool(active.any()):      # one host read every 8 steps; the records of finished envs are dropped by `active` below
             break
     act = torch.stack(rec["active"], 0).cpu().numpy()                       # [steps, n]
+    env._played = act
     tgt = torch.stack(rec["target"], 0).double().cpu().numpy(); pred = torch.stack(rec["pred"], 0).double().cpu().numpy()
     parked = np.zeros(35); parked[0::7] = [100.0 * (i + 1) for i in range(5)]; parked[1::7] = 100.0
     objs = None if rec["obj_pose"][0] is None else torch.stack(rec["obj_pose"], 0).double().cpu().numpy()
@@ -56,7 +61,21 @@ def run_sequences(env, policy_net, keys, fail_safe=False, max_steps=100000):
 
 
 @torch.no_grad()
-def eval_dataset(env, policy_net, ctx_builder, dataset, fail_safe=False, inds=None):
+def _with_pushes(env, schedule, play, keys):
+    """play() with the schedule installed in env; afterwards the env is as it was and a recording schedule holds the pushes of `keys`"""
+    first = 0 if schedule.log is None else len(schedule.log)
+    before, env.push_schedule = env.push_schedule, schedule
+    try:
+        out = play()
+    finally:
+        env.push_schedule = before
+    if schedule.log is not None:
+        schedule.collect(first, env._played, [k for k in keys if not str(k).startswith("__fill_")])
+    return out
+
+
+@torch.no_grad()
+def eval_dataset(env, policy_net, ctx_builder, dataset, fail_safe=False, inds=None, push_schedule=None):
     """`eval_seq` for every take of a data set (agent_ar.py:463-503; eval_ar_policy.py's run_seq loop :178-262), env.n takes at a time: each
     env plays one WHOLE take (`get_seq_by_ind(ind, full_sample=True)`), takes of different length share a batch padded to its longest
     (`ctx['len']` ends every env on its own last frame; init_context averages every row's context over its own frames).  ctx_builder:
@@ -72,7 +91,7 @@ def eval_dataset(env, policy_net, ctx_builder, dataset, fail_safe=False, inds=No
         ctx = ctx_builder.init_context(data, need_rollout=True)
         env.load_context(ctx)
         keys = [dataset.takes[j] for j in chunk] + [f"__fill_{j}" for j in range(env.n - len(chunk))]
-        res = run_sequences(env, policy_net, keys, fail_safe=fail_safe)
+        res = run_sequences(env, policy_net, keys, fail_safe=fail_safe, push_schedule=push_schedule)
         out.update({k: res[k] for k in keys[:len(chunk)]})
     return out
 
@@ -93,12 +112,14 @@ def write_coverage(results: dict, result_dir: str, iter_num: int, data_file: str
 # uhc/core/agent_copycat.py:101-131), env.n takes at a time on a take library (BatchedHumanoidEnv.load_takes).
 
 @torch.no_grad()
-def run_uhc_sequences(env, policy_net, running_state, take_ids, keys, fail_safe=False, max_steps=100000):
+def run_uhc_sequences(env, policy_net, running_state, take_ids, keys, fail_safe=False, max_steps=100000, push_schedule=None):
     """Every env plays one WHOLE take (take_ids [env.n], library ids) with the mean action and running_state(update=False).  Per step, before the
     action: gt = the expert's qpos at get_expert_index(t), pred = the simulated qpos (eval_uhc.py:175-178; on a library with objects env.data.qpos is
     the full 111-wide row, so pred = [qpos 76 | object block 35] while gt stays 76 wide).  An env that ends early (percent != 1) is,
     with fail_safe, put back on the expert and goes on (:188-196); without it the episode is over.  Returns {key: {gt, pred, percent, fail_safe}}
-    for the first len(keys) envs."""
+    for the first len(keys) envs.  push_schedule: as in run_sequences."""
+    if push_schedule is not None:
+        return _with_pushes(env, push_schedule, lambda: run_uhc_sequences(env, policy_net, running_state, take_ids, keys, fail_safe, max_steps), keys)
     n, dev, lib = env.n, env.device, env.takes
     norm = (lambda o: running_state(o, update=False)) if running_state is not None else (lambda o: o)
     everyone = torch.ones(n, dtype=torch.bool, device=dev)
@@ -127,7 +148,7 @@ def run_uhc_sequences(env, policy_net, running_state, take_ids, keys, fail_safe=
         obs = norm(env.reset(done & ~active))       # a finished env waits on its take's first frame; its records are dropped by `active`
         if step % 8 == 7 and not bool(active.any()):
             break
-    act = torch.stack(act, 0).cpu().numpy()
+    act = env._played = torch.stack(act, 0).cpu().numpy()
     gt, pred = torch.stack(gt, 0).double().cpu().numpy(), torch.stack(pred, 0).double().cpu().numpy()
     out = {}
     for e, key in enumerate(keys):
@@ -137,7 +158,7 @@ def run_uhc_sequences(env, policy_net, running_state, take_ids, keys, fail_safe=
 
 
 @torch.no_grad()
-def eval_uhc_takes(env, policy_net, running_state, dataset, fail_safe=False, inds=None, library=None):
+def eval_uhc_takes(env, policy_net, running_state, dataset, fail_safe=False, inds=None, library=None, push_schedule=None):
     """test_coverage's loop (eval_uhc.py:202-224) over the takes of an AmassSingleDataset or SmplObjDataset, env.n at a time; a short last chunk is padded with copies of
     its last take.  Loads the data set's library into env (library: one already built with env.sim).  Returns {take name: seq_result} in data-set order."""
     lib = library if library is not None else dataset.to_library(env.sim)
@@ -147,7 +168,7 @@ def eval_uhc_takes(env, policy_net, running_state, dataset, fail_safe=False, ind
     for i in range(0, len(inds), env.n):
         chunk = inds[i:i + env.n]
         ids = chunk + [chunk[-1]] * (env.n - len(chunk))
-        out.update(run_uhc_sequences(env, policy_net, running_state, ids, [dataset.data_keys[j] for j in chunk], fail_safe=fail_safe))
+        out.update(run_uhc_sequences(env, policy_net, running_state, ids, [dataset.data_keys[j] for j in chunk], fail_safe=fail_safe, push_schedule=push_schedule))
     return out
 
 

@@ -142,6 +142,7 @@ _SIGNATURES = {
     "kp_sim_status_device": (_V, [_V]), "kp_sim_contacts": (_I, [_V, _V]), "kp_sim_mass_matrix": (_I, [_V, _V, _V]),
     "kp_sim_set_state": (_I, [_V, _V, _V, _V]), "kp_sim_set_full_state": (_I, [_V, _V, _V, _V, _V, _V]), "kp_sim_set_target": (_I, [_V, _V, _V]),
     "kp_sim_set_objects": (_I, [_V, _V, _V]), "kp_sim_set_obj_state": (_I, [_V, _V, _V, _V]),
+    "kp_sim_apply_impulse": (_I, [_V, _V, _V, _V, _V, _V]),
     "kp_sim_fk": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]), "kp_sim_fk_backward": (_I, [_V, _I, _V, _V, _V, _V, _V]),
     "kp_sim_pose_contacts": (_I, [_V, _I, _V, _V, _V, _F, _V, _V, _V]),
     # the offscreen renderer (kp_render.hip); kp_model_hull_planes is host only
@@ -437,6 +438,15 @@ class KpSim:
     def set_full_state(self, qpos, qvel, qpos_d, qvel_d, env_mask=None):
         _check(self.L.kp_sim_set_full_state(self.h, _ptr(qpos, self.n, NQ), _ptr(qvel, self.n, NV), _ptr(qpos_d, self.n, NQ),
                                             _ptr(qvel_d, self.n, NV), _mask_ptr(env_mask, self.n)), "kp_sim_set_full_state")
+
+    def apply_impulse(self, entity, impulse, offset=None, env_mask=None, want_dqvel=False):
+        """An impulse push between two control steps (kp_sim_apply_impulse): qvel += M(qpos)^-1 J^T [p; l] per env.  entity: int32 [N] device tensor
+        (0..23 body, 24 + k object slot, anything else: no push); impulse [N,6] = (p in N s, l in N m s), world axes; offset [N,3] or None: the
+        point on the entity, in its own frame; env_mask uint8 [N] or None.  want_dqvel: return the humanoid's velocity jump [N,75]."""
+        dq = self._new(NV) if want_dqvel else None
+        _check(self.L.kp_sim_apply_impulse(self.h, _dev("entity", entity, (self.n,), torch.int32), _dev("offset", offset, (self.n, 3)),
+                                           _dev("impulse", impulse, (self.n, 6)), _mask_ptr(env_mask, self.n), _ptr(dq, self.n, NV)), "kp_sim_apply_impulse")
+        return dq
 
     def fk(self, qpos_rows: torch.Tensor):
         """qpos_fk_batch on [R,76] rows -> dict(qpos, wbpos, wbquat, bquat, body_com) of device tensors."""

@@ -187,8 +187,9 @@ class BatchedHumanoidEnv:
     and the episode / reward constants of its file; without it the env is uhc.yml's (784-d get_full_obs_v1, env_term_body 'body')."""
 
     def __init__(self, n_envs, device=0, kpm_path=None, env_episode_len=100000, env_init_noise=0.0, env_expert_trail_steps=0,
-                 body_diff_thresh=0.5, reward_weights=None, model_options=None, seed=0, cfg=None, reward_id=None):
+                 body_diff_thresh=0.5, reward_weights=None, model_options=None, seed=0, cfg=None, reward_id=None, push_schedule=None):
         self.n = int(n_envs)
+        self.push_schedule = push_schedule       # kinpoly_amd.push.PushSchedule or None: pushes at the tail of step() (None: no launch is added)
         self.cfg = cfg
         if cfg is not None:
             env_episode_len, env_init_noise, env_expert_trail_steps = cfg.env_episode_len, cfg.env_init_noise, cfg.env_expert_trail_steps
@@ -314,6 +315,21 @@ class BatchedHumanoidEnv:
         from .render import render_env
         return render_env(self.sim, self.get_obj_qpos().clone() if self.has_objects else None, envs, camera, width, height)
 
+    def push(self, entity, impulse, offset=None, env_mask=None):
+        """An impulse push of the current state (KpSim.apply_impulse): entity int32 [N] (0..23 body, 24 + k object slot, -1 none), impulse [N, 6] = (p, l),
+        offset [N, 3] or None, env_mask bool / uint8 [N] or None.  Call it between two step()s; the observation step() returned is then one push old."""
+        m8 = None if env_mask is None else env_mask.to(self.device, torch.uint8).contiguous()
+        self.sim.apply_impulse(entity.to(self.device, torch.int32).contiguous(), impulse.to(self.device, torch.float32).contiguous(),
+                               None if offset is None else offset.to(self.device, torch.float32).contiguous(), m8)
+
+    def _scheduled_push(self, done):
+        """the tail of step(): what the schedule draws for the episode clock the step just advanced, for the envs that go on.
+        With a schedule installed a non-finite body_diff counts as a failure: a push far beyond what a body survives (1e4 N s at every step) drives the fp32
+        state to inf / nan within a control step, and the reference's `body_diff > thresh` (humanoid_im.py:559) is False for a nan -- without pushes that rule
+        stays as it is."""
+        entity, impulse, offset = self.push_schedule.draw(self.cur_t, done == 0)
+        self.sim.apply_impulse(entity, impulse, offset)
+
     def _step_takes(self, a):
         if self._next_ids is not None:
             raise RuntimeError("load_takes: call reset() before the first step (the envs are on no take yet)")
@@ -327,6 +343,10 @@ class BatchedHumanoidEnv:
         sim.step_ctrl_base(a.contiguous(), self._base, self.frame_skip)
         track, tc = (sim.uhc_track, self._tc) if self._tcr is None else (sim.uhc_track_r, self._tcr)
         track(self.takes, self._st, tc, a, o["custom_reward"], o["custom_info"], o["body_diff"], o["fail"], o["end"], o["done"], o["percent"])
+        if self.push_schedule is not None:
+            bad = (~torch.isfinite(o["body_diff"])).to(torch.uint8)      # a diverged env fails (see _scheduled_push)
+            o["fail"] |= bad; o["done"] |= bad
+            self._scheduled_push(o["done"])
         obs = self._obs_takes()
         info = {k: (v.view(torch.bool) if v.dtype == torch.uint8 else v) for k, v in o.items()}
         return obs, torch.ones(self.n, device=self.device), info.pop("done"), info
@@ -395,6 +415,9 @@ class BatchedHumanoidEnv:
             fail = torch.zeros_like(body_diff, dtype=torch.bool)
         end = (self.cur_t >= self.env_episode_len) | (self.cur_t >= self.expert["len"] + self.trail)
         reward, rinfo = self._reward_clip(a, xpos, bquat, com, prev_qpos)
+        if self.push_schedule is not None:
+            fail = fail | ~torch.isfinite(body_diff)                    # a diverged env fails (see _scheduled_push)
+            self._scheduled_push(fail | end)
         obs = self._obs_now()
         return obs, torch.ones(self.n, device=self.device), fail | end, {"fail": fail, "end": end, "percent": self.cur_t.float() / self.expert["len"],
                                                                         "custom_reward": reward, "custom_info": rinfo, "body_diff": body_diff}
@@ -435,8 +458,10 @@ class CopycatAgent:
     on the batched env: one process per GPU, built from the same steps as kinpoly_amd.ppo.PPOTrainer."""
 
     def __init__(self, env: BatchedHumanoidEnv, policy: PolicyMCP | None = None, value=None, gamma=0.95, tau=0.95, clip_epsilon=0.2,
-                 policy_lr=5e-5, value_lr=3e-4, num_optim_epoch=10, group=None, dataset=None, seed=0, output_dir=None):
+                 policy_lr=5e-5, value_lr=3e-4, num_optim_epoch=10, group=None, dataset=None, seed=0, output_dir=None, push_schedule=None):
         self.env, self.group = env, group
+        if push_schedule is not None:            # pushes while sampling and evaluating (kinpoly_amd.push.PushSchedule): the env applies them
+            env.push_schedule = push_schedule
         cfg = getattr(env, "cfg", None)
         self.policy = (policy or (cfg.make_policy() if cfg is not None else PolicyMCP())).to(env.device).float()
         self.value = (value or (cfg.make_value() if cfg is not None else Value(MLP(env.obs_dim, (1024, 512), "relu")))).to(env.device).float()

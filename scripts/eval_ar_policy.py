@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--num_seq", type=int, default=256)
     ap.add_argument("--clip_len", type=int, default=100)
@@ -41,7 +41,21 @@ def main():
                     "compute_physcis_metris) on the scene the run used, printed after the kinematic line")
     ap.add_argument("--cfg", type=str, default=None)
     ap.add_argument("--config_root", type=str, default=None)
-    args = ap.parse_args()
+    from kinpoly_amd.push import add_push_arguments
+    return add_push_arguments(ap)      # --push_impulse LO [HI] and friends: perturbation pushes while the sequences play (off by default)
+
+
+def report_pushes(sched, res, result_dir, iter_num, data_file):
+    """`pushes applied`, `coverage under pushes` and <result_dir>/push_log_<iter>_<data>.pkl = {take: [(step, body, impulse[6])]}"""
+    import joblib
+    os.makedirs(result_dir, exist_ok=True)
+    joblib.dump(sched.by_take, os.path.join(result_dir, f"push_log_{iter_num}_{data_file}.pkl"))
+    print(f"pushes applied: {sum(len(v) for v in sched.by_take.values())}")
+    print(f"coverage under pushes: {sum(1 for r in res.values() if r['percent'] == 1 and not r['fail_safe'])} out of {len(res)}")
+
+
+def main():
+    args = build_parser().parse_args()
     from kinpoly_amd import checkpoint as ck
     from kinpoly_amd import sim as kpsim
     from kinpoly_amd.context import PolicyARContext, TrajARNet
@@ -81,6 +95,8 @@ def main():
         ctx_kw = cfg.context_kwargs(int(np.asarray(next(iter(of.values()))).shape[1]) if of else None)
     ctx_block = int(ctx_kw.get("rnn_hdim", 1024)) if (ctx_kw.get("use_context") or ctx_kw.get("of_dim")) else 0          # TrajARNet.ctx_block
     env = BatchedHumanoidAREnv(n, 0, mode="test", wild=args.wild, ar_mode=args.ar_mode, seed=0, **obs_kw, ctx_dim=ctx_block, of_dim=ctx_kw.get("of_dim", 0))
+    from kinpoly_amd.push import schedule_from_args
+    sched = schedule_from_args(args, n, env.device, record=True)
     if cfg is not None:
         cfg.apply_reward_weights(env)
     net = TrajARNet(log_std=cfg.policy_specs["log_std"] if cfg else -3.2, **obs_kw, **ctx_kw, of_in_state=bool(ctx_kw.get("of_dim", 0))).to(env.device)
@@ -96,8 +112,11 @@ def main():
         from kinpoly_amd.evaluate import eval_dataset
         ds = D.StateARDataset(args.data if feats is None else feats, takes=takes, data_mode="test", fr_num=T, wild=args.wild, seed=0, device=env.device, of_features=of)
         builder = PolicyARContext(net, kpsim.KpSim(env.model, n, 0), smooth=bool(cfg.smooth) if cfg else True, keep_context_feat=bool(ctx_block))
-        res = eval_dataset(env, net, builder, ds, fail_safe=args.fail_safe)
-        cov = write_coverage(res, args.result_dir, args.iter, args.data_file if args.cfg else os.path.splitext(os.path.basename(args.data))[0])
+        res = eval_dataset(env, net, builder, ds, fail_safe=args.fail_safe, push_schedule=sched)
+        data_file = args.data_file if args.cfg else os.path.splitext(os.path.basename(args.data))[0]
+        cov = write_coverage(res, args.result_dir, args.iter, data_file)
+        if sched is not None:
+            report_pushes(sched, res, args.result_dir, args.iter, data_file)
         pct = np.array([r["percent"] for r in res.values()])
         print(f"Coverage of {cov} out of {len(res)} | mean percent {pct.mean():.3f} | fail-safe used in {sum(r['fail_safe'] for r in res.values())}")
         if args.metrics or args.physics_metrics:    # the paper metrics of scripts/eval_pose_all.py --mode stats (kinpoly_amd/metrics.py)
@@ -121,8 +140,10 @@ def main():
     ctx = PolicyARContext(net, kpsim.KpSim(env.model, n, 0), smooth=True).init_context(ctx)
     env.load_context(ctx)
     keys = [f"standing-{i:05d}" for i in range(n)]
-    res = run_sequences(env, net, keys, fail_safe=args.fail_safe)
+    res = run_sequences(env, net, keys, fail_safe=args.fail_safe, push_schedule=sched)
     cov = write_coverage(res, args.result_dir, args.iter, args.data_file)
+    if sched is not None:
+        report_pushes(sched, res, args.result_dir, args.iter, args.data_file)
     pct = np.array([r["percent"] for r in res.values()])
     print(f"Coverage of {cov} out of {n} | mean percent {pct.mean():.3f} | fail-safe used in {sum(r['fail_safe'] for r in res.values())}")
 

@@ -48,7 +48,8 @@ def build_parser():
     p.add_argument("--num_envs", type=int, default=64)
     p.add_argument("--dataset", choices=("amass_single", "smpl_obj"), default="amass_single",
                    help="the loader of the take file: amass_single (DatasetAMASSSingle's pickle) or smpl_obj (DatasetSMPLObj's: takes that carry objects)")
-    return p
+    from kinpoly_amd.push import add_push_arguments
+    return add_push_arguments(p)       # --push_impulse LO [HI] and friends: perturbation pushes while the takes play (off by default)
 
 
 def check_mode(args):
@@ -97,12 +98,19 @@ def main(argv=None):
         rs._mean64.copy_(torch.as_tensor(st._M, dtype=torch.float64)); rs._m2.copy_(torch.as_tensor(st._S, dtype=torch.float64))
         rs.mean.copy_(rs._mean64.float())
         rs.std.copy_((torch.sqrt(rs._m2 / (rs.count - 1)) if rs.count > 1 else rs._mean64.abs()).float())
-    res = eval_uhc_takes(env, agent.policy, rs, ds, fail_safe=args.fail_safe)
+    from kinpoly_amd.push import schedule_from_args
+    sched = schedule_from_args(args, n, env.device, record=True)
+    res = eval_uhc_takes(env, agent.policy, rs, ds, fail_safe=args.fail_safe, push_schedule=sched)
     for k, r in res.items():
         print(f"{r['percent']}  | {k} | {r['fail_safe']}")
     out_dir = os.path.dirname(os.path.abspath(ckpt))
     cov = write_uhc_coverage(res, out_dir, args.iter, args.data, no_full=args.no_full)
     print(f"Coverage of {cov} out of {ds.get_len()}")
+    if sched is not None:              # the coverage pickles keep their keys; the pushes go to a file of their own
+        import joblib
+        joblib.dump(sched.by_take, os.path.join(out_dir, f"push_log_{args.iter}_{args.data}.pkl"))
+        print(f"pushes applied: {sum(len(v) for v in sched.by_take.values())}")
+        print(f"coverage under pushes: {cov} out of {ds.get_len()}")
 
 
 if __name__ == "__main__":

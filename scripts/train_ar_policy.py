@@ -30,7 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--num_envs", type=int, default=4096)
     ap.add_argument("--iters", type=int, default=3)
@@ -72,7 +72,12 @@ def main():
     ap.add_argument("--no_log", action="store_true")
     ap.add_argument("--test_data", type=str, nargs="*", default=[], help="feature files of the test sets evaluated every save_model_interval iterations")
     ap.add_argument("--test_data_wild", type=str, nargs="*", default=[], help="the same for --wild test sets (evaluated on the ..._mesh_all.xml engine, agent_ar.py:305-314, 464)")
-    args = ap.parse_args()
+    from kinpoly_amd.push import add_push_arguments
+    return add_push_arguments(ap)      # --push_impulse LO [HI] and friends: train under perturbation pushes (off by default)
+
+
+def main():
+    args = build_parser().parse_args()
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local)
     if world > 1:
@@ -122,6 +127,7 @@ def main():
     cc_ckpt = args.cc_ckpt or (cfg.cc_checkpoint_path() if cfg is not None else None) or None
     if rank == 0 and cc_ckpt:
         print(f"loading model from checkpoint: {cc_ckpt}", flush=True)
+    from kinpoly_amd.push import schedule_from_args
     upd_kw = dict(update_dtype=torch.float64 if args.update_dtype == "fp64" else None, reference_bugs=not args.no_reference_bugs)
     if rank == 0 and not args.no_reference_bugs:          # nothing at run time says so otherwise
         print("note: reference_bugs = True (results identical to the reference's): the policy gradient is clipped on the run's FIRST optimiser step only, a resumed run "
@@ -129,7 +135,8 @@ def main():
     if cfg is None:
         agent = AgentAR(args.num_envs, dataset=ds, device=local, horizon=args.horizon, **upd_kw, num_optim_epoch=args.num_optim_epoch, cc_checkpoint=cc_ckpt, result_dir=args.result_dir or None,
                         num_step_update=args.num_step_update, sampling_temp=0.3, sampling_freq=0.5, pool_depth=args.pool_depth, cache_init_context=args.cache_init_context,
-                        rl_update=bool(args.rl_update), step_update=bool(args.step_update), min_batch_size=args.min_batch_size or 0)
+                        rl_update=bool(args.rl_update), step_update=bool(args.step_update), min_batch_size=args.min_batch_size or 0,
+                        push_schedule=schedule_from_args(args, args.num_envs, torch.device("cuda", local)))
         first, last, interval = 0, args.iters, 0
     else:
         # the reference collects min_batch_size steps of WHOLE episodes (~ fr_num frames each); a lock-step sampler with thousands of envs would meet
@@ -139,7 +146,8 @@ def main():
             print(f"horizon {horizon} steps per env = {horizon * args.num_envs * world} samples per iteration (min_batch_size {cfg.policy_specs.get('min_batch_size', 10000)})", flush=True)
         agent = AgentAR(args.num_envs, dataset=ds, device=local, horizon=horizon, pool_depth=args.pool_depth, **upd_kw,
                         cache_init_context=args.cache_init_context, result_dir=cfg.result_dir, cc_checkpoint=cc_ckpt, **cfg.agent_kwargs(ds.of_dim or None),
-                        min_batch_size=int(cfg.policy_specs.get("min_batch_size", 10000)) if args.min_batch_size is None else args.min_batch_size)
+                        min_batch_size=int(cfg.policy_specs.get("min_batch_size", 10000)) if args.min_batch_size is None else args.min_batch_size,
+                        push_schedule=schedule_from_args(args, args.num_envs, torch.device("cuda", local)))
         cfg.apply_reward_weights(agent.env)
         if cfg.use_of and (args.test_data or args.test_data_wild):
             raise SystemExit("--test_data / --test_data_wild with use_of: the test sets' image features have no command-line option yet")

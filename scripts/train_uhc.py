@@ -53,7 +53,8 @@ def train_on_takes(args, rank, local, world):
     env = BatchedHumanoidEnv(args.num_envs, local, seed=1 + rank, cfg=cfg) if cfg is not None else BatchedHumanoidEnv(args.num_envs, local, env_init_noise=0.0, seed=1 + rank)
     group = dist.group.WORLD if world > 1 else None
     kw = {**(cfg.ppo_kwargs() if cfg is not None else {}), "num_optim_epoch": args.num_optim_epoch}
-    agent = CopycatAgent(env, group=group, dataset=ds, seed=1, output_dir=out_dir, **kw)
+    from kinpoly_amd.push import schedule_from_args
+    agent = CopycatAgent(env, group=group, dataset=ds, seed=1, output_dir=out_dir, push_schedule=schedule_from_args(args, args.num_envs, env.device), **kw)
     if world > 1:
         for p in list(agent.policy.parameters()) + list(agent.value.parameters()):
             dist.broadcast(p.data, 0)
@@ -85,7 +86,8 @@ def build_parser():
     ap.add_argument("--t_min", type=int, default=None, help="shortest take kept (default: the config's data_specs, else 90)")
     ap.add_argument("--dataset", choices=("amass_single", "smpl_obj"), default="amass_single",
                     help="the loader of --data / --test_data: amass_single (DatasetAMASSSingle's pickle) or smpl_obj (DatasetSMPLObj's: takes that carry objects)")
-    return ap
+    from kinpoly_amd.push import add_push_arguments
+    return add_push_arguments(ap)      # --push_impulse LO [HI] and friends: train under perturbation pushes (off by default)
 
 
 def main(argv=None):
@@ -96,6 +98,7 @@ def main(argv=None):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     from kinpoly_amd import checkpoint as ck
+    from kinpoly_amd.push import schedule_from_args
     from kinpoly_amd.uhc_env import BatchedHumanoidEnv, CopycatAgent
     std = np.load(os.path.join(ROOT, "tests", "golden", "standing_neutral.npz"))
     rng = np.random.default_rng(1 + rank)
@@ -112,11 +115,11 @@ def main(argv=None):
         cfg = UhcConfig(args.cfg, config_root=args.config_root)
         env = BatchedHumanoidEnv(n, local, seed=1 + rank, cfg=cfg)
         env.load_expert(torch.tensor(clips, dtype=torch.float32))
-        agent = CopycatAgent(env, **{**cfg.ppo_kwargs(), "num_optim_epoch": args.num_optim_epoch})
+        agent = CopycatAgent(env, **{**cfg.ppo_kwargs(), "num_optim_epoch": args.num_optim_epoch}, push_schedule=schedule_from_args(args, n, env.device))
     else:
         env = BatchedHumanoidEnv(n, local, env_init_noise=0.0, seed=1 + rank)
         env.load_expert(torch.tensor(clips, dtype=torch.float32))
-        agent = CopycatAgent(env, num_optim_epoch=args.num_optim_epoch)
+        agent = CopycatAgent(env, num_optim_epoch=args.num_optim_epoch, push_schedule=schedule_from_args(args, n, env.device))
     if world > 1:
         for p in list(agent.policy.parameters()) + list(agent.value.parameters()):
             dist.broadcast(p.data, 0)
