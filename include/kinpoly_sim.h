@@ -206,6 +206,27 @@ void kp_render_style_default(kp_render_style*);
 int kp_sim_render(kp_sim*, int n_rows, int n_fig, const float* xpos, const float* xquat, const float* obj_qpos, const float* camera, int camera_rows,
                   int width, int height, const kp_render_style* style, int32_t* geom, float* depth, uint8_t* rgba);
 
+/* The egocentric renderer: kp_sim_render's ray-caster behind a camera given as a pose (one that sits on a body and rolls with it, which the viewer's
+ * free camera cannot), and for a pair of frames A and B the exact optical flow of every pixel of A.  Rows, figures, object block, style and the
+ * outputs geom / depth / rgba are kp_sim_render's.  camera [camera_rows,8] on the device, camera_rows = 1 or R: eye[3], quaternion[4] (w, x, y, z,
+ * world from camera, normalised by the kernel), fovy (degrees).  The camera's axes are the head body's: forward = R e_z, up = R e_y, right = -R e_x,
+ * so the head's world quaternion is a camera looking where the head looks; dir = normalize(forward + sx th (W/H) right + sy th up), th = tan(fovy/2),
+ * (sx, sy) the pixel centre in -1..1, row 0 at the top.  hide_body: -1, or a body 0..23 of figure 0 that is not drawn (an eye outside the head hull).
+ * The B side -- xpos_b, xquat_b, camera_b, and obj_qpos_b exactly when obj_qpos is given; or all four NULL -- is the same rows one frame later.  With
+ * it, the point a pixel of A shows is carried to B by the rigid motion of what was hit (floor: stays; body b of figure k: x_B + R_B R_A^T (p - x_A);
+ * object geom: the same with the geom's world poses, a geom parked in B gives ok = 0; sky: the ray direction, a point at infinity) and projected
+ * through camera B: c = R_camB^T (p_B - eye_B), u' = (W/2)(1 + (-c_x/c_z)/(th_B W/H)), v' = (H/2)(1 - (c_y/c_z)/th_B).  There is no visibility test in
+ * B: this is the motion field of the points visible in A.  Further outputs, each may be NULL: flow float [R,H,W,2] = (u' - (px + .5), v' - (py + .5))
+ * in pixels; ok uint8 [R,H,W] = c_z > 0.01 (flow is (0, 0) where ok = 0); cells float [R,grid_y,grid_x,2] = the mean flow over the ok pixels of each
+ * grid cell (0 for a cell without one), which needs width = 8 a grid_x and height = 8 b grid_y with whole a, b >= 1 and is summed in a fixed order
+ * without atomics: equal inputs give equal bits.  With cells alone no per-pixel array is written.  Refused before anything is launched: everything
+ * kp_sim_render refuses; a B side given only in part; flow / ok / cells without a B side; a cells grid that does not divide the image into whole
+ * 8 x 8 tiles; hide_body outside -1..23; camera_rows neither 1 nor R; all six outputs NULL.  Enqueued on the sim's stream. */
+int kp_sim_render_ego(kp_sim*, int n_rows, int n_fig, const float* xpos, const float* xquat, const float* obj_qpos, const float* camera,
+                      const float* xpos_b, const float* xquat_b, const float* obj_qpos_b, const float* camera_b, int camera_rows, int width, int height,
+                      int hide_body, const kp_render_style* style, int grid_x, int grid_y,
+                      int32_t* geom, float* depth, uint8_t* rgba, float* flow, uint8_t* ok, float* cells);
+
 /* backward of qpos -> wbpos of the same rows (the autograd path through Humanoid.qpos_fk that TrajARNet.compute_loss_lite's
  * end-effector term takes, traj_ar_smpl_net.py:459-497, torch_smpl_humanoid.py:125-202): grad_qpos [n_rows,76] =
  * (d wbpos / d qpos)^T grad_wbpos [n_rows,72]; wbpos / wbquat are the outputs of the kp_sim_fk call on those rows. */

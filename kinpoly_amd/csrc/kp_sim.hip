@@ -23,6 +23,7 @@
 #include "kp_push.hpp"
 #include "kp_pose_contacts.hpp"
 #include "kp_render.hpp"
+#include "kp_render_ego.hpp"
 #include "kp_takes.hpp"
 #include "kp_kin_tape.hpp"
 #include "kp_obs_ctx.hpp"
@@ -87,8 +88,9 @@ struct Timing {
     bool ring_on = false, timed = false;
 };
 
-struct RenderTables {     // the hulls' face planes (kp::hull_planes), uploaded by the first kp_sim_render
+struct RenderTables {     // the hulls' face planes (kp::hull_planes), uploaded by the first kp_sim_render / kp_sim_render_ego
     const float* planes = nullptr; const int32_t* adr = nullptr;
+    float* partial = nullptr; size_t partial_n = 0;       // kp_sim_render_ego's per-tile flow sums (floats held); grows on demand
 };
 
 struct kp_sim {
@@ -656,6 +658,7 @@ void kp_sim_destroy(kp_sim* s) {
     hipSetDevice(s->device);
     hipStreamSynchronize(s->stream);
     for (void* p : s->allocs) hipFree(p);
+    if (s->rd.partial) hipFree(s->rd.partial);
     for (hipEvent_t e : s->tm.ring) hipEventDestroy(e);
     if (s->ovf.host) { hipHostFree(s->ovf.host); for (hipEvent_t e : s->ovf.ev) if (e) hipEventDestroy(e); }
     if (s->tm.ev0) hipEventDestroy(s->tm.ev0);
@@ -844,39 +847,55 @@ void kp_render_style_default(kp_render_style* st) {
     *st = d;
 }
 
-int kp_sim_render(kp_sim* s, int n_rows, int n_fig, const float* xpos, const float* xquat, const float* obj_qpos, const float* camera, int camera_rows,
-                  int width, int height, const kp_render_style* style, int32_t* geom, float* depth, uint8_t* rgba) {
-    static_assert(sizeof(kp_render_style) == sizeof(kp::RenderStyle), "kp_render_style and kp::RenderStyle are one layout");
-    if (!s) return fail("kp_sim_render: null sim");
-    if (n_rows < 0) return fail("kp_sim_render: n_rows < 0");
-    if (n_fig < 1 || n_fig > kp::RD_MAXFIG) return fail("kp_sim_render: n_fig outside 1..4");
-    if (width < 1 || width > kp::RD_MAXDIM || height < 1 || height > kp::RD_MAXDIM) return fail("kp_sim_render: width / height outside 1..4096");
-    if (!xpos || !xquat) return fail("kp_sim_render: null xpos / xquat");
-    if (!camera) return fail("kp_sim_render: null camera");
-    if (camera_rows != 1 && camera_rows != n_rows) return fail("kp_sim_render: camera_rows is neither 1 nor n_rows");
-    if (!geom && !depth && !rgba) return fail("kp_sim_render: null output (geom, depth and rgba are all null)");
-    if (obj_qpos && !s->obj.d_geoms) return fail("kp_sim_render: obj_qpos given but the model blob has no object geoms");
-    if (s->obj.n_geoms > kp::RD_MAXGEOM) return fail("kp_sim_render: the model has more object geoms than the renderer holds (16)");
+namespace {
+// what both renderers refuse, as the message of `who` ("" when the arguments are fine); n_out: outputs that are not null
+std::string render_refusal(const char* who, const kp_sim* s, int n_rows, int n_fig, const float* xpos, const float* xquat, const float* obj_qpos, const float* camera,
+                           int camera_rows, int width, int height, const kp_render_style* style, int n_out, const char* outputs) {
+    const std::string w = std::string(who) + ": ";
+    if (!s) return w + "null sim";
+    if (n_rows < 0) return w + "n_rows < 0";
+    if (n_fig < 1 || n_fig > kp::RD_MAXFIG) return w + "n_fig outside 1..4";
+    if (width < 1 || width > kp::RD_MAXDIM || height < 1 || height > kp::RD_MAXDIM) return w + "width / height outside 1..4096";
+    if (!xpos || !xquat) return w + "null xpos / xquat";
+    if (!camera) return w + "null camera";
+    if (camera_rows != 1 && camera_rows != n_rows) return w + "camera_rows is neither 1 nor n_rows";
+    if (n_out == 0) return w + "null output (" + outputs + " are all null)";
+    if (obj_qpos && !s->obj.d_geoms) return w + "obj_qpos given but the model blob has no object geoms";
+    if (s->obj.n_geoms > kp::RD_MAXGEOM) return w + "the model has more object geoms than the renderer holds (16)";
     if (obj_qpos)
         for (int g = 0; g < s->obj.n_geoms; g++) {      // what the kernel draws: boxes and cylinders of the five objects of the 35-float block
             const double* og = s->model->h.obj_geoms.data() + 18 * g;
-            if (og[1] != 0.0 && og[1] != 1.0) return fail("kp_sim_render: the model has an object geom that is neither a box (0) nor a cylinder (1)");
-            if (og[0] < 0.0 || og[0] >= 5.0 || og[0] >= (double)s->obj.n_obj) return fail("kp_sim_render: the model has an object geom of an object outside the 35-float object block");
+            if (og[1] != 0.0 && og[1] != 1.0) return w + "the model has an object geom that is neither a box (0) nor a cylinder (1)";
+            if (og[0] < 0.0 || og[0] >= 5.0 || og[0] >= (double)s->obj.n_obj) return w + "the model has an object geom of an object outside the 35-float object block";
         }
-    if (style && !(style->zfar > 0.f)) return fail("kp_sim_render: style.zfar must be positive");
+    if (style && !(style->zfar > 0.f)) return w + "style.zfar must be positive";
     const long tiles = (long)((width + 7) / 8) * ((height + 7) / 8), blocks = (tiles + kp::RD_TILES - 1) / kp::RD_TILES * (long)n_rows;
-    if (blocks > INT_MAX) return fail("kp_sim_render: n_rows x image tiles exceed one launch (render fewer rows per call)");
+    if (blocks > INT_MAX) return w + "n_rows x image tiles exceed one launch (render fewer rows per call)";
+    return "";
+}
+
+// the hull planes on the device, uploaded by the first render
+bool render_tables(kp_sim* s) {
+    if (s->rd.planes) return true;
+    std::vector<float> pl; std::vector<int32_t> ad;
+    kp::hull_planes(s->model->h, pl, ad);
+    bool ok = true;
+    const float* dp = upload<float>(s, pl, &ok);
+    const int32_t* da = upload<int32_t>(s, ad, &ok);
+    if (ok) { s->rd.planes = dp; s->rd.adr = da; }
+    return ok;
+}
+}  // namespace
+
+int kp_sim_render(kp_sim* s, int n_rows, int n_fig, const float* xpos, const float* xquat, const float* obj_qpos, const float* camera, int camera_rows,
+                  int width, int height, const kp_render_style* style, int32_t* geom, float* depth, uint8_t* rgba) {
+    static_assert(sizeof(kp_render_style) == sizeof(kp::RenderStyle), "kp_render_style and kp::RenderStyle are one layout");
+    const std::string no = render_refusal("kp_sim_render", s, n_rows, n_fig, xpos, xquat, obj_qpos, camera, camera_rows, width, height, style,
+                                          (geom != nullptr) + (depth != nullptr) + (rgba != nullptr), "geom, depth and rgba");
+    if (!no.empty()) return fail(no);
     if (n_rows == 0) return 0;
     HIP_OK(hipSetDevice(s->device));
-    if (!s->rd.planes) {
-        std::vector<float> pl; std::vector<int32_t> ad;
-        kp::hull_planes(s->model->h, pl, ad);
-        bool ok = true;
-        const float* dp = upload<float>(s, pl, &ok);
-        const int32_t* da = upload<int32_t>(s, ad, &ok);
-        if (!ok) return fail("kp_sim_render: uploading the hull planes failed");
-        s->rd.planes = dp; s->rd.adr = da;
-    }
+    if (!render_tables(s)) return fail("kp_sim_render: uploading the hull planes failed");
     kp::RenderArgs A{};
     A.n_rows = n_rows; A.n_fig = n_fig; A.width = width; A.height = height; A.cam_rows = camera_rows; A.n_og = s->obj.n_geoms; A.n_obj = s->obj.n_obj;
     A.xpos = xpos; A.xquat = xquat; A.obj_qpos = obj_qpos; A.camera = camera; A.og = s->obj.d_geoms; A.rbound = s->T.body_rbound;
@@ -886,6 +905,51 @@ int kp_sim_render(kp_sim* s, int n_rows, int n_fig, const float* xpos, const flo
     std::memcpy(&A.style, &st, sizeof(st));
     A.geom = geom; A.depth = depth; A.rgba = (uint32_t*)rgba;
     HIP_OK(kp::launch_render(A, s->stream));
+    return 0;
+}
+
+int kp_sim_render_ego(kp_sim* s, int n_rows, int n_fig, const float* xpos, const float* xquat, const float* obj_qpos, const float* camera,
+                      const float* xpos_b, const float* xquat_b, const float* obj_qpos_b, const float* camera_b, int camera_rows, int width, int height,
+                      int hide_body, const kp_render_style* style, int grid_x, int grid_y,
+                      int32_t* geom, float* depth, uint8_t* rgba, float* flow, uint8_t* ok, float* cells) {
+    const char* who = "kp_sim_render_ego";
+    const int n_out = (geom != nullptr) + (depth != nullptr) + (rgba != nullptr) + (flow != nullptr) + (ok != nullptr) + (cells != nullptr);
+    const std::string no = render_refusal(who, s, n_rows, n_fig, xpos, xquat, obj_qpos, camera, camera_rows, width, height, style, n_out,
+                                          "geom, depth, rgba, flow, ok and cells");
+    if (!no.empty()) return fail(no);
+    const bool pair = xpos_b && xquat_b && camera_b;
+    if (!pair && (xpos_b || xquat_b || camera_b || obj_qpos_b))
+        return fail("kp_sim_render_ego: the B side is given only in part (xpos_b, xquat_b and camera_b go together; obj_qpos_b needs them)");
+    if (pair && (obj_qpos_b != nullptr) != (obj_qpos != nullptr))
+        return fail("kp_sim_render_ego: the B side is given only in part (obj_qpos_b must be given exactly when obj_qpos is)");
+    if (!pair && (flow || ok || cells)) return fail("kp_sim_render_ego: flow / ok / cells need a B side (xpos_b, xquat_b, camera_b)");
+    if (hide_body < -1 || hide_body > 23) return fail("kp_sim_render_ego: hide_body outside -1..23");
+    if (cells && (grid_x < 1 || grid_y < 1 || width % (8 * grid_x) != 0 || height % (8 * grid_y) != 0))
+        return fail("kp_sim_render_ego: the cells grid does not divide the image into whole 8 x 8 tiles (width = 8 a grid_x, height = 8 b grid_y)");
+    if (n_rows == 0) return 0;
+    HIP_OK(hipSetDevice(s->device));
+    if (!render_tables(s)) return fail("kp_sim_render_ego: uploading the hull planes failed");
+    kp::RenderEgoArgs A{};
+    if (cells) {                                 // the per-tile partial sums: a scratch of the handle that only grows
+        const size_t need = (size_t)n_rows * ((width + 7) / 8) * ((height + 7) / 8) * 3;
+        if (need > s->rd.partial_n) {
+            if (s->rd.partial) { HIP_OK(hipStreamSynchronize(s->stream)); HIP_OK(hipFree(s->rd.partial)); s->rd.partial = nullptr; s->rd.partial_n = 0; }
+            HIP_OK(hipMalloc((void**)&s->rd.partial, sizeof(float) * need));
+            s->rd.partial_n = need;
+        }
+        A.partial = s->rd.partial; A.grid_x = grid_x; A.grid_y = grid_y;
+    }
+    A.n_rows = n_rows; A.n_fig = n_fig; A.width = width; A.height = height; A.cam_rows = camera_rows; A.n_og = s->obj.n_geoms; A.n_obj = s->obj.n_obj;
+    A.hide_body = hide_body;
+    A.xpos = xpos; A.xquat = xquat; A.obj_qpos = obj_qpos; A.camera = camera;
+    if (pair) { A.xpos_b = xpos_b; A.xquat_b = xquat_b; A.obj_qpos_b = obj_qpos_b; A.camera_b = camera_b; }
+    A.og = s->obj.d_geoms; A.rbound = s->T.body_rbound;
+    A.planes = (const float4*)s->rd.planes; A.plane_adr = s->rd.adr;
+    kp_render_style st;
+    if (style) st = *style; else kp_render_style_default(&st);
+    std::memcpy(&A.style, &st, sizeof(st));
+    A.geom = geom; A.depth = depth; A.rgba = (uint32_t*)rgba; A.flow = flow; A.ok = ok; A.cells = cells;
+    HIP_OK(kp::launch_render_ego(A, s->stream));
     return 0;
 }
 

@@ -283,6 +283,68 @@ def synthetic_of_features(takes: dict, dim: int = 512, seed: int = 0) -> dict:
     return out
 
 
+def take_object_block(e: dict):
+    """The [T, 35] object block of a feature take (obj_pose [T, 7] / [T, 14] at its action's offset, the rest parked: convert_obj_qpos_np), an
+    obj_pose that already is the block as it stands, None for a take without an action object."""
+    obj = e.get("obj_pose")
+    if obj is None:
+        return None
+    obj = np.asarray(obj, np.float64)
+    if obj.ndim == 2 and obj.shape[1] == OBJ_QPOS_DIM:
+        return obj
+    one_hot = np.asarray(e.get("action_one_hot", np.zeros((1, 4))), np.float64).reshape(-1, 4)[0]
+    if not one_hot.sum() > 0:
+        return None
+    action = ACTIONS[int(np.argmax(one_hot))]
+    return convert_obj_qpos_np(obj[:, :OBJ_ACTION_LEN[action]], action)
+
+
+def rendered_of_features(takes: dict, sim, dim: int = 512, **kw) -> dict:
+    """The schema of synthetic_of_features -- take -> [T, dim] float32 -- computed instead of drawn: the exact optical flow of the head camera over
+    each take's qpos and objects, pooled over a grid (kinpoly_amd.render.ego_flow_features; kw: size, camera, scale).  A function of egocentric
+    motion and scene, which is what the context GRU is meant to read; needs the ground-truth body, so a wild take has none."""
+    from .render import ego_flow_features, flow_grid
+    flow_grid(dim)
+    return {take: ego_flow_features(sim, np.asarray(takes[take]["qpos"]), take_object_block(takes[take]), dim=dim, **kw) for take in sorted(takes)}
+
+
+OF_SOURCES = ("auto", "file", "standin", "rendered")
+
+
+def add_of_source_argument(ap):
+    ap.add_argument("--of_source", choices=OF_SOURCES, default="auto", help="use_of: where the per-frame image features come from.  auto: the yml's feature file if it "
+                    "exists, else the synthetic stand-in; file: the file or an error; standin: synthetic_of_features; rendered: the head camera's exact optical "
+                    "flow over each take (rendered_of_features; not with --wild)")
+    return ap
+
+
+def of_source_refusal(of_source: str, wild: bool):
+    """the message of a refused --of_source, or None"""
+    if of_source not in OF_SOURCES:
+        return f"--of_source must be one of {', '.join(OF_SOURCES)}, got {of_source}"
+    if of_source == "rendered" and wild:
+        return "--of_source rendered cannot go with --wild: a wild take has no ground-truth body to render"
+    return None
+
+
+def select_of_features(of_source: str, takes: dict, of_path: str, dim: int, seed: int, sim=None, wild: bool = False):
+    """The `of` features of a run -> (a feature file's path or a dict take -> [T, dim], a line that says which).  auto is the rule the scripts always
+    had: the file if it exists, else the stand-in."""
+    no = of_source_refusal(of_source, wild)
+    if no:
+        raise ValueError(no)
+    have = os.path.exists(of_path)
+    if of_source == "file" and not have:
+        raise FileNotFoundError(f"--of_source file: {of_path} does not exist")
+    if of_source == "file" or (of_source == "auto" and have):
+        return of_path, of_path
+    if of_source == "rendered":
+        if sim is None:
+            raise ValueError("--of_source rendered needs a simulator handle to render with")
+        return rendered_of_features(takes, sim, dim), f"rendered from the head camera ({dim} wide)"
+    return synthetic_of_features(takes, dim, seed=seed), "synthetic stand-in" + ("" if of_source == "standin" else f" (no {of_path})")
+
+
 def _ewma(x, alpha=0.05):
     """uhc/utils/math_utils.py:8-12, the recursion as written"""
     avg = x[0]

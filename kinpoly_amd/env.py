@@ -360,6 +360,12 @@ class BatchedHumanoidAREnv:
         from .render import render_env
         return render_env(self.sim, self.obj_qpos, envs, camera, width, height)
 
+    def render_ego(self, envs=None, width=64, height=64, camera=None):
+        """What every env's simulated figure sees from its head (all envs, or the indices `envs`), with the env's objects -> uint8 [n, H, W, 4] on the
+        device (kinpoly_amd.render.render_env_ego; camera: a HeadCamera, None for the default one at the head hull's centroid, fovy 90)."""
+        from .render import render_env_ego
+        return render_env_ego(self.sim, self.obj_qpos, envs, camera, width, height)
+
     @property
     def ctx_len(self):
         """ar_context['len'] of every env's current clip (int32 [N])."""

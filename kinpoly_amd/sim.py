@@ -148,6 +148,8 @@ _SIGNATURES = {
     # the offscreen renderer (kp_render.hip); kp_model_hull_planes is host only
     "kp_model_hull_planes": (_I, [_V, _V, _V]), "kp_render_style_default": (None, [_STYLE]),
     "kp_sim_render": (_I, [_V, _I, _I, _V, _V, _V, _V, _I, _I, _I, _STYLE, _V, _V, _V]),
+    # the egocentric renderer (kp_render_ego.hip): A side, B side, camera_rows, width, height, hide_body, style, grid, six outputs
+    "kp_sim_render_ego": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _STYLE, _I, _I, _V, _V, _V, _V, _V, _V]),
     "kp_sim_step_ctrl": (_I, [_V, _V, _I, _V]), "kp_sim_step_ctrl_base": (_I, [_V, _V, _I, _V, _V]), "kp_sim_step_kin": (_I, [_V, _V, _V]),
     "kp_sim_step_head": (_I, [_V, _V]), "kp_sim_step_begin": (_I, [_V]),
     "kp_sim_obs_cc": (_I, [_V, _V, _V, _V, _F]), "kp_sim_obs_cc_ex": (_I, [_V, _V, _V, _V, _F, _V]), "kp_sim_cc_obs_dim": (_I, [_V]),
@@ -553,6 +555,74 @@ class KpSim:
         R, K = qpos_rows.shape[:2]
         f = self.fk(qpos_rows.reshape(R * K, NQ)) if R else {"wbpos": qpos_rows.new_empty((0, 72)), "wbquat": qpos_rows.new_empty((0, 96))}
         return self.render_poses(f["wbpos"].view(R, K, 72), f["wbquat"].view(R, K, 96), obj_qpos, camera, width, height, want, style)
+
+    EGO_OUTPUTS = {**RENDER_OUTPUTS, "flow": (torch.float32, (2,)), "ok": (torch.uint8, ()), "cells": (torch.float32, (2,))}
+
+    def _pose_camera(self, camera, R, what):
+        """a HeadCamera-free camera argument of the ego renderer: a [8] / [1,8] / [R,8] device tensor (eye[3], quaternion[4] w x y z, fovy) -> [1 or R, 8]"""
+        cam = camera.reshape(1, 8) if camera.dim() == 1 else camera
+        if cam.dim() != 2 or cam.shape[0] not in (1, R) or cam.shape[1] != 8:
+            raise ValueError(f"render_ego: {what} must be [8], [1,8] or [{R},8], got {tuple(camera.shape)}")
+        _dev("render_ego: " + what, cam, (cam.shape[0], 8))
+        return cam
+
+    def render_ego_poses(self, xpos: torch.Tensor, xquat: torch.Tensor, obj_qpos: torch.Tensor | None, camera: torch.Tensor, xpos_b: torch.Tensor | None = None,
+                         xquat_b: torch.Tensor | None = None, obj_qpos_b: torch.Tensor | None = None, camera_b: torch.Tensor | None = None, width: int = 64,
+                         height: int = 64, want=("rgba",), grid=None, hide_body: int = -1, style: "KpRenderStyle | None" = None) -> dict:
+        """kp_sim_render_ego on body poses: the A side as render_poses takes it but with pose cameras [R,8] / [1,8] / [8] (eye[3], quaternion[4] w x y z
+        world from camera, fovy in degrees; the head body's axes: +z forward, +y up, +x left), and optionally the same rows one frame later as the B
+        side (xpos_b, xquat_b, camera_b; obj_qpos_b exactly when obj_qpos is given) -> dict of device tensors for the names in `want`: rgba, geom,
+        depth as render_poses; flow float32 [R,H,W,2] (pixels, A -> B), ok uint8 [R,H,W], cells float32 [R,Gy,Gx,2] (grid = (Gy, Gx) or one int: the
+        mean flow of the ok pixels of every cell).  hide_body: a body 0..23 of figure 0 that is not drawn, -1 for none."""
+        _dev("render_ego: xpos", xpos, (None, None, 72))
+        R, K = xpos.shape[:2]
+        xq = _dev("render_ego: xquat", xquat, (R, K, 96))
+        op = _dev("render_ego: obj_qpos", obj_qpos, (R, 35))
+        cam = self._pose_camera(camera, R, "camera")
+        b = [_dev("render_ego: xpos_b", xpos_b, (R, K, 72)), _dev("render_ego: xquat_b", xquat_b, (R, K, 96)), _dev("render_ego: obj_qpos_b", obj_qpos_b, (R, 35)), None]
+        if camera_b is not None:
+            cam_b = self._pose_camera(camera_b, R, "camera_b")
+            if cam_b.shape[0] != cam.shape[0]:
+                raise ValueError(f"render_ego: camera and camera_b must have the same number of rows, got {cam.shape[0]} and {cam_b.shape[0]}")
+            b[3] = C.c_void_p(cam_b.data_ptr())
+        unknown = [k for k in want if k not in self.EGO_OUTPUTS]
+        if unknown or not want:
+            raise ValueError(f"render_ego: want must name some of {sorted(self.EGO_OUTPUTS)}, got {tuple(want)}")
+        gy, gx = (0, 0) if grid is None else ((int(grid), int(grid)) if isinstance(grid, int) else (int(grid[0]), int(grid[1])))
+        if "cells" in want and grid is None:
+            raise ValueError("render_ego: want names cells but no grid is given")
+        out = {k: torch.empty(((R, gy, gx) if k == "cells" else (R, int(height), int(width))) + self.EGO_OUTPUTS[k][1], dtype=self.EGO_OUTPUTS[k][0], device=self.device)
+               for k in want}
+        ptr = lambda k: C.c_void_p(out[k].data_ptr()) if k in out else None      # noqa: E731
+        _check(self.L.kp_sim_render_ego(self.h, R, K, C.c_void_p(xpos.data_ptr()), xq, op, C.c_void_p(cam.data_ptr()), *b, cam.shape[0], int(width), int(height),
+                                        int(hide_body), None if style is None else C.byref(style), gx, gy,
+                                        *[ptr(k) for k in ("geom", "depth", "rgba", "flow", "ok", "cells")]), "kp_sim_render_ego")
+        return out
+
+    def render_ego(self, qpos_a: torch.Tensor, obj_a: torch.Tensor | None, cam_a, qpos_b: torch.Tensor | None = None, obj_b: torch.Tensor | None = None, cam_b=None,
+                   width: int = 64, height: int = 64, want=("rgba",), grid=None, hide_body: int = -1, style: "KpRenderStyle | None" = None) -> dict:
+        """Egocentric frames of qpos rows [R,76] or [R,K,76]: fk() of every figure, then render_ego_poses.  cam_a / cam_b: pose-camera tensors, or a
+        kinpoly_amd.render.HeadCamera (the camera rides on figure 0's head in that frame; its hide_head sets hide_body).  qpos_b (+ obj_b, cam_b): the rows
+        one frame later."""
+        def poses(q, what):
+            if q.dim() == 2:
+                q = q[:, None]
+            _dev("render_ego: " + what, q, (None, None, NQ))
+            R, K = q.shape[:2]
+            f = self.fk(q.reshape(R * K, NQ)) if R else {"wbpos": q.new_empty((0, 72)), "wbquat": q.new_empty((0, 96))}
+            return f["wbpos"].view(R, K, 72), f["wbquat"].view(R, K, 96)
+
+        def cam(c, xp, xq):
+            return c.rows(xp[:, 0], xq[:, 0]) if hasattr(c, "rows") else c
+
+        if hide_body < 0 and getattr(cam_a, "hide_head", False):
+            hide_body = cam_a.hide_body
+        xp, xq = poses(qpos_a, "qpos_a")
+        if qpos_b is None:
+            return self.render_ego_poses(xp, xq, obj_a, cam(cam_a, xp, xq), None, None, obj_b, cam_b, width, height, want, grid, hide_body, style)
+        xpb, xqb = poses(qpos_b, "qpos_b")
+        return self.render_ego_poses(xp, xq, obj_a, cam(cam_a, xp, xq), xpb, xqb, obj_b, None if cam_b is None else cam(cam_b, xpb, xqb), width, height, want,
+                                     grid, hide_body, style)
 
     def step_begin(self):
         _check(self.L.kp_sim_step_begin(self.h), "kp_sim_step_begin")

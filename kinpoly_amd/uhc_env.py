@@ -315,6 +315,12 @@ class BatchedHumanoidEnv:
         from .render import render_env
         return render_env(self.sim, self.get_obj_qpos().clone() if self.has_objects else None, envs, camera, width, height)
 
+    def render_ego(self, envs=None, width=64, height=64, camera=None):
+        """What every env's simulated figure sees from its head (all envs, or the indices `envs`), with the env's objects -> uint8 [n, H, W, 4] on the
+        device (kinpoly_amd.render.render_env_ego; camera: a HeadCamera, None for the default one at the head hull's centroid, fovy 90)."""
+        from .render import render_env_ego
+        return render_env_ego(self.sim, self.get_obj_qpos().clone() if self.has_objects else None, envs, camera, width, height)
+
     def push(self, entity, impulse, offset=None, env_mask=None):
         """An impulse push of the current state (KpSim.apply_impulse): entity int32 [N] (0..23 body, 24 + k object slot, -1 none), impulse [N, 6] = (p, l),
         offset [N, 3] or None, env_mask bool / uint8 [N] or None.  Call it between two step()s; the observation step() returned is then one push old."""

@@ -41,8 +41,20 @@ def build_parser():
                     "compute_physcis_metris) on the scene the run used, printed after the kinematic line")
     ap.add_argument("--cfg", type=str, default=None)
     ap.add_argument("--config_root", type=str, default=None)
+    from kinpoly_amd.dataset import add_of_source_argument
+    add_of_source_argument(ap)
     from kinpoly_amd.push import add_push_arguments
     return add_push_arguments(ap)      # --push_impulse LO [HI] and friends: perturbation pushes while the sequences play (off by default)
+
+
+def parse_args(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    from kinpoly_amd.dataset import of_source_refusal
+    no = of_source_refusal(args.of_source, args.wild)
+    if no:
+        ap.error(no)
+    return args
 
 
 def report_pushes(sched, res, result_dir, iter_num, data_file):
@@ -55,7 +67,7 @@ def report_pushes(sched, res, result_dir, iter_num, data_file):
 
 
 def main():
-    args = build_parser().parse_args()
+    args = parse_args()
     from kinpoly_amd import checkpoint as ck
     from kinpoly_amd import sim as kpsim
     from kinpoly_amd.context import PolicyARContext, TrajARNet
@@ -87,10 +99,10 @@ def main():
         from kinpoly_amd import dataset as D
         feats = joblib.load(args.data)
         if cfg.use_of:
-            of_path = cfg.of_feature_path()
-            have = os.path.exists(of_path)
-            print(f"of features: {of_path if have else 'synthetic stand-in (no ' + of_path + ')'}", flush=True)
-            of = joblib.load(of_path) if have else D.synthetic_of_features(feats, int(cfg.model_specs.get("cnn_fdim", 512)), seed=cfg.seed)
+            render_sim = kpsim.KpSim(kpsim.KpModel(kpsim.STEP_KPM), 1, 0) if args.of_source == "rendered" else None
+            of, said = D.select_of_features(args.of_source, feats, cfg.of_feature_path(), int(cfg.model_specs.get("cnn_fdim", 512)), cfg.seed, render_sim, args.wild)
+            print(f"of features: {said}", flush=True)
+            of = joblib.load(of) if isinstance(of, str) else of
     if cfg is not None:          # the net sizes the yml names (as train_ar_policy.py builds the agent), the context block and the `of` block
         ctx_kw = cfg.context_kwargs(int(np.asarray(next(iter(of.values()))).shape[1]) if of else None)
     ctx_block = int(ctx_kw.get("rnn_hdim", 1024)) if (ctx_kw.get("use_context") or ctx_kw.get("of_dim")) else 0          # TrajARNet.ctx_block

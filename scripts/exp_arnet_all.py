@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cfg", default=None)
     ap.add_argument("--mode", default="train", choices=("train", "test"))
@@ -40,7 +40,22 @@ def main():
     ap.add_argument("--epochs", type=int, default=0, help="stop after this many epochs of this run (0: up to cfg.num_epoch)")
     ap.add_argument("--num_sample", type=int, default=None); ap.add_argument("--batch_size", type=int, default=None)
     ap.add_argument("--save_interval", type=int, default=None)
-    args = ap.parse_args()
+    from kinpoly_amd.dataset import add_of_source_argument
+    return add_of_source_argument(ap)
+
+
+def parse_args(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    from kinpoly_amd.dataset import of_source_refusal
+    no = of_source_refusal(args.of_source, args.wild)
+    if no:
+        ap.error(no)
+    return ap, args
+
+
+def main():
+    ap, args = parse_args()
     if args.cfg is None:
         ap.error("--cfg is required (a config id under --config_root, or a .yml path)")
     if args.data is None:
@@ -80,8 +95,8 @@ def main():
         take_list = None
     of = None
     if cfg.use_of:      # the file's features (their width is the file's), or this repository's synthetic stand-in model_specs.cnn_fdim wide
-        of = of_path if os.path.exists(of_path) else D.synthetic_of_features(takes, int(cfg.model_specs.get("cnn_fdim", 512)), seed=cfg.seed)
-        print(f"of features: {of_path if isinstance(of, str) else 'synthetic stand-in (no ' + of_path + ')'}", flush=True)
+        of, said = D.select_of_features(args.of_source, takes, of_path, int(cfg.model_specs.get("cnn_fdim", 512)), cfg.seed, fk_sim, args.wild)
+        print(f"of features: {said}", flush=True)
     ds = D.StateARDataset(takes, takes=take_list, data_mode=data_mode, fr_num=E.FR_NUM_START, wild=args.wild, seed=cfg.seed, device=device, of_features=of)
     net = E.build_net(cfg.use_vel, cfg.use_head, cfg.use_action, as_policy=args.as_policy, use_context=bool(cfg.use_context), of_dim=ds.of_dim, **mk).to(device)
     # the training path: --path, else the default measured for the file's kind (DESIGN.md section 10 holds both records)

@@ -9,7 +9,8 @@ Reads either evaluation pickle: eval_ar_policy.py's `*_coverage_full.pkl` (per t
 / `gt`; columns 76..110 of a 111-wide `pred` are the object block).  Writes `<video_dir>/<take>/%04d.png` (characters of a take name other than letters, digits, `-`, `_`, `.` become `_`): the simulated figure in grey, the expert / kinematic
 target in red (unless --hide_expert), the take's objects, a checkered floor.  A take whose `pred` and expert lengths differ is cut to the shorter
 (eval_pose_all.py:687-692).  The frames show the collision geometry (the convex hulls), not the visual mesh.  --video assembles an mp4 per take with
-ffmpeg when it is on PATH.
+ffmpeg when it is on PATH.  --ego also writes what the simulated figure sees from its head (KpSim.render_ego through kinpoly_amd.render.HeadCamera) as
+`<video_dir>/<take>/ego_%04d.png`, --ego_size pixels square.
 """
 import argparse
 import os
@@ -37,6 +38,10 @@ def build_parser():
     p.add_argument("--every", type=int, default=1, help="render every N-th frame")
     p.add_argument("--kpm", default="", help="model blob (default: the shipped smpl_humanoid.kpm)")
     p.add_argument("--video", action="store_true", default=False, help="also assemble <video_dir>/<take>.mp4 with ffmpeg, when it is on PATH")
+    p.add_argument("--ego", action="store_true", default=False, help="also write ego_%%04d.png beside the frames: the simulated figure's own view from its head")
+    p.add_argument("--ego_size", type=int, default=256, help="width = height of the --ego frames")
+    p.add_argument("--ego_fovy", type=float, default=90.0)
+    p.add_argument("--ego_pitch", type=float, default=0.0, help="degrees the head camera looks down from the head's forward axis")
     return p
 
 
@@ -78,7 +83,7 @@ def main(argv=None):
     if missing:
         raise SystemExit(f"render_results.py: takes not in {args.results}: {', '.join(missing)} (it has {', '.join(list(takes)[:8])} ...)")
     from kinpoly_amd import sim as kpsim
-    from kinpoly_amd.render import Camera, render_sequence, write_png
+    from kinpoly_amd.render import Camera, HeadCamera, ego_sequence, render_sequence, write_png
     sim = kpsim.KpSim(kpsim.KpModel(args.kpm or kpsim.DEFAULT_KPM), 1)
     if int(sim.model.get_option("n_obj_geoms")) == 0:
         for t in takes.values():
@@ -96,7 +101,12 @@ def main(argv=None):
         d = os.path.join(args.video_dir, safe)
         for i, fr in enumerate(frames):
             write_png(os.path.join(d, "%04d.png" % i), fr)
-        print(f"{name}: {len(frames)} frames -> {d}")
+        if args.ego:
+            ego = ego_sequence(sim, t["pred"][sl], None if t["obj_pose"] is None else t["obj_pose"][sl], HeadCamera(fovy=args.ego_fovy, pitch=args.ego_pitch),
+                               args.ego_size, args.ego_size)
+            for i, fr in enumerate(ego):
+                write_png(os.path.join(d, "ego_%04d.png" % i), fr)
+        print(f"{name}: {len(frames)} frames{' and their ego views' if args.ego else ''} -> {d}")
         if ffmpeg:
             subprocess.check_call([ffmpeg, "-y", "-loglevel", "error", "-framerate", str(max(1, round(30 / args.every))), "-i", os.path.join(d, "%04d.png"),
                                    "-pix_fmt", "yuv420p", os.path.join(args.video_dir, f"{safe}.mp4")])

@@ -72,12 +72,24 @@ def build_parser():
     ap.add_argument("--no_log", action="store_true")
     ap.add_argument("--test_data", type=str, nargs="*", default=[], help="feature files of the test sets evaluated every save_model_interval iterations")
     ap.add_argument("--test_data_wild", type=str, nargs="*", default=[], help="the same for --wild test sets (evaluated on the ..._mesh_all.xml engine, agent_ar.py:305-314, 464)")
+    from kinpoly_amd.dataset import add_of_source_argument
+    add_of_source_argument(ap)
     from kinpoly_amd.push import add_push_arguments
     return add_push_arguments(ap)      # --push_impulse LO [HI] and friends: train under perturbation pushes (off by default)
 
 
+def parse_args(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    from kinpoly_amd.dataset import of_source_refusal
+    no = of_source_refusal(args.of_source, args.wild)
+    if no:
+        ap.error(no)
+    return args
+
+
 def main():
-    args = build_parser().parse_args()
+    args = parse_args()
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local)
     if world > 1:
@@ -100,14 +112,14 @@ def main():
         if not args.data and os.path.exists(cfg.feature_path()):
             args.data = cfg.feature_path()
     def of_features(takes):
-        """`use_of`: the yml's feature file, or the synthetic stand-in model_specs.cnn_fdim wide (as scripts/exp_arnet_all.py); None without use_of"""
+        """`use_of`: the features --of_source names (auto: the yml's feature file, or the synthetic stand-in model_specs.cnn_fdim wide, as
+        scripts/exp_arnet_all.py); None without use_of"""
         if cfg is None or not cfg.use_of:
             return None
-        of_path = cfg.of_feature_path()
-        have = os.path.exists(of_path)
+        of, said = D.select_of_features(args.of_source, takes, cfg.of_feature_path(), int(cfg.model_specs.get("cnn_fdim", 512)), cfg.seed, fk_sim, args.wild)
         if rank == 0:
-            print(f"of features: {of_path if have else 'synthetic stand-in (no ' + of_path + ')'}", flush=True)
-        return of_path if have else D.synthetic_of_features(takes, int(cfg.model_specs.get("cnn_fdim", 512)), seed=cfg.seed)
+            print(f"of features: {said}", flush=True)
+        return of
     if args.data:
         import joblib
         feats = joblib.load(args.data)
