@@ -454,6 +454,36 @@ int kp_sim_set_obj_state(kp_sim*, const float* obj_qpos, const float* obj_qvel, 
  * Enqueued on the handle's stream, no sync.  Refused (-1, kp_last_error) before anything is launched: null handle, null entity, null impulse. */
 int kp_sim_apply_impulse(kp_sim*, const int32_t* entity, const float* offset, const float* impulse, const uint8_t* env_mask, float* dqvel);
 
+/* Contact-force read-out of the STORED state.  Replaces what a mujoco-py user reads after `sim.forward()`: mj_contactForce / data.efc_force,
+ * data.cfrc_ext, data.qfrc_constraint, data.qacc and data.qfrc_actuator.  The reference reads none of them (deviation 38).
+ * The kernel runs the mj_forward of substep 0 of the control step kp_sim_step_ctrl would run next -- forward kinematics, collision, constraint rows,
+ * the Newton solve from the stored warm start -- and stops before the integration.  It stores into the output rows alone: every row of the handle
+ * (state, derived state, warm starts, diag) stays bit for bit, and a call between two control steps does not change them.
+ *   actuation  0 none (qfrc_applied = ctrl = 0);
+ *              1 torque: act [N,75] = qfrc_applied[0:6] ++ ctrl[69], used as given (no clipping);
+ *              2 controller: act [N, cc_action_dim] is a cc_action row; the torque is the one the control step's FIRST substep forms from it (stable
+ *                PD + residual force, on the kinematics of the derived state with stale_kinematics = 1, of the stored state otherwise; the
+ *                extended controller of a handle that has one, at i_iter = 0).  Zero where the model option actuation is 0.
+ *   act        device; required for actuation 1 and 2, ignored for 0.
+ *   env_mask   [N] or NULL: a masked-out env gets zero rows and ncon = 0.
+ *   out        device arrays, each may be NULL but not all:
+ *     ncon            int32 [N]        contacts of the collision pass
+ *     contact         float [N,64,12]  A, B, dist, pos[3], normal[3], force[3].  A = entity carrying the vertex (0..23 body, 24 + k object slot, the
+ *                                      numbering of kp_sim_contacts), B = entity carrying the surface (-1 world: floor or static geom; 24 + k), normal
+ *                                      pointing into A, force acting on A (N, world axes).  Rows >= ncon are zero.
+ *     wrench          float [N,26,6]   per entity the net contact force[3] and torque[3] ABOUT THE WORLD ORIGIN (world axes): + f on A, - f on an
+ *                                      object-slot B; floor and static geoms receive nothing.  Differs from data.cfrc_ext in the reference point only
+ *                                      (cfrc_ext: the subtree COM); kinpoly_amd.contact.shift_wrench moves it.
+ *     qfrc_constraint float [N,75]     J^T f of the contact rows + the joint-limit row forces
+ *     qacc            float [N,75]     the solve's minimiser
+ *     torque          float [N,75]     qfrc_applied[0:6] ++ ctrl[69] as the solve used them (mode 2: after the torque clip)
+ *     obj_qacc        float [N,2,6]    accelerations of the simulated object slots in their free-joint coordinates; zero without simulated objects
+ * Runs on the object layout exactly when the control step does (kp_sim_set_objects has installed a block).  Enqueued on the handle's stream, no sync.
+ * Refused (-1, kp_last_error names the argument) before anything is launched: null handle, null out, all outputs null, actuation outside 0..2,
+ * act NULL with actuation 1 or 2, a handle whose threads_per_env is not 64. */
+typedef struct { int32_t* ncon; float *contact, *wrench, *qfrc_constraint, *qacc, *torque, *obj_qacc; } kp_contact_out;
+int kp_sim_contact_forces(kp_sim*, int actuation, const float* act, const uint8_t* env_mask, const kp_contact_out* out);
+
 /* read-outs of the mujoco-py data fields the env uses (humanoid_im.py:342-416, humanoid_ar_v1.py:460-512) */
 typedef enum {
     KP_QPOS = 0,        /* data.qpos[:76]                    [N,76]  */

@@ -21,6 +21,7 @@
 #include "kp_policy_kernels.hpp"
 #include "kp_step_kernel.hpp"
 #include "kp_push.hpp"
+#include "kp_contact_force.hpp"
 #include "kp_pose_contacts.hpp"
 #include "kp_render.hpp"
 #include "kp_render_ego.hpp"
@@ -1793,6 +1794,31 @@ int kp_ctx_rows_write(int m, int R, int T, int Tp, int ctx_dim, int of_dim, cons
         if (p && !on_device(p)) return fail(w + "rows, sources and tables must be device memory (a host pointer was given)");
     HIP_OK(kp::launch_ctx_rows_write(kp::CtxRowsArgs{m, R, T, Tp, ctx_dim, of_dim, (const long long*)rows, seq, of, ctx_table, of_table}, (hipStream_t)stream));
     return 0;
+}
+
+int kp_sim_contact_forces(kp_sim* s, int actuation, const float* act, const uint8_t* mask, const kp_contact_out* out) {
+    if (!s) return fail("kp_sim_contact_forces: null handle");
+    if (!out) return fail("kp_sim_contact_forces: null out");
+    if (!out->ncon && !out->contact && !out->wrench && !out->qfrc_constraint && !out->qacc && !out->torque && !out->obj_qacc)
+        return fail("kp_sim_contact_forces: every output of out is null");
+    if (actuation < 0 || actuation > 2) return fail("kp_sim_contact_forces: actuation must be 0 (none), 1 (torque) or 2 (controller)");
+    if (actuation != 0 && !act) return fail("kp_sim_contact_forces: act is null with actuation 1 or 2");
+    if (s->model->threads != 64) return fail("kp_sim_contact_forces: needs a handle with threads_per_env = 64");
+    HIP_OK(hipSetDevice(s->device));
+    // the step kernels' argument pack without substeps and without a job queue; the kernel reads the state rows and the warm start only
+    StepPlan p{};
+    kp::StepArgs A = step_args(s, p, 0, nullptr, mask, nullptr);
+    A.warm_extrap = 0.f; A.prof = nullptr; A.dbg_contacts = nullptr; A.order = nullptr;
+    const kp::ContactOut O{out->ncon, out->contact, out->wrench, out->qfrc_constraint, out->qacc, out->torque, out->obj_qacc};
+    const dim3 grid(s->n), block(64);
+    if (s->obj.on) {
+        if (s->xc_on) hipLaunchKernelGGL((kp::k_contact_forces<true, true>), grid, block, sizeof(kp::EnvLdsObj), s->stream, A, s->xc, actuation, act, mask, O);
+        else hipLaunchKernelGGL((kp::k_contact_forces<true, false>), grid, block, sizeof(kp::EnvLdsObj), s->stream, A, s->xc, actuation, act, mask, O);
+    } else {
+        if (s->xc_on) hipLaunchKernelGGL((kp::k_contact_forces<false, true>), grid, block, sizeof(kp::EnvLds), s->stream, A, s->xc, actuation, act, mask, O);
+        else hipLaunchKernelGGL((kp::k_contact_forces<false, false>), grid, block, sizeof(kp::EnvLds), s->stream, A, s->xc, actuation, act, mask, O);
+    }
+    return launched();
 }
 
 }  // extern "C"

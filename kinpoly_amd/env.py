@@ -431,6 +431,7 @@ class BatchedHumanoidAREnv:
         with torch.no_grad():
             cc_action = self.cc_policy.select_action(cc_obs, mean_action, self.gen, cc_noise).contiguous()
         sim.step_ctrl(cc_action, self.frame_skip)
+        self._last_cc_action = cc_action          # contact_forces(None) reads it
         # cur_t += 1; fail (body diffs), reward, end / done / percent, and the action object's simulated pose for the next observation, in one launch (:288-316)
         self._flip ^= 1
         o = self._outs[self._flip]
@@ -451,6 +452,22 @@ class BatchedHumanoidAREnv:
         offset [N, 3] or None, env_mask bool / uint8 [N] or None.  Call it between two step()s; the observation step() returned is then one push old."""
         self.sim.apply_impulse(entity.to(self.device, torch.int32).contiguous(), impulse.to(self.device, torch.float32).contiguous(),
                                None if offset is None else offset.to(self.device, torch.float32).contiguous(), self._mask8(env_mask, self.device))
+
+    def contact_forces(self, cc_action=None, **kw) -> dict:
+        """Contact forces of the current state (KpSim.contact_forces: per-contact forces, per-entity wrenches about the world origin, qfrc_constraint, qacc,
+        the controller's torque) as device tensors.  cc_action [N, cc_action_dim]: the UHC action the torque is formed from; None = the cc_action of the
+        last step() (the env keeps a reference to that buffer), i.e. the forces the NEXT control step would start with if the controller repeated its action.
+        For an env that was reset inside or after that step the held action still belongs to the finished episode.  kw: env_mask, want (KpSim.contact_forces);
+        torque=[N,75] replaces the controller by a given torque."""
+        if "torque" in kw:
+            if cc_action is not None:
+                raise ValueError("contact_forces: cc_action and torque are mutually exclusive")
+            return self.sim.contact_forces(**kw)
+        if cc_action is None:
+            cc_action = getattr(self, "_last_cc_action", None)
+            if cc_action is None:
+                raise RuntimeError("contact_forces(): no cc_action yet -- call step() first, or pass cc_action")
+        return self.sim.contact_forces(action=cc_action.to(self.device, torch.float32).contiguous(), **kw)
 
     # getters (device tensors; reference names)
     def get_humanoid_qpos(self):
@@ -668,6 +685,10 @@ class HumanoidAREnv:
         body frame or None (BatchedHumanoidAREnv.push; no reference counterpart)."""
         t = lambda v, dt: torch.as_tensor(np.asarray(v), dtype=dt, device=self.b.device).reshape(1, -1)      # noqa: E731
         self.b.push(t(int(body), torch.int32).reshape(1), t(impulse, torch.float32), None if offset is None else t(offset, torch.float32))
+
+    def contact_forces(self, **kw) -> dict:
+        """BatchedHumanoidAREnv.contact_forces of the one env, as numpy arrays without the env axis"""
+        return {k: v[0].cpu().numpy() for k, v in self.b.contact_forces(**kw).items()}
 
     def _g(self, name):
         return self.b.sim.get(name)[0].double().cpu().numpy()

@@ -224,3 +224,32 @@ def coverage_physics_metrics(results: dict, gt: dict, sim, chunk_rows: int = 655
         by_action.setdefault(k.split("-")[0], []).append(m["succ"])
     return {**{kk: float(np.mean([m[kk] for m in per.values()])) for kk in keys},
             "succ_by_action": {a: float(np.mean(v)) for a, v in by_action.items()}, "per_take": per}
+
+
+def grf_metrics(results: dict, weight: float) -> dict:
+    """Ground-reaction summary of an evaluation run with grf=True (kinpoly_amd.evaluate): over all recorded frames of all sequences,
+        grf_mean_bw / grf_peak_bw   mean and peak of the feet's total vertical force sum_feet F_z / weight (weight = m g in N, contact.body_weight)
+        no_support / double_support share of frames with no foot / both feet in contact (foot_contact)
+        frames                      frames counted
+    Sequences recorded without grf are refused."""
+    fz, sup = [], []
+    for k, r in results.items():
+        if "grf" not in r or "foot_contact" not in r:
+            raise KeyError(f"grf_metrics: sequence {k!r} has no grf record (run the evaluation with grf=True)")
+        fz.append(np.asarray(r["grf"], np.float64)[:, :, 2].sum(1)); sup.append(np.asarray(r["foot_contact"], bool))
+    fz, sup = np.concatenate(fz) if fz else np.zeros(0), np.concatenate(sup) if sup else np.zeros((0, 2), bool)
+    if len(fz) == 0:
+        return {"grf_mean_bw": float("nan"), "grf_peak_bw": float("nan"), "no_support": float("nan"), "double_support": float("nan"), "frames": 0}
+    return {"grf_mean_bw": float(fz.mean() / weight), "grf_peak_bw": float(fz.max() / weight), "no_support": float((~sup.any(1)).mean()),
+            "double_support": float(sup.all(1).mean()), "frames": int(len(fz))}
+
+
+def write_grf_metrics(results: dict, weight: float, result_dir: str, iter_num: int, data_file: str) -> dict:
+    """grf_metrics as `<result_dir>/grf_metrics_<iter>_<data_file>.json`; returns them"""
+    import json
+    import os
+    m = grf_metrics(results, weight)
+    os.makedirs(result_dir, exist_ok=True)
+    with open(os.path.join(result_dir, f"grf_metrics_{iter_num}_{data_file}.json"), "w") as f:
+        json.dump(m, f, indent=1)
+    return m

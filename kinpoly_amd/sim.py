@@ -126,6 +126,16 @@ class KpRenderStyle(C.Structure):
         return st
 
 
+class KpContactOut(C.Structure):
+    """mirror of kp_contact_out: the device arrays kp_sim_contact_forces fills (each may be NULL, not all)"""
+    _fields_ = [(k, C.c_void_p) for k in ("ncon", "contact", "wrench", "qfrc_constraint", "qacc", "torque", "obj_qacc")]
+
+
+# outputs of KpSim.contact_forces: name -> (trailing shape, dtype)
+CONTACT_OUTPUTS = {"ncon": ((), torch.int32), "contact": ((64, 12), torch.float32), "wrench": ((26, 6), torch.float32), "qfrc_constraint": ((75,), torch.float32),
+                   "qacc": ((75,), torch.float32), "torque": ((75,), torch.float32), "obj_qacc": ((2, 6), torch.float32)}
+
+
 class KinPolyNativeError(RuntimeError):
     pass
 
@@ -143,6 +153,7 @@ _SIGNATURES = {
     "kp_sim_set_state": (_I, [_V, _V, _V, _V]), "kp_sim_set_full_state": (_I, [_V, _V, _V, _V, _V, _V]), "kp_sim_set_target": (_I, [_V, _V, _V]),
     "kp_sim_set_objects": (_I, [_V, _V, _V]), "kp_sim_set_obj_state": (_I, [_V, _V, _V, _V]),
     "kp_sim_apply_impulse": (_I, [_V, _V, _V, _V, _V, _V]),
+    "kp_sim_contact_forces": (_I, [_V, _I, _V, _V, _V]),      # handle, actuation, act, env_mask, kp_contact_out*
     "kp_sim_fk": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]), "kp_sim_fk_backward": (_I, [_V, _I, _V, _V, _V, _V, _V]),
     "kp_sim_pose_contacts": (_I, [_V, _I, _V, _V, _V, _F, _V, _V, _V]),
     # the offscreen renderer (kp_render.hip); kp_model_hull_planes is host only
@@ -449,6 +460,24 @@ class KpSim:
         _check(self.L.kp_sim_apply_impulse(self.h, _dev("entity", entity, (self.n,), torch.int32), _dev("offset", offset, (self.n, 3)),
                                            _dev("impulse", impulse, (self.n, 6)), _mask_ptr(env_mask, self.n), _ptr(dq, self.n, NV)), "kp_sim_apply_impulse")
         return dq
+
+    def contact_forces(self, action=None, torque=None, env_mask=None, want=tuple(CONTACT_OUTPUTS)) -> dict:
+        """Contact forces of the STORED state (kp_sim_contact_forces): the mj_forward of substep 0 of the control step step_ctrl would run next, without
+        the integration; nothing the handle stores changes.  action [N, cc_action_dim]: the controller's torque for that cc_action (mode 2); torque
+        [N,75] = qfrc_applied[0:6] ++ ctrl[69], as given (mode 1); neither: no actuation (mode 0).  want: names of CONTACT_OUTPUTS.  Returns a dict of
+        device tensors: ncon int32 [N]; contact [N,64,12] = A, B, dist, pos[3], normal[3] (into A), force[3] (on A); wrench [N,26,6] = force, torque about
+        the world origin per entity (24 bodies, 2 object slots); qfrc_constraint, qacc, torque [N,75]; obj_qacc [N,2,6]."""
+        if action is not None and torque is not None:
+            raise ValueError("contact_forces: action and torque are mutually exclusive")
+        want = tuple(want)
+        bad = [k for k in want if k not in CONTACT_OUTPUTS]
+        if bad or not want:
+            raise ValueError(f"contact_forces: want must name some of {tuple(CONTACT_OUTPUTS)}, got {want}")
+        mode, act = (2, _dev("action", action, (self.n, self.cc_action_dim))) if action is not None else (1, _dev("torque", torque, (self.n, NV))) if torque is not None else (0, None)
+        out = {k: torch.empty((self.n, *CONTACT_OUTPUTS[k][0]), dtype=CONTACT_OUTPUTS[k][1], device=self.device) for k in want}
+        st = KpContactOut(*[_dev(k, out.get(k), (self.n, *CONTACT_OUTPUTS[k][0]), CONTACT_OUTPUTS[k][1]) for k in CONTACT_OUTPUTS])
+        _check(self.L.kp_sim_contact_forces(self.h, mode, act, _mask_ptr(env_mask, self.n), C.byref(st)), "kp_sim_contact_forces")
+        return out
 
     def fk(self, qpos_rows: torch.Tensor):
         """qpos_fk_batch on [R,76] rows -> dict(qpos, wbpos, wbquat, bquat, body_com) of device tensors."""

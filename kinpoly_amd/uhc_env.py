@@ -328,6 +328,22 @@ class BatchedHumanoidEnv:
         self.sim.apply_impulse(entity.to(self.device, torch.int32).contiguous(), impulse.to(self.device, torch.float32).contiguous(),
                                None if offset is None else offset.to(self.device, torch.float32).contiguous(), m8)
 
+    def contact_forces(self, cc_action=None, **kw) -> dict:
+        """Contact forces of the current state (KpSim.contact_forces: per-contact forces, per-entity wrenches about the world origin, qfrc_constraint, qacc,
+        the controller's torque) as device tensors.  cc_action [N, action_dim]: the action the stable-PD torque is formed from, against the PD base pose the
+        handle stores at the time of the call (after step(): the expert frame of the observation); None = the action of the last step() (the env keeps a
+        reference to that buffer).  For an env that was reset inside or after that step the held action still belongs to the finished episode.
+        kw: env_mask, want; torque=[N,75] replaces the controller by a given torque."""
+        if "torque" in kw:
+            if cc_action is not None:
+                raise ValueError("contact_forces: cc_action and torque are mutually exclusive")
+            return self.sim.contact_forces(**kw)
+        if cc_action is None:
+            cc_action = getattr(self, "_last_cc_action", None)
+            if cc_action is None:
+                raise RuntimeError("contact_forces(): no action yet -- call step() first, or pass cc_action")
+        return self.sim.contact_forces(action=cc_action.to(self.device, torch.float32).contiguous(), **kw)
+
     def _scheduled_push(self, done):
         """the tail of step(): what the schedule draws for the episode clock the step just advanced, for the envs that go on.
         With a schedule installed a non-finite body_diff counts as a failure: a push far beyond what a body survives (1e4 N s at every step) drives the fp32
@@ -347,6 +363,7 @@ class BatchedHumanoidEnv:
         if self._prev_qpos is not None:                                # env.prev_qpos (humanoid_im.py:538): local_rfc_implicit's root velocities
             self._prev_qpos.copy_(sim.view("qpos"))
         sim.step_ctrl_base(a.contiguous(), self._base, self.frame_skip)
+        self._last_cc_action = a
         track, tc = (sim.uhc_track, self._tc) if self._tcr is None else (sim.uhc_track_r, self._tcr)
         track(self.takes, self._st, tc, a, o["custom_reward"], o["custom_info"], o["body_diff"], o["fail"], o["end"], o["done"], o["percent"])
         if self.push_schedule is not None:
@@ -410,6 +427,7 @@ class BatchedHumanoidEnv:
         sim.set_target(tq)
         prev_qpos = sim.get("qpos") if self._prev_qpos is not None else None       # env.prev_qpos (humanoid_im.py:538)
         sim.step_ctrl(a.contiguous(), self.frame_skip)
+        self._last_cc_action = a
         self.cur_t += 1
         xpos, bquat = sim.get("xpos"), sim.get("bquat")
         com = (sim.get("xipos").view(self.n, 24, 3) * self.body_mass[None, :, None]).sum(1) / self.body_mass.sum()

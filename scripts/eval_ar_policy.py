@@ -39,6 +39,8 @@ def build_parser():
     ap.add_argument("--metrics", action="store_true", help="with --data: root_dist / mpjpe / accel_dist / vel_dist / head_dist / succ over the takes (eval_pose_all.py's kinematic metrics)")
     ap.add_argument("--physics_metrics", action="store_true", help="with --data: pen_pred / pen_gt / slide_pred / slide_gt / succ (eval_pose_all.py's "
                     "compute_physcis_metris) on the scene the run used, printed after the kinematic line")
+    ap.add_argument("--grf", action="store_true", help="record ground reaction forces after every env step (grf / cop / foot_contact / load in the "
+                    "coverage_full record) and write grf_metrics_<iter>_<data>.json; off: every output file is what it is without the flag")
     ap.add_argument("--cfg", type=str, default=None)
     ap.add_argument("--config_root", type=str, default=None)
     from kinpoly_amd.dataset import add_of_source_argument
@@ -64,6 +66,15 @@ def report_pushes(sched, res, result_dir, iter_num, data_file):
     joblib.dump(sched.by_take, os.path.join(result_dir, f"push_log_{iter_num}_{data_file}.pkl"))
     print(f"pushes applied: {sum(len(v) for v in sched.by_take.values())}")
     print(f"coverage under pushes: {sum(1 for r in res.values() if r['percent'] == 1 and not r['fail_safe'])} out of {len(res)}")
+
+
+def report_grf(res, result_dir, iter_num, data_file):
+    """the --grf line and <result_dir>/grf_metrics_<iter>_<data>.json"""
+    from kinpoly_amd import metrics as M
+    from kinpoly_amd.contact import body_weight
+    from kinpoly_amd.model_compiler import DEFAULT_KPM
+    m = M.write_grf_metrics(res, body_weight(DEFAULT_KPM), result_dir, iter_num, data_file)
+    print("".join(f"{k}:{v:.3f} \t " for k, v in m.items()))
 
 
 def main():
@@ -124,9 +135,11 @@ def main():
         from kinpoly_amd.evaluate import eval_dataset
         ds = D.StateARDataset(args.data if feats is None else feats, takes=takes, data_mode="test", fr_num=T, wild=args.wild, seed=0, device=env.device, of_features=of)
         builder = PolicyARContext(net, kpsim.KpSim(env.model, n, 0), smooth=bool(cfg.smooth) if cfg else True, keep_context_feat=bool(ctx_block))
-        res = eval_dataset(env, net, builder, ds, fail_safe=args.fail_safe, push_schedule=sched)
+        res = eval_dataset(env, net, builder, ds, fail_safe=args.fail_safe, push_schedule=sched, grf=args.grf)
         data_file = args.data_file if args.cfg else os.path.splitext(os.path.basename(args.data))[0]
         cov = write_coverage(res, args.result_dir, args.iter, data_file)
+        if args.grf:
+            report_grf(res, args.result_dir, args.iter, data_file)
         if sched is not None:
             report_pushes(sched, res, args.result_dir, args.iter, data_file)
         pct = np.array([r["percent"] for r in res.values()])
@@ -152,8 +165,10 @@ def main():
     ctx = PolicyARContext(net, kpsim.KpSim(env.model, n, 0), smooth=True).init_context(ctx)
     env.load_context(ctx)
     keys = [f"standing-{i:05d}" for i in range(n)]
-    res = run_sequences(env, net, keys, fail_safe=args.fail_safe, push_schedule=sched)
+    res = run_sequences(env, net, keys, fail_safe=args.fail_safe, push_schedule=sched, grf=args.grf)
     cov = write_coverage(res, args.result_dir, args.iter, args.data_file)
+    if args.grf:
+        report_grf(res, args.result_dir, args.iter, args.data_file)
     if sched is not None:
         report_pushes(sched, res, args.result_dir, args.iter, args.data_file)
     pct = np.array([r["percent"] for r in res.values()])

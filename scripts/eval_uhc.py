@@ -48,6 +48,8 @@ def build_parser():
     p.add_argument("--num_envs", type=int, default=64)
     p.add_argument("--dataset", choices=("amass_single", "smpl_obj"), default="amass_single",
                    help="the loader of the take file: amass_single (DatasetAMASSSingle's pickle) or smpl_obj (DatasetSMPLObj's: takes that carry objects)")
+    p.add_argument("--grf", action="store_true", help="record ground reaction forces after every env step (grf / cop / foot_contact / load in the "
+                   "coverage_full record) and write grf_metrics_<iter>_<data>.json; off: every output file is what it is without the flag")
     from kinpoly_amd.push import add_push_arguments
     return add_push_arguments(p)       # --push_impulse LO [HI] and friends: perturbation pushes while the takes play (off by default)
 
@@ -100,12 +102,17 @@ def main(argv=None):
         rs.std.copy_((torch.sqrt(rs._m2 / (rs.count - 1)) if rs.count > 1 else rs._mean64.abs()).float())
     from kinpoly_amd.push import schedule_from_args
     sched = schedule_from_args(args, n, env.device, record=True)
-    res = eval_uhc_takes(env, agent.policy, rs, ds, fail_safe=args.fail_safe, push_schedule=sched)
+    res = eval_uhc_takes(env, agent.policy, rs, ds, fail_safe=args.fail_safe, push_schedule=sched, grf=args.grf)
     for k, r in res.items():
         print(f"{r['percent']}  | {k} | {r['fail_safe']}")
     out_dir = os.path.dirname(os.path.abspath(ckpt))
     cov = write_uhc_coverage(res, out_dir, args.iter, args.data, no_full=args.no_full)
     print(f"Coverage of {cov} out of {ds.get_len()}")
+    if args.grf:
+        from kinpoly_amd import metrics as M
+        from kinpoly_amd.contact import body_weight
+        m = M.write_grf_metrics(res, body_weight(env), out_dir, args.iter, args.data)       # env.body_mass: the masses of the model the env runs
+        print("".join(f"{k}:{v:.3f} \t " for k, v in m.items()))
     if sched is not None:              # the coverage pickles keep their keys; the pushes go to a file of their own
         import joblib
         joblib.dump(sched.by_take, os.path.join(out_dir, f"push_log_{args.iter}_{args.data}.pkl"))

@@ -1,0 +1,98 @@
+#!/usr/bin/env python
+"""Resource table of the kernels in a built libkinpoly_sim.so, read from the code objects' metadata (no GPU needed): VGPRs, AGPRs, SGPRs, scratch bytes per
+lane, static LDS bytes and code bytes per kernel.  Two builds of the same sources give identical tables; `--diff other.so` compares them row by row.
+
+    python tools/kernel_resources.py [lib.so] [--match kp_step_] [--diff other.so]
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import re
+import shutil
+import struct
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+COLS = ("vgpr", "agpr", "sgpr", "scratch_bytes", "lds_bytes", "code_bytes")
+
+
+def _llvm(tool: str) -> str:
+    for d in (os.path.dirname(shutil.which("hipcc") or ""), "/opt/rocm/bin"):
+        p = os.path.normpath(os.path.join(os.path.realpath(d), "..", "lib", "llvm", "bin", tool))
+        if os.path.exists(p):
+            return p
+    for p in (shutil.which(tool), "/opt/rocm/llvm/bin/" + tool):
+        if p and os.path.exists(p):
+            return p
+    raise RuntimeError(f"{tool} not found (ROCm's LLVM tools are required)")
+
+
+def code_objects(lib: str) -> list[bytes]:
+    """the gfx950 ELF images inside the library's .hip_fatbin section (one per translation unit)"""
+    with tempfile.TemporaryDirectory() as tmp:
+        fb = os.path.join(tmp, "fatbin")
+        subprocess.check_call([_llvm("llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", lib, fb])
+        blob = open(fb, "rb").read()
+    out = []
+    for m in re.finditer(b"\x7fELF\x02\x01", blob):
+        o = m.start()
+        if struct.unpack_from("<H", blob, o + 18)[0] != 224:           # EM_AMDGPU
+            continue
+        shoff, = struct.unpack_from("<Q", blob, o + 40)
+        shentsize, shnum = struct.unpack_from("<HH", blob, o + 58)
+        out.append(blob[o:o + shoff + shentsize * shnum])
+    return out
+
+
+def table(lib: str) -> dict:
+    """kernel name (demangled) -> dict of COLS"""
+    rows = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for i, img in enumerate(code_objects(lib)):
+            p = os.path.join(tmp, f"co{i}.o")
+            open(p, "wb").write(img)
+            notes = subprocess.check_output([_llvm("llvm-readelf"), "--notes", p], text=True)
+            sizes = {}
+            for ln in subprocess.check_output([_llvm("llvm-readelf"), "-sW", p], text=True).splitlines():
+                f = ln.split()
+                if len(f) >= 8 and f[3] == "FUNC":
+                    sizes[f[7]] = int(f[2])
+            for blk in re.split(r"\n\s*- \.agpr_count:", notes)[1:]:
+                blk = ".agpr_count:" + blk
+                g = lambda k: re.search(r"\." + k + r":\s*(\S+)", blk)      # noqa: E731
+                sym = g("symbol").group(1)[:-3]                                # drop the .kd suffix
+                filt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")      # readable names where a demangler exists; the mangled one otherwise
+                name = subprocess.check_output([filt, sym], text=True).strip() if filt else sym
+                rows[name] = dict(vgpr=int(g("vgpr_count").group(1)), agpr=int(g("agpr_count").group(1)), sgpr=int(g("sgpr_count").group(1)),
+                                  scratch_bytes=int(g("private_segment_fixed_size").group(1)), lds_bytes=int(g("group_segment_fixed_size").group(1)),
+                                  code_bytes=sizes.get(sym, -1))
+    return rows
+
+
+def render(rows: dict) -> str:
+    out = ["| kernel | " + " | ".join(COLS) + " |", "|---|" + "---:|" * len(COLS)]
+    for k in sorted(rows):
+        out.append(f"| `{k}` | " + " | ".join(str(rows[k][c]) for c in COLS) + " |")
+    return "\n".join(out)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("lib", nargs="?", default=os.path.join(ROOT, "kinpoly_amd", "libkinpoly_sim.so"))
+    ap.add_argument("--match", default="", help="only kernels whose name contains this")
+    ap.add_argument("--diff", default=None, help="another build of the library: exit 1 unless the matched rows are identical")
+    a = ap.parse_args()
+    rows = {k: v for k, v in table(a.lib).items() if a.match in k}
+    print(render(rows))
+    if a.diff:
+        other = {k: v for k, v in table(a.diff).items() if a.match in k}
+        bad = sorted(k for k in set(rows) | set(other) if rows.get(k) != other.get(k))
+        print(f"\n{len(rows)} kernels here, {len(other)} there, {len(bad)} differ" + "".join(f"\n  {k}: {rows.get(k)} != {other.get(k)}" for k in bad))
+        sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()
