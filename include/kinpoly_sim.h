@@ -484,6 +484,33 @@ int kp_sim_apply_impulse(kp_sim*, const int32_t* entity, const float* offset, co
 typedef struct { int32_t* ncon; float *contact, *wrench, *qfrc_constraint, *qacc, *torque, *obj_qacc; } kp_contact_out;
 int kp_sim_contact_forces(kp_sim*, int actuation, const float* act, const uint8_t* env_mask, const kp_contact_out* out);
 
+/* Inverse dynamics on motion ROWS.  Replaces what a mujoco-py user reads after `mj_inverse`: data.qfrc_inverse, the generalized force the model
+ * needs to perform a given motion (qpos, qvel, qacc).  The reference never calls it (deviation 39).  In the soft-constraint model
+ * the inverse is closed form, no solve: jar = J qacc - aref, row forces -D jar where jar < 0, qfrc_inverse = M qacc + qfrc_bias - J^T f.  Its first
+ * six entries are the residual wrench no contact and no joint supplies (force on the root in world axes, torque about the root position in the
+ * root's own axes: kinpoly_amd.dynamics.root_residual); the other 69 are the joint torques a controller would have to deliver.
+ * A rows API like kp_sim_fk: n_rows is independent of the handle's envs; the kernel reads the model tables (options contact / limits honoured) and
+ * the row inputs, none of the handle's stored state and no warm start, and stores into the output rows alone.  Kinematics are always those of the
+ * given pose.  One launch for all rows (one wavefront per row).
+ *   qpos      [R,76] device, required.
+ *   qvel      [R,75] or NULL: zero velocities.
+ *   qacc      [R,75] or NULL: zero accelerations (gravity compensation: the static torque of a pose).
+ *   obj_qpos  [R,35] or NULL: the five objects' free-joint poses; those within 50 m of the origin are STATIC obstacles at that pose (zero velocity,
+ *             zero acceleration: what dynamic_objects = 0 means in the control step), the humanoid's hulls collide with their boxes and cylinders.
+ *             NULL, or a row with every object parked, is the floor scene (bit for bit the same result).
+ *   out       device arrays, each may be NULL but not all:
+ *     qfrc_inverse    float [R,75]     in the coordinates of qfrc_applied[0:6] ++ ctrl[69] (kp_sim_contact_forces' torque)
+ *     qfrc_constraint float [R,75]     J^T f of the contact rows + the joint-limit row forces, at the GIVEN qacc
+ *     qfrc_bias       float [R,75]     C(q, qvel) + g of the forward pass (kp_sim_mass_matrix' bias)
+ *     contact         float [R,64,12]  the rows of kp_sim_contact_forces; B = -1 for the floor and for a static geom
+ *     net_wrench      float [R,6]      sum of the contact forces on the humanoid and their torque ABOUT THE WORLD ORIGIN (world axes)
+ *     ncon            int32 [R]        contacts of the collision pass
+ * Enqueued on the handle's stream, no sync (the first call with obj_qpos, and one with more rows than any before, grows a scratch buffer and waits
+ * for the stream once).  n_rows == 0 does nothing.  Refused (-1, kp_last_error names the argument) before anything is launched: null handle, null
+ * qpos, null out, all outputs null, n_rows < 0, a handle whose threads_per_env is not 64, obj_qpos on a blob without object geoms. */
+typedef struct { float *qfrc_inverse, *qfrc_constraint, *qfrc_bias, *contact, *net_wrench; int32_t* ncon; } kp_invdyn_out;
+int kp_sim_inverse_dynamics(kp_sim*, int n_rows, const float* qpos, const float* qvel, const float* qacc, const float* obj_qpos, const kp_invdyn_out* out);
+
 /* read-outs of the mujoco-py data fields the env uses (humanoid_im.py:342-416, humanoid_ar_v1.py:460-512) */
 typedef enum {
     KP_QPOS = 0,        /* data.qpos[:76]                    [N,76]  */

@@ -22,6 +22,7 @@
 #include "kp_step_kernel.hpp"
 #include "kp_push.hpp"
 #include "kp_contact_force.hpp"
+#include "kp_inverse_dyn.hpp"
 #include "kp_pose_contacts.hpp"
 #include "kp_render.hpp"
 #include "kp_render_ego.hpp"
@@ -94,6 +95,10 @@ struct RenderTables {     // the hulls' face planes (kp::hull_planes), uploaded 
     float* partial = nullptr; size_t partial_n = 0;       // kp_sim_render_ego's per-tile flow sums (floats held); grows on demand
 };
 
+struct InvDynScratch {    // kp_sim_inverse_dynamics with objects: what the placement kernel (k_set_objects) writes for the call's rows; grows on demand
+    float* buf = nullptr; size_t rows = 0;
+};
+
 struct kp_sim {
     const kp_model* model = nullptr;
     int n = 0, device = 0;
@@ -113,6 +118,7 @@ struct kp_sim {
     OverflowReadback ovf;
     ObjectRows obj;
     RenderTables rd;
+    InvDynScratch idyn;
     Timing tm;
     long launch_index = 0;
     int last_nsub = 15;                               // substeps of the last control step (kp_sim_lean_state)
@@ -660,6 +666,7 @@ void kp_sim_destroy(kp_sim* s) {
     hipStreamSynchronize(s->stream);
     for (void* p : s->allocs) hipFree(p);
     if (s->rd.partial) hipFree(s->rd.partial);
+    if (s->idyn.buf) hipFree(s->idyn.buf);
     for (hipEvent_t e : s->tm.ring) hipEventDestroy(e);
     if (s->ovf.host) { hipHostFree(s->ovf.host); for (hipEvent_t e : s->ovf.ev) if (e) hipEventDestroy(e); }
     if (s->tm.ev0) hipEventDestroy(s->tm.ev0);
@@ -1817,6 +1824,52 @@ int kp_sim_contact_forces(kp_sim* s, int actuation, const float* act, const uint
     } else {
         if (s->xc_on) hipLaunchKernelGGL((kp::k_contact_forces<false, true>), grid, block, sizeof(kp::EnvLds), s->stream, A, s->xc, actuation, act, mask, O);
         else hipLaunchKernelGGL((kp::k_contact_forces<false, false>), grid, block, sizeof(kp::EnvLds), s->stream, A, s->xc, actuation, act, mask, O);
+    }
+    return launched();
+}
+
+int kp_sim_inverse_dynamics(kp_sim* s, int n_rows, const float* qpos, const float* qvel, const float* qacc, const float* obj_qpos, const kp_invdyn_out* out) {
+    if (!s) return fail("kp_sim_inverse_dynamics: null handle");
+    if (n_rows < 0) return fail("kp_sim_inverse_dynamics: n_rows < 0");
+    if (!qpos) return fail("kp_sim_inverse_dynamics: null qpos");
+    if (!out) return fail("kp_sim_inverse_dynamics: null out");
+    if (!out->qfrc_inverse && !out->qfrc_constraint && !out->qfrc_bias && !out->contact && !out->net_wrench && !out->ncon)
+        return fail("kp_sim_inverse_dynamics: every output of out is null");
+    if (s->model->threads != 64) return fail("kp_sim_inverse_dynamics: needs a handle with threads_per_env = 64");
+    if (obj_qpos && !s->obj.d_geoms) return fail("kp_sim_inverse_dynamics: obj_qpos given but the model blob has no object geoms");
+    if (n_rows == 0) return 0;
+    HIP_OK(hipSetDevice(s->device));
+    kp::InvDynArgs A{};
+    A.T = s->T; A.P = s->P; A.n_rows = n_rows;
+    A.qpos = qpos; A.qvel = qvel; A.qacc = qacc;
+    A.O = kp::InvDynOut{out->qfrc_inverse, out->qfrc_constraint, out->qfrc_bias, out->contact, out->net_wrench, out->ncon};
+    if (obj_qpos) {
+        // the rows' static geoms, placed by the kernel kp_sim_set_objects uses (static mode), into the call's scratch: per row the geoms [8,17], then what
+        // that kernel stores besides (object block [35], velocities [30], warm start [12], geom count, slots), none of which is read here
+        constexpr size_t GW = kp::D_MAXGEOM * 17, PER_ROW = GW + 35 + 30 + 6 * kp::D_MAXOBJ + 1 + 1;
+        InvDynScratch& sc = s->idyn;
+        if ((size_t)n_rows > sc.rows) {
+            if (sc.buf) { HIP_OK(hipStreamSynchronize(s->stream)); HIP_OK(hipFree(sc.buf)); sc.buf = nullptr; sc.rows = 0; }
+            HIP_OK(hipMalloc((void**)&sc.buf, sizeof(float) * PER_ROW * (size_t)n_rows));
+            sc.rows = (size_t)n_rows;
+        }
+        const size_t R = (size_t)n_rows;
+        float* geoms = sc.buf; float* oq = geoms + R * GW; float* ov = oq + R * 35; float* ow = ov + R * 30;
+        int* ngeom = (int*)(ow + R * 6 * kp::D_MAXOBJ);
+        signed char* slot = (signed char*)(ngeom + R);
+        static_assert(kp::D_MAXOBJ <= 4, "the slot bytes of a row fit the one word the scratch keeps for them");
+        hipLaunchKernelGGL(k_set_objects, dim3((n_rows + 63) / 64), dim3(64), 0, s->stream, n_rows, obj_qpos, (const uint8_t*)nullptr, oq, geoms, ngeom,
+                           s->obj.d_geoms, s->obj.d_mass, s->obj.n_geoms, s->obj.n_obj, 0, slot, ov, ow, (const int*)nullptr, (const float*)nullptr, (float*)nullptr);
+        HIP_OK(hipGetLastError());
+        A.geoms = geoms; A.ngeom = ngeom;
+    }
+    // one wavefront per row; a launch holds at most 2^24 rows (grid x block stays below 2^32 threads)
+    constexpr int CHUNK = 1 << 24;
+    for (int r0 = 0; r0 < n_rows; r0 += CHUNK) {
+        A.row0 = r0;
+        const dim3 grid(std::min(CHUNK, n_rows - r0)), block(64);
+        if (obj_qpos) hipLaunchKernelGGL((kp::k_inverse_dynamics<true>), grid, block, sizeof(kp::EnvLdsObj), s->stream, A);
+        else hipLaunchKernelGGL((kp::k_inverse_dynamics<false>), grid, block, sizeof(kp::EnvLds), s->stream, A);
     }
     return launched();
 }

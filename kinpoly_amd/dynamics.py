@@ -1,0 +1,90 @@
+"""Inverse dynamics of pose sequences (KpSim.inverse_dynamics): finite-difference velocities and accelerations of a motion, the
+root residual wrench, and the plausibility scores built on them.  Torch only; everything but inverse_dynamics_sequence works on CPU tensors too.
+
+Coordinates.  qfrc_inverse [., 75] is a generalized force in the model's dof coordinates: entries 0..2 pair with the root's linear velocity (world
+axes), entries 3..5 with its angular velocity, which the free joint expresses in the ROOT's own axes (the motion axes of dofs 3..5 are the columns of
+the root's rotation matrix, taken about the root position; forward_kin_bias in kp_step_kernel.hpp), entries 6..74 are the 69 hinge torques in ctrl order.
+"""
+from __future__ import annotations
+
+import torch
+
+from .uhc_env import get_qvel_fd_new_t
+
+NQ, NV, NU = 76, 75, 69
+
+
+def _take_bounds(T: int, take_off, device):
+    """per row the first row and the row past the last of its take; take_off: [n_takes + 1] row offsets (0 first, T last) or None = one take"""
+    if take_off is None:
+        return torch.zeros(T, dtype=torch.long, device=device), torch.full((T,), T, dtype=torch.long, device=device)
+    off = torch.as_tensor(take_off, dtype=torch.long, device=device).reshape(-1)
+    if off.numel() < 2 or int(off[0]) != 0 or int(off[-1]) != T or bool((off[1:] <= off[:-1]).any()):
+        raise ValueError(f"motion_derivatives: take_off must rise from 0 to {T}, got {off.tolist()}")
+    take = torch.searchsorted(off, torch.arange(T, device=device), right=True) - 1
+    return off[take], off[take + 1]
+
+
+def motion_derivatives(qpos: torch.Tensor, dt: float, take_off=None):
+    """qpos [T, 76] -> (qvel [T, 75], qacc [T, 75]) by the take library's convention: qvel[t] = get_qvel_fd_new(qpos[t], qpos[t + 1], dt), the last row
+    of a take repeating its predecessor's; qacc[t] = (qvel[t + 1] - qvel[t]) / dt, the last two rows repeating the one before them.  No clamp (the
+    observation clamps at +-10; a dynamics score must not).  take_off: row offsets [n_takes + 1] of takes stored back to back -- no difference crosses
+    a boundary.  A take of one row has zero velocity, one of fewer than three rows zero acceleration."""
+    if qpos.dim() != 2 or qpos.shape[1] != NQ:
+        raise ValueError(f"motion_derivatives: qpos must be [T, {NQ}], got {tuple(qpos.shape)}")
+    T = qpos.shape[0]
+    if T == 0:
+        return qpos.new_zeros((0, NV)), qpos.new_zeros((0, NV))
+    start, end = _take_bounds(T, take_off, qpos.device)
+    t = torch.arange(T, device=qpos.device)
+    iv = torch.maximum(torch.minimum(t, end - 2), start)               # the row whose forward difference this row takes
+    qvel = get_qvel_fd_new_t(qpos[iv], qpos[torch.minimum(iv + 1, end - 1)], dt)
+    ia = torch.maximum(torch.minimum(t, end - 3), start)
+    qacc = (qvel[torch.minimum(ia + 1, end - 1)] - qvel[ia]) / dt
+    return qvel, qacc
+
+
+def _quat_rotate(q: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """R(q) v for q [., 4] = (w, x, y, z), normalised here"""
+    q = q / q.norm(dim=-1, keepdim=True).clamp_min(1e-30)
+    u, w = q[..., 1:], q[..., :1]
+    c = torch.cross(u, v, dim=-1)
+    return v + 2.0 * (w * c + torch.cross(u, c, dim=-1))
+
+
+def root_residual(qfrc_inverse: torch.Tensor, qpos: torch.Tensor):
+    """The residual wrench on the root: (force [., 3], torque [., 3]) in WORLD axes, the torque about the root position qpos[., 0:3].  It is what no
+    contact and no joint supplies: zero for a physically possible motion."""
+    return qfrc_inverse[..., :3], _quat_rotate(qpos[..., 3:7], qfrc_inverse[..., 3:6])
+
+
+def inverse_dynamics_sequence(sim, qpos: torch.Tensor, dt: float, obj_qpos: torch.Tensor | None = None, chunk_rows: int = 65536, take_off=None,
+                              want=("qfrc_inverse", "qfrc_constraint", "qfrc_bias", "contact", "net_wrench", "ncon")) -> dict:
+    """KpSim.inverse_dynamics over a whole sequence qpos [T, 76] (+ obj_qpos [T, 35]) with motion_derivatives' qvel / qacc, chunk_rows rows per launch.
+    Returns the kernel's outputs named in `want` for all T rows, plus 'qvel' and 'qacc'."""
+    q = qpos.to(sim.device, torch.float32).contiguous()
+    o = None if obj_qpos is None else obj_qpos.to(sim.device, torch.float32).contiguous()
+    qvel, qacc = motion_derivatives(q, dt, take_off)
+    parts = []
+    for a in range(0, q.shape[0], max(int(chunk_rows), 1)):
+        b = a + max(int(chunk_rows), 1)
+        parts.append(sim.inverse_dynamics(q[a:b], qvel[a:b].contiguous(), qacc[a:b].contiguous(), None if o is None else o[a:b], want=want))
+    out = {k: torch.cat([p[k] for p in parts]) for k in want} if parts else sim.inverse_dynamics(q, qvel, qacc, o, want=want)
+    out["qvel"], out["qacc"] = qvel, qacc
+    return out
+
+
+def plausibility(qfrc_inverse: torch.Tensor, qpos: torch.Tensor, qvel: torch.Tensor, torque_lim, weight: float) -> dict:
+    """Per-frame dynamics scores of a motion from its inverse dynamics (rows [T, .]) and their means under 'mean':
+        resid_force       |root residual force| / weight (weight = m g in N: 1.0 = the whole body held up by nothing)
+        resid_torque      |root residual torque| in N m (about the root position)
+        joint_torque_rms  rms of the 69 joint torques, N m
+        over_limit        share of the joints with |tau| > torque_lim [69]
+        power             sum_j |tau_j qvel_j| over the joints, W"""
+    f, tq = root_residual(qfrc_inverse, qpos)
+    tau = qfrc_inverse[..., 6:]
+    lim = torch.as_tensor(torque_lim, dtype=tau.dtype, device=tau.device)
+    out = {"resid_force": f.norm(dim=-1) / weight, "resid_torque": tq.norm(dim=-1), "joint_torque_rms": tau.pow(2).mean(-1).sqrt(),
+           "over_limit": (tau.abs() > lim).to(tau.dtype).mean(-1), "power": (tau * qvel[..., 6:]).abs().sum(-1)}
+    out["mean"] = {k: v.mean() for k, v in out.items()}
+    return out

@@ -226,6 +226,71 @@ def coverage_physics_metrics(results: dict, gt: dict, sim, chunk_rows: int = 655
             "succ_by_action": {a: float(np.mean(v)) for a, v in by_action.items()}, "per_take": per}
 
 
+DYNAMICS_KEYS = ("resid_force", "resid_torque", "torque_rms", "over_limit", "power")
+
+
+def coverage_dynamics_metrics(results: dict, gt: dict, sim, dt=1.0 / 30.0, kpm=None, chunk_rows: int = 65536) -> dict:
+    """Dynamics score of pose sequences that were never simulated: inverse dynamics (KpSim.inverse_dynamics on
+    dynamics.motion_derivatives' finite differences) of the predicted (`pred`, its first 76 columns) and the ground-truth trajectory of every take of a
+    `*_coverage_full.pkl` dict, with the take's object block (`obj_pose` [T, 35], static obstacles) where the pickle has one and sim's blob has object
+    geoms.  gt as in coverage_metrics; takes are cut to n = min(len(pred), len(gt qpos)), n >= 3.  kpm: the blob (path or read_kpm dict) whose
+    torque_lim and body masses are used; default: the blob sim's model was loaded from.  Per side (pred / gt), means over a take's frames of
+    dynamics.plausibility: resid_force_* (root residual force / body weight), resid_torque_* (N m), torque_rms_* (N m), over_limit_* (share of
+    joint-frames beyond torque_lim), power_* (W).  Returns their means over the takes, 'by_action' (the same per action prefix) and 'per_take'."""
+    import torch
+    from . import dynamics
+    from .contact import body_weight
+    from .model_compiler import DEFAULT_KPM, read_kpm
+    kpm = kpm if kpm is not None else (getattr(sim.model, "kpm_path", None) or DEFAULT_KPM)
+    kpm = read_kpm(kpm) if isinstance(kpm, str) else kpm
+    weight, lim = body_weight(kpm), torch.tensor(np.asarray(kpm["torque_lim"], np.float32), device=sim.device)
+    has_geoms = int(sim.model.get_option("n_obj_geoms")) > 0
+    takes, q_rows, o_rows, off = [], [], [], [0]
+    for k, r in results.items():
+        if k not in gt:
+            continue
+        pred, g = np.asarray(r["pred"], np.float64)[:, :76], np.asarray(gt[k]["qpos"], np.float64)[:, :76]
+        n = min(len(pred), len(g))
+        if n < 3:
+            continue
+        obj = np.asarray(r["obj_pose"], np.float64)[:n] if has_geoms and r.get("obj_pose") is not None else None
+        if obj is not None and obj.shape != (n, 35):
+            raise ValueError(f"{k}: obj_pose must hold the 35-float object block of every frame")
+        takes.append((k, n))
+        for side in (pred[:n], g[:n]):
+            q_rows.append(side); o_rows.append(obj); off.append(off[-1] + n)
+    keys = [f"{a}_{b}" for a in DYNAMICS_KEYS for b in ("pred", "gt")]
+    if not takes:
+        return {"per_take": {}, "by_action": {}}
+    if any(o is None for o in o_rows) and not all(o is None for o in o_rows):      # a pickle that mixes takes with and without a block: parked where there is none
+        park = np.zeros(35); park[3::7] = 1.0; park[0::7] = 100.0 * np.arange(1, 6); park[1::7] = 100.0
+        o_rows = [np.tile(park, (len(q), 1)) if o is None else o for q, o in zip(q_rows, o_rows)]
+    Q = torch.from_numpy(np.concatenate(q_rows).astype(np.float32))
+    Ob = None if o_rows[0] is None else torch.from_numpy(np.concatenate(o_rows).astype(np.float32))
+    out = dynamics.inverse_dynamics_sequence(sim, Q, dt, Ob, chunk_rows, take_off=off, want=("qfrc_inverse",))
+    p = dynamics.plausibility(out["qfrc_inverse"], Q.to(sim.device), out["qvel"], lim, weight)
+    frames = {a: p[b].double().cpu().numpy() for a, b in zip(DYNAMICS_KEYS, ("resid_force", "resid_torque", "joint_torque_rms", "over_limit", "power"))}
+    per = {}
+    for i, (k, n) in enumerate(takes):
+        per[k] = {f"{a}_{side}": float(frames[a][off[2 * i + j]:off[2 * i + j + 1]].mean()) for a in DYNAMICS_KEYS for j, side in enumerate(("pred", "gt"))}
+    by_action = {}
+    for k, m in per.items():
+        by_action.setdefault(k.split("-")[0], []).append(m)
+    return {**{kk: float(np.mean([m[kk] for m in per.values()])) for kk in keys},
+            "by_action": {a: {kk: float(np.mean([m[kk] for m in v])) for kk in keys} for a, v in by_action.items()}, "per_take": per}
+
+
+def write_dynamics_metrics(results: dict, gt: dict, sim, result_dir: str, iter_num: int, data_file: str, dt=1.0 / 30.0) -> dict:
+    """coverage_dynamics_metrics as `<result_dir>/dynamics_metrics_<iter>_<data_file>.json`; returns them"""
+    import json
+    import os
+    m = coverage_dynamics_metrics(results, gt, sim, dt)
+    os.makedirs(result_dir, exist_ok=True)
+    with open(os.path.join(result_dir, f"dynamics_metrics_{iter_num}_{data_file}.json"), "w") as f:
+        json.dump(m, f, indent=1)
+    return m
+
+
 def grf_metrics(results: dict, weight: float) -> dict:
     """Ground-reaction summary of an evaluation run with grf=True (kinpoly_amd.evaluate): over all recorded frames of all sequences,
         grf_mean_bw / grf_peak_bw   mean and peak of the feet's total vertical force sum_feet F_z / weight (weight = m g in N, contact.body_weight)

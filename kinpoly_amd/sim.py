@@ -136,6 +136,16 @@ CONTACT_OUTPUTS = {"ncon": ((), torch.int32), "contact": ((64, 12), torch.float3
                    "qacc": ((75,), torch.float32), "torque": ((75,), torch.float32), "obj_qacc": ((2, 6), torch.float32)}
 
 
+class KpInvDynOut(C.Structure):
+    """mirror of kp_invdyn_out: the device arrays kp_sim_inverse_dynamics fills (each may be NULL, not all)"""
+    _fields_ = [(k, C.c_void_p) for k in ("qfrc_inverse", "qfrc_constraint", "qfrc_bias", "contact", "net_wrench", "ncon")]
+
+
+# outputs of KpSim.inverse_dynamics: name -> (trailing shape, dtype), in kp_invdyn_out's order
+INVDYN_OUTPUTS = {"qfrc_inverse": ((75,), torch.float32), "qfrc_constraint": ((75,), torch.float32), "qfrc_bias": ((75,), torch.float32),
+                  "contact": ((64, 12), torch.float32), "net_wrench": ((6,), torch.float32), "ncon": ((), torch.int32)}
+
+
 class KinPolyNativeError(RuntimeError):
     pass
 
@@ -154,6 +164,7 @@ _SIGNATURES = {
     "kp_sim_set_objects": (_I, [_V, _V, _V]), "kp_sim_set_obj_state": (_I, [_V, _V, _V, _V]),
     "kp_sim_apply_impulse": (_I, [_V, _V, _V, _V, _V, _V]),
     "kp_sim_contact_forces": (_I, [_V, _I, _V, _V, _V]),      # handle, actuation, act, env_mask, kp_contact_out*
+    "kp_sim_inverse_dynamics": (_I, [_V, _I, _V, _V, _V, _V, _V]),      # handle, n_rows, qpos, qvel, qacc, obj_qpos, kp_invdyn_out*
     "kp_sim_fk": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]), "kp_sim_fk_backward": (_I, [_V, _I, _V, _V, _V, _V, _V]),
     "kp_sim_pose_contacts": (_I, [_V, _I, _V, _V, _V, _F, _V, _V, _V]),
     # the offscreen renderer (kp_render.hip); kp_model_hull_planes is host only
@@ -234,6 +245,7 @@ class KpModel:
     def __init__(self, kpm_path: str = DEFAULT_KPM, xml: tuple | None = None, **options):
         """kpm_path: a compiled blob; or xml=(xml_path, uhc_yml_path or None): compile the reference's scene on the spot (kp_model_load_xml)."""
         self.L = load_library()
+        self.kpm_path = None if xml is not None else kpm_path      # the blob's tables for host-side consumers (read_kpm)
         if xml is not None:
             self.h = self.L.kp_model_load_xml(xml[0].encode(), None if xml[1] is None else xml[1].encode())
         else:
@@ -478,6 +490,36 @@ class KpSim:
         st = KpContactOut(*[_dev(k, out.get(k), (self.n, *CONTACT_OUTPUTS[k][0]), CONTACT_OUTPUTS[k][1]) for k in CONTACT_OUTPUTS])
         _check(self.L.kp_sim_contact_forces(self.h, mode, act, _mask_ptr(env_mask, self.n), C.byref(st)), "kp_sim_contact_forces")
         return out
+
+    def inverse_dynamics(self, qpos, qvel=None, qacc=None, obj_qpos=None, want=("qfrc_inverse",)) -> dict:
+        """Inverse dynamics of motion rows (kp_sim_inverse_dynamics, mj_inverse's data.qfrc_inverse): qpos [..., 76], qvel / qacc [..., 75] or None
+        (zeros), obj_qpos [..., 35] or None (objects within 50 m are static obstacles), any leading shape, the same on every input.  Nothing the
+        handle stores is read or changed.  want: names of INVDYN_OUTPUTS.  Returns a dict of device tensors with that leading shape: qfrc_inverse,
+        qfrc_constraint, qfrc_bias [..., 75] (qfrc_applied[0:6] ++ ctrl[69] coordinates); contact [..., 64, 12] = A, B (-1), dist, pos[3], normal[3],
+        force[3]; net_wrench [..., 6] = contact force on the humanoid, torque about the world origin; ncon int32 [...]."""
+        want = tuple(want)
+        bad = [k for k in want if k not in INVDYN_OUTPUTS]
+        if bad or not want:
+            raise ValueError(f"inverse_dynamics: want must name some of {tuple(INVDYN_OUTPUTS)}, got {want}")
+        if qpos.dim() < 1 or qpos.shape[-1] != NQ:
+            raise ValueError(f"inverse_dynamics: qpos must be [..., {NQ}], got {tuple(qpos.shape)}")
+        lead = tuple(qpos.shape[:-1])
+        R = int(np.prod(lead, dtype=np.int64))
+
+        def rows(name, t, dim):
+            if t is None:
+                return None, None
+            if tuple(t.shape) != lead + (dim,):
+                raise ValueError(f"inverse_dynamics: {name} must be {lead + (dim,)}, got {tuple(t.shape)}")
+            t = t.reshape(R, dim)
+            return t, _dev("inverse_dynamics: " + name, t, (R, dim))
+
+        ins = [rows(k, t, d) for k, t, d in (("qpos", qpos, NQ), ("qvel", qvel, NV), ("qacc", qacc, NV), ("obj_qpos", obj_qpos, 35))]
+        out = {k: torch.empty((R, *INVDYN_OUTPUTS[k][0]), dtype=INVDYN_OUTPUTS[k][1], device=self.device) for k in want}
+        st = KpInvDynOut(*[_dev(k, out.get(k), (R, *INVDYN_OUTPUTS[k][0]), INVDYN_OUTPUTS[k][1]) for k in INVDYN_OUTPUTS])
+        if R > 0:                # no rows: nothing to launch (and an empty tensor has no address to hand over)
+            _check(self.L.kp_sim_inverse_dynamics(self.h, R, *[p for _, p in ins], C.byref(st)), "kp_sim_inverse_dynamics")
+        return {k: v.view(lead + INVDYN_OUTPUTS[k][0]) for k, v in out.items()}
 
     def fk(self, qpos_rows: torch.Tensor):
         """qpos_fk_batch on [R,76] rows -> dict(qpos, wbpos, wbquat, bquat, body_com) of device tensors."""

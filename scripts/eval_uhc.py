@@ -50,6 +50,9 @@ def build_parser():
                    help="the loader of the take file: amass_single (DatasetAMASSSingle's pickle) or smpl_obj (DatasetSMPLObj's: takes that carry objects)")
     p.add_argument("--grf", action="store_true", help="record ground reaction forces after every env step (grf / cop / foot_contact / load in the "
                    "coverage_full record) and write grf_metrics_<iter>_<data>.json; off: every output file is what it is without the flag")
+    p.add_argument("--dynamics_metrics", action="store_true", help="inverse dynamics of the simulated (pred) and the expert (gt) poses of every take (root "
+                   "residual force / body weight, residual torque, joint torque rms, share over torque_lim, power) printed and written to "
+                   "dynamics_metrics_<iter>_<data>.json; off: every output file is what it is without the flag")
     from kinpoly_amd.push import add_push_arguments
     return add_push_arguments(p)       # --push_impulse LO [HI] and friends: perturbation pushes while the takes play (off by default)
 
@@ -113,6 +116,11 @@ def main(argv=None):
         from kinpoly_amd.contact import body_weight
         m = M.write_grf_metrics(res, body_weight(env), out_dir, args.iter, args.data)       # env.body_mass: the masses of the model the env runs
         print("".join(f"{k}:{v:.3f} \t " for k, v in m.items()))
+    if args.dynamics_metrics:          # a dynamics score of the expert takes themselves (gt) beside the simulated states (pred): floor scene, rows API of the env's handle
+        from kinpoly_amd import metrics as M
+        gt = {k: {"qpos": np.asarray(r["gt"])} for k, r in res.items()}
+        dm = M.write_dynamics_metrics(res, gt, env.sim, out_dir, args.iter, args.data, dt=env.dt)
+        print("".join(f"{k}:{v:.4f} \t " for k, v in dm.items() if k not in ("per_take", "by_action")))
     if sched is not None:              # the coverage pickles keep their keys; the pushes go to a file of their own
         import joblib
         joblib.dump(sched.by_take, os.path.join(out_dir, f"push_log_{args.iter}_{args.data}.pkl"))
