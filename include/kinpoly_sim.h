@@ -579,7 +579,8 @@ double kp_sim_timing_mean_seconds(kp_sim*, int* n_launches);
 
 /* Diagnostic: mean shader-clock cycles per environment the last kp_sim_step_ctrl spent in each phase
  * {stable-PD, kinematics+bias, collision, constraint set-up, smooth solve, contact solve, integrate, total}.
- * Collected only if the environment variable KP_PROFILE=1 was set at kp_sim_create.  Synchronises. */
+ * Collected only if the environment variable KP_PROFILE=1 was set at kp_sim_create.  The profiler is compiled into the one-workgroup-per-env
+ * step kernels only: such a handle runs every control step in that launch form (never the job queue) and says so once on stderr.  Synchronises. */
 int kp_sim_phase_cycles(kp_sim*, double* out8_host);
 /* the same per environment: out_host [N, 8] (the tail of a launch is a few environments, not the mean). */
 int kp_sim_phase_cycles_env(kp_sim*, double* out_host);

@@ -123,6 +123,7 @@ struct kp_sim {
     long launch_index = 0;
     int last_nsub = 15;                               // substeps of the last control step (kp_sim_lean_state)
     unsigned long long* prof = nullptr;
+    bool prof_noted = false;      // launch_step has said that profiling keeps this handle off the job queue
     float* dbg_contacts = nullptr;
     int32_t* uhc_stage = nullptr;                     // [2, N] kp_sim_uhc_assign's take ids and starts on their way to the device
 };
@@ -321,6 +322,7 @@ enum Layout { FULL = 0, OBJECTS = 1, LEAN = 2 };      // EnvLds, EnvLdsObj, EnvL
 // What one launch_step runs, from the handle's options and state alone (no HIP calls, no writes): launch_step launches it, kp_sim_lean_state reports it.
 struct StepPlan {
     bool queue, lpt;      // the job queue (kp_step_queue_kernel on `slots` resident waves) instead of one workgroup per env; k_lpt_order first
+    bool prof_per_env;    // the job queue would run, but the handle is profiled (KP_PROFILE=1) and the phase profiler exists in the one-workgroup-per-env kernels only
     Layout layout;        // the queue's LDS layout (one workgroup per env runs on FULL or OBJECTS)
     int threads, slots, parts, sizes[16], queue_prio, queue_late, ovf_grid;      // ovf_grid: workgroups of kp_step_overflow_kernel
     size_t lds;           // dynamic LDS bytes of the step kernel
@@ -363,7 +365,8 @@ StepPlan plan_step(const kp_sim& s, int nsub, bool capturing) {
     // which ends on a long tail.  The queue pays from the env count on that one-workgroup-per-env launches (full layout) cannot hold resident at once; the lean
     // queue then runs with every env resident up to its own slot count and in rounds beyond it.  Env ids take 24 bits of a queue entry.
     const int resident_full = s.q.wave_slots / 8 * envs_per_cu(lds, 8);
-    p.queue = nsub > 0 && p.parts > 1 && m.threads == 64 && s.n > std::min(p.slots, resident_full) && s.n <= 0xFFFFFF && !s.prof;
+    const bool queue = nsub > 0 && p.parts > 1 && m.threads == 64 && s.n > std::min(p.slots, resident_full) && s.n <= 0xFFFFFF;
+    p.queue = queue && !s.prof; p.prof_per_env = queue && s.prof;
     p.lds = p.queue ? lds_q : lds;
     p.queue_prio = m.queue_prio >= 0 ? m.queue_prio : (lean ? 3 : 0);
     p.queue_late = m.queue_late >= 0 ? m.queue_late : (lean ? 1 : 0);
@@ -376,7 +379,10 @@ StepPlan plan_step(const kp_sim& s, int nsub, bool capturing) {
 // one workgroup of NT threads per env: the control step, or (nsub = 0) the forward pass alone
 template <int NT, bool OBJ>
 void launch_per_env(const kp_sim* s, const kp::StepArgs& A, int nsub, size_t lds) {
-    if (nsub > 0 && s->xc_on) hipLaunchKernelGGL((kp::kp_step_kernel_xc<NT, OBJ>), dim3(s->n), dim3(NT), lds, s->stream, A, s->xc);
+    // a profiled handle (KP_PROFILE=1) runs the instantiations that carry the phase profiler; plan_step keeps it on this launch form
+    if (nsub > 0 && s->prof && s->xc_on) hipLaunchKernelGGL((kp::kp_step_kernel_xc<NT, OBJ, true>), dim3(s->n), dim3(NT), lds, s->stream, A, s->xc);
+    else if (nsub > 0 && s->prof) hipLaunchKernelGGL((kp::kp_step_kernel<NT, OBJ, true>), dim3(s->n), dim3(NT), lds, s->stream, A);
+    else if (nsub > 0 && s->xc_on) hipLaunchKernelGGL((kp::kp_step_kernel_xc<NT, OBJ>), dim3(s->n), dim3(NT), lds, s->stream, A, s->xc);
     else if (nsub > 0) hipLaunchKernelGGL((kp::kp_step_kernel<NT, OBJ>), dim3(s->n), dim3(NT), lds, s->stream, A);
     else hipLaunchKernelGGL((kp::kp_forward_kernel<NT, OBJ>), dim3(s->n), dim3(NT), lds, s->stream, A);
 }
@@ -464,6 +470,11 @@ int launch_step(kp_sim* s, const float* action, int nsub, const uint8_t* mask, b
     if (nsub > 0 && s->ovf.host && !capturing && lean_eligible(*s) && poll_overflow(s)) return -1;
     const StepPlan p = plan_step(*s, nsub, capturing);
     if (nsub > 0) { s->launch_index++; s->last_nsub = nsub; }
+    if (p.prof_per_env && !s->prof_noted) {      // said once per handle: the figures of kp_sim_phase_cycles are those of another launch form than the unprofiled handle's
+        std::fprintf(stderr, "kp_sim: KP_PROFILE=1: the job-queue kernels carry no phase profiler; this handle's control steps run one workgroup per env "
+                             "(kp_step_kernel), whose profiling instantiation fills kp_sim_phase_cycles\n");
+        s->prof_noted = true;
+    }
     kp::StepArgs A = step_args(s, p, nsub, action, mask, base_qpos);
     // longest env first (inside the timed bracket): order the workgroups / the queue's first jobs by the cycles of the previous control step
     if (p.lpt) hipLaunchKernelGGL(kp::k_lpt_order, dim3(1), dim3(1024), 0, s->stream, s->n, s->q.cost, s->q.order);

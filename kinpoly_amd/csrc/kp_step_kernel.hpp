@@ -92,6 +92,16 @@ struct StepArgs {
 };
 
 
+// The argument block as it lies in the kernarg segment, behind a laundered scalar pointer.  Every kernel that runs step_body takes its StepArgs by value as
+// its FIRST parameter, i.e. at offset 0 of the segment.  Read through the by-value parameter, all ~110 dwords of the block are loaded at the kernel's entry (in
+// tuples of up to 16) and then parked in spill lanes for the whole job, to be restored tuple-wise inside the loops that use one field of them; read through
+// this reference, a field is one scalar load from the constant cache at the site that uses it.  Same memory, same values.
+__device__ __forceinline__ const StepArgs& kp_kernarg() {
+    auto p = (const __attribute__((address_space(4))) StepArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(const StepArgs*)p;
+}
+
 template <int NT, class SL>
 __device__ __forceinline__ float block_sum(SL& s, float v, int tid) {
     v = wave_sum(v);
@@ -574,9 +584,13 @@ __device__ __forceinline__ void aba_solve(SL& s, const Params& P, const Lane8& L
                     Krow[0] += pq.x; Krow[1] += pq.y; Krow[2] += pq.z; Krow[3] += q.x; Krow[4] += q.y; Krow[5] += q.z;
                 }
                 }
+                // the column of register k from a laundered copy of r (col[k] = r ^ KX[k], see Lane8): the 40 lane masks of the selects below are invariant over
+                // the level loop and the Newton loop, so the compiler formed them once per solve and kept them in 80 scalar registers -- all spilled, and read
+                // back lane by lane here at every level that carries contacts.  Forty compares cost less than eighty spill reads.
+                const int rl = kp_launder(r);
 #pragma unroll
                 for (int k = 0; k < 8; k++) {
-                    const int c = L.col[k];
+                    const int c = rl ^ (k < 4 ? k : 11 - k);
                     float v = Krow[0];
                     v = c == 1 ? Krow[1] : v; v = c == 2 ? Krow[2] : v; v = c == 3 ? Krow[3] : v; v = c == 4 ? Krow[4] : v; v = c == 5 ? Krow[5] : v;
                     if (rowok && c < 6) IAx[k] += v;
@@ -1942,6 +1956,11 @@ __device__ __forceinline__ int solve_constraints_obj(EnvLdsObj& s, const Params&
 }
 
 // ---------------------------------------------------------------- the kernel
+// the phase profiler's state (step_body<..., PROF = true>): shader-clock cycles per phase of the substep loop, [7] = the whole loop
+struct PhaseClock {
+    unsigned long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t0 = 0, tstart = 0;
+    __device__ __forceinline__ void lap(int i) { const unsigned long long t1 = __builtin_readcyclecounter(); pc[i] += t1 - t0; t0 = t1; }
+};
 // FWD = true compiles the forward-only launch (sim.forward(): derived quantities at a new state, no substeps) as its own
 // small kernel, so that the control-step kernel's launches are the only ones under its name in a profile.
 // Global accesses to state that one job of kp_step_queue_kernel writes and a later job (another wave, maybe another XCD with its own
@@ -1958,10 +1977,16 @@ template <bool Q, typename V> __device__ __forceinline__ void gst(V* p, V v) {
 
 // LEAN: the floor scenes' job-queue layout (EnvLdsLean).  Returns 1 when the lean layout could not hold a substep's contacts: the job has written nothing to HBM at
 // that point and is re-run on the full layout (kp_step_overflow_kernel); 0 otherwise.
-template <int NT, bool OBJ, bool FWD, bool Q = false, bool LEAN = false, bool XC = false>
-__device__ __forceinline__ int step_body(const StepArgs& A, const int env_in, const int part, const XcArgs* X = nullptr) {
+// PROF: the phase profiler (kp_sim_phase_cycles) is a compile-time property.  Its eight counters and three time stamps are live through the whole job; as a
+// run-time flag they cost every step kernel a quarter of its scalar-register spills and the lean queue kernel two vector spills.  The product
+// instantiations carry none of it; the one-workgroup-per-env kernels exist a second time with it, and a profiled handle launches those.
+template <int NT, bool OBJ, bool FWD, bool Q = false, bool LEAN = false, bool XC = false, bool PROF = false>
+__device__ __forceinline__ int step_body(const int env_in, const int part, const XcArgs* X = nullptr) {
     static_assert(!LEAN || (Q && !OBJ && !FWD && NT == 64), "the lean layout serves the floor scenes' job queue only");
-    // this job's share of the control step; A stays the kernel's read-only argument block (a by-value copy that the job modifies is a private copy per job)
+    static_assert(!PROF || (!Q && !FWD), "the phase profiler runs on the one-workgroup-per-env step kernels");
+    // A is the kernel's read-only argument block where it lies in memory (kp_kernarg), taken anew at the top of every pass of the substep loop
+    const StepArgs& A = kp_kernarg();
+    // this job's share of the control step
     const int n_substeps = FWD ? 0 : (part >= 0 ? (int)(((part < 8 ? A.part_sub_lo >> (8 * part) : A.part_sub_hi >> (8 * (part - 8)))) & 255ull) : A.n_substeps);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     using SL = typename std::conditional<OBJ, EnvLdsObj, typename std::conditional<LEAN, EnvLdsLean, EnvLds>::type>::type;
@@ -2052,10 +2077,9 @@ __device__ __forceinline__ int step_body(const StepArgs& A, const int env_in, co
         }
         for (int i = lane; i < 96; i += NT) A.xquat[(size_t)e * 96 + (unsigned)(i)] = s.xquat[i];
     };
-    unsigned long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t0 = 0, t1 = 0;
-    const bool prof = A.prof != nullptr;
-#define KP_T(i) if (prof) { t1 = __builtin_readcyclecounter(); pc[i] += t1 - t0; t0 = t1; }
-    unsigned long long tstart = 0;
+    struct NoClock {};
+    typename std::conditional<PROF, PhaseClock, NoClock>::type pk;
+#define KP_T(i) if constexpr (PROF) pk.lap(i);
     // One loop, one inlined copy of every phase.  Pass -1 is the entry pass: the forward pass on the derived state the job was handed
     // (qpos_d / qvel_d), after which the real state is loaded; passes 0 .. n - 1 are the substeps; in fresh mode (stale_kinematics = 0)
     // pass n is the forward pass on the final state.  Running the entry pass through the SAME code as a substep's forward pass is what
@@ -2068,6 +2092,9 @@ __device__ __forceinline__ int step_body(const StepArgs& A, const int env_in, co
         // per-lane invariants are re-derived from a laundered lane index every pass (see kp_launder): table addresses, the body's tree
         // level and offset, and -- at the top of each solve -- the Lane8 schedule
         const int tid = kp_launder(tid0);
+        const StepArgs& A = kp_kernarg();
+        const DevTables& T = A.T;
+        const Params& P = A.P;
         const int depth = tid < D_NB ? (int)s.bdep[tid] : -1;
         const V3 bpos = tid < D_NB ? ld3(T.body_pos + 3 * tid) : v3(0.f, 0.f, 0.f);
         const bool substep = sub >= 0 && sub < n_substeps;
@@ -2079,8 +2106,7 @@ __device__ __forceinline__ int step_body(const StepArgs& A, const int env_in, co
                 if (lvl >= 3) __builtin_amdgcn_s_setprio(3); else if (lvl == 2) __builtin_amdgcn_s_setprio(2); else if (lvl == 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
             }
         }
-        if (prof && sub == 0) tstart = __builtin_readcyclecounter();
-        if (prof) t0 = __builtin_readcyclecounter();
+        if constexpr (PROF) { if (sub == 0) pk.tstart = __builtin_readcyclecounter(); pk.t0 = __builtin_readcyclecounter(); }
         // stale mode: the controller sees M / bias of the previous forward pass (cinert, cdof, bias still in LDS)
         const bool spd_pass = torque_out && sub == n_substeps;           // the extra pass of a job that is not the control step's last: the successor's first torque
         // (the spd pass computes the torque of the control step's substep sub_base + n_substeps, the successor job's first)
@@ -2216,9 +2242,11 @@ __device__ __forceinline__ int step_body(const StepArgs& A, const int env_in, co
         KP_SYNC();
         KP_T(6)
     }
-    if (prof && tid == 0 && n_substeps > 0) {
-        pc[7] = __builtin_readcyclecounter() - tstart;
-        for (int k = 0; k < 8; k++) A.prof[8 * (size_t)env + k] = pc[k];
+    if constexpr (PROF) {
+        if (tid == 0 && n_substeps > 0) {
+            pk.pc[7] = __builtin_readcyclecounter() - pk.tstart;
+            for (int k = 0; k < 8; k++) A.prof[8 * (size_t)env + k] = pk.pc[k];
+        }
     }
     // ---- store.  The row addresses are re-derived from laundered copies of the env and lane indices: the ones the load section formed at the top of the job
     // would otherwise stay live through the whole job (37 spilled 64-bit addresses per lane in the object queue kernel)
@@ -2324,17 +2352,17 @@ __global__ __launch_bounds__(1024) void k_lpt_order(int n, const unsigned* __res
     for (int i = tid; i < n; i += 1024) order[atomicAdd(&base[255 - (int)((float)cost[i] * sc)], 1u)] = i;
 }
 
-template <int NT, bool OBJ>
+template <int NT, bool OBJ, bool PROF = false>
 __global__ __launch_bounds__(NT, (NT == 64 ? 2 : 1)) void kp_step_kernel(StepArgs A) {
-    step_body<NT, OBJ, false>(A, A.order ? A.order[blockIdx.x] : (int)blockIdx.x, -1);
+    step_body<NT, OBJ, false, false, false, false, PROF>(A.order ? A.order[blockIdx.x] : (int)blockIdx.x, -1);
 }
 // the extended controller (XcArgs), one workgroup per env
-template <int NT, bool OBJ>
+template <int NT, bool OBJ, bool PROF = false>
 __global__ __launch_bounds__(NT, (NT == 64 ? 2 : 1)) void kp_step_kernel_xc(StepArgs A, XcArgs X) {
-    step_body<NT, OBJ, false, false, false, true>(A, A.order ? A.order[blockIdx.x] : (int)blockIdx.x, -1, &X);
+    step_body<NT, OBJ, false, false, false, true, PROF>(A.order ? A.order[blockIdx.x] : (int)blockIdx.x, -1, &X);
 }
 template <int NT, bool OBJ>
-__global__ __launch_bounds__(NT, (NT == 64 ? 2 : 1)) void kp_forward_kernel(StepArgs A) { step_body<NT, OBJ, true>(A, (int)blockIdx.x, -1); }
+__global__ __launch_bounds__(NT, (NT == 64 ? 2 : 1)) void kp_forward_kernel(StepArgs A) { step_body<NT, OBJ, true>((int)blockIdx.x, -1); }
 
 // Same control step, scheduled in finer grains.  4096 envs on 8 x 256 wave slots are two rounds of whole-control-step jobs whose
 // lengths spread 2.9 M .. 5.4 M cycles, so a third of a kp_step_kernel launch is its tail (tools/launch_balance.py).  Here one
@@ -2401,7 +2429,7 @@ __device__ __forceinline__ void step_queue_body(const StepArgs& A, const XcArgs*
         if (A.queue_prio == 2) { if (part == 0) __builtin_amdgcn_s_setprio(2); else if (part + 1 < A.n_parts) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
         for (;;) {
             const unsigned long long tj = __builtin_amdgcn_s_memrealtime();          // 100 MHz ticks: only ratios of job times are used
-            const int overflow = step_body<64, OBJ, false, true, LEAN, XC>(A, env, part, X);
+            const int overflow = step_body<64, OBJ, false, true, LEAN, XC>(env, part, X);
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // every lane's write-through state store has been acknowledged ...
             if (A.queue_fence) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");      // memory-model variant: release all of this wave's stores at agent scope
             if (LEAN && overflow) {
@@ -2461,7 +2489,7 @@ __global__ __launch_bounds__(64, 2) void kp_step_overflow_kernel(StepArgs A) {
         const unsigned e = (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&A.ovfq[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
         const int env = (int)(e & 0xFFFFFFu);
         for (int part = (int)(e >> 24); part < A.n_parts; part++) {
-            step_body<64, false, false, true, false>(A, env, part);
+            step_body<64, false, false, true, false>(env, part);
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             if (A.queue_fence) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); }
         }

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Resource table of the kernels in a built libkinpoly_sim.so, read from the code objects' metadata (no GPU needed): VGPRs, AGPRs, SGPRs, scratch bytes per
-lane, static LDS bytes and code bytes per kernel.  Two builds of the same sources give identical tables; `--diff other.so` compares them row by row.
+lane, static LDS bytes, code bytes and the registers the allocator spilled (sgpr_spill: scalar registers parked in lanes of a VGPR, vgpr_spill: vector registers
+parked in scratch) per kernel.  Two builds of the same sources give identical tables; `--diff other.so` compares them row by row.
 
     python tools/kernel_resources.py [lib.so] [--match kp_step_] [--diff other.so]
 """
@@ -16,7 +17,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COLS = ("vgpr", "agpr", "sgpr", "scratch_bytes", "lds_bytes", "code_bytes")
+COLS = ("vgpr", "agpr", "sgpr", "sgpr_spill", "vgpr_spill", "scratch_bytes", "lds_bytes", "code_bytes")
 
 
 def _llvm(tool: str) -> str:
@@ -67,6 +68,7 @@ def table(lib: str) -> dict:
                 filt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")      # readable names where a demangler exists; the mangled one otherwise
                 name = subprocess.check_output([filt, sym], text=True).strip() if filt else sym
                 rows[name] = dict(vgpr=int(g("vgpr_count").group(1)), agpr=int(g("agpr_count").group(1)), sgpr=int(g("sgpr_count").group(1)),
+                                  sgpr_spill=int(g("sgpr_spill_count").group(1)), vgpr_spill=int(g("vgpr_spill_count").group(1)),
                                   scratch_bytes=int(g("private_segment_fixed_size").group(1)), lds_bytes=int(g("group_segment_fixed_size").group(1)),
                                   code_bytes=sizes.get(sym, -1))
     return rows
@@ -77,6 +79,18 @@ def render(rows: dict) -> str:
     for k in sorted(rows):
         out.append(f"| `{k}` | " + " | ".join(str(rows[k][c]) for c in COLS) + " |")
     return "\n".join(out)
+
+
+def parse(md: str) -> dict:
+    """a table render() wrote (e.g. a committed profiles/*/kernels_*.md) back as kernel name -> dict of its columns"""
+    rows, cols = {}, None
+    for ln in md.splitlines():
+        f = [c.strip() for c in ln.strip().strip("|").split("|")]
+        if ln.startswith("| kernel |"):
+            cols = f[1:]
+        elif cols and ln.startswith("| `"):
+            rows[f[0].strip("`")] = dict(zip(cols, map(int, f[1:])))
+    return rows
 
 
 def main():
