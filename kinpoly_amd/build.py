@@ -11,7 +11,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(_HERE, "libkinpoly_sim.so")
-SOURCES = ["kp_sim.hip", "kp_pose_contacts.hip", "kp_render.hip", "kp_render_ego.hip", "kp_takes.hip", "kp_kin_tape.hip", "kp_obs_ctx.hip"]
+SOURCES = ["kp_sim.hip", "kp_pose_contacts.hip", "kp_render.hip", "kp_render_ego.hip", "kp_takes.hip", "kp_kin_tape.hip", "kp_obs_ctx.hip", "kp_readout.hip"]
 STAMP = LIB + ".flags"          # the flag list the library was built with (a change of flags rebuilds, like a change of a source)
 
 

@@ -6,25 +6,15 @@
 // step and kept only qpos / qvel.  Nothing of the control step changes: the kernel is composed from the step kernel's device functions the way
 // kp_push.hpp is, reads the stored rows (and the warm start, read only) and stores into its own output rows alone.
 // Always the full layouts (EnvLds / EnvLdsObj, 64 contact slots): no lean layout, so no overflow path.
-// Included by kp_sim.hip behind kp_step_kernel.hpp (that header defines non-template kernels: one translation unit only).
+// Compiled in the read-out unit (kp_readout.hip), which the step kernels' unit cannot see.
 #pragma once
-#include "kp_step_kernel.hpp"
+#include "kp_readout.hpp"
+#include "kp_readout_device.hpp"
 
 namespace kp {
 
 constexpr int D_CF_ENTITIES = D_NB + D_MAXOBJ;      // 0..23 humanoid bodies, 24 + k object slot k (the numbering of kp_sim_contacts)
 constexpr int D_CF_ROW = 12;                        // floats of a contact row: A, B, dist, pos[3], normal[3], force[3]
-
-// every pointer optional (kp_contact_out of the C ABI)
-struct ContactOut {
-    int32_t* ncon;             // [N]
-    float *contact;            // [N, 64, 12]
-    float *wrench;             // [N, 26, 6] force, torque about the WORLD ORIGIN (world axes)
-    float *qfrc_constraint;    // [N, 75]
-    float *qacc;               // [N, 75]
-    float *torque;             // [N, 75] qfrc_applied[0:6] ++ ctrl[69] as the solve used them
-    float *obj_qacc;           // [N, 2, 6] object slots, joint coordinates
-};
 
 // con_force (kp_step_kernel.hpp) for both layouts: the world force of contact c at the residuals in jar3, acting on the entity that carries
 // the vertex (A).  Row forces fe = -D jar where jar < 0, frame components (sum fe, mu (fe0 - fe1), mu (fe2 - fe3)).
@@ -73,20 +63,15 @@ __global__ __launch_bounds__(64) void k_contact_forces(StepArgs A, XcArgs X, int
     for (int i = tid; i < D_NQ; i += NT) s.qpos[i] = (stale_ctrl ? A.qpos_d : A.qpos)[e * D_NQ + i];
     for (int i = tid; i < D_NV; i += NT) {
         s.qvel[i] = (stale_ctrl ? A.qvel_d : A.qvel)[e * D_NV + i];
-        s.arm[i] = T.dof_armature[i]; s.extra[i] = 0.f; s.dbody[i] = T.dof_body[i];
         s.qacc[i] = A.warm[e * D_NV + i];                // the warm start, read only; no extrapolation (beta = 0): the minimiser does not depend on the start
     }
-    if (tid < D_NB) { s.bpar[tid] = (unsigned char)(T.body_parent[tid] < 0 ? 0 : T.body_parent[tid]); s.bsub[tid] = T.body_subtree[tid]; s.bdep[tid] = T.body_depth[tid]; }
-    for (int i = tid; i < 78; i += NT) s.applied[i] = 0.f;             // applied[6] ++ ctrl[72]
-    if (tid < 25) s.IAa[22 * tid + 21] = 0.f;
-    if (tid < 22) s.IAa[22 * 24 + tid] = 0.f;
-    if (tid < 6) s.pAa[6 * 24 + tid] = 0.f;
-    if (tid == 0) { s.ncon = 0; s.nlim = 0; s.flag = 0; }
+    readout_prologue(s, T, tid);
+    readout_aba_zeros(s, tid);
     if constexpr (OBJ) {
         for (int i = tid; i < D_MAXGEOM * 17; i += NT) s.geom[i] = A.geoms[e * D_MAXGEOM * 17 + i];
+        if (tid < D_MAXGEOM) s.gobj[tid] = -1;
         const int ngs = A.ngeom[env];
         int nobj = 0, ng = ngs;
-        if (tid < D_MAXGEOM) s.gobj[tid] = -1;
         for (int k = 0; k < D_MAXOBJ; k++) {
             const int oi = A.obj_slot ? A.obj_slot[e * D_MAXOBJ + k] : -1;
             if (oi < 0 || oi >= T.n_obj) break;
@@ -140,26 +125,7 @@ __global__ __launch_bounds__(64) void k_contact_forces(StepArgs A, XcArgs X, int
     if (rows) {
         if (tid < ncon) st3(fc + 3 * tid, contact_force<OBJ>(s, P, tid));
         KP_SYNC();
-        // qfrc_constraint = J^T f as a PROJECTION of the forces (never M qacc - qfrc_smooth): the hulls' contact wrenches about o, their subtree sums, the
-        // dot product with every dof's motion axis; the limit rows add sgn (-D jar) on their own dof (lim_D is the signed weight) -> s.x.
-        // (wrench_project does the same with the opposite sign; its instantiations belong to the step kernels, whose code must not depend on this header)
-        if (tid < D_NB) {
-            const V3 o = ld3(s.xpos);
-            S6 W = S6{v3(0.f, 0.f, 0.f), v3(0.f, 0.f, 0.f)};
-            for (int c = s.con_start[tid]; c < s.con_start[tid + 1]; c++) {
-                const V3 F = ld3(fc + 3 * c), p = ld3(s.con_pos + 3 * c) - o;
-                W.a = W.a + cross(p, F); W.l = W.l + F;
-            }
-            sts6(s.sw + 6 * tid, W);
-        }
-        KP_SYNC();
-        subtree_sums<NT>(s, tid);
-        for (int d = tid; d < D_NV; d += NT) {
-            float v = dot6(lds6(s.cdof + 6 * d), lds6(s.sa + 6 * s.dbody[d]));
-            if (d >= 6) { const float jr = s.lim_jar[d - 6]; if (jr < 0.f) v -= s.lim_D[d - 6] * jr; }
-            s.x[d] = v;
-        }
-        KP_SYNC();
+        project_contact_forces(s, fc, s.x, tid);                        // qfrc_constraint
     }
     if (O.ncon && tid == 0) O.ncon[e] = ncon;
     if (O.contact) {

@@ -10,41 +10,13 @@
 // its own output rows alone.  Always the full layouts (EnvLds / EnvLdsObj, 64 contact slots): no lean layout, so no overflow path.
 // Objects are static obstacles at the row's pose (nobj = 0: no obj_forward, no Schur part); their world geoms come from a per-call scratch buffer that
 // the placement kernel of kp_sim_set_objects filled.  A row without a placed geom runs the floor code, so a parked block and no block agree bit for bit.
-// The projections are written out here (nothing in this header may change how the step kernels' shared functions are specialised).
-// Included by kp_sim.hip behind kp_step_kernel.hpp (that header defines non-template kernels: one translation unit only).
+// Compiled in the read-out unit (kp_readout.hip), which the step kernels' unit cannot see; the force projections are kp_readout_device.hpp's.  The load
+// section is the kernel's own, like step_body's: it is readout_prologue's stores fused into the row loads, and calling the helper instead (two loops over
+// the dofs where this is one) costs k_inverse_dynamics<true> 5 to 9 scalar-register spills and 1 % of its time.
 #pragma once
 #include "kp_contact_force.hpp"
 
 namespace kp {
-
-// every pointer optional (kp_invdyn_out of the C ABI)
-struct InvDynOut {
-    float *qfrc_inverse;       // [R, 75] qfrc_applied[0:6] ++ ctrl[69] coordinates
-    float *qfrc_constraint;    // [R, 75] J^T f + the limit rows at the given qacc
-    float *qfrc_bias;          // [R, 75] C(q, qd) + g
-    float *contact;            // [R, 64, 12] the rows of kp_sim_contact_forces
-    float *net_wrench;         // [R, 6] sum of the contact forces, their torque about the WORLD ORIGIN (world axes)
-    int32_t* ncon;             // [R]
-};
-
-struct InvDynArgs {
-    DevTables T;
-    Params P;
-    int n_rows, row0;          // this launch covers rows row0 .. n_rows - 1 (blockIdx.x + row0)
-    const float *qpos, *qvel, *qacc;     // [R, 76], [R, 75] or null (zero), [R, 75] or null (zero)
-    const float* geoms;        // OBJ: [R, D_MAXGEOM, 17] world-frame static geoms of the rows
-    const int* ngeom;          // OBJ: [R]
-    InvDynOut O;
-};
-
-// out[d] = cdof_d . (sum of the body wrenches s.sw over the subtree of d's body): the backward half of mj_rne on whatever wrenches the caller stored
-template <class SL>
-__device__ __forceinline__ void invdyn_project(SL& s, float* out, int tid) {
-    KP_SYNC();
-    subtree_sums<64>(s, tid);
-    for (int d = tid; d < D_NV; d += 64) out[d] = dot6(lds6(s.cdof + 6 * d), lds6(s.sa + 6 * s.dbody[d]));
-    KP_SYNC();
-}
 
 // one row on one wavefront; s: the row's LDS block with qpos, qvel, qacc and the per-lane tables loaded (OBJ: the static geoms too)
 template <bool OBJ, class SL>
@@ -67,12 +39,12 @@ __device__ __forceinline__ void invdyn_row(SL& s, const InvDynArgs& A, size_t r,
 
     // ---- M qacc + qfrc_bias -> s.qacc_s: body wrenches I_b a_b + fb_b, subtree sums, projection, armature
     if (tid < D_NB) sts6(s.sw + 6 * tid, inert_mul(s.cinert + 10 * tid, lds6(sacc + 6 * tid)) + lds6(s.fb + 6 * tid));
-    invdyn_project(s, s.qacc_s, tid);
+    project_body_wrenches(s, s.qacc_s, tid);
     for (int d = tid; d < D_NV; d += 64) s.qacc_s[d] += s.arm[d] * s.qacc[d];
     // ---- qfrc_bias alone -> s.search (only when asked for: no other output depends on it)
     if (O.qfrc_bias) {
         if (tid < D_NB) sts6(s.sw + 6 * tid, lds6(s.fb + 6 * tid));
-        invdyn_project(s, s.search, tid);
+        project_body_wrenches(s, s.search, tid);
     }
     // ---- J^T f -> s.x, as k_contact_forces forms it: the contacts' world forces, hull wrenches about o, subtree sums, projection, the limit rows
     float* fc = s.jv3;                                                  // [ncon][3] world force on A (aref is folded into jar3 by now)
@@ -80,17 +52,7 @@ __device__ __forceinline__ void invdyn_row(SL& s, const InvDynArgs& A, size_t r,
         KP_SYNC();
         if (tid < ncon) st3(fc + 3 * tid, contact_force<OBJ>(s, P, tid));
         KP_SYNC();
-        if (tid < D_NB) {
-            const V3 o = ld3(s.xpos);
-            S6 W = S6{v3(0.f, 0.f, 0.f), v3(0.f, 0.f, 0.f)};
-            for (int c = s.con_start[tid]; c < s.con_start[tid + 1]; c++) {
-                const V3 F = ld3(fc + 3 * c), p = ld3(s.con_pos + 3 * c) - o;
-                W.a = W.a + cross(p, F); W.l = W.l + F;
-            }
-            sts6(s.sw + 6 * tid, W);
-        }
-        invdyn_project(s, s.x, tid);
-        for (int d = 6 + tid; d < D_NV; d += 64) { const float jr = s.lim_jar[d - 6]; if (jr < 0.f) s.x[d] -= s.lim_D[d - 6] * jr; }
+        project_contact_forces(s, fc, s.x, tid);
     }
     KP_SYNC();
 
@@ -103,12 +65,14 @@ __device__ __forceinline__ void invdyn_row(SL& s, const InvDynArgs& A, size_t r,
     }
     if (O.ncon && tid == 0) O.ncon[r] = ncon;
     if (O.contact) {
+        // k_contact_forces' row store with B = -1 (the floor or a static geom, always).  Written out in both kernels: as one function of the LDS block it
+        // costs the object kernels 5 % code and 1.5 % time (profiles/readout_split/tool_benches.md)
         float* row = O.contact + (r * D_MAXCON + tid) * D_CF_ROW;
         if (tid < ncon) {
             V3 n = v3(0.f, 0.f, 1.f);
             if constexpr (OBJ) n = ld3(s.con_n + 3 * tid);
             const V3 f = ld3(fc + 3 * tid);
-            row[0] = (float)s.con_body[tid]; row[1] = -1.f; row[2] = my_dist;       // B: the floor or a static geom
+            row[0] = (float)s.con_body[tid]; row[1] = -1.f; row[2] = my_dist;
             st3(row + 3, ld3(s.con_pos + 3 * tid)); st3(row + 6, n); st3(row + 9, f);
         } else {
 #pragma unroll

@@ -6,9 +6,9 @@
 // Nothing of the control step changes: the kernel reads and writes the stored rows (KP_QPOS, KP_QVEL, KP_OBJ_QPOS, KP_OBJ_QVEL) and
 // is built from the step kernel's device functions -- forward_kin_bias for the kinematics at the CURRENT qpos (not the stale
 // qpos_d the read-outs belong to) and the matrix-free aba_solve with the model's armature and no contact rows for M^-1.
-// Included by kp_sim.hip behind kp_step_kernel.hpp (that header defines non-template kernels: one translation unit only).
+// Compiled in the read-out unit (kp_readout.hip), which the step kernels' unit cannot see.
 #pragma once
-#include "kp_step_kernel.hpp"
+#include "kp_readout_device.hpp"
 
 namespace kp {
 
@@ -139,11 +139,9 @@ __global__ __launch_bounds__(64) void k_apply_impulse(StepArgs A, const int32_t*
     const int depth = tid < D_NB ? T.body_depth[tid] : -1;
     const V3 bpos = tid < D_NB ? ld3(T.body_pos + 3 * tid) : v3(0.f, 0.f, 0.f);
     for (int i = tid; i < D_NQ; i += NT) s.qpos[i] = A.qpos[(size_t)env * D_NQ + i];
-    for (int i = tid; i < D_NV; i += NT) { s.qvel[i] = A.qvel[(size_t)env * D_NV + i]; s.arm[i] = T.dof_armature[i]; s.extra[i] = 0.f; s.dbody[i] = T.dof_body[i]; }
-    if (tid < D_NB) { s.bpar[tid] = (unsigned char)(T.body_parent[tid] < 0 ? 0 : T.body_parent[tid]); s.bsub[tid] = T.body_subtree[tid]; s.bdep[tid] = T.body_depth[tid]; }
-    if (tid < 25) s.IAa[22 * tid + 21] = 0.f;          // the zero words / zero record the articulated-body passes read for padded and absent operands
-    if (tid < 22) s.IAa[22 * 24 + tid] = 0.f;
-    if (tid < 6) s.pAa[6 * 24 + tid] = 0.f;
+    for (int i = tid; i < D_NV; i += NT) s.qvel[i] = A.qvel[(size_t)env * D_NV + i];
+    readout_prologue(s, T, tid);
+    readout_aba_zeros(s, tid);
     KP_SYNC();
     forward_kin_bias<NT>(s, T, P, depth, bpos, tid);
     // g = J_b(r)^T [p; l]: the impulse as a wrench about o (the root body origin, where every spatial quantity of the env is expressed),

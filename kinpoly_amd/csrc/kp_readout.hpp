@@ -1,0 +1,51 @@
+// kp_readout.hpp -- the kernels beside the control step that are built from its device functions (kp_step_device.hpp): impulse pushes (kp_push.hpp,
+// DESIGN.md section 12), the contact-force read-out (kp_contact_force.hpp, section 14) and inverse dynamics on motion rows (kp_inverse_dyn.hpp,
+// section 15).  They live in their own translation unit (kp_readout.hip): however they specialise the shared device functions, the step kernels' unit
+// does not see it, so the step kernels' code cannot move with them.  kp_sim.hip keeps the entry points' argument checks and calls the launchers below.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "kp_step_device.hpp"
+
+namespace kp {
+
+// every pointer optional (kp_contact_out of the C ABI)
+struct ContactOut {
+    int32_t* ncon;             // [N]
+    float *contact;            // [N, 64, 12]
+    float *wrench;             // [N, 26, 6] force, torque about the WORLD ORIGIN (world axes)
+    float *qfrc_constraint;    // [N, 75]
+    float *qacc;               // [N, 75]
+    float *torque;             // [N, 75] qfrc_applied[0:6] ++ ctrl[69] as the solve used them
+    float *obj_qacc;           // [N, 2, 6] object slots, joint coordinates
+};
+
+// every pointer optional (kp_invdyn_out of the C ABI)
+struct InvDynOut {
+    float *qfrc_inverse;       // [R, 75] qfrc_applied[0:6] ++ ctrl[69] coordinates
+    float *qfrc_constraint;    // [R, 75] J^T f + the limit rows at the given qacc
+    float *qfrc_bias;          // [R, 75] C(q, qd) + g
+    float *contact;            // [R, 64, 12] the rows of kp_sim_contact_forces
+    float *net_wrench;         // [R, 6] sum of the contact forces, their torque about the WORLD ORIGIN (world axes)
+    int32_t* ncon;             // [R]
+};
+
+struct InvDynArgs {
+    DevTables T;
+    Params P;
+    int n_rows, row0;          // a launch covers rows row0 .. n_rows - 1 (blockIdx.x + row0); row0 is the launcher's
+    const float *qpos, *qvel, *qacc;     // [R, 76], [R, 75] or null (zero), [R, 75] or null (zero)
+    const float* geoms;        // OBJ: [R, D_MAXGEOM, 17] world-frame static geoms of the rows
+    const int* ngeom;          // OBJ: [R]
+    InvDynOut O;
+};
+
+// Each enqueues on `stream` and returns; the caller reads the launch status (hipGetLastError).  One wavefront per env / row, full LDS layouts.
+// A: the step kernels' argument pack (state rows, object rows); one block per env
+void launch_apply_impulse(const StepArgs& A, const int32_t* entity, const float* offset, const float* impulse, const uint8_t* mask, float* dqvel, hipStream_t stream);
+// obj: the handle simulates objects (EnvLdsObj); xc: the extended controller (X); one block per env
+void launch_contact_forces(const StepArgs& A, const XcArgs& X, bool obj, bool xc, int actuation, const float* act, const uint8_t* mask, const ContactOut& O, hipStream_t stream);
+// obj: the rows carry static geoms (A.geoms / A.ngeom); launches of at most 2^24 rows each
+void launch_inverse_dynamics(InvDynArgs A, bool obj, hipStream_t stream);
+
+}  // namespace kp

@@ -20,9 +20,7 @@
 #include "kp_rollout_kernels.hpp"
 #include "kp_policy_kernels.hpp"
 #include "kp_step_kernel.hpp"
-#include "kp_push.hpp"
-#include "kp_contact_force.hpp"
-#include "kp_inverse_dyn.hpp"
+#include "kp_readout.hpp"
 #include "kp_pose_contacts.hpp"
 #include "kp_render.hpp"
 #include "kp_render_ego.hpp"
@@ -1567,7 +1565,7 @@ int kp_sim_apply_impulse(kp_sim* s, const int32_t* entity, const float* offset, 
     // the object slots mean something once kp_sim_set_objects / kp_sim_reset_rows have installed a block (zero-filled before that)
     const ObjectRows& o = s->obj;
     if (o.on && s->T.obj_inertial) { A.obj_slot = o.slot; A.obj_qpos = o.qpos; A.obj_qvel = o.qvel; }
-    hipLaunchKernelGGL(kp::k_apply_impulse, dim3(s->n), dim3(64), sizeof(kp::EnvLds), s->stream, A, entity, offset, impulse, mask, dqvel);
+    kp::launch_apply_impulse(A, entity, offset, impulse, mask, dqvel, s->stream);
     return launched();
 }
 
@@ -1828,14 +1826,7 @@ int kp_sim_contact_forces(kp_sim* s, int actuation, const float* act, const uint
     kp::StepArgs A = step_args(s, p, 0, nullptr, mask, nullptr);
     A.warm_extrap = 0.f; A.prof = nullptr; A.dbg_contacts = nullptr; A.order = nullptr;
     const kp::ContactOut O{out->ncon, out->contact, out->wrench, out->qfrc_constraint, out->qacc, out->torque, out->obj_qacc};
-    const dim3 grid(s->n), block(64);
-    if (s->obj.on) {
-        if (s->xc_on) hipLaunchKernelGGL((kp::k_contact_forces<true, true>), grid, block, sizeof(kp::EnvLdsObj), s->stream, A, s->xc, actuation, act, mask, O);
-        else hipLaunchKernelGGL((kp::k_contact_forces<true, false>), grid, block, sizeof(kp::EnvLdsObj), s->stream, A, s->xc, actuation, act, mask, O);
-    } else {
-        if (s->xc_on) hipLaunchKernelGGL((kp::k_contact_forces<false, true>), grid, block, sizeof(kp::EnvLds), s->stream, A, s->xc, actuation, act, mask, O);
-        else hipLaunchKernelGGL((kp::k_contact_forces<false, false>), grid, block, sizeof(kp::EnvLds), s->stream, A, s->xc, actuation, act, mask, O);
-    }
+    kp::launch_contact_forces(A, s->xc, s->obj.on, s->xc_on, actuation, act, mask, O, s->stream);
     return launched();
 }
 
@@ -1874,14 +1865,7 @@ int kp_sim_inverse_dynamics(kp_sim* s, int n_rows, const float* qpos, const floa
         HIP_OK(hipGetLastError());
         A.geoms = geoms; A.ngeom = ngeom;
     }
-    // one wavefront per row; a launch holds at most 2^24 rows (grid x block stays below 2^32 threads)
-    constexpr int CHUNK = 1 << 24;
-    for (int r0 = 0; r0 < n_rows; r0 += CHUNK) {
-        A.row0 = r0;
-        const dim3 grid(std::min(CHUNK, n_rows - r0)), block(64);
-        if (obj_qpos) hipLaunchKernelGGL((kp::k_inverse_dynamics<true>), grid, block, sizeof(kp::EnvLdsObj), s->stream, A);
-        else hipLaunchKernelGGL((kp::k_inverse_dynamics<false>), grid, block, sizeof(kp::EnvLds), s->stream, A);
-    }
+    kp::launch_inverse_dynamics(A, obj_qpos != nullptr, s->stream);
     return launched();
 }
 

@@ -26,7 +26,8 @@
 // when there are more envs than wavefront slots; bit-identical results; the finishing job hands its successor the next stable-PD torque, and a wave
 // keeps an env it finds heavy or that started late).  The functions are templates over the LDS layout (kp_device.hpp): floor scenes' queue launches run on
 // EnvLdsLean (12 envs per CU) and hand a job with more contacts than it holds to kp_step_overflow_kernel (full layout); same arithmetic, same bits.
-#pragma once
+#ifndef KP_STEP_DEVICE_PART      // two include guards, one per half: kp_step_device.hpp and this header may be included in either order
+#define KP_STEP_DEVICE_PART
 #include <type_traits>
 
 #include "kp_device.hpp"
@@ -1955,7 +1956,16 @@ __device__ __forceinline__ int solve_constraints_obj(EnvLdsObj& s, const Params&
     return it;
 }
 
+}  // namespace kp
+#endif  // KP_STEP_DEVICE_PART
+
 // ---------------------------------------------------------------- the kernel
+// Everything above defines no __global__ function and may be included from any translation unit: kp_step_device.hpp does so for the read-out unit
+// (kp_readout.hip), with everything below cut off.  Below: step_body and the kernels, non-template ones among them -- kp_sim.hip only.
+#if !defined(KP_STEP_DEVICE_ONLY) && !defined(KP_STEP_KERNEL_PART)
+#define KP_STEP_KERNEL_PART
+namespace kp {
+
 // the phase profiler's state (step_body<..., PROF = true>): shader-clock cycles per phase of the substep loop, [7] = the whole loop
 struct PhaseClock {
     unsigned long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t0 = 0, tstart = 0;
@@ -2505,3 +2515,4 @@ __global__ void k_queue_init(int n_envs, unsigned total, unsigned* __restrict__ 
 }
 
 }  // namespace kp
+#endif  // KP_STEP_KERNEL_PART
