@@ -511,6 +511,29 @@ int kp_sim_contact_forces(kp_sim*, int actuation, const float* act, const uint8_
 typedef struct { float *qfrc_inverse, *qfrc_constraint, *qfrc_bias, *contact, *net_wrench; int32_t* ncon; } kp_invdyn_out;
 int kp_sim_inverse_dynamics(kp_sim*, int n_rows, const float* qpos, const float* qvel, const float* qacc, const float* obj_qpos, const kp_invdyn_out* out);
 
+/* Body velocities and accelerations, momentum and energy on motion ROWS.  Replaces what a mujoco-py user reads from data.body_xvelr / body_xvelp,
+ * mj_objectAcceleration, the root's data.subtree_com / subtree_linvel / subtree_angmom and mj_energyPos / mj_energyVel (data.energy).  The reference
+ * never reads them (deviation 40).  The forward pass of the control step (kinematics, spatial velocities, velocity-product
+ * accelerations, inertias, bias wrenches) on the given rows and a read-out of what it leaves behind: no collision pass, no constraint, no solve; a
+ * smooth function of its inputs.  A rows API like kp_sim_fk: n_rows is independent of the handle's envs; the kernel reads the model tables (masses,
+ * inertias, armature, gravity) and the row inputs, none of the handle's stored state, and stores into the output rows alone.  The root quaternion is
+ * normalised first, as everywhere.  One launch for all rows (one wavefront per row); a row's result does not depend on the other rows.
+ *   qpos      [R,76] device, required.
+ *   qvel      [R,75] or NULL: zero velocities.
+ *   qacc      [R,75] or NULL: zero accelerations.
+ *   out       device arrays, each may be NULL but not all; world axes throughout:
+ *     body_vel     float [R,24,6]  angular velocity[3] (body_xvelr), linear velocity[3] of the body frame origin xpos (body_xvelp)
+ *     body_acc     float [R,24,6]  angular acceleration[3], classical (coordinate) linear acceleration[3] of the body frame origin: the second time
+ *                                  derivative of xpos, gravity not included (mj_objectAcceleration reports it with +(-g); subtract g to compare)
+ *     body_com_vel float [R,24,3]  linear velocity of each body's centre of mass xipos
+ *     centroid     float [R,18]    com[3], com_vel[3], L_com[3] (angular momentum about the centre of mass), ke (1/2 qvel^T M qvel, armature
+ *                                  included: mj_energyVel), pe (-m g . com: mj_energyPos), com_acc[3], Ldot_com[3] (rate of L_com), mass.
+ *                                  With qacc = NULL, com_acc and Ldot_com are the acceleration-free part (what the velocity products give at qacc = 0).
+ * Enqueued on the handle's stream, does not synchronise.  n_rows == 0 does nothing.  Refused (-1, kp_last_error names the argument) before anything is
+ * launched: null handle, n_rows < 0, null qpos, null out, all outputs null, a handle whose threads_per_env is not 64. */
+typedef struct { float *body_vel, *body_acc, *body_com_vel, *centroid; } kp_motion_out;
+int kp_sim_body_motion(kp_sim*, int n_rows, const float* qpos, const float* qvel, const float* qacc, const kp_motion_out* out);
+
 /* read-outs of the mujoco-py data fields the env uses (humanoid_im.py:342-416, humanoid_ar_v1.py:460-512) */
 typedef enum {
     KP_QPOS = 0,        /* data.qpos[:76]                    [N,76]  */

@@ -5,6 +5,7 @@
 #include "kp_push.hpp"
 #include "kp_contact_force.hpp"
 #include "kp_inverse_dyn.hpp"
+#include "kp_body_motion.hpp"
 
 namespace kp {
 
@@ -31,6 +32,14 @@ void launch_inverse_dynamics(InvDynArgs A, bool obj, hipStream_t stream) {
         const dim3 grid(std::min(CHUNK, A.n_rows - r0)), block(64);
         if (obj) hipLaunchKernelGGL((k_inverse_dynamics<true>), grid, block, sizeof(EnvLdsObj), stream, A);
         else hipLaunchKernelGGL((k_inverse_dynamics<false>), grid, block, sizeof(EnvLds), stream, A);
+    }
+}
+
+void launch_body_motion(BodyMotionArgs A, hipStream_t stream) {
+    constexpr int CHUNK = 1 << 24;                                      // as launch_inverse_dynamics
+    for (int r0 = 0; r0 < A.n_rows; r0 += CHUNK) {
+        A.row0 = r0;
+        hipLaunchKernelGGL(k_body_motion, dim3(std::min(CHUNK, A.n_rows - r0)), dim3(64), sizeof(BodyMotionLds), stream, A);
     }
 }
 

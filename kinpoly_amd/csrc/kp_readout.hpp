@@ -1,6 +1,6 @@
 // kp_readout.hpp -- the kernels beside the control step that are built from its device functions (kp_step_device.hpp): impulse pushes (kp_push.hpp,
-// DESIGN.md section 12), the contact-force read-out (kp_contact_force.hpp, section 14) and inverse dynamics on motion rows (kp_inverse_dyn.hpp,
-// section 15).  They live in their own translation unit (kp_readout.hip): however they specialise the shared device functions, the step kernels' unit
+// DESIGN.md section 12), the contact-force read-out (kp_contact_force.hpp, section 14) inverse dynamics on motion rows (kp_inverse_dyn.hpp,
+// section 15) and body motion, momentum and energy on motion rows (kp_body_motion.hpp, section 16).  They live in their own translation unit (kp_readout.hip): however they specialise the shared device functions, the step kernels' unit
 // does not see it, so the step kernels' code cannot move with them.  kp_sim.hip keeps the entry points' argument checks and calls the launchers below.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -40,6 +40,22 @@ struct InvDynArgs {
     InvDynOut O;
 };
 
+// every pointer optional (kp_motion_out of the C ABI)
+struct BodyMotionOut {
+    float *body_vel;           // [R, 24, 6] world angular velocity, world linear velocity of the body frame origin
+    float *body_acc;           // [R, 24, 6] world angular acceleration, classical linear acceleration of the body frame origin
+    float *body_com_vel;       // [R, 24, 3] linear velocity of the body's centre of mass
+    float *centroid;           // [R, 18] com, com_vel, L_com, ke, pe, com_acc, Ldot_com, mass
+};
+
+struct BodyMotionArgs {
+    DevTables T;
+    Params P;
+    int n_rows, row0;          // as InvDynArgs
+    const float *qpos, *qvel, *qacc;     // [R, 76], [R, 75] or null (zero), [R, 75] or null (zero)
+    BodyMotionOut O;
+};
+
 // Each enqueues on `stream` and returns; the caller reads the launch status (hipGetLastError).  One wavefront per env / row, full LDS layouts.
 // A: the step kernels' argument pack (state rows, object rows); one block per env
 void launch_apply_impulse(const StepArgs& A, const int32_t* entity, const float* offset, const float* impulse, const uint8_t* mask, float* dqvel, hipStream_t stream);
@@ -47,5 +63,7 @@ void launch_apply_impulse(const StepArgs& A, const int32_t* entity, const float*
 void launch_contact_forces(const StepArgs& A, const XcArgs& X, bool obj, bool xc, int actuation, const float* act, const uint8_t* mask, const ContactOut& O, hipStream_t stream);
 // obj: the rows carry static geoms (A.geoms / A.ngeom); launches of at most 2^24 rows each
 void launch_inverse_dynamics(InvDynArgs A, bool obj, hipStream_t stream);
+// body motion, momentum and energy of rows (kp_body_motion.hpp, section 16): its own small LDS layout; launches of at most 2^24 rows each
+void launch_body_motion(BodyMotionArgs A, hipStream_t stream);
 
 }  // namespace kp

@@ -1869,6 +1869,23 @@ int kp_sim_inverse_dynamics(kp_sim* s, int n_rows, const float* qpos, const floa
     return launched();
 }
 
+int kp_sim_body_motion(kp_sim* s, int n_rows, const float* qpos, const float* qvel, const float* qacc, const kp_motion_out* out) {
+    if (!s) return fail("kp_sim_body_motion: null handle");
+    if (n_rows < 0) return fail("kp_sim_body_motion: n_rows < 0");
+    if (!qpos) return fail("kp_sim_body_motion: null qpos");
+    if (!out) return fail("kp_sim_body_motion: null out");
+    if (!out->body_vel && !out->body_acc && !out->body_com_vel && !out->centroid) return fail("kp_sim_body_motion: every output of out is null");
+    if (s->model->threads != 64) return fail("kp_sim_body_motion: needs a handle with threads_per_env = 64");
+    if (n_rows == 0) return 0;
+    HIP_OK(hipSetDevice(s->device));
+    kp::BodyMotionArgs A{};
+    A.T = s->T; A.P = s->P; A.n_rows = n_rows;
+    A.qpos = qpos; A.qvel = qvel; A.qacc = qacc;
+    A.O = kp::BodyMotionOut{out->body_vel, out->body_acc, out->body_com_vel, out->centroid};
+    kp::launch_body_motion(A, s->stream);
+    return launched();
+}
+
 }  // extern "C"
 
 // ---- model compiler behind the ABI (host only).  Included last: its `#pragma clang fp contract(off)` (bit-reproducible double arithmetic,

@@ -88,3 +88,20 @@ def plausibility(qfrc_inverse: torch.Tensor, qpos: torch.Tensor, qvel: torch.Ten
            "over_limit": (tau.abs() > lim).to(tau.dtype).mean(-1), "power": (tau * qvel[..., 6:]).abs().sum(-1)}
     out["mean"] = {k: v.mean() for k, v in out.items()}
     return out
+
+
+def body_imu(motion: dict, xquat: torch.Tensor, body: int, offset=None, g=(0.0, 0.0, -9.81)):
+    """Gyro and accelerometer of a point fixed on a body, in the body's own frame: what an IMU mounted there reads.  motion: KpSim.body_motion's dict
+    with body_vel and body_acc [..., 24, 6]; xquat [..., 24, 4] or [..., 96]: the bodies' world orientations (fk()'s wbquat, the stored field xquat);
+    offset [3]: the point in the body's frame (None: the frame origin); g: the gravity vector.  With R the body's rotation, r = R offset:
+        gyro = R^T w,     accel = R^T (a + alpha x r + w x (w x r) - g)            (proper acceleration: +9.81 up at rest)
+    Returns (gyro [..., 3], accel [..., 3])."""
+    vel, acc = motion["body_vel"][..., body, :], motion["body_acc"][..., body, :]
+    q = xquat.reshape(*xquat.shape[:-2], 24, 4)[..., body, :] if xquat.shape[-1] == 4 else xquat.reshape(*xquat.shape[:-1], 24, 4)[..., body, :]
+    w, al, a = vel[..., :3], acc[..., :3], acc[..., 3:]
+    gv = torch.as_tensor(g, dtype=a.dtype, device=a.device)
+    if offset is not None:
+        r = _quat_rotate(q, torch.as_tensor(offset, dtype=a.dtype, device=a.device).expand_as(a))
+        a = a + torch.cross(al, r, dim=-1) + torch.cross(w, torch.cross(w, r, dim=-1), dim=-1)
+    conj = q * torch.tensor([1.0, -1.0, -1.0, -1.0], dtype=q.dtype, device=q.device)
+    return _quat_rotate(conj, w), _quat_rotate(conj, a - gv)

@@ -469,6 +469,16 @@ class BatchedHumanoidAREnv:
                 raise RuntimeError("contact_forces(): no cc_action yet -- call step() first, or pass cc_action")
         return self.sim.contact_forces(action=cc_action.to(self.device, torch.float32).contiguous(), **kw)
 
+    def body_motion(self, qacc=None, outputs=("body_vel", "body_com_vel", "centroid")) -> dict:
+        """KpSim.body_motion on the STORED qpos / qvel of every env (zero-copy views: no host round trip): body velocities, momentum and energy of the
+        current state as device tensors [N, ...].  qacc [N, 75] or None: the accelerations body_acc, com_acc and Ldot_com are formed with."""
+        return self.sim.body_motion(self.sim.view("qpos"), self.sim.view("qvel"), qacc, outputs=outputs)
+
+    def centroidal(self, qacc=None) -> dict:
+        """balance.centroidal of the stored state: com, com_vel, L_com, ke, pe, com_acc, Ldot_com, mass per env (device tensors)"""
+        from . import balance
+        return balance.centroidal(self.sim, self.sim.view("qpos"), self.sim.view("qvel"), qacc)
+
     # getters (device tensors; reference names)
     def get_humanoid_qpos(self):
         return self.sim.get("qpos")

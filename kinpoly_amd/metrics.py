@@ -291,6 +291,64 @@ def write_dynamics_metrics(results: dict, gt: dict, sim, result_dir: str, iter_n
     return m
 
 
+BALANCE_KEYS = ("com_margin", "xcom_margin", "zmp_margin", "stable_frac", "airborne_frac", "zmp_out_mean")
+
+
+def coverage_balance_metrics(results: dict, gt: dict, sim, dt=1.0 / 30.0) -> dict:
+    """Balance score of pose sequences that were never simulated: balance.balance_sequence (one KpSim.body_motion and one
+    KpSim.inverse_dynamics call over all rows; dynamics.motion_derivatives inside the takes) of the predicted (`pred`, its first 76 columns) and the
+    ground-truth trajectory of every take of a `*_coverage_full.pkl` dict, on the FLOOR scene (the support polygon is the hull of the floor contacts; a
+    seat carries nothing here).  Takes are cut to n = min(len(pred), len(gt qpos)), n >= 3.  Per side (pred / gt) and take: the means over the frames
+    with floor contact of com_margin_*, xcom_margin_*, zmp_margin_* (m, positive inside the polygon), and stable_frac_*, airborne_frac_*,
+    zmp_out_mean_* (balance.balance).  Returns their means over the takes (NaN-aware), 'by_action' (the same per action prefix) and 'per_take'."""
+    from . import balance
+    takes, q_rows, off = [], [], [0]
+    for k, r in results.items():
+        if k not in gt:
+            continue
+        pred, g = np.asarray(r["pred"], np.float64)[:, :76], np.asarray(gt[k]["qpos"], np.float64)[:, :76]
+        n = min(len(pred), len(g))
+        if n < 3:
+            continue
+        takes.append((k, n))
+        for side in (pred[:n], g[:n]):
+            q_rows.append(side); off.append(off[-1] + n)
+    keys = [f"{a}_{b}" for a in BALANCE_KEYS for b in ("pred", "gt")]
+    if not takes:
+        return {"per_take": {}, "by_action": {}}
+    fr = balance.balance_sequence(sim, np.concatenate(q_rows).astype(np.float32), dt, take_off=off)
+
+    def nanmean(x):
+        x = np.asarray(x, np.float64)
+        x = x[np.isfinite(x)]
+        return float(x.mean()) if len(x) else float("nan")
+
+    per = {}
+    for i, (k, n) in enumerate(takes):
+        m = {}
+        for j, side in enumerate(("pred", "gt")):
+            rows = slice(off[2 * i + j], off[2 * i + j + 1])
+            m.update({f"{a}_{side}": nanmean(fr[a][rows]) for a in BALANCE_KEYS[:3]})
+            m.update({f"{a}_{side}": v for a, v in balance.summary(fr, rows).items()})
+        per[k] = m
+    by_action = {}
+    for k, m in per.items():
+        by_action.setdefault(k.split("-")[0], []).append(m)
+    return {**{kk: nanmean([m[kk] for m in per.values()]) for kk in keys},
+            "by_action": {a: {kk: nanmean([m[kk] for m in v]) for kk in keys} for a, v in by_action.items()}, "per_take": per}
+
+
+def write_balance_metrics(results: dict, gt: dict, sim, result_dir: str, iter_num: int, data_file: str, dt=1.0 / 30.0) -> dict:
+    """coverage_balance_metrics as `<result_dir>/balance_metrics_<iter>_<data_file>.json`; returns them"""
+    import json
+    import os
+    m = coverage_balance_metrics(results, gt, sim, dt)
+    os.makedirs(result_dir, exist_ok=True)
+    with open(os.path.join(result_dir, f"balance_metrics_{iter_num}_{data_file}.json"), "w") as f:
+        json.dump(m, f, indent=1)
+    return m
+
+
 def grf_metrics(results: dict, weight: float) -> dict:
     """Ground-reaction summary of an evaluation run with grf=True (kinpoly_amd.evaluate): over all recorded frames of all sequences,
         grf_mean_bw / grf_peak_bw   mean and peak of the feet's total vertical force sum_feet F_z / weight (weight = m g in N, contact.body_weight)

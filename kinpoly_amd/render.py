@@ -166,6 +166,16 @@ class HeadCamera:
         q = torch.stack([hq[:, 0] * pw - hq[:, 1] * px, hq[:, 0] * px + hq[:, 1] * pw, hq[:, 2] * pw + hq[:, 3] * px, hq[:, 3] * pw - hq[:, 2] * px], 1)
         return torch.cat([eye, q, torch.full_like(hp[:, :1], float(self.fovy))], 1).contiguous()
 
+    def imu(self, sim, qpos, dt: float, take_off=None):
+        """(gyro [T, 3], accel [T, 3]) of an IMU at the camera's eye, in the HEAD's frame, for the frames ego_sequence renders of qpos [T, 76]:
+        dynamics.motion_derivatives' qvel / qacc, one KpSim.body_motion call, dynamics.body_imu on the head body (device tensors)"""
+        import torch
+        from . import dynamics
+        q = torch.as_tensor(np.asarray(qpos, np.float32)[:, :76]).to(sim.device).contiguous()
+        qvel, qacc = dynamics.motion_derivatives(q, dt, take_off)
+        motion = sim.body_motion(q, qvel.contiguous(), qacc.contiguous(), outputs=("body_vel", "body_acc"))
+        return dynamics.body_imu(motion, sim.fk(q)["wbquat"], HEAD_BODY, self.eye_offset())
+
     def basis(self, head_pos, head_quat):
         """(eye, forward, right, up) in fp64: forward = R e_z, up = R e_y, right = -R e_x of the camera's quaternion"""
         r = self.row(head_pos, head_quat)

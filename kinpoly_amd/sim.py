@@ -146,6 +146,19 @@ INVDYN_OUTPUTS = {"qfrc_inverse": ((75,), torch.float32), "qfrc_constraint": ((7
                   "contact": ((64, 12), torch.float32), "net_wrench": ((6,), torch.float32), "ncon": ((), torch.int32)}
 
 
+class KpMotionOut(C.Structure):
+    """mirror of kp_motion_out: the device arrays kp_sim_body_motion fills (each may be NULL, not all)"""
+    _fields_ = [(k, C.c_void_p) for k in ("body_vel", "body_acc", "body_com_vel", "centroid")]
+
+
+# outputs of KpSim.body_motion: name -> (trailing shape, dtype), in kp_motion_out's order
+MOTION_OUTPUTS = {"body_vel": ((24, 6), torch.float32), "body_acc": ((24, 6), torch.float32), "body_com_vel": ((24, 3), torch.float32),
+                  "centroid": ((18,), torch.float32)}
+# the fields of a centroid row: name -> slice
+CENTROID_FIELDS = {"com": slice(0, 3), "com_vel": slice(3, 6), "L_com": slice(6, 9), "ke": 9, "pe": 10, "com_acc": slice(11, 14), "Ldot_com": slice(14, 17),
+                   "mass": 17}
+
+
 class KinPolyNativeError(RuntimeError):
     pass
 
@@ -165,6 +178,7 @@ _SIGNATURES = {
     "kp_sim_apply_impulse": (_I, [_V, _V, _V, _V, _V, _V]),
     "kp_sim_contact_forces": (_I, [_V, _I, _V, _V, _V]),      # handle, actuation, act, env_mask, kp_contact_out*
     "kp_sim_inverse_dynamics": (_I, [_V, _I, _V, _V, _V, _V, _V]),      # handle, n_rows, qpos, qvel, qacc, obj_qpos, kp_invdyn_out*
+    "kp_sim_body_motion": (_I, [_V, _I, _V, _V, _V, _V]),      # handle, n_rows, qpos, qvel, qacc, kp_motion_out*
     "kp_sim_fk": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]), "kp_sim_fk_backward": (_I, [_V, _I, _V, _V, _V, _V, _V]),
     "kp_sim_pose_contacts": (_I, [_V, _I, _V, _V, _V, _F, _V, _V, _V]),
     # the offscreen renderer (kp_render.hip); kp_model_hull_planes is host only
@@ -520,6 +534,32 @@ class KpSim:
         if R > 0:                # no rows: nothing to launch (and an empty tensor has no address to hand over)
             _check(self.L.kp_sim_inverse_dynamics(self.h, R, *[p for _, p in ins], C.byref(st)), "kp_sim_inverse_dynamics")
         return {k: v.view(lead + INVDYN_OUTPUTS[k][0]) for k, v in out.items()}
+
+    def body_motion(self, qpos, qvel=None, qacc=None, outputs=tuple(MOTION_OUTPUTS)) -> dict:
+        """Body velocities and accelerations, momentum and energy of motion rows (kp_sim_body_motion): qpos [..., 76], qvel / qacc [..., 75] or None
+        (zeros), any leading shape, the same on every input.  Nothing the handle stores is read or changed.  outputs: names of MOTION_OUTPUTS.  Returns
+        a dict of device tensors with that leading shape, world axes: body_vel [..., 24, 6] = angular, linear velocity of the body frame origin;
+        body_acc [..., 24, 6] = angular, classical linear acceleration of it; body_com_vel [..., 24, 3]; centroid [..., 18] (CENTROID_FIELDS: com,
+        com_vel, L_com, ke, pe, com_acc, Ldot_com, mass)."""
+        want = tuple(outputs)
+        bad = [k for k in want if k not in MOTION_OUTPUTS]
+        if bad or not want:
+            raise ValueError(f"body_motion: outputs must name some of {tuple(MOTION_OUTPUTS)}, got {want}")
+        if qpos.dim() < 1 or qpos.shape[-1] != NQ:
+            raise ValueError(f"body_motion: qpos must be [..., {NQ}], got {tuple(qpos.shape)}")
+        lead = tuple(qpos.shape[:-1])
+        R = int(np.prod(lead, dtype=np.int64))
+        ins = []
+        for name, t, dim in (("qpos", qpos, NQ), ("qvel", qvel, NV), ("qacc", qacc, NV)):
+            if t is not None and tuple(t.shape) != lead + (dim,):
+                raise ValueError(f"body_motion: {name} must be {lead + (dim,)}, got {tuple(t.shape)}")
+            ins.append(None if t is None else t.reshape(R, dim))
+        out = {k: torch.empty((R, *MOTION_OUTPUTS[k][0]), dtype=MOTION_OUTPUTS[k][1], device=self.device) for k in want}
+        if R > 0:                # no rows: nothing to launch (and an empty tensor has no address to hand over)
+            st = KpMotionOut(*[_dev(k, out.get(k), (R, *MOTION_OUTPUTS[k][0])) for k in MOTION_OUTPUTS])
+            ptrs = [_dev("body_motion: " + k, t, (R, d)) for k, t, d in zip(("qpos", "qvel", "qacc"), ins, (NQ, NV, NV))]
+            _check(self.L.kp_sim_body_motion(self.h, R, *ptrs, C.byref(st)), "kp_sim_body_motion")
+        return {k: v.view(lead + MOTION_OUTPUTS[k][0]) for k, v in out.items()}
 
     def fk(self, qpos_rows: torch.Tensor):
         """qpos_fk_batch on [R,76] rows -> dict(qpos, wbpos, wbquat, bquat, body_com) of device tensors."""

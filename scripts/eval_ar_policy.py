@@ -44,6 +44,9 @@ def build_parser():
     ap.add_argument("--dynamics_metrics", action="store_true", help="with --data: inverse dynamics of the predicted and the ground-truth poses (root residual "
                     "force / body weight, residual torque, joint torque rms, share over torque_lim, power; pred and gt) printed and written to "
                     "dynamics_metrics_<iter>_<data>.json; off: every output is what it is without the flag")
+    ap.add_argument("--balance_metrics", action="store_true", help="with --data: balance of the predicted and the ground-truth poses (margins of the centre of "
+                    "mass, the capture point and the zero-moment point to the support polygon, stable / airborne share; pred and gt) printed and written to "
+                    "balance_metrics_<iter>_<data>.json; off: every output is what it is without the flag")
     ap.add_argument("--cfg", type=str, default=None)
     ap.add_argument("--config_root", type=str, default=None)
     from kinpoly_amd.dataset import add_of_source_argument
@@ -147,7 +150,7 @@ def main():
             report_pushes(sched, res, args.result_dir, args.iter, data_file)
         pct = np.array([r["percent"] for r in res.values()])
         print(f"Coverage of {cov} out of {len(res)} | mean percent {pct.mean():.3f} | fail-safe used in {sum(r['fail_safe'] for r in res.values())}")
-        if args.metrics or args.physics_metrics or args.dynamics_metrics:    # the paper metrics of scripts/eval_pose_all.py --mode stats (kinpoly_amd/metrics.py)
+        if args.metrics or args.physics_metrics or args.dynamics_metrics or args.balance_metrics:    # the paper metrics of scripts/eval_pose_all.py --mode stats (kinpoly_amd/metrics.py)
             from kinpoly_amd import metrics as M
             gt = {k: {"qpos": ds.data["qpos"][i].double().numpy(), "head_pose": ds.data["head_pose"][i].double().numpy()} for i, k in enumerate(ds.takes)}
         if args.metrics:                            # the kinematic ones
@@ -164,6 +167,9 @@ def main():
         if args.dynamics_metrics:                   # inverse dynamics of poses that were never simulated (kinematic target and ground truth), on the run's scene
             dm = M.write_dynamics_metrics(res, gt, kpsim.KpSim(env.model, 1, 0), args.result_dir, args.iter, data_file)
             print("".join(f"{k}:{v:.4f} \t " for k, v in dm.items() if k not in ("per_take", "by_action")))
+        if args.balance_metrics:                    # balance of the same poses, floor scene
+            bm = M.write_balance_metrics(res, gt, kpsim.KpSim(env.model, 1, 0), args.result_dir, args.iter, data_file)
+            print("".join(f"{k}:{v:.4f} \t " for k, v in bm.items() if k not in ("per_take", "by_action")))
         return
     g = torch.Generator().manual_seed(0)
     ctx = standing_context(n, T, std["qpos"], std["qvel"], env.sim, (torch.rand(n, generator=g) * 2 - 1) * np.pi)

@@ -53,6 +53,9 @@ def build_parser():
     p.add_argument("--dynamics_metrics", action="store_true", help="inverse dynamics of the simulated (pred) and the expert (gt) poses of every take (root "
                    "residual force / body weight, residual torque, joint torque rms, share over torque_lim, power) printed and written to "
                    "dynamics_metrics_<iter>_<data>.json; off: every output file is what it is without the flag")
+    p.add_argument("--balance_metrics", action="store_true", help="balance of the simulated (pred) and the expert (gt) poses of every take (margins of the "
+                   "centre of mass, the capture point and the zero-moment point to the support polygon, stable / airborne share) printed and written to "
+                   "balance_metrics_<iter>_<data>.json; off: every output file is what it is without the flag")
     from kinpoly_amd.push import add_push_arguments
     return add_push_arguments(p)       # --push_impulse LO [HI] and friends: perturbation pushes while the takes play (off by default)
 
@@ -121,6 +124,11 @@ def main(argv=None):
         gt = {k: {"qpos": np.asarray(r["gt"])} for k, r in res.items()}
         dm = M.write_dynamics_metrics(res, gt, env.sim, out_dir, args.iter, args.data, dt=env.dt)
         print("".join(f"{k}:{v:.4f} \t " for k, v in dm.items() if k not in ("per_take", "by_action")))
+    if args.balance_metrics:           # the same for balance: floor scene, rows API of the env's handle
+        from kinpoly_amd import metrics as M
+        gt = {k: {"qpos": np.asarray(r["gt"])} for k, r in res.items()}
+        bm = M.write_balance_metrics(res, gt, env.sim, out_dir, args.iter, args.data, dt=env.dt)
+        print("".join(f"{k}:{v:.4f} \t " for k, v in bm.items() if k not in ("per_take", "by_action")))
     if sched is not None:              # the coverage pickles keep their keys; the pushes go to a file of their own
         import joblib
         joblib.dump(sched.by_take, os.path.join(out_dir, f"push_log_{args.iter}_{args.data}.pkl"))
