@@ -16,7 +16,7 @@ namespace kp {
 constexpr int D_CF_ENTITIES = D_NB + D_MAXOBJ;      // 0..23 humanoid bodies, 24 + k object slot k (the numbering of kp_sim_contacts)
 constexpr int D_CF_ROW = 12;                        // floats of a contact row: A, B, dist, pos[3], normal[3], force[3]
 
-// con_force (kp_step_kernel.hpp) for both layouts: the world force of contact c at the residuals in jar3, acting on the entity that carries
+// con_force (kp_step_obj.hpp) for both layouts: the world force of contact c at the residuals in jar3, acting on the entity that carries
 // the vertex (A).  Row forces fe = -D jar where jar < 0, frame components (sum fe, mu (fe0 - fe1), mu (fe2 - fe3)).
 template <bool OBJ, class SL>
 __device__ __forceinline__ V3 contact_force(const SL& s, const Params& P, int c) {

@@ -1,5 +1,5 @@
 // kp_pose_contacts.hip -- k_pose_contacts, the batched pose-contact query declared in kp_pose_contacts.hpp (see there).
-// Narrow phases: kp_collide.hpp; the culls and the floor rule are those of collide<> (kp_step_kernel.hpp).
+// Narrow phases: kp_collide.hpp; the culls and the floor rule are those of collide<> (kp_step_collide.hpp).
 #include "kp_pose_contacts.hpp"
 #include "kp_collide.hpp"
 
@@ -11,7 +11,7 @@ struct __attribute__((aligned(16))) PoseLds {
     float hrec[16];                   // hull record of the support functor (hull_support_store)
 };
 
-// Twin of the floor branch of collide<> (kp_step_kernel.hpp), kept as a separate copy so that the step kernels' code is untouched: mjc_PlaneConvex
+// Twin of the floor branch of collide<> (kp_step_collide.hpp), kept as a separate copy so that the step kernels' code is untouched: mjc_PlaneConvex
 // on hull b, whose world vertices xw sit on the lanes below the hull's vertex count (z = 3e38 on the others).  The deepest vertex (first on ties)
 // makes the first contact; then its hull-graph neighbours in graph order, up to maxplanemesh contacts in all, each within the margin and not
 // closer than tolplanemesh * rbound to the first contact's position.  Adds the contacts to ncon and their penetration to pen (wave-uniform).

@@ -2,7 +2,7 @@
 // the walk of data.contact) on arbitrary poses, batched over frames and with no dynamics.
 //
 // One wavefront per row; a row is one frame: the 24 body poses (xpos / xquat, kp_sim_fk's wbpos / wbquat) and the frame's 35-float object
-// block.  The pairs and narrow phases are those of collide<> (kp_step_kernel.hpp): hull - floor (mjc_PlaneConvex) and hull - object geom
+// block.  The pairs and narrow phases are those of collide<> (kp_step_collide.hpp): hull - floor (mjc_PlaneConvex) and hull - object geom
 // (mjc_Convex, MPR in fp64, kp_collide.hpp), behind the same exact-safe culls.  What the metrics read is accumulated in registers instead of
 // stored: the number of hull - (floor | object) contacts, the sum of their penetrations beyond pen_margin, and per object geom the set of
 // hulls it touches.  No contact record is kept, so a row may hold any number of contacts (a lying pose sunk into the floor has 72).

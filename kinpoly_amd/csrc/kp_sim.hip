@@ -199,7 +199,7 @@ bool build_tables(kp_sim* s) {
     lev_start[D_NLEV + 1] = (int)lev_body.size();
     if ((int)lev_body.size() != NB || lev_start[D_NLEV] != NB) return false;  // tree deeper than D_NLEV levels
     T.lev_start = upload<uint8_t>(s, lev_start, &ok); T.lev_body = upload<uint8_t>(s, lev_body, &ok);
-    // static schedule of the 8-lanes-per-body tree passes (Lane8, kp_step_kernel.hpp): lane = 8 * slot + row, 28 words per lane, built
+    // static schedule of the 8-lanes-per-body tree passes (Lane8, kp_step_aba.hpp): lane = 8 * slot + row, 28 words per lane, built
     // here once so that the kernels load it instead of deriving it (they re-read it at the top of every solve to keep it out of the
     // registers in between)
     std::vector<unsigned> tab(64 * 28, 0u);

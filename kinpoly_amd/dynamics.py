@@ -3,7 +3,7 @@ root residual wrench, and the plausibility scores built on them.  Torch only; ev
 
 Coordinates.  qfrc_inverse [., 75] is a generalized force in the model's dof coordinates: entries 0..2 pair with the root's linear velocity (world
 axes), entries 3..5 with its angular velocity, which the free joint expresses in the ROOT's own axes (the motion axes of dofs 3..5 are the columns of
-the root's rotation matrix, taken about the root position; forward_kin_bias in kp_step_kernel.hpp), entries 6..74 are the 69 hinge torques in ctrl order.
+the root's rotation matrix, taken about the root position; forward_kin_bias in kp_step_kin.hpp), entries 6..74 are the 69 hinge torques in ctrl order.
 """
 from __future__ import annotations
 

@@ -10,7 +10,7 @@ NB, NV, NU, MAXOBJ = 24, 75, 69, 2
 
 
 def make_frame(n):
-    """mju_makeFrame of a unit normal: rows n, t1, t2 (the rule of contact_frame in kp_step_kernel.hpp)"""
+    """mju_makeFrame of a unit normal: rows n, t1, t2 (the rule of contact_frame in kp_step_args.hpp)"""
     n = np.asarray(n, float)
     y = np.array([0.0, 1.0, 0.0]) if abs(n[1]) < 0.5 else np.array([0.0, 0.0, 1.0])
     y = y - n.dot(y) * n

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 dst = os.path.join(ROOT, "gpurun_out", os.environ.get("KP_ROUND", "r05") + "_prof", "summary")
 os.makedirs(dst, exist_ok=True)
 KERNEL = "kp_step_queue_kernel"
-N_SIMD, CLOCK_GHZ = 1024, 2.35          # 256 CUs x 4 SIMDs; shader clock under this kernel (tools/micro/queue_timeline.py)
+N_SIMD, CLOCK_GHZ = 1024, 2.35          # 256 CUs x 4 SIMDs; shader clock under this kernel (profiles/r03/queue_timeline.log)
 
 
 def counters(tag):

@@ -1,19 +1,13 @@
-"""Where the object kernel's cycles go.  (1) KP_PROFILE substep phases of the shipped library on the object scenes of tools/obj_bench.py and on
-bench.py's `objects` workload, with the per-env cost of the last launch grouped by action class; (2) with KP_OBJ_NEWTON=1 the sub-phases of
-solve_constraints_obj from the instrumented build (tools/micro/obj_instr.py)."""
+"""Where the object kernel's cycles go.  KP_PROFILE substep phases of the shipped library on the object scenes of tools/obj_bench.py and on
+bench.py's `objects` workload, with the per-env cost of the last launch grouped by action class."""
 import os, sys
 os.environ["KP_PROFILE"] = "1"
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import numpy as np
 import torch
-from kinpoly_amd import sim as _sim
-newton = os.environ.get("KP_OBJ_NEWTON") == "1"
-if newton:
-    _sim.load_library(os.path.join(ROOT, "tools", "micro", "bin", "libkinpoly_sim_objnewton.so"))
 import bench
-names = ("init+cand", "gradient", "Hhh_factor", "schur_cols", "dense+backsub", "rows+ls", "update+cost", "total") if newton else \
-        ("stable-PD", "kinematics", "collision", "constraints", "smooth", "newton", "integrate", "total")
+names = ("stable-PD", "kinematics", "collision", "constraints", "smooth", "newton", "integrate", "total")
 rec, env, policy, sampler, std = bench.run_workload("objects", 0, 4, 64, 8, 4)
 pc = env.sim.phase_cycles()
 d = np.asarray(rec["diag"])

@@ -5,9 +5,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 import numpy as np
 import torch
-from kinpoly_amd import sim as _sim
-if os.environ.get("KP_OBJ_NEWTON") == "1":
-    _sim.load_library(os.path.join(ROOT, "tools", "micro", "bin", "libkinpoly_sim_objnewton.so"))
 import bench
 steps = int(os.environ.get("STEPS", "40"))
 rec, env, policy, sampler, std = bench.run_workload("objects", 0, 4, 64, steps, 10)
@@ -21,8 +18,7 @@ qp = env.sim.get("qpos").cpu().numpy()
 order = np.argsort(-cost)
 if os.environ.get("KP_PROFILE") == "1":
     pe = env.sim.phase_cycles_env() / 15.0
-    newton = os.environ.get("KP_OBJ_NEWTON") == "1"
-    names8 = ("init+cand", "gradient", "Hhh_factor", "schur_cols", "dense+backsub", "rows+ls", "update+cost", "total") if newton else ("stable-PD", "kinematics", "collision", "constraints", "smooth", "newton", "integrate", "total")
+    names8 = ("stable-PD", "kinematics", "collision", "constraints", "smooth", "newton", "integrate", "total")
     top = order[:40]
     print("cycles per substep, mean over the 40 costliest envs:", {n_: int(v) for n_, v in zip(names8, pe[top].mean(0))})
     print("cycles per substep, median env:", {n_: int(v) for n_, v in zip(names8, np.median(pe, 0))})
