@@ -534,6 +534,41 @@ int kp_sim_inverse_dynamics(kp_sim*, int n_rows, const float* qpos, const float*
 typedef struct { float *body_vel, *body_acc, *body_com_vel, *centroid; } kp_motion_out;
 int kp_sim_body_motion(kp_sim*, int n_rows, const float* qpos, const float* qvel, const float* qacc, const kp_motion_out* out);
 
+/* Point Jacobians on motion ROWS.  Stands in for mj_jac (mj_jacBody with offset NULL): per row the Jacobian of one point of one body.  The reference
+ * never calls it (deviation 41).  The forward pass' motion axes read out, no solve.  A rows API like kp_sim_body_motion: any n_rows,
+ * the kernel reads the model tables and the row inputs, none of the handle's stored state, and stores into J alone.
+ *   qpos    [R,76] device, required (root quaternion normalised first).
+ *   body    int32 [R] device, required: 0..23; any other value gives a zero row.
+ *   offset  [R,3] or NULL: the point in the body's frame (NULL: the body origin xpos).
+ *   J       float [R,6,75]: rows 0..2 the world velocity of the point r = xpos_b + R_b offset, rows 3..5 the body's world angular velocity, per unit
+ *           dof velocity.  Columns in qvel order: root translation (world axes), root rotation (about the root's own axes), the 69 hinges.
+ * Enqueued on the handle's stream, does not synchronise.  n_rows == 0 does nothing.  Refused (-1, kp_last_error names the argument) before anything is
+ * launched: null handle, n_rows < 0, null qpos / body / J, a handle whose threads_per_env is not 64. */
+int kp_sim_point_jacobian(kp_sim*, int n_rows, const float* qpos, const int32_t* body, const float* offset, float* J);
+
+/* Pose fitting on ROWS: from body poses to qpos.  No reference counterpart (the reference converts SMPL axis-angles offline, uhc/data_process); it
+ * is the IK loop a mujoco-py user would write on mj_jacBody (deviation 41).  Per row, n_iters Levenberg-Marquardt iterations on
+ *     c(q) = 1/2 sum_b w_pos_b |x*_b - x_b|^2 + 1/2 sum_b w_rot_b |log(R*_b R_b^T)|^2 + 1/2 sum_d w_prior_d (q*_d - q_d)^2
+ * over the 24 body origins.  One iteration: residuals e at q; g = J^T W e (+ the prior's share); dq = (J^T W J + diag(mu damp + w_prior))^-1 g by the
+ * control step's matrix-free articulated-body pass (the normal matrix is the joint-space inertia of the tree with point masses w_pos and spherical
+ * inertias w_rot); trial q' = q (+) dq as mj_integratePos with dt = 1 (hinges clamped to jnt_range with clamp_limits); accepted
+ * iff c(q') is finite and < c(q): mu <- max(mu mu_down, mu_min), else q stays and mu <- min(mu mu_up, mu_max).
+ *   in   qpos0 [R,76] and tgt_pos [R,24,3] required; tgt_quat [R,24,4] or NULL (no orientation term; normalised, either sign); w_pos [R,24] or NULL
+ *        (ones); w_rot [R,24] or NULL (zeros); q_prior / w_prior [R,69], both or neither.  Weights below zero count as zero.
+ *   cfg  kp_fit_cfg_default: n_iters 30, mu0 1e-2, mu_min 1e-7, mu_max 1e6, mu_up 8, mu_down 0.3, damp 1 on every dof, clamp_limits 0.
+ *   out  qpos [R,76] (root quaternion normalised) and info [R,8] required: first cost, final cost, accepted steps, final mu, max |e_pos| (m) and
+ *        max |e_rot| (rad) over the bodies with a positive weight, |dq|_inf of the last solve, status (0 ok; 1: a non-finite input or first cost, the
+ *        row ran no iteration and qpos is the input as given).  dq [R,75] or NULL: the last solve's step.
+ * n_iters == 0 returns the input with its quaternion normalised and both costs filled.  A row's result depends on that row alone.  Enqueued on the
+ * handle's stream, does not synchronise; nothing the handle stores is read or written.  n_rows == 0 does nothing.  Refused (-1, kp_last_error names
+ * the argument) before anything is launched: null handle / in / cfg / out, n_rows < 0, a null required array, a prior without its weights or the
+ * reverse, n_iters < 0, any of mu0, mu_min, mu_max, mu_up, mu_down, damp[d] not > 0 (NaN included), a handle whose threads_per_env is not 64. */
+typedef struct { const float *qpos0, *tgt_pos, *tgt_quat, *w_pos, *w_rot, *q_prior, *w_prior; } kp_fit_in;
+typedef struct { int n_iters; float mu0, mu_min, mu_max, mu_up, mu_down; float damp[75]; int clamp_limits; } kp_fit_cfg;
+typedef struct { float *qpos, *info, *dq; } kp_fit_out;
+void kp_fit_cfg_default(kp_fit_cfg* cfg);
+int kp_sim_fit_pose(kp_sim*, int n_rows, const kp_fit_in* in, const kp_fit_cfg* cfg, const kp_fit_out* out);
+
 /* read-outs of the mujoco-py data fields the env uses (humanoid_im.py:342-416, humanoid_ar_v1.py:460-512) */
 typedef enum {
     KP_QPOS = 0,        /* data.qpos[:76]                    [N,76]  */

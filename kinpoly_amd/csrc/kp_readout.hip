@@ -6,6 +6,7 @@
 #include "kp_contact_force.hpp"
 #include "kp_inverse_dyn.hpp"
 #include "kp_body_motion.hpp"
+#include "kp_fit_pose.hpp"
 
 namespace kp {
 
@@ -40,6 +41,22 @@ void launch_body_motion(BodyMotionArgs A, hipStream_t stream) {
     for (int r0 = 0; r0 < A.n_rows; r0 += CHUNK) {
         A.row0 = r0;
         hipLaunchKernelGGL(k_body_motion, dim3(std::min(CHUNK, A.n_rows - r0)), dim3(64), sizeof(BodyMotionLds), stream, A);
+    }
+}
+
+void launch_point_jacobian(PointJacArgs A, hipStream_t stream) {
+    constexpr int CHUNK = 1 << 24;                                      // as launch_inverse_dynamics
+    for (int r0 = 0; r0 < A.n_rows; r0 += CHUNK) {
+        A.row0 = r0;
+        hipLaunchKernelGGL(k_point_jacobian, dim3(std::min(CHUNK, A.n_rows - r0)), dim3(64), sizeof(PointJacLds), stream, A);
+    }
+}
+
+void launch_fit_pose(FitPoseArgs A, hipStream_t stream) {
+    constexpr int CHUNK = 1 << 24;                                      // as launch_inverse_dynamics
+    for (int r0 = 0; r0 < A.n_rows; r0 += CHUNK) {
+        A.row0 = r0;
+        hipLaunchKernelGGL(k_fit_pose, dim3(std::min(CHUNK, A.n_rows - r0)), dim3(64), sizeof(EnvLds), stream, A);
     }
 }
 

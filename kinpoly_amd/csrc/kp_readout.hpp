@@ -1,6 +1,7 @@
 // kp_readout.hpp -- the kernels beside the control step that are built from its device functions (kp_step_device.hpp): impulse pushes (kp_push.hpp,
 // DESIGN.md section 12), the contact-force read-out (kp_contact_force.hpp, section 14) inverse dynamics on motion rows (kp_inverse_dyn.hpp,
-// section 15) and body motion, momentum and energy on motion rows (kp_body_motion.hpp, section 16).  They live in their own translation unit (kp_readout.hip): however they specialise the shared device functions, the step kernels' unit
+// section 15), body motion, momentum and energy on motion rows (kp_body_motion.hpp, section 16) and point Jacobians and pose fitting on motion rows
+// (kp_fit_pose.hpp, section 17).  They live in their own translation unit (kp_readout.hip): however they specialise the shared device functions, the step kernels' unit
 // does not see it, so the step kernels' code cannot move with them.  kp_sim.hip keeps the entry points' argument checks and calls the launchers below.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -56,6 +57,28 @@ struct BodyMotionArgs {
     BodyMotionOut O;
 };
 
+struct PointJacArgs {
+    DevTables T;
+    Params P;
+    int n_rows, row0;          // as InvDynArgs
+    const float* qpos;         // [R, 76]
+    const int32_t* body;       // [R] 0..23; anything else: a zero row
+    const float* offset;       // [R, 3] in the body frame, or null (the body origin)
+    float* J;                  // [R, 6, 75]
+};
+
+// kp_fit_in, kp_fit_cfg and kp_fit_out of the C ABI in one block
+struct FitPoseArgs {
+    DevTables T;
+    Params P;
+    int n_rows, row0;          // as InvDynArgs
+    const float *qpos0, *tgt_pos, *tgt_quat, *w_pos, *w_rot, *q_prior, *w_prior;      // [R, 76], [R, 24, 3], then optional: [R, 24, 4], [R, 24], [R, 24], [R, 69], [R, 69]
+    int n_iters, clamp_limits;
+    float mu0, mu_min, mu_max, mu_up, mu_down;
+    float damp[D_NV];
+    float *qpos, *info, *dq;   // [R, 76], [R, 8], [R, 75] or null
+};
+
 // Each enqueues on `stream` and returns; the caller reads the launch status (hipGetLastError).  One wavefront per env / row, full LDS layouts.
 // A: the step kernels' argument pack (state rows, object rows); one block per env
 void launch_apply_impulse(const StepArgs& A, const int32_t* entity, const float* offset, const float* impulse, const uint8_t* mask, float* dqvel, hipStream_t stream);
@@ -65,5 +88,8 @@ void launch_contact_forces(const StepArgs& A, const XcArgs& X, bool obj, bool xc
 void launch_inverse_dynamics(InvDynArgs A, bool obj, hipStream_t stream);
 // body motion, momentum and energy of rows (kp_body_motion.hpp, section 16): its own small LDS layout; launches of at most 2^24 rows each
 void launch_body_motion(BodyMotionArgs A, hipStream_t stream);
+// point Jacobians and pose fitting on rows (kp_fit_pose.hpp, section 17): the first on its own small LDS layout, the second on EnvLds; launches of at most 2^24 rows each
+void launch_point_jacobian(PointJacArgs A, hipStream_t stream);
+void launch_fit_pose(FitPoseArgs A, hipStream_t stream);
 
 }  // namespace kp

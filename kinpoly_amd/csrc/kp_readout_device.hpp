@@ -1,4 +1,4 @@
-// kp_readout_device.hpp -- what the read-out kernels (kp_push.hpp, kp_contact_force.hpp, kp_inverse_dyn.hpp) share beyond the control step's own device
+// kp_readout_device.hpp -- what the read-out kernels (kp_push.hpp, kp_contact_force.hpp, kp_inverse_dyn.hpp, kp_fit_pose.hpp) share beyond the control step's own device
 // functions: the env prologue and the projection of forces on the dofs.  Read-out unit only (kp_readout.hip): the step kernels' unit does not see how these
 // specialise the step's functions.  Each helper holds what ALL its users did before it existed, no more: a store one kernel does not need costs the
 // object instantiations scalar registers (profiles/readout_split/tool_benches.md).
@@ -8,7 +8,7 @@
 namespace kp {
 
 // An env's LDS block before a kernel's own state rows: the per-lane model tables, no applied force (applied[6] ++ ctrl[72]), no rows yet.  The caller loads
-// its state (OBJ: its geoms and slots) and syncs.  k_apply_impulse and k_contact_forces; k_inverse_dynamics has the same stores fused into its row loads.
+// its state (OBJ: its geoms and slots) and syncs.  k_apply_impulse, k_contact_forces and k_fit_pose; k_inverse_dynamics has the same stores fused into its row loads.
 template <class SL>
 __device__ __forceinline__ void readout_prologue(SL& s, const DevTables& T, int tid) {
     for (int i = tid; i < D_NV; i += 64) { s.arm[i] = T.dof_armature[i]; s.dbody[i] = T.dof_body[i]; }
@@ -18,7 +18,7 @@ __device__ __forceinline__ void readout_prologue(SL& s, const DevTables& T, int 
 }
 
 // What the articulated-body passes read besides: no extra armature, and the zero words / zero record of IAa / pAa for padded and absent operands.  The two
-// kernels that run such a pass (k_apply_impulse, k_contact_forces).
+// kernels that run such a pass (k_apply_impulse, k_contact_forces, k_fit_pose).
 template <class SL>
 __device__ __forceinline__ void readout_aba_zeros(SL& s, int tid) {
     for (int i = tid; i < D_NV; i += 64) s.extra[i] = 0.f;

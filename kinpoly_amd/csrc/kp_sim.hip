@@ -1886,6 +1886,62 @@ int kp_sim_body_motion(kp_sim* s, int n_rows, const float* qpos, const float* qv
     return launched();
 }
 
+int kp_sim_point_jacobian(kp_sim* s, int n_rows, const float* qpos, const int32_t* body, const float* offset, float* J) {
+    if (!s) return fail("kp_sim_point_jacobian: null handle");
+    if (n_rows < 0) return fail("kp_sim_point_jacobian: n_rows < 0");
+    if (!qpos) return fail("kp_sim_point_jacobian: null qpos");
+    if (!body) return fail("kp_sim_point_jacobian: null body");
+    if (!J) return fail("kp_sim_point_jacobian: null J");
+    if (s->model->threads != 64) return fail("kp_sim_point_jacobian: needs a handle with threads_per_env = 64");
+    if (n_rows == 0) return 0;
+    HIP_OK(hipSetDevice(s->device));
+    kp::PointJacArgs A{};
+    A.T = s->T; A.P = s->P; A.n_rows = n_rows;
+    A.qpos = qpos; A.body = body; A.offset = offset; A.J = J;
+    kp::launch_point_jacobian(A, s->stream);
+    return launched();
+}
+
+void kp_fit_cfg_default(kp_fit_cfg* c) {
+    if (!c) return;
+    c->n_iters = 30;
+    c->mu0 = 1e-2f; c->mu_min = 1e-7f; c->mu_max = 1e6f; c->mu_up = 8.f; c->mu_down = 0.3f;
+    for (int d = 0; d < kp::D_NV; d++) c->damp[d] = 1.f;
+    c->clamp_limits = 0;
+}
+
+int kp_sim_fit_pose(kp_sim* s, int n_rows, const kp_fit_in* in, const kp_fit_cfg* cfg, const kp_fit_out* out) {
+    if (!s) return fail("kp_sim_fit_pose: null handle");
+    if (n_rows < 0) return fail("kp_sim_fit_pose: n_rows < 0");
+    if (!in) return fail("kp_sim_fit_pose: null in");
+    if (!cfg) return fail("kp_sim_fit_pose: null cfg");
+    if (!out) return fail("kp_sim_fit_pose: null out");
+    if (!in->qpos0) return fail("kp_sim_fit_pose: null qpos0");
+    if (!in->tgt_pos) return fail("kp_sim_fit_pose: null tgt_pos");
+    if (!in->q_prior != !in->w_prior) return fail("kp_sim_fit_pose: q_prior and w_prior go together (one of them is null)");
+    if (!out->qpos) return fail("kp_sim_fit_pose: null out qpos");
+    if (!out->info) return fail("kp_sim_fit_pose: null out info");
+    if (cfg->n_iters < 0) return fail("kp_sim_fit_pose: n_iters < 0");
+    // !(x > 0) also refuses a NaN
+    const std::pair<const char*, float> pos[] = {{"mu0", cfg->mu0}, {"mu_min", cfg->mu_min}, {"mu_max", cfg->mu_max}, {"mu_up", cfg->mu_up}, {"mu_down", cfg->mu_down}};
+    for (const auto& p : pos)
+        if (!(p.second > 0.f)) return fail(std::string("kp_sim_fit_pose: ") + p.first + " must be > 0");
+    for (int d = 0; d < kp::D_NV; d++)
+        if (!(cfg->damp[d] > 0.f)) return fail("kp_sim_fit_pose: damp[" + std::to_string(d) + "] must be > 0");
+    if (s->model->threads != 64) return fail("kp_sim_fit_pose: needs a handle with threads_per_env = 64");
+    if (n_rows == 0) return 0;
+    HIP_OK(hipSetDevice(s->device));
+    kp::FitPoseArgs A{};
+    A.T = s->T; A.P = s->P; A.n_rows = n_rows;
+    A.qpos0 = in->qpos0; A.tgt_pos = in->tgt_pos; A.tgt_quat = in->tgt_quat; A.w_pos = in->w_pos; A.w_rot = in->w_rot; A.q_prior = in->q_prior; A.w_prior = in->w_prior;
+    A.n_iters = cfg->n_iters; A.clamp_limits = cfg->clamp_limits;
+    A.mu0 = cfg->mu0; A.mu_min = cfg->mu_min; A.mu_max = cfg->mu_max; A.mu_up = cfg->mu_up; A.mu_down = cfg->mu_down;
+    for (int d = 0; d < kp::D_NV; d++) A.damp[d] = cfg->damp[d];
+    A.qpos = out->qpos; A.info = out->info; A.dq = out->dq;
+    kp::launch_fit_pose(A, s->stream);
+    return launched();
+}
+
 }  // extern "C"
 
 // ---- model compiler behind the ABI (host only).  Included last: its `#pragma clang fp contract(off)` (bit-reproducible double arithmetic,

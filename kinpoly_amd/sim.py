@@ -159,6 +159,31 @@ CENTROID_FIELDS = {"com": slice(0, 3), "com_vel": slice(3, 6), "L_com": slice(6,
                    "mass": 17}
 
 
+class KpFitIn(C.Structure):
+    """mirror of kp_fit_in: the device rows kp_sim_fit_pose reads (qpos0 and tgt_pos required, the others may be NULL)"""
+    _fields_ = [(k, C.c_void_p) for k in ("qpos0", "tgt_pos", "tgt_quat", "w_pos", "w_rot", "q_prior", "w_prior")]
+
+
+class KpFitCfg(C.Structure):
+    """mirror of kp_fit_cfg (host side): the Levenberg-Marquardt schedule of kp_sim_fit_pose"""
+    _fields_ = [("n_iters", C.c_int)] + [(k, C.c_float) for k in ("mu0", "mu_min", "mu_max", "mu_up", "mu_down")] + [("damp", C.c_float * 75), ("clamp_limits", C.c_int)]
+
+    @classmethod
+    def default(cls):
+        c = cls()
+        load_library().kp_fit_cfg_default(C.byref(c))
+        return c
+
+
+class KpFitOut(C.Structure):
+    """mirror of kp_fit_out: the device rows kp_sim_fit_pose fills (dq may be NULL)"""
+    _fields_ = [(k, C.c_void_p) for k in ("qpos", "info", "dq")]
+
+
+# the columns of KpSim.fit_pose's info rows: name -> index
+FIT_INFO = {"cost0": 0, "cost": 1, "accepted": 2, "mu": 3, "max_epos": 4, "max_erot": 5, "dq_inf": 6, "status": 7}
+
+
 class KinPolyNativeError(RuntimeError):
     pass
 
@@ -179,6 +204,9 @@ _SIGNATURES = {
     "kp_sim_contact_forces": (_I, [_V, _I, _V, _V, _V]),      # handle, actuation, act, env_mask, kp_contact_out*
     "kp_sim_inverse_dynamics": (_I, [_V, _I, _V, _V, _V, _V, _V]),      # handle, n_rows, qpos, qvel, qacc, obj_qpos, kp_invdyn_out*
     "kp_sim_body_motion": (_I, [_V, _I, _V, _V, _V, _V]),      # handle, n_rows, qpos, qvel, qacc, kp_motion_out*
+    "kp_sim_point_jacobian": (_I, [_V, _I, _V, _V, _V, _V]),      # handle, n_rows, qpos, body, offset, J
+    "kp_fit_cfg_default": (None, [C.POINTER(KpFitCfg)]),
+    "kp_sim_fit_pose": (_I, [_V, _I, _V, _V, _V]),      # handle, n_rows, kp_fit_in*, kp_fit_cfg*, kp_fit_out*
     "kp_sim_fk": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]), "kp_sim_fk_backward": (_I, [_V, _I, _V, _V, _V, _V, _V]),
     "kp_sim_pose_contacts": (_I, [_V, _I, _V, _V, _V, _F, _V, _V, _V]),
     # the offscreen renderer (kp_render.hip); kp_model_hull_planes is host only
@@ -560,6 +588,55 @@ class KpSim:
             ptrs = [_dev("body_motion: " + k, t, (R, d)) for k, t, d in zip(("qpos", "qvel", "qacc"), ins, (NQ, NV, NV))]
             _check(self.L.kp_sim_body_motion(self.h, R, *ptrs, C.byref(st)), "kp_sim_body_motion")
         return {k: v.view(lead + MOTION_OUTPUTS[k][0]) for k, v in out.items()}
+
+    def point_jacobian(self, qpos, body, offset=None) -> torch.Tensor:
+        """mj_jac on rows (kp_sim_point_jacobian): qpos [..., 76], body int32 [...] (0..23; anything else: a zero row), offset [..., 3] in the body's
+        frame or None (the body origin), any leading shape.  Returns J [..., 6, 75]: rows 0..2 the world velocity of the point, rows 3..5 the body's
+        world angular velocity, per unit dof velocity (qvel order).  Nothing the handle stores is read or changed."""
+        if qpos.dim() < 1 or qpos.shape[-1] != NQ:
+            raise ValueError(f"point_jacobian: qpos must be [..., {NQ}], got {tuple(qpos.shape)}")
+        lead = tuple(qpos.shape[:-1])
+        R = int(np.prod(lead, dtype=np.int64))
+        if tuple(body.shape) != lead:
+            raise ValueError(f"point_jacobian: body must be {lead}, got {tuple(body.shape)}")
+        if offset is not None and tuple(offset.shape) != lead + (3,):
+            raise ValueError(f"point_jacobian: offset must be {lead + (3,)}, got {tuple(offset.shape)}")
+        J = torch.empty((R, 6, NV), dtype=torch.float32, device=self.device)
+        if R > 0:                # no rows: nothing to launch (and an empty tensor has no address to hand over)
+            ptrs = [_dev("point_jacobian: qpos", qpos.reshape(R, NQ), (R, NQ)), _dev("point_jacobian: body", body.reshape(R), (R,), torch.int32),
+                    _dev("point_jacobian: offset", None if offset is None else offset.reshape(R, 3), (R, 3))]
+            _check(self.L.kp_sim_point_jacobian(self.h, R, *ptrs, C.c_void_p(J.data_ptr())), "kp_sim_point_jacobian")
+        return J.view(lead + (6, NV))
+
+    def fit_pose(self, qpos0, tgt_pos, tgt_quat=None, w_pos=None, w_rot=None, q_prior=None, w_prior=None, cfg: KpFitCfg | None = None, want_dq=False) -> dict:
+        """Pose fitting on rows (kp_sim_fit_pose): Levenberg-Marquardt from qpos0 [..., 76] towards the body positions tgt_pos [..., 24, 3] and, where
+        given, orientations tgt_quat [..., 24, 4], weighted by w_pos / w_rot [..., 24] (None: ones / zeros), with the hinge prior q_prior / w_prior
+        [..., 69] (both or neither); any leading shape, the same on every input.  cfg: a KpFitCfg (None: KpFitCfg.default()).  Returns a dict of device
+        tensors: qpos [..., 76], info [..., 8] (FIT_INFO: cost0, cost, accepted, mu, max_epos, max_erot, dq_inf, status) and, with want_dq, dq
+        [..., 75] of the last solve.  Nothing the handle stores is read or changed."""
+        if qpos0.dim() < 1 or qpos0.shape[-1] != NQ:
+            raise ValueError(f"fit_pose: qpos0 must be [..., {NQ}], got {tuple(qpos0.shape)}")
+        if (q_prior is None) != (w_prior is None):
+            raise ValueError("fit_pose: q_prior and w_prior go together")
+        lead = tuple(qpos0.shape[:-1])
+        R = int(np.prod(lead, dtype=np.int64))
+        ins = []
+        for name, t, tail in (("qpos0", qpos0, (NQ,)), ("tgt_pos", tgt_pos, (24, 3)), ("tgt_quat", tgt_quat, (24, 4)), ("w_pos", w_pos, (24,)), ("w_rot", w_rot, (24,)),
+                              ("q_prior", q_prior, (69,)), ("w_prior", w_prior, (69,))):
+            if t is None and name == "tgt_pos":
+                raise ValueError("fit_pose: tgt_pos is required")
+            if t is not None and tuple(t.shape) != lead + tail:
+                raise ValueError(f"fit_pose: {name} must be {lead + tail}, got {tuple(t.shape)}")
+            ins.append((name, None if t is None else t.reshape((R,) + tail), (R,) + tail))
+        cfg = KpFitCfg.default() if cfg is None else cfg
+        out = {"qpos": torch.empty((R, NQ), dtype=torch.float32, device=self.device), "info": torch.empty((R, 8), dtype=torch.float32, device=self.device)}
+        if want_dq:
+            out["dq"] = torch.empty((R, NV), dtype=torch.float32, device=self.device)
+        if R > 0:                # no rows: nothing to launch (and an empty tensor has no address to hand over)
+            fin = KpFitIn(*[_dev("fit_pose: " + k, t, shp) for k, t, shp in ins])
+            fout = KpFitOut(*[None if k not in out else C.c_void_p(out[k].data_ptr()) for k in ("qpos", "info", "dq")])
+            _check(self.L.kp_sim_fit_pose(self.h, R, C.byref(fin), C.byref(cfg), C.byref(fout)), "kp_sim_fit_pose")
+        return {k: v.view(lead + tuple(v.shape[1:])) for k, v in out.items()}
 
     def fk(self, qpos_rows: torch.Tensor):
         """qpos_fk_batch on [R,76] rows -> dict(qpos, wbpos, wbquat, bquat, body_com) of device tensors."""

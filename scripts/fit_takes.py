@@ -1,0 +1,96 @@
+#!/usr/bin/env python
+"""Body-position tracks -> a take library the UHC pipeline reads (kinpoly_amd/fit.py).  No reference counterpart: the
+reference gets qpos from SMPL axis-angles offline (uhc/data_process); this is the way in for marker or key-point tracks.
+
+    python scripts/fit_takes.py --tracks in.pkl --out takes.pkl [--mode chained|independent] [--iters N] [--smooth W] [--limits]
+
+in.pkl:  {take: {"wbpos": [T, 24, 3], optional "wbquat": [T, 24, 4], optional "obj_pose"}} (joblib or pickle).
+out:     {take: {"qpos": [T, 76], "pose_aa": zeros [T, 72], "trans": zeros [T, 3], (obj_pose as given)}}: the schema AmassSingleDataset reads (of pose_aa
+         and trans only the length is read, by its length filter), and next to it fit_report.json (per take: mean / max position error, share of
+         accepted steps, failed rows).
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def load_tracks(path):
+    import joblib
+    tracks = joblib.load(path)
+    if not isinstance(tracks, dict) or not tracks:
+        raise ValueError(f"{path}: expected a non-empty dict take -> {{'wbpos': [T, 24, 3], ...}}")
+    for k, v in tracks.items():
+        wb = np.asarray(v["wbpos"])
+        if wb.ndim == 2 and wb.shape[1] == 72:
+            wb = wb.reshape(-1, 24, 3)
+        if wb.ndim != 3 or wb.shape[1:] != (24, 3) or wb.shape[0] < 1:
+            raise ValueError(f"take '{k}': wbpos must be [T, 24, 3], got {np.shape(v['wbpos'])}")
+        if v.get("wbquat") is not None and np.asarray(v["wbquat"]).reshape(-1, 24, 4).shape[0] != wb.shape[0]:
+            raise ValueError(f"take '{k}': wbquat must be [T, 24, 4] with wbpos' T")
+    return tracks
+
+
+def fit_tracks(sim, tracks: dict, mode="chained", iters=30, smooth=1e-2, limits=False):
+    """(takes in AmassSingleDataset's schema, report).  All takes go through ONE fit_sequence: shorter tracks are padded with their last frame and cut
+    again (a padded frame costs a fit and changes nothing before it).  Orientations are used only when every take carries them."""
+    from kinpoly_amd import fit
+    names = list(tracks)
+    lens = [np.asarray(tracks[k]["wbpos"]).reshape(-1, 24, 3).shape[0] for k in names]
+    Tm = max(lens)
+
+    def padded(key, w):
+        rows = []
+        for k in names:
+            a = np.asarray(tracks[k][key], np.float32).reshape(-1, 24, w)
+            rows.append(np.concatenate([a, np.repeat(a[-1:], Tm - a.shape[0], 0)], 0))
+        return torch.as_tensor(np.stack(rows), device=sim.device)
+
+    tp = padded("wbpos", 3)
+    tq = padded("wbquat", 4) if all(tracks[k].get("wbquat") is not None for k in names) else None
+    cfg = fit.FitConfig(n_iters=iters, clamp_limits=limits)
+    out = fit.fit_sequence(sim, tp, tq, mode=mode, smooth=smooth, config=cfg)
+    rep = fit.fit_report(sim, names, out["qpos"], tp, out["info"], iters)
+    qpos = out["qpos"].double().cpu().numpy()
+    takes = {}
+    for b, k in enumerate(names):
+        T = lens[b]
+        takes[k] = {"qpos": qpos[b, :T], "pose_aa": np.zeros((T, 72)), "trans": np.zeros((T, 3))}
+        if tracks[k].get("obj_pose") is not None:
+            takes[k]["obj_pose"] = np.asarray(tracks[k]["obj_pose"])
+    return takes, rep
+
+
+def main(argv=None, sim=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--tracks", required=True)
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--mode", choices=("chained", "independent"), default="chained")
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--smooth", type=float, default=1e-2)
+    ap.add_argument("--limits", action="store_true")
+    a = ap.parse_args(argv)
+    tracks = load_tracks(a.tracks)
+    if sim is None:
+        from kinpoly_amd import sim as kpsim
+        sim = kpsim.KpSim(kpsim.KpModel(), 1)
+    takes, rep = fit_tracks(sim, tracks, a.mode, a.iters, a.smooth, a.limits)
+    import joblib
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    joblib.dump(takes, a.out)
+    rp = os.path.join(os.path.dirname(os.path.abspath(a.out)), "fit_report.json")
+    with open(rp, "w") as f:
+        json.dump(rep, f, indent=1)
+    print(json.dumps({"takes": len(takes), "frames": int(sum(len(v["qpos"]) for v in takes.values())), "out": a.out, "report": rp,
+                      "max_pos_err": max(r["max_pos_err"] for r in rep.values())}))
+    return takes, rep
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,281 @@
+"""fp64 reference of the pose fit and the point Jacobian (kp_sim_fit_pose, kp_sim_point_jacobian): test infrastructure.
+
+Kinematics come from OracleSim (xpos, xquat), body Jacobians from push_oracle.body_jacobians / point_jacobian (the oracle's own cvel, column by column).
+The Levenberg-Marquardt loop is the kernel's, with a dense numpy.linalg.solve of J^T W J + diag(mu damp + w_prior) where the kernel runs its
+articulated-body pass: the same residuals (x* - x; log(R* R^T) as a world rotation vector on the shortest arc), the same q (+) dq (mj_integratePos with
+dt = 1), the same accept rule (finite and strictly smaller cost) and the same mu schedule.
+"""
+import numpy as np
+
+import push_oracle as PO
+from oracle.kpo import OracleSim
+
+NV, NB, NU, NQ = 75, 24, 69, 76
+# kp_fit_cfg_default
+DEFAULT_CFG = dict(n_iters=30, mu0=1e-2, mu_min=1e-7, mu_max=1e6, mu_up=8.0, mu_down=0.3, damp=np.ones(NV), clamp_limits=False)
+
+
+def oracle(kpm_path):
+    """kinematics only: no contact rows, no limit rows (forward() is called 76 times per Jacobian)"""
+    return OracleSim(kpm=kpm_path, contact=False, limits=False)
+
+
+def qmul(a, b):
+    w0, x0, y0, z0 = a; w1, x1, y1, z1 = b
+    return np.array([w0 * w1 - x0 * x1 - y0 * y1 - z0 * z1, w0 * x1 + x0 * w1 + y0 * z1 - z0 * y1, w0 * y1 - x0 * z1 + y0 * w1 + z0 * x1, w0 * z1 + x0 * y1 - y0 * x1 + z0 * w1])
+
+
+def qnormalize(q):
+    n = np.linalg.norm(q)
+    return np.array([1.0, 0, 0, 0]) if n < 1e-15 else np.asarray(q, float) / n
+
+
+def quat_log(q):
+    """rotation vector of a unit quaternion, shortest arc (the sign with w >= 0)"""
+    q = np.asarray(q, float)
+    if q[0] < 0:
+        q = -q
+    n = np.linalg.norm(q[1:])
+    if n < 1e-8:
+        return 2.0 / q[0] * (1.0 - n * n / (3.0 * q[0] * q[0])) * q[1:]
+    return 2.0 * np.arctan2(n, q[0]) / n * q[1:]
+
+
+def quat_exp(w):
+    a = np.linalg.norm(w)
+    if a < 1e-8:
+        return np.concatenate([[1.0 - a * a / 8.0], (0.5 - a * a / 48.0) * np.asarray(w, float)])
+    return np.concatenate([[np.cos(a / 2)], np.sin(a / 2) / a * np.asarray(w, float)])
+
+
+def normalized(q):
+    q = np.array(q, np.float64)
+    q[3:7] = qnormalize(q[3:7])
+    return q
+
+
+def oplus(q, dq, jnt_range=None, jnt_limited=None):
+    """q (+) dq: root position += dq[0:3], root quaternion (x) exp(dq[3:6]) (body frame), hinges += dq[6:]; with a range, limited hinges are clamped"""
+    out = np.array(q, np.float64)
+    out[:3] += dq[:3]
+    out[3:7] = qnormalize(qmul(qnormalize(out[3:7]), quat_exp(dq[3:6])))
+    out[7:] += dq[6:]
+    if jnt_range is not None:
+        lim = np.asarray(jnt_limited).astype(bool)[:NU]
+        rng = np.asarray(jnt_range, float).reshape(-1, 2)[:NU]
+        out[7:] = np.where(lim, np.clip(out[7:], rng[:, 0], rng[:, 1]), out[7:])
+    return out
+
+
+def fk(o, q):
+    """(xpos [24, 3], xquat [24, 4]) of the oracle's forward pass at q (root quaternion normalised first)"""
+    o.set_state_raw(normalized(q), np.zeros(NV)); o.forward()
+    return o.get("xpos").reshape(NB, 3).copy(), o.get("xquat").reshape(NB, 4).copy()
+
+
+def origin_jacobians(o, q):
+    """J [24, 6, 75]: rows 0..2 the world velocity of body b's origin, rows 3..5 its world angular velocity, per unit dof velocity; and xpos, xquat"""
+    Jc, com, xpos, xquat = PO.body_jacobians(o, normalized(q))
+    J = np.zeros((NB, 6, NV))
+    for b in range(NB):
+        J[b, :3] = Jc[b, 3:] - PO._skew(xpos[b] - com) @ Jc[b, :3]
+        J[b, 3:] = Jc[b, :3]
+    return J, xpos, xquat
+
+
+def problem(tgt_pos, tgt_quat=None, w_pos=None, w_rot=None, q_prior=None, w_prior=None):
+    """the inputs of one row with the kernel's defaults filled in: null weights are 1 / 0, negative ones 0, target quaternions normalised"""
+    tp = np.asarray(tgt_pos, np.float64).reshape(NB, 3)
+    tq = None if tgt_quat is None else np.stack([qnormalize(x) for x in np.asarray(tgt_quat, np.float64).reshape(NB, 4)])
+    wp = np.ones(NB) if w_pos is None else np.maximum(np.asarray(w_pos, np.float64), 0.0)
+    wr = np.zeros(NB) if (w_rot is None or tq is None) else np.maximum(np.asarray(w_rot, np.float64), 0.0)
+    assert (q_prior is None) == (w_prior is None)
+    qp = np.zeros(NU) if q_prior is None else np.asarray(q_prior, np.float64)
+    wq = np.zeros(NU) if w_prior is None else np.maximum(np.asarray(w_prior, np.float64), 0.0)
+    return dict(tp=tp, tq=tq, wp=wp, wr=wr, qp=qp, wq=wq)
+
+
+def residuals(pb, xpos, xquat):
+    e_pos = pb["tp"] - xpos
+    e_rot = np.zeros((NB, 3))
+    if pb["tq"] is not None:
+        for b in range(NB):
+            e_rot[b] = quat_log(qmul(pb["tq"][b], xquat[b] * np.array([1.0, -1, -1, -1])))
+    return e_pos, e_rot
+
+
+def cost_of(pb, q, e_pos, e_rot):
+    return 0.5 * float(pb["wp"] @ (e_pos ** 2).sum(1)) + 0.5 * float(pb["wr"] @ (e_rot ** 2).sum(1)) + 0.5 * float(pb["wq"] @ (pb["qp"] - q[7:]) ** 2)
+
+
+def evaluate(o, pb, q):
+    xpos, xquat = fk(o, q)
+    e_pos, e_rot = residuals(pb, xpos, xquat)
+    return cost_of(pb, q, e_pos, e_rot), e_pos, e_rot
+
+
+def normal_system(o, pb, q, mu, damp):
+    """A = J^T W J + diag(mu damp + w_prior), g = J^T W e + w_prior (q* - q) at q; also J^T W J alone"""
+    J, xpos, xquat = origin_jacobians(o, q)
+    e_pos, e_rot = residuals(pb, xpos, xquat)
+    H = np.zeros((NV, NV)); g = np.zeros(NV)
+    for b in range(NB):
+        H += pb["wp"][b] * J[b, :3].T @ J[b, :3] + pb["wr"][b] * J[b, 3:].T @ J[b, 3:]
+        g += pb["wp"][b] * J[b, :3].T @ e_pos[b] + pb["wr"][b] * J[b, 3:].T @ e_rot[b]
+    extra = mu * np.asarray(damp, float)
+    extra[6:] += pb["wq"]
+    g[6:] += pb["wq"] * (pb["qp"] - np.asarray(q, float)[7:])
+    return H + np.diag(extra), g, H
+
+
+def errors(pb, e_pos, e_rot):
+    """max |e_pos|, max |e_rot| over the bodies with a positive weight (info columns 4, 5)"""
+    ep = np.linalg.norm(e_pos, axis=1) * (pb["wp"] > 0); er = np.linalg.norm(e_rot, axis=1) * (pb["wr"] > 0)
+    return float(ep.max()), float(er.max())
+
+
+def lm(o, q0, pb, cfg=None, jnt_range=None, jnt_limited=None, stop=None):
+    """The kernel's loop in fp64.  Returns dict(qpos, info [8], dq [75], A, g (last system), costs (after every iteration), iters_to_stop: the first
+    iteration count after which stop(max_epos, max_erot) held, or None)."""
+    cfg = {**DEFAULT_CFG, **(cfg or {})}
+    q = normalized(q0)
+    c, e_pos, e_rot = evaluate(o, pb, q)
+    cost0, mu, nacc = c, float(cfg["mu0"]), 0
+    dq = np.zeros(NV); A = g = None
+    costs, hit = [], None
+    bad = not (np.isfinite(c) and np.all(np.isfinite(q0)))
+    for it in range(0 if bad else int(cfg["n_iters"])):
+        A, g, _ = normal_system(o, pb, q, mu, cfg["damp"])
+        dq = np.linalg.solve(A, g)
+        qt = oplus(q, dq, *((jnt_range, jnt_limited) if cfg["clamp_limits"] else (None, None)))
+        ct, ept, ert = evaluate(o, pb, qt)
+        if np.isfinite(ct) and ct < c:
+            q, c, e_pos, e_rot = qt, ct, ept, ert
+            nacc += 1; mu = max(mu * cfg["mu_down"], cfg["mu_min"])
+        else:
+            mu = min(mu * cfg["mu_up"], cfg["mu_max"])
+        costs.append(c)
+        if stop is not None and hit is None and stop(*errors(pb, e_pos, e_rot)):
+            hit = it + 1
+    ep, er = errors(pb, e_pos, e_rot)
+    info = np.array([cost0, c, nacc, mu, ep, er, float(np.abs(dq).max()), 1.0 if bad else 0.0])
+    return dict(qpos=np.array(q0, np.float64) if bad else q, info=info, dq=dq, A=A, g=g, costs=costs, iters_to_stop=hit)
+
+
+def pseudo_inertia_crba(o, q, w_pos, w_rot, dof_body, body_parent):
+    """The joint-space inertia of the tree whose body b is a point mass w_pos[b] at its origin plus a spherical rotational inertia w_rot[b] I_3, by the
+    composite-rigid-body algorithm: spatial inertias about one point, summed leaves -> root, M[i, j] = s_i^T Ic[body(i)] s_j for every dof j on the
+    path from i's body to the root.  Spatial vectors are [ang; lin] about the oracle's subtree_com with world axes; s_d is dof d's own motion axis,
+    read from the cvel of d's own body."""
+    Jc, com, xpos, _ = PO.body_jacobians(o, normalized(q))
+    Ic = np.zeros((NB, 6, 6))
+    for b in range(NB):
+        r = xpos[b] - com; S = PO._skew(r); m = w_pos[b]
+        Ic[b, :3, :3] = w_rot[b] * np.eye(3) - m * S @ S
+        Ic[b, :3, 3:] = m * S; Ic[b, 3:, :3] = -m * S
+        Ic[b, 3:, 3:] = m * np.eye(3)
+    for b in range(NB - 1, 0, -1):
+        Ic[body_parent[b]] += Ic[b]
+    s = np.stack([Jc[dof_body[d], :, d] for d in range(NV)])
+    anc = []                     # bodies on the path root .. b
+    for b in range(NB):
+        path = [b]
+        while body_parent[path[-1]] >= 0:
+            path.append(body_parent[path[-1]])
+        anc.append(set(path))
+    M = np.zeros((NV, NV))
+    for i in range(NV):
+        bi = dof_body[i]
+        f = Ic[bi] @ s[i]
+        for j in range(NV):
+            if dof_body[j] in anc[bi] and (dof_body[j] != bi or j <= i):
+                M[i, j] = M[j, i] = s[j] @ f
+    return M
+
+
+# ---------------------------------------------------------------- the cases of the GPU tests (chosen in tests/test_fit_pose_cpu.py)
+
+def perturbed(q, seed):
+    """the init of a convergence case: the truth plus N(0, 0.2 rad) on the hinges, +-0.1 m and +-0.2 rad on the root (seeded)"""
+    rng = np.random.default_rng(seed)
+    dq = np.concatenate([rng.uniform(-0.1, 0.1, 3), rng.uniform(-0.2, 0.2, 3), rng.normal(size=NU) * 0.2])
+    return oplus(q, dq)
+
+
+def f32(a):
+    return np.asarray(a, np.float32).astype(np.float64)
+
+
+ROWS = (1, 5, 67)
+# iterations the fp64 loop needs on the worst convergence case to bring both errors under 1e-9 (tests/test_fit_pose_cpu.py asserts it), and what the
+# GPU test runs: that count + 50 %
+CONVERGENCE_ITERS = 5
+GPU_CONVERGENCE_ITERS = 8
+NOISY_ITERS = 45              # both inits of every noisy case sit at the same minimum (to 1e-9 of the cost) after this many (asserted there too)
+NOISE_SIGMA, NOISE_W_PRIOR = 0.02, 1e-2
+
+
+def deep_squat(std_qpos):
+    """hips, knees and ankles bent about their x hinges, the pelvis 0.45 m lower (bodies 1..3 left leg, 5..7 right leg; hinge x of body b is 3 (b - 1) + 2)"""
+    q = np.array(std_qpos, float)
+    for hip in (1, 5):
+        q[7 + 3 * (hip - 1) + 2] -= 1.8; q[7 + 3 * hip + 2] += 2.2; q[7 + 3 * (hip + 1) + 2] -= 0.4
+    q[2] -= 0.45
+    return q
+
+
+def jacobian_poses(std_qpos, named):
+    """name -> qpos (fp32-representable) of the Jacobian parity test: standing, lying, deep squat, yaw = pi, hinges at +-3 pi, a non-unit root quaternion"""
+    import body_motion_oracle as BM
+    edge = BM.edge_rows(std_qpos)
+    by = {s["name"]: s["q"] for s in named}
+    return {"standing": f32(by["a_standing"]), "lying": f32(by["d_lying"]), "deep_squat": f32(deep_squat(std_qpos)), "yaw_pi": edge["heading_+pi"][0],
+            "hinges_3pi": edge["joints_3pi"][0], "nonunit_quat": edge["nonunit_quat"][0]}
+
+
+def truth_poses(named, sweep):
+    """the 67 poses of the fit tests: the six named states, then the first 61 sweep states"""
+    return [f32(s["q"]) for s in list(named) + list(sweep)[:67 - len(named)]]
+
+
+def reachable_case(o, q_true, seed, exact=False):
+    """targets = FK of the truth, every position and orientation weighted 1; init = perturbed truth.  exact: the fp64 targets, which the truth
+    reaches to the last bit (the CPU convergence check); otherwise their fp32 roundings, which the kernel is given (reachable to ~1e-7)"""
+    xpos, xquat = fk(o, q_true)
+    r = (lambda a: a) if exact else f32
+    return dict(q_true=normalized(q_true), q0=f32(perturbed(q_true, seed)), tgt_pos=r(xpos), tgt_quat=r(xquat), w_pos=np.ones(NB), w_rot=np.ones(NB))
+
+
+def noisy_case(o, q_true, std_qpos, seed):
+    """positions only with N(0, 2 cm) noise, a prior of weight 1e-2 towards the standing pose; two inits: the perturbed truth and the standing pose
+    moved to the pelvis target"""
+    rng = np.random.default_rng(seed)
+    xpos, _ = fk(o, q_true)
+    tp = f32(xpos + rng.normal(size=(NB, 3)) * NOISE_SIGMA)
+    qa = f32(perturbed(q_true, seed + 1))
+    qb = np.array(std_qpos, float); qb[:3] = tp[0]; qb[3:7] = normalized(q_true)[3:7]
+    return dict(q0=qa, q0_alt=f32(qb), tgt_pos=tp, q_prior=f32(np.asarray(std_qpos, float)[7:]), w_prior=f32(np.full(NU, NOISE_W_PRIOR)))
+
+
+def noisy_reference(o, truths, std_qpos):
+    """(qpos [n, 76], cost [n]) of the reference's minimum of every noisy case, from its first init"""
+    qs, cs = [], []
+    for i, q in enumerate(truths):
+        c = noisy_case(o, q, std_qpos, 500 + i)
+        r = lm(o, c["q0"], problem(c["tgt_pos"], None, None, None, c["q_prior"], c["w_prior"]), dict(n_iters=NOISY_ITERS))
+        qs.append(r["qpos"]); cs.append(r["info"][1])
+    return np.stack(qs), np.array(cs)
+
+
+if __name__ == "__main__":
+    # rewrites tests/golden/fit_pose_noisy_ref.npz (tests/test_fit_pose_cpu.py checks the file against a fresh computation)
+    import os
+    import inverse_dynamics_oracle as ID
+    from kinpoly_amd.model_compiler import DEFAULT_KPM, STEP_KPM, read_kpm
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    std = np.load(os.path.join(root, "tests", "golden", "standing_neutral.npz"))
+    kpm = read_kpm(DEFAULT_KPM)
+    truths = truth_poses(ID.named_states(kpm, read_kpm(STEP_KPM), std["qpos"], std["qvel"]), ID.sweep_states(kpm, std["qpos"]))
+    qpos, cost = noisy_reference(oracle(DEFAULT_KPM), truths, std["qpos"])
+    np.savez(os.path.join(root, "tests", "golden", "fit_pose_noisy_ref.npz"), qpos=qpos, cost=cost)
+    print(f"{len(cost)} minima written, costs {cost.min():.4e} .. {cost.max():.4e}")
