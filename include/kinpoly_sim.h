@@ -569,6 +569,45 @@ typedef struct { float *qpos, *info, *dq; } kp_fit_out;
 void kp_fit_cfg_default(kp_fit_cfg* cfg);
 int kp_sim_fit_pose(kp_sim*, int n_rows, const kp_fit_in* in, const kp_fit_cfg* cfg, const kp_fit_out* out);
 
+/* Contact forces ESTIMATED from kinematics on motion ROWS: the ground reaction a motion would need.  No reference counterpart and no mujoco-py one
+ * (deviation 42); it is the support-force estimate of physics-based pose estimation and biomechanics.  kp_sim_inverse_dynamics charges
+ * a row the forces of the soft-constraint model, a function of how many millimetres a hull penetrates; this call asks which forces inside the friction
+ * pyramids of the points NEAR a surface explain the row's root residual best.  Per row:
+ *   candidates  the contacts the control step's collision pass finds at the row's pose with its margin set to cfg->reach (everything else the model's):
+ *               up to planemesh_max per hull on the floor, one per hull and box / cylinder, 64 slots in the stored order.  Candidate c has the point
+ *               p_c, the unit normal n_c into the hull, the tangents t1_c, t2_c of the step's contact frame and the four pyramid edges
+ *               d_ck = n_c + mu t1_c, n_c - mu t1_c, n_c + mu t2_c, n_c - mu t2_c (mu = cfg->mu if > 0, else the model's).
+ *   demand      need = M qacc + qfrc_bias (+ armature) exactly as kp_sim_inverse_dynamics forms it; no joint-limit row is evaluated.
+ *               r = [need[0:3]; R_root need[3:6]]: force and moment in world axes about the root position x_root.
+ *   solve       lambda >= 0 in R^(4C) minimising 1/2 (r - G lambda)^T W (r - G lambda) + 1/2 rho |lambda|^2, g_ck = [d_ck; (p_c - x_root) x d_ck],
+ *               W = diag(w_f I3, w_m I3).  Strictly convex: the minimiser is unique and does not depend on the method (a semismooth Newton iteration with an
+ *               exact line search on the 6-vector e = r - G lambda, at most n_iters steps).
+ * The score is a LOWER bound on the residual: every nearby point may push.  Objects are static obstacles as in kp_sim_inverse_dynamics.
+ *   qpos, qvel, qacc, obj_qpos   as kp_sim_inverse_dynamics (NULL qvel / qacc: zeros; NULL obj_qpos or every object parked: the floor scene, bit for bit).
+ *   cfg  kp_estimate_cfg_default(model, cfg), with m the model's total mass and g its gravity: reach 0.03 m, w_f = 1 / (m g)^2, w_m = 1 / (m g x 1 m)^2,
+ *        rho = 1e-3 w_f, mu 0 (the model's), n_iters 20.  Conventions, not measurements.
+ *   out  device arrays, each may be NULL but not all:
+ *     qfrc_inverse float [R,75]     need - qfrc_contact; its first six entries are the residual in kp_sim_inverse_dynamics' root convention
+ *     qfrc_contact float [R,75]     J^T f of the estimated forces
+ *     contact      float [R,64,12]  the rows of kp_sim_contact_forces: A, B = -1, the candidate's distance, pos[3], normal[3], force f_c = sum_k lambda_ck d_ck
+ *     lambda       float [R,64,4]   the multipliers (N) in the edge order above; zero rows past ncon
+ *     resid        float [R,6]      e = r - G lambda: force, moment about the root position, world axes
+ *     net_wrench   float [R,6]      sum of the estimated forces and their torque ABOUT THE WORLD ORIGIN (world axes)
+ *     ncon         int32 [R]        candidates
+ *     info         float [R,8]      cost at lambda = 0, final cost (both in the scaled units: 1/2 r^T W r), Newton iterations, active columns,
+ *                                   |F(e)| at exit (scaled), iterations that needed a line search, 0, status
+ *   status  0 ok; 1: a non-finite input, the row ran nothing and every output row is zero; bit 2: all 64 slots are taken, candidates may have been
+ *           dropped; bit 4: n_iters ran out before the stopping rule held.
+ * A row's result depends on that row alone.  Enqueued on the handle's stream, does not synchronise (the first call with obj_qpos, and one with more rows
+ * than any before, grows the scratch buffer kp_sim_inverse_dynamics uses and waits for the stream once); nothing else the handle stores is read or
+ * written.  n_rows == 0 does nothing.  Refused (-1, kp_last_error names the argument) before anything is launched: null handle / qpos / cfg / out, all
+ * outputs null, n_rows < 0, reach not > 0, w_f, w_m or rho not > 0 or not finite (NaN included), mu < 0, n_iters < 0, a handle whose threads_per_env
+ * is not 64, obj_qpos on a blob without object geoms. */
+typedef struct { float reach, w_f, w_m, rho, mu; int n_iters; } kp_estimate_cfg;
+typedef struct { float *qfrc_inverse, *qfrc_contact, *contact, *lambda, *resid, *net_wrench; int32_t* ncon; float* info; } kp_estimate_out;
+void kp_estimate_cfg_default(const kp_model* model, kp_estimate_cfg* cfg);
+int kp_sim_estimate_contacts(kp_sim*, int n_rows, const float* qpos, const float* qvel, const float* qacc, const float* obj_qpos, const kp_estimate_cfg* cfg, const kp_estimate_out* out);
+
 /* read-outs of the mujoco-py data fields the env uses (humanoid_im.py:342-416, humanoid_ar_v1.py:460-512) */
 typedef enum {
     KP_QPOS = 0,        /* data.qpos[:76]                    [N,76]  */

@@ -39,6 +39,20 @@ def ground_reaction(wrench: torch.Tensor, groups=FOOT_BODIES, min_fz: float = 1.
     return {"force": f, "torque": t, "cop": cop, "free_moment": free, "support": support}
 
 
+def wrench_from_contacts(contact: torch.Tensor) -> torch.Tensor:
+    """Adapter from contact rows to ground_reaction's input: contact [..., 64, 12] (A, B, dist, pos[3], normal[3], force[3], zero rows past ncon; the
+    rows of KpSim.contact_forces, inverse_dynamics and estimate_contacts) -> wrench [..., 26, 6], per entity the sum of the forces on it and of their
+    torques about the world origin.  A row acts on A; where B is an object slot (24 + k) the opposite force acts on it, as contact_forces' wrench
+    counts it.  Rows with a zero force add nothing, so the padding needs no count."""
+    a, b = contact[..., 0].long(), contact[..., 1].long()
+    w = torch.cat([contact[..., 9:12], torch.cross(contact[..., 3:6], contact[..., 9:12], dim=-1)], dim=-1)
+    out = contact.new_zeros(contact.shape[:-2] + (26, 6))
+    out.scatter_add_(-2, a.clamp(0, 25).unsqueeze(-1).expand_as(w), w)
+    on_b = (b >= 24).unsqueeze(-1)
+    out.scatter_add_(-2, b.clamp(0, 25).unsqueeze(-1).expand_as(w), torch.where(on_b, -w, torch.zeros_like(w)))
+    return out
+
+
 def total_mass(model) -> float:
     """mass (kg) of the humanoid: model = a compiled blob's path, the dict read_kpm returns, or anything with a body_mass array"""
     if isinstance(model, str):

@@ -7,6 +7,7 @@
 #include "kp_inverse_dyn.hpp"
 #include "kp_body_motion.hpp"
 #include "kp_fit_pose.hpp"
+#include "kp_contact_estimate.hpp"
 
 namespace kp {
 
@@ -57,6 +58,16 @@ void launch_fit_pose(FitPoseArgs A, hipStream_t stream) {
     for (int r0 = 0; r0 < A.n_rows; r0 += CHUNK) {
         A.row0 = r0;
         hipLaunchKernelGGL(k_fit_pose, dim3(std::min(CHUNK, A.n_rows - r0)), dim3(64), sizeof(EnvLds), stream, A);
+    }
+}
+
+void launch_estimate_contacts(EstimateArgs A, bool obj, hipStream_t stream) {
+    constexpr int CHUNK = 1 << 24;                                      // as launch_inverse_dynamics
+    for (int r0 = 0; r0 < A.n_rows; r0 += CHUNK) {
+        A.row0 = r0;
+        const dim3 grid(std::min(CHUNK, A.n_rows - r0)), block(64);
+        if (obj) hipLaunchKernelGGL((k_estimate_contacts<true>), grid, block, sizeof(EnvLdsObj), stream, A);
+        else hipLaunchKernelGGL((k_estimate_contacts<false>), grid, block, sizeof(EnvLds), stream, A);
     }
 }
 

@@ -1,7 +1,7 @@
 // kp_readout.hpp -- the kernels beside the control step that are built from its device functions (kp_step_device.hpp): impulse pushes (kp_push.hpp,
 // DESIGN.md section 12), the contact-force read-out (kp_contact_force.hpp, section 14) inverse dynamics on motion rows (kp_inverse_dyn.hpp,
 // section 15), body motion, momentum and energy on motion rows (kp_body_motion.hpp, section 16) and point Jacobians and pose fitting on motion rows
-// (kp_fit_pose.hpp, section 17).  They live in their own translation unit (kp_readout.hip): however they specialise the shared device functions, the step kernels' unit
+// (kp_fit_pose.hpp, section 17) and contact forces estimated from kinematics on motion rows (kp_contact_estimate.hpp, section 18).  They live in their own translation unit (kp_readout.hip): however they specialise the shared device functions, the step kernels' unit
 // does not see it, so the step kernels' code cannot move with them.  kp_sim.hip keeps the entry points' argument checks and calls the launchers below.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -79,6 +79,30 @@ struct FitPoseArgs {
     float *qpos, *info, *dq;   // [R, 76], [R, 8], [R, 75] or null
 };
 
+// every pointer optional (kp_estimate_out of the C ABI)
+struct EstimateOut {
+    float *qfrc_inverse;       // [R, 75] need - qfrc_contact; its root part is the residual
+    float *qfrc_contact;       // [R, 75] J^T f of the estimated forces
+    float *contact;            // [R, 64, 12] the rows of kp_sim_contact_forces: B = -1, the candidate's distance, the estimated force
+    float *lambda;             // [R, 64, 4] pyramid-edge multipliers (N), edges n + mu t1, n - mu t1, n + mu t2, n - mu t2
+    float *resid;              // [R, 6] e = r - G lambda: force, moment about the root position (world axes)
+    float *net_wrench;         // [R, 6] sum of the estimated forces, their torque about the WORLD ORIGIN (world axes)
+    int32_t* ncon;             // [R] candidates
+    float *info;               // [R, 8] cost at lambda = 0, final cost, iterations, active columns, |F(e)| at exit, line searches, 0, status
+};
+
+struct EstimateArgs {
+    DevTables T;
+    Params P;                  // the model's with margin = reach and mu = the call's
+    int n_rows, row0;          // as InvDynArgs
+    const float *qpos, *qvel, *qacc;     // [R, 76], [R, 75] or null (zero), [R, 75] or null (zero)
+    const float* geoms;        // OBJ: [R, D_MAXGEOM, 17] world-frame static geoms of the rows
+    const int* ngeom;          // OBJ: [R]
+    float sf, sm, rho_hat;     // sqrt(w_f), sqrt(w_m), rho / w_f
+    int n_iters;
+    EstimateOut O;
+};
+
 // Each enqueues on `stream` and returns; the caller reads the launch status (hipGetLastError).  One wavefront per env / row, full LDS layouts.
 // A: the step kernels' argument pack (state rows, object rows); one block per env
 void launch_apply_impulse(const StepArgs& A, const int32_t* entity, const float* offset, const float* impulse, const uint8_t* mask, float* dqvel, hipStream_t stream);
@@ -91,5 +115,7 @@ void launch_body_motion(BodyMotionArgs A, hipStream_t stream);
 // point Jacobians and pose fitting on rows (kp_fit_pose.hpp, section 17): the first on its own small LDS layout, the second on EnvLds; launches of at most 2^24 rows each
 void launch_point_jacobian(PointJacArgs A, hipStream_t stream);
 void launch_fit_pose(FitPoseArgs A, hipStream_t stream);
+// contact forces estimated from kinematics (kp_contact_estimate.hpp, section 18): obj as launch_inverse_dynamics; launches of at most 2^24 rows each
+void launch_estimate_contacts(EstimateArgs A, bool obj, hipStream_t stream);
 
 }  // namespace kp

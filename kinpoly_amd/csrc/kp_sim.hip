@@ -1830,6 +1830,29 @@ int kp_sim_contact_forces(kp_sim* s, int actuation, const float* act, const uint
     return launched();
 }
 
+// The static geoms of motion rows (kp_sim_inverse_dynamics, kp_sim_estimate_contacts), placed by the kernel kp_sim_set_objects uses (static mode) into the
+// call's scratch: per row the geoms [8,17], then what that kernel stores besides (object block [35], velocities [30], warm start [12], geom count, slots),
+// none of which the callers read.  Stream-ordered: the next call's placement waits for this call's kernel.
+static int place_static_rows(kp_sim* s, int n_rows, const float* obj_qpos, const float** geoms_out, const int** ngeom_out) {
+    constexpr size_t GW = kp::D_MAXGEOM * 17, PER_ROW = GW + 35 + 30 + 6 * kp::D_MAXOBJ + 1 + 1;
+    InvDynScratch& sc = s->idyn;
+    if ((size_t)n_rows > sc.rows) {
+        if (sc.buf) { HIP_OK(hipStreamSynchronize(s->stream)); HIP_OK(hipFree(sc.buf)); sc.buf = nullptr; sc.rows = 0; }
+        HIP_OK(hipMalloc((void**)&sc.buf, sizeof(float) * PER_ROW * (size_t)n_rows));
+        sc.rows = (size_t)n_rows;
+    }
+    const size_t R = (size_t)n_rows;
+    float* geoms = sc.buf; float* oq = geoms + R * GW; float* ov = oq + R * 35; float* ow = ov + R * 30;
+    int* ngeom = (int*)(ow + R * 6 * kp::D_MAXOBJ);
+    signed char* slot = (signed char*)(ngeom + R);
+    static_assert(kp::D_MAXOBJ <= 4, "the slot bytes of a row fit the one word the scratch keeps for them");
+    hipLaunchKernelGGL(k_set_objects, dim3((n_rows + 63) / 64), dim3(64), 0, s->stream, n_rows, obj_qpos, (const uint8_t*)nullptr, oq, geoms, ngeom,
+                       s->obj.d_geoms, s->obj.d_mass, s->obj.n_geoms, s->obj.n_obj, 0, slot, ov, ow, (const int*)nullptr, (const float*)nullptr, (float*)nullptr);
+    HIP_OK(hipGetLastError());
+    *geoms_out = geoms; *ngeom_out = ngeom;
+    return 0;
+}
+
 int kp_sim_inverse_dynamics(kp_sim* s, int n_rows, const float* qpos, const float* qvel, const float* qacc, const float* obj_qpos, const kp_invdyn_out* out) {
     if (!s) return fail("kp_sim_inverse_dynamics: null handle");
     if (n_rows < 0) return fail("kp_sim_inverse_dynamics: n_rows < 0");
@@ -1845,27 +1868,56 @@ int kp_sim_inverse_dynamics(kp_sim* s, int n_rows, const float* qpos, const floa
     A.T = s->T; A.P = s->P; A.n_rows = n_rows;
     A.qpos = qpos; A.qvel = qvel; A.qacc = qacc;
     A.O = kp::InvDynOut{out->qfrc_inverse, out->qfrc_constraint, out->qfrc_bias, out->contact, out->net_wrench, out->ncon};
-    if (obj_qpos) {
-        // the rows' static geoms, placed by the kernel kp_sim_set_objects uses (static mode), into the call's scratch: per row the geoms [8,17], then what
-        // that kernel stores besides (object block [35], velocities [30], warm start [12], geom count, slots), none of which is read here
-        constexpr size_t GW = kp::D_MAXGEOM * 17, PER_ROW = GW + 35 + 30 + 6 * kp::D_MAXOBJ + 1 + 1;
-        InvDynScratch& sc = s->idyn;
-        if ((size_t)n_rows > sc.rows) {
-            if (sc.buf) { HIP_OK(hipStreamSynchronize(s->stream)); HIP_OK(hipFree(sc.buf)); sc.buf = nullptr; sc.rows = 0; }
-            HIP_OK(hipMalloc((void**)&sc.buf, sizeof(float) * PER_ROW * (size_t)n_rows));
-            sc.rows = (size_t)n_rows;
-        }
-        const size_t R = (size_t)n_rows;
-        float* geoms = sc.buf; float* oq = geoms + R * GW; float* ov = oq + R * 35; float* ow = ov + R * 30;
-        int* ngeom = (int*)(ow + R * 6 * kp::D_MAXOBJ);
-        signed char* slot = (signed char*)(ngeom + R);
-        static_assert(kp::D_MAXOBJ <= 4, "the slot bytes of a row fit the one word the scratch keeps for them");
-        hipLaunchKernelGGL(k_set_objects, dim3((n_rows + 63) / 64), dim3(64), 0, s->stream, n_rows, obj_qpos, (const uint8_t*)nullptr, oq, geoms, ngeom,
-                           s->obj.d_geoms, s->obj.d_mass, s->obj.n_geoms, s->obj.n_obj, 0, slot, ov, ow, (const int*)nullptr, (const float*)nullptr, (float*)nullptr);
-        HIP_OK(hipGetLastError());
-        A.geoms = geoms; A.ngeom = ngeom;
-    }
+    if (obj_qpos && place_static_rows(s, n_rows, obj_qpos, &A.geoms, &A.ngeom)) return -1;
     kp::launch_inverse_dynamics(A, obj_qpos != nullptr, s->stream);
+    return launched();
+}
+
+void kp_estimate_cfg_default(const kp_model* m, kp_estimate_cfg* c) {
+    if (!c) return;
+    double mass = 0.0, g = 9.81;
+    if (m) {
+        for (double b : m->h.body_mass) mass += b;
+        g = std::sqrt(m->gravity_x * m->gravity_x + m->gravity_y * m->gravity_y + m->gravity_z * m->gravity_z);
+    }
+    const double bw = mass * g;                     // body weight; without a model (or without gravity) the weights come out non-finite and the call refuses them
+    c->reach = 0.03f;
+    c->w_f = (float)(1.0 / (bw * bw)); c->w_m = (float)(1.0 / (bw * bw));       // 1 / (m g)^2 and 1 / (m g x 1 m)^2
+    c->rho = (float)(1e-3 / (bw * bw));
+    c->mu = 0.f;
+    c->n_iters = 20;
+}
+
+int kp_sim_estimate_contacts(kp_sim* s, int n_rows, const float* qpos, const float* qvel, const float* qacc, const float* obj_qpos, const kp_estimate_cfg* cfg,
+                             const kp_estimate_out* out) {
+    if (!s) return fail("kp_sim_estimate_contacts: null handle");
+    if (n_rows < 0) return fail("kp_sim_estimate_contacts: n_rows < 0");
+    if (!qpos) return fail("kp_sim_estimate_contacts: null qpos");
+    if (!cfg) return fail("kp_sim_estimate_contacts: null cfg");
+    if (!out) return fail("kp_sim_estimate_contacts: null out");
+    if (!out->qfrc_inverse && !out->qfrc_contact && !out->contact && !out->lambda && !out->resid && !out->net_wrench && !out->ncon && !out->info)
+        return fail("kp_sim_estimate_contacts: every output of out is null");
+    // !(x > 0) also refuses a NaN
+    if (!(cfg->reach > 0.f) || !std::isfinite(cfg->reach)) return fail("kp_sim_estimate_contacts: reach must be > 0 and finite");
+    const std::pair<const char*, float> pos[] = {{"w_f", cfg->w_f}, {"w_m", cfg->w_m}, {"rho", cfg->rho}};
+    for (const auto& p : pos)
+        if (!(p.second > 0.f) || !std::isfinite(p.second)) return fail(std::string("kp_sim_estimate_contacts: ") + p.first + " must be > 0 and finite");
+    if (!(cfg->mu >= 0.f) || !std::isfinite(cfg->mu)) return fail("kp_sim_estimate_contacts: mu must be >= 0 and finite (0: the model's)");
+    if (cfg->n_iters < 0) return fail("kp_sim_estimate_contacts: n_iters < 0");
+    if (s->model->threads != 64) return fail("kp_sim_estimate_contacts: needs a handle with threads_per_env = 64");
+    if (obj_qpos && !s->obj.d_geoms) return fail("kp_sim_estimate_contacts: obj_qpos given but the model blob has no object geoms");
+    if (n_rows == 0) return 0;
+    HIP_OK(hipSetDevice(s->device));
+    kp::EstimateArgs A{};
+    A.T = s->T; A.P = s->P; A.n_rows = n_rows;
+    A.P.margin = cfg->reach;                        // the detection distance of the collision pass; everything else is the model's
+    if (cfg->mu > 0.f) A.P.mu = cfg->mu;
+    A.qpos = qpos; A.qvel = qvel; A.qacc = qacc;
+    A.sf = (float)std::sqrt((double)cfg->w_f); A.sm = (float)std::sqrt((double)cfg->w_m); A.rho_hat = (float)((double)cfg->rho / (double)cfg->w_f);
+    A.n_iters = cfg->n_iters;
+    A.O = kp::EstimateOut{out->qfrc_inverse, out->qfrc_contact, out->contact, out->lambda, out->resid, out->net_wrench, out->ncon, out->info};
+    if (obj_qpos && place_static_rows(s, n_rows, obj_qpos, &A.geoms, &A.ngeom)) return -1;
+    kp::launch_estimate_contacts(A, obj_qpos != nullptr, s->stream);
     return launched();
 }
 

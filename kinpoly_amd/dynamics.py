@@ -1,11 +1,16 @@
 """Inverse dynamics of pose sequences (KpSim.inverse_dynamics): finite-difference velocities and accelerations of a motion, the
-root residual wrench, and the plausibility scores built on them.  Torch only; everything but inverse_dynamics_sequence works on CPU tensors too.
+root residual wrench, and the plausibility scores built on them; the same scores with contact forces ESTIMATED from kinematics
+(KpSim.estimate_contacts; DESIGN.md section 18: EstimateConfig, estimate_contacts_sequence, plausibility_estimated).  Torch only; everything but the
+two *_sequence functions works on CPU tensors too.
 
 Coordinates.  qfrc_inverse [., 75] is a generalized force in the model's dof coordinates: entries 0..2 pair with the root's linear velocity (world
 axes), entries 3..5 with its angular velocity, which the free joint expresses in the ROOT's own axes (the motion axes of dofs 3..5 are the columns of
 the root's rotation matrix, taken about the root position; forward_kin_bias in kp_step_kin.hpp), entries 6..74 are the 69 hinge torques in ctrl order.
 """
 from __future__ import annotations
+
+import dataclasses
+import math
 
 import torch
 
@@ -87,6 +92,84 @@ def plausibility(qfrc_inverse: torch.Tensor, qpos: torch.Tensor, qvel: torch.Ten
     out = {"resid_force": f.norm(dim=-1) / weight, "resid_torque": tq.norm(dim=-1), "joint_torque_rms": tau.pow(2).mean(-1).sqrt(),
            "over_limit": (tau.abs() > lim).to(tau.dtype).mean(-1), "power": (tau * qvel[..., 6:]).abs().sum(-1)}
     out["mean"] = {k: v.mean() for k, v in out.items()}
+    return out
+
+
+ESTIMATE_WANT = ("qfrc_inverse", "qfrc_contact", "contact", "lambda", "resid", "net_wrench", "ncon", "info")
+
+
+@dataclasses.dataclass
+class EstimateConfig:
+    """kp_estimate_cfg without a device.  None = the convention of kp_estimate_cfg_default for the model the call runs on:
+    w_f = 1 / (m g)^2, w_m = 1 / (m g x 1 m)^2, rho = 1e-3 w_f.  mu = 0: the model's friction coefficient."""
+    reach: float = 0.03
+    w_f: float | None = None
+    w_m: float | None = None
+    rho: float | None = None
+    mu: float = 0.0
+    n_iters: int = 20
+
+    def __post_init__(self):
+        if not (math.isfinite(self.reach) and self.reach > 0):
+            raise ValueError(f"EstimateConfig: reach must be > 0 and finite, got {self.reach}")
+        for k in ("w_f", "w_m", "rho"):
+            v = getattr(self, k)
+            if v is not None and not (math.isfinite(v) and v > 0):
+                raise ValueError(f"EstimateConfig: {k} must be > 0 and finite, got {v}")
+        if not (math.isfinite(self.mu) and self.mu >= 0):
+            raise ValueError(f"EstimateConfig: mu must be >= 0 and finite, got {self.mu}")
+        if int(self.n_iters) < 0:
+            raise ValueError(f"EstimateConfig: n_iters must be >= 0, got {self.n_iters}")
+
+    def resolved(self, weight: float) -> dict:
+        """every field as a number; weight = m g in N fills the conventions"""
+        if not (math.isfinite(weight) and weight > 0):
+            raise ValueError(f"EstimateConfig: the body weight must be > 0 and finite, got {weight}")
+        w_f = 1.0 / weight ** 2 if self.w_f is None else self.w_f
+        return dict(reach=self.reach, w_f=w_f, w_m=1.0 / weight ** 2 if self.w_m is None else self.w_m, rho=1e-3 * w_f if self.rho is None else self.rho,
+                    mu=self.mu, n_iters=int(self.n_iters))
+
+    def native(self, sim):
+        """the KpEstimateCfg of a KpSim's model: kp_estimate_cfg_default, then the fields given here"""
+        from .sim import KpEstimateCfg
+        c = KpEstimateCfg.default(sim.model)
+        c.reach, c.mu, c.n_iters = self.reach, self.mu, int(self.n_iters)
+        if self.w_f is not None:
+            c.w_f = self.w_f
+            c.rho = 1e-3 * self.w_f                 # the convention follows the weight it is stated in
+        if self.w_m is not None:
+            c.w_m = self.w_m
+        if self.rho is not None:
+            c.rho = self.rho
+        return c
+
+
+def estimate_contacts_sequence(sim, qpos: torch.Tensor, dt: float, obj_qpos: torch.Tensor | None = None, chunk_rows: int = 65536, take_off=None,
+                               cfg: EstimateConfig | None = None, want=ESTIMATE_WANT) -> dict:
+    """KpSim.estimate_contacts over a whole sequence qpos [T, 76] (+ obj_qpos [T, 35]) with motion_derivatives' qvel / qacc (take_off respected: no
+    difference crosses a take boundary), chunk_rows rows per launch.  Returns the kernel's outputs named in `want` for all T rows, plus 'qvel', 'qacc'."""
+    q = qpos.to(sim.device, torch.float32).contiguous()
+    o = None if obj_qpos is None else obj_qpos.to(sim.device, torch.float32).contiguous()
+    qvel, qacc = motion_derivatives(q, dt, take_off)
+    c = (cfg or EstimateConfig()).native(sim)
+    parts = []
+    for a in range(0, q.shape[0], max(int(chunk_rows), 1)):
+        b = a + max(int(chunk_rows), 1)
+        parts.append(sim.estimate_contacts(q[a:b], qvel[a:b].contiguous(), qacc[a:b].contiguous(), None if o is None else o[a:b], cfg=c, want=want))
+    out = {k: torch.cat([p[k] for p in parts]) for k in want} if parts else sim.estimate_contacts(q, qvel, qacc, o, cfg=c, want=want)
+    out["qvel"], out["qacc"] = qvel, qacc
+    return out
+
+
+def plausibility_estimated(est: dict, qpos: torch.Tensor, torque_lim, weight: float) -> dict:
+    """plausibility's scores from the ESTIMATED contact forces: est = estimate_contacts_sequence's dict (qfrc_inverse, qvel, net_wrench, ncon).  The same
+    keys, with the root residual now what no force inside the friction pyramids of the nearby points can supply, plus per row
+        grf           the estimated ground reaction: net contact force [., 3] / weight
+    and under 'mean' also support_share, the fraction of rows with at least one candidate."""
+    out = plausibility(est["qfrc_inverse"], qpos, est["qvel"], torque_lim, weight)
+    out["grf"] = est["net_wrench"][..., :3] / weight
+    out["mean"]["grf"] = out["grf"].reshape(-1, 3).mean(0)
+    out["mean"]["support_share"] = (est["ncon"] > 0).to(est["qfrc_inverse"].dtype).mean()
     return out
 
 

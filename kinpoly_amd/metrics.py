@@ -229,14 +229,20 @@ def coverage_physics_metrics(results: dict, gt: dict, sim, chunk_rows: int = 655
 DYNAMICS_KEYS = ("resid_force", "resid_torque", "torque_rms", "over_limit", "power")
 
 
-def coverage_dynamics_metrics(results: dict, gt: dict, sim, dt=1.0 / 30.0, kpm=None, chunk_rows: int = 65536) -> dict:
+def coverage_dynamics_metrics(results: dict, gt: dict, sim, dt=1.0 / 30.0, kpm=None, chunk_rows: int = 65536, contacts: str = "soft", estimate_cfg=None) -> dict:
     """Dynamics score of pose sequences that were never simulated: inverse dynamics (KpSim.inverse_dynamics on
     dynamics.motion_derivatives' finite differences) of the predicted (`pred`, its first 76 columns) and the ground-truth trajectory of every take of a
     `*_coverage_full.pkl` dict, with the take's object block (`obj_pose` [T, 35], static obstacles) where the pickle has one and sim's blob has object
     geoms.  gt as in coverage_metrics; takes are cut to n = min(len(pred), len(gt qpos)), n >= 3.  kpm: the blob (path or read_kpm dict) whose
     torque_lim and body masses are used; default: the blob sim's model was loaded from.  Per side (pred / gt), means over a take's frames of
     dynamics.plausibility: resid_force_* (root residual force / body weight), resid_torque_* (N m), torque_rms_* (N m), over_limit_* (share of
-    joint-frames beyond torque_lim), power_* (W).  Returns their means over the takes, 'by_action' (the same per action prefix) and 'per_take'."""
+    joint-frames beyond torque_lim), power_* (W).  Returns their means over the takes, 'by_action' (the same per action prefix) and 'per_take'.
+    contacts: "soft" (the default: the soft-constraint contact forces of inverse dynamics, the keys above and nothing else), "estimated" (the contact
+    forces estimated from kinematics, DESIGN.md section 18: the same scores from KpSim.estimate_contacts under the keys `<name>_<side>_est`, plus
+    support_share_<side>_est, the share of frames with a candidate, and grf_z_<side>_est, the estimated vertical ground reaction / body weight) or
+    "both".  estimate_cfg: a dynamics.EstimateConfig (None: the defaults)."""
+    if contacts not in ("soft", "estimated", "both"):
+        raise ValueError(f'coverage_dynamics_metrics: contacts must be "soft", "estimated" or "both", got {contacts!r}')
     import torch
     from . import dynamics
     from .contact import body_weight
@@ -259,7 +265,6 @@ def coverage_dynamics_metrics(results: dict, gt: dict, sim, dt=1.0 / 30.0, kpm=N
         takes.append((k, n))
         for side in (pred[:n], g[:n]):
             q_rows.append(side); o_rows.append(obj); off.append(off[-1] + n)
-    keys = [f"{a}_{b}" for a in DYNAMICS_KEYS for b in ("pred", "gt")]
     if not takes:
         return {"per_take": {}, "by_action": {}}
     if any(o is None for o in o_rows) and not all(o is None for o in o_rows):      # a pickle that mixes takes with and without a block: parked where there is none
@@ -267,12 +272,23 @@ def coverage_dynamics_metrics(results: dict, gt: dict, sim, dt=1.0 / 30.0, kpm=N
         o_rows = [np.tile(park, (len(q), 1)) if o is None else o for q, o in zip(q_rows, o_rows)]
     Q = torch.from_numpy(np.concatenate(q_rows).astype(np.float32))
     Ob = None if o_rows[0] is None else torch.from_numpy(np.concatenate(o_rows).astype(np.float32))
-    out = dynamics.inverse_dynamics_sequence(sim, Q, dt, Ob, chunk_rows, take_off=off, want=("qfrc_inverse",))
-    p = dynamics.plausibility(out["qfrc_inverse"], Q.to(sim.device), out["qvel"], lim, weight)
-    frames = {a: p[b].double().cpu().numpy() for a, b in zip(DYNAMICS_KEYS, ("resid_force", "resid_torque", "joint_torque_rms", "over_limit", "power"))}
+    names = ("resid_force", "resid_torque", "joint_torque_rms", "over_limit", "power")
+    frames, keys = {}, []
+    if contacts in ("soft", "both"):
+        out = dynamics.inverse_dynamics_sequence(sim, Q, dt, Ob, chunk_rows, take_off=off, want=("qfrc_inverse",))
+        p = dynamics.plausibility(out["qfrc_inverse"], Q.to(sim.device), out["qvel"], lim, weight)
+        frames.update({(a, ""): p[b].double().cpu().numpy() for a, b in zip(DYNAMICS_KEYS, names)})
+        keys += [f"{a}_{b}" for a in DYNAMICS_KEYS for b in ("pred", "gt")]
+    if contacts in ("estimated", "both"):
+        est = dynamics.estimate_contacts_sequence(sim, Q, dt, Ob, chunk_rows, take_off=off, cfg=estimate_cfg, want=("qfrc_inverse", "net_wrench", "ncon"))
+        p = dynamics.plausibility_estimated(est, Q.to(sim.device), lim, weight)
+        frames.update({(a, "_est"): p[b].double().cpu().numpy() for a, b in zip(DYNAMICS_KEYS, names)})
+        frames[("support_share", "_est")] = (est["ncon"] > 0).double().cpu().numpy()
+        frames[("grf_z", "_est")] = p["grf"][:, 2].double().cpu().numpy()
+        keys += [f"{a}_{b}_est" for a in DYNAMICS_KEYS + ("support_share", "grf_z") for b in ("pred", "gt")]
     per = {}
     for i, (k, n) in enumerate(takes):
-        per[k] = {f"{a}_{side}": float(frames[a][off[2 * i + j]:off[2 * i + j + 1]].mean()) for a in DYNAMICS_KEYS for j, side in enumerate(("pred", "gt"))}
+        per[k] = {f"{a}_{side}{sfx}": float(fr[off[2 * i + j]:off[2 * i + j + 1]].mean()) for (a, sfx), fr in frames.items() for j, side in enumerate(("pred", "gt"))}
     by_action = {}
     for k, m in per.items():
         by_action.setdefault(k.split("-")[0], []).append(m)
@@ -280,11 +296,11 @@ def coverage_dynamics_metrics(results: dict, gt: dict, sim, dt=1.0 / 30.0, kpm=N
             "by_action": {a: {kk: float(np.mean([m[kk] for m in v])) for kk in keys} for a, v in by_action.items()}, "per_take": per}
 
 
-def write_dynamics_metrics(results: dict, gt: dict, sim, result_dir: str, iter_num: int, data_file: str, dt=1.0 / 30.0) -> dict:
-    """coverage_dynamics_metrics as `<result_dir>/dynamics_metrics_<iter>_<data_file>.json`; returns them"""
+def write_dynamics_metrics(results: dict, gt: dict, sim, result_dir: str, iter_num: int, data_file: str, dt=1.0 / 30.0, contacts: str = "soft") -> dict:
+    """coverage_dynamics_metrics as `<result_dir>/dynamics_metrics_<iter>_<data_file>.json`; returns them.  contacts: "soft" | "estimated" | "both"."""
     import json
     import os
-    m = coverage_dynamics_metrics(results, gt, sim, dt)
+    m = coverage_dynamics_metrics(results, gt, sim, dt, contacts=contacts)
     os.makedirs(result_dir, exist_ok=True)
     with open(os.path.join(result_dir, f"dynamics_metrics_{iter_num}_{data_file}.json"), "w") as f:
         json.dump(m, f, indent=1)

@@ -184,6 +184,32 @@ class KpFitOut(C.Structure):
 FIT_INFO = {"cost0": 0, "cost": 1, "accepted": 2, "mu": 3, "max_epos": 4, "max_erot": 5, "dq_inf": 6, "status": 7}
 
 
+class KpEstimateCfg(C.Structure):
+    """mirror of kp_estimate_cfg (host side): the candidates' reach, the weights of the residual force / moment, the multiplier penalty, the friction
+    coefficient (0: the model's) and the Newton iterations of kp_sim_estimate_contacts"""
+    _fields_ = [(k, C.c_float) for k in ("reach", "w_f", "w_m", "rho", "mu")] + [("n_iters", C.c_int)]
+
+    @classmethod
+    def default(cls, model):
+        """kp_estimate_cfg_default for a KpModel: reach 0.03 m, w_f = 1 / (m g)^2, w_m = 1 / (m g x 1 m)^2, rho = 1e-3 w_f, mu 0, n_iters 20"""
+        c = cls()
+        load_library().kp_estimate_cfg_default(model.h, C.byref(c))
+        return c
+
+
+class KpEstimateOut(C.Structure):
+    """mirror of kp_estimate_out: the device arrays kp_sim_estimate_contacts fills (each may be NULL, not all)"""
+    _fields_ = [(k, C.c_void_p) for k in ("qfrc_inverse", "qfrc_contact", "contact", "lambda", "resid", "net_wrench", "ncon", "info")]
+
+
+# outputs of KpSim.estimate_contacts: name -> (trailing shape, dtype), in kp_estimate_out's order
+ESTIMATE_OUTPUTS = {"qfrc_inverse": ((75,), torch.float32), "qfrc_contact": ((75,), torch.float32), "contact": ((64, 12), torch.float32),
+                    "lambda": ((64, 4), torch.float32), "resid": ((6,), torch.float32), "net_wrench": ((6,), torch.float32), "ncon": ((), torch.int32),
+                    "info": ((8,), torch.float32)}
+# the columns of an info row: name -> index; status: 0 ok, 1 non-finite input (zero rows), bit 2 possibly truncated (64 candidates), bit 4 not converged
+ESTIMATE_INFO = {"cost0": 0, "cost": 1, "iters": 2, "active": 3, "f_norm": 4, "searches": 5, "reserved": 6, "status": 7}
+
+
 class KinPolyNativeError(RuntimeError):
     pass
 
@@ -207,6 +233,8 @@ _SIGNATURES = {
     "kp_sim_point_jacobian": (_I, [_V, _I, _V, _V, _V, _V]),      # handle, n_rows, qpos, body, offset, J
     "kp_fit_cfg_default": (None, [C.POINTER(KpFitCfg)]),
     "kp_sim_fit_pose": (_I, [_V, _I, _V, _V, _V]),      # handle, n_rows, kp_fit_in*, kp_fit_cfg*, kp_fit_out*
+    "kp_estimate_cfg_default": (None, [_V, C.POINTER(KpEstimateCfg)]),
+    "kp_sim_estimate_contacts": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]),      # handle, n_rows, qpos, qvel, qacc, obj_qpos, kp_estimate_cfg*, kp_estimate_out*
     "kp_sim_fk": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]), "kp_sim_fk_backward": (_I, [_V, _I, _V, _V, _V, _V, _V]),
     "kp_sim_pose_contacts": (_I, [_V, _I, _V, _V, _V, _F, _V, _V, _V]),
     # the offscreen renderer (kp_render.hip); kp_model_hull_planes is host only
@@ -562,6 +590,34 @@ class KpSim:
         if R > 0:                # no rows: nothing to launch (and an empty tensor has no address to hand over)
             _check(self.L.kp_sim_inverse_dynamics(self.h, R, *[p for _, p in ins], C.byref(st)), "kp_sim_inverse_dynamics")
         return {k: v.view(lead + INVDYN_OUTPUTS[k][0]) for k, v in out.items()}
+
+    def estimate_contacts(self, qpos, qvel=None, qacc=None, obj_qpos=None, cfg: KpEstimateCfg | None = None, want=("qfrc_inverse",)) -> dict:
+        """Contact forces estimated from kinematics (kp_sim_estimate_contacts): the forces inside the friction pyramids of the points within cfg.reach of
+        a surface that best explain the rows' root residual.  Inputs as inverse_dynamics: qpos [..., 76], qvel / qacc [..., 75] or None (zeros), obj_qpos
+        [..., 35] or None, any leading shape.  cfg: a KpEstimateCfg (None: KpEstimateCfg.default(self.model)).  want: names of ESTIMATE_OUTPUTS.
+        Returns a dict of device tensors with that leading shape: qfrc_inverse, qfrc_contact [..., 75]; contact [..., 64, 12] (contact_forces' rows,
+        B = -1, the estimated force); lambda [..., 64, 4]; resid [..., 6] (force, moment about the root position, world axes); net_wrench [..., 6] (about
+        the world origin); ncon int32 [...]; info [..., 8] (ESTIMATE_INFO).  Nothing the handle stores is read or changed."""
+        want = tuple(want)
+        bad = [k for k in want if k not in ESTIMATE_OUTPUTS]
+        if bad or not want:
+            raise ValueError(f"estimate_contacts: want must name some of {tuple(ESTIMATE_OUTPUTS)}, got {want}")
+        if qpos.dim() < 1 or qpos.shape[-1] != NQ:
+            raise ValueError(f"estimate_contacts: qpos must be [..., {NQ}], got {tuple(qpos.shape)}")
+        lead = tuple(qpos.shape[:-1])
+        R = int(np.prod(lead, dtype=np.int64))
+        ptrs = []
+        for name, t, dim in (("qpos", qpos, NQ), ("qvel", qvel, NV), ("qacc", qacc, NV), ("obj_qpos", obj_qpos, 35)):
+            if t is not None and tuple(t.shape) != lead + (dim,):
+                raise ValueError(f"estimate_contacts: {name} must be {lead + (dim,)}, got {tuple(t.shape)}")
+            ptrs.append((name, None if t is None else t.reshape(R, dim), dim))
+        cfg = KpEstimateCfg.default(self.model) if cfg is None else cfg
+        out = {k: torch.empty((R, *ESTIMATE_OUTPUTS[k][0]), dtype=ESTIMATE_OUTPUTS[k][1], device=self.device) for k in want}
+        if R > 0:                # no rows: nothing to launch (and an empty tensor has no address to hand over)
+            st = KpEstimateOut(*[_dev(k, out.get(k), (R, *ESTIMATE_OUTPUTS[k][0]), ESTIMATE_OUTPUTS[k][1]) for k in ESTIMATE_OUTPUTS])
+            ins = [_dev("estimate_contacts: " + k, t, (R, d)) for k, t, d in ptrs]
+            _check(self.L.kp_sim_estimate_contacts(self.h, R, *ins, C.byref(cfg), C.byref(st)), "kp_sim_estimate_contacts")
+        return {k: v.view(lead + ESTIMATE_OUTPUTS[k][0]) for k, v in out.items()}
 
     def body_motion(self, qpos, qvel=None, qacc=None, outputs=tuple(MOTION_OUTPUTS)) -> dict:
         """Body velocities and accelerations, momentum and energy of motion rows (kp_sim_body_motion): qpos [..., 76], qvel / qacc [..., 75] or None

@@ -44,6 +44,9 @@ def build_parser():
     ap.add_argument("--dynamics_metrics", action="store_true", help="with --data: inverse dynamics of the predicted and the ground-truth poses (root residual "
                     "force / body weight, residual torque, joint torque rms, share over torque_lim, power; pred and gt) printed and written to "
                     "dynamics_metrics_<iter>_<data>.json; off: every output is what it is without the flag")
+    ap.add_argument("--dynamics_contacts", choices=("soft", "estimated", "both"), default="soft", help="with --dynamics_metrics: the contact forces the score "
+                    "credits: soft (the soft-constraint forces of inverse dynamics), estimated (forces inside the friction cones of the points near a "
+                    "surface that best explain the root residual; keys *_est of the same json) or both")
     ap.add_argument("--balance_metrics", action="store_true", help="with --data: balance of the predicted and the ground-truth poses (margins of the centre of "
                     "mass, the capture point and the zero-moment point to the support polygon, stable / airborne share; pred and gt) printed and written to "
                     "balance_metrics_<iter>_<data>.json; off: every output is what it is without the flag")
@@ -165,7 +168,7 @@ def main():
             print("".join(f"{k}:{v:.3f} \t " for k, v in pm.items() if k not in ("per_take", "succ_by_action")))
             print({k: round(v, 3) for k, v in pm["succ_by_action"].items()})
         if args.dynamics_metrics:                   # inverse dynamics of poses that were never simulated (kinematic target and ground truth), on the run's scene
-            dm = M.write_dynamics_metrics(res, gt, kpsim.KpSim(env.model, 1, 0), args.result_dir, args.iter, data_file)
+            dm = M.write_dynamics_metrics(res, gt, kpsim.KpSim(env.model, 1, 0), args.result_dir, args.iter, data_file, contacts=args.dynamics_contacts)
             print("".join(f"{k}:{v:.4f} \t " for k, v in dm.items() if k not in ("per_take", "by_action")))
         if args.balance_metrics:                    # balance of the same poses, floor scene
             bm = M.write_balance_metrics(res, gt, kpsim.KpSim(env.model, 1, 0), args.result_dir, args.iter, data_file)

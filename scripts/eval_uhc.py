@@ -53,6 +53,9 @@ def build_parser():
     p.add_argument("--dynamics_metrics", action="store_true", help="inverse dynamics of the simulated (pred) and the expert (gt) poses of every take (root "
                    "residual force / body weight, residual torque, joint torque rms, share over torque_lim, power) printed and written to "
                    "dynamics_metrics_<iter>_<data>.json; off: every output file is what it is without the flag")
+    p.add_argument("--dynamics_contacts", choices=("soft", "estimated", "both"), default="soft", help="with --dynamics_metrics: the contact forces the score "
+                   "credits: soft (the soft-constraint forces of inverse dynamics), estimated (forces inside the friction cones of the points near a "
+                   "surface that best explain the root residual; keys *_est of the same json) or both")
     p.add_argument("--balance_metrics", action="store_true", help="balance of the simulated (pred) and the expert (gt) poses of every take (margins of the "
                    "centre of mass, the capture point and the zero-moment point to the support polygon, stable / airborne share) printed and written to "
                    "balance_metrics_<iter>_<data>.json; off: every output file is what it is without the flag")
@@ -122,7 +125,7 @@ def main(argv=None):
     if args.dynamics_metrics:          # a dynamics score of the expert takes themselves (gt) beside the simulated states (pred): floor scene, rows API of the env's handle
         from kinpoly_amd import metrics as M
         gt = {k: {"qpos": np.asarray(r["gt"])} for k, r in res.items()}
-        dm = M.write_dynamics_metrics(res, gt, env.sim, out_dir, args.iter, args.data, dt=env.dt)
+        dm = M.write_dynamics_metrics(res, gt, env.sim, out_dir, args.iter, args.data, dt=env.dt, contacts=args.dynamics_contacts)
         print("".join(f"{k}:{v:.4f} \t " for k, v in dm.items() if k not in ("per_take", "by_action")))
     if args.balance_metrics:           # the same for balance: floor scene, rows API of the env's handle
         from kinpoly_amd import metrics as M

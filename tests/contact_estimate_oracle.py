@@ -1,0 +1,277 @@
+"""fp64 reference of the contact-force estimate (kp_sim_estimate_contacts), on top of OracleSim: test infrastructure.
+
+For a state (qpos, qvel, optional object block whose unparked objects are STATIC geoms) and a given qacc:
+  * forward pass (fullM, qfrc_bias, contact Jacobian rows) from an OracleSim whose blob carries margin = reach, so its collision pass yields the
+    candidates: the oracle's own pair order, plane-mesh rule and MPR query at that detection distance;
+  * the tangent frame of a normal, written out here (mju_makeFrame: the rule of contact_frame in kp_step_args.hpp);
+  * G, r and W as include/kinpoly_sim.h states them;
+  * the minimiser by scipy.optimize.lsq_linear on the augmented system [W^1/2 G; sqrt(rho) I] lambda ~ [W^1/2 r; 0], lambda >= 0, polished by one exact
+    solve on its active set (lsq_linear stops at a tolerance; the KKT identity of test (a) wants 1e-10).
+"""
+import os
+
+import numpy as np
+from scipy.optimize import lsq_linear
+
+import contact_force_oracle as CF
+import inverse_dynamics_oracle as ID
+from kinpoly_amd.model_compiler import read_kpm, write_kpm
+
+NV = 75
+REACH, N_ITERS = 0.03, 20
+
+
+def default_cfg(kpm):
+    """kp_estimate_cfg_default's conventions from the blob's masses and gravity"""
+    bw = float(kpm["body_mass"].sum()) * float(np.linalg.norm(kpm["opt"][1:4]))
+    return dict(reach=REACH, w_f=1.0 / bw ** 2, w_m=1.0 / bw ** 2, rho=1e-3 / bw ** 2, mu=0.0, n_iters=N_ITERS)
+
+
+def f32_cfg(cfg):
+    """the values the kernel receives: the C struct holds floats"""
+    return {k: (v if k == "n_iters" else float(np.float32(v))) for k, v in cfg.items()}
+
+
+_REACH_BLOBS = {}
+
+
+def reach_blob(kpm_path, reach, tmpdir):
+    """a copy of the blob with the contact margin set to `reach` (nothing else changes) -> its path"""
+    key = (kpm_path, float(reach), str(tmpdir))
+    if key not in _REACH_BLOBS:
+        m = read_kpm(kpm_path)
+        opt = np.array(m["opt"], dtype=m["opt"].dtype); opt[ID.MARGIN_OPT] = reach
+        m["opt"] = opt
+        out = os.path.join(str(tmpdir), f"reach_{len(_REACH_BLOBS)}_{os.path.basename(kpm_path)}")
+        write_kpm(m, out)
+        _REACH_BLOBS[key] = out
+    return _REACH_BLOBS[key]
+
+
+def make_frame(n):
+    """rows n, t1, t2 for a unit normal: t1 = the y axis (the z axis when |n_y| >= 0.5) made orthogonal to n and normalised, t2 = n x t1"""
+    n = np.asarray(n, float)
+    y = np.array([0.0, 1.0, 0.0]) if abs(n[1]) < 0.5 else np.array([0.0, 0.0, 1.0])
+    y = y - n.dot(y) * n
+    y = y / np.linalg.norm(y)
+    return np.stack([n, y, np.cross(n, y)])
+
+
+def quat_matrix(q):
+    w, x, y, z = np.asarray(q, float) / np.linalg.norm(q)
+    return np.array([[w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), w * w - x * x + y * y - z * z, 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z]])
+
+
+def edges(frame, mu):
+    """the four pyramid edges of a frame, in the kernel's column order"""
+    n, t1, t2 = frame
+    return np.stack([n + mu * t1, n - mu * t1, n + mu * t2, n - mu * t2])
+
+
+def build_G(pos, normal, x_root, mu):
+    """G [6, 4 C]: columns [d_ck; (p_c - x_root) x d_ck]"""
+    cols = []
+    for p, n in zip(pos, normal):
+        for d in edges(make_frame(n), mu):
+            cols.append(np.concatenate([d, np.cross(np.asarray(p, float) - x_root, d)]))
+    return np.array(cols).T.reshape(6, -1) if cols else np.zeros((6, 0))
+
+
+def minimise(G, r, w_f, w_m, rho):
+    """the unique minimiser of 1/2 (r - G lam)^T W (r - G lam) + 1/2 rho |lam|^2 over lam >= 0 -> (lam, e = r - G lam)"""
+    n = G.shape[1]
+    if n == 0:
+        return np.zeros(0), r.copy()
+    sw = np.sqrt(np.array([w_f] * 3 + [w_m] * 3))
+    A = np.vstack([sw[:, None] * G, np.sqrt(rho) * np.eye(n)])
+    b = np.concatenate([sw * r, np.zeros(n)])
+    sc = 1.0 / np.sqrt(w_f)                      # lam in units of sqrt(1 / w_f) (body weights with the default weights): a well-scaled problem for the solver
+    res = lsq_linear(A * sc, b, bounds=(0.0, np.inf), method="bvls", tol=1e-15, max_iter=100 * n + 100)
+    lam = res.x * sc
+    # polish: the exact solve on the active set the solver found, accepted only where it stays a KKT point
+    act = lam > 0
+    for _ in range(50):
+        la = np.zeros(n)
+        if act.any():
+            la[act] = np.linalg.lstsq(A[:, act], b, rcond=None)[0]
+        e = r - G @ la
+        z = G.T @ (np.array([w_f] * 3 + [w_m] * 3) * e)
+        new = (la > 0) & act | (~act & (z > 0))
+        if (new == act).all() and (la[act] >= 0).all():
+            lam = la
+            break
+        act = new
+    return lam, r - G @ lam
+
+
+def prepared(kpm_path, reach, tmpdir, qpos, qvel, blk=None):
+    """OracleSim on the blob with margin = reach holding the state (ID.prepared: static geoms, no actuation, forward() done) -> (o, kpm dict)"""
+    path = reach_blob(kpm_path, reach, tmpdir)
+    kpm = read_kpm(path)
+    return ID.prepared(path, kpm, qpos, qvel, blk), kpm
+
+
+def point_jacobians(o, mu_model):
+    """per candidate the translational Jacobian rows (n, t1, t2) . J_p [3, 75], recovered from the oracle's pyramid rows (n +- mu t1) J_p, (n +- mu t2) J_p"""
+    _, _, _, J = o.efc()
+    con = o.contacts_full()
+    C = len(con["body"])
+    Jc = J[len(J) - 4 * C:].reshape(C, 4, NV)
+    return np.stack([(Jc[:, 0] + Jc[:, 1]) / 2, (Jc[:, 0] - Jc[:, 1]) / (2 * mu_model), (Jc[:, 2] - Jc[:, 3]) / (2 * mu_model)], 1) if C else np.zeros((0, 3, NV))
+
+
+def estimate(o, kpm, qacc, cfg):
+    """the reference estimate at `qacc` [75] from what forward() left in `o` (prepared above).  Returns dict(resid [6], qfrc_inverse, qfrc_contact, need
+    [75], contacts, force [C, 3], lam [C, 4], net_wrench [6], ncon, G, r, x_root, R_root, mu)."""
+    qacc = np.asarray(qacc, float)
+    mu_model = float(kpm["opt"][11])
+    mu = cfg["mu"] if cfg["mu"] > 0 else mu_model
+    need = o.fullM() @ qacc + o.get("qfrc_bias")
+    q = o.get("qpos")
+    x_root, R = q[:3].copy(), quat_matrix(q[3:7])
+    r = np.concatenate([need[:3], R @ need[3:6]])
+    con = o.contacts_full()
+    C = len(con["body"])
+    G = build_G(con["pos"], con["normal"], x_root, mu)
+    lam, e = minimise(G, r, cfg["w_f"], cfg["w_m"], cfg["rho"])
+    lam = lam.reshape(C, 4)
+    force = np.array([lam[c] @ edges(make_frame(con["normal"][c]), mu) for c in range(C)]).reshape(C, 3)
+    Jp = point_jacobians(o, mu_model)
+    qc = np.zeros(NV)
+    net = np.zeros(6)
+    for c in range(C):
+        fr = make_frame(con["normal"][c])
+        qc += Jp[c].T @ (fr @ force[c])                                  # frame components of f_c on the frame's Jacobian rows
+        net[:3] += force[c]; net[3:] += np.cross(con["pos"][c], force[c])
+    return dict(resid=e, qfrc_inverse=need - qc, qfrc_contact=qc, need=need, contacts=con, force=force, lam=lam, net_wrench=net, ncon=C, G=G, r=r,
+                x_root=x_root, R_root=R, mu=mu)
+
+
+def kkt_defect(ref, cfg):
+    """|lam - max(0, G^T W e) / rho|_inf relative to max(|lam|_inf, tiny)"""
+    if ref["ncon"] == 0:
+        return 0.0
+    W = np.array([cfg["w_f"]] * 3 + [cfg["w_m"]] * 3)
+    lam = ref["lam"].reshape(-1)
+    want = np.maximum(0.0, ref["G"].T @ (W * ref["resid"])) / cfg["rho"]
+    return float(np.abs(lam - want).max() / max(np.abs(lam).max(), 1e-300))
+
+
+def hull2d(pts):
+    """convex hull (monotone chain) of 2-D points -> vertices counter-clockwise"""
+    pts = sorted(map(tuple, np.round(np.asarray(pts, float), 12)))
+    if len(pts) <= 2:
+        return np.array(pts)
+    def half(seq):
+        h = []
+        for p in seq:
+            while len(h) >= 2 and (h[-1][0] - h[-2][0]) * (p[1] - h[-2][1]) - (h[-1][1] - h[-2][1]) * (p[0] - h[-2][0]) <= 0:
+                h.pop()
+            h.append(p)
+        return h[:-1]
+    return np.array(half(pts) + half(pts[::-1]))
+
+
+def inside_hull2d(hull, p, slack=0.0):
+    """p inside the counter-clockwise polygon `hull`, up to `slack` metres outside"""
+    if len(hull) < 3:
+        return False
+    for a, b in zip(hull, np.roll(hull, -1, axis=0)):
+        ed = b - a
+        if (ed[0] * (p[1] - a[1]) - ed[1] * (p[0] - a[0])) / max(np.linalg.norm(ed), 1e-300) < -slack:
+            return False
+    return True
+
+
+def com_xy(kpm, qpos):
+    """ground projection of the centre of mass at qpos (oracle FK)"""
+    from oracle import np_oracle as O
+    fk = O.qpos_fk(qpos, kpm["body_pos"].reshape(24, 3), kpm["body_ipos"].reshape(24, 3), kpm["body_parent"])
+    m = np.asarray(kpm["body_mass"], float)
+    return (m[:, None] * fk["body_com"].reshape(24, 3)).sum(0)[:2] / m.sum()
+
+
+def named_states(kpm_floor, kpm_step, std_qpos, std_qvel):
+    """The issue's named states with fp32-representable values: standing, lifted 2 cm, airborne (1 m up), lying, deep squat, g_sit with the static chair.
+    list of dict(name, q, v, blk, step)."""
+    fl = CF.floor_states(kpm_floor, std_qpos, std_qvel)
+    # standing: the model's zero pose (every hinge at 0, arms out) upright, set down where its lowest hull vertex is 0.2 mm in the floor, the depth at which
+    # a floor of 4e6 N/m carries the body weight.  Its soles are flat and level to 3 mm, so both feet stay within the reach when the pose is lifted (the
+    # golden standing pose stands 2 cm deep, one foot 8 mm above the other and pitched: lifted 2 cm it keeps one foot's candidates only).  lifted: the same
+    # pose 2 cm higher, clear of the model's 1 mm margin.
+    q = np.zeros(76); q[3:7] = [0.0, 0.0, np.sqrt(0.5), np.sqrt(0.5)]
+    q[:2] = std_qpos[:2]
+    q[2] = -0.0002 - CF.hull_world_verts(kpm_floor, q, range(24))[:, 2].min()
+    out = [dict(name="standing", q=ID.f32(q), v=np.zeros(75), blk=None, step=False)]
+    q = q.copy(); q[2] += 0.02
+    out.append(dict(name="lifted_2cm", q=ID.f32(q), v=np.zeros(75), blk=None, step=False))
+    out.append(dict(name="airborne", q=ID.f32(fl["c_airborne"][0]), v=ID.f32(fl["c_airborne"][1]), blk=None, step=False))
+    out.append(dict(name="lying", q=ID.f32(fl["d_lying"][0]), v=np.zeros(75), blk=None, step=False))
+    # deep squat: hips and knees flexed, ankles dorsiflexed; the lowest hull vertex 1 mm into the floor
+    q = np.array(std_qpos, float)
+    for hip, knee, ankle in ((0, 1, 2), (4, 5, 6)):
+        q[7 + 3 * hip + 2] = -1.9; q[7 + 3 * knee + 2] = 2.2; q[7 + 3 * ankle + 2] = -0.5
+    q[2] = 0.0
+    q[2] = -0.001 - CF.hull_world_verts(kpm_floor, q, range(24))[:, 2].min()
+    out.append(dict(name="deep_squat", q=ID.f32(q), v=np.zeros(75), blk=None, step=False))
+    g = ID.named_states(kpm_floor, kpm_step, std_qpos, std_qvel)[-1]
+    out.append(dict(name="g_sit", q=g["q"], v=g["v"], blk=g["blk"], step=True))
+    return out
+
+
+def on_edge(o, kpm, ref, reach):
+    """Edge classification of a case: the fp32 kernel may legitimately land on the other side of a switch when a candidate's distance lies within 1e-5 of
+    `reach` (a candidate about to appear or vanish), or two vertices of a touching hull tie in depth to 1e-6 (the plane-mesh rule may pick the other
+    one), as inverse_dynamics_oracle.on_edge classifies."""
+    con = ref["contacts"]
+    if len(con["dist"]) and np.any(np.abs(con["dist"] - reach) < 1e-5):
+        return True
+    q = o.get("qpos")
+    for b in range(24):
+        z = np.sort(CF.hull_world_verts(kpm, q, (b,))[:, 2])
+        if z[0] <= reach + 1e-5 and len(z) > 1 and z[1] - z[0] < 1e-6:
+            return True
+    return False
+
+
+# ---------------------------------------------------------------- cases: (state, qacc) with the reference, computed once per process
+
+SWEEP_SEEDS = tuple(range(1000, 1064))       # the 64 falling states of the GPU sweep (inverse_dynamics_oracle.falling_state)
+_CASES, _TMP = {}, []
+
+
+def _tmpdir():
+    if not _TMP:
+        import atexit
+        import shutil
+        import tempfile
+        _TMP.append(tempfile.mkdtemp(prefix="kp_estimate_"))
+        atexit.register(shutil.rmtree, _TMP[0], ignore_errors=True)
+    return _TMP[0]
+
+
+def cases(scene, kpm_paths, std_qpos, std_qvel, cfg):
+    """list of dict(name, q, v, a, blk, ref, edge); scene: floor | g_sit | sweep; kpm_paths = (floor blob, object blob).  Inputs are fp32-representable;
+    the three accelerations of a state are inverse_dynamics_oracle.qacc_choices' (zero, the state's forward qacc at the model's own margin, seeded
+    N(0, 30^2)); ref = estimate() on them."""
+    if scene in _CASES:
+        return _CASES[scene]
+    kf, ks = read_kpm(kpm_paths[0]), read_kpm(kpm_paths[1])
+    if scene == "sweep":
+        sts = [dict(name=f"sweep_{seed}", q=ID.f32(q), v=ID.f32(v), blk=None, step=False) for seed in SWEEP_SEEDS for q, v in [ID.falling_state(kf, std_qpos, seed)]]
+    else:
+        named = named_states(kf, ks, std_qpos, std_qvel)
+        sts = named[:-1] if scene == "floor" else named[-1:]
+    out = []
+    for s in sts:
+        path = kpm_paths[1] if s["step"] else kpm_paths[0]
+        fwd = ID.prepared(path, ks if s["step"] else kf, s["q"], s["v"], s["blk"])
+        o, kpm = prepared(path, cfg["reach"], _tmpdir(), s["q"], s["v"], s["blk"])
+        for k, a in ID.qacc_choices(fwd, s["name"]).items():
+            a = ID.f32(a)
+            ref = estimate(o, kpm, a, cfg)
+            out.append(dict(name=f"{s['name']}/{k}", q=s["q"], v=s["v"], a=a, blk=s["blk"], ref=ref, edge=on_edge(o, kpm, ref, cfg["reach"])))
+    _CASES[scene] = out
+    return out
