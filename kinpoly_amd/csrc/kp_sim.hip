@@ -1830,6 +1830,38 @@ int kp_sim_contact_forces(kp_sim* s, int actuation, const float* act, const uint
     return launched();
 }
 
+// ---- the rows tools: read-only kernels on motion rows the caller passes, one wavefront per row.  rows_begin is the preamble of
+// their entry points: the handle and n_rows, then own() -- the entry point's checks of its own arguments, 0 or fail's -1 -- then what the handle must
+// offer; every refusal comes before the first HIP call.  Returns -1: refused; 0: no rows, nothing to do; 1: go -- the device is set and A.T / A.P /
+// A.n_rows are filled.  obj_given: the call carries obj_qpos.  (A generic lambda: this part of the file has C linkage, which a template cannot have.)
+static const auto rows_begin = [](const char* who, kp_sim* s, int n_rows, bool obj_given, auto& A, auto own) -> int {
+    const auto no = [who](const char* what) { return fail(std::string(who) + ": " + what); };
+    if (!s) return no("null handle");
+    if (n_rows < 0) return no("n_rows < 0");
+    if (own()) return -1;
+    if (s->model->threads != 64) return no("needs a handle with threads_per_env = 64");
+    if (obj_given && !s->obj.d_geoms) return no("obj_qpos given but the model blob has no object geoms");
+    if (n_rows == 0) return 0;
+    HIP_OK(hipSetDevice(s->device));
+    A.T = s->T; A.P = s->P; A.n_rows = n_rows;
+    return 1;
+};
+
+// the first null among named arguments: "<who>: null <name>"
+static int refuse_null(const char* who, std::initializer_list<std::pair<const char*, const void*>> args) {
+    for (const auto& a : args)
+        if (!a.second) return fail(std::string(who) + ": null " + a.first);
+    return 0;
+}
+
+// named floats that must be > 0 (!(x > 0) also refuses a NaN) and, where `finite`, not +inf either
+static int refuse_not_positive(const char* who, std::initializer_list<std::pair<const char*, float>> fields, bool finite) {
+    for (const auto& f : fields)
+        if (!(f.second > 0.f) || (finite && !std::isfinite(f.second)))
+            return fail(std::string(who) + ": " + f.first + " must be > 0" + (finite ? " and finite" : ""));
+    return 0;
+}
+
 // The static geoms of motion rows (kp_sim_inverse_dynamics, kp_sim_estimate_contacts), placed by the kernel kp_sim_set_objects uses (static mode) into the
 // call's scratch: per row the geoms [8,17], then what that kernel stores besides (object block [35], velocities [30], warm start [12], geom count, slots),
 // none of which the callers read.  Stream-ordered: the next call's placement waits for this call's kernel.
@@ -1854,18 +1886,15 @@ static int place_static_rows(kp_sim* s, int n_rows, const float* obj_qpos, const
 }
 
 int kp_sim_inverse_dynamics(kp_sim* s, int n_rows, const float* qpos, const float* qvel, const float* qacc, const float* obj_qpos, const kp_invdyn_out* out) {
-    if (!s) return fail("kp_sim_inverse_dynamics: null handle");
-    if (n_rows < 0) return fail("kp_sim_inverse_dynamics: n_rows < 0");
-    if (!qpos) return fail("kp_sim_inverse_dynamics: null qpos");
-    if (!out) return fail("kp_sim_inverse_dynamics: null out");
-    if (!out->qfrc_inverse && !out->qfrc_constraint && !out->qfrc_bias && !out->contact && !out->net_wrench && !out->ncon)
-        return fail("kp_sim_inverse_dynamics: every output of out is null");
-    if (s->model->threads != 64) return fail("kp_sim_inverse_dynamics: needs a handle with threads_per_env = 64");
-    if (obj_qpos && !s->obj.d_geoms) return fail("kp_sim_inverse_dynamics: obj_qpos given but the model blob has no object geoms");
-    if (n_rows == 0) return 0;
-    HIP_OK(hipSetDevice(s->device));
+    const char* who = "kp_sim_inverse_dynamics";
     kp::InvDynArgs A{};
-    A.T = s->T; A.P = s->P; A.n_rows = n_rows;
+    const int go = rows_begin(who, s, n_rows, obj_qpos != nullptr, A, [&] {
+        if (refuse_null(who, {{"qpos", qpos}, {"out", out}})) return -1;
+        if (!out->qfrc_inverse && !out->qfrc_constraint && !out->qfrc_bias && !out->contact && !out->net_wrench && !out->ncon)
+            return fail("kp_sim_inverse_dynamics: every output of out is null");
+        return 0;
+    });
+    if (go <= 0) return go;
     A.qpos = qpos; A.qvel = qvel; A.qacc = qacc;
     A.O = kp::InvDynOut{out->qfrc_inverse, out->qfrc_constraint, out->qfrc_bias, out->contact, out->net_wrench, out->ncon};
     if (obj_qpos && place_static_rows(s, n_rows, obj_qpos, &A.geoms, &A.ngeom)) return -1;
@@ -1890,26 +1919,18 @@ void kp_estimate_cfg_default(const kp_model* m, kp_estimate_cfg* c) {
 
 int kp_sim_estimate_contacts(kp_sim* s, int n_rows, const float* qpos, const float* qvel, const float* qacc, const float* obj_qpos, const kp_estimate_cfg* cfg,
                              const kp_estimate_out* out) {
-    if (!s) return fail("kp_sim_estimate_contacts: null handle");
-    if (n_rows < 0) return fail("kp_sim_estimate_contacts: n_rows < 0");
-    if (!qpos) return fail("kp_sim_estimate_contacts: null qpos");
-    if (!cfg) return fail("kp_sim_estimate_contacts: null cfg");
-    if (!out) return fail("kp_sim_estimate_contacts: null out");
-    if (!out->qfrc_inverse && !out->qfrc_contact && !out->contact && !out->lambda && !out->resid && !out->net_wrench && !out->ncon && !out->info)
-        return fail("kp_sim_estimate_contacts: every output of out is null");
-    // !(x > 0) also refuses a NaN
-    if (!(cfg->reach > 0.f) || !std::isfinite(cfg->reach)) return fail("kp_sim_estimate_contacts: reach must be > 0 and finite");
-    const std::pair<const char*, float> pos[] = {{"w_f", cfg->w_f}, {"w_m", cfg->w_m}, {"rho", cfg->rho}};
-    for (const auto& p : pos)
-        if (!(p.second > 0.f) || !std::isfinite(p.second)) return fail(std::string("kp_sim_estimate_contacts: ") + p.first + " must be > 0 and finite");
-    if (!(cfg->mu >= 0.f) || !std::isfinite(cfg->mu)) return fail("kp_sim_estimate_contacts: mu must be >= 0 and finite (0: the model's)");
-    if (cfg->n_iters < 0) return fail("kp_sim_estimate_contacts: n_iters < 0");
-    if (s->model->threads != 64) return fail("kp_sim_estimate_contacts: needs a handle with threads_per_env = 64");
-    if (obj_qpos && !s->obj.d_geoms) return fail("kp_sim_estimate_contacts: obj_qpos given but the model blob has no object geoms");
-    if (n_rows == 0) return 0;
-    HIP_OK(hipSetDevice(s->device));
+    const char* who = "kp_sim_estimate_contacts";
     kp::EstimateArgs A{};
-    A.T = s->T; A.P = s->P; A.n_rows = n_rows;
+    const int go = rows_begin(who, s, n_rows, obj_qpos != nullptr, A, [&] {
+        if (refuse_null(who, {{"qpos", qpos}, {"cfg", cfg}, {"out", out}})) return -1;
+        if (!out->qfrc_inverse && !out->qfrc_contact && !out->contact && !out->lambda && !out->resid && !out->net_wrench && !out->ncon && !out->info)
+            return fail("kp_sim_estimate_contacts: every output of out is null");
+        if (refuse_not_positive(who, {{"reach", cfg->reach}, {"w_f", cfg->w_f}, {"w_m", cfg->w_m}, {"rho", cfg->rho}}, true)) return -1;
+        if (!(cfg->mu >= 0.f) || !std::isfinite(cfg->mu)) return fail("kp_sim_estimate_contacts: mu must be >= 0 and finite (0: the model's)");
+        if (cfg->n_iters < 0) return fail("kp_sim_estimate_contacts: n_iters < 0");
+        return 0;
+    });
+    if (go <= 0) return go;
     A.P.margin = cfg->reach;                        // the detection distance of the collision pass; everything else is the model's
     if (cfg->mu > 0.f) A.P.mu = cfg->mu;
     A.qpos = qpos; A.qvel = qvel; A.qacc = qacc;
@@ -1922,16 +1943,14 @@ int kp_sim_estimate_contacts(kp_sim* s, int n_rows, const float* qpos, const flo
 }
 
 int kp_sim_body_motion(kp_sim* s, int n_rows, const float* qpos, const float* qvel, const float* qacc, const kp_motion_out* out) {
-    if (!s) return fail("kp_sim_body_motion: null handle");
-    if (n_rows < 0) return fail("kp_sim_body_motion: n_rows < 0");
-    if (!qpos) return fail("kp_sim_body_motion: null qpos");
-    if (!out) return fail("kp_sim_body_motion: null out");
-    if (!out->body_vel && !out->body_acc && !out->body_com_vel && !out->centroid) return fail("kp_sim_body_motion: every output of out is null");
-    if (s->model->threads != 64) return fail("kp_sim_body_motion: needs a handle with threads_per_env = 64");
-    if (n_rows == 0) return 0;
-    HIP_OK(hipSetDevice(s->device));
+    const char* who = "kp_sim_body_motion";
     kp::BodyMotionArgs A{};
-    A.T = s->T; A.P = s->P; A.n_rows = n_rows;
+    const int go = rows_begin(who, s, n_rows, false, A, [&] {
+        if (refuse_null(who, {{"qpos", qpos}, {"out", out}})) return -1;
+        if (!out->body_vel && !out->body_acc && !out->body_com_vel && !out->centroid) return fail("kp_sim_body_motion: every output of out is null");
+        return 0;
+    });
+    if (go <= 0) return go;
     A.qpos = qpos; A.qvel = qvel; A.qacc = qacc;
     A.O = kp::BodyMotionOut{out->body_vel, out->body_acc, out->body_com_vel, out->centroid};
     kp::launch_body_motion(A, s->stream);
@@ -1939,16 +1958,10 @@ int kp_sim_body_motion(kp_sim* s, int n_rows, const float* qpos, const float* qv
 }
 
 int kp_sim_point_jacobian(kp_sim* s, int n_rows, const float* qpos, const int32_t* body, const float* offset, float* J) {
-    if (!s) return fail("kp_sim_point_jacobian: null handle");
-    if (n_rows < 0) return fail("kp_sim_point_jacobian: n_rows < 0");
-    if (!qpos) return fail("kp_sim_point_jacobian: null qpos");
-    if (!body) return fail("kp_sim_point_jacobian: null body");
-    if (!J) return fail("kp_sim_point_jacobian: null J");
-    if (s->model->threads != 64) return fail("kp_sim_point_jacobian: needs a handle with threads_per_env = 64");
-    if (n_rows == 0) return 0;
-    HIP_OK(hipSetDevice(s->device));
+    const char* who = "kp_sim_point_jacobian";
     kp::PointJacArgs A{};
-    A.T = s->T; A.P = s->P; A.n_rows = n_rows;
+    const int go = rows_begin(who, s, n_rows, false, A, [&] { return refuse_null(who, {{"qpos", qpos}, {"body", body}, {"J", J}}); });
+    if (go <= 0) return go;
     A.qpos = qpos; A.body = body; A.offset = offset; A.J = J;
     kp::launch_point_jacobian(A, s->stream);
     return launched();
@@ -1963,28 +1976,20 @@ void kp_fit_cfg_default(kp_fit_cfg* c) {
 }
 
 int kp_sim_fit_pose(kp_sim* s, int n_rows, const kp_fit_in* in, const kp_fit_cfg* cfg, const kp_fit_out* out) {
-    if (!s) return fail("kp_sim_fit_pose: null handle");
-    if (n_rows < 0) return fail("kp_sim_fit_pose: n_rows < 0");
-    if (!in) return fail("kp_sim_fit_pose: null in");
-    if (!cfg) return fail("kp_sim_fit_pose: null cfg");
-    if (!out) return fail("kp_sim_fit_pose: null out");
-    if (!in->qpos0) return fail("kp_sim_fit_pose: null qpos0");
-    if (!in->tgt_pos) return fail("kp_sim_fit_pose: null tgt_pos");
-    if (!in->q_prior != !in->w_prior) return fail("kp_sim_fit_pose: q_prior and w_prior go together (one of them is null)");
-    if (!out->qpos) return fail("kp_sim_fit_pose: null out qpos");
-    if (!out->info) return fail("kp_sim_fit_pose: null out info");
-    if (cfg->n_iters < 0) return fail("kp_sim_fit_pose: n_iters < 0");
-    // !(x > 0) also refuses a NaN
-    const std::pair<const char*, float> pos[] = {{"mu0", cfg->mu0}, {"mu_min", cfg->mu_min}, {"mu_max", cfg->mu_max}, {"mu_up", cfg->mu_up}, {"mu_down", cfg->mu_down}};
-    for (const auto& p : pos)
-        if (!(p.second > 0.f)) return fail(std::string("kp_sim_fit_pose: ") + p.first + " must be > 0");
-    for (int d = 0; d < kp::D_NV; d++)
-        if (!(cfg->damp[d] > 0.f)) return fail("kp_sim_fit_pose: damp[" + std::to_string(d) + "] must be > 0");
-    if (s->model->threads != 64) return fail("kp_sim_fit_pose: needs a handle with threads_per_env = 64");
-    if (n_rows == 0) return 0;
-    HIP_OK(hipSetDevice(s->device));
+    const char* who = "kp_sim_fit_pose";
     kp::FitPoseArgs A{};
-    A.T = s->T; A.P = s->P; A.n_rows = n_rows;
+    const int go = rows_begin(who, s, n_rows, false, A, [&] {
+        if (refuse_null(who, {{"in", in}, {"cfg", cfg}, {"out", out}}) || refuse_null(who, {{"qpos0", in->qpos0}, {"tgt_pos", in->tgt_pos}})) return -1;
+        if (!in->q_prior != !in->w_prior) return fail("kp_sim_fit_pose: q_prior and w_prior go together (one of them is null)");
+        if (refuse_null(who, {{"out qpos", out->qpos}, {"out info", out->info}})) return -1;
+        if (cfg->n_iters < 0) return fail("kp_sim_fit_pose: n_iters < 0");
+        // +inf passes here, where kp_sim_estimate_contacts refuses it
+        if (refuse_not_positive(who, {{"mu0", cfg->mu0}, {"mu_min", cfg->mu_min}, {"mu_max", cfg->mu_max}, {"mu_up", cfg->mu_up}, {"mu_down", cfg->mu_down}}, false)) return -1;
+        for (int d = 0; d < kp::D_NV; d++)
+            if (!(cfg->damp[d] > 0.f)) return fail("kp_sim_fit_pose: damp[" + std::to_string(d) + "] must be > 0");
+        return 0;
+    });
+    if (go <= 0) return go;
     A.qpos0 = in->qpos0; A.tgt_pos = in->tgt_pos; A.tgt_quat = in->tgt_quat; A.w_pos = in->w_pos; A.w_rot = in->w_rot; A.q_prior = in->q_prior; A.w_prior = in->w_prior;
     A.n_iters = cfg->n_iters; A.clamp_limits = cfg->clamp_limits;
     A.mu0 = cfg->mu0; A.mu_min = cfg->mu_min; A.mu_max = cfg->mu_max; A.mu_up = cfg->mu_up; A.mu_down = cfg->mu_down;

@@ -375,6 +375,64 @@ def _device_view(ptr, shape, device, typestr="<f4") -> torch.Tensor:
     return torch.as_tensor(type("_KpDeviceView", (), {"__cuda_array_interface__": iface})(), device=device)
 
 
+# ---- the rows tools (inverse_dynamics, estimate_contacts, body_motion, point_jacobian, fit_pose; contact_forces for its outputs): what their bindings
+# share.  Plain functions on tensors of any device (tests/test_rows_binding_cpu.py runs them without the library); the methods add _dev's device check.
+_JAC_OUTPUTS = {"J": ((6, NV), torch.float32)}
+_FIT_OUTPUTS = {"qpos": ((NQ,), torch.float32), "info": ((8,), torch.float32), "dq": ((NV,), torch.float32)}      # in kp_fit_out's order
+
+
+def _motion_spec(qpos, qvel, qacc, obj_qpos=None):
+    """the inputs of the tools that take a motion: _rows_inputs' list"""
+    f32 = torch.float32
+    return [("qpos", qpos, (NQ,), f32, True), ("qvel", qvel, (NV,), f32, False), ("qacc", qacc, (NV,), f32, False), ("obj_qpos", obj_qpos, (35,), f32, False)]
+
+
+def _rows_want(who, want, table, arg="want") -> tuple:
+    """the wanted output names as a tuple, after the check that they are some of `table`'s"""
+    want = tuple(want)
+    if not want or any(k not in table for k in want):
+        raise ValueError(f"{who}: {arg} must name some of {tuple(table)}, got {want}")
+    return want
+
+
+def _rows_inputs(who, spec):
+    """The inputs of a rows call, spec = [(name, tensor or None, tail shape, dtype, required)]: the first, qpos [..., 76], sets the leading shape, which the
+    others must have too.  Returns lead, R = prod(lead) and the inputs flattened to [R, *tail] (None for an optional one that was not given)."""
+    name0, qpos = spec[0][:2]
+    if qpos.dim() < 1 or qpos.shape[-1] != NQ:
+        raise ValueError(f"{who}: {name0} must be [..., {NQ}], got {tuple(qpos.shape)}")
+    lead = tuple(qpos.shape[:-1])
+    R = int(np.prod(lead, dtype=np.int64))
+    flat = []
+    for name, t, tail, _, required in spec:
+        if t is None and required:
+            raise ValueError(f"{who}: {name} is required")
+        if t is not None and tuple(t.shape) != lead + tail:
+            raise ValueError(f"{who}: {name} must be {lead + tail}, got {tuple(t.shape)}")
+        flat.append(None if t is None else t.reshape((R,) + tail))
+    return lead, R, flat
+
+
+def _rows_ptrs(who, spec, flat) -> list:
+    """the device pointers of _rows_inputs' rows: _dev's check of device, dtype and contiguity (the shapes are checked already; they go into its message)"""
+    return [_dev(f"{who}: {name}", t, None if t is None else tuple(t.shape), dtype) for (name, _, _, dtype, _), t in zip(spec, flat)]
+
+
+def _rows_outputs(R, table, want, device) -> dict:
+    """the [R, *shape] outputs of `table` (name -> (trailing shape, dtype)) for the wanted names"""
+    return {k: torch.empty((R, *table[k][0]), dtype=table[k][1], device=device) for k in want}
+
+
+def _rows_struct(cls, table, out):
+    """the C struct of output pointers, in the table's order: NULL for what was not wanted"""
+    return cls(*[C.c_void_p(out[k].data_ptr()) if k in out else None for k in table])
+
+
+def _rows_view(out, lead) -> dict:
+    """the outputs of _rows_outputs with the leading shape of the inputs"""
+    return {k: v.view(lead + tuple(v.shape[1:])) for k, v in out.items()}
+
+
 class KpSim:
     """N batched environments on one GPU (one kp_sim handle)."""
 
@@ -551,14 +609,10 @@ class KpSim:
         the world origin per entity (24 bodies, 2 object slots); qfrc_constraint, qacc, torque [N,75]; obj_qacc [N,2,6]."""
         if action is not None and torque is not None:
             raise ValueError("contact_forces: action and torque are mutually exclusive")
-        want = tuple(want)
-        bad = [k for k in want if k not in CONTACT_OUTPUTS]
-        if bad or not want:
-            raise ValueError(f"contact_forces: want must name some of {tuple(CONTACT_OUTPUTS)}, got {want}")
+        want = _rows_want("contact_forces", want, CONTACT_OUTPUTS)
         mode, act = (2, _dev("action", action, (self.n, self.cc_action_dim))) if action is not None else (1, _dev("torque", torque, (self.n, NV))) if torque is not None else (0, None)
-        out = {k: torch.empty((self.n, *CONTACT_OUTPUTS[k][0]), dtype=CONTACT_OUTPUTS[k][1], device=self.device) for k in want}
-        st = KpContactOut(*[_dev(k, out.get(k), (self.n, *CONTACT_OUTPUTS[k][0]), CONTACT_OUTPUTS[k][1]) for k in CONTACT_OUTPUTS])
-        _check(self.L.kp_sim_contact_forces(self.h, mode, act, _mask_ptr(env_mask, self.n), C.byref(st)), "kp_sim_contact_forces")
+        out = _rows_outputs(self.n, CONTACT_OUTPUTS, want, self.device)
+        _check(self.L.kp_sim_contact_forces(self.h, mode, act, _mask_ptr(env_mask, self.n), C.byref(_rows_struct(KpContactOut, CONTACT_OUTPUTS, out))), "kp_sim_contact_forces")
         return out
 
     def inverse_dynamics(self, qpos, qvel=None, qacc=None, obj_qpos=None, want=("qfrc_inverse",)) -> dict:
@@ -567,29 +621,14 @@ class KpSim:
         handle stores is read or changed.  want: names of INVDYN_OUTPUTS.  Returns a dict of device tensors with that leading shape: qfrc_inverse,
         qfrc_constraint, qfrc_bias [..., 75] (qfrc_applied[0:6] ++ ctrl[69] coordinates); contact [..., 64, 12] = A, B (-1), dist, pos[3], normal[3],
         force[3]; net_wrench [..., 6] = contact force on the humanoid, torque about the world origin; ncon int32 [...]."""
-        want = tuple(want)
-        bad = [k for k in want if k not in INVDYN_OUTPUTS]
-        if bad or not want:
-            raise ValueError(f"inverse_dynamics: want must name some of {tuple(INVDYN_OUTPUTS)}, got {want}")
-        if qpos.dim() < 1 or qpos.shape[-1] != NQ:
-            raise ValueError(f"inverse_dynamics: qpos must be [..., {NQ}], got {tuple(qpos.shape)}")
-        lead = tuple(qpos.shape[:-1])
-        R = int(np.prod(lead, dtype=np.int64))
-
-        def rows(name, t, dim):
-            if t is None:
-                return None, None
-            if tuple(t.shape) != lead + (dim,):
-                raise ValueError(f"inverse_dynamics: {name} must be {lead + (dim,)}, got {tuple(t.shape)}")
-            t = t.reshape(R, dim)
-            return t, _dev("inverse_dynamics: " + name, t, (R, dim))
-
-        ins = [rows(k, t, d) for k, t, d in (("qpos", qpos, NQ), ("qvel", qvel, NV), ("qacc", qacc, NV), ("obj_qpos", obj_qpos, 35))]
-        out = {k: torch.empty((R, *INVDYN_OUTPUTS[k][0]), dtype=INVDYN_OUTPUTS[k][1], device=self.device) for k in want}
-        st = KpInvDynOut(*[_dev(k, out.get(k), (R, *INVDYN_OUTPUTS[k][0]), INVDYN_OUTPUTS[k][1]) for k in INVDYN_OUTPUTS])
+        want = _rows_want("inverse_dynamics", want, INVDYN_OUTPUTS)
+        spec = _motion_spec(qpos, qvel, qacc, obj_qpos)
+        lead, R, rows = _rows_inputs("inverse_dynamics", spec)
+        ins = _rows_ptrs("inverse_dynamics", spec, rows)
+        out = _rows_outputs(R, INVDYN_OUTPUTS, want, self.device)
         if R > 0:                # no rows: nothing to launch (and an empty tensor has no address to hand over)
-            _check(self.L.kp_sim_inverse_dynamics(self.h, R, *[p for _, p in ins], C.byref(st)), "kp_sim_inverse_dynamics")
-        return {k: v.view(lead + INVDYN_OUTPUTS[k][0]) for k, v in out.items()}
+            _check(self.L.kp_sim_inverse_dynamics(self.h, R, *ins, C.byref(_rows_struct(KpInvDynOut, INVDYN_OUTPUTS, out))), "kp_sim_inverse_dynamics")
+        return _rows_view(out, lead)
 
     def estimate_contacts(self, qpos, qvel=None, qacc=None, obj_qpos=None, cfg: KpEstimateCfg | None = None, want=("qfrc_inverse",)) -> dict:
         """Contact forces estimated from kinematics (kp_sim_estimate_contacts): the forces inside the friction pyramids of the points within cfg.reach of
@@ -598,26 +637,15 @@ class KpSim:
         Returns a dict of device tensors with that leading shape: qfrc_inverse, qfrc_contact [..., 75]; contact [..., 64, 12] (contact_forces' rows,
         B = -1, the estimated force); lambda [..., 64, 4]; resid [..., 6] (force, moment about the root position, world axes); net_wrench [..., 6] (about
         the world origin); ncon int32 [...]; info [..., 8] (ESTIMATE_INFO).  Nothing the handle stores is read or changed."""
-        want = tuple(want)
-        bad = [k for k in want if k not in ESTIMATE_OUTPUTS]
-        if bad or not want:
-            raise ValueError(f"estimate_contacts: want must name some of {tuple(ESTIMATE_OUTPUTS)}, got {want}")
-        if qpos.dim() < 1 or qpos.shape[-1] != NQ:
-            raise ValueError(f"estimate_contacts: qpos must be [..., {NQ}], got {tuple(qpos.shape)}")
-        lead = tuple(qpos.shape[:-1])
-        R = int(np.prod(lead, dtype=np.int64))
-        ptrs = []
-        for name, t, dim in (("qpos", qpos, NQ), ("qvel", qvel, NV), ("qacc", qacc, NV), ("obj_qpos", obj_qpos, 35)):
-            if t is not None and tuple(t.shape) != lead + (dim,):
-                raise ValueError(f"estimate_contacts: {name} must be {lead + (dim,)}, got {tuple(t.shape)}")
-            ptrs.append((name, None if t is None else t.reshape(R, dim), dim))
+        want = _rows_want("estimate_contacts", want, ESTIMATE_OUTPUTS)
+        spec = _motion_spec(qpos, qvel, qacc, obj_qpos)
+        lead, R, rows = _rows_inputs("estimate_contacts", spec)
+        ins = _rows_ptrs("estimate_contacts", spec, rows)
         cfg = KpEstimateCfg.default(self.model) if cfg is None else cfg
-        out = {k: torch.empty((R, *ESTIMATE_OUTPUTS[k][0]), dtype=ESTIMATE_OUTPUTS[k][1], device=self.device) for k in want}
-        if R > 0:                # no rows: nothing to launch (and an empty tensor has no address to hand over)
-            st = KpEstimateOut(*[_dev(k, out.get(k), (R, *ESTIMATE_OUTPUTS[k][0]), ESTIMATE_OUTPUTS[k][1]) for k in ESTIMATE_OUTPUTS])
-            ins = [_dev("estimate_contacts: " + k, t, (R, d)) for k, t, d in ptrs]
-            _check(self.L.kp_sim_estimate_contacts(self.h, R, *ins, C.byref(cfg), C.byref(st)), "kp_sim_estimate_contacts")
-        return {k: v.view(lead + ESTIMATE_OUTPUTS[k][0]) for k, v in out.items()}
+        out = _rows_outputs(R, ESTIMATE_OUTPUTS, want, self.device)
+        if R > 0:
+            _check(self.L.kp_sim_estimate_contacts(self.h, R, *ins, C.byref(cfg), C.byref(_rows_struct(KpEstimateOut, ESTIMATE_OUTPUTS, out))), "kp_sim_estimate_contacts")
+        return _rows_view(out, lead)
 
     def body_motion(self, qpos, qvel=None, qacc=None, outputs=tuple(MOTION_OUTPUTS)) -> dict:
         """Body velocities and accelerations, momentum and energy of motion rows (kp_sim_body_motion): qpos [..., 76], qvel / qacc [..., 75] or None
@@ -625,44 +653,26 @@ class KpSim:
         a dict of device tensors with that leading shape, world axes: body_vel [..., 24, 6] = angular, linear velocity of the body frame origin;
         body_acc [..., 24, 6] = angular, classical linear acceleration of it; body_com_vel [..., 24, 3]; centroid [..., 18] (CENTROID_FIELDS: com,
         com_vel, L_com, ke, pe, com_acc, Ldot_com, mass)."""
-        want = tuple(outputs)
-        bad = [k for k in want if k not in MOTION_OUTPUTS]
-        if bad or not want:
-            raise ValueError(f"body_motion: outputs must name some of {tuple(MOTION_OUTPUTS)}, got {want}")
-        if qpos.dim() < 1 or qpos.shape[-1] != NQ:
-            raise ValueError(f"body_motion: qpos must be [..., {NQ}], got {tuple(qpos.shape)}")
-        lead = tuple(qpos.shape[:-1])
-        R = int(np.prod(lead, dtype=np.int64))
-        ins = []
-        for name, t, dim in (("qpos", qpos, NQ), ("qvel", qvel, NV), ("qacc", qacc, NV)):
-            if t is not None and tuple(t.shape) != lead + (dim,):
-                raise ValueError(f"body_motion: {name} must be {lead + (dim,)}, got {tuple(t.shape)}")
-            ins.append(None if t is None else t.reshape(R, dim))
-        out = {k: torch.empty((R, *MOTION_OUTPUTS[k][0]), dtype=MOTION_OUTPUTS[k][1], device=self.device) for k in want}
-        if R > 0:                # no rows: nothing to launch (and an empty tensor has no address to hand over)
-            st = KpMotionOut(*[_dev(k, out.get(k), (R, *MOTION_OUTPUTS[k][0])) for k in MOTION_OUTPUTS])
-            ptrs = [_dev("body_motion: " + k, t, (R, d)) for k, t, d in zip(("qpos", "qvel", "qacc"), ins, (NQ, NV, NV))]
-            _check(self.L.kp_sim_body_motion(self.h, R, *ptrs, C.byref(st)), "kp_sim_body_motion")
-        return {k: v.view(lead + MOTION_OUTPUTS[k][0]) for k, v in out.items()}
+        want = _rows_want("body_motion", outputs, MOTION_OUTPUTS, "outputs")
+        spec = _motion_spec(qpos, qvel, qacc)[:3]
+        lead, R, rows = _rows_inputs("body_motion", spec)
+        ins = _rows_ptrs("body_motion", spec, rows)
+        out = _rows_outputs(R, MOTION_OUTPUTS, want, self.device)
+        if R > 0:
+            _check(self.L.kp_sim_body_motion(self.h, R, *ins, C.byref(_rows_struct(KpMotionOut, MOTION_OUTPUTS, out))), "kp_sim_body_motion")
+        return _rows_view(out, lead)
 
     def point_jacobian(self, qpos, body, offset=None) -> torch.Tensor:
         """mj_jac on rows (kp_sim_point_jacobian): qpos [..., 76], body int32 [...] (0..23; anything else: a zero row), offset [..., 3] in the body's
         frame or None (the body origin), any leading shape.  Returns J [..., 6, 75]: rows 0..2 the world velocity of the point, rows 3..5 the body's
         world angular velocity, per unit dof velocity (qvel order).  Nothing the handle stores is read or changed."""
-        if qpos.dim() < 1 or qpos.shape[-1] != NQ:
-            raise ValueError(f"point_jacobian: qpos must be [..., {NQ}], got {tuple(qpos.shape)}")
-        lead = tuple(qpos.shape[:-1])
-        R = int(np.prod(lead, dtype=np.int64))
-        if tuple(body.shape) != lead:
-            raise ValueError(f"point_jacobian: body must be {lead}, got {tuple(body.shape)}")
-        if offset is not None and tuple(offset.shape) != lead + (3,):
-            raise ValueError(f"point_jacobian: offset must be {lead + (3,)}, got {tuple(offset.shape)}")
-        J = torch.empty((R, 6, NV), dtype=torch.float32, device=self.device)
-        if R > 0:                # no rows: nothing to launch (and an empty tensor has no address to hand over)
-            ptrs = [_dev("point_jacobian: qpos", qpos.reshape(R, NQ), (R, NQ)), _dev("point_jacobian: body", body.reshape(R), (R,), torch.int32),
-                    _dev("point_jacobian: offset", None if offset is None else offset.reshape(R, 3), (R, 3))]
-            _check(self.L.kp_sim_point_jacobian(self.h, R, *ptrs, C.c_void_p(J.data_ptr())), "kp_sim_point_jacobian")
-        return J.view(lead + (6, NV))
+        spec = [("qpos", qpos, (NQ,), torch.float32, True), ("body", body, (), torch.int32, True), ("offset", offset, (3,), torch.float32, False)]
+        lead, R, rows = _rows_inputs("point_jacobian", spec)
+        ins = _rows_ptrs("point_jacobian", spec, rows)
+        out = _rows_outputs(R, _JAC_OUTPUTS, ("J",), self.device)
+        if R > 0:
+            _check(self.L.kp_sim_point_jacobian(self.h, R, *ins, C.c_void_p(out["J"].data_ptr())), "kp_sim_point_jacobian")
+        return _rows_view(out, lead)["J"]
 
     def fit_pose(self, qpos0, tgt_pos, tgt_quat=None, w_pos=None, w_rot=None, q_prior=None, w_prior=None, cfg: KpFitCfg | None = None, want_dq=False) -> dict:
         """Pose fitting on rows (kp_sim_fit_pose): Levenberg-Marquardt from qpos0 [..., 76] towards the body positions tgt_pos [..., 24, 3] and, where
@@ -670,29 +680,18 @@ class KpSim:
         [..., 69] (both or neither); any leading shape, the same on every input.  cfg: a KpFitCfg (None: KpFitCfg.default()).  Returns a dict of device
         tensors: qpos [..., 76], info [..., 8] (FIT_INFO: cost0, cost, accepted, mu, max_epos, max_erot, dq_inf, status) and, with want_dq, dq
         [..., 75] of the last solve.  Nothing the handle stores is read or changed."""
-        if qpos0.dim() < 1 or qpos0.shape[-1] != NQ:
-            raise ValueError(f"fit_pose: qpos0 must be [..., {NQ}], got {tuple(qpos0.shape)}")
         if (q_prior is None) != (w_prior is None):
             raise ValueError("fit_pose: q_prior and w_prior go together")
-        lead = tuple(qpos0.shape[:-1])
-        R = int(np.prod(lead, dtype=np.int64))
-        ins = []
-        for name, t, tail in (("qpos0", qpos0, (NQ,)), ("tgt_pos", tgt_pos, (24, 3)), ("tgt_quat", tgt_quat, (24, 4)), ("w_pos", w_pos, (24,)), ("w_rot", w_rot, (24,)),
-                              ("q_prior", q_prior, (69,)), ("w_prior", w_prior, (69,))):
-            if t is None and name == "tgt_pos":
-                raise ValueError("fit_pose: tgt_pos is required")
-            if t is not None and tuple(t.shape) != lead + tail:
-                raise ValueError(f"fit_pose: {name} must be {lead + tail}, got {tuple(t.shape)}")
-            ins.append((name, None if t is None else t.reshape((R,) + tail), (R,) + tail))
+        f32 = torch.float32
+        spec = [("qpos0", qpos0, (NQ,), f32, True), ("tgt_pos", tgt_pos, (24, 3), f32, True), ("tgt_quat", tgt_quat, (24, 4), f32, False), ("w_pos", w_pos, (24,), f32, False),
+                ("w_rot", w_rot, (24,), f32, False), ("q_prior", q_prior, (69,), f32, False), ("w_prior", w_prior, (69,), f32, False)]
+        lead, R, rows = _rows_inputs("fit_pose", spec)
+        ins = _rows_ptrs("fit_pose", spec, rows)
         cfg = KpFitCfg.default() if cfg is None else cfg
-        out = {"qpos": torch.empty((R, NQ), dtype=torch.float32, device=self.device), "info": torch.empty((R, 8), dtype=torch.float32, device=self.device)}
-        if want_dq:
-            out["dq"] = torch.empty((R, NV), dtype=torch.float32, device=self.device)
-        if R > 0:                # no rows: nothing to launch (and an empty tensor has no address to hand over)
-            fin = KpFitIn(*[_dev("fit_pose: " + k, t, shp) for k, t, shp in ins])
-            fout = KpFitOut(*[None if k not in out else C.c_void_p(out[k].data_ptr()) for k in ("qpos", "info", "dq")])
-            _check(self.L.kp_sim_fit_pose(self.h, R, C.byref(fin), C.byref(cfg), C.byref(fout)), "kp_sim_fit_pose")
-        return {k: v.view(lead + tuple(v.shape[1:])) for k, v in out.items()}
+        out = _rows_outputs(R, _FIT_OUTPUTS, ("qpos", "info", "dq") if want_dq else ("qpos", "info"), self.device)
+        if R > 0:
+            _check(self.L.kp_sim_fit_pose(self.h, R, C.byref(KpFitIn(*ins)), C.byref(cfg), C.byref(_rows_struct(KpFitOut, _FIT_OUTPUTS, out))), "kp_sim_fit_pose")
+        return _rows_view(out, lead)
 
     def fk(self, qpos_rows: torch.Tensor):
         """qpos_fk_batch on [R,76] rows -> dict(qpos, wbpos, wbquat, bquat, body_com) of device tensors."""

@@ -16,7 +16,7 @@ bodies with the blob's masses and inertias.  None of this shares anything with t
 """
 import numpy as np
 
-from oracle.kpo import OracleSim
+from np_rigid import f32, oracle, qmul  # noqa: F401  (the tests reach them through this module)
 
 NB, NQ, NV = 24, 76, 75
 
@@ -30,11 +30,6 @@ def auto_eps(v, a):
 CENTROID = {"com": slice(0, 3), "com_vel": slice(3, 6), "L_com": slice(6, 9), "ke": 9, "pe": 10, "com_acc": slice(11, 14), "Ldot_com": slice(14, 17), "mass": 17}
 
 
-def qmul(a, b):
-    return np.array([a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3], a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
-                     a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1], a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0]])
-
-
 def qexp(r):
     """unit quaternion of the rotation vector r"""
     th = np.linalg.norm(r)
@@ -43,6 +38,8 @@ def qexp(r):
 
 
 def qmat(q):
+    """not np_rigid.quat_matrix: 1 - 2 (y^2 + z^2) on the diagonal where that one has w^2 + x^2 - y^2 - z^2; equal to rounding, not bit
+    for bit (profiles/rows_call/helpers_equal.log)"""
     w, x, y, z = q / np.linalg.norm(q)
     return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)], [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
                      [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
@@ -67,7 +64,8 @@ def advance(q, v, a, t):
 
 
 def fk(o, q):
-    """(xpos [24,3], R [24,3,3], xipos [24,3]) of the pose q on the oracle"""
+    """(xpos [24,3], R [24,3,3], xipos [24,3]) of the pose q on the oracle.  Not fit_pose_oracle.fk: that one returns (xpos, xquat) and normalises the
+    root quaternion itself before a raw set_state + forward; this one resets the oracle with q as given"""
     o.reset(q, np.zeros(NV))
     xq = o.get("xquat").reshape(NB, 4)
     return o.get("xpos").reshape(NB, 3), np.stack([qmat(x) for x in xq]), o.get("xipos").reshape(NB, 3)
@@ -130,14 +128,6 @@ def conservation_drift(kpm, c0, c1, t):
     m, g = float(np.asarray(kpm["body_mass"], float).sum()), np.asarray(kpm["opt"][1:4], float)
     return (m * (c1[CENTROID["com_vel"]] - c0[CENTROID["com_vel"]]) - m * g * t, c1[CENTROID["L_com"]] - c0[CENTROID["L_com"]],
             (c1[CENTROID["ke"]] + c1[CENTROID["pe"]]) - (c0[CENTROID["ke"]] + c0[CENTROID["pe"]]))
-
-
-def oracle(kpm_path):
-    return OracleSim(kpm=kpm_path, contact=False, limits=False)
-
-
-def f32(x):
-    return np.asarray(x, np.float32).astype(np.float64)
 
 
 def edge_rows(std_qpos):

@@ -15,6 +15,7 @@ from scipy.optimize import lsq_linear
 
 import contact_force_oracle as CF
 import inverse_dynamics_oracle as ID
+from np_rigid import make_frame, quat_matrix  # noqa: F401  (the tests reach them through this module)
 from kinpoly_amd.model_compiler import read_kpm, write_kpm
 
 NV = 75
@@ -46,22 +47,6 @@ def reach_blob(kpm_path, reach, tmpdir):
         write_kpm(m, out)
         _REACH_BLOBS[key] = out
     return _REACH_BLOBS[key]
-
-
-def make_frame(n):
-    """rows n, t1, t2 for a unit normal: t1 = the y axis (the z axis when |n_y| >= 0.5) made orthogonal to n and normalised, t2 = n x t1"""
-    n = np.asarray(n, float)
-    y = np.array([0.0, 1.0, 0.0]) if abs(n[1]) < 0.5 else np.array([0.0, 0.0, 1.0])
-    y = y - n.dot(y) * n
-    y = y / np.linalg.norm(y)
-    return np.stack([n, y, np.cross(n, y)])
-
-
-def quat_matrix(q):
-    w, x, y, z = np.asarray(q, float) / np.linalg.norm(q)
-    return np.array([[w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y)],
-                     [2 * (x * y + w * z), w * w - x * x + y * y - z * z, 2 * (y * z - w * x)],
-                     [2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z]])
 
 
 def edges(frame, mu):

@@ -6,16 +6,9 @@ contact list and the solve.  The caller puts the state in first: for the stale c
 """
 import numpy as np
 
+from np_rigid import make_frame  # noqa: F401  (the tests reach it through this module)
+
 NB, NV, NU, MAXOBJ = 24, 75, 69, 2
-
-
-def make_frame(n):
-    """mju_makeFrame of a unit normal: rows n, t1, t2 (the rule of contact_frame in kp_step_args.hpp)"""
-    n = np.asarray(n, float)
-    y = np.array([0.0, 1.0, 0.0]) if abs(n[1]) < 0.5 else np.array([0.0, 0.0, 1.0])
-    y = y - n.dot(y) * n
-    y /= np.linalg.norm(y)
-    return np.stack([n, y, np.cross(n, y)])
 
 
 def contact_forces_from_efc(efc_force, contacts, mu):

@@ -8,21 +8,11 @@ dt = 1), the same accept rule (finite and strictly smaller cost) and the same mu
 import numpy as np
 
 import push_oracle as PO
-from oracle.kpo import OracleSim
+from np_rigid import f32, oracle, qmul  # noqa: F401  (the tests reach them through this module)
 
 NV, NB, NU, NQ = 75, 24, 69, 76
 # kp_fit_cfg_default
 DEFAULT_CFG = dict(n_iters=30, mu0=1e-2, mu_min=1e-7, mu_max=1e6, mu_up=8.0, mu_down=0.3, damp=np.ones(NV), clamp_limits=False)
-
-
-def oracle(kpm_path):
-    """kinematics only: no contact rows, no limit rows (forward() is called 76 times per Jacobian)"""
-    return OracleSim(kpm=kpm_path, contact=False, limits=False)
-
-
-def qmul(a, b):
-    w0, x0, y0, z0 = a; w1, x1, y1, z1 = b
-    return np.array([w0 * w1 - x0 * x1 - y0 * y1 - z0 * z1, w0 * x1 + x0 * w1 + y0 * z1 - z0 * y1, w0 * y1 - x0 * z1 + y0 * w1 + z0 * x1, w0 * z1 + x0 * y1 - y0 * x1 + z0 * w1])
 
 
 def qnormalize(q):
@@ -68,7 +58,7 @@ def oplus(q, dq, jnt_range=None, jnt_limited=None):
 
 
 def fk(o, q):
-    """(xpos [24, 3], xquat [24, 4]) of the oracle's forward pass at q (root quaternion normalised first)"""
+    """(xpos [24, 3], xquat [24, 4]) of the oracle's forward pass at q (root quaternion normalised first); body_motion_oracle.fk is another function"""
     o.set_state_raw(normalized(q), np.zeros(NV)); o.forward()
     return o.get("xpos").reshape(NB, 3).copy(), o.get("xquat").reshape(NB, 4).copy()
 
@@ -200,10 +190,6 @@ def perturbed(q, seed):
     rng = np.random.default_rng(seed)
     dq = np.concatenate([rng.uniform(-0.1, 0.1, 3), rng.uniform(-0.2, 0.2, 3), rng.normal(size=NU) * 0.2])
     return oplus(q, dq)
-
-
-def f32(a):
-    return np.asarray(a, np.float32).astype(np.float64)
 
 
 ROWS = (1, 5, 67)

@@ -8,6 +8,7 @@ tests/test_inverse_dynamics_cpu.py shows that this is an inverse of the oracle's
 import numpy as np
 
 import contact_force_oracle as CF
+from np_rigid import f32  # noqa: F401  (the tests reach it through this module)
 from oracle.kpo import OracleSim, object_geoms
 
 NV, NU = 75, 69
@@ -62,10 +63,6 @@ def falling_state(kpm, std_qpos, seed):
 
 SWEEP_SEEDS = tuple(range(1000, 1064))       # the 64 falling states of the GPU sweep
 MARGIN_OPT = 14                              # kpm["opt"] index of the contact margin (model_compiler.OPT_FIELDS)
-
-
-def f32(a):
-    return np.asarray(a, np.float32).astype(np.float64)
 
 
 def named_states(kpm_floor, kpm_step, std_qpos, std_qvel):

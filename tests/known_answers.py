@@ -93,7 +93,8 @@ def limit_penetration(torque, invw):
 
 
 def make_frame(n):
-    """mju_makeFrame: complete the contact normal to a right-handed frame (n, t1, t2): the reference axis is y unless n is within
+    """Not np_rigid.make_frame: this one normalises n and returns the tuple (n, t1, t2), that one takes a unit normal as it is and returns the rows.
+    mju_makeFrame: complete the contact normal to a right-handed frame (n, t1, t2): the reference axis is y unless n is within
     60 degrees of it (|n.y| >= 0.5), then z; t1 = its part orthogonal to n, normalised; t2 = n x t1."""
     n = np.asarray(n, float) / np.linalg.norm(n)
     ref = np.array([0.0, 1.0, 0.0]) if abs(n[1]) < 0.5 else np.array([0.0, 0.0, 1.0])

@@ -7,14 +7,9 @@ The push is dv = M^-1 J_b(r)^T [p; l] with M^-1 the oracle's solveM (armature in
 """
 import numpy as np
 
+from np_rigid import quat_matrix as _rot
+
 NV, NB = 75, 24
-
-
-def _rot(q):
-    w, x, y, z = np.asarray(q, float) / np.linalg.norm(q)
-    return np.array([[w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y)],
-                     [2 * (x * y + w * z), w * w - x * x + y * y - z * z, 2 * (y * z - w * x)],
-                     [2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z]])
 
 
 def _skew(a):

@@ -19,6 +19,8 @@ torch = pytest.importorskip("torch")
 import body_motion_oracle as BM  # noqa: E402
 import contact_force_oracle as CF  # noqa: E402
 import inverse_dynamics_oracle as ID  # noqa: E402
+import rows_harness as H  # noqa: E402
+from rows_harness import dev, handle  # noqa: E402
 from kinpoly_amd.model_compiler import DEFAULT_KPM, OPT_FIELDS, STEP_KPM, read_kpm  # noqa: E402
 from oracle.kpo import OracleSim  # noqa: E402
 
@@ -53,19 +55,12 @@ TOL = {
     "Ldot_com": 4 * 5.850e-06,   # measured 5.850e-06
     "mass": 4 * 7.877e-09,       # measured 7.877e-09
 }
-MEASURED = {}
+MEASURED = H.Measured()
 
 
 @pytest.fixture(scope="module")
 def kp():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test selected but no HIP device is visible")
-    from kinpoly_amd import sim as kpsim
-    return kpsim
-
-
-def dev(a, dt=torch.float32):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dt, device="cuda")
+    return H.gpu_module()
 
 
 # ---------------------------------------------------------------- cases: (q, v, a) with the fp64 reference, computed once
@@ -101,16 +96,6 @@ def cases(scene):
             add(k, q, v, rng.normal(size=75) * 30.0)
     _CASES[scene] = out
     return out
-
-
-_SIMS = {}
-
-
-def handle(kp, blob=DEFAULT_KPM, n=1, **opts):
-    key = (blob, n, tuple(sorted(opts.items())))
-    if key not in _SIMS:
-        _SIMS[key] = kp.KpSim(kp.KpModel(blob, **opts), n)
-    return _SIMS[key]
 
 
 def run(sim, cs, want=OUT_KEYS, qvel=True, qacc=True):
@@ -177,27 +162,22 @@ def test_parity_edge_rows(kp, n):
 
 # ---------------------------------------------------------------- bitwise
 
-def _same(a, b, keys=OUT_KEYS):
-    for k in keys:
-        assert np.array_equal(a[k].view(np.int32), b[k].view(np.int32)), k
-
-
 def test_bitwise(kp):
     base = cases("floor") + cases("edge")
     cs = [base[e % len(base)] for e in range(67)]
     sim = handle(kp)
     out = run(sim, cs)
-    _same(out, run(sim, cs))                                            # a second identical call
+    H.same_bits(out, run(sim, cs))                                            # a second identical call
     for e in (0, 7, 64, 66):                                            # a row of the R = 67 call against the same row alone
         one = run(sim, [cs[e]])
         for k in OUT_KEYS:
             assert np.array_equal(out[k][e].view(np.int32), one[k][0].view(np.int32)), (cs[e]["name"], k)
     for k in OUT_KEYS:                                                  # each output requested alone
-        _same(out, run(sim, cs, want=(k,)), (k,))
+        H.same_bits(out, run(sim, cs, want=(k,)), (k,))
     still = [dict(c, v=np.zeros(75)) for c in cs]                       # qvel = NULL equals explicit zeros
-    _same(run(sim, still), run(sim, still, qvel=False))
+    H.same_bits(run(sim, still), run(sim, still, qvel=False))
     flat = [dict(c, a=np.zeros(75)) for c in cs]                        # qacc = NULL equals explicit zeros
-    _same(run(sim, flat), run(sim, flat, qacc=False))
+    H.same_bits(run(sim, flat), run(sim, flat, qacc=False))
     lead = sim.body_motion(dev(np.stack([c["q"] for c in cs[:6]])).view(2, 3, 76), dev(np.stack([c["v"] for c in cs[:6]])).view(2, 3, 75))      # leading shape
     assert lead["body_vel"].shape == (2, 3, 24, 6) and lead["body_com_vel"].shape == (2, 3, 24, 3) and lead["centroid"].shape == (2, 3, 18)
     assert np.array_equal(lead["centroid"].cpu().numpy().reshape(6, 18).view(np.int32), run(sim, flat[:6])["centroid"].view(np.int32))
@@ -311,39 +291,13 @@ def test_a_control_step_in_flight_keeps_the_laws(kp):
 
 @pytest.mark.parametrize("scene", ["floor", "h_push"])
 def test_the_control_step_is_bit_identical(kp, scene):
-    blob = DEFAULT_KPM if scene == "floor" else STEP_KPM
     fl = cases("floor")
-    if scene == "floor":
-        sts = [dict(q=fl[3 * (e % 5)]["q"], v=fl[3 * (e % 5)]["v"], blk=None) for e in range(67)]
-    else:
-        q, v, blk, _ = CF.object_scenes(read_kpm(STEP_KPM), STD["qpos"])["h_push"]
-        sts = [dict(q=ID.f32(q), v=ID.f32(v), blk=ID.f32(blk)) for _ in range(67)]
-    sims = []
-    for _ in range(2):
-        sim = kp.KpSim(kp.KpModel(blob, queue_slots=16), 67)             # 67 envs on 16 wave slots: the job queue (lean layout on the floor handle)
-        if sts[0]["blk"] is not None:
-            sim.set_objects(dev(np.stack([s["blk"] for s in sts])))
-        sim.set_state(dev(np.stack([s["q"] for s in sts])), dev(np.stack([s["v"] for s in sts])))
-        sim.set_target(dev(np.tile(ID.f32(STD["qpos"]), (67, 1))))
-        sims.append(sim)
-    act = dev(np.random.default_rng(3).normal(size=(67, 75)) * 0.3)
-    for _ in range(3):
-        a = run(sims[0], fl[:5])
-        _same(a, run(sims[0], fl[:5]))
-        stored = sims[0].body_motion(sims[0].view("qpos"), sims[0].view("qvel"))      # on the stored rows too
+
+    def between(sim):
+        H.same_bits(run(sim, fl[:5]), run(sim, fl[:5]), OUT_KEYS)
+        stored = sim.body_motion(sim.view("qpos"), sim.view("qvel"))      # on the stored rows too
         assert torch.isfinite(stored["centroid"]).all()
-        for s in sims:
-            s.step_ctrl(act, 15)
-    assert sims[0].queue_counters()["claimed"] > 0
-    for k in kp.FIELDS:
-        try:
-            x = sims[0].get(k)
-        except kp.KinPolyNativeError:
-            with pytest.raises(kp.KinPolyNativeError):
-                sims[1].get(k)
-            continue
-        assert torch.equal(x.view(torch.int32), sims[1].get(k).view(torch.int32)), k
-    assert np.array_equal(sims[0].diag(), sims[1].diag())
+    H.control_step_untouched(kp, scene, between)
 
 
 # ---------------------------------------------------------------- refusals
@@ -351,8 +305,7 @@ def test_the_control_step_is_bit_identical(kp, scene):
 def test_refusals(kp):
     sim = handle(kp)
     L, err = sim.L, lambda: sim.L.kp_last_error().decode()      # noqa: E731
-    bufs = {k: torch.full((5, *kp.MOTION_OUTPUTS[k][0]), 7, dtype=torch.float32, device="cuda") for k in kp.MOTION_OUTPUTS}
-    full = kp.KpMotionOut(*[ctypes.c_void_p(bufs[k].data_ptr()) for k in kp.MOTION_OUTPUTS])
+    bufs, full = H.sentinel(kp.MOTION_OUTPUTS, kp.KpMotionOut)
     q = dev(np.tile(ID.f32(STD["qpos"]), (5, 1)))
     qp = ctypes.c_void_p(q.data_ptr())
     f = L.kp_sim_body_motion
@@ -364,9 +317,7 @@ def test_refusals(kp):
     wide = kp.KpSim(kp.KpModel(threads_per_env=128), 5)
     assert f(wide.h, 5, qp, None, None, ctypes.byref(full)) != 0 and "threads_per_env" in err()
     assert f(sim.h, 0, qp, None, None, ctypes.byref(full)) == 0, "n_rows == 0 does nothing"
-    torch.cuda.synchronize()
-    for k, b in bufs.items():
-        assert bool((b == 7).all()), f"a refused call launched nothing: {k}"
+    H.refused_calls_wrote_nothing(bufs)
     with pytest.raises(ValueError):
         sim.body_motion(q, outputs=("qacc",))
     with pytest.raises(ValueError):

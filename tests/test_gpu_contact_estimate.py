@@ -20,6 +20,8 @@ torch = pytest.importorskip("torch")
 import contact_estimate_oracle as CE  # noqa: E402
 import contact_force_oracle as CF  # noqa: E402
 import inverse_dynamics_oracle as ID  # noqa: E402
+import rows_harness as H  # noqa: E402
+from rows_harness import dev, handle  # noqa: E402
 from kinpoly_amd.model_compiler import DEFAULT_KPM, STEP_KPM, read_kpm  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -54,37 +56,16 @@ TOLS = dict(resid=TOL_RESID, qfrc_inverse=TOL_QINV, qfrc_contact=TOL_QCON, conta
 TOL_KKT = 4 * 6.204e-5        # |lambda - max(0, G^T W e) / rho|_inf / scale; measured 6.204e-5
 TOL_E = 4 * 1.281e-4          # |e - (r - G lambda)|_inf / scale; measured 1.281e-4
 TOL_ROOT = 4 * 1.280e-4       # |root part of qfrc_inverse - resid in the root convention|_inf / scale; measured 1.280e-4
-MEASURED = {}
+MEASURED = H.Measured()
 
 
 @pytest.fixture(scope="module")
 def kp():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test selected but no HIP device is visible")
-    from kinpoly_amd import sim as kpsim
-    return kpsim
-
-
-def dev(a, dt=torch.float32):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dt, device="cuda")
-
-
-def note(key, v):
-    MEASURED[key] = max(MEASURED.get(key, 0.0), float(v))
+    return H.gpu_module()
 
 
 def cases(scene):
     return CE.cases(scene, (DEFAULT_KPM, STEP_KPM), STD["qpos"], STD["qvel"], CFG)
-
-
-_SIMS = {}
-
-
-def handle(kp, blob, n=1, **opts):
-    key = (blob, n, tuple(sorted(opts.items())))
-    if key not in _SIMS:
-        _SIMS[key] = kp.KpSim(kp.KpModel(blob, **opts), n)
-    return _SIMS[key]
 
 
 def run(sim, cs, blk="own", want=OUT_KEYS, qvel=True, cfg=None):
@@ -111,7 +92,7 @@ def scale_of(r):
 def compare(out, e, ref, local, name):
     """deviations of row e from the reference, relative to the case's scale -> local and MEASURED.  The candidate sets must be equal."""
     def rec(k, v):
-        note(k, v); local[k] = max(local.get(k, 0.0), float(v))
+        MEASURED.note(k, v, local)
     sc = scale_of(ref["r"])
     got = rows_of(out, e)
     con = ref["contacts"]
@@ -213,7 +194,7 @@ def test_solver_against_its_definition(kp):
         root = np.concatenate([ev[:3], quat_rot(q[3:7], ev[3:], inverse=True)])
         d_root = np.abs(out["qfrc_inverse"][e][:6] - root).max() / sc
         for k, v in (("kkt", d_kkt), ("e_definition", d_e), ("root_part", d_root)):
-            note(k, v); local[k] = max(local.get(k, 0.0), float(v))
+            MEASURED.note(k, v, local)
     print("solver definition: " + ", ".join(f"{k} {v:.3e}" for k, v in local.items()))
     assert local["kkt"] <= TOL_KKT and local["e_definition"] <= TOL_E and local["root_part"] <= TOL_ROOT
 
@@ -266,26 +247,21 @@ def test_known_answers(kp):
 
 # ---------------------------------------------------------------- bitwise
 
-def _same(a, b, keys=OUT_KEYS):
-    for k in keys:
-        assert np.array_equal(a[k].view(np.int32), b[k].view(np.int32)), k
-
-
 @pytest.mark.parametrize("scene", ["floor", "g_sit"])
 def test_bitwise(kp, scene):
     base = cases(scene) + (cases("sweep")[:30] if scene == "floor" else [])
     cs = [base[e % len(base)] for e in range(67)]
     sim = handle(kp, DEFAULT_KPM if scene == "floor" else STEP_KPM)
     out = run(sim, cs)
-    _same(out, run(sim, cs))                                            # a second identical call
+    H.same_bits(out, run(sim, cs))                                            # a second identical call
     for e in (0, 7, 64, 66) if scene == "floor" else (0, 66):           # a row of the R = 67 call against the same row alone
         one = run(sim, [cs[e]])
         for k in OUT_KEYS:
             assert np.array_equal(out[k][e].view(np.int32), one[k][0].view(np.int32)), (cs[e]["name"], k)
     for k in OUT_KEYS:                                                  # outputs requested one at a time
-        _same(out, run(sim, cs, want=(k,)), (k,))
+        H.same_bits(out, run(sim, cs, want=(k,)), (k,))
     still = [dict(c, v=np.zeros(75)) for c in cs]                       # qvel = NULL equals explicit zeros
-    _same(run(sim, still), run(sim, still, qvel=False))
+    H.same_bits(run(sim, still), run(sim, still, qvel=False))
     # a non-finite row reports status 1, writes zeros and leaves its neighbours' bits alone
     bad = [dict(c) for c in cs]
     bad[5] = dict(bad[5], q=np.where(np.arange(76) == 9, np.nan, bad[5]["q"])); bad[64] = dict(bad[64], a=np.where(np.arange(75) == 0, np.inf, bad[64]["a"]))
@@ -308,38 +284,9 @@ def test_bitwise(kp, scene):
 def test_the_control_step_is_bit_identical(kp, scene):
     """every stored field and kp_sim_diag of a floor handle (lean job queue) and of an object handle after three control steps, with and without estimate
     calls in between"""
-    blob = DEFAULT_KPM if scene == "floor" else STEP_KPM
     fl = cases("floor")
-    if scene == "floor":
-        sts = [dict(q=fl[3 * (e % 5)]["q"], v=fl[3 * (e % 5)]["v"], blk=None) for e in range(67)]
-    else:
-        q, v, blk, _ = CF.object_scenes(KPMS[STEP_KPM], STD["qpos"])["h_push"]
-        sts = [dict(q=ID.f32(q), v=ID.f32(v), blk=ID.f32(blk)) for _ in range(67)]
-    sims = []
-    for _ in range(2):
-        sim = kp.KpSim(kp.KpModel(blob, queue_slots=16), 67)             # 67 envs on 16 wave slots: the job queue (lean layout on the floor handle)
-        if sts[0]["blk"] is not None:
-            sim.set_objects(dev(np.stack([s["blk"] for s in sts])))
-        sim.set_state(dev(np.stack([s["q"] for s in sts])), dev(np.stack([s["v"] for s in sts])))
-        sim.set_target(dev(np.tile(ID.f32(STD["qpos"]), (67, 1))))
-        sims.append(sim)
-    act = dev(np.random.default_rng(3).normal(size=(67, 75)) * 0.3)
-    rows = fl[:5] if scene == "floor" else [dict(fl[0], blk=sts[0]["blk"])] * 5
-    for _ in range(3):
-        a = run(sims[0], rows)
-        _same(a, run(sims[0], rows))
-        for s in sims:
-            s.step_ctrl(act, 15)
-    assert sims[0].queue_counters()["claimed"] > 0
-    for k in kp.FIELDS:
-        try:
-            x = sims[0].get(k)
-        except kp.KinPolyNativeError:
-            with pytest.raises(kp.KinPolyNativeError):
-                sims[1].get(k)
-            continue
-        assert torch.equal(x.view(torch.int32), sims[1].get(k).view(torch.int32)), k
-    assert np.array_equal(sims[0].diag(), sims[1].diag())
+    rows = fl[:5] if scene == "floor" else [dict(fl[0], blk=ID.f32(CF.object_scenes(KPMS[STEP_KPM], STD["qpos"])["h_push"][2]))] * 5
+    H.control_step_untouched(kp, scene, lambda sim: H.same_bits(run(sim, rows), run(sim, rows), OUT_KEYS), floor=fl[::3])
 
 
 # ---------------------------------------------------------------- refusals
@@ -347,8 +294,7 @@ def test_the_control_step_is_bit_identical(kp, scene):
 def test_refusals(kp, tmp_path):
     sim = handle(kp, DEFAULT_KPM)
     L, err = sim.L, lambda: sim.L.kp_last_error().decode()      # noqa: E731
-    bufs = {k: torch.full((5, *kp.ESTIMATE_OUTPUTS[k][0]), 7, dtype=kp.ESTIMATE_OUTPUTS[k][1], device="cuda") for k in kp.ESTIMATE_OUTPUTS}
-    full = kp.KpEstimateOut(*[ctypes.c_void_p(bufs[k].data_ptr()) for k in kp.ESTIMATE_OUTPUTS])
+    bufs, full = H.sentinel(kp.ESTIMATE_OUTPUTS, kp.KpEstimateOut)
     q = dev(np.tile(ID.f32(STD["qpos"]), (5, 1)))
     qp, blk = ctypes.c_void_p(q.data_ptr()), dev(np.tile(ID.f32(CF.parked_block()), (5, 1)))
     good = kp.KpEstimateCfg.default(sim.model)
@@ -374,9 +320,7 @@ def test_refusals(kp, tmp_path):
     wide = kp.KpSim(kp.KpModel(threads_per_env=128), 5)
     assert f(wide.h, 5, qp, None, None, None, by(good), by(full)) != 0 and "threads_per_env" in err()
     assert f(sim.h, 0, qp, None, None, None, by(good), by(full)) == 0, "n_rows == 0 does nothing"
-    torch.cuda.synchronize()
-    for k, b in bufs.items():
-        assert bool((b == 7).all()), f"a refused call launched nothing: {k}"
+    H.refused_calls_wrote_nothing(bufs)
     with pytest.raises(ValueError):
         sim.estimate_contacts(q, want=("qacc",))
     with pytest.raises(ValueError):

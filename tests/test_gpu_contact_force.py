@@ -15,6 +15,8 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 import contact_force_oracle as CF  # noqa: E402
+import rows_harness as H  # noqa: E402
+from rows_harness import dev  # noqa: E402
 from kinpoly_amd.model_compiler import DEFAULT_KPM, STEP_KPM, read_kpm  # noqa: E402
 from oracle.kpo import OracleSim  # noqa: E402
 
@@ -35,19 +37,12 @@ TOL_QFRC = 4 * 5.08e-3        # N / N m, qfrc_constraint; measured 5.08e-3
 TOL_QACC = 4 * 1.69e-2        # rad/s^2 (m/s^2), qacc; measured 1.69e-2 on accelerations up to 1.0e3
 TOL_TORQUE = 4 * 3.68e-4      # N m, the controller's torque (mode 2); measured 3.20e-4 (default controller), 3.68e-4 (meta-PD against tests/uhc_ctrl_oracle.py)
 TOL_OBJ_QACC = 4 * 5.74e-4    # object accelerations; measured 5.74e-4
-MEASURED = {}
+MEASURED = H.Measured()
 
 
 @pytest.fixture(scope="module")
 def kp():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test selected but no HIP device is visible")
-    from kinpoly_amd import sim as kpsim
-    return kpsim
-
-
-def dev(a, dt=torch.float32):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dt, device="cuda")
+    return H.gpu_module()
 
 
 def f32(a):
@@ -160,8 +155,7 @@ _LOCAL = {}
 
 
 def note(key, v):
-    MEASURED[key] = max(MEASURED.get(key, 0.0), float(v))
-    _LOCAL[key] = max(_LOCAL.get(key, 0.0), float(v))
+    MEASURED.note(key, v, _LOCAL)
 
 
 # ---------------------------------------------------------------- 4. parity
@@ -279,23 +273,13 @@ def test_read_out_leaves_the_control_step_bit_identical(kp, scene):
     sts = [base[e % len(base)] for e in range(67)]
     sims = [make_sim(kp, scene, sts, queue_slots=16) for _ in range(2)]        # 67 envs on 16 wave slots: the job queue (lean layout on the floor handle)
     act = dev(np.stack([inputs(s["name"])[0] for s in sts]))
-    for _ in range(3):
-        a = sims[0].contact_forces(action=act)
-        b = sims[0].contact_forces(action=act)
+
+    def between(sim):
+        a = sim.contact_forces(action=act)
+        b = sim.contact_forces(action=act)
         for k in a:
             assert torch.equal(a[k], b[k]), f"the same call twice: {k}"
-        for s in sims:
-            s.step_ctrl(act, 15)
-    assert sims[0].queue_counters()["claimed"] > 0
-    for k in kp.FIELDS:
-        try:
-            x = sims[0].get(k)
-        except kp.KinPolyNativeError:
-            with pytest.raises(kp.KinPolyNativeError):
-                sims[1].get(k)
-            continue
-        assert torch.equal(x.view(torch.int32), sims[1].get(k).view(torch.int32)), k
-    assert np.array_equal(sims[0].diag(), sims[1].diag())
+    H.control_step_untouched(kp, scene, between, pair=(sims, act))
 
 
 # ---------------------------------------------------------------- 8. mask
@@ -323,8 +307,7 @@ def test_refusals(kp):
     sim = make_sim(kp, "floor", sts)
     before = call(sim, sts, 2)
     L, err = sim.L, lambda: sim.L.kp_last_error().decode()      # noqa: E731
-    bufs = {k: torch.full((5, *kp.CONTACT_OUTPUTS[k][0]), 7, dtype=kp.CONTACT_OUTPUTS[k][1], device="cuda") for k in OUT_KEYS}
-    full = kp.KpContactOut(*[ctypes.c_void_p(bufs[k].data_ptr()) for k in OUT_KEYS])
+    bufs, full = H.sentinel(kp.CONTACT_OUTPUTS, kp.KpContactOut)
     act = dev(np.zeros((5, 75)))
     ap = ctypes.c_void_p(act.data_ptr())
     assert L.kp_sim_contact_forces(None, 0, None, None, ctypes.byref(full)) != 0 and "null handle" in err()
@@ -336,9 +319,7 @@ def test_refusals(kp):
         assert L.kp_sim_contact_forces(sim.h, mode, None, None, ctypes.byref(full)) != 0 and "act is null" in err()
     wide = kp.KpSim(kp.KpModel(threads_per_env=128), 5)
     assert L.kp_sim_contact_forces(wide.h, 0, None, None, ctypes.byref(full)) != 0 and "threads_per_env" in err()
-    torch.cuda.synchronize()
-    for k, b in bufs.items():
-        assert bool((b == 7).all()), f"a refused call launched nothing: {k}"
+    H.refused_calls_wrote_nothing(bufs)
     with pytest.raises(ValueError):
         sim.contact_forces(action=act, torque=act)
     after = call(sim, sts, 2)

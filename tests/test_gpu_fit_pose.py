@@ -14,9 +14,10 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-import contact_force_oracle as CF  # noqa: E402
 import fit_pose_oracle as FP  # noqa: E402
 import inverse_dynamics_oracle as ID  # noqa: E402
+import rows_harness as H  # noqa: E402
+from rows_harness import dev, handle  # noqa: E402
 from kinpoly_amd.model_compiler import DEFAULT_KPM, STEP_KPM, read_kpm  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,24 +47,10 @@ for _k, _c in CAP.items():
 
 @pytest.fixture(scope="module")
 def kp():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test selected but no HIP device is visible")
-    from kinpoly_amd import sim as kpsim
-    return kpsim
+    return H.gpu_module()
 
 
-def dev(a, dt=torch.float32):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dt, device="cuda")
-
-
-_SIMS, _MEMO = {}, {}
-
-
-def handle(kp, blob=DEFAULT_KPM, n=1, **opts):
-    key = (blob, n, tuple(sorted(opts.items())))
-    if key not in _SIMS:
-        _SIMS[key] = kp.KpSim(kp.KpModel(blob, **opts), n)
-    return _SIMS[key]
+_MEMO = {}
 
 
 def memo(key, make):
@@ -329,44 +316,18 @@ def test_bitwise_consistency(kp):
 
 @pytest.mark.parametrize("scene", ["floor", "h_push"])
 def test_the_control_step_is_bit_identical(kp, scene):
-    blob = DEFAULT_KPM if scene == "floor" else STEP_KPM
-    named = states()[0]
-    if scene == "floor":
-        sts = [dict(q=named[e % 5]["q"], v=named[e % 5]["v"], blk=None) for e in range(67)]
-    else:
-        q, v, blk, _ = CF.object_scenes(read_kpm(STEP_KPM), STD["qpos"])["h_push"]
-        sts = [dict(q=ID.f32(q), v=ID.f32(v), blk=ID.f32(blk)) for _ in range(67)]
-    sims = []
-    for _ in range(2):
-        sim = kp.KpSim(kp.KpModel(blob, queue_slots=16), 67)             # 67 envs on 16 wave slots: the job queue (lean layout on the floor handle)
-        if sts[0]["blk"] is not None:
-            sim.set_objects(dev(np.stack([s["blk"] for s in sts])))
-        sim.set_state(dev(np.stack([s["q"] for s in sts])), dev(np.stack([s["v"] for s in sts])))
-        sim.set_target(dev(np.tile(ID.f32(STD["qpos"]), (67, 1))))
-        sims.append(sim)
-    act = dev(np.random.default_rng(3).normal(size=(67, 75)) * 0.3)
     cs = reachable()
     a = [stack(cs, k, 5) for k in ("q0", "tgt_pos", "tgt_quat", "w_pos", "w_rot")]
     jq, jb, joff, _ = jacobian_rows()
-    for _ in range(3):
-        out = sims[0].fit_pose(*a, cfg=cfg(kp, n_iters=4))
+
+    def between(sim):
+        out = sim.fit_pose(*a, cfg=cfg(kp, n_iters=4))
         assert torch.isfinite(out["qpos"]).all()
-        stored = sims[0].fit_pose(sims[0].view("qpos"), sims[0].fk(sims[0].view("qpos"))["wbpos"].view(67, 24, 3), cfg=cfg(kp, n_iters=2))      # on the stored rows too
+        stored = sim.fit_pose(sim.view("qpos"), sim.fk(sim.view("qpos"))["wbpos"].view(67, 24, 3), cfg=cfg(kp, n_iters=2))      # on the stored rows too
         assert not stored["info"][:, 7].any()
-        assert torch.isfinite(sims[0].point_jacobian(sims[0].view("qpos"), dev(np.arange(67) % 24, torch.int32))).all()
-        sims[0].point_jacobian(dev(jq[:5]), dev(jb[:5], torch.int32), dev(joff[:5]))
-        for s in sims:
-            s.step_ctrl(act, 15)
-    assert sims[0].queue_counters()["claimed"] > 0
-    for k in kp.FIELDS:
-        try:
-            x = sims[0].get(k)
-        except kp.KinPolyNativeError:
-            with pytest.raises(kp.KinPolyNativeError):
-                sims[1].get(k)
-            continue
-        assert torch.equal(x.view(torch.int32), sims[1].get(k).view(torch.int32)), k
-    assert np.array_equal(sims[0].diag(), sims[1].diag())
+        assert torch.isfinite(sim.point_jacobian(sim.view("qpos"), dev(np.arange(67) % 24, torch.int32))).all()
+        sim.point_jacobian(dev(jq[:5]), dev(jb[:5], torch.int32), dev(joff[:5]))
+    H.control_step_untouched(kp, scene, between, floor=states()[0])
 
 
 # ---------------------------------------------------------------- 8. end to end
@@ -436,8 +397,7 @@ def test_refusals(kp):
     assert j(sim.h, 5, P(a[0]), P(body), None, None) != 0 and "null J" in err()
     assert j(wide.h, 5, P(a[0]), P(body), None, P(Jb)) != 0 and "threads_per_env" in err()
     assert j(sim.h, 0, P(a[0]), P(body), None, P(Jb)) == 0
-    torch.cuda.synchronize()
-    assert bool((qout == 7).all()) and bool((info == 7).all()) and bool((Jb == 7).all()), "a refused call launched nothing"
+    H.refused_calls_wrote_nothing(qout, info, Jb)
     # the Python layer: wrong shapes, host tensors, the configuration
     for call in (lambda: sim.fit_pose(a[0][:, :75], a[1]), lambda: sim.fit_pose(a[0], a[1][:4]), lambda: sim.fit_pose(a[0], a[1], a[2][:, :23]),
                  lambda: sim.fit_pose(a[0], a[1], w_pos=a[3][:, :5]), lambda: sim.fit_pose(a[0], a[1], q_prior=a[0][:, 7:].contiguous()),

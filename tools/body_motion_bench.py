@@ -4,55 +4,15 @@ work (the forward pass and one spatial_accumulate; no collide, no make_constrain
 should not be the slower one.  Device events around blocks of calls, medians of 5 blocks after a warm-up.  States: standing poses with joint noise,
 settled by 10 control steps; qacc = the accelerations the contact read-out solved for.
     python tools/body_motion_bench.py"""
-import os
-import statistics
-import sys
-
 import numpy as np
-import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
-
-from kinpoly_amd import sim as kpsim  # noqa: E402
+from _rows_bench import settled_floor, timed
 
 N = 4096
-std = np.load(os.path.join(ROOT, "tests", "golden", "standing_neutral.npz"))
-dev = torch.device("cuda", 0)
-t = lambda a, dt=torch.float32: torch.tensor(np.ascontiguousarray(a), dtype=dt, device=dev)  # noqa: E731
-
-
-def blocks(fn, reps, nblocks=5):
-    """(median, min, max) over nblocks of (event time of reps calls) / reps, in ms"""
-    out = []
-    for _ in range(nblocks):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record(); torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1) / reps)
-    return statistics.median(out), min(out), max(out)
-
-
-def timed(label, fn, rows, reps, base=None):
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    med, lo, hi = blocks(fn, reps)
-    tail = "" if base is None else f"   = {med / base:5.2f} x inverse_dynamics"
-    print(f"{label:58s} {med:8.4f} ms   ({lo:.4f} .. {hi:.4f})   {rows / med * 1e3 / 1e6:7.2f} M rows/s{tail}")
-    return med
-
 
 print("# ms per call, median (min .. max) of 5 blocks; the same rows for every line of a size")
 rng = np.random.default_rng(0)
-qpos = np.tile(std["qpos"], (N, 1)); qpos[:, 7:] += rng.normal(size=(N, 69)) * 0.1
-sim = kpsim.KpSim(kpsim.KpModel(kpsim.DEFAULT_KPM), N)
-sim.set_state(t(qpos), t(rng.normal(size=(N, 75)) * 0.3)); sim.set_target(t(np.tile(std["qpos"], (N, 1))))
-act = t(rng.normal(size=(N, 75)) * 0.2)
-for _ in range(10):
-    sim.step_ctrl(act, 15)
+sim, _ = settled_floor(N, rng)
 q, v = sim.get("qpos").clone(), sim.get("qvel").clone()
 a = sim.contact_forces(want=("qacc",))["qacc"].clone()
 for mult, reps in ((1, 20), (16, 5)):

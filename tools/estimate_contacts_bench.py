@@ -5,67 +5,19 @@ constraint rows once, the estimate runs its Newton iterations on the 6-vector.  
 warm-up.  Floor rows: standing poses with joint noise, settled by 10 control steps, qacc = the accelerations the read-out solved for.  Sit rows: the sit
 pose of tests/contact_force_oracle.py with joint noise.
     python tools/estimate_contacts_bench.py"""
-import os
-import statistics
-import sys
+import functools
 
 import numpy as np
-import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
-
-import contact_force_oracle as CF  # noqa: E402
-from kinpoly_amd import sim as kpsim  # noqa: E402
-from kinpoly_amd.model_compiler import read_kpm  # noqa: E402
+from _rows_bench import kpsim, motion_scene, timed
 
 N = 4096
-std = np.load(os.path.join(ROOT, "tests", "golden", "standing_neutral.npz"))
-dev = torch.device("cuda", 0)
-t = lambda a, dt=torch.float32: torch.tensor(np.ascontiguousarray(a), dtype=dt, device=dev)  # noqa: E731
-
-
-def blocks(fn, reps, nblocks=5):
-    """(median, min, max) over nblocks of (event time of reps calls) / reps, in ms"""
-    out = []
-    for _ in range(nblocks):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record(); torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1) / reps)
-    return statistics.median(out), min(out), max(out)
-
-
-def timed(label, fn, rows, reps, base=None):
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    med, lo, hi = blocks(fn, reps)
-    tail = "" if base is None else f"   = {med / base:5.2f} x inverse_dynamics"
-    print(f"{label:62s} {med:8.4f} ms   ({lo:.4f} .. {hi:.4f})   {rows / med * 1e3 / 1e6:7.2f} M rows/s{tail}")
-    return med
-
+timed = functools.partial(timed, width=62)
 
 print(f"# ms per call, median (min .. max) of 5 blocks; {N} distinct states per scene, repeated 16 times for R = {16 * N}")
 rng = np.random.default_rng(0)
 for scene in ("floor", "sit"):
-    if scene == "floor":
-        qpos = np.tile(std["qpos"], (N, 1)); qpos[:, 7:] += rng.normal(size=(N, 69)) * 0.1
-        sim = kpsim.KpSim(kpsim.KpModel(kpsim.DEFAULT_KPM), N)
-        sim.set_state(t(qpos), t(rng.normal(size=(N, 75)) * 0.3)); sim.set_target(t(np.tile(std["qpos"], (N, 1))))
-        act = t(rng.normal(size=(N, 75)) * 0.2)
-        for _ in range(10):
-            sim.step_ctrl(act, 15)
-        obj = None
-    else:
-        q, v, blk, _ = CF.object_scenes(read_kpm(kpsim.STEP_KPM), std["qpos"])["g_sit"]
-        qpos = np.tile(q, (N, 1)); qpos[:, 7 + 12:] += rng.normal(size=(N, 57)) * 0.05          # the legs stay as they sit
-        sim = kpsim.KpSim(kpsim.KpModel(kpsim.STEP_KPM, dynamic_objects=0), N)
-        obj = t(np.tile(blk, (N, 1)))
-        sim.set_objects(obj)
-        sim.set_state(t(qpos), t(rng.normal(size=(N, 75)) * 0.3))
+    sim, obj = motion_scene(scene, N, rng)
     q, v = sim.get("qpos").clone(), sim.get("qvel").clone()
     a = sim.contact_forces(want=("qacc",))["qacc"].clone()
     est = sim.estimate_contacts(q, v, a, obj, want=("ncon", "info"))

@@ -3,46 +3,15 @@
 qfrc_inverse alone) on the SAME rows in the same run as the yardstick.  Device events around blocks of calls, medians of 5 blocks after a warm-up.
 Rows: standing poses with joint noise as the truth, their FK as targets (positions and orientations), the fit starts 0.2 rad of joint noise away.
     python tools/fit_pose_bench.py"""
-import os
-import statistics
-import sys
+import functools
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
-
-from kinpoly_amd import sim as kpsim  # noqa: E402
+from _rows_bench import dev, kpsim, std, t, timed
 
 N = 4096
-std = np.load(os.path.join(ROOT, "tests", "golden", "standing_neutral.npz"))
-dev = torch.device("cuda", 0)
-t = lambda a, dt=torch.float32: torch.tensor(np.ascontiguousarray(a), dtype=dt, device=dev)  # noqa: E731
-
-
-def blocks(fn, reps, nblocks=5):
-    """(median, min, max) over nblocks of (event time of reps calls) / reps, in ms"""
-    out = []
-    for _ in range(nblocks):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record(); torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1) / reps)
-    return statistics.median(out), min(out), max(out)
-
-
-def timed(label, fn, rows, reps, base=None):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    med, lo, hi = blocks(fn, reps)
-    tail = "" if base is None else f"   = {med / base:6.2f} x inverse_dynamics"
-    print(f"{label:64s} {med:9.4f} ms   ({lo:.4f} .. {hi:.4f})   {rows / med * 1e3 / 1e6:7.3f} M rows/s{tail}")
-    return med
-
+timed = functools.partial(timed, width=64, wide=1, warm=3)
 
 def cfg(n_iters):
     c = kpsim.KpFitCfg.default()

@@ -1,7 +1,6 @@
 """What impulse pushes cost: the time of k_apply_impulse at 4096 envs with every env pushed, next to one control-step
 launch of the same handle, and CopycatAgent.sample env-steps/s without a schedule, with interval=30 and with interval=1.  HIP events,
 medians of 3 blocks.      python tools/push_bench.py [n_envs] [horizon]"""
-import os
 import statistics
 import sys
 import time
@@ -9,36 +8,22 @@ import time
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-from kinpoly_amd import sim as kpsim  # noqa: E402
-from kinpoly_amd.push import PushSchedule  # noqa: E402
-from kinpoly_amd.uhc_env import BatchedHumanoidEnv, CopycatAgent  # noqa: E402
+from _rows_bench import blocks as _blocks, dev, kpsim, std, t
+from kinpoly_amd.push import PushSchedule
+from kinpoly_amd.uhc_env import BatchedHumanoidEnv, CopycatAgent
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 horizon = int(sys.argv[2]) if len(sys.argv) > 2 else 32
-std = np.load(os.path.join(ROOT, "tests", "golden", "standing_neutral.npz"))
-dev = torch.device("cuda", 0)
 
 
-def blocks(fn, reps, nblocks=3):
-    """median over nblocks of (event time of reps calls) / reps, in ms"""
-    out = []
-    for _ in range(nblocks):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record(); torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1) / reps)
-    return statistics.median(out)
+def blocks(fn, reps):
+    """median over 3 blocks of (event time of reps calls) / reps, in ms"""
+    return _blocks(fn, reps, 3)[0]
 
 
 # ---- the kernel
 rng = np.random.default_rng(0)
 qpos = np.tile(std["qpos"], (n, 1)); qpos[:, 7:] += rng.normal(size=(n, 69)) * 0.1
-t = lambda a, dt=torch.float32: torch.tensor(np.ascontiguousarray(a), dtype=dt, device=dev)  # noqa: E731
 sim = kpsim.KpSim(kpsim.KpModel(), n)
 sim.set_state(t(qpos), t(rng.normal(size=(n, 75)) * 0.3)); sim.set_target(t(np.tile(std["qpos"], (n, 1))))
 act = t(rng.normal(size=(n, 75)) * 0.2)
