@@ -569,6 +569,41 @@ typedef struct { float *qpos, *info, *dq; } kp_fit_out;
 void kp_fit_cfg_default(kp_fit_cfg* cfg);
 int kp_sim_fit_pose(kp_sim*, int n_rows, const kp_fit_in* in, const kp_fit_cfg* cfg, const kp_fit_out* out);
 
+/* Pose fitting on ROWS to POINTS AT BODY OFFSETS, with a floor that holds: mocap markers on the surface, 3D key points (nose, ears, toes, heels,
+ * finger tips), end-effector targets; occluded points; hull vertices kept out of the ground.  No reference counterpart (deviation 43;
+ * DESIGN.md section 20).  Per row, n_iters Levenberg-Marquardt iterations on
+ *     c(q) = c_fit(q)                                              kp_sim_fit_pose's three terms (tgt_pos is optional here)
+ *          + 1/2 sum_k w_k |t_k - (x_b(k) + R_b(k) o_k)|^2          points: body b(k), offset o_k in the body frame, world target t_k
+ *          + 1/2 w_floor sum_v min(0, z_v - floor_z)^2             every hull vertex v of every body (the model blob's verts / vert_adr)
+ * The iteration, q (+) dq, clamp_limits, the accept rule (cost finite and strictly smaller) and the mu schedule are kp_sim_fit_pose's.  The GRADIENT is
+ * exact: J_p^T w e per point, with e = (0, 0, floor_z - z_v) on the vertices with z_v < floor_z.  The MATRIX is J^T W J + diag(mu damp + w_prior) with
+ * every point and every vertex below the floor counted as an ISOTROPIC point mass (w_k, w_floor) at its place: a weighted point rigidly attached to a
+ * body is a point mass, so the matrix is still the joint-space inertia of the same tree and the articulated-body pass solves it.  For the points that
+ * is Gauss-Newton itself; for the floor it is a majoriser of the point-to-plane term (w I >= w n n^T), not its Gauss-Newton block.  The accept test
+ * runs on the true cost, so descent stays monotone.
+ *   markers  the marker set, shared by all rows, on the HOST: n_points K (0 .. 1024), pt_body int32 [K] (0..23), pt_offset float [K,3] (finite).  The
+ *            call checks it, orders the points by body (stable) and keeps the ordered table in a scratch buffer of the handle; a call with another
+ *            marker set than the one before waits for the stream once.
+ *   in       device rows: qpos0 [R,76] required; pt_tgt [R,K,3] required when K > 0; pt_w [R,K] or NULL (ones); tgt_pos [R,24,3] or NULL (no origin
+ *            term); tgt_quat, w_pos, w_rot, q_prior, w_prior as in kp_fit_in: w_rot needs tgt_quat.  At least one of K > 0 and tgt_pos.
+ *            A point with w <= 0 is skipped and its target is not read into anything: it may be NaN (an occluded marker).  A NaN weight, or a target
+ *            that is not finite under a positive weight, gives the row status 1.
+ *   cfg      kp_fit_points_cfg_default: kp_fit_cfg_default's values, w_floor 0 (>= 0 and finite; 0 switches the term off), floor_z 0 (finite).
+ *   out      qpos [R,76] and info [R,12] required.  info 0..7 as kp_sim_fit_pose; 8: max |e_k| and 9: rms |e_k| over the points with a positive
+ *            weight (m); 10: the deepest hull vertex below floor_z at the result (m, >= 0) and 11: the number of hull vertices below it, both
+ *            computed whether or not w_floor > 0.  dq [R,75] or NULL.  pt_err [R,K] or NULL: the distance at the result in the caller's point
+ *            order, 0 for skipped points.  A row with status 1 ran no iteration, returns its input and zeros in info 8..11 and pt_err.
+ * A row's result depends on that row alone.  Enqueued on the handle's stream; nothing else the handle stores is read or written.  n_rows == 0 does
+ * nothing.  Refused (-1, kp_last_error names the argument) before the first HIP call: what kp_sim_fit_pose refuses (tgt_pos may be null), null markers,
+ * n_points outside 0 .. 1024, null pt_body / pt_offset with K > 0, a body outside 0..23, an offset that is not finite, null pt_tgt with K > 0, K == 0
+ * without tgt_pos, w_floor < 0 or not finite, floor_z not finite. */
+typedef struct { int n_points; const int32_t* pt_body; const float* pt_offset; } kp_marker_set;
+typedef struct { const float *qpos0, *pt_tgt, *pt_w, *tgt_pos, *tgt_quat, *w_pos, *w_rot, *q_prior, *w_prior; } kp_fit_points_in;
+typedef struct { kp_fit_cfg fit; float w_floor, floor_z; } kp_fit_points_cfg;
+typedef struct { float *qpos, *info, *dq, *pt_err; } kp_fit_points_out;
+void kp_fit_points_cfg_default(kp_fit_points_cfg* cfg);
+int kp_sim_fit_points(kp_sim*, int n_rows, const kp_marker_set* markers, const kp_fit_points_in* in, const kp_fit_points_cfg* cfg, const kp_fit_points_out* out);
+
 /* Contact forces ESTIMATED from kinematics on motion ROWS: the ground reaction a motion would need.  No reference counterpart and no mujoco-py one
  * (deviation 42); it is the support-force estimate of physics-based pose estimation and biomechanics.  kp_sim_inverse_dynamics charges
  * a row the forces of the soft-constraint model, a function of how many millimetres a hull penetrates; this call asks which forces inside the friction

@@ -1,7 +1,7 @@
 // kp_readout.hpp -- the kernels beside the control step that are built from its device functions (kp_step_device.hpp): impulse pushes (kp_push.hpp,
 // DESIGN.md section 12), the contact-force read-out (kp_contact_force.hpp, section 14) inverse dynamics on motion rows (kp_inverse_dyn.hpp,
 // section 15), body motion, momentum and energy on motion rows (kp_body_motion.hpp, section 16) and point Jacobians and pose fitting on motion rows
-// (kp_fit_pose.hpp, section 17) and contact forces estimated from kinematics on motion rows (kp_contact_estimate.hpp, section 18).  They live in their own translation unit (kp_readout.hip): however they specialise the shared device functions, the step kernels' unit
+// (kp_fit_pose.hpp, section 17; kp_fit_points.hpp, section 20) and contact forces estimated from kinematics on motion rows (kp_contact_estimate.hpp, section 18).  They live in their own translation unit (kp_readout.hip): however they specialise the shared device functions, the step kernels' unit
 // does not see it, so the step kernels' code cannot move with them.  kp_sim.hip keeps the entry points' argument checks and calls the launchers below.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -79,6 +79,22 @@ struct FitPoseArgs {
     float *qpos, *info, *dq;   // [R, 76], [R, 8], [R, 75] or null
 };
 
+// kp_fit_points_in, kp_fit_points_cfg and kp_fit_points_out of the C ABI in one block, and the marker set as kp_sim_fit_points uploads it
+struct FitPointsArgs {
+    DevTables T;
+    Params P;
+    int n_rows, row0;          // as InvDynArgs
+    const float *qpos0, *pt_tgt, *pt_w, *tgt_pos, *tgt_quat, *w_pos, *w_rot, *q_prior, *w_prior;      // [R, 76], [R, K, 3], then optional: [R, K], [R, 24, 3], [R, 24, 4], [R, 24], [R, 24], [R, 69], [R, 69]
+    int n_points;              // K
+    const float* pt_off;       // [K, 3] offsets in the body frame, ordered by body
+    const int32_t *pt_perm, *pt_adr;     // [K] the caller's index of ordered point j; [25] body b owns ordered points adr[b] .. adr[b + 1]
+    int n_iters, clamp_limits;
+    float mu0, mu_min, mu_max, mu_up, mu_down;
+    float damp[D_NV];
+    float w_floor, floor_z;
+    float *qpos, *info, *dq, *pt_err;    // [R, 76], [R, 12], [R, 75] or null, [R, K] or null (the caller's point order)
+};
+
 // every pointer optional (kp_estimate_out of the C ABI)
 struct EstimateOut {
     float *qfrc_inverse;       // [R, 75] need - qfrc_contact; its root part is the residual
@@ -115,6 +131,8 @@ void launch_body_motion(BodyMotionArgs A, hipStream_t stream);
 // point Jacobians and pose fitting on rows (kp_fit_pose.hpp, section 17): the first on its own small LDS layout, the second on EnvLds; launches of at most 2^24 rows each
 void launch_point_jacobian(PointJacArgs A, hipStream_t stream);
 void launch_fit_pose(FitPoseArgs A, hipStream_t stream);
+// pose fitting to points at body offsets with a floor term (kp_fit_points.hpp, section 20): on EnvLds; launches of at most 2^24 rows each
+void launch_fit_points(FitPointsArgs A, hipStream_t stream);
 // contact forces estimated from kinematics (kp_contact_estimate.hpp, section 18): obj as launch_inverse_dynamics; launches of at most 2^24 rows each
 void launch_estimate_contacts(EstimateArgs A, bool obj, hipStream_t stream);
 

@@ -97,6 +97,12 @@ struct InvDynScratch {    // kp_sim_inverse_dynamics with objects: what the plac
     float* buf = nullptr; size_t rows = 0;
 };
 
+struct MarkerScratch {    // kp_sim_fit_points: the marker set ordered by body as the kernel reads it (offsets [K,3] | perm [K] | adr [25], 4-byte words); allocated once
+    static constexpr int MAXK = 1024, WORDS = 4 * MAXK + 25;
+    void* buf = nullptr;
+    std::vector<uint32_t> host;       // what buf holds: a call with the same marker set uploads nothing
+};
+
 struct kp_sim {
     const kp_model* model = nullptr;
     int n = 0, device = 0;
@@ -117,6 +123,7 @@ struct kp_sim {
     ObjectRows obj;
     RenderTables rd;
     InvDynScratch idyn;
+    MarkerScratch mk;
     Timing tm;
     long launch_index = 0;
     int last_nsub = 15;                               // substeps of the last control step (kp_sim_lean_state)
@@ -676,6 +683,7 @@ void kp_sim_destroy(kp_sim* s) {
     for (void* p : s->allocs) hipFree(p);
     if (s->rd.partial) hipFree(s->rd.partial);
     if (s->idyn.buf) hipFree(s->idyn.buf);
+    if (s->mk.buf) hipFree(s->mk.buf);
     for (hipEvent_t e : s->tm.ring) hipEventDestroy(e);
     if (s->ovf.host) { hipHostFree(s->ovf.host); for (hipEvent_t e : s->ovf.ev) if (e) hipEventDestroy(e); }
     if (s->tm.ev0) hipEventDestroy(s->tm.ev0);
@@ -1996,6 +2004,77 @@ int kp_sim_fit_pose(kp_sim* s, int n_rows, const kp_fit_in* in, const kp_fit_cfg
     for (int d = 0; d < kp::D_NV; d++) A.damp[d] = cfg->damp[d];
     A.qpos = out->qpos; A.info = out->info; A.dq = out->dq;
     kp::launch_fit_pose(A, s->stream);
+    return launched();
+}
+
+void kp_fit_points_cfg_default(kp_fit_points_cfg* c) {
+    if (!c) return;
+    kp_fit_cfg_default(&c->fit);
+    c->w_floor = 0.f; c->floor_z = 0.f;
+}
+
+int kp_sim_fit_points(kp_sim* s, int n_rows, const kp_marker_set* markers, const kp_fit_points_in* in, const kp_fit_points_cfg* cfg, const kp_fit_points_out* out) {
+    const char* who = "kp_sim_fit_points";
+    kp::FitPointsArgs A{};
+    const int go = rows_begin(who, s, n_rows, false, A, [&] {
+        if (refuse_null(who, {{"markers", markers}, {"in", in}, {"cfg", cfg}, {"out", out}})) return -1;
+        const int K = markers->n_points;
+        if (K < 0 || K > MarkerScratch::MAXK) return fail("kp_sim_fit_points: n_points must be 0 .. " + std::to_string(MarkerScratch::MAXK));
+        if (K > 0 && refuse_null(who, {{"pt_body", markers->pt_body}, {"pt_offset", markers->pt_offset}})) return -1;
+        for (int k = 0; k < K; k++) {
+            if (markers->pt_body[k] < 0 || markers->pt_body[k] >= kp::D_NB) return fail("kp_sim_fit_points: pt_body[" + std::to_string(k) + "] must be 0 .. 23");
+            for (int i = 0; i < 3; i++)
+                if (!std::isfinite(markers->pt_offset[3 * k + i])) return fail("kp_sim_fit_points: pt_offset[" + std::to_string(k) + "] must be finite");
+        }
+        if (refuse_null(who, {{"qpos0", in->qpos0}})) return -1;
+        if (K > 0 && refuse_null(who, {{"pt_tgt", in->pt_tgt}})) return -1;
+        if (K == 0 && !in->tgt_pos) return fail("kp_sim_fit_points: nothing to fit (n_points == 0 and null tgt_pos)");
+        if (!in->q_prior != !in->w_prior) return fail("kp_sim_fit_points: q_prior and w_prior go together (one of them is null)");
+        if (refuse_null(who, {{"out qpos", out->qpos}, {"out info", out->info}})) return -1;
+        const kp_fit_cfg& f = cfg->fit;
+        if (f.n_iters < 0) return fail("kp_sim_fit_points: n_iters < 0");
+        if (refuse_not_positive(who, {{"mu0", f.mu0}, {"mu_min", f.mu_min}, {"mu_max", f.mu_max}, {"mu_up", f.mu_up}, {"mu_down", f.mu_down}}, false)) return -1;      // as kp_sim_fit_pose
+        for (int d = 0; d < kp::D_NV; d++)
+            if (!(f.damp[d] > 0.f)) return fail("kp_sim_fit_points: damp[" + std::to_string(d) + "] must be > 0");
+        if (!(cfg->w_floor >= 0.f) || !std::isfinite(cfg->w_floor)) return fail("kp_sim_fit_points: w_floor must be >= 0 and finite");
+        if (!std::isfinite(cfg->floor_z)) return fail("kp_sim_fit_points: floor_z must be finite");
+        return 0;
+    });
+    if (go <= 0) return go;
+    // the marker set ordered by body (stable: a body's points keep the caller's order): offsets [K,3] | perm [K] | adr [25]
+    const int K = markers->n_points;
+    std::vector<uint32_t> tab((size_t)4 * K + 25);
+    {
+        float* off = (float*)tab.data();
+        int32_t* perm = (int32_t*)tab.data() + 3 * K;
+        int32_t* adr = perm + K;
+        int j = 0;
+        for (int b = 0; b < kp::D_NB; b++) {
+            adr[b] = j;
+            for (int k = 0; k < K; k++)
+                if (markers->pt_body[k] == b) { perm[j] = k; for (int i = 0; i < 3; i++) off[3 * j + i] = markers->pt_offset[3 * k + i]; j++; }
+        }
+        adr[kp::D_NB] = j;
+    }
+    MarkerScratch& mk = s->mk;
+    if (!mk.buf) HIP_OK(hipMalloc(&mk.buf, sizeof(uint32_t) * MarkerScratch::WORDS));
+    if (tab != mk.host) {      // another marker set: the kernels of earlier calls may still read the old one
+        HIP_OK(hipStreamSynchronize(s->stream));
+        mk.host.clear();
+        HIP_OK(hipMemcpy(mk.buf, tab.data(), sizeof(uint32_t) * tab.size(), hipMemcpyHostToDevice));
+        mk.host = tab;
+    }
+    A.n_points = K;
+    A.pt_off = (const float*)mk.buf; A.pt_perm = (const int32_t*)mk.buf + 3 * K; A.pt_adr = A.pt_perm + K;
+    A.qpos0 = in->qpos0; A.pt_tgt = in->pt_tgt; A.pt_w = in->pt_w; A.tgt_pos = in->tgt_pos; A.tgt_quat = in->tgt_quat; A.w_pos = in->w_pos; A.w_rot = in->w_rot;
+    A.q_prior = in->q_prior; A.w_prior = in->w_prior;
+    const kp_fit_cfg& f = cfg->fit;
+    A.n_iters = f.n_iters; A.clamp_limits = f.clamp_limits;
+    A.mu0 = f.mu0; A.mu_min = f.mu_min; A.mu_max = f.mu_max; A.mu_up = f.mu_up; A.mu_down = f.mu_down;
+    for (int d = 0; d < kp::D_NV; d++) A.damp[d] = f.damp[d];
+    A.w_floor = cfg->w_floor; A.floor_z = cfg->floor_z;
+    A.qpos = out->qpos; A.info = out->info; A.dq = out->dq; A.pt_err = out->pt_err;
+    kp::launch_fit_points(A, s->stream);
     return launched();
 }
 

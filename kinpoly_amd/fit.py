@@ -33,6 +33,8 @@ class FitConfig:
     mu_down: float = 0.3
     damp: float | tuple = 1.0
     clamp_limits: bool = False
+    w_floor: float = 0.0          # fit_points only (kp_fit_points_cfg): weight of the hull vertices below floor_z; 0 switches the term off
+    floor_z: float = 0.0
     _names = ("mu0", "mu_min", "mu_max", "mu_up", "mu_down")
 
     def damp_vector(self) -> np.ndarray:
@@ -52,6 +54,10 @@ class FitConfig:
                 raise ValueError(f"FitConfig: {k} must be > 0, got {getattr(self, k)}")
         if not np.all(self.damp_vector() > 0.0):
             raise ValueError("FitConfig: every damp entry must be > 0")
+        if not (float(self.w_floor) >= 0.0 and np.isfinite(float(self.w_floor))):
+            raise ValueError(f"FitConfig: w_floor must be >= 0 and finite, got {self.w_floor}")
+        if not np.isfinite(float(self.floor_z)):
+            raise ValueError(f"FitConfig: floor_z must be finite, got {self.floor_z}")
         return self
 
     def native(self):
@@ -65,6 +71,14 @@ class FitConfig:
         for d, v in enumerate(self.damp_vector()):
             c.damp[d] = float(v)
         c.clamp_limits = int(bool(self.clamp_limits))
+        return c
+
+    def native_points(self):
+        """the KpFitPointsCfg kp_sim_fit_points takes"""
+        from .sim import KpFitPointsCfg
+        c = KpFitPointsCfg()
+        c.fit = self.native()
+        c.w_floor, c.floor_z = float(self.w_floor), float(self.floor_z)
         return c
 
 
@@ -85,9 +99,11 @@ def _check_targets(tgt_pos, tgt_quat):
 
 def fit_pose(sim, tgt_pos, tgt_quat=None, init=None, w_pos=None, w_rot=None, q_prior=None, w_prior=None, config: FitConfig | None = None, std_qpos=None) -> dict:
     """One fit per row: device tensors tgt_pos [..., 24, 3], tgt_quat [..., 24, 4] or None, init [..., 76] or None (default_init).  With tgt_quat and
-    no w_rot the orientations count with weight 1.  Returns KpSim.fit_pose's dict (qpos, info)."""
+    no w_rot the orientations count with weight 1.  Returns KpSim.fit_pose's dict (qpos, info).  With config.w_floor > 0 the same problem runs with the
+    floor term through KpSim.fit_points (no points, tgt_pos given): info then has 12 columns (FIT_POINTS_INFO)."""
     _check_targets(tgt_pos, tgt_quat)
-    cfg = (config or FitConfig()).native()
+    floor = float((config or FitConfig()).w_floor) > 0.0
+    cfg = (config or FitConfig()).native_points() if floor else (config or FitConfig()).native()
     tgt_pos = tgt_pos.float().contiguous()
     if init is None:
         init = default_init(tgt_pos, std_qpos)
@@ -95,11 +111,13 @@ def fit_pose(sim, tgt_pos, tgt_quat=None, init=None, w_pos=None, w_rot=None, q_p
         tgt_quat = tgt_quat.float().contiguous()
         if w_rot is None:
             w_rot = torch.ones(tuple(tgt_pos.shape[:-1]), dtype=torch.float32, device=tgt_pos.device)
+    if floor:
+        return sim.fit_points(init.float().contiguous(), np.zeros(0, np.int32), np.zeros((0, 3), np.float32), None, None, tgt_pos, tgt_quat, w_pos, w_rot, q_prior, w_prior, cfg=cfg)
     return sim.fit_pose(init.float().contiguous(), tgt_pos, tgt_quat, w_pos, w_rot, q_prior, w_prior, cfg=cfg)
 
 
 def fit_sequence(sim, tgt_pos, tgt_quat=None, mode: str = "chained", smooth: float = 1e-2, init=None, config: FitConfig | None = None, std_qpos=None) -> dict:
-    """Tracks tgt_pos [B, T, 24, 3] (tgt_quat [B, T, 24, 4] or None) -> qpos [B, T, 76], info [B, T, 8].
+    """Tracks tgt_pos [B, T, 24, 3] (tgt_quat [B, T, 24, 4] or None) -> qpos [B, T, 76], info [B, T, 8] (12 with config.w_floor > 0: fit_pose).
     independent: all B T rows in ONE call from one init (init [B, T, 76] or [76]-broadcastable, default default_init per frame).
     chained: frame t of all B tracks in one call, warm-started from the solution at t - 1, with that solution as the hinge prior at weight `smooth`
     (frame 0: from init [B, 76] or default_init, no prior)."""
@@ -125,17 +143,185 @@ def fit_sequence(sim, tgt_pos, tgt_quat=None, mode: str = "chained", smooth: flo
     return {"qpos": torch.stack(qs, 1), "info": torch.stack(infos, 1)}
 
 
+@dataclass(eq=False)
+class MarkerSet:
+    """K points rigidly attached to bodies: names [K], body [K] (0..23), offset [K, 3] in the body frames (m).  Shared by all rows of a fit."""
+    names: tuple
+    body: np.ndarray
+    offset: np.ndarray
+
+    def __post_init__(self):
+        from .sim import marker_arrays
+        self.names = tuple(str(n) for n in self.names)
+        self.body, self.offset = marker_arrays("MarkerSet", self.body, self.offset)
+        if len(self.names) != len(self.body):
+            raise ValueError(f"MarkerSet: {len(self.names)} names for {len(self.body)} points")
+        if len(set(self.names)) != len(self.names):
+            raise ValueError("MarkerSet: names must be unique")
+
+    def __len__(self):
+        return len(self.body)
+
+    def __eq__(self, other):
+        return isinstance(other, MarkerSet) and self.names == other.names and np.array_equal(self.body, other.body) and np.array_equal(self.offset, other.offset)
+
+    __hash__ = None
+
+    @classmethod
+    def body_origins(cls):
+        """the 24 body origins as points: fit_points on these is fit_pose on tgt_pos"""
+        return cls(tuple(f"body{b}" for b in range(NB)), np.arange(NB), np.zeros((NB, 3)))
+
+    @classmethod
+    def from_pose(cls, sim, qpos, world_points, body, names=None):
+        """offsets calibrated from ONE pose: o = R_b^T (p - x_b) with the engine's forward kinematics (kp_sim_fk) at qpos [76]; world_points [K, 3],
+        body [K]"""
+        p = np.asarray(world_points, np.float64).reshape(-1, 3)
+        body = np.asarray(body)
+        if body.shape != (len(p),):
+            raise ValueError(f"MarkerSet.from_pose: {len(p)} points and body {body.shape}")
+        if len(p) and (body.min() < 0 or body.max() >= NB):
+            raise ValueError("MarkerSet.from_pose: body must lie in 0..23")
+        q = torch.as_tensor(np.asarray(qpos, np.float32).reshape(1, NQ), device=sim.device)
+        out = sim.fk(q)
+        x = out["wbpos"].view(NB, 3).double().cpu().numpy()[body]
+        qt = out["wbquat"].view(NB, 4).double().cpu().numpy()[body]
+        d = p - x
+        # R^T d for the unit quaternion (w, u): the rotation by its conjugate
+        w, u = qt[:, :1], -qt[:, 1:]
+        t = 2.0 * np.cross(u, d)
+        off = d + w * t + np.cross(u, t)
+        return cls(tuple(names) if names is not None else tuple(f"m{k}" for k in range(len(p))), body, off)
+
+    def save(self, path):
+        import json
+        with open(path, "w") as f:
+            json.dump({"names": list(self.names), "body": [int(b) for b in self.body], "offset": [[float(v) for v in o] for o in self.offset]}, f, indent=1)
+
+    @classmethod
+    def load(cls, path):
+        import json
+        with open(path) as f:
+            d = json.load(f)
+        for k in ("names", "body", "offset"):
+            if k not in d:
+                raise ValueError(f"MarkerSet.load: {path} has no {k!r}")
+        return cls(tuple(d["names"]), np.asarray(d["body"], np.int64).reshape(-1), np.asarray(d["offset"], np.float64).reshape(-1, 3))
+
+
+def occlusion_weights(tgt, w=None):
+    """(targets, weights) as fit_points hands them on: a point whose target holds a NaN gets weight 0 (an occluded marker); w None: ones"""
+    seen = ~torch.isnan(tgt).any(dim=-1)
+    w = torch.ones(tuple(tgt.shape[:-1]), dtype=torch.float32, device=tgt.device) if w is None else w.float()
+    return tgt, torch.where(seen, w, torch.zeros_like(w)).contiguous()
+
+
+def fit_points(sim, markers: MarkerSet, tgt, w=None, init=None, tgt_pos=None, tgt_quat=None, w_pos=None, w_rot=None, q_prior=None, w_prior=None,
+               config: FitConfig | None = None, std_qpos=None, want=("qpos", "info")) -> dict:
+    """One fit per row to the world targets tgt [..., K, 3] of the marker set (device tensors); w [..., K] or None (ones).  A target with a NaN is an
+    occluded marker: its weight becomes 0 here.  init [..., 76] or None: the standing pose, translated so that its pelvis sits at the mean of the
+    row's visible targets minus the same mean of the standing pose's markers.  config.w_floor / floor_z switch the floor term on.  Returns
+    KpSim.fit_points' dict."""
+    K = len(markers)
+    if tgt.dim() < 2 or tuple(tgt.shape[-2:]) != (K, 3):
+        raise ValueError(f"fit_points: tgt must be [..., {K}, 3] for this marker set, got {tuple(tgt.shape)}")
+    if w is not None and tuple(w.shape) != tuple(tgt.shape[:-1]):
+        raise ValueError(f"fit_points: w must be {tuple(tgt.shape[:-1])}, got {tuple(w.shape)}")
+    cfg = (config or FitConfig()).native_points()
+    tgt, w = occlusion_weights(tgt.float().contiguous(), w)
+    if init is None:
+        init = default_init_points(sim, markers, tgt, w, std_qpos)
+    if tgt_quat is not None and w_rot is None:
+        w_rot = torch.ones(tuple(tgt.shape[:-2]) + (NB,), dtype=torch.float32, device=tgt.device)
+    return sim.fit_points(init.float().contiguous(), markers.body, markers.offset, tgt, w, tgt_pos, tgt_quat, w_pos, w_rot, q_prior, w_prior, cfg=cfg, want=want)
+
+
+def default_init_points(sim, markers: MarkerSet, tgt, w, std_qpos=None) -> torch.Tensor:
+    """the standing pose, translated by (weighted mean of the row's targets) - (the same mean of the standing pose's own markers): [..., 76]"""
+    std = np.asarray(standing_qpos() if std_qpos is None else std_qpos, np.float64)
+    fk = sim.fk(torch.as_tensor(std.astype(np.float32).reshape(1, NQ), device=sim.device))
+    x = fk["wbpos"].view(NB, 3)[torch.as_tensor(markers.body, dtype=torch.long, device=sim.device)]
+    qt = fk["wbquat"].view(NB, 4)[torch.as_tensor(markers.body, dtype=torch.long, device=sim.device)]
+    o = torch.as_tensor(markers.offset, device=sim.device)
+    u = qt[:, 1:]
+    t = 2.0 * torch.cross(u, o, dim=-1)
+    p_std = x + o + qt[:, :1] * t + torch.cross(u, t, dim=-1)                      # [K, 3] the standing pose's markers
+    ww = (w > 0).float().unsqueeze(-1)
+    n = ww.sum(-2).clamp(min=1.0)
+    shift = (torch.where(ww > 0, tgt, torch.zeros_like(tgt)) * ww).sum(-2) / n - (p_std * ww).sum(-2) / n
+    q = torch.as_tensor(std, dtype=torch.float32, device=sim.device).expand(tuple(tgt.shape[:-2]) + (NQ,)).clone()
+    q[..., :3] += shift
+    return q
+
+
+def fit_sequence_points(sim, markers: MarkerSet, tgt, w=None, mode: str = "chained", smooth: float = 1e-2, init=None, config: FitConfig | None = None, std_qpos=None) -> dict:
+    """Marker tracks tgt [B, T, K, 3] (w [B, T, K] or None; NaN targets are occluded) -> qpos [B, T, 76], info [B, T, 12], pt_err [B, T, K].
+    independent / chained as fit_sequence: chained warm-starts frame t from the solution at t - 1 with that solution as the hinge prior at weight
+    `smooth` (frame 0: from init [B, 76] or the default, no prior)."""
+    if mode not in ("chained", "independent"):
+        raise ValueError(f"fit_sequence_points: mode must be 'chained' or 'independent', got {mode!r}")
+    K = len(markers)
+    if tgt.dim() != 4 or tuple(tgt.shape[-2:]) != (K, 3):
+        raise ValueError(f"fit_sequence_points: tgt must be [B, T, {K}, 3], got {tuple(tgt.shape)}")
+    if not float(smooth) >= 0.0:
+        raise ValueError(f"fit_sequence_points: smooth must be >= 0, got {smooth}")
+    B, T = tgt.shape[:2]
+    want = ("qpos", "info", "pt_err")
+    if mode == "independent":
+        if init is not None:
+            init = init.float().expand(B, T, NQ)
+        return fit_points(sim, markers, tgt, w, init=init, config=config, std_qpos=std_qpos, want=want)
+    outs = {k: [] for k in want}
+    q = init
+    for t in range(T):
+        prior = {} if t == 0 or smooth == 0.0 else dict(q_prior=q[:, 7:].contiguous(), w_prior=torch.full((B, NU), float(smooth), dtype=torch.float32, device=tgt.device))
+        out = fit_points(sim, markers, tgt[:, t], None if w is None else w[:, t], init=q, config=config, std_qpos=std_qpos, want=want, **prior)
+        q = out["qpos"]
+        for k in want:
+            outs[k].append(out[k])
+    return {k: torch.stack(v, 1) for k, v in outs.items()}
+
+
+def points_report(names, marker_names, pt_err, pt_w, info, n_iters: int) -> dict:
+    """take -> the columns of a marker fit (host arrays): pt_err [B, T, K] (0 where skipped), pt_w [B, T, K] (> 0: the point counted), info [B, T, 12].
+    Percentiles of the error over the counted points, per take and per marker; accepted share and failed rows as report_from_errors; the
+    penetration columns from info 10 / 11."""
+    err, w, info = np.asarray(pt_err, np.float64), np.asarray(pt_w, np.float64) > 0, np.asarray(info, np.float64)
+    if len(names) != err.shape[0] or info.shape[:2] != err.shape[:2] or w.shape != err.shape or len(marker_names) != err.shape[2]:
+        raise ValueError(f"points_report: {len(names)} names, {len(marker_names)} markers, errors {err.shape}, weights {w.shape}, info {info.shape}")
+    pct = lambda v: {f"p{p}": (float(np.percentile(v, p)) if v.size else None) for p in (50, 90, 99)}      # noqa: E731
+    out = {}
+    for b, k in enumerate(names):
+        e = err[b][w[b]]
+        out[k] = dict(mean_pt_err=float(e.mean()) if e.size else None, max_pt_err=float(e.max()) if e.size else None, **{f"pt_err_{n}": v for n, v in pct(e).items()},
+                      visible_share=float(w[b].mean()) if w[b].size else None,
+                      per_marker={m: pct(err[b, :, j][w[b, :, j]]) for j, m in enumerate(marker_names)},
+                      accepted_share=float(info[b, :, 2].sum() / max(1, n_iters * err.shape[1])), failed_rows=int((info[b, :, 7] != 0).sum()),
+                      **penetration_columns(info[b]))
+    return out
+
+
+def penetration_columns(info) -> dict:
+    """the floor figures of info rows [T, 12]: deepest hull vertex below the floor over the take (m), mean of the per-frame depth, frames with any"""
+    info = np.asarray(info, np.float64)
+    return dict(max_penetration=float(info[:, 10].max()), mean_penetration=float(info[:, 10].mean()), frames_penetrating=int((info[:, 11] > 0).sum()))
+
+
 def fit_report(sim, names, qpos, tgt_pos, info, n_iters: int) -> dict:
     """take -> dict(mean_pos_err, max_pos_err in metres over frames and bodies, accepted_share: accepted steps / iterations run, failed_rows: rows with
     status 1).  qpos [B, T, 76], tgt_pos [B, T, 24, 3], info [B, T, 8] of fit_sequence; the errors are measured with the engine's own forward kinematics."""
     B, T = qpos.shape[:2]
     wb = sim.fk(qpos.reshape(B * T, NQ).contiguous())["wbpos"].view(B, T, NB, 3)
     err = (wb - tgt_pos.float()).norm(dim=-1)
-    return report_from_errors(names, err.cpu().numpy(), info.cpu().numpy(), n_iters)
+    rep = report_from_errors(names, err.cpu().numpy(), info.cpu().numpy(), n_iters)
+    if info.shape[-1] >= 12:                      # fit_points' rows: the penetration columns are present
+        for b, k in enumerate(names):
+            rep[k].update(penetration_columns(info[b].cpu().numpy()))
+    return rep
 
 
 def report_from_errors(names, err, info, n_iters: int) -> dict:
-    """fit_report's host half: err [B, T, 24] position errors, info [B, T, 8]"""
+    """fit_report's host half: err [B, T, 24] position errors, info [B, T, 8] (or 12)"""
     err, info = np.asarray(err, np.float64), np.asarray(info, np.float64)
     if len(names) != err.shape[0] or info.shape[:2] != err.shape[:2]:
         raise ValueError(f"fit_report: {len(names)} names for errors {err.shape} and info {info.shape}")

@@ -184,6 +184,37 @@ class KpFitOut(C.Structure):
 FIT_INFO = {"cost0": 0, "cost": 1, "accepted": 2, "mu": 3, "max_epos": 4, "max_erot": 5, "dq_inf": 6, "status": 7}
 
 
+class KpMarkerSet(C.Structure):
+    """mirror of kp_marker_set (host side): n_points, pt_body int32 [K], pt_offset float [K, 3]"""
+    _fields_ = [("n_points", C.c_int), ("pt_body", C.c_void_p), ("pt_offset", C.c_void_p)]
+
+
+class KpFitPointsIn(C.Structure):
+    """mirror of kp_fit_points_in: the device rows kp_sim_fit_points reads (qpos0 required, pt_tgt with K > 0, the others may be NULL)"""
+    _fields_ = [(k, C.c_void_p) for k in ("qpos0", "pt_tgt", "pt_w", "tgt_pos", "tgt_quat", "w_pos", "w_rot", "q_prior", "w_prior")]
+
+
+class KpFitPointsCfg(C.Structure):
+    """mirror of kp_fit_points_cfg (host side): kp_sim_fit_pose's schedule (fit), the floor term's weight and height"""
+    _fields_ = [("fit", KpFitCfg), ("w_floor", C.c_float), ("floor_z", C.c_float)]
+
+    @classmethod
+    def default(cls):
+        c = cls()
+        load_library().kp_fit_points_cfg_default(C.byref(c))
+        return c
+
+
+class KpFitPointsOut(C.Structure):
+    """mirror of kp_fit_points_out: the device rows kp_sim_fit_points fills (dq and pt_err may be NULL)"""
+    _fields_ = [(k, C.c_void_p) for k in ("qpos", "info", "dq", "pt_err")]
+
+
+# the columns of KpSim.fit_points' info rows: FIT_INFO's, then the points' and the floor's figures at the result
+FIT_POINTS_INFO = {**FIT_INFO, "max_ept": 8, "rms_ept": 9, "max_depth": 10, "n_below": 11}
+MAX_POINTS = 1024
+
+
 class KpEstimateCfg(C.Structure):
     """mirror of kp_estimate_cfg (host side): the candidates' reach, the weights of the residual force / moment, the multiplier penalty, the friction
     coefficient (0: the model's) and the Newton iterations of kp_sim_estimate_contacts"""
@@ -233,6 +264,8 @@ _SIGNATURES = {
     "kp_sim_point_jacobian": (_I, [_V, _I, _V, _V, _V, _V]),      # handle, n_rows, qpos, body, offset, J
     "kp_fit_cfg_default": (None, [C.POINTER(KpFitCfg)]),
     "kp_sim_fit_pose": (_I, [_V, _I, _V, _V, _V]),      # handle, n_rows, kp_fit_in*, kp_fit_cfg*, kp_fit_out*
+    "kp_fit_points_cfg_default": (None, [C.POINTER(KpFitPointsCfg)]),
+    "kp_sim_fit_points": (_I, [_V, _I, _V, _V, _V, _V]),      # handle, n_rows, kp_marker_set*, kp_fit_points_in*, kp_fit_points_cfg*, kp_fit_points_out*
     "kp_estimate_cfg_default": (None, [_V, C.POINTER(KpEstimateCfg)]),
     "kp_sim_estimate_contacts": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]),      # handle, n_rows, qpos, qvel, qacc, obj_qpos, kp_estimate_cfg*, kp_estimate_out*
     "kp_sim_fk": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]), "kp_sim_fk_backward": (_I, [_V, _I, _V, _V, _V, _V, _V]),
@@ -379,6 +412,33 @@ def _device_view(ptr, shape, device, typestr="<f4") -> torch.Tensor:
 # share.  Plain functions on tensors of any device (tests/test_rows_binding_cpu.py runs them without the library); the methods add _dev's device check.
 _JAC_OUTPUTS = {"J": ((6, NV), torch.float32)}
 _FIT_OUTPUTS = {"qpos": ((NQ,), torch.float32), "info": ((8,), torch.float32), "dq": ((NV,), torch.float32)}      # in kp_fit_out's order
+
+
+def fit_points_outputs(K: int) -> dict:
+    """outputs of KpSim.fit_points for K points: name -> (trailing shape, dtype), in kp_fit_points_out's order"""
+    return {"qpos": ((NQ,), torch.float32), "info": ((12,), torch.float32), "dq": ((NV,), torch.float32), "pt_err": ((int(K),), torch.float32)}
+
+
+def marker_arrays(who, pt_body, pt_offset):
+    """The marker set of a fit_points call as the host arrays kp_marker_set points at: body int32 [K], offset float32 [K, 3], after the entry point's
+    own checks (K 0 .. 1024, bodies 0..23, finite offsets), so that a bad set is a ValueError before anything native runs."""
+    body = np.asarray(pt_body)
+    if body.ndim != 1 or (body.size and not np.issubdtype(body.dtype, np.integer)):
+        raise ValueError(f"{who}: pt_body must be a 1-d integer array, got {body.dtype} {body.shape}")
+    K = body.shape[0]
+    off = np.asarray(pt_offset, np.float64)
+    if K == 0:
+        off = off.reshape(0, 3)
+    if off.shape != (K, 3):
+        raise ValueError(f"{who}: pt_offset must be ({K}, 3), got {off.shape}")
+    if K > MAX_POINTS:
+        raise ValueError(f"{who}: at most {MAX_POINTS} points, got {K}")
+    if K and (body.min() < 0 or body.max() >= 24):
+        raise ValueError(f"{who}: pt_body must lie in 0..23")
+    off = np.ascontiguousarray(off, np.float32)
+    if not np.all(np.isfinite(off)):
+        raise ValueError(f"{who}: pt_offset must be finite")
+    return np.ascontiguousarray(body, np.int32), off
 
 
 def _motion_spec(qpos, qvel, qacc, obj_qpos=None):
@@ -691,6 +751,38 @@ class KpSim:
         out = _rows_outputs(R, _FIT_OUTPUTS, ("qpos", "info", "dq") if want_dq else ("qpos", "info"), self.device)
         if R > 0:
             _check(self.L.kp_sim_fit_pose(self.h, R, C.byref(KpFitIn(*ins)), C.byref(cfg), C.byref(_rows_struct(KpFitOut, _FIT_OUTPUTS, out))), "kp_sim_fit_pose")
+        return _rows_view(out, lead)
+
+    def fit_points(self, qpos0, pt_body, pt_offset, pt_tgt=None, pt_w=None, tgt_pos=None, tgt_quat=None, w_pos=None, w_rot=None, q_prior=None, w_prior=None,
+                   cfg: KpFitPointsCfg | None = None, want=("qpos", "info")) -> dict:
+        """Pose fitting to points at body offsets, with a floor term (kp_sim_fit_points): Levenberg-Marquardt from qpos0 [..., 76].  The marker set
+        is HOST data shared by all rows: pt_body [K] integers 0..23, pt_offset [K, 3] in the body frames (K 0 .. 1024).  Device rows of any leading
+        shape, the same on every input: pt_tgt [..., K, 3] (required when K > 0), pt_w [..., K] or None (ones; a point with w <= 0 is skipped and its
+        target may be NaN), tgt_pos [..., 24, 3] or None (no origin term), tgt_quat, w_pos, w_rot, q_prior, w_prior as in fit_pose.  At least one of
+        K > 0 and tgt_pos.  cfg: a KpFitPointsCfg (None: its default, the floor term off).  want: names of fit_points_outputs(K).  Returns a dict of
+        device tensors: qpos [..., 76], info [..., 12] (FIT_POINTS_INFO), dq [..., 75], pt_err [..., K] (the caller's point order).  Nothing the
+        handle stores is read or changed."""
+        body, off = marker_arrays("fit_points", pt_body, pt_offset)
+        K = body.shape[0]
+        table = fit_points_outputs(K)
+        want = _rows_want("fit_points", want, table)
+        if (q_prior is None) != (w_prior is None):
+            raise ValueError("fit_points: q_prior and w_prior go together")
+        if K == 0 and tgt_pos is None:
+            raise ValueError("fit_points: nothing to fit (no points and no tgt_pos)")
+        f32 = torch.float32
+        spec = [("qpos0", qpos0, (NQ,), f32, True), ("pt_tgt", pt_tgt, (K, 3), f32, K > 0), ("pt_w", pt_w, (K,), f32, False), ("tgt_pos", tgt_pos, (24, 3), f32, False),
+                ("tgt_quat", tgt_quat, (24, 4), f32, False), ("w_pos", w_pos, (24,), f32, False), ("w_rot", w_rot, (24,), f32, False),
+                ("q_prior", q_prior, (69,), f32, False), ("w_prior", w_prior, (69,), f32, False)]
+        lead, R, rows = _rows_inputs("fit_points", spec)
+        ins = _rows_ptrs("fit_points", spec, rows)
+        cfg = KpFitPointsCfg.default() if cfg is None else cfg
+        out = _rows_outputs(R, table, want, self.device)
+        if R > 0:
+            need = {k: out[k] if k in out else torch.empty((R, *table[k][0]), dtype=f32, device=self.device) for k in ("qpos", "info")}      # the two the entry point requires
+            ms = KpMarkerSet(K, body.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p))
+            _check(self.L.kp_sim_fit_points(self.h, R, C.byref(ms), C.byref(KpFitPointsIn(*ins)), C.byref(cfg), C.byref(_rows_struct(KpFitPointsOut, table, {**need, **out}))),
+                   "kp_sim_fit_points")
         return _rows_view(out, lead)
 
     def fk(self, qpos_rows: torch.Tensor):

@@ -3,8 +3,12 @@
 reference gets qpos from SMPL axis-angles offline (uhc/data_process); this is the way in for marker or key-point tracks.
 
     python scripts/fit_takes.py --tracks in.pkl --out takes.pkl [--mode chained|independent] [--iters N] [--smooth W] [--limits]
+                                [--markers set.json] [--floor W [--floor_z Z]]
 
 in.pkl:  {take: {"wbpos": [T, 24, 3], optional "wbquat": [T, 24, 4], optional "obj_pose"}} (joblib or pickle).
+         With --markers set.json (a kinpoly_amd.fit.MarkerSet: names, body, offset): {take: {"markers": [T, K, 3], optional "obj_pose"}}, NaN where a
+         marker is occluded.  --floor W (> 0; 0 switches the term off) keeps the hull vertices above floor_z with weight W, with
+         either kind of input; the report then gains the penetration columns, and with --markers the per-marker error percentiles.
 out:     {take: {"qpos": [T, 76], "pose_aa": zeros [T, 72], "trans": zeros [T, 3], (obj_pose as given)}}: the schema AmassSingleDataset reads (of pose_aa
          and trans only the length is read, by its length filter), and next to it fit_report.json (per take: mean / max position error, share of
          accepted steps, failed rows).
@@ -19,6 +23,45 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def load_marker_tracks(path, markers):
+    """{take: {"markers": [T, K, 3], ...}} for the K points of `markers`"""
+    import joblib
+    tracks = joblib.load(path)
+    K = len(markers)
+    if not isinstance(tracks, dict) or not tracks:
+        raise ValueError(f"{path}: expected a non-empty dict take -> {{'markers': [T, {K}, 3], ...}}")
+    for k, v in tracks.items():
+        if "markers" not in v:
+            raise ValueError(f"take '{k}': no 'markers' (--markers reads marker tracks, not wbpos)")
+        m = np.asarray(v["markers"])
+        if m.ndim != 3 or m.shape[1:] != (K, 3) or m.shape[0] < 1:
+            raise ValueError(f"take '{k}': markers must be [T, {K}, 3] for the {K} points of the marker set, got {m.shape}")
+    return tracks
+
+
+def fit_marker_tracks(sim, tracks: dict, markers, mode="chained", iters=30, smooth=1e-2, limits=False, w_floor=0.0, floor_z=0.0):
+    """fit_tracks for points of a marker set (tracks[take]["markers"] [T, K, 3], NaN: occluded) through fit_sequence_points; the floor term with w_floor > 0"""
+    from kinpoly_amd import fit
+    names = list(tracks)
+    K = len(markers)
+    arrs = [np.asarray(tracks[k]["markers"], np.float32).reshape(-1, K, 3) for k in names]
+    lens = [a.shape[0] for a in arrs]
+    Tm = max(lens)
+    tgt = torch.as_tensor(np.stack([np.concatenate([a, np.repeat(a[-1:], Tm - a.shape[0], 0)], 0) for a in arrs]), device=sim.device)
+    cfg = fit.FitConfig(n_iters=iters, clamp_limits=limits, w_floor=w_floor, floor_z=floor_z)
+    out = fit.fit_sequence_points(sim, markers, tgt, mode=mode, smooth=smooth, config=cfg)
+    seen = (~torch.isnan(tgt).any(-1)).float()
+    rep = fit.points_report(names, markers.names, out["pt_err"].cpu().numpy(), seen.cpu().numpy(), out["info"].cpu().numpy(), iters)
+    qpos = out["qpos"].double().cpu().numpy()
+    takes = {}
+    for b, k in enumerate(names):
+        T = lens[b]
+        takes[k] = {"qpos": qpos[b, :T], "pose_aa": np.zeros((T, 72)), "trans": np.zeros((T, 3))}
+        if tracks[k].get("obj_pose") is not None:
+            takes[k]["obj_pose"] = np.asarray(tracks[k]["obj_pose"])
+    return takes, rep
 
 
 def load_tracks(path):
@@ -37,9 +80,10 @@ def load_tracks(path):
     return tracks
 
 
-def fit_tracks(sim, tracks: dict, mode="chained", iters=30, smooth=1e-2, limits=False):
+def fit_tracks(sim, tracks: dict, mode="chained", iters=30, smooth=1e-2, limits=False, w_floor=0.0, floor_z=0.0):
     """(takes in AmassSingleDataset's schema, report).  All takes go through ONE fit_sequence: shorter tracks are padded with their last frame and cut
-    again (a padded frame costs a fit and changes nothing before it).  Orientations are used only when every take carries them."""
+    again (a padded frame costs a fit and changes nothing before it).  Orientations are used only when every take carries them.  w_floor > 0: the same
+    targets with the floor term (fit.fit_pose routes the call through kp_sim_fit_points); the report then gains the penetration columns."""
     from kinpoly_amd import fit
     names = list(tracks)
     lens = [np.asarray(tracks[k]["wbpos"]).reshape(-1, 24, 3).shape[0] for k in names]
@@ -54,7 +98,7 @@ def fit_tracks(sim, tracks: dict, mode="chained", iters=30, smooth=1e-2, limits=
 
     tp = padded("wbpos", 3)
     tq = padded("wbquat", 4) if all(tracks[k].get("wbquat") is not None for k in names) else None
-    cfg = fit.FitConfig(n_iters=iters, clamp_limits=limits)
+    cfg = fit.FitConfig(n_iters=iters, clamp_limits=limits, w_floor=w_floor, floor_z=floor_z)
     out = fit.fit_sequence(sim, tp, tq, mode=mode, smooth=smooth, config=cfg)
     rep = fit.fit_report(sim, names, out["qpos"], tp, out["info"], iters)
     qpos = out["qpos"].double().cpu().numpy()
@@ -75,12 +119,30 @@ def main(argv=None, sim=None):
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--smooth", type=float, default=1e-2)
     ap.add_argument("--limits", action="store_true")
+    ap.add_argument("--markers", default=None, help="a MarkerSet json: the tracks carry 'markers' [T, K, 3] in place of wbpos")
+    ap.add_argument("--floor", type=float, default=None, help="weight of the floor term (hull vertices below --floor_z)")
+    ap.add_argument("--floor_z", type=float, default=0.0)
     a = ap.parse_args(argv)
-    tracks = load_tracks(a.tracks)
+    if a.floor is not None and not (a.floor >= 0.0 and np.isfinite(a.floor)):
+        ap.error("--floor must be >= 0 and finite")
+    if a.floor is None and a.floor_z != 0.0:
+        ap.error("--floor_z needs --floor")
+    markers = None
+    if a.markers is not None:
+        from kinpoly_amd import fit
+        markers = fit.MarkerSet.load(a.markers)
+        tracks = load_marker_tracks(a.tracks, markers)
+    else:
+        tracks = load_tracks(a.tracks)
     if sim is None:
         from kinpoly_amd import sim as kpsim
         sim = kpsim.KpSim(kpsim.KpModel(), 1)
-    takes, rep = fit_tracks(sim, tracks, a.mode, a.iters, a.smooth, a.limits)
+    if markers is not None:
+        takes, rep = fit_marker_tracks(sim, tracks, markers, a.mode, a.iters, a.smooth, a.limits, a.floor or 0.0, a.floor_z)
+    elif a.floor:                  # positions (and orientations, where every take carries them) with the floor term; --floor 0 is the term switched off
+        takes, rep = fit_tracks(sim, tracks, a.mode, a.iters, a.smooth, a.limits, a.floor, a.floor_z)
+    else:
+        takes, rep = fit_tracks(sim, tracks, a.mode, a.iters, a.smooth, a.limits)
     import joblib
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     joblib.dump(takes, a.out)
@@ -88,7 +150,7 @@ def main(argv=None, sim=None):
     with open(rp, "w") as f:
         json.dump(rep, f, indent=1)
     print(json.dumps({"takes": len(takes), "frames": int(sum(len(v["qpos"]) for v in takes.values())), "out": a.out, "report": rp,
-                      "max_pos_err": max(r["max_pos_err"] for r in rep.values())}))
+                      "max_pos_err": max(r["max_pos_err" if "max_pos_err" in r else "max_pt_err"] or 0.0 for r in rep.values())}))
     return takes, rep
 
 
