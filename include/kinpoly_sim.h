@@ -604,6 +604,34 @@ typedef struct { float *qpos, *info, *dq, *pt_err; } kp_fit_points_out;
 void kp_fit_points_cfg_default(kp_fit_points_cfg* cfg);
 int kp_sim_fit_points(kp_sim*, int n_rows, const kp_marker_set* markers, const kp_fit_points_in* in, const kp_fit_points_cfg* cfg, const kp_fit_points_out* out);
 
+/* Pose fitting on ROWS that keeps the hulls out of the scene's STATIC OBJECTS: kp_sim_fit_points with one more term.  No reference counterpart
+ * (deviation 44).  obj_qpos [R,35] are the rows' object poses; the objects within 50 m are static boxes and
+ * z-axis cylinders, placed exactly as for kp_sim_inverse_dynamics (at most 8 geoms per row).  Per row
+ *     c(q) = kp_sim_fit_points' cost + 1/2 w_obj sum over pairs (hull b, geom g) sum_{v in footprint of f*} max(0, d_f* - n_f* . x_v)^2
+ * A pair is skipped when sdf_g(xpos_b) - body_rbound[b] > 0.  Candidate planes (n, d): a box's faces (+-a_i, n.c + h_i) in the order +x -x +y -y +z -z;
+ * a cylinder's caps +-a_3 and, when the radial part of xpos_b - c is longer than 1e-6, the tangent plane n = u, d = u.c + rho, u the unit radial
+ * direction towards the body origin.  D_f = max_v (d_f - n_f . x_v) over ALL vertices of the hull; some D_f <= 0: the pair has no term; otherwise f* is
+ * the first plane of least D_f.  The footprint of f* is the primitive's extent in the directions other than n (box: |a_j.(x - c)| < h_j on the two
+ * other axes; cap: radial distance < rho; tangent plane: |a_3.(x - c)| < h and |(a_3 x u).(x - c)| < rho).  Every footprint vertex behind the plane
+ * counts, however deep, pulled to its own projection on the plane, re-projected at every evaluation; a vertex in two geoms' footprints counts in both.
+ * GRADIENT: J_v^T w_obj (d - n.x_v) n with n held fixed: exact for faces and caps, without the turn of u with the body origin for the tangent plane.
+ * MATRIX: every counted vertex is an isotropic point mass w_obj (a majoriser, as for the floor).  The accept test runs on the true cost.  The fit is
+ * local: a hull far through a thin slab leaves through the nearer face of its deepest extent, which need not be the side it came from.
+ *   markers, in   as kp_sim_fit_points.
+ *   obj_qpos  device [R,35] or NULL: every row is the floor scene.  A row whose placed geom records are not finite (a NaN pose) gets status 1.
+ *   cfg       kp_fit_scene_cfg_default: kp_fit_points_cfg_default's values, w_obj 0 (>= 0 and finite; 0 switches the term off).
+ *   out       kp_fit_points_out with info [R,16]: 0..11 as kp_sim_fit_points; 12: the deepest counted vertex at the result (m); 13: the number of
+ *             counted vertices; 14: the number of pairs with a term (no separating candidate plane); 15: 0.  12..14 are computed whether or not
+ *             w_obj > 0.  A row with status 1 ran no iteration, returns its input and zeros in info 8..14 and pt_err.
+ * With NULL obj_qpos, every object parked, w_obj == 0 or every pair separated, qpos, info 0..11, dq and pt_err are kp_sim_fit_points' bit for bit.
+ * A row's result depends on that row alone.  Enqueued on the handle's stream; nothing else the handle stores is read or written.  Refused (-1)
+ * before the first HIP call: what kp_sim_fit_points refuses, w_obj < 0 or not finite, obj_qpos on a blob without object geoms, a handle whose
+ * threads_per_env is not 64. */
+typedef struct { kp_fit_points_cfg pts; float w_obj; } kp_fit_scene_cfg;
+typedef kp_fit_points_out kp_fit_scene_out;
+void kp_fit_scene_cfg_default(kp_fit_scene_cfg* cfg);
+int kp_sim_fit_scene(kp_sim*, int n_rows, const kp_marker_set* markers, const kp_fit_points_in* in, const float* obj_qpos, const kp_fit_scene_cfg* cfg, const kp_fit_scene_out* out);
+
 /* Contact forces ESTIMATED from kinematics on motion ROWS: the ground reaction a motion would need.  No reference counterpart and no mujoco-py one
  * (deviation 42); it is the support-force estimate of physics-based pose estimation and biomechanics.  kp_sim_inverse_dynamics charges
  * a row the forces of the soft-constraint model, a function of how many millimetres a hull penetrates; this call asks which forces inside the friction

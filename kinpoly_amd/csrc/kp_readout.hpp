@@ -1,7 +1,7 @@
 // kp_readout.hpp -- the kernels beside the control step that are built from its device functions (kp_step_device.hpp): impulse pushes (kp_push.hpp,
 // DESIGN.md section 12), the contact-force read-out (kp_contact_force.hpp, section 14) inverse dynamics on motion rows (kp_inverse_dyn.hpp,
 // section 15), body motion, momentum and energy on motion rows (kp_body_motion.hpp, section 16) and point Jacobians and pose fitting on motion rows
-// (kp_fit_pose.hpp, section 17; kp_fit_points.hpp, section 20) and contact forces estimated from kinematics on motion rows (kp_contact_estimate.hpp, section 18).  They live in their own translation unit (kp_readout.hip): however they specialise the shared device functions, the step kernels' unit
+// (kp_fit_pose.hpp, section 17; kp_fit_points.hpp, section 20; kp_fit_scene.hpp, section 21) and contact forces estimated from kinematics on motion rows (kp_contact_estimate.hpp, section 18).  They live in their own translation unit (kp_readout.hip): however they specialise the shared device functions, the step kernels' unit
 // does not see it, so the step kernels' code cannot move with them.  kp_sim.hip keeps the entry points' argument checks and calls the launchers below.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -95,6 +95,13 @@ struct FitPointsArgs {
     float *qpos, *info, *dq, *pt_err;    // [R, 76], [R, 12], [R, 75] or null, [R, K] or null (the caller's point order)
 };
 
+// kp_sim_fit_scene: kp_sim_fit_points' block, the rows' static geoms as place_static_rows leaves them and the object term's weight
+struct FitSceneArgs : FitPointsArgs {      // info is [R, 16] here
+    const float* geoms;        // [R, D_MAXGEOM, 17] world-frame static geoms of the rows, or null: every row is the floor scene
+    const int* ngeom;          // [R]
+    float w_obj;
+};
+
 // every pointer optional (kp_estimate_out of the C ABI)
 struct EstimateOut {
     float *qfrc_inverse;       // [R, 75] need - qfrc_contact; its root part is the residual
@@ -133,6 +140,8 @@ void launch_point_jacobian(PointJacArgs A, hipStream_t stream);
 void launch_fit_pose(FitPoseArgs A, hipStream_t stream);
 // pose fitting to points at body offsets with a floor term (kp_fit_points.hpp, section 20): on EnvLds; launches of at most 2^24 rows each
 void launch_fit_points(FitPointsArgs A, hipStream_t stream);
+// pose fitting that keeps the hulls out of the rows' static objects (kp_fit_scene.hpp, section 21): on EnvLds; launches of at most 2^24 rows each
+void launch_fit_scene(FitSceneArgs A, hipStream_t stream);
 // contact forces estimated from kinematics (kp_contact_estimate.hpp, section 18): obj as launch_inverse_dynamics; launches of at most 2^24 rows each
 void launch_estimate_contacts(EstimateArgs A, bool obj, hipStream_t stream);
 

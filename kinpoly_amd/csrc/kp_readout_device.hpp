@@ -1,4 +1,4 @@
-// kp_readout_device.hpp -- what the read-out kernels (kp_push.hpp, kp_contact_force.hpp, kp_inverse_dyn.hpp, kp_fit_pose.hpp, kp_fit_points.hpp) share beyond the control step's own device
+// kp_readout_device.hpp -- what the read-out kernels (kp_push.hpp, kp_contact_force.hpp, kp_inverse_dyn.hpp, kp_fit_pose.hpp, kp_fit_points.hpp, kp_fit_scene.hpp) share beyond the control step's own device
 // functions: the env prologue and the projection of forces on the dofs.  Read-out unit only (kp_readout.hip): the step kernels' unit does not see how these
 // specialise the step's functions.  Each helper holds what ALL its users did before it existed, no more: a store one kernel does not need costs the
 // object instantiations scalar registers (profiles/readout_split/tool_benches.md).

@@ -2013,34 +2013,35 @@ void kp_fit_points_cfg_default(kp_fit_points_cfg* c) {
     c->w_floor = 0.f; c->floor_z = 0.f;
 }
 
-int kp_sim_fit_points(kp_sim* s, int n_rows, const kp_marker_set* markers, const kp_fit_points_in* in, const kp_fit_points_cfg* cfg, const kp_fit_points_out* out) {
-    const char* who = "kp_sim_fit_points";
-    kp::FitPointsArgs A{};
-    const int go = rows_begin(who, s, n_rows, false, A, [&] {
-        if (refuse_null(who, {{"markers", markers}, {"in", in}, {"cfg", cfg}, {"out", out}})) return -1;
-        const int K = markers->n_points;
-        if (K < 0 || K > MarkerScratch::MAXK) return fail("kp_sim_fit_points: n_points must be 0 .. " + std::to_string(MarkerScratch::MAXK));
-        if (K > 0 && refuse_null(who, {{"pt_body", markers->pt_body}, {"pt_offset", markers->pt_offset}})) return -1;
-        for (int k = 0; k < K; k++) {
-            if (markers->pt_body[k] < 0 || markers->pt_body[k] >= kp::D_NB) return fail("kp_sim_fit_points: pt_body[" + std::to_string(k) + "] must be 0 .. 23");
-            for (int i = 0; i < 3; i++)
-                if (!std::isfinite(markers->pt_offset[3 * k + i])) return fail("kp_sim_fit_points: pt_offset[" + std::to_string(k) + "] must be finite");
-        }
-        if (refuse_null(who, {{"qpos0", in->qpos0}})) return -1;
-        if (K > 0 && refuse_null(who, {{"pt_tgt", in->pt_tgt}})) return -1;
-        if (K == 0 && !in->tgt_pos) return fail("kp_sim_fit_points: nothing to fit (n_points == 0 and null tgt_pos)");
-        if (!in->q_prior != !in->w_prior) return fail("kp_sim_fit_points: q_prior and w_prior go together (one of them is null)");
-        if (refuse_null(who, {{"out qpos", out->qpos}, {"out info", out->info}})) return -1;
-        const kp_fit_cfg& f = cfg->fit;
-        if (f.n_iters < 0) return fail("kp_sim_fit_points: n_iters < 0");
-        if (refuse_not_positive(who, {{"mu0", f.mu0}, {"mu_min", f.mu_min}, {"mu_max", f.mu_max}, {"mu_up", f.mu_up}, {"mu_down", f.mu_down}}, false)) return -1;      // as kp_sim_fit_pose
-        for (int d = 0; d < kp::D_NV; d++)
-            if (!(f.damp[d] > 0.f)) return fail("kp_sim_fit_points: damp[" + std::to_string(d) + "] must be > 0");
-        if (!(cfg->w_floor >= 0.f) || !std::isfinite(cfg->w_floor)) return fail("kp_sim_fit_points: w_floor must be >= 0 and finite");
-        if (!std::isfinite(cfg->floor_z)) return fail("kp_sim_fit_points: floor_z must be finite");
-        return 0;
-    });
-    if (go <= 0) return go;
+// what kp_sim_fit_points and kp_sim_fit_scene check of the arguments they share: 0, or fail's -1
+static int fit_points_refuse(const char* who, const kp_marker_set* markers, const kp_fit_points_in* in, const kp_fit_points_cfg* cfg, const kp_fit_points_out* out) {
+    const std::string w = std::string(who) + ": ";
+    if (refuse_null(who, {{"markers", markers}, {"in", in}, {"cfg", cfg}, {"out", out}})) return -1;
+    const int K = markers->n_points;
+    if (K < 0 || K > MarkerScratch::MAXK) return fail(w + "n_points must be 0 .. " + std::to_string(MarkerScratch::MAXK));
+    if (K > 0 && refuse_null(who, {{"pt_body", markers->pt_body}, {"pt_offset", markers->pt_offset}})) return -1;
+    for (int k = 0; k < K; k++) {
+        if (markers->pt_body[k] < 0 || markers->pt_body[k] >= kp::D_NB) return fail(w + "pt_body[" + std::to_string(k) + "] must be 0 .. 23");
+        for (int i = 0; i < 3; i++)
+            if (!std::isfinite(markers->pt_offset[3 * k + i])) return fail(w + "pt_offset[" + std::to_string(k) + "] must be finite");
+    }
+    if (refuse_null(who, {{"qpos0", in->qpos0}})) return -1;
+    if (K > 0 && refuse_null(who, {{"pt_tgt", in->pt_tgt}})) return -1;
+    if (K == 0 && !in->tgt_pos) return fail(w + "nothing to fit (n_points == 0 and null tgt_pos)");
+    if (!in->q_prior != !in->w_prior) return fail(w + "q_prior and w_prior go together (one of them is null)");
+    if (refuse_null(who, {{"out qpos", out->qpos}, {"out info", out->info}})) return -1;
+    const kp_fit_cfg& f = cfg->fit;
+    if (f.n_iters < 0) return fail(w + "n_iters < 0");
+    if (refuse_not_positive(who, {{"mu0", f.mu0}, {"mu_min", f.mu_min}, {"mu_max", f.mu_max}, {"mu_up", f.mu_up}, {"mu_down", f.mu_down}}, false)) return -1;      // as kp_sim_fit_pose
+    for (int d = 0; d < kp::D_NV; d++)
+        if (!(f.damp[d] > 0.f)) return fail(w + "damp[" + std::to_string(d) + "] must be > 0");
+    if (!(cfg->w_floor >= 0.f) || !std::isfinite(cfg->w_floor)) return fail(w + "w_floor must be >= 0 and finite");
+    if (!std::isfinite(cfg->floor_z)) return fail(w + "floor_z must be finite");
+    return 0;
+}
+
+// the marker set ordered by body into the handle's scratch, and the argument block of the two kernels filled from the C structs
+static int fit_points_fill(kp_sim* s, kp::FitPointsArgs& A, const kp_marker_set* markers, const kp_fit_points_in* in, const kp_fit_points_cfg* cfg, const kp_fit_points_out* out) {
     // the marker set ordered by body (stable: a body's points keep the caller's order): offsets [K,3] | perm [K] | adr [25]
     const int K = markers->n_points;
     std::vector<uint32_t> tab((size_t)4 * K + 25);
@@ -2074,7 +2075,39 @@ int kp_sim_fit_points(kp_sim* s, int n_rows, const kp_marker_set* markers, const
     for (int d = 0; d < kp::D_NV; d++) A.damp[d] = f.damp[d];
     A.w_floor = cfg->w_floor; A.floor_z = cfg->floor_z;
     A.qpos = out->qpos; A.info = out->info; A.dq = out->dq; A.pt_err = out->pt_err;
+    return 0;
+}
+
+int kp_sim_fit_points(kp_sim* s, int n_rows, const kp_marker_set* markers, const kp_fit_points_in* in, const kp_fit_points_cfg* cfg, const kp_fit_points_out* out) {
+    const char* who = "kp_sim_fit_points";
+    kp::FitPointsArgs A{};
+    const int go = rows_begin(who, s, n_rows, false, A, [&] { return fit_points_refuse(who, markers, in, cfg, out); });
+    if (go <= 0) return go;
+    if (fit_points_fill(s, A, markers, in, cfg, out)) return -1;
     kp::launch_fit_points(A, s->stream);
+    return launched();
+}
+
+void kp_fit_scene_cfg_default(kp_fit_scene_cfg* c) {
+    if (!c) return;
+    kp_fit_points_cfg_default(&c->pts);
+    c->w_obj = 0.f;
+}
+
+int kp_sim_fit_scene(kp_sim* s, int n_rows, const kp_marker_set* markers, const kp_fit_points_in* in, const float* obj_qpos, const kp_fit_scene_cfg* cfg, const kp_fit_scene_out* out) {
+    const char* who = "kp_sim_fit_scene";
+    kp::FitSceneArgs A{};
+    const int go = rows_begin(who, s, n_rows, obj_qpos != nullptr, A, [&] {
+        if (refuse_null(who, {{"cfg", cfg}})) return -1;
+        if (fit_points_refuse(who, markers, in, &cfg->pts, out)) return -1;
+        if (!(cfg->w_obj >= 0.f) || !std::isfinite(cfg->w_obj)) return fail("kp_sim_fit_scene: w_obj must be >= 0 and finite");
+        return 0;
+    });
+    if (go <= 0) return go;
+    if (fit_points_fill(s, A, markers, in, &cfg->pts, out)) return -1;
+    A.w_obj = cfg->w_obj;
+    if (obj_qpos && place_static_rows(s, n_rows, obj_qpos, &A.geoms, &A.ngeom)) return -1;
+    kp::launch_fit_scene(A, s->stream);
     return launched();
 }
 

@@ -35,6 +35,7 @@ class FitConfig:
     clamp_limits: bool = False
     w_floor: float = 0.0          # fit_points only (kp_fit_points_cfg): weight of the hull vertices below floor_z; 0 switches the term off
     floor_z: float = 0.0
+    w_obj: float = 0.0            # fit_scene only (kp_fit_scene_cfg): weight of the hull vertices inside the scene's static objects; needs obj_qpos; 0: off
     _names = ("mu0", "mu_min", "mu_max", "mu_up", "mu_down")
 
     def damp_vector(self) -> np.ndarray:
@@ -58,6 +59,8 @@ class FitConfig:
             raise ValueError(f"FitConfig: w_floor must be >= 0 and finite, got {self.w_floor}")
         if not np.isfinite(float(self.floor_z)):
             raise ValueError(f"FitConfig: floor_z must be finite, got {self.floor_z}")
+        if not (float(self.w_obj) >= 0.0 and np.isfinite(float(self.w_obj))):
+            raise ValueError(f"FitConfig: w_obj must be >= 0 and finite, got {self.w_obj}")
         return self
 
     def native(self):
@@ -81,6 +84,14 @@ class FitConfig:
         c.w_floor, c.floor_z = float(self.w_floor), float(self.floor_z)
         return c
 
+    def native_scene(self):
+        """the KpFitSceneCfg kp_sim_fit_scene takes"""
+        from .sim import KpFitSceneCfg
+        c = KpFitSceneCfg()
+        c.pts = self.native_points()
+        c.w_obj = float(self.w_obj)
+        return c
+
 
 def default_init(tgt_pos: torch.Tensor, std_qpos=None) -> torch.Tensor:
     """the standing pose, translated so that its pelvis (the root body, whose origin is qpos[0:3]) sits at the pelvis target: [..., 76]"""
@@ -90,6 +101,13 @@ def default_init(tgt_pos: torch.Tensor, std_qpos=None) -> torch.Tensor:
     return q
 
 
+def _check_objects(who, obj_qpos, lead):
+    """obj_qpos [..., 35] of a fit with the scene's objects: the rows' leading shape, float32, contiguous"""
+    if tuple(obj_qpos.shape) != tuple(lead) + (35,):
+        raise ValueError(f"{who}: obj_qpos must be {tuple(lead) + (35,)}, got {tuple(obj_qpos.shape)}")
+    return obj_qpos.float().contiguous()
+
+
 def _check_targets(tgt_pos, tgt_quat):
     if tgt_pos.dim() < 2 or tuple(tgt_pos.shape[-2:]) != (NB, 3):
         raise ValueError(f"fit: tgt_pos must be [..., {NB}, 3], got {tuple(tgt_pos.shape)}")
@@ -97,13 +115,20 @@ def _check_targets(tgt_pos, tgt_quat):
         raise ValueError(f"fit: tgt_quat must be {tuple(tgt_pos.shape[:-1]) + (4,)}, got {tuple(tgt_quat.shape)}")
 
 
-def fit_pose(sim, tgt_pos, tgt_quat=None, init=None, w_pos=None, w_rot=None, q_prior=None, w_prior=None, config: FitConfig | None = None, std_qpos=None) -> dict:
+def fit_pose(sim, tgt_pos, tgt_quat=None, init=None, w_pos=None, w_rot=None, q_prior=None, w_prior=None, config: FitConfig | None = None, std_qpos=None,
+             obj_qpos=None) -> dict:
     """One fit per row: device tensors tgt_pos [..., 24, 3], tgt_quat [..., 24, 4] or None, init [..., 76] or None (default_init).  With tgt_quat and
     no w_rot the orientations count with weight 1.  Returns KpSim.fit_pose's dict (qpos, info).  With config.w_floor > 0 the same problem runs with the
-    floor term through KpSim.fit_points (no points, tgt_pos given): info then has 12 columns (FIT_POINTS_INFO)."""
+    floor term through KpSim.fit_points (no points, tgt_pos given): info then has 12 columns (FIT_POINTS_INFO).  With obj_qpos [..., 35] (the rows'
+    object poses) it runs through KpSim.fit_scene with the scene's static objects as obstacles at weight config.w_obj: info has 16 columns
+    (FIT_SCENE_INFO).  Without obj_qpos the call takes the path it took before the argument existed."""
     _check_targets(tgt_pos, tgt_quat)
     floor = float((config or FitConfig()).w_floor) > 0.0
-    cfg = (config or FitConfig()).native_points() if floor else (config or FitConfig()).native()
+    if obj_qpos is not None:
+        obj_qpos = _check_objects("fit_pose", obj_qpos, tgt_pos.shape[:-2])
+        cfg = (config or FitConfig()).native_scene()
+    else:
+        cfg = (config or FitConfig()).native_points() if floor else (config or FitConfig()).native()
     tgt_pos = tgt_pos.float().contiguous()
     if init is None:
         init = default_init(tgt_pos, std_qpos)
@@ -111,16 +136,20 @@ def fit_pose(sim, tgt_pos, tgt_quat=None, init=None, w_pos=None, w_rot=None, q_p
         tgt_quat = tgt_quat.float().contiguous()
         if w_rot is None:
             w_rot = torch.ones(tuple(tgt_pos.shape[:-1]), dtype=torch.float32, device=tgt_pos.device)
+    if obj_qpos is not None:
+        return sim.fit_scene(init.float().contiguous(), np.zeros(0, np.int32), np.zeros((0, 3), np.float32), None, None, tgt_pos, tgt_quat, w_pos, w_rot, q_prior, w_prior,
+                             obj_qpos=obj_qpos, cfg=cfg)
     if floor:
         return sim.fit_points(init.float().contiguous(), np.zeros(0, np.int32), np.zeros((0, 3), np.float32), None, None, tgt_pos, tgt_quat, w_pos, w_rot, q_prior, w_prior, cfg=cfg)
     return sim.fit_pose(init.float().contiguous(), tgt_pos, tgt_quat, w_pos, w_rot, q_prior, w_prior, cfg=cfg)
 
 
-def fit_sequence(sim, tgt_pos, tgt_quat=None, mode: str = "chained", smooth: float = 1e-2, init=None, config: FitConfig | None = None, std_qpos=None) -> dict:
+def fit_sequence(sim, tgt_pos, tgt_quat=None, mode: str = "chained", smooth: float = 1e-2, init=None, config: FitConfig | None = None, std_qpos=None,
+                 obj_qpos=None) -> dict:
     """Tracks tgt_pos [B, T, 24, 3] (tgt_quat [B, T, 24, 4] or None) -> qpos [B, T, 76], info [B, T, 8] (12 with config.w_floor > 0: fit_pose).
     independent: all B T rows in ONE call from one init (init [B, T, 76] or [76]-broadcastable, default default_init per frame).
     chained: frame t of all B tracks in one call, warm-started from the solution at t - 1, with that solution as the hinge prior at weight `smooth`
-    (frame 0: from init [B, 76] or default_init, no prior)."""
+    (frame 0: from init [B, 76] or default_init, no prior).  obj_qpos [B, T, 35] or None: the frames' object poses (fit_pose; info then [B, T, 16])."""
     if mode not in ("chained", "independent"):
         raise ValueError(f"fit_sequence: mode must be 'chained' or 'independent', got {mode!r}")
     if tgt_pos.dim() != 4:
@@ -132,11 +161,15 @@ def fit_sequence(sim, tgt_pos, tgt_quat=None, mode: str = "chained", smooth: flo
     if mode == "independent":
         if init is not None:
             init = init.float().expand(B, T, NQ)
-        return fit_pose(sim, tgt_pos, tgt_quat, init=init, config=config, std_qpos=std_qpos)
+        return fit_pose(sim, tgt_pos, tgt_quat, init=init, config=config, std_qpos=std_qpos, **({} if obj_qpos is None else dict(obj_qpos=obj_qpos)))
+    if obj_qpos is not None:
+        obj_qpos = _check_objects("fit_sequence", obj_qpos, (B, T))
     qs, infos = [], []
     q = init
     for t in range(T):
         prior = {} if t == 0 or smooth == 0.0 else dict(q_prior=q[:, 7:].contiguous(), w_prior=torch.full((B, NU), float(smooth), dtype=torch.float32, device=tgt_pos.device))
+        if obj_qpos is not None:
+            prior = dict(prior, obj_qpos=obj_qpos[:, t].contiguous())
         out = fit_pose(sim, tgt_pos[:, t], None if tgt_quat is None else tgt_quat[:, t], init=q, config=config, std_qpos=std_qpos, **prior)
         q = out["qpos"]
         qs.append(q); infos.append(out["info"])
@@ -217,22 +250,28 @@ def occlusion_weights(tgt, w=None):
 
 
 def fit_points(sim, markers: MarkerSet, tgt, w=None, init=None, tgt_pos=None, tgt_quat=None, w_pos=None, w_rot=None, q_prior=None, w_prior=None,
-               config: FitConfig | None = None, std_qpos=None, want=("qpos", "info")) -> dict:
+               config: FitConfig | None = None, std_qpos=None, want=("qpos", "info"), obj_qpos=None) -> dict:
     """One fit per row to the world targets tgt [..., K, 3] of the marker set (device tensors); w [..., K] or None (ones).  A target with a NaN is an
     occluded marker: its weight becomes 0 here.  init [..., 76] or None: the standing pose, translated so that its pelvis sits at the mean of the
     row's visible targets minus the same mean of the standing pose's markers.  config.w_floor / floor_z switch the floor term on.  Returns
-    KpSim.fit_points' dict."""
+    KpSim.fit_points' dict.  With obj_qpos [..., 35] the call goes through KpSim.fit_scene (static objects as obstacles at config.w_obj; info
+    [..., 16]); without it, through KpSim.fit_points as before."""
     K = len(markers)
     if tgt.dim() < 2 or tuple(tgt.shape[-2:]) != (K, 3):
         raise ValueError(f"fit_points: tgt must be [..., {K}, 3] for this marker set, got {tuple(tgt.shape)}")
     if w is not None and tuple(w.shape) != tuple(tgt.shape[:-1]):
         raise ValueError(f"fit_points: w must be {tuple(tgt.shape[:-1])}, got {tuple(w.shape)}")
-    cfg = (config or FitConfig()).native_points()
+    if obj_qpos is not None:
+        obj_qpos = _check_objects("fit_points", obj_qpos, tgt.shape[:-2])
+    cfg = (config or FitConfig()).native_points() if obj_qpos is None else (config or FitConfig()).native_scene()
     tgt, w = occlusion_weights(tgt.float().contiguous(), w)
     if init is None:
         init = default_init_points(sim, markers, tgt, w, std_qpos)
     if tgt_quat is not None and w_rot is None:
         w_rot = torch.ones(tuple(tgt.shape[:-2]) + (NB,), dtype=torch.float32, device=tgt.device)
+    if obj_qpos is not None:
+        return sim.fit_scene(init.float().contiguous(), markers.body, markers.offset, tgt, w, tgt_pos, tgt_quat, w_pos, w_rot, q_prior, w_prior, obj_qpos=obj_qpos, cfg=cfg,
+                             want=want)
     return sim.fit_points(init.float().contiguous(), markers.body, markers.offset, tgt, w, tgt_pos, tgt_quat, w_pos, w_rot, q_prior, w_prior, cfg=cfg, want=want)
 
 
@@ -254,10 +293,11 @@ def default_init_points(sim, markers: MarkerSet, tgt, w, std_qpos=None) -> torch
     return q
 
 
-def fit_sequence_points(sim, markers: MarkerSet, tgt, w=None, mode: str = "chained", smooth: float = 1e-2, init=None, config: FitConfig | None = None, std_qpos=None) -> dict:
+def fit_sequence_points(sim, markers: MarkerSet, tgt, w=None, mode: str = "chained", smooth: float = 1e-2, init=None, config: FitConfig | None = None, std_qpos=None,
+                        obj_qpos=None) -> dict:
     """Marker tracks tgt [B, T, K, 3] (w [B, T, K] or None; NaN targets are occluded) -> qpos [B, T, 76], info [B, T, 12], pt_err [B, T, K].
     independent / chained as fit_sequence: chained warm-starts frame t from the solution at t - 1 with that solution as the hinge prior at weight
-    `smooth` (frame 0: from init [B, 76] or the default, no prior)."""
+    `smooth` (frame 0: from init [B, 76] or the default, no prior).  obj_qpos [B, T, 35] or None: the frames' object poses (fit_points; info [B, T, 16])."""
     if mode not in ("chained", "independent"):
         raise ValueError(f"fit_sequence_points: mode must be 'chained' or 'independent', got {mode!r}")
     K = len(markers)
@@ -270,11 +310,15 @@ def fit_sequence_points(sim, markers: MarkerSet, tgt, w=None, mode: str = "chain
     if mode == "independent":
         if init is not None:
             init = init.float().expand(B, T, NQ)
-        return fit_points(sim, markers, tgt, w, init=init, config=config, std_qpos=std_qpos, want=want)
+        return fit_points(sim, markers, tgt, w, init=init, config=config, std_qpos=std_qpos, want=want, **({} if obj_qpos is None else dict(obj_qpos=obj_qpos)))
+    if obj_qpos is not None:
+        obj_qpos = _check_objects("fit_sequence_points", obj_qpos, (B, T))
     outs = {k: [] for k in want}
     q = init
     for t in range(T):
         prior = {} if t == 0 or smooth == 0.0 else dict(q_prior=q[:, 7:].contiguous(), w_prior=torch.full((B, NU), float(smooth), dtype=torch.float32, device=tgt.device))
+        if obj_qpos is not None:
+            prior = dict(prior, obj_qpos=obj_qpos[:, t].contiguous())
         out = fit_points(sim, markers, tgt[:, t], None if w is None else w[:, t], init=q, config=config, std_qpos=std_qpos, want=want, **prior)
         q = out["qpos"]
         for k in want:
@@ -302,9 +346,13 @@ def points_report(names, marker_names, pt_err, pt_w, info, n_iters: int) -> dict
 
 
 def penetration_columns(info) -> dict:
-    """the floor figures of info rows [T, 12]: deepest hull vertex below the floor over the take (m), mean of the per-frame depth, frames with any"""
+    """the floor figures of info rows [T, 12]: deepest hull vertex below the floor over the take (m), mean of the per-frame depth, frames with any; with
+    fit_scene's rows [T, 16] the same three for the vertices counted inside static objects (info 12 / 13)"""
     info = np.asarray(info, np.float64)
-    return dict(max_penetration=float(info[:, 10].max()), mean_penetration=float(info[:, 10].mean()), frames_penetrating=int((info[:, 11] > 0).sum()))
+    out = dict(max_penetration=float(info[:, 10].max()), mean_penetration=float(info[:, 10].mean()), frames_penetrating=int((info[:, 11] > 0).sum()))
+    if info.shape[-1] >= 16:                      # fit_scene's rows: the object figures are present
+        out.update(max_obj_penetration=float(info[:, 12].max()), mean_obj_penetration=float(info[:, 12].mean()), frames_in_objects=int((info[:, 13] > 0).sum()))
+    return out
 
 
 def fit_report(sim, names, qpos, tgt_pos, info, n_iters: int) -> dict:

@@ -215,6 +215,21 @@ FIT_POINTS_INFO = {**FIT_INFO, "max_ept": 8, "rms_ept": 9, "max_depth": 10, "n_b
 MAX_POINTS = 1024
 
 
+class KpFitSceneCfg(C.Structure):
+    """mirror of kp_fit_scene_cfg (host side): kp_sim_fit_points' configuration (pts) and the object term's weight"""
+    _fields_ = [("pts", KpFitPointsCfg), ("w_obj", C.c_float)]
+
+    @classmethod
+    def default(cls):
+        c = cls()
+        load_library().kp_fit_scene_cfg_default(C.byref(c))
+        return c
+
+
+# the columns of KpSim.fit_scene's info rows: FIT_POINTS_INFO's, then the object term's figures at the result (15 is a spare zero)
+FIT_SCENE_INFO = {**FIT_POINTS_INFO, "max_obj_depth": 12, "n_obj_verts": 13, "n_obj_pairs": 14}
+
+
 class KpEstimateCfg(C.Structure):
     """mirror of kp_estimate_cfg (host side): the candidates' reach, the weights of the residual force / moment, the multiplier penalty, the friction
     coefficient (0: the model's) and the Newton iterations of kp_sim_estimate_contacts"""
@@ -266,6 +281,8 @@ _SIGNATURES = {
     "kp_sim_fit_pose": (_I, [_V, _I, _V, _V, _V]),      # handle, n_rows, kp_fit_in*, kp_fit_cfg*, kp_fit_out*
     "kp_fit_points_cfg_default": (None, [C.POINTER(KpFitPointsCfg)]),
     "kp_sim_fit_points": (_I, [_V, _I, _V, _V, _V, _V]),      # handle, n_rows, kp_marker_set*, kp_fit_points_in*, kp_fit_points_cfg*, kp_fit_points_out*
+    "kp_fit_scene_cfg_default": (None, [C.POINTER(KpFitSceneCfg)]),
+    "kp_sim_fit_scene": (_I, [_V, _I, _V, _V, _V, _V, _V]),      # handle, n_rows, kp_marker_set*, kp_fit_points_in*, obj_qpos, kp_fit_scene_cfg*, kp_fit_scene_out*
     "kp_estimate_cfg_default": (None, [_V, C.POINTER(KpEstimateCfg)]),
     "kp_sim_estimate_contacts": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]),      # handle, n_rows, qpos, qvel, qacc, obj_qpos, kp_estimate_cfg*, kp_estimate_out*
     "kp_sim_fk": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]), "kp_sim_fk_backward": (_I, [_V, _I, _V, _V, _V, _V, _V]),
@@ -417,6 +434,11 @@ _FIT_OUTPUTS = {"qpos": ((NQ,), torch.float32), "info": ((8,), torch.float32), "
 def fit_points_outputs(K: int) -> dict:
     """outputs of KpSim.fit_points for K points: name -> (trailing shape, dtype), in kp_fit_points_out's order"""
     return {"qpos": ((NQ,), torch.float32), "info": ((12,), torch.float32), "dq": ((NV,), torch.float32), "pt_err": ((int(K),), torch.float32)}
+
+
+def fit_scene_outputs(K: int) -> dict:
+    """outputs of KpSim.fit_scene for K points: fit_points_outputs' with info [16] (FIT_SCENE_INFO)"""
+    return {**fit_points_outputs(K), "info": ((16,), torch.float32)}
 
 
 def marker_arrays(who, pt_body, pt_offset):
@@ -783,6 +805,38 @@ class KpSim:
             ms = KpMarkerSet(K, body.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p))
             _check(self.L.kp_sim_fit_points(self.h, R, C.byref(ms), C.byref(KpFitPointsIn(*ins)), C.byref(cfg), C.byref(_rows_struct(KpFitPointsOut, table, {**need, **out}))),
                    "kp_sim_fit_points")
+        return _rows_view(out, lead)
+
+    def fit_scene(self, qpos0, pt_body, pt_offset, pt_tgt=None, pt_w=None, tgt_pos=None, tgt_quat=None, w_pos=None, w_rot=None, q_prior=None, w_prior=None,
+                  obj_qpos=None, cfg: KpFitSceneCfg | None = None, want=("qpos", "info")) -> dict:
+        """fit_points with the scene's static objects as obstacles (kp_sim_fit_scene): the same inputs, and obj_qpos [..., 35] or None (every row is the
+        floor scene) -- the rows' object poses, placed as for inverse_dynamics (objects farther than 50 m are parked).  cfg: a KpFitSceneCfg (None: its
+        default, the object and the floor term off).  want: names of fit_scene_outputs(K).  Returns fit_points' dict with info [..., 16]
+        (FIT_SCENE_INFO: the deepest counted vertex, the counted vertices and the pairs with a term at the result in 12..14).  Needs a handle on a
+        blob with object geoms when obj_qpos is given.  Nothing the handle stores is read or changed."""
+        body, off = marker_arrays("fit_scene", pt_body, pt_offset)
+        K = body.shape[0]
+        table = fit_scene_outputs(K)
+        want = _rows_want("fit_scene", want, table)
+        if (q_prior is None) != (w_prior is None):
+            raise ValueError("fit_scene: q_prior and w_prior go together")
+        if K == 0 and tgt_pos is None:
+            raise ValueError("fit_scene: nothing to fit (no points and no tgt_pos)")
+        f32 = torch.float32
+        spec = [("qpos0", qpos0, (NQ,), f32, True), ("pt_tgt", pt_tgt, (K, 3), f32, K > 0), ("pt_w", pt_w, (K,), f32, False), ("tgt_pos", tgt_pos, (24, 3), f32, False),
+                ("tgt_quat", tgt_quat, (24, 4), f32, False), ("w_pos", w_pos, (24,), f32, False), ("w_rot", w_rot, (24,), f32, False),
+                ("q_prior", q_prior, (69,), f32, False), ("w_prior", w_prior, (69,), f32, False), ("obj_qpos", obj_qpos, (35,), f32, False)]
+        lead, R, rows = _rows_inputs("fit_scene", spec)
+        ins = _rows_ptrs("fit_scene", spec, rows)
+        cfg = KpFitSceneCfg.default() if cfg is None else cfg
+        if not (cfg.w_obj >= 0.0 and np.isfinite(cfg.w_obj)):
+            raise ValueError("fit_scene: w_obj must be >= 0 and finite")
+        out = _rows_outputs(R, table, want, self.device)
+        if R > 0:
+            need = {k: out[k] if k in out else torch.empty((R, *table[k][0]), dtype=f32, device=self.device) for k in ("qpos", "info")}      # the two the entry point requires
+            ms = KpMarkerSet(K, body.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p))
+            _check(self.L.kp_sim_fit_scene(self.h, R, C.byref(ms), C.byref(KpFitPointsIn(*ins[:9])), ins[9], C.byref(cfg),
+                                           C.byref(_rows_struct(KpFitPointsOut, table, {**need, **out}))), "kp_sim_fit_scene")
         return _rows_view(out, lead)
 
     def fk(self, qpos_rows: torch.Tensor):

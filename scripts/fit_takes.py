@@ -3,12 +3,15 @@
 reference gets qpos from SMPL axis-angles offline (uhc/data_process); this is the way in for marker or key-point tracks.
 
     python scripts/fit_takes.py --tracks in.pkl --out takes.pkl [--mode chained|independent] [--iters N] [--smooth W] [--limits]
-                                [--markers set.json] [--floor W [--floor_z Z]]
+                                [--markers set.json] [--floor W [--floor_z Z]] [--objects W]
 
 in.pkl:  {take: {"wbpos": [T, 24, 3], optional "wbquat": [T, 24, 4], optional "obj_pose"}} (joblib or pickle).
          With --markers set.json (a kinpoly_amd.fit.MarkerSet: names, body, offset): {take: {"markers": [T, K, 3], optional "obj_pose"}}, NaN where a
          marker is occluded.  --floor W (> 0; 0 switches the term off) keeps the hull vertices above floor_z with weight W, with
          either kind of input; the report then gains the penetration columns, and with --markers the per-marker error percentiles.
+         --objects W (> 0) reads each take's "obj_pose" [T, 35] (five object poses, as the take library carries them) and keeps the hull vertices out
+         of those objects, static boxes and cylinders, with weight W (the object blob is loaded); a take without obj_pose has
+         every object parked.  The report gains the object-penetration columns.  Without the flag the code path and the output are the old ones.
 out:     {take: {"qpos": [T, 76], "pose_aa": zeros [T, 72], "trans": zeros [T, 3], (obj_pose as given)}}: the schema AmassSingleDataset reads (of pose_aa
          and trans only the length is read, by its length filter), and next to it fit_report.json (per take: mean / max position error, share of
          accepted steps, failed rows).
@@ -41,8 +44,30 @@ def load_marker_tracks(path, markers):
     return tracks
 
 
-def fit_marker_tracks(sim, tracks: dict, markers, mode="chained", iters=30, smooth=1e-2, limits=False, w_floor=0.0, floor_z=0.0):
-    """fit_tracks for points of a marker set (tracks[take]["markers"] [T, K, 3], NaN: occluded) through fit_sequence_points; the floor term with w_floor > 0"""
+def parked_objects(T):
+    """[T, 35]: every object parked where convert_obj_qpos parks the inactive ones (beyond the 50 m within which an object counts)"""
+    blk = np.zeros((T, 35), np.float32)
+    for i in range(5):
+        blk[:, 7 * i: 7 * i + 3] = [(i + 1) * 100, 100, 0]
+    blk[:, 3::7] = 1.0
+    return blk
+
+
+def object_rows(sim, tracks, names, lens, Tm):
+    """obj_pose of the takes as [B, Tm, 35] device rows, padded with the last frame like the tracks; a take without obj_pose: parked"""
+    rows = []
+    for k, T in zip(names, lens):
+        a = tracks[k].get("obj_pose")
+        a = parked_objects(T) if a is None else np.asarray(a, np.float32)
+        if a.shape != (T, 35):
+            raise ValueError(f"take '{k}': obj_pose must be [{T}, 35], got {a.shape}")
+        rows.append(np.concatenate([a, np.repeat(a[-1:], Tm - T, 0)], 0))
+    return torch.as_tensor(np.stack(rows), device=sim.device)
+
+
+def fit_marker_tracks(sim, tracks: dict, markers, mode="chained", iters=30, smooth=1e-2, limits=False, w_floor=0.0, floor_z=0.0, w_obj=0.0):
+    """fit_tracks for points of a marker set (tracks[take]["markers"] [T, K, 3], NaN: occluded) through fit_sequence_points; the floor term with w_floor > 0,
+    the takes' objects as obstacles with w_obj > 0"""
     from kinpoly_amd import fit
     names = list(tracks)
     K = len(markers)
@@ -50,8 +75,9 @@ def fit_marker_tracks(sim, tracks: dict, markers, mode="chained", iters=30, smoo
     lens = [a.shape[0] for a in arrs]
     Tm = max(lens)
     tgt = torch.as_tensor(np.stack([np.concatenate([a, np.repeat(a[-1:], Tm - a.shape[0], 0)], 0) for a in arrs]), device=sim.device)
-    cfg = fit.FitConfig(n_iters=iters, clamp_limits=limits, w_floor=w_floor, floor_z=floor_z)
-    out = fit.fit_sequence_points(sim, markers, tgt, mode=mode, smooth=smooth, config=cfg)
+    cfg = fit.FitConfig(n_iters=iters, clamp_limits=limits, w_floor=w_floor, floor_z=floor_z, w_obj=w_obj)
+    objs = dict(obj_qpos=object_rows(sim, tracks, names, lens, Tm)) if w_obj > 0.0 else {}
+    out = fit.fit_sequence_points(sim, markers, tgt, mode=mode, smooth=smooth, config=cfg, **objs)
     seen = (~torch.isnan(tgt).any(-1)).float()
     rep = fit.points_report(names, markers.names, out["pt_err"].cpu().numpy(), seen.cpu().numpy(), out["info"].cpu().numpy(), iters)
     qpos = out["qpos"].double().cpu().numpy()
@@ -80,10 +106,11 @@ def load_tracks(path):
     return tracks
 
 
-def fit_tracks(sim, tracks: dict, mode="chained", iters=30, smooth=1e-2, limits=False, w_floor=0.0, floor_z=0.0):
+def fit_tracks(sim, tracks: dict, mode="chained", iters=30, smooth=1e-2, limits=False, w_floor=0.0, floor_z=0.0, w_obj=0.0):
     """(takes in AmassSingleDataset's schema, report).  All takes go through ONE fit_sequence: shorter tracks are padded with their last frame and cut
     again (a padded frame costs a fit and changes nothing before it).  Orientations are used only when every take carries them.  w_floor > 0: the same
-    targets with the floor term (fit.fit_pose routes the call through kp_sim_fit_points); the report then gains the penetration columns."""
+    targets with the floor term (fit.fit_pose routes the call through kp_sim_fit_points); the report then gains the penetration columns.  w_obj > 0:
+    the takes' objects as static obstacles (kp_sim_fit_scene), and the object-penetration columns."""
     from kinpoly_amd import fit
     names = list(tracks)
     lens = [np.asarray(tracks[k]["wbpos"]).reshape(-1, 24, 3).shape[0] for k in names]
@@ -98,8 +125,9 @@ def fit_tracks(sim, tracks: dict, mode="chained", iters=30, smooth=1e-2, limits=
 
     tp = padded("wbpos", 3)
     tq = padded("wbquat", 4) if all(tracks[k].get("wbquat") is not None for k in names) else None
-    cfg = fit.FitConfig(n_iters=iters, clamp_limits=limits, w_floor=w_floor, floor_z=floor_z)
-    out = fit.fit_sequence(sim, tp, tq, mode=mode, smooth=smooth, config=cfg)
+    cfg = fit.FitConfig(n_iters=iters, clamp_limits=limits, w_floor=w_floor, floor_z=floor_z, w_obj=w_obj)
+    objs = dict(obj_qpos=object_rows(sim, tracks, names, lens, Tm)) if w_obj > 0.0 else {}
+    out = fit.fit_sequence(sim, tp, tq, mode=mode, smooth=smooth, config=cfg, **objs)
     rep = fit.fit_report(sim, names, out["qpos"], tp, out["info"], iters)
     qpos = out["qpos"].double().cpu().numpy()
     takes = {}
@@ -122,9 +150,12 @@ def main(argv=None, sim=None):
     ap.add_argument("--markers", default=None, help="a MarkerSet json: the tracks carry 'markers' [T, K, 3] in place of wbpos")
     ap.add_argument("--floor", type=float, default=None, help="weight of the floor term (hull vertices below --floor_z)")
     ap.add_argument("--floor_z", type=float, default=0.0)
+    ap.add_argument("--objects", type=float, default=None, help="weight of the object term (hull vertices inside the objects of each take's obj_pose)")
     a = ap.parse_args(argv)
     if a.floor is not None and not (a.floor >= 0.0 and np.isfinite(a.floor)):
         ap.error("--floor must be >= 0 and finite")
+    if a.objects is not None and not (a.objects > 0.0 and np.isfinite(a.objects)):
+        ap.error("--objects must be > 0 and finite")
     if a.floor is None and a.floor_z != 0.0:
         ap.error("--floor_z needs --floor")
     markers = None
@@ -136,8 +167,15 @@ def main(argv=None, sim=None):
         tracks = load_tracks(a.tracks)
     if sim is None:
         from kinpoly_amd import sim as kpsim
-        sim = kpsim.KpSim(kpsim.KpModel(), 1)
-    if markers is not None:
+        if a.objects:
+            from kinpoly_amd.model_compiler import STEP_KPM
+            sim = kpsim.KpSim(kpsim.KpModel(STEP_KPM), 1)
+        else:
+            sim = kpsim.KpSim(kpsim.KpModel(), 1)
+    if a.objects:
+        fn, extra = (fit_marker_tracks, (markers,)) if markers is not None else (fit_tracks, ())
+        takes, rep = fn(sim, tracks, *extra, a.mode, a.iters, a.smooth, a.limits, a.floor or 0.0, a.floor_z, a.objects)
+    elif markers is not None:
         takes, rep = fit_marker_tracks(sim, tracks, markers, a.mode, a.iters, a.smooth, a.limits, a.floor or 0.0, a.floor_z)
     elif a.floor:                  # positions (and orientations, where every take carries them) with the floor term; --floor 0 is the term switched off
         takes, rep = fit_tracks(sim, tracks, a.mode, a.iters, a.smooth, a.limits, a.floor, a.floor_z)
