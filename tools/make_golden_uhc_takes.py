@@ -63,18 +63,14 @@ FREQ_CASES = {
 }
 
 
-def write_npz():
-    import json
-    import types
+def reference_env(frame_skip=15):
+    """(G, env, o, load): a HumanoidEnv of the reference whose sim.forward() is this repository's fp64 oracle `o` (load(env.data) copies o's bodies in), for
+    the reference's get_expert; env.dt is the reference's property timestep * frame_skip.  tools/make_golden_take_edges.py runs on the same scaffolding."""
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import make_golden as G
-    from uhc.utils.tools import get_expert
-    from uhc.core.reward_function import world_rfc_implicit_reward
-    from uhc.data_loaders.dataset_amass_single import DatasetAMASSSingle
-    from oracle import np_oracle as O
     env = G.make_env(G.him.HumanoidEnv)
-    env.frame_skip = 15
+    env.frame_skip = frame_skip
     env.cur_t, env.start_ind = 0, 0
     o = G.OracleSim()
 
@@ -94,6 +90,17 @@ def write_npz():
     d = G.FakeData(); d.qpos = np.zeros(76); d.qvel = np.zeros(75)
     d.get_body_xipos = lambda name: d.xipos[(["world"] + G.NAMES).index(name)]
     env.data = d
+    return G, env, o, load
+
+
+def write_npz():
+    import json
+    import types
+    G, env, o, load = reference_env()
+    from uhc.utils.tools import get_expert
+    from uhc.core.reward_function import world_rfc_implicit_reward
+    from uhc.data_loaders.dataset_amass_single import DatasetAMASSSingle
+    from oracle import np_oracle as O
     out = {}
     takes = make_takes()
     for k, (name, tk) in enumerate(takes.items()):
