@@ -632,6 +632,39 @@ typedef kp_fit_points_out kp_fit_scene_out;
 void kp_fit_scene_cfg_default(kp_fit_scene_cfg* cfg);
 int kp_sim_fit_scene(kp_sim*, int n_rows, const kp_marker_set* markers, const kp_fit_points_in* in, const float* obj_qpos, const kp_fit_scene_cfg* cfg, const kp_fit_scene_out* out);
 
+/* Pose fitting on ROWS to 2D KEY POINTS seen by CALIBRATED CAMERAS: kp_sim_fit_scene with one more term.  No reference counterpart (INTEGRATION.md,
+ * deviation 45).  Detections in video from one or several cameras need no triangulation first: a point seen by a single camera
+ * counts, and the floor, object and prior terms resolve depth.  Per row
+ *     c(q) = kp_sim_fit_scene's cost + 1/2 sum_c sum_k w_ck |uv_ck - pi_c(p_k)|^2,    p_k = x_b(k) + R_b(k) o_k  (the call's one marker set)
+ * A camera record is 16 floats: R_cw (9, row-major), t (3), fx, fy, cx, cy; cam = R_cw p + t, the camera looks along +z,
+ * pi = (cx + fx cam_x / cam_z, cy + fy cam_y / cam_z) in pixels.  GRADIENT: exact, J_p^T (w J_pi^T (uv - pi)), a force at the point.  MATRIX: the point
+ * counts as an isotropic mass m = w lambda, lambda the largest eigenvalue of the 2 x 2 J_pi J_pi^T in closed form (fx == fy == f: (f / cam_z)^2 (1 + a^2
+ * + b^2), a = cam_x / cam_z, b = cam_y / cam_z): m I >= w J_pi^T J_pi, a majoriser as for the floor and the objects, so the matrix is still a joint-space
+ * inertia.  The accept test runs on the true cost.
+ *   markers, in, obj_qpos   as kp_sim_fit_scene, but in->pt_tgt may be NULL with K > 0: no 3D term (pt_w is not read then, pt_err is zeros).  At least
+ *             one of 3D targets (K > 0 and pt_tgt), tgt_pos and observations (K > 0 and n_cams > 0).
+ *   obs       NULL or n_cams == 0: no image term.  n_cams C 0 .. 8; device arrays cam [camera_rows,C,16] with camera_rows 1 or R, uv [R,C,K,2] in
+ *             the caller's point order, uv_w [R,C,K] or NULL (ones).  An observation with w <= 0 is skipped and its uv is not read into anything: it
+ *             may be NaN (an undetected key point).  A NaN weight, a uv that is not finite under a positive weight or a camera record that is not
+ *             finite gives the row status 1.
+ *   cfg       kp_fit_image_cfg_default: kp_fit_scene_cfg_default's values, z_near 0.05 m (> 0 and finite).  BEHIND THE CAMERA: a weighted
+ *             observation with cam_z < z_near at the start gives the row status 2: it runs no iteration and returns its input.  The same condition in
+ *             a trial pose makes that trial's cost +inf, which the accept rule rejects: the fit never lowers its cost by hiding a point.
+ *   out       qpos [R,76] and info [R,20] required.  info 0..15 as kp_sim_fit_scene (7: status 0, 1 or 2; both costs of a status 2 row are +inf);
+ *             over the weighted observations at the result: 16 the max and 17 the rms reprojection error (pixels), 18 their number, 19 the smallest
+ *             cam_z among them (m; 0 without any).  dq [R,75], pt_err [R,K], uv_err [R,C,K] or NULL: uv_err is the reprojection error in the caller's
+ *             order, 0 for skipped observations.  A row with status 1 or 2 returns zeros in info 8..19, pt_err and uv_err.
+ * With n_cams == 0, NULL obs or every uv_w <= 0, qpos, info 0..15, dq and pt_err are kp_sim_fit_scene's bit for bit.  A row's result depends on that
+ * row alone.  Enqueued on the handle's stream; nothing else the handle stores is read or written.  n_rows == 0 does nothing.  Refused (-1) before the
+ * first HIP call: what kp_sim_fit_scene refuses (pt_tgt may be null), n_cams outside 0 .. 8, camera_rows neither 1 nor R, null cam or uv with
+ * n_cams > 0, z_near not > 0 or not finite, nothing to fit. */
+typedef struct { kp_fit_scene_cfg scene; float z_near; } kp_fit_image_cfg;
+typedef struct { int n_cams, camera_rows; const float *cam, *uv, *uv_w; } kp_fit_image_obs;
+typedef struct { float *qpos, *info, *dq, *pt_err, *uv_err; } kp_fit_image_out;
+void kp_fit_image_cfg_default(kp_fit_image_cfg* cfg);
+int kp_sim_fit_image(kp_sim*, int n_rows, const kp_marker_set* markers, const kp_fit_points_in* in, const float* obj_qpos, const kp_fit_image_obs* obs,
+                     const kp_fit_image_cfg* cfg, const kp_fit_image_out* out);
+
 /* Contact forces ESTIMATED from kinematics on motion ROWS: the ground reaction a motion would need.  No reference counterpart and no mujoco-py one
  * (deviation 42); it is the support-force estimate of physics-based pose estimation and biomechanics.  kp_sim_inverse_dynamics charges
  * a row the forces of the soft-constraint model, a function of how many millimetres a hull penetrates; this call asks which forces inside the friction

@@ -10,6 +10,7 @@
 #include "kp_fit_pose.hpp"
 #include "kp_fit_points.hpp"
 #include "kp_fit_scene.hpp"
+#include "kp_fit_image.hpp"
 #include "kp_contact_estimate.hpp"
 
 namespace kp {
@@ -66,6 +67,8 @@ void launch_fit_pose(FitPoseArgs A, hipStream_t stream) { launch_rows<k_fit_pose
 void launch_fit_points(FitPointsArgs A, hipStream_t stream) { launch_rows<k_fit_points, sizeof(EnvLds)>(A, stream); }
 
 void launch_fit_scene(FitSceneArgs A, hipStream_t stream) { launch_rows<k_fit_scene, sizeof(EnvLds)>(A, stream); }
+
+void launch_fit_image(FitImageArgs A, hipStream_t stream) { launch_rows<k_fit_image, sizeof(EnvLds)>(A, stream); }
 
 void launch_estimate_contacts(EstimateArgs A, bool obj, hipStream_t stream) {
     if (obj) launch_rows<k_estimate_contacts<true>, sizeof(EnvLdsObj)>(A, stream);

@@ -1,7 +1,7 @@
 // kp_readout.hpp -- the kernels beside the control step that are built from its device functions (kp_step_device.hpp): impulse pushes (kp_push.hpp,
 // DESIGN.md section 12), the contact-force read-out (kp_contact_force.hpp, section 14) inverse dynamics on motion rows (kp_inverse_dyn.hpp,
 // section 15), body motion, momentum and energy on motion rows (kp_body_motion.hpp, section 16) and point Jacobians and pose fitting on motion rows
-// (kp_fit_pose.hpp, section 17; kp_fit_points.hpp, section 20; kp_fit_scene.hpp, section 21) and contact forces estimated from kinematics on motion rows (kp_contact_estimate.hpp, section 18).  They live in their own translation unit (kp_readout.hip): however they specialise the shared device functions, the step kernels' unit
+// (kp_fit_pose.hpp, section 17; kp_fit_points.hpp, section 20; kp_fit_scene.hpp, section 21; kp_fit_image.hpp, section 22) and contact forces estimated from kinematics on motion rows (kp_contact_estimate.hpp, section 18).  They live in their own translation unit (kp_readout.hip): however they specialise the shared device functions, the step kernels' unit
 // does not see it, so the step kernels' code cannot move with them.  kp_sim.hip keeps the entry points' argument checks and calls the launchers below.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -102,6 +102,15 @@ struct FitSceneArgs : FitPointsArgs {      // info is [R, 16] here
     float w_obj;
 };
 
+// kp_sim_fit_image: kp_sim_fit_scene's block and the 2D observations of calibrated cameras (kp_fit_image_obs / kp_fit_image_cfg / kp_fit_image_out)
+struct FitImageArgs : FitSceneArgs {      // info is [R, 20] here; pt_adr is a table of zeros when the call has no 3D targets (pt_tgt null)
+    const int32_t* img_adr;    // [25] the marker set's own adr: the points the image walk covers
+    int n_cams, camera_rows;   // C (0..8); 1 or R
+    const float *cam, *uv, *uv_w;        // [camera_rows, C, 16] R_cw (row-major), t, fx, fy, cx, cy; [R, C, K, 2]; [R, C, K] or null (ones)
+    float z_near;
+    float* uv_err;             // [R, C, K] or null (the caller's order)
+};
+
 // every pointer optional (kp_estimate_out of the C ABI)
 struct EstimateOut {
     float *qfrc_inverse;       // [R, 75] need - qfrc_contact; its root part is the residual
@@ -142,6 +151,8 @@ void launch_fit_pose(FitPoseArgs A, hipStream_t stream);
 void launch_fit_points(FitPointsArgs A, hipStream_t stream);
 // pose fitting that keeps the hulls out of the rows' static objects (kp_fit_scene.hpp, section 21): on EnvLds; launches of at most 2^24 rows each
 void launch_fit_scene(FitSceneArgs A, hipStream_t stream);
+// pose fitting to 2D key points seen by calibrated cameras (kp_fit_image.hpp, section 22): on EnvLds; launches of at most 2^24 rows each
+void launch_fit_image(FitImageArgs A, hipStream_t stream);
 // contact forces estimated from kinematics (kp_contact_estimate.hpp, section 18): obj as launch_inverse_dynamics; launches of at most 2^24 rows each
 void launch_estimate_contacts(EstimateArgs A, bool obj, hipStream_t stream);
 

@@ -98,7 +98,7 @@ struct InvDynScratch {    // kp_sim_inverse_dynamics with objects: what the plac
 };
 
 struct MarkerScratch {    // kp_sim_fit_points: the marker set ordered by body as the kernel reads it (offsets [K,3] | perm [K] | adr [25], 4-byte words); allocated once
-    static constexpr int MAXK = 1024, WORDS = 4 * MAXK + 25;
+    static constexpr int MAXK = 1024, ZEROS = 4 * MAXK + 25, WORDS = ZEROS + 25;      // the last 25 words stay zero: the adr of a call without 3D targets (kp_sim_fit_image)
     void* buf = nullptr;
     std::vector<uint32_t> host;       // what buf holds: a call with the same marker set uploads nothing
 };
@@ -2014,7 +2014,8 @@ void kp_fit_points_cfg_default(kp_fit_points_cfg* c) {
 }
 
 // what kp_sim_fit_points and kp_sim_fit_scene check of the arguments they share: 0, or fail's -1
-static int fit_points_refuse(const char* who, const kp_marker_set* markers, const kp_fit_points_in* in, const kp_fit_points_cfg* cfg, const kp_fit_points_out* out) {
+// image: kp_sim_fit_image's rule for what must be present (pt_tgt may be null there; the caller checks the rest)
+static int fit_points_refuse(const char* who, const kp_marker_set* markers, const kp_fit_points_in* in, const kp_fit_points_cfg* cfg, const kp_fit_points_out* out, bool image = false) {
     const std::string w = std::string(who) + ": ";
     if (refuse_null(who, {{"markers", markers}, {"in", in}, {"cfg", cfg}, {"out", out}})) return -1;
     const int K = markers->n_points;
@@ -2026,8 +2027,8 @@ static int fit_points_refuse(const char* who, const kp_marker_set* markers, cons
             if (!std::isfinite(markers->pt_offset[3 * k + i])) return fail(w + "pt_offset[" + std::to_string(k) + "] must be finite");
     }
     if (refuse_null(who, {{"qpos0", in->qpos0}})) return -1;
-    if (K > 0 && refuse_null(who, {{"pt_tgt", in->pt_tgt}})) return -1;
-    if (K == 0 && !in->tgt_pos) return fail(w + "nothing to fit (n_points == 0 and null tgt_pos)");
+    if (!image && K > 0 && refuse_null(who, {{"pt_tgt", in->pt_tgt}})) return -1;
+    if (!image && K == 0 && !in->tgt_pos) return fail(w + "nothing to fit (n_points == 0 and null tgt_pos)");
     if (!in->q_prior != !in->w_prior) return fail(w + "q_prior and w_prior go together (one of them is null)");
     if (refuse_null(who, {{"out qpos", out->qpos}, {"out info", out->info}})) return -1;
     const kp_fit_cfg& f = cfg->fit;
@@ -2058,7 +2059,10 @@ static int fit_points_fill(kp_sim* s, kp::FitPointsArgs& A, const kp_marker_set*
         adr[kp::D_NB] = j;
     }
     MarkerScratch& mk = s->mk;
-    if (!mk.buf) HIP_OK(hipMalloc(&mk.buf, sizeof(uint32_t) * MarkerScratch::WORDS));
+    if (!mk.buf) {
+        HIP_OK(hipMalloc(&mk.buf, sizeof(uint32_t) * MarkerScratch::WORDS));
+        HIP_OK(hipMemset((uint32_t*)mk.buf + MarkerScratch::ZEROS, 0, sizeof(uint32_t) * 25));
+    }
     if (tab != mk.host) {      // another marker set: the kernels of earlier calls may still read the old one
         HIP_OK(hipStreamSynchronize(s->stream));
         mk.host.clear();
@@ -2108,6 +2112,45 @@ int kp_sim_fit_scene(kp_sim* s, int n_rows, const kp_marker_set* markers, const 
     A.w_obj = cfg->w_obj;
     if (obj_qpos && place_static_rows(s, n_rows, obj_qpos, &A.geoms, &A.ngeom)) return -1;
     kp::launch_fit_scene(A, s->stream);
+    return launched();
+}
+
+void kp_fit_image_cfg_default(kp_fit_image_cfg* c) {
+    if (!c) return;
+    kp_fit_scene_cfg_default(&c->scene);
+    c->z_near = 0.05f;
+}
+
+int kp_sim_fit_image(kp_sim* s, int n_rows, const kp_marker_set* markers, const kp_fit_points_in* in, const float* obj_qpos, const kp_fit_image_obs* obs, const kp_fit_image_cfg* cfg,
+                     const kp_fit_image_out* out) {
+    const char* who = "kp_sim_fit_image";
+    kp::FitImageArgs A{};
+    const int C = obs ? obs->n_cams : 0;
+    const int go = rows_begin(who, s, n_rows, obj_qpos != nullptr, A, [&] {
+        if (refuse_null(who, {{"cfg", cfg}, {"out", out}})) return -1;
+        const kp_fit_points_out pout{out->qpos, out->info, out->dq, out->pt_err};
+        if (fit_points_refuse(who, markers, in, &cfg->scene.pts, &pout, true)) return -1;
+        if (!(cfg->scene.w_obj >= 0.f) || !std::isfinite(cfg->scene.w_obj)) return fail("kp_sim_fit_image: w_obj must be >= 0 and finite");
+        if (!(cfg->z_near > 0.f) || !std::isfinite(cfg->z_near)) return fail("kp_sim_fit_image: z_near must be > 0 and finite");
+        if (C < 0 || C > 8) return fail("kp_sim_fit_image: n_cams must be 0 .. 8");
+        if (C > 0 && obs->camera_rows != 1 && obs->camera_rows != n_rows) return fail("kp_sim_fit_image: camera_rows must be 1 or n_rows");
+        if (C > 0 && refuse_null(who, {{"cam", obs->cam}, {"uv", obs->uv}})) return -1;
+        const int K = markers->n_points;
+        if (!(K > 0 && in->pt_tgt) && !in->tgt_pos && !(K > 0 && C > 0)) return fail("kp_sim_fit_image: nothing to fit (no 3D targets, null tgt_pos and no observations)");
+        return 0;
+    });
+    if (go <= 0) return go;
+    const kp_fit_points_out pout{out->qpos, out->info, out->dq, out->pt_err};
+    if (fit_points_fill(s, A, markers, in, &cfg->scene.pts, &pout)) return -1;
+    A.img_adr = A.pt_adr;
+    if (!in->pt_tgt) A.pt_adr = (const int32_t*)s->mk.buf + MarkerScratch::ZEROS;      // no 3D term: the shared walks find no point
+    A.w_obj = cfg->scene.w_obj;
+    A.n_cams = C; A.camera_rows = C > 0 ? obs->camera_rows : 1;
+    A.cam = C > 0 ? obs->cam : nullptr; A.uv = C > 0 ? obs->uv : nullptr; A.uv_w = C > 0 ? obs->uv_w : nullptr;
+    A.z_near = cfg->z_near;
+    A.uv_err = C > 0 ? out->uv_err : nullptr;
+    if (obj_qpos && place_static_rows(s, n_rows, obj_qpos, &A.geoms, &A.ngeom)) return -1;
+    kp::launch_fit_image(A, s->stream);
     return launched();
 }
 

@@ -36,6 +36,7 @@ class FitConfig:
     w_floor: float = 0.0          # fit_points only (kp_fit_points_cfg): weight of the hull vertices below floor_z; 0 switches the term off
     floor_z: float = 0.0
     w_obj: float = 0.0            # fit_scene only (kp_fit_scene_cfg): weight of the hull vertices inside the scene's static objects; needs obj_qpos; 0: off
+    z_near: float = 0.05          # fit_image only (kp_fit_image_cfg): the nearest camera depth (m) a weighted observation may have
     _names = ("mu0", "mu_min", "mu_max", "mu_up", "mu_down")
 
     def damp_vector(self) -> np.ndarray:
@@ -61,6 +62,8 @@ class FitConfig:
             raise ValueError(f"FitConfig: floor_z must be finite, got {self.floor_z}")
         if not (float(self.w_obj) >= 0.0 and np.isfinite(float(self.w_obj))):
             raise ValueError(f"FitConfig: w_obj must be >= 0 and finite, got {self.w_obj}")
+        if not (float(self.z_near) > 0.0 and np.isfinite(float(self.z_near))):
+            raise ValueError(f"FitConfig: z_near must be > 0 and finite, got {self.z_near}")
         return self
 
     def native(self):
@@ -90,6 +93,14 @@ class FitConfig:
         c = KpFitSceneCfg()
         c.pts = self.native_points()
         c.w_obj = float(self.w_obj)
+        return c
+
+    def native_image(self):
+        """the KpFitImageCfg kp_sim_fit_image takes"""
+        from .sim import KpFitImageCfg
+        c = KpFitImageCfg()
+        c.scene = self.native_scene()
+        c.z_near = float(self.z_near)
         return c
 
 
@@ -377,4 +388,178 @@ def report_from_errors(names, err, info, n_iters: int) -> dict:
     for b, k in enumerate(names):
         out[k] = dict(mean_pos_err=float(err[b].mean()), max_pos_err=float(err[b].max()),
                       accepted_share=float(info[b, :, 2].sum() / max(1, n_iters * err.shape[1])), failed_rows=int((info[b, :, 7] != 0).sum()))
+    return out
+
+
+# ---------------------------------------------------------------- 2D key points seen by calibrated cameras
+
+def _quat_matrix(q):
+    w, x, y, z = np.asarray(q, np.float64) / np.linalg.norm(q)
+    return np.array([[w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), w * w - x * x + y * y - z * z, 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z]])
+
+
+@dataclass(eq=False)
+class Pinhole:
+    """A calibrated camera as kp_sim_fit_image reads it: cam = R p + t (R [3, 3] world -> camera, t [3]), looking along +z,
+    pixel = (cx + fx cam_x / cam_z, cy + fy cam_y / cam_z); x to the right, y down, row 0 at the top."""
+    R: np.ndarray
+    t: np.ndarray
+    fx: float
+    fy: float
+    cx: float
+    cy: float
+
+    def __post_init__(self):
+        self.R, self.t = np.asarray(self.R, np.float64).reshape(3, 3), np.asarray(self.t, np.float64).reshape(3)
+        self.fx, self.fy, self.cx, self.cy = float(self.fx), float(self.fy), float(self.cx), float(self.cy)
+
+    def camera_points(self, points):
+        return np.asarray(points, np.float64) @ self.R.T + self.t
+
+    def project(self, points):
+        """pixels [..., 2] of world points [..., 3] (host arrays, fp64); no test for points behind the camera"""
+        c = self.camera_points(points)
+        return np.stack([self.cx + self.fx * c[..., 0] / c[..., 2], self.cy + self.fy * c[..., 1] / c[..., 2]], -1)
+
+    def pack(self) -> np.ndarray:
+        """the 16 floats of a camera record: R (row-major), t, fx, fy, cx, cy"""
+        return np.concatenate([self.R.ravel(), self.t, [self.fx, self.fy, self.cx, self.cy]]).astype(np.float32)
+
+    @classmethod
+    def from_axes(cls, eye, right, down, forward, fovy_deg, width, height):
+        """square pixels from a vertical field of view: fx = fy = H / (2 tan(fovy / 2)), the principal point at the image centre"""
+        R = np.stack([np.asarray(a, np.float64) for a in (right, down, forward)])
+        f = float(height) / (2.0 * np.tan(0.5 * np.radians(float(fovy_deg))))
+        return cls(R, -R @ np.asarray(eye, np.float64), f, f, 0.5 * float(width), 0.5 * float(height))
+
+    @classmethod
+    def from_camera(cls, camera7, width, height):
+        """kp_sim_render's viewer camera: lookat[3], distance, azimuth, elevation, fovy (degrees)"""
+        c = np.asarray(camera7, np.float64).reshape(7)
+        az, el = np.radians(c[4]), np.radians(c[5])
+        f = np.array([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)])
+        r = np.cross(f, [0.0, 0.0, 1.0]); r /= np.linalg.norm(r)
+        u = np.cross(r, f)
+        return cls.from_axes(c[:3] - c[3] * f, r, -u, f, c[6], width, height)
+
+    @classmethod
+    def from_head_camera(cls, camera8, width, height):
+        """kp_sim_render_ego's pose camera: eye[3], quaternion (w, x, y, z; world from camera), fovy (degrees).  Its axes are the head body's
+        (forward = R e_z, up = R e_y, right = -R e_x), so the pinhole's x is -c_x and its y is -c_y of c = R^T (p - eye)."""
+        c = np.asarray(camera8, np.float64).reshape(8)
+        Rc = _quat_matrix(c[3:7])
+        return cls.from_axes(c[:3], -Rc[:, 0], -Rc[:, 1], Rc[:, 2], c[7], width, height)
+
+
+def pack_cameras(cams, device) -> torch.Tensor:
+    """cams as the device tensor fit_image takes: a sequence of Pinhole -> [C, 16]; a tensor [C, 16] or [..., C, 16] passes through"""
+    if isinstance(cams, torch.Tensor):
+        return cams.float().contiguous().to(device)
+    if isinstance(cams, Pinhole):
+        cams = [cams]
+    return torch.as_tensor(np.stack([c.pack() for c in cams]).reshape(-1, 16), dtype=torch.float32, device=device)
+
+
+def detection_weights(uv, uv_w=None):
+    """(uv, weights) as fit_keypoints hands them on: an observation whose uv holds a NaN (an undetected key point) gets weight 0; uv_w None: ones"""
+    seen = ~torch.isnan(uv).any(dim=-1)
+    w = torch.ones(tuple(uv.shape[:-1]), dtype=torch.float32, device=uv.device) if uv_w is None else uv_w.float()
+    return uv, torch.where(seen, w, torch.zeros_like(w)).contiguous()
+
+
+def fit_keypoints(sim, markers: MarkerSet, uv, cams, uv_w=None, tgt=None, w=None, init=None, tgt_pos=None, tgt_quat=None, w_pos=None, w_rot=None, q_prior=None,
+                  w_prior=None, obj_qpos=None, config: FitConfig | None = None, std_qpos=None, want=("qpos", "info")) -> dict:
+    """One fit per row to the pixels uv [..., C, K, 2] at which C calibrated cameras see the marker set's points (device tensors); uv_w [..., C, K] or
+    None (ones; a detector's confidence).  A uv with a NaN, or a weight <= 0, is an undetected key point.  cams: Pinholes, or a tensor [C, 16] (all
+    rows) / [..., C, 16] (per row).  tgt [..., K, 3] / w: optional world targets of the same points (fit_points' term; NaN: occluded); tgt_pos and
+    the others as fit_points.  init [..., 76] or None: fit_points' default when tgt is given, fit_pose's when tgt_pos is, otherwise the standing pose
+    where the fixture has it.  config.w_floor / floor_z, w_obj with obj_qpos [..., 35] and z_near as in FitConfig.  Returns KpSim.fit_image's dict."""
+    K = len(markers)
+    if uv.dim() < 3 or tuple(uv.shape[-2:]) != (K, 2):
+        raise ValueError(f"fit_keypoints: uv must be [..., C, {K}, 2] for this marker set, got {tuple(uv.shape)}")
+    lead, Cn = tuple(uv.shape[:-3]), int(uv.shape[-3])
+    if uv_w is not None and tuple(uv_w.shape) != lead + (Cn, K):
+        raise ValueError(f"fit_keypoints: uv_w must be {lead + (Cn, K)}, got {tuple(uv_w.shape)}")
+    cam = pack_cameras(cams, uv.device)
+    if tuple(cam.shape) not in ((Cn, 16), lead + (Cn, 16)):
+        raise ValueError(f"fit_keypoints: {Cn} cameras in uv, cams {tuple(cam.shape)}")
+    if tgt is not None and tuple(tgt.shape) != lead + (K, 3):
+        raise ValueError(f"fit_keypoints: tgt must be {lead + (K, 3)}, got {tuple(tgt.shape)}")
+    if w is not None and (tgt is None or tuple(w.shape) != lead + (K,)):
+        raise ValueError(f"fit_keypoints: w goes with tgt and must be {lead + (K,)}")
+    if obj_qpos is not None:
+        obj_qpos = _check_objects("fit_keypoints", obj_qpos, lead)
+    cfg = (config or FitConfig()).native_image()
+    uv, uv_w = detection_weights(uv.float().contiguous(), uv_w)
+    if tgt is not None:
+        tgt, w = occlusion_weights(tgt.float().contiguous(), w)
+    if init is None:
+        if tgt is not None:
+            init = default_init_points(sim, markers, tgt, w, std_qpos)
+        elif tgt_pos is not None:
+            init = default_init(tgt_pos.float(), std_qpos)
+        else:
+            std = np.asarray(standing_qpos() if std_qpos is None else std_qpos, np.float64)
+            init = torch.as_tensor(std, dtype=torch.float32, device=uv.device).expand(lead + (NQ,)).clone()
+    if tgt_quat is not None and w_rot is None:
+        w_rot = torch.ones(lead + (NB,), dtype=torch.float32, device=uv.device)
+    return sim.fit_image(init.float().contiguous(), markers.body, markers.offset, cam, uv, uv_w, tgt, w, tgt_pos, tgt_quat, w_pos, w_rot, q_prior, w_prior,
+                         obj_qpos=obj_qpos, cfg=cfg, want=want)
+
+
+def fit_sequence_keypoints(sim, markers: MarkerSet, uv, cams, uv_w=None, tgt=None, w=None, mode: str = "chained", smooth: float = 1e-2, init=None,
+                           config: FitConfig | None = None, std_qpos=None, obj_qpos=None) -> dict:
+    """Key-point tracks uv [B, T, C, K, 2] (uv_w [B, T, C, K] or None; NaN: undetected) -> qpos [B, T, 76], info [B, T, 20], uv_err [B, T, C, K],
+    pt_err [B, T, K].  cams: Pinholes or [C, 16] (fixed cameras), or [B, T, C, 16] (moving ones).  tgt [B, T, K, 3] / w: optional 3D tracks of the
+    same points.  independent / chained as fit_sequence_points: chained warm-starts frame t from the solution at t - 1 with that solution as the
+    hinge prior at weight `smooth` (frame 0: from init [B, 76] or fit_keypoints' default, no prior).  obj_qpos [B, T, 35] or None."""
+    if mode not in ("chained", "independent"):
+        raise ValueError(f"fit_sequence_keypoints: mode must be 'chained' or 'independent', got {mode!r}")
+    K = len(markers)
+    if uv.dim() != 5 or tuple(uv.shape[-2:]) != (K, 2):
+        raise ValueError(f"fit_sequence_keypoints: uv must be [B, T, C, {K}, 2], got {tuple(uv.shape)}")
+    if not float(smooth) >= 0.0:
+        raise ValueError(f"fit_sequence_keypoints: smooth must be >= 0, got {smooth}")
+    B, T = uv.shape[:2]
+    want = ("qpos", "info", "pt_err", "uv_err")
+    cam = pack_cameras(cams, uv.device)
+    if mode == "independent":
+        if init is not None:
+            init = init.float().expand(B, T, NQ)
+        return fit_keypoints(sim, markers, uv, cam, uv_w, tgt, w, init=init, config=config, std_qpos=std_qpos, want=want, obj_qpos=obj_qpos)
+    if obj_qpos is not None:
+        obj_qpos = _check_objects("fit_sequence_keypoints", obj_qpos, (B, T))
+    outs = {k: [] for k in want}
+    q = init
+    at = lambda a, t: None if a is None else a[:, t].contiguous()      # noqa: E731
+    for t in range(T):
+        prior = {} if t == 0 or smooth == 0.0 else dict(q_prior=q[:, 7:].contiguous(), w_prior=torch.full((B, NU), float(smooth), dtype=torch.float32, device=uv.device))
+        out = fit_keypoints(sim, markers, uv[:, t].contiguous(), cam if cam.dim() == 2 else cam[:, t].contiguous(), at(uv_w, t), at(tgt, t), at(w, t), init=q, config=config,
+                            std_qpos=std_qpos, want=want, obj_qpos=at(obj_qpos, t), **prior)
+        q = out["qpos"]
+        for k in want:
+            outs[k].append(out[k])
+    return {k: torch.stack(v, 1) for k, v in outs.items()}
+
+
+def keypoints_report(names, marker_names, uv_err, uv_w, info, n_iters: int) -> dict:
+    """take -> the columns of a key-point fit (host arrays): uv_err [B, T, C, K] in pixels (0 where skipped), uv_w [B, T, C, K] (> 0: the observation
+    counted), info [B, T, 20].  Percentiles of the reprojection error over the counted observations, per take, per camera and per marker; the detected
+    share; rows behind a camera (status 2); accepted share, failed rows and the penetration columns as points_report."""
+    err, w, info = np.asarray(uv_err, np.float64), np.asarray(uv_w, np.float64) > 0, np.asarray(info, np.float64)
+    if len(names) != err.shape[0] or info.shape[:2] != err.shape[:2] or w.shape != err.shape or len(marker_names) != err.shape[3]:
+        raise ValueError(f"keypoints_report: {len(names)} names, {len(marker_names)} markers, errors {err.shape}, weights {w.shape}, info {info.shape}")
+    pct = lambda v: {f"p{p}": (float(np.percentile(v, p)) if v.size else None) for p in (50, 90, 99)}      # noqa: E731
+    out = {}
+    for b, k in enumerate(names):
+        e = err[b][w[b]]
+        out[k] = dict(mean_px_err=float(e.mean()) if e.size else None, max_px_err=float(e.max()) if e.size else None, **{f"px_err_{n}": v for n, v in pct(e).items()},
+                      detected_share=float(w[b].mean()) if w[b].size else None,
+                      per_camera=[pct(err[b, :, c][w[b, :, c]]) for c in range(err.shape[2])],
+                      per_marker={m: pct(err[b, :, :, j][w[b, :, :, j]]) for j, m in enumerate(marker_names)},
+                      min_depth=float(info[b, :, 19][info[b, :, 18] > 0].min()) if (info[b, :, 18] > 0).any() else None,
+                      accepted_share=float(info[b, :, 2].sum() / max(1, n_iters * err.shape[1])), failed_rows=int((info[b, :, 7] == 1).sum()),
+                      rows_behind_camera=int((info[b, :, 7] == 2).sum()), **penetration_columns(info[b]))
     return out

@@ -230,6 +230,33 @@ class KpFitSceneCfg(C.Structure):
 FIT_SCENE_INFO = {**FIT_POINTS_INFO, "max_obj_depth": 12, "n_obj_verts": 13, "n_obj_pairs": 14}
 
 
+class KpFitImageCfg(C.Structure):
+    """mirror of kp_fit_image_cfg (host side): kp_sim_fit_scene's configuration (scene) and the nearest camera depth a weighted observation may have"""
+    _fields_ = [("scene", KpFitSceneCfg), ("z_near", C.c_float)]
+
+    @classmethod
+    def default(cls):
+        c = cls()
+        load_library().kp_fit_image_cfg_default(C.byref(c))
+        return c
+
+
+class KpFitImageObs(C.Structure):
+    """mirror of kp_fit_image_obs: n_cams, camera_rows and the device arrays cam [camera_rows, C, 16], uv [R, C, K, 2], uv_w [R, C, K] (may be NULL)"""
+    _fields_ = [("n_cams", C.c_int), ("camera_rows", C.c_int), ("cam", C.c_void_p), ("uv", C.c_void_p), ("uv_w", C.c_void_p)]
+
+
+class KpFitImageOut(C.Structure):
+    """mirror of kp_fit_image_out: the device rows kp_sim_fit_image fills (dq, pt_err and uv_err may be NULL)"""
+    _fields_ = [(k, C.c_void_p) for k in ("qpos", "info", "dq", "pt_err", "uv_err")]
+
+
+# the columns of KpSim.fit_image's info rows: FIT_SCENE_INFO's (status 2: a weighted observation behind z_near at the start), then the reprojection
+# figures at the result over the weighted observations (pixels; their number; the smallest camera depth)
+FIT_IMAGE_INFO = {**FIT_SCENE_INFO, "max_euv": 16, "rms_euv": 17, "n_uv": 18, "min_depth": 19}
+MAX_CAMS = 8
+
+
 class KpEstimateCfg(C.Structure):
     """mirror of kp_estimate_cfg (host side): the candidates' reach, the weights of the residual force / moment, the multiplier penalty, the friction
     coefficient (0: the model's) and the Newton iterations of kp_sim_estimate_contacts"""
@@ -283,6 +310,9 @@ _SIGNATURES = {
     "kp_sim_fit_points": (_I, [_V, _I, _V, _V, _V, _V]),      # handle, n_rows, kp_marker_set*, kp_fit_points_in*, kp_fit_points_cfg*, kp_fit_points_out*
     "kp_fit_scene_cfg_default": (None, [C.POINTER(KpFitSceneCfg)]),
     "kp_sim_fit_scene": (_I, [_V, _I, _V, _V, _V, _V, _V]),      # handle, n_rows, kp_marker_set*, kp_fit_points_in*, obj_qpos, kp_fit_scene_cfg*, kp_fit_scene_out*
+    "kp_fit_image_cfg_default": (None, [C.POINTER(KpFitImageCfg)]),
+    # handle, n_rows, kp_marker_set*, kp_fit_points_in*, obj_qpos, kp_fit_image_obs*, kp_fit_image_cfg*, kp_fit_image_out*
+    "kp_sim_fit_image": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]),
     "kp_estimate_cfg_default": (None, [_V, C.POINTER(KpEstimateCfg)]),
     "kp_sim_estimate_contacts": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]),      # handle, n_rows, qpos, qvel, qacc, obj_qpos, kp_estimate_cfg*, kp_estimate_out*
     "kp_sim_fk": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]), "kp_sim_fk_backward": (_I, [_V, _I, _V, _V, _V, _V, _V]),
@@ -439,6 +469,11 @@ def fit_points_outputs(K: int) -> dict:
 def fit_scene_outputs(K: int) -> dict:
     """outputs of KpSim.fit_scene for K points: fit_points_outputs' with info [16] (FIT_SCENE_INFO)"""
     return {**fit_points_outputs(K), "info": ((16,), torch.float32)}
+
+
+def fit_image_outputs(K: int, n_cams: int) -> dict:
+    """outputs of KpSim.fit_image for K points and n_cams cameras: fit_scene_outputs' with info [20] (FIT_IMAGE_INFO) and uv_err, in kp_fit_image_out's order"""
+    return {**fit_scene_outputs(K), "info": ((20,), torch.float32), "uv_err": ((int(n_cams), int(K)), torch.float32)}
 
 
 def marker_arrays(who, pt_body, pt_offset):
@@ -837,6 +872,52 @@ class KpSim:
             ms = KpMarkerSet(K, body.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p))
             _check(self.L.kp_sim_fit_scene(self.h, R, C.byref(ms), C.byref(KpFitPointsIn(*ins[:9])), ins[9], C.byref(cfg),
                                            C.byref(_rows_struct(KpFitPointsOut, table, {**need, **out}))), "kp_sim_fit_scene")
+        return _rows_view(out, lead)
+
+    def fit_image(self, qpos0, pt_body, pt_offset, cam=None, uv=None, uv_w=None, pt_tgt=None, pt_w=None, tgt_pos=None, tgt_quat=None, w_pos=None, w_rot=None,
+                  q_prior=None, w_prior=None, obj_qpos=None, cfg: KpFitImageCfg | None = None, want=("qpos", "info")) -> dict:
+        """fit_scene with 2D key points seen by calibrated cameras (kp_sim_fit_image): the same inputs (pt_tgt may be None with K > 0: no 3D term), and
+        cam [C, 16] (one set of cameras for all rows) or [..., C, 16] (one per row), uv [..., C, K, 2] in pixels, uv_w [..., C, K] or None (ones; an
+        observation with w <= 0 is skipped and its uv may be NaN).  C 0 .. 8; a record is R_cw (9, row-major), t, fx, fy, cx, cy (fit.Pinhole.pack).
+        cam None: no image term.  cfg: a KpFitImageCfg (None: its default).  want: names of fit_image_outputs(K, C).  Returns fit_scene's dict with
+        info [..., 20] (FIT_IMAGE_INFO) and uv_err [..., C, K].  Nothing the handle stores is read or changed."""
+        body, off = marker_arrays("fit_image", pt_body, pt_offset)
+        K = body.shape[0]
+        if (cam is None) != (uv is None):
+            raise ValueError("fit_image: cam and uv go together")
+        if cam is not None and (cam.dim() < 2 or cam.shape[-1] != 16):
+            raise ValueError(f"fit_image: cam must be [C, 16] or [..., C, 16], got {tuple(cam.shape)}")
+        Cn = 0 if cam is None else int(cam.shape[-2])
+        if Cn > MAX_CAMS:
+            raise ValueError(f"fit_image: at most {MAX_CAMS} cameras, got {Cn}")
+        table = fit_image_outputs(K, Cn)
+        want = _rows_want("fit_image", want, table)
+        if (q_prior is None) != (w_prior is None):
+            raise ValueError("fit_image: q_prior and w_prior go together")
+        if not (K > 0 and pt_tgt is not None) and tgt_pos is None and not (K > 0 and Cn > 0):
+            raise ValueError("fit_image: nothing to fit (no 3D targets, no tgt_pos and no observations)")
+        f32 = torch.float32
+        shared = cam is not None and cam.dim() == 2
+        spec = [("qpos0", qpos0, (NQ,), f32, True), ("pt_tgt", pt_tgt, (K, 3), f32, False), ("pt_w", pt_w, (K,), f32, False), ("tgt_pos", tgt_pos, (24, 3), f32, False),
+                ("tgt_quat", tgt_quat, (24, 4), f32, False), ("w_pos", w_pos, (24,), f32, False), ("w_rot", w_rot, (24,), f32, False),
+                ("q_prior", q_prior, (69,), f32, False), ("w_prior", w_prior, (69,), f32, False), ("obj_qpos", obj_qpos, (35,), f32, False),
+                ("cam", None if shared else cam, (Cn, 16), f32, False), ("uv", uv, (Cn, K, 2), f32, False), ("uv_w", uv_w, (Cn, K), f32, False)]
+        lead, R, rows = _rows_inputs("fit_image", spec)
+        ins = _rows_ptrs("fit_image", spec, rows)
+        if shared:
+            ins[10] = _dev("fit_image: cam", cam, (Cn, 16), f32)
+        cfg = KpFitImageCfg.default() if cfg is None else cfg
+        if not (cfg.scene.w_obj >= 0.0 and np.isfinite(cfg.scene.w_obj)):
+            raise ValueError("fit_image: w_obj must be >= 0 and finite")
+        if not (cfg.z_near > 0.0 and np.isfinite(cfg.z_near)):
+            raise ValueError("fit_image: z_near must be > 0 and finite")
+        out = _rows_outputs(R, table, want, self.device)
+        if R > 0:
+            need = {k: out[k] if k in out else torch.empty((R, *table[k][0]), dtype=f32, device=self.device) for k in ("qpos", "info")}      # the two the entry point requires
+            ms = KpMarkerSet(K, body.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p))
+            obs = KpFitImageObs(Cn, 1 if shared else R, ins[10], ins[11], ins[12])
+            _check(self.L.kp_sim_fit_image(self.h, R, C.byref(ms), C.byref(KpFitPointsIn(*ins[:9])), ins[9], C.byref(obs), C.byref(cfg),
+                                           C.byref(_rows_struct(KpFitImageOut, table, {**need, **out}))), "kp_sim_fit_image")
         return _rows_view(out, lead)
 
     def fk(self, qpos_rows: torch.Tensor):
